@@ -254,6 +254,30 @@ def measure_ncsnpp(local, dev, prec, vcfg, vsd, mix, src, L, graphs, steps=3, pa
     return rec
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each [B, ...] array as out_dir/<name>.npy in float32.  Past DUMP_BUDGET_BYTES in all, keep the same
+    fixed, seeded subset of batch items in every array and write their indices as <name>_index.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.detach().float()
+        idx = None
+        if total > DUMP_BUDGET_BYTES:
+            per_item = sum(x[0].numel() * 4 + 8 for x in arrays.values())
+            keep = max(1, min(a.shape[0], DUMP_BUDGET_BYTES // per_item))
+            idx = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.cpu().numpy())
+        if idx is not None:
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.numpy().astype(np.float64))
+        log(f"dumped {name} {tuple(a.shape)} float32 to {out_dir}" + ("" if idx is None else " (seeded sample)"))
+
+
 def git_head():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True,
@@ -276,7 +300,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the secondary-precision measurement")
     ap.add_argument("--no-extra", action="store_true", help="skip the C1 latency / long-form side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the separated waveforms) "
+                         "as DIR/<name>.npy, float32, at most 64 MB (a fixed seeded sample of mixtures beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     force_dist = bool(os.environ.get("DITSEP_FORCE_DIST"))     # rehearse the RCCL path with world size 1
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -360,7 +389,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(k):
-            step(w + i, engine)
+            last_out[:] = [step(w + i, engine)]
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -375,10 +404,14 @@ def main():
         return el
 
     rank_times = []
+    last_out = []                                      # what the last timed step returned (the waveforms on rank 0)
 
     elapsed = timed(args.steps, args.warmup)
     value = n_ranks * B * args.steps / elapsed
     log(f"timed region: {elapsed:.3f} s for {args.steps} steps -> {value:.2f} utt/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"wav": last_out[0]})
+    last_out.clear()
     dist_info = None
     if dist is not None:
         # the one data-path collective on its own (waveforms already computed): an upper bound on what a step can expose

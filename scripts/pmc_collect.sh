@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the HBM-traffic counters of one DiT score call, one NCSN++ score call and one decode (separate --pmc passes,
 # no other tracing), into gpurun_out/pmc/<part>_<counter>/ ; summarise with scripts/pmc_summary.py afterwards.
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.." || exit 1
 out=gpurun_out/pmc; mkdir -p $out
 run() {  # name counter
   echo "== $1 $2" >> $out/log.txt

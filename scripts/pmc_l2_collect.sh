@@ -1,7 +1,7 @@
 #!/bin/bash
 # L2 (TCC) hit / miss counts per kernel of one DiT score call at C2 (separate --pmc passes, no other tracing);
 # summarise with scripts/pmc_l2_summary.py
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.." || exit 1
 out=gpurun_out/pmc_l2; mkdir -p $out
 export PART=score SCORE=dit
 for c in TCC_HIT_sum TCC_MISS_sum; do

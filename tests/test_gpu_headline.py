@@ -15,7 +15,6 @@ with the fp32 CPU oracle on identical inputs:
 
 Reference path: src/diffsep_latent.py:471-487 (separate), src/models/diffsep/score_models.py:173-186.
 """
-import os
 
 import pytest
 import torch
@@ -38,9 +37,6 @@ PICK = (0, 31, 63)                           # first, middle and last row panel 
 
 def _log(msg):
     print(msg)
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/headline_parity.log", "a") as fh:
-        fh.write(msg + "\n")
 
 
 @pytest.fixture(scope="module")
