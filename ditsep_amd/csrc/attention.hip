@@ -382,8 +382,7 @@ void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<P, F16, DH>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    static const char* wl = getenv("DSN_ATTN_WL");  // development
-    const int W = wl ? std::max(1, std::min(8, atoi(wl))) : 4;  // measured (1 / 2 / 4 / 8): NCSN++ 944 tokens 7.48 / 7.17 / 7.14 / 7.31 ms per call, DiT 301 tokens 32.5 / 26.5 / 23.4 / 25.0 us
+    const int W = 4;  // measured (1 / 2 / 4 / 8): NCSN++ 944 tokens 7.48 / 7.17 / 7.14 / 7.31 ms per call, DiT 301 tokens 32.5 / 26.5 / 23.4 / 25.0 us
     hipLaunchKernelGGL((attention_long_kernel<P, F16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sml, st, qkv, ps,
                        out, out_ps, S, H, o8s);
     return;
@@ -391,8 +390,7 @@ void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S
   const size_t sm = (size_t)P * nkt * 16 * DH * sizeof(op16_t);
   if (nkt <= 4) {
     // waves per workgroup: each takes one query tile of the same (item, head) and they stage V once
-    static const char* wenv = getenv("DSN_ATTN_W");
-    const int W = wenv ? std::max(1, std::min(4, atoi(wenv))) : 3;  // measured at S = 33 (3 query tiles): 12.9 / 12.6 / 12.3 / 12.5 us for 1..4
+    const int W = 3;  // measured at S = 33 (3 query tiles): 12.9 / 12.6 / 12.3 / 12.5 us for 1..4
     hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 4, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st, qkv,
                        ps, out, out_ps, S, H, o8s);
   } else {
@@ -405,9 +403,7 @@ void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S
     // the query tiles of an (item, head) share workgroups of up to 8 waves: V is staged once per workgroup (it used to be
     // one wave per workgroup for 64-wide heads: at S = 236 every one of the 15 query tiles staged the 30 KB of V
     // again -- 44 -> 23 us per launch at the C5 shape)
-    static const char* wenv16 = getenv("DSN_ATTN_W16");  // development
-    int W = nkt >= 8 ? 8 : (nkt >= 4 ? 4 : 1);
-    if (wenv16) W = std::max(1, std::min(8, atoi(wenv16)));
+    const int W = nkt >= 8 ? 8 : (nkt >= 4 ? 4 : 1);
     hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st,
                        qkv, ps, out, out_ps, S, H, o8s);
   }

@@ -734,17 +734,6 @@ struct dsn_ctx {
     d.act_mod = 1;
     return d;
   }
-  // development: "bm,bn,nst,bk" from the environment overrides the tile heuristic of one call site
-  void dev_tile(GemmDesc& d, const char* var) const {
-    const char* v = getenv(var);
-    int bm, bn, nstg, bk;
-    if (v && P == 1 && sscanf(v, "%d,%d,%d,%d", &bm, &bn, &nstg, &bk) == 4 && d.Cin % bk == 0) {
-      d.cfg_bm = bm;
-      d.cfg_bn = bn;
-      d.cfg_nst = nstg;
-      d.cfg_bk = bk;
-    }
-  }
   void set_act(GemmDesc& d, const ActP& a) {
     d.act = a.kind;
     d.act_a = a.a;
@@ -753,10 +742,9 @@ struct dsn_ctx {
   }
   // split-K factor for a GEMM whose output tile count cannot fill the chip (see dit_forward)
   int pick_ksplit(const GemmDesc& d) const {
-    static const char* env = getenv("DSN_KSPLIT");
     const int nkt = d.taps * (d.Cin / 32);
     const int tiles = cdiv(d.M, 128) * cdiv(d.N, 128);
-    int k = env ? atoi(env) : (400 + tiles / 2) / tiles;
+    int k = (400 + tiles / 2) / tiles;
     k = std::min(k, std::min(8, nkt / 8));
     return std::max(k, 1);
   }
@@ -845,12 +833,10 @@ struct dsn_ctx {
       pr.tag = cur_tag;
       HIPCHK(hipEventRecord(pr.a, st));
     }
-    static const bool use_v1 = getenv("DSN_IGEMM_V1") != nullptr;
     // NCSN++ convs of single mixtures: a handful of 128 x 128 tiles each walking a long K alone -> split-K over enough
     // workgroups for a quarter of the chip, then the slab epilogue (B = 1, T = 16: score call 3.07 -> see DESIGN 5)
-    static const bool no_csplit = getenv("DSN_NO_CONV_SPLIT") != nullptr;
     const long ctiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-    if (!no_csplit && P == 1 && cfg.score_kind == DSN_SCORE_NCSNPP && !skinny && panel_bn == 0 && d.ksplit <= 1 &&
+    if (P == 1 && cfg.score_kind == DSN_SCORE_NCSNPP && !skinny && panel_bn == 0 && d.ksplit <= 1 &&
         d.Cin % 32 == 0 && d.N % 64 == 0 && ctiles <= 32 && d.taps * d.Cin >= 512 && !d.swiglu && !d.rope_cos &&
         (d.out_f32 || d.out_planes) && d.out_off >= 0 && d.tap_dil >= 0 && d.in_stride == 1 &&
         (d.img_w > 0 || (d.taps == 1 && d.in_pad == 0))) {
@@ -879,8 +865,7 @@ struct dsn_ctx {
       return;
     }
     hipError_t e = skinny ? igemm_skinny_launch(d, PL, st)
-                          : (panel_bn > 0 ? igemm_panel_launch(d, PL, panel_bn, st)
-                                          : ((use_v1 && d.ksplit <= 1) ? igemm_launch(d, PL, st) : igemm2_launch(d, PL, st)));
+                          : (panel_bn > 0 ? igemm_panel_launch(d, PL, panel_bn, st) : igemm2_launch(d, PL, st));
     if (profiling) {
       HIPCHK(hipEventRecord(pr.b, st));
       prof.push_back(pr);
@@ -926,8 +911,7 @@ struct dsn_ctx {
 
   // fused ResidualUnit (ru_fused.hip) for the 128-channel layers; `in` and `out` planes must differ
   bool ru_fusable(const ResUnit& r) const {
-    static const bool off = getenv("DSN_NO_FUSED_RU") != nullptr;
-    return !off && r.conv7.taps == 7 && r.conv7.Cin == 128 && r.conv7.N == 128 && r.conv1.taps == 1 &&
+    return r.conv7.taps == 7 && r.conv7.Cin == 128 && r.conv7.N == 128 && r.conv1.taps == 1 &&
            r.conv1.Cin == 128 && r.conv1.N == 128 && r.dil <= 9;
   }
   void run_ru(const ResUnit& r, const op16_t* in, long ps, float* xf, float* out_f32, op16_t* out, const ActP& next,
@@ -1005,7 +989,6 @@ struct dsn_ctx {
     }
   } time_cache;
 
-  static bool use_panel_ok(int D) { return getenv("DSN_NO_PANEL") == nullptr && D % 64 == 0; }
   float* dit_forward(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st) {
     const int n = cfg.n_src, Dl = cfg.latent_dim, D = cfg.dit_embed_dim, H = cfg.dit_heads;
     const int io = n * Dl, din = io + Dl, S = T + 1;
@@ -1031,15 +1014,13 @@ struct dsn_ctx {
     // score call): M = 33: 1.52 ms vs 2.27 ms with the panel kernels; M = 17 (config C1): 1.37 vs 2.02 ms; M = 9:
     // 1.28 vs 2.01 ms; M = 61 (4 sub-tiles): 1.77 vs 2.10 ms; M = 66 (5): 1.72 vs 2.07; M = 99 (7): 2.03 vs 2.08; M = 126 (8): 2.22 vs 2.10.  (The window used to start at 33 rows: below it the launcher picked the 1- / 2-sub-tile
     // instantiations, which run 2.5x slower than the 3-sub-tile one on the same data -- see igemm_skinny_launch.)
-    static const bool no_skinny = getenv("DSN_NO_SKINNY") != nullptr;
-    const char* skm = getenv("DSN_SKINNY_MIN");  // read per call (tests)
-    const char* skx = getenv("DSN_SKINNY_MAX");
-    const int skinny_min = skm ? atoi(skm) : 1, skinny_max = skx ? std::min(atoi(skx), 128) : 80;
-    const bool skinny = !no_skinny && P == 1 && !fp8 && M >= skinny_min && M <= skinny_max && D % 256 == 0;
-    const char* sks = getenv("DSN_SKINNY_KS");  // development: split-K of the skinny N = D GEMMs (default 8)
-    const int skinny_ks = sks ? std::max(1, std::min(atoi(sks), 8)) : 8;
+    const char* skx = getenv("DSN_SKINNY_MAX");  // read per call (tests)
+    const int skinny_max = skx ? std::min(atoi(skx), 128) : 80;
+    const bool skinny = P == 1 && !fp8 && M <= skinny_max && D % 256 == 0;
+    const int skinny_ks = 8;
+    const bool use_panel = D % 64 == 0;  // row-panel kernels
     int fold_rows = 0;
-    if ((fold_ln || fold_ln8) && use_panel_ok(D) && !skinny) {
+    if ((fold_ln || fold_ln8) && use_panel && !skinny) {
       for (int rounds = 1; rounds <= 4 && !fold_rows; ++rounds) {
         const int np = 256 * rounds / std::max(1, cdiv(D, 128));
         if (np >= 1 && cdiv(M, np) <= 80) fold_rows = cdiv(M, np);
@@ -1079,15 +1060,12 @@ struct dsn_ctx {
     // Residual-stream GEMMs (out-proj, FF-out) have N = D only: at M ~ 2k rows that is too few
     // 128x128 tiles to fill 256 CUs, so they run split-K into fp32 slabs and the slab reduction
     // (+ bias + residual) is fused into the LayerNorm that follows.
-    static const bool no_panel = getenv("DSN_NO_PANEL") != nullptr;
-    const bool use_panel = !no_panel && (D % 64 == 0);
     // Short row panels for the three narrower GEMMs in the single-plane modes, sized so that panels x column tiles
     // x split-K is one balanced round of 256 workgroups: at M = 2112 out-proj 16 x 8 x split-K 2 and FF-out
     // 16 x 4 x split-K 4 (132-row panels, 9 sub-tiles) = 256, QKV 21 x 12 (104-row panels, 7 sub-tiles) = 252
     // (sweep: profiles/r01_gemm_sweep_dit_panel132.log).
-    static const bool no_short = getenv("DSN_NO_SHORT_PANEL") != nullptr;
     // (also for small batches: many short panels keep every CU streaming weights -- B = 8: 197 -> 145 ms per step)
-    const bool short_panel = use_panel && !no_short && P == 1;  // split modes: measured, no gain
+    const bool short_panel = use_panel && P == 1;  // split modes: measured, no gain
     // panel height for a GEMM with `wg_per_panel` = column tiles x split-K workgroups per row panel: as many
     // panels as fill whole rounds of 256 CUs
     auto panel_rows_for = [&](int wg_per_panel, int max_rows = 272) {
@@ -1097,14 +1075,12 @@ struct dsn_ctx {
         if (rows <= max_rows) return rows;
       }
     };
-    static const char* qkv_panel_env = getenv("DSN_QKV_PANEL");
-    const int qkv_panel = (use_panel && qkv_panel_env) ? atoi(qkv_panel_env) : (short_panel ? 256 : 0);
+    const int qkv_panel = short_panel ? 256 : 0;
     // Fused to_qkv + attention (single-plane 16-bit modes, 64-wide heads, panels of whole items up to 144 rows -- 240 for
     // one long item, the 2-stage-ring variant): as many items per panel as keep panels x heads at a full round of the
     // chip; small batches (fewer than half a round of workgroups) and the skinny window keep the separate kernels.
-    static const bool no_qa = getenv("DSN_NO_QKV_FUSE") != nullptr;
     int qa_ipp = 0;
-    if (!no_qa && P == 1 && !skinny && D == H * 64 && S <= qkv_attention_max_rows()) {
+    if (P == 1 && !skinny && D == H * 64 && S <= qkv_attention_max_rows()) {
       int ipp = std::min(B, std::max(1, 144 / S));  // several items share a panel only in the 144-row tile
       while (ipp > 1 && cdiv(B, ipp) * H < 256) --ipp;
       if (cdiv(B, ipp) * H >= 128) qa_ipp = ipp;
@@ -1169,10 +1145,7 @@ struct dsn_ctx {
         d.qkv_D = D;
         d.q_scale = 0.125f;
         d.m_fast = 1;
-        if (qkv_panel) {
-          const int np = cdiv(M, 272);
-          d.panel_rows = short_panel ? panel_rows_for(cdiv(3 * D, qkv_panel)) : (cdiv(M, np) + 7) / 8 * 8;
-        }
+        if (qkv_panel) d.panel_rows = panel_rows_for(cdiv(3 * D, qkv_panel));
         if (fp8) {
           d.panel_rows = panel_rows_for(cdiv(3 * D, 256), 208);
           run_fp8(d, st, 256);
@@ -1199,19 +1172,16 @@ struct dsn_ctx {
           d.out_ps = M * D;
           d.stat_out = ST;
           d.stat_np = D / 64;
-          static const bool out_mfast = getenv("DSN_OUT_MFAST") != nullptr;
-          d.m_fast = out_mfast ? 1 : 0;  // an XCD's share walks ACROSS the 8 column tiles of a few row panels: the whole
-                                         // 2 MB weight and 4 panels fit its L2 (m_fast = 1: every XCD re-fetches all of A)
+          d.m_fast = 0;  // an XCD's share walks ACROSS the 8 column tiles of a few row panels: the whole
+                         // 2 MB weight and 4 panels fit its L2 (m_fast = 1: every XCD re-fetches all of A)
           if (fp8) run_fp8(d, st, 128);
           else run(d, st, 128);
           pend_n = 0;
           pend_bias = nullptr;
         } else {
-        static const char* ocfg = getenv("DSN_OUT_CFG");  // "bn,ksplit" (development)
-        int obn = 128, oks = 2;
-        if (ocfg) sscanf(ocfg, "%d,%d", &obn, &oks);
+        const int obn = 128, oks = 2;
         d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? oks : pick_ksplit(d));
-        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, obn) * oks, (fp8 && obn == 256) ? 208 : 272);
+        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, obn) * oks);
         if (d.ksplit > 1) {
           slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
           d.out_f32 = slabs;
@@ -1264,8 +1234,7 @@ struct dsn_ctx {
         }
         if (fp8) {
           // 256-column fp8 tiles up to 17 row sub-tiles (8 waves x 256 registers, branch-free main loop): one round at C2
-          static const char* f8rows = getenv("DSN_FP8_FF1_ROWS");  // development: cap of the panel height (144: round 2)
-          d.panel_rows = panel_rows_for(cdiv(4 * D * 2, 256), f8rows ? atoi(f8rows) : 272);
+          d.panel_rows = panel_rows_for(cdiv(4 * D * 2, 256));
           run_fp8(d, st, 256);
         } else if (skinny) {
           run(d, st, 0, true);
@@ -1276,11 +1245,9 @@ struct dsn_ctx {
       {
         Tag tg(this, "dit.ff_out");
         GemmDesc d = fp8 ? fp8_desc(H8, SH8, L.ff2_8, (int)M) : base_desc(FF, M * 4 * D, L.ff2, 1, (int)M, (int)M);
-        static const char* fcfg = getenv("DSN_FF2_CFG");
-        int fbn = 256, fks = 4;
-        if (fcfg) sscanf(fcfg, "%d,%d", &fbn, &fks);
+        const int fbn = 256, fks = 4;
         d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? fks : pick_ksplit(d));
-        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, fbn) * fks, (fp8 && fbn == 256) ? 208 : 272);
+        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, fbn) * fks, fp8 ? 208 : 272);
         if (d.ksplit > 1) {
           slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
           d.out_f32 = slabs;
@@ -1311,8 +1278,7 @@ struct dsn_ctx {
       d.out_f32 = SC;
       // N = n_src * latent_dim is ONE 128-column tile: 128-row tiles leave B*T/128 (17 at C2) workgroups walking the
       // whole K alone; 64-row panels x 8 waves with a 4-stage ring double the workgroups and the loads in flight
-      static const bool po_tile = getenv("DSN_POUT_TILE") != nullptr;
-      if (use_panel && P == 1 && !po_tile && d.N <= 128 && d.M >= 1024) {
+      if (use_panel && P == 1 && d.N <= 128 && d.M >= 1024) {
         d.panel_rows = 64;
         run(d, st, 128);
       } else {
@@ -1641,13 +1607,9 @@ struct dsn_ctx {
         d.out_planes = pb;
         d.out_ps = o_ps;
         set_act(d, b.ru[0].act0);
-        {
-          // Shallow-K phase GEMMs (the last up-sampling layers: K = 2 x 128 or 2 x 256): while the 256 x 256 kernel
-          // spilled ~200 registers a 3-stage 256 x 128 tile was faster there (8.3 vs 9.2 ms over the 5 layers); with
-          // the lean epilogue the default 256 x 256 x BK 64 tile wins again (6.2 vs 7.3 ms) -- override kept for sweeps
-          if (d.taps * d.Cin <= 512) dev_tile(d, "DSN_CONVT_TILE");
-          if (d.taps * d.Cin > 512) dev_tile(d, "DSN_CONVT_DEEP_TILE");
-        }
+        // Shallow-K phase GEMMs (the last up-sampling layers: K = 2 x 128 or 2 x 256): while the 256 x 256 kernel
+        // spilled ~200 registers a 3-stage 256 x 128 tile was faster there (8.3 vs 9.2 ms over the 5 layers); with
+        // the lean epilogue the default 256 x 256 x BK 64 tile wins again (6.2 vs 7.3 ms)
         run(d, st);
       }
       for (int j = 0; j < 3; ++j) {
@@ -1666,7 +1628,6 @@ struct dsn_ctx {
           d.out_planes = ph;
           d.out_ps = o_ps;
           set_act(d, r.act2);
-          dev_tile(d, "DSN_RU7_TILE");
           run(d, st);
         }
         {
@@ -1676,7 +1637,6 @@ struct dsn_ctx {
           d.out_ps = o_ps;
           if (j < 2) d.out_f32 = xf;
           set_act(d, next);
-          dev_tile(d, "DSN_RU1_TILE");
           run(d, st);
         }
       }

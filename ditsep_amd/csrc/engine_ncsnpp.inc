@@ -264,10 +264,7 @@ float* gn_slot(int B) {
 }
 // ask the GEMM that produces `C` channels per row to accumulate that tensor's GroupNorm statistics
 float* gn_in_epilogue(GemmDesc& d, int C, int B, int HW) {
-  static const bool off = getenv("DSN_NO_GN_FUSE") != nullptr;
-  if (off || HW % 64 != 0 || d.ksplit > 1) return nullptr;
-  const int G = std::min(C / 4, 32);
-  (void)G;
+  if (HW % 64 != 0 || d.ksplit > 1) return nullptr;
   d.gn_stats = gn_slot(B);
   return d.gn_stats;
 }
@@ -281,10 +278,9 @@ void track_output(GemmDesc& d, const View& out, int B, int HW) {
   float* s = gn_in_epilogue(d, out.C, B, HW);
   if (s) ncs_stats_of[{out.f + out.coff, out.C}] = s;
   else ncs_stats_of.erase({out.f + out.coff, out.C});
-  static const bool no_cat = getenv("DSN_NO_GN_CAT") != nullptr;
   if (out.cat && out.C < out.rs) {  // a channel slice of a concat buffer: partials also in the concatenation's layout
     const int bit = out.coff == 0 ? 1 : 2;
-    if (s && !no_cat && out.coff % 4 == 0) {
+    if (s && out.coff % 4 == 0) {
       if (!out.cat->slot) out.cat->slot = gn_slot(B);
       d.gn_stats2 = out.cat->slot;
       d.gn_nq2 = out.cat->nq;
@@ -352,8 +348,7 @@ void ncs_resblock(const NcsnRes& r, const View& x, const View& out, const float*
       f.gnf_eps = 1e-6f;
       f.gnf_silu = 1;
       if (igemm_halo3x3_gnfin_ok(f, PL)) {
-        const int tile = (long)(f.M / 256) * cdiv(f.N, 128) >= 512 ? 256 : 128;
-        f.gnf_sync = gnf_counters(Ho * Wo / tile, (long)B * cdiv(r.cout, 128), st);
+        f.gnf_sync = gnf_counters(Ho * Wo / igemm_halo3x3_tile(f, PL), (long)B * cdiv(r.cout, 128), st);
         f.gnf_err = fin_err_dev;
         d = f;
         gn_done = true;
@@ -373,9 +368,8 @@ void ncs_resblock(const NcsnRes& r, const View& x, const View& out, const float*
   View sc;
   // NIN shortcut (Conv_2, 1x1 over the raw block input): where the halo kernel runs Conv_1 it accumulates the shortcut
   // into the same tile first (GemmDesc::sc_A) -- no launch, no fp32 round trip of Conv_2's output
-  static const bool no_scf = getenv("DSN_NO_SHORTCUT_FUSE") != nullptr;
   bool sc_fused = false;
-  if (r.has_conv2 && !no_scf && P == 1 && r.conv2.taps == 1 && r.conv2.Cin % 32 == 0 && r.conv2.N == r.cout &&
+  if (r.has_conv2 && P == 1 && r.conv2.taps == 1 && r.conv2.Cin % 32 == 0 && r.conv2.N == r.cout &&
       (long)cdiv(rows_o, 128) * cdiv(r.cout, 128) > 32) {
     GemmDesc probe = conv_desc(a1, r.conv1, B, Ho, Wo);
     sc_fused = igemm_halo3x3_eligible(probe, PL);

@@ -135,6 +135,8 @@ hipError_t igemm_slab_epilogue_launch(const GemmDesc& d, int pl, const float* sl
                                       hipStream_t stream);
 // halo-resident 3x3 conv (single-plane modes, W <= 32, H*W % 256 == 0); hipErrorNotSupported when not eligible
 hipError_t igemm_halo3x3_launch(const GemmDesc& d, int pl, hipStream_t stream);
+// row-tile height the halo kernel runs `d` with: 256 (8 waves) or 128 (4 waves); 0 = not eligible
+int igemm_halo3x3_tile(const GemmDesc& d, int pl);
 // can `d` (with gnf_out set) run as a producer-finished GroupNorm conv: halo-kernel eligible and one resident round?
 bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl);
 bool igemm2_gnfin_ok(const GemmDesc& d, int pl);   // the same inside igemm2's 128 x 64 tile (128-pixel images, no hand-off)

@@ -21,12 +21,6 @@
 #ifndef DSN_SETPRIO
 #define DSN_SETPRIO 0
 #endif
-#ifndef DSN_SKINNY_U
-#define DSN_SKINNY_U 4  // k-steps per load batch of the skinny kernel (development: 8 = the whole K share of a wave at K = 1024)
-#endif
-#ifndef DSN_DBG_MODE
-#define DSN_DBG_MODE 0  // development ablation builds: 1 = no in-loop staging, 2 = no MFMAs, 3 = no epilogue (halo kernel)
-#endif
 
 namespace {
 
@@ -79,9 +73,8 @@ __device__ __forceinline__ void seed_acc(const GemmDesc& d, f32x4 (&acc)[NT][MT]
 // same counter, every block's stores wait for the previous block's to complete.
 __device__ __forceinline__ void dsn_touch(const f32x4& v) { asm volatile("" ::"v"(v)); }
 
-// Issue gap between the last MFMAs of a k loop and the epilogue's first VALU writes ("MFMA operand
-// registers reused too early"): hipcc re-uses the A / B fragment registers of the final MFMAs for epilogue state within
-// a few instructions of issuing them; experiment switch DSN_DRAIN_NOPS (0 = off).
+// Issue gap between the last MFMAs of a k loop and the epilogue's first VALU writes: a 4 x `s_nop 15` drain, kept by
+// default.  Its cause is unconfirmed (see DESIGN.md 5 on the B = 64 GroupNorm partials); DSN_DRAIN_NOPS = 0 removes it.
 #ifndef DSN_DRAIN_NOPS
 #define DSN_DRAIN_NOPS 4
 #endif
@@ -113,11 +106,7 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
   const bool f_rope = !(LEAN & LEAN_NO_DIT) && d.rope_cos != nullptr;
   const bool f_qkv = !(LEAN & LEAN_NO_DIT) && d.qkv_D > 0;
   const bool f_swiglu = !(LEAN & LEAN_NO_DIT) && d.swiglu;
-#if DSN_DBG_MODE == 5
-  const bool f_gn = false;
-#else
   const bool f_gn = !(LEAN & LEAN_NO_NCSN) && d.gn_stats != nullptr;
-#endif
   const bool f_bbias = !(LEAN & LEAN_NO_NCSN) && d.bbias != nullptr;
   const bool f_tanh = !(LEAN & LEAN_NO_NCSN) && d.f32_op == DSN_F32_TANH;
   const int nq = (lane >> 4) * 4;
@@ -417,11 +406,7 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = tanhf(v[r]);
           }
-#if DSN_DBG_MODE == 4
-          asm volatile("" ::"v"(o));
-#else
           *reinterpret_cast<f32x4*>(d.out_f32 + off) = o;
-#endif
         }
         if (d.out_planes) {
           f32x4 a = v;
@@ -889,18 +874,9 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
     else
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // everyone's part of tile i landed; everyone finished tile i-1
-#if DSN_DBG_MODE != 1
     if (i + NST - 1 < nkt) issue((i + NST - 1) % NST);
-#endif
 
     const op16_t* base = lds + (i % NST) * STAGE_ELEMS;
-#if DSN_DBG_MODE == 2
-    {
-      op16x8 v = *reinterpret_cast<const op16x8*>(base + a_row_off);
-      asm volatile("" ::"v"(v));
-      continue;
-    }
-#endif
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int coff = ((ks * 4 + fchunk) ^ fsw) * 8;
@@ -1215,10 +1191,8 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
     else
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#if DSN_DBG_MODE != 1
     if (tap == 0 && c + 1 < nchunks) issue_halo(c + 1);
     if (i + NSTW - 1 < nkt) issue_w((i + NSTW - 1) % NSTW);
-#endif
 
     const op16_t* hb = (c & 1) ? hbuf + HBUF : hbuf;
     const op16_t* wb = wring + (i % NSTW) * WBUF;
@@ -1237,26 +1211,15 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
       for (int k = 0; k < 4; ++k)
         if ((mk >> k) & 1u) fa[k] = op16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
-#if DSN_DBG_MODE == 2
-#pragma unroll
-    for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(fa[k]), "v"(fw[k]));
-#else
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
       for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma16<F16>(fw[tn], fa[tm], acc[tn][tm]);
-#endif
     if (++tap == 9) {
       tap = 0;
       ++c;
     }
   }
-#if DSN_DBG_MODE == 3
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb) asm volatile("" ::"v"(acc[a][bb]));
-#else
   epilogue_gen<1, F16, 4, 4, 0, LEAN_NO_DIT | LEAN_SEEDED>(d, acc, m0 + wm * 64, d.M, n0 + wn * 64, lane, 0);
   if (d.gnf_out) {
     // ---- GroupNorm finished here (GemmDesc::gnf_out; the epilogue above stored nothing but this tile's slice partials,
@@ -1348,7 +1311,6 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
       }
     }
   }
-#endif
 }
 
 // ============================================================================
@@ -1784,7 +1746,7 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const GemmDesc d) {
   // 4 waves per workgroup split its K range (more loads in flight per CU: the kernel is one HBM round trip long);
   // their partial tiles are summed through LDS in wave order (deterministic) by wave 0, which runs the epilogue
   constexpr int KW = 4;
-  constexpr int U = MT <= 4 ? DSN_SKINNY_U : 2;  // k-steps of 32 per load batch (registers: U * (MT + 2) fragments)
+  constexpr int U = MT <= 4 ? 4 : 2;  // k-steps of 32 per load batch (registers: U * (MT + 2) fragments)
   __shared__ f32x4 red[KW - 1][2 * MT][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1930,8 +1892,10 @@ static hipError_t launch_halo_t(GemmDesc d, const op16_t* zp, hipStream_t stream
                      stream, d, zp);
   return hipGetLastError();
 }
-// which halo variant runs `d`: 256 (8 waves, 256-row tiles), 128 (4 waves), 0 = not eligible
-static int halo_variant(const GemmDesc& d, int pl) {
+// 128-row images (NCSN++ level 2, 128 workgroups of 4 waves) measured slower than igemm2's 128 x 128 x BK 64 tiles
+// (62 vs 55 us): not eligible.  At least two 256-row workgroups per CU (MI355X: 256 CUs): 8-wave 256-row tiles;
+// fewer (NCSN++ level 1: 256): 128-row tiles of 4 waves, two of them per CU (whole score call 5.48 -> 5.38 ms).
+int igemm_halo3x3_tile(const GemmDesc& d, int pl) {
   if (PL_COUNT(pl) != 1 || d.img_w <= 0 || d.img_w > 32 || d.taps != 9 || d.Cin % 32 != 0 || d.in_stride != 1 ||
       d.ksplit > 1 || d.swiglu || d.rows_per_b % 256 != 0 || d.rows_per_b != d.img_w * d.img_h || d.M % 256 != 0 ||
       d.in_pad != 0)
@@ -1957,19 +1921,17 @@ static int halo_resident_blocks() {
 // GroupNorm finished inside igemm2's 128 x 64 tile (128-pixel images: one workgroup holds the image).  The caller
 // forces that tile (cfg_bm/bn/nst/bk = 128, 64, 3, 64).
 bool igemm2_gnfin_ok(const GemmDesc& d, int pl) {
-  if (getenv("DSN_NO_GN_FIN") != nullptr || getenv("DSN_NO_GN_FIN_L2") != nullptr || PL_COUNT(pl) != 1 || !d.gn_stats || d.rows_per_b != 128 || d.M % 128 != 0 ||
+  if (getenv("DSN_NO_GN_FIN") != nullptr || PL_COUNT(pl) != 1 || !d.gn_stats || d.rows_per_b != 128 || d.M % 128 != 0 ||
       d.N % 64 != 0 || d.N > 1024 || d.Cin % 64 != 0 || d.ksplit > 1 || d.resid || d.out_scale != 1.f || d.swiglu ||
       d.rope_cos || d.qkv_D > 0)
     return false;
   const int G = std::min(d.N / 4, 32), cpg = d.N / G;
   return cpg % 4 == 0 && 64 % cpg == 0;
 }
-bool igemm_halo3x3_eligible(const GemmDesc& d, int pl) {
-  return getenv("DSN_NO_HALO") == nullptr && halo_variant(d, pl) != 0;
-}
+bool igemm_halo3x3_eligible(const GemmDesc& d, int pl) { return igemm_halo3x3_tile(d, pl) != 0; }
 bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl) {
-  const bool off = getenv("DSN_NO_GN_FIN") != nullptr || getenv("DSN_NO_HALO") != nullptr;  // (per call: tests flip it)
-  const int v = halo_variant(d, pl);
+  const bool off = getenv("DSN_NO_GN_FIN") != nullptr;  // (per call: tests flip it)
+  const int v = igemm_halo3x3_tile(d, pl);
   if (off || !v || !d.gn_stats || d.N % 32 != 0 || d.N > 1024 || d.rows_per_b % v != 0 || d.out_scale != 1.f) return false;
   const int G = std::min(d.N / 4, 32), cpg = d.N / G;
   if (cpg % 4 != 0 || 128 % cpg != 0) return false;  // groups made of whole quads, never across a column tile
@@ -1980,30 +1942,21 @@ bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl) {
                  : (PL_F16(pl) ? halo_resident_blocks<1, 128, 1>() : halo_resident_blocks<0, 128, 1>());
   return (long)(d.M / v) * cdiv(d.N, 128) <= c;  // every workgroup resident at once: they wait for each other
 }
-hipError_t igemm_halo3x3_launch(const GemmDesc& din, int pl, hipStream_t stream) {
-  const int planes = PL_COUNT(pl), f16 = PL_F16(pl);
-  const GemmDesc& d = din;
+hipError_t igemm_halo3x3_launch(const GemmDesc& d, int pl, hipStream_t stream) {
+  const int f16 = PL_F16(pl);
   if (d.gnf_out && (!igemm_halo3x3_gnfin_ok(d, pl) || !d.gnf_gamma || !d.gnf_beta || !d.gnf_sync || !d.gnf_err ||
                     d.out_f32 || d.out_planes))
     return hipErrorInvalidValue;
   if (d.sc_A && (!d.sc_W || d.sc_Cin < 32 || d.sc_Cin % 32 != 0 || d.sc_row_elems < d.sc_Cin)) return hipErrorInvalidValue;
-  // 128-row images (NCSN++ level 2, 128 workgroups of 4 waves) measured slower than igemm2's 128 x 128 x BK 64 tiles
-  // (62 vs 55 us): not routed here
-  if (planes != 1 || d.img_w <= 0 || d.img_w > 32 || d.taps != 9 || d.Cin % 32 != 0 || d.in_stride != 1 ||
-      d.ksplit > 1 || d.swiglu || d.rows_per_b % 256 != 0 || d.rows_per_b != d.img_w * d.img_h || d.M % 256 != 0 ||
-      d.in_pad != 0)
-    return hipErrorNotSupported;
+  const int tile = igemm_halo3x3_tile(d, pl);
+  if (!tile) return hipErrorNotSupported;
   const op16_t* zp = zero_page();
   if (!zp) return hipErrorOutOfMemory;
-  const long wgs = (long)(d.M / 256) * cdiv(d.N, 128);
   if (d.sc_A) {
-    if (wgs >= 2 * 256) return f16 ? launch_halo_t<1, 256, 4, 1>(d, zp, stream) : launch_halo_t<0, 256, 4, 1>(d, zp, stream);
+    if (tile == 256) return f16 ? launch_halo_t<1, 256, 4, 1>(d, zp, stream) : launch_halo_t<0, 256, 4, 1>(d, zp, stream);
     return f16 ? launch_halo_t<1, 128, 1, 1>(d, zp, stream) : launch_halo_t<0, 128, 1, 1>(d, zp, stream);
   }
-  if (wgs >= 2 * 256)  // MI355X: 256 CUs
-    return f16 ? launch_halo_t<1, 256, 4>(d, zp, stream) : launch_halo_t<0, 256, 4>(d, zp, stream);
-  // fewer than two 256-row workgroups per CU (NCSN++ level 1: 256): 128-row tiles of 4 waves, two of them per CU
-  // (whole score call 5.48 -> 5.38 ms)
+  if (tile == 256) return f16 ? launch_halo_t<1, 256, 4>(d, zp, stream) : launch_halo_t<0, 256, 4>(d, zp, stream);
   return f16 ? launch_halo_t<1, 128, 1>(d, zp, stream) : launch_halo_t<0, 128, 1>(d, zp, stream);
 }
 
@@ -2072,7 +2025,7 @@ hipError_t igemm2_launch(const GemmDesc& d, int pl, hipStream_t stream) {
   // The kernel is L2->LDS bound and, at the DiT's M ~ 2k rows, wave-quantisation bound: take the
   // biggest tile whose grid still fills 256 CUs.
   if (d.cfg_bm > 0) return igemm2_launch_cfg(d, pl, d.cfg_bm, d.cfg_bn, d.cfg_nst, d.cfg_bk, stream);
-  if (d.img_w > 0 && getenv("DSN_NO_HALO") == nullptr) {  // 3x3 convs: halo-resident kernel where it applies
+  if (d.img_w > 0) {  // 3x3 convs: halo-resident kernel where it applies
     const hipError_t e = igemm_halo3x3_launch(d, pl, stream);
     if (e != hipErrorNotSupported) return e;
   }
@@ -2099,8 +2052,7 @@ hipError_t igemm2_launch(const GemmDesc& d, int pl, hipStream_t stream) {
     } else if (k64) {                                    // (NCSN++ level 2: M = 8192)
       bk = 64;
       // 128 x 128 tiles would leave half the chip idle (64 x 2 workgroups): 128 x 64 tiles of four 64 x 32 waves
-      static const bool no_n64 = getenv("DSN_NO_N64_TILE") != nullptr;
-      if (!no_n64 && d.ksplit <= 1 && tiles(128, 128) <= 160 && d.N % 64 == 0) bn = 64;
+      if (d.ksplit <= 1 && tiles(128, 128) <= 160 && d.N % 64 == 0) bn = 64;
     }
   } else if (d.M >= 4096 && d.N >= 4096) {   // ConvTranspose phase GEMMs
     bm = bn = 256;
@@ -2208,8 +2160,7 @@ hipError_t igemm_skinny_launch(const GemmDesc& din, int pl, hipStream_t stream) 
   // every M <= 48 runs the 3-sub-tile instantiation (rows beyond M are clamped re-reads, masked in the epilogue): the
   // 1- and 2-sub-tile instantiations of the same source measured 2.5x SLOWER (M = 17: FF-in 35.7 vs 12.4 us), which
   // is what had made the skinny path look like a loss below 33 rows
-  int mt = std::max((d.M + 15) / 16, 3);
-  if (const char* f = getenv("DSN_SKINNY_MT")) mt = std::max(mt, atoi(f));  // development
+  const int mt = std::max((d.M + 15) / 16, 3);
 #define SK(MT_)                                                                                     \
   if (mt == MT_) {                                                                                  \
     if (PL_F16(pl)) hipLaunchKernelGGL((igemm_skinny_kernel<1, MT_>), dim3(grid), dim3(256), 0, stream, d); \

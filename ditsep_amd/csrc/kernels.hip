@@ -1029,8 +1029,7 @@ void launch_residual_norm(float* x, const float* slabs, int nslab, long slab_str
     case 7: RN_LAUNCH(MV, 7, BT_); break;                                                  \
     default: RN_LAUNCH(MV, 8, BT_); break;  /* pick_ksplit caps the split at 8 */          \
   }
-  static const bool no_rowk = getenv("DSN_NO_LN_ROWK") != nullptr;
-  if (!no_rowk && D == 4 * TPB && rows > 256 && nslab <= 4) {  // bandwidth-bound: a row per workgroup, everything in flight
+  if (D == 4 * TPB && rows > 256 && nslab <= 4) {  // bandwidth-bound: a row per workgroup, everything in flight
 #define RNR(NS_)                                                                                                     \
   hipLaunchKernelGGL((residual_norm_row_kernel<NS_>), dim3(rows), dim3(TPB), 0, st, x, slabs, slab_stride, bias, gamma, \
                      beta, out, ps, planes, D, eps, do_norm, o8s)

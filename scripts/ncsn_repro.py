@@ -1,7 +1,7 @@
 """Development: localise run-to-run differences of the NCSN++ score call.  Runs the same call REPS times and compares
 the persistent workspace tensors (skip / concat buffers, middle, up-path outputs, pyramid heads, score) between
-runs, in forward order; prints the first tensors that differ.  Environment: B, T, PREC, REPS + the engine's DSN_*
-switches (DSN_NO_HALO, DSN_NO_GN_FUSE, ...)."""
+runs, in forward order; prints the first tensors that differ.  Environment: B, T, PREC, REPS, and DSN_NO_GN_FIN
+(GroupNorm_1 as a separate statistics + apply pass)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
-"""Development check: fp16 decode with the fused ResidualUnit v2 / v1 / unfused path on identical input
-(each variant in its own process: the switches are read once), compared against the bf16x3 strict mode."""
+"""Development check: fp16 decode with the fused ResidualUnit v2 / v1 kernels on identical input (each variant in
+its own process), compared against the bf16x3 strict mode."""
 import os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = "/tmp/ru_variant_%s.pt"
@@ -17,9 +17,7 @@ if len(sys.argv) > 1:
     sys.exit(0)
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-runs = {"x3": ({}, 2), "v2": ({}, 3), "v1": ({"DSN_RU_V1": "1"}, 3), "unfused": ({"DSN_NO_FUSED_RU": "1"}, 3)}
-if os.path.exists(os.path.join(ROOT, "ditsep_amd", "libditsep_dbg.so")):
-    runs["v2safe"] = ({"DSN_LIB": os.path.join(ROOT, "ditsep_amd", "libditsep_dbg.so")}, 3)
+runs = {"x3": ({}, 2), "v2": ({}, 3), "v1": ({"DSN_RU_V1": "1"}, 3)}
 for tag, (env, prec) in runs.items():
     subprocess.run([sys.executable, __file__, tag, str(prec)], env={**os.environ, **env}, check=True)
 ref = torch.load(OUT % "x3").double()
