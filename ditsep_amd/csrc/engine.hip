@@ -768,7 +768,9 @@ struct dsn_ctx {
            "(M=%d N=%d Cin=%d taps=%d rows_per_b=%d)", what, lo_bytes, hi_bytes, (long)(b0 - q), (long)(b0 + size - q),
            d.M, d.N, d.Cin, d.taps, d.rows_per_b);
   }
-  void audit_desc(const GemmDesc& d) const {
+  // engine_gn_slots: GroupNorm partials go to the engine's statistics slots (the test hook passes caller-owned buffers,
+  // audited by their allocation alone)
+  void audit_desc(const GemmDesc& d, bool engine_gn_slots = true) const {
     if (d.a_scale) return;  // fp8 descriptors address bytes pairwise: audited by their launcher's shape checks
     const long nb = cdiv(d.M, d.rows_per_b), rows_last = d.M - (nb - 1) * (long)d.rows_per_b;
     const long rows_max = nb > 1 ? d.rows_per_b : rows_last;
@@ -801,11 +803,11 @@ struct dsn_ctx {
         fail(DSN_EINVAL, "audit: GroupNorm partials need whole 64-row slices (rows_per_b=%d M=%d N=%d ksplit=%d)",
              d.rows_per_b, d.M, d.N, d.ksplit);
       audit_span("gn_stats", d.gn_stats, 0, nb * (d.rows_per_b / 64) * (long)(d.N / 4) * 2 * e32, d);
-      if (nb * (d.rows_per_b / 64) * (long)(d.N / 4) * 2 > ncs_slot_floats)
+      if (engine_gn_slots && nb * (d.rows_per_b / 64) * (long)(d.N / 4) * 2 > ncs_slot_floats)
         fail(DSN_EINVAL, "audit: GroupNorm partials overflow their statistics slot");
       if (d.gn_stats2) {
         if (d.gn_qoff2 < 0 || d.gn_qoff2 + d.N / 4 > d.gn_nq2 ||
-            nb * (d.rows_per_b / 64) * (long)d.gn_nq2 * 2 > ncs_slot_floats)
+            (engine_gn_slots && nb * (d.rows_per_b / 64) * (long)d.gn_nq2 * 2 > ncs_slot_floats))
           fail(DSN_EINVAL, "audit: concat GroupNorm partials outside their slot (nq2=%d qoff2=%d N=%d)", d.gn_nq2,
                d.gn_qoff2, d.N);
         audit_span("gn_stats2", d.gn_stats2, 0, nb * (d.rows_per_b / 64) * (long)d.gn_nq2 * 2 * e32, d);
@@ -818,6 +820,11 @@ struct dsn_ctx {
     if (d.rope_cos) {
       audit_span("rope_cos", d.rope_cos, 0, (long)d.rope_S * 32 * e32, d);
       audit_span("rope_sin", d.rope_sin, 0, (long)d.rope_S * 32 * e32, d);
+    }
+    if (d.sc_A) {  // 1x1 shortcut of the halo conv (single-plane modes)
+      audit_span("sc_A", d.sc_A, 0, ((nb - 1) * d.sc_bstride + (rows_max - 1) * (long)d.sc_row_elems + d.sc_Cin) * e16, d);
+      audit_span("sc_W", d.sc_W, 0, (long)d.N * d.sc_Cin * e16, d);
+      audit_span("sc_bias", d.sc_bias, 0, (long)d.N * e32, d);
     }
     if (d.img_w > 0 && (d.rows_per_b != d.img_w * d.img_h || d.taps != 9))
       fail(DSN_EINVAL, "audit: 2-D conv descriptor with rows_per_b != H*W");
@@ -2520,6 +2527,132 @@ int dsn_test_igemm(dsn_ctx* ctx, const float* a, const float* w, float* out, int
       if (e != hipSuccess) fail(DSN_EHIP, "panel launch: %s", hipGetErrorString(e));
     } else {
       ctx->run(d, st);
+    }
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// Test hook: one chosen kernel of the implicit-GEMM family on a caller-built descriptor (include/ditsep_hip.h).
+int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream) {
+  return guarded(ctx, [&] {
+    hipStream_t st = (hipStream_t)stream;
+    const int P = ctx->P, PL = ctx->PL;
+    if (!t || !t->a || !t->w || t->a_numel % 4 != 0) fail(DSN_EINVAL, "test_gemm: operands missing or a_numel %% 4 != 0");
+    const long wn = (long)t->N * t->taps * t->Cin;
+    op16_t* ap = ctx->wsbuf<op16_t>("tg_a", t->a_numel * P);
+    op16_t* wp = ctx->wsbuf<op16_t>("tg_w", wn * P);
+    launch_to_planes(t->a, ap, t->a_numel, PL, t->a_numel, st);
+    launch_to_planes(t->w, wp, wn, PL, wn, st);
+    Packed pk;
+    pk.w = wp;
+    pk.ps = wn;
+    pk.N = t->N;
+    pk.Cin = t->Cin;
+    pk.taps = t->taps;
+    pk.K = t->taps * t->Cin;
+    pk.bias = const_cast<float*>(t->bias);
+    pk.bias_mod = t->bias ? (t->bias_mod > 0 ? t->bias_mod : t->N) : 1;
+    GemmDesc d = ctx->base_desc(ap + t->a_off, t->a_numel, pk, t->B, t->rows_per_b, t->Lin);
+    if (t->M > 0) d.M = t->M;
+    d.in_stride = t->in_stride;
+    d.tap_dil = t->tap_dil;
+    d.in_pad = t->in_pad;
+    if (t->in_row_elems > 0) d.in_row_elems = t->in_row_elems;
+    d.in_bstride = t->in_bstride > 0 ? t->in_bstride : (long)t->Lin * d.in_row_elems;
+    d.img_h = t->img_h;
+    d.img_w = t->img_w;
+    const int n_out = t->swiglu ? t->N / 2 : t->N;
+    d.out_row_elems = t->out_row_elems > 0 ? t->out_row_elems : n_out;
+    d.out_bstride = t->out_bstride > 0 ? t->out_bstride : (long)t->rows_per_b * d.out_row_elems;
+    d.out_off = t->out_off;
+    d.out_limit = t->out_limit > 0 ? t->out_limit : d.out_bstride;
+    d.bbias = t->bbias;
+    d.bbias_stride = t->bbias_stride > 0 ? t->bbias_stride : t->N;
+    d.resid = t->resid;
+    d.resid_row_elems = t->resid_row_elems > 0 ? t->resid_row_elems : d.out_row_elems;
+    d.resid_bstride = t->resid_bstride > 0 ? t->resid_bstride : (long)t->rows_per_b * d.resid_row_elems;
+    d.resid_off = t->resid_off;
+    d.out_scale = t->out_scale != 0.f ? t->out_scale : 1.f;
+    d.f32_op = t->f32_op;
+    d.act = t->act;
+    d.act_a = t->act_a;
+    d.act_b = t->act_b;
+    d.act_mod = t->act_mod > 0 ? t->act_mod : t->N;
+    d.swiglu = t->swiglu;
+    d.gn_stats = t->gn_stats;
+    d.gn_stats2 = t->gn_stats2;
+    d.gn_nq2 = t->gn_nq2;
+    d.gn_qoff2 = t->gn_qoff2;
+    d.out_f32 = t->out_f32;
+    d.out_planes = reinterpret_cast<op16_t*>(t->out_planes);
+    d.out_ps = t->out_ps;
+    if (t->sc_a) {
+      if (!t->sc_w || t->sc_a_numel % 4 != 0) fail(DSN_EINVAL, "test_gemm: shortcut weight missing or sc_a_numel %% 4 != 0");
+      const long sw = (long)t->N * t->sc_Cin;
+      op16_t* sap = ctx->wsbuf<op16_t>("tg_sa", t->sc_a_numel * P);
+      op16_t* swp = ctx->wsbuf<op16_t>("tg_sw", sw * P);
+      launch_to_planes(t->sc_a, sap, t->sc_a_numel, PL, t->sc_a_numel, st);
+      launch_to_planes(t->sc_w, swp, sw, PL, sw, st);
+      d.sc_A = sap;
+      d.sc_W = swp;
+      d.sc_bias = t->sc_bias;
+      d.sc_Cin = t->sc_Cin;
+      d.sc_row_elems = t->sc_row_elems > 0 ? t->sc_row_elems : t->sc_Cin;
+      d.sc_bstride = (long)t->rows_per_b * d.sc_row_elems;
+    }
+    static const bool audit = getenv("DSN_AUDIT") != nullptr;
+    auto check = [&](hipError_t e, const char* what) {
+      if (e != hipSuccess) fail(DSN_EHIP, "test_gemm: %s refused or failed: %s (M=%d N=%d Cin=%d taps=%d)", what,
+                                hipGetErrorString(e), d.M, d.N, d.Cin, d.taps);
+    };
+    switch (t->kernel) {
+      case DSN_TG_AUTO:
+        ctx->run(d, st);  // (audits when DSN_AUDIT is set)
+        break;
+      case DSN_TG_TILE:
+        if (audit) ctx->audit_desc(d, false);
+        check(igemm2_launch_cfg(d, PL, t->bm, t->bn, t->nst, t->bk, st), "igemm2 tile");
+        break;
+      case DSN_TG_V1:
+        if (audit) ctx->audit_desc(d, false);
+        check(igemm_launch(d, PL, st), "igemm v1");
+        break;
+      case DSN_TG_PANEL:
+        d.panel_rows = t->panel_rows;
+        d.panel_wm = t->panel_wm;
+        d.cfg_nst = t->nst;
+        d.cfg_bk = t->bk;
+        if (audit) ctx->audit_desc(d, false);
+        check(igemm_panel_launch(d, PL, t->panel_bn, st), "row-panel kernel");
+        break;
+      case DSN_TG_SKINNY:
+        d.ksplit = std::max(t->ksplit, 1);
+        d.slab_stride = t->slab_stride;
+        if (audit) ctx->audit_desc(d, false);
+        check(igemm_skinny_launch(d, PL, st), "skinny kernel");
+        break;
+      case DSN_TG_HALO:
+        if (audit) ctx->audit_desc(d, false);
+        check(igemm_halo3x3_launch(d, PL, st), "halo 3x3 kernel");
+        break;
+      case DSN_TG_SPLITK: {
+        if (!t->slabs || t->ksplit < 2 || t->slab_stride <= 0) fail(DSN_EINVAL, "test_gemm: split-K needs slabs, ksplit >= 2");
+        GemmDesc g = d;  // the GEMM: raw partial sums only
+        g.ksplit = t->ksplit;
+        g.slab_stride = t->slab_stride;
+        g.out_f32 = t->slabs;
+        g.out_planes = nullptr;
+        g.gn_stats = g.gn_stats2 = nullptr;
+        if (audit) {
+          ctx->audit_desc(g, false);
+          ctx->audit_desc(d, false);  // (the slab epilogue reads the slabs over the extent g writes)
+        }
+        check(igemm2_launch_cfg(g, PL, t->bm, t->bn, t->nst, t->bk, st), "igemm2 split-K tile");
+        check(igemm_slab_epilogue_launch(d, PL, t->slabs, t->ksplit, t->slab_stride, st), "slab epilogue");
+        break;
+      }
+      default:
+        fail(DSN_EINVAL, "test_gemm: unknown kernel %d", t->kernel);
     }
     HIPCHK(hipGetLastError());
   });

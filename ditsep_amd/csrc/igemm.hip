@@ -1976,7 +1976,7 @@ __global__ __launch_bounds__(64) void igemm_slab_epilogue_kernel(GemmDesc d, con
   const int mw0 = tile_m * 64, nw0 = tile_n * 64;
   const int nq = (lane >> 4) * 4;
   f32x4 acc[4][4];
-  long offs[4];
+  long offs[4], rels[4];
   bool rowok[4];
   seed_acc<4, 4>(d, acc, mw0, d.M, nw0, lane);
 #pragma unroll
@@ -1987,7 +1987,8 @@ __global__ __launch_bounds__(64) void igemm_slab_epilogue_kernel(GemmDesc d, con
     const int j = mok ? m - b * d.rows_per_b : 0;
     const long row_rel = (long)j * d.out_row_elems + d.out_off;
     offs[tm] = (long)b * d.out_bstride + row_rel;
-    rowok[tm] = mok && row_rel + nw0 >= 0 && row_rel + nw0 + 64 <= d.out_limit;
+    rels[tm] = row_rel;
+    rowok[tm] = mok;
   }
   for (int z = 0; z < nslab; ++z) {
     f32x4 part[4][4];
@@ -1995,9 +1996,13 @@ __global__ __launch_bounds__(64) void igemm_slab_epilogue_kernel(GemmDesc d, con
     for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
       for (int tn = 0; tn < 4; ++tn) {
+        // exactly the 4-column groups the GEMM's split-K store wrote (epilogue_gen: first column inside
+        // [0, out_limit)) -- and that the epilogue below stores: a row clipped inside a 64-column chunk still gets its sums
         const int n = nw0 + tn * 16 + nq;
-        part[tn][tm] = (rowok[tm] && n < d.N) ? *reinterpret_cast<const f32x4*>(slabs + z * slab_stride + offs[tm] + n)
-                                              : f32x4{0.f, 0.f, 0.f, 0.f};
+        const long rel = rels[tm] + n;
+        part[tn][tm] = (rowok[tm] && n < d.N && rel >= 0 && rel < d.out_limit)
+                           ? *reinterpret_cast<const f32x4*>(slabs + z * slab_stride + offs[tm] + n)
+                           : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
     for (int tm = 0; tm < 4; ++tm)

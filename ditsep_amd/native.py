@@ -29,7 +29,7 @@ EXPORTS = [
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
-    "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
+    "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
 ]
 
 
@@ -70,6 +70,34 @@ class DsnConfig(C.Structure):
         ("vae_enc_latent_dim", C.c_int32), ("vae_use_snake", C.c_int32), ("vae_final_tanh", C.c_int32),
         ("vae_has_encoder", C.c_int32), ("vae_has_decoder", C.c_int32),
         ("sde_theta", C.c_float), ("sde_sigma_min", C.c_float), ("sde_sigma_max", C.c_float),
+    ]
+
+
+# dsn_test_gemm (include/ditsep_hip.h): which kernel of the implicit-GEMM family runs the descriptor
+TEST_GEMM_KERNELS = {"auto": 0, "tile": 1, "v1": 2, "panel": 3, "skinny": 4, "halo": 5, "splitk": 6}
+ACT_NONE, ACT_ELU, ACT_SNAKE, ACT_SILU = 0, 1, 2, 3
+F32_NONE, F32_TANH = 0, 1
+
+
+class DsnTestGemm(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("nst", C.c_int), ("bk", C.c_int),
+        ("panel_rows", C.c_int), ("panel_bn", C.c_int), ("panel_wm", C.c_int), ("ksplit", C.c_int),
+        ("B", C.c_int), ("Lin", C.c_int), ("Cin", C.c_int), ("N", C.c_int), ("taps", C.c_int), ("in_stride", C.c_int),
+        ("tap_dil", C.c_int), ("in_pad", C.c_int), ("rows_per_b", C.c_int), ("M", C.c_int),
+        ("in_row_elems", C.c_int), ("a_off", C.c_int), ("in_bstride", C.c_int64),
+        ("img_h", C.c_int), ("img_w", C.c_int), ("out_bstride", C.c_int64),
+        ("out_row_elems", C.c_int), ("out_off", C.c_int), ("out_limit", C.c_int64),
+        ("a", C.c_void_p), ("a_numel", C.c_int64), ("w", C.c_void_p),
+        ("bias", C.c_void_p), ("bias_mod", C.c_int), ("bbias", C.c_void_p), ("bbias_stride", C.c_int),
+        ("resid", C.c_void_p), ("resid_bstride", C.c_int64), ("resid_row_elems", C.c_int), ("resid_off", C.c_int),
+        ("out_scale", C.c_float), ("f32_op", C.c_int), ("act", C.c_int), ("act_a", C.c_void_p), ("act_b", C.c_void_p),
+        ("act_mod", C.c_int), ("swiglu", C.c_int), ("gn_stats", C.c_void_p), ("gn_stats2", C.c_void_p),
+        ("gn_nq2", C.c_int), ("gn_qoff2", C.c_int),
+        ("sc_a", C.c_void_p), ("sc_a_numel", C.c_int64), ("sc_w", C.c_void_p), ("sc_bias", C.c_void_p),
+        ("sc_Cin", C.c_int), ("sc_row_elems", C.c_int),
+        ("out_f32", C.c_void_p), ("out_planes", C.c_void_p), ("out_ps", C.c_int64),
+        ("slabs", C.c_void_p), ("slab_stride", C.c_int64),
     ]
 
 
@@ -121,6 +149,7 @@ def load_library() -> C.CDLL:
     lib.dsn_profile_rows.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.dsn_test_igemm.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
+    lib.dsn_test_gemm.argtypes = [vp, C.POINTER(DsnTestGemm), vp]
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
@@ -435,3 +464,43 @@ class Engine:
         self._check(self.lib.dsn_test_igemm(self.ctx, _ptr(a), _ptr(w), _ptr(out), B, Lin, Cin, N, taps, in_stride,
                                             tap_dil, in_pad, rpb, panel_rows, panel_bn, self._stream()), "dsn_test_igemm")
         return out
+
+    # operand format of this context: (planes, fp16?) per precision code
+    _PLANES = {PREC_BF16: (1, False), PREC_BF16X3: (2, False), PREC_FP16: (1, True), PREC_FP16X3: (2, True)}
+
+    def test_gemm(self, a, w, *, kernel="auto", B, Lin, Cin, N, taps=1, rows_per_b=None, **kw):
+        """Run one kernel of the implicit-GEMM family (dsn_test_gemm, include/ditsep_hip.h) on caller-owned fp32
+        device tensors.  `a` is the whole input (a channel slice is addressed with in_row_elems / a_off), `w` is
+        [N][taps*Cin].  Outputs (out_f32, out_planes as int16 [P][out_ps], slabs, gn_stats...) are written in place;
+        every other keyword is the DsnTestGemm field of the same name (tensors are passed by pointer)."""
+        t = DsnTestGemm()
+        t.kernel = TEST_GEMM_KERNELS[kernel]
+        t.B, t.Lin, t.Cin, t.N, t.taps = B, Lin, Cin, N, taps
+        t.rows_per_b = Lin if rows_per_b is None else rows_per_b
+        t.in_stride, t.tap_dil, t.out_scale = 1, 1, 1.0
+        keep = [a, w]
+        for name, tensor_like in (("a", a), ("w", w)):
+            assert tensor_like.is_cuda and tensor_like.dtype == torch.float32 and tensor_like.is_contiguous(), name
+        t.a, t.a_numel, t.w = a.data_ptr(), a.numel(), w.data_ptr()
+        if w.numel() != N * taps * Cin:
+            raise ValueError(f"w has {w.numel()} elements, N*taps*Cin = {N * taps * Cin}")
+        for k, v in kw.items():
+            if isinstance(v, torch.Tensor):
+                assert v.is_cuda and v.is_contiguous(), k
+                assert v.dtype == (torch.int16 if k == "out_planes" else torch.float32), k
+                keep.append(v)
+                setattr(t, k, v.data_ptr())
+                if k == "sc_a":
+                    t.sc_a_numel = v.numel()
+                if k == "out_planes" and "out_ps" not in kw:
+                    t.out_ps = v.shape[-1] if v.dim() > 1 else v.numel()
+            elif v is not None:
+                setattr(t, k, v)
+        self._check(self.lib.dsn_test_gemm(self.ctx, C.byref(t), self._stream()), f"dsn_test_gemm({kernel})")
+
+    def decode_planes(self, raw):
+        """int16 operand planes [P][n] as written by a GEMM epilogue -> float64 values (hi, or hi + lo)."""
+        P, f16 = self._PLANES[self.cfg.precision]
+        raw = raw.reshape(P, -1)
+        planes = [(raw[p].view(torch.float16) if f16 else raw[p].view(torch.bfloat16)).double() for p in range(P)]
+        return planes[0] if P == 1 else planes[0] + planes[1]

@@ -230,7 +230,7 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
                      int64_t* launches);
 
 /* ---- NOT PART OF THE ABI ------------------------------------------------------------------------------------
- * dsn_test_igemm, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests, repro scripts and
+ * dsn_test_igemm, dsn_test_gemm, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests, repro scripts and
  * kernel sweeps.  They name internal workspace buffers and kernel variants, change without notice, and a binding of
  * the reference-facing interface must not use them. */
 /* Test hook: run the implicit-GEMM kernel on caller-provided fp32 operands.
@@ -238,6 +238,62 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
 int dsn_test_igemm(dsn_ctx* ctx, const float* a, const float* w, float* out, int B, int Lin, int Cin, int N,
                    int taps, int in_stride, int tap_dil, int in_pad, int rows_per_b, int panel_rows, int panel_bn,
                    void* stream);   /* panel_rows > 0: row-panel kernel with panel_bn (128|256) columns */
+
+/* Test hook: run ONE chosen kernel of the implicit-GEMM family (ditsep_amd/csrc/igemm.h) on a descriptor built from
+ * caller-owned fp32 device tensors, with any subset of the epilogue features.  Operands are rounded to the engine's
+ * operand planes first.  A launcher that refuses the descriptor fails the call by name: there is no fall-back to another
+ * kernel.  Every descriptor built here is bounds-audited when DSN_AUDIT is set (the test suite sets it). */
+enum { DSN_TG_AUTO = 0, DSN_TG_TILE = 1, DSN_TG_V1 = 2, DSN_TG_PANEL = 3, DSN_TG_SKINNY = 4, DSN_TG_HALO = 5,
+       DSN_TG_SPLITK = 6 };
+typedef struct DsnTestGemm {
+  int kernel;                 /* DSN_TG_* */
+  int bm, bn, nst, bk;        /* TILE: igemm2 instantiation; PANEL: nst / bk pick the 8-wave ring (0 = any) */
+  int panel_rows, panel_bn, panel_wm;  /* PANEL */
+  int ksplit;                 /* SKINNY (slabs in out_f32, slab_stride apart) and SPLITK (slabs in `slabs`) */
+  /* geometry: out[b][j][n] = sum_{tap,ci} w[n][tap*Cin+ci] a[b*in_bstride + (j*in_stride + tap*tap_dil - in_pad) *
+   * in_row_elems + a_off + ci]; 2-D 3x3 mode when img_w > 0.  Zero in_row_elems / in_bstride / out_* = dense. */
+  int B, Lin, Cin, N, taps, in_stride, tap_dil, in_pad, rows_per_b;
+  int M;                      /* GEMM rows; 0 = B * rows_per_b (fewer: the last item is short) */
+  int in_row_elems, a_off;
+  int64_t in_bstride;
+  int img_h, img_w;
+  int64_t out_bstride;
+  int out_row_elems, out_off;
+  int64_t out_limit;
+  const float* a;             /* input, a_numel floats (a multiple of 4) */
+  int64_t a_numel;
+  const float* w;             /* [N][taps*Cin] */
+  /* epilogue operands (null = off) */
+  const float* bias;
+  int bias_mod;
+  const float* bbias;
+  int bbias_stride;
+  const float* resid;
+  int64_t resid_bstride;
+  int resid_row_elems, resid_off;
+  float out_scale;
+  int f32_op;                 /* DSN_F32_* of the kernels: 1 = tanh */
+  int act;                    /* 1 = ELU, 2 = Snake, 3 = SiLU (operand-plane output only) */
+  const float* act_a;
+  const float* act_b;
+  int act_mod;
+  int swiglu;
+  float* gn_stats;
+  float* gn_stats2;
+  int gn_nq2, gn_qoff2;
+  const float* sc_a;          /* halo 1x1 shortcut input [B][rows_per_b][sc_row_elems], sc_a_numel floats */
+  int64_t sc_a_numel;
+  const float* sc_w;          /* [N][sc_Cin] */
+  const float* sc_bias;
+  int sc_Cin, sc_row_elems;
+  /* outputs */
+  float* out_f32;
+  int16_t* out_planes;        /* P planes of out_ps elements each, raw 16-bit operand bits */
+  int64_t out_ps;
+  float* slabs;               /* SPLITK: ksplit slabs, slab_stride floats apart */
+  int64_t slab_stride;
+} DsnTestGemm;
+int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream);
 
 /* Development hook: copy `count` floats of a named workspace buffer to host memory. */
 int dsn_debug_read(dsn_ctx* ctx, const char* name, float* host, int64_t count);

@@ -77,6 +77,42 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(native.EXPORTS)
 
 
+def test_gemm_kernel_tests_cover_every_instantiation():
+    """tests/test_gpu_gemm_kernels.py runs every igemm2 tile (CFGL / CFG lines of igemm2_launch_cfg) and every skinny
+    MT (SK lines): an instantiation added to igemm.hip without a test entry fails here."""
+    from tests.test_gpu_gemm_kernels import FULL, IGEMM_SRC, LEAN, SKINNY_MT
+
+    src = open(IGEMM_SRC).read()
+
+    def body(fn):
+        b = src[src.index(fn):]
+        return b[:b.index("\n}\n")]
+
+    cfg = body("hipError_t igemm2_launch_cfg(")
+    calls = lambda mac: sorted(tuple(int(x) for x in m.groups())
+                               for m in re.finditer(r"\b" + mac + r"\((\d+), (\d+), (\d+), (\d+), (\d+)\)", cfg))
+    assert calls("CFGL") == sorted(LEAN)
+    assert calls("CFG") == sorted(FULL)
+    assert re.findall(r"launch_cfg<\d[^>]*>", cfg) == [
+        "launch_cfg<1, 1, 128, 64, 3, 64, 0, 32>", "launch_cfg<1, 0, 128, 64, 3, 64, 0, 32>"]  # the 128 x 64 tile
+    sk = body("hipError_t igemm_skinny_launch(")
+    assert sorted(int(m) for m in re.findall(r"\bSK\((\d+)\)", sk)) == SKINNY_MT
+
+
+def test_test_gemm_struct_matches_header():
+    """native.DsnTestGemm mirrors struct DsnTestGemm of include/ditsep_hip.h field by field"""
+    hdr = open(os.path.join(ROOT, "include", "ditsep_hip.h")).read()
+    body = hdr[hdr.index("typedef struct DsnTestGemm {"):hdr.index("} DsnTestGemm;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
+    names = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            names += [re.sub(r"^.*?[\s*]+(\w+)$", r"\1", d.strip()) if i == 0 else d.strip().lstrip("*")
+                      for i, d in enumerate(decl.split(","))]
+    assert names == [f[0] for f in native.DsnTestGemm._fields_]
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(native, "_lib", None)
     monkeypatch.setattr(native, "LIB_PATH", "/nonexistent/libditsep_hip.so")
