@@ -120,6 +120,80 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- NCSN++ GroupNorm: one owner of the group geometry and of the statistics combine ----
+// The (mean, M2) partials of a tensor are laid out stats[item][S][C/4][2], S = ceil(HW / 64): one entry per 64-row slice
+// and 4-channel quad (GemmDesc::gn_stats, gn_stats_kernel).  Every consumer -- gn_apply_kernel and the GEMMs that
+// finish a GroupNorm themselves (GemmDesc::gnf_out) -- combines them through gn_combine below, so they normalise with
+// the same bits.
+struct GnGeom {
+  int G, cpg, qpg;  // groups, channels per group, quads per group
+};
+__host__ __device__ inline GnGeom gn_geom(int C) {
+  const int G = C / 4 < 32 ? C / 4 : 32;
+  return GnGeom{G, C / G, C / G / 4};
+}
+// lanes per group of the combine in a block of `block` threads: the largest power of two <= 64 that fits all G groups
+__host__ __device__ inline int gn_tpg(int G, int block) {
+  int tpg = 1;
+  while (tpg < 64 && G * tpg * 2 <= block) tpg *= 2;
+  return tpg;
+}
+// groups made of whole quads, none across a column tile of width W
+__host__ __device__ inline bool gn_groups_fit(int C, int W) {
+  if (C < 4) return false;
+  const GnGeom g = gn_geom(C);
+  return C % (4 * g.G) == 0 && W % g.cpg == 0;
+}
+// how the combine reads a partial: plain loads, or relaxed agent-scope atomic loads where other waves / workgroups of
+// the same launch have just written the partials write-through (the GEMM finishes)
+struct GnLoadPlain {
+  __device__ static float ld(const float* p) { return *p; }
+};
+struct GnLoadAgent {
+  __device__ static float ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+// (mean, rstd) of groups g0 .. g0 + ngroups - 1 of one item -> gm[g], gr[g] (g counted from g0), by `block` threads
+// (tid = thread index).  stats = the item's partials.  TPG lanes per group share the (slice, quad) partials: lane-local
+// sums in index order, then a fixed xor tree -- the same bits on every launch.  Two passes (mean, then M2 about it:
+// Chan's parallel formula M2 = sum M2_p + sum n_p (mean_p - mean)^2).  The caller synchronises before reading gm / gr.
+template <class L>
+__device__ __forceinline__ void gn_combine(const float* stats, int C, int g0, int ngroups, int HW, int block, int tid,
+                                           float eps, float* gm, float* gr) {
+  const GnGeom gg = gn_geom(C);
+  const int nq = C >> 2, qpg = gg.qpg;
+  const int S = (HW + 63) >> 6;
+  const int tpg = gn_tpg(gg.G, block);
+  const int lg = __builtin_ctz(tpg);  // (tpg is a power of two: shifts, not divisions)
+  const int g = tid >> lg, sub = tid & (tpg - 1);
+  const bool live = g < ngroups;
+  const float* sp = stats + (long)(g0 + (live ? g : 0)) * qpg * 2;
+  const int items = S * qpg;
+  float wsum = 0.f;
+  if (live)
+    for (int it = sub; it < items; it += tpg) {
+      const int sl = it / qpg, q = it - sl * qpg;
+      const float cnt = (float)((min(sl * 64 + 64, HW) - sl * 64) * 4);
+      wsum += cnt * L::ld(sp + ((long)sl * nq + q) * 2);
+    }
+  for (int o = tpg >> 1; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
+  const float ntot = (float)HW * (float)gg.cpg;
+  const float mean = wsum / ntot;
+  float m2 = 0.f;
+  if (live)
+    for (int it = sub; it < items; it += tpg) {
+      const int sl = it / qpg, q = it - sl * qpg;
+      const float cnt = (float)((min(sl * 64 + 64, HW) - sl * 64) * 4);
+      const float* pp = sp + ((long)sl * nq + q) * 2;
+      const float dm = L::ld(pp) - mean;
+      m2 += L::ld(pp + 1) + cnt * dm * dm;
+    }
+  for (int o = tpg >> 1; o >= 1; o >>= 1) m2 += __shfl_xor(m2, o, 64);
+  if (live && sub == 0) {
+    gm[g] = mean;
+    gr[g] = rsqrtf(m2 / ntot + eps);
+  }
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // One-time per-DEVICE setup from host launch code (function attributes, zero pages): several engine contexts on

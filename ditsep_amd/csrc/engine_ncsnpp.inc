@@ -295,7 +295,6 @@ void track_output(GemmDesc& d, const View& out, int B, int HW) {
 void group_norm(const View& x, const float* gamma, const float* beta, int B, int HW, bool silu, float* of, op16_t* op,
                 long ops, hipStream_t st, float* stats = nullptr, bool tracked = true) {
   // tracked = false: a scratch tensor that every block reuses (its producer hands `stats` over directly)
-  const int G = std::min(x.C / 4, 32);
   if (!stats && tracked) {
     auto it = ncs_stats_of.find({x.f + x.coff, x.C});
     if (it != ncs_stats_of.end()) stats = it->second;
@@ -304,10 +303,10 @@ void group_norm(const View& x, const float* gamma, const float* beta, int B, int
   if (!stats && tracked && x.cat && x.C == x.rs && x.coff == 0 && x.cat->parts == 3) stats = x.cat->slot;
   if (!stats) {
     stats = gn_slot(B);
-    launch_gn_stats(x.f + x.coff, x.bs, x.rs, x.C, G, B, HW, stats, st);
+    launch_gn_stats(x.f + x.coff, x.bs, x.rs, x.C, B, HW, stats, st);
     if (tracked) ncs_stats_of[{x.f + x.coff, x.C}] = stats;
   }
-  launch_gn_apply(x.f + x.coff, x.bs, x.rs, x.C, G, B, HW, stats, gamma, beta, 1e-6f, silu ? 1 : 0, of, op, ops, PL, st);
+  launch_gn_apply(x.f + x.coff, x.bs, x.rs, x.C, B, HW, stats, gamma, beta, 1e-6f, silu ? 1 : 0, of, op, ops, PL, st);
 }
 
 // ResnetBlockBigGANpp: x (H x W) -> out (H' x W'), out may be a channel slice of a concat buffer

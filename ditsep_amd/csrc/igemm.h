@@ -110,8 +110,9 @@ struct GemmDesc {
   long sc_bstride;
   // GroupNorm finished by the producing conv (igemm_halo3x3_kernel, gnf_out != null; needs gn_stats): the row-tile
   // workgroups of an image publish their slice partials write-through, meet at the (image, column tile) counter, combine
-  // the image's partials exactly as gn_apply_kernel does, and store silu(GroupNorm(out)) as the operand plane of the next
-  // conv straight from their accumulators -- the fp32 tensor is never written and the gn_apply launch is not needed.
+  // the image's partials with gn_combine (common.h, the combine gn_apply_kernel runs), and store silu(GroupNorm(out)) as
+  // the operand plane of the next conv straight from their accumulators -- the fp32 tensor is never written and the
+  // gn_apply launch is not needed.
   // All workgroups of the grid must be resident together (igemm_halo3x3_gnfin_ok).
   op16_t* gnf_out;           // [B * rows_per_b][N] 16-bit plane
   const float* gnf_gamma;    // [N]

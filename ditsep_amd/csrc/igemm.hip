@@ -762,6 +762,38 @@ __device__ __forceinline__ int swzk(int row) {
   return TBK == 32 ? ((-(row >> 2)) & 3) : ((row >> 1) & 7);
 }
 
+// GroupNorm finished by the producing conv (GemmDesc::gnf_out), last step: silu(GroupNorm(out)) of a wave's NT x 4
+// sub-tiles (rows from mw0, columns from nw0) to the next conv's operand plane, straight from the accumulators.
+// val(tn, tm, n) = the value the epilogue would have stored in the fp32 tensor, in the caller's own order of operations;
+// gm / gr = (mean, rstd) of the groups from column n0 on (gn_combine).  Whole row tiles: M % TBM == 0 (*_gnfin_ok).
+template <int F16, int NT, class Val>
+__device__ __forceinline__ void gn_finish_store(const GemmDesc& d, int mw0, int nw0, int n0, int lane, const float* gm,
+                                                const float* gr, Val val) {
+  const int C = d.N, cpg = gn_geom(C).cpg;
+  const int nqc = (lane >> 4) * 4;
+#pragma unroll
+  for (int tn = 0; tn < NT; ++tn) {
+    const int n = nw0 + tn * 16 + nqc;
+    if (n >= C) continue;
+    const int gl = (n - n0) / cpg;
+    const float mean = gm[gl], rstd = gr[gl];
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(d.gnf_gamma + n);
+    const f32x4 be = *reinterpret_cast<const f32x4*>(d.gnf_beta + n);
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm) {
+      const int m = mw0 + tm * 16 + (lane & 15);
+      const f32x4 v = val(tn, tm, n);
+      op16x4 h;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float t = (v[k] - mean) * rstd * ga[k] + be[k];
+        h[k] = to_op16(d.gnf_silu ? dsn_silu(t) : t, F16);
+      }
+      *reinterpret_cast<op16x4*>(d.gnf_out + (long)m * C + n) = h;
+    }
+  }
+}
+
 // WTN: columns of a wave tile (64, or 32 for the 128 x 64 workgroup tile that gives a GEMM of few rows twice the workgroups)
 template <int P, int F16, int TBM, int TBN, int NST, int TBK, int LEAN = 0, int WTN = 64>
 __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kernel(const GemmDesc d,
@@ -914,79 +946,30 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
     if (d.gnf_out) {
       // ---- GroupNorm finished by this workgroup alone (GemmDesc::gnf_out with 128-pixel images: the tile IS the
       // image, its 64 columns hold whole groups): the epilogue above stored nothing but the two slices' partials; they are
-      // combined exactly as gn_apply_kernel does and silu(GroupNorm(out)) goes to the next conv's operand plane from the
-      // accumulators.  No other workgroup is involved (igemm_halo3x3_kernel has the cross-workgroup form).
+      // combined by gn_combine and silu(GroupNorm(out)) goes to the next conv's operand plane from the accumulators.  No
+      // other workgroup is involved (igemm_halo3x3_kernel has the cross-workgroup form).
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       float* const gm = reinterpret_cast<float*>(lds);
       float* const gr = gm + 64;
       const int HW = d.rows_per_b, b = m0 / HW;
-      const int C = d.N, nq_all = C >> 2;
-      const int G = min(C >> 2, 32), cpg = C / G, qpg = cpg >> 2;
-      const int S = HW >> 6;
-      int tpg = 1;
-      while (tpg < 64 && G * tpg * 2 <= 256) tpg *= 2;
-      const int ngt = min(TBN, C - n0) / cpg;
-      {
-        const int gl = tid / tpg, sub = tid - gl * tpg;
-        const bool live = gl < ngt;
-        const float* sp = d.gn_stats + ((long)b * S * nq_all + (long)(n0 / cpg + (live ? gl : 0)) * qpg) * 2;
-        const int items = S * qpg;
-        const float cnt = 256.f;
-        float wsum = 0.f;
-        if (live)
-          for (int it = sub; it < items; it += tpg) {
-            const int sl = it / qpg, q2 = it - sl * qpg;
-            wsum += cnt * __hip_atomic_load(sp + ((long)sl * nq_all + q2) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        for (int o = tpg >> 1; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
-        const float ntot = (float)HW * (float)cpg;
-        const float mean = wsum / ntot;
-        float m2 = 0.f;
-        if (live)
-          for (int it = sub; it < items; it += tpg) {
-            const int sl = it / qpg, q2 = it - sl * qpg;
-            const float* pp = sp + ((long)sl * nq_all + q2) * 2;
-            const float px = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float py = __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float dm = px - mean;
-            m2 += py + cnt * dm * dm;
-          }
-        for (int o = tpg >> 1; o >= 1; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-        if (live && sub == 0) {
-          gm[gl] = mean;
-          gr[gl] = rsqrtf(m2 / ntot + d.gnf_eps);
-        }
-      }
+      const int C = d.N, cpg = gn_geom(C).cpg;
+      gn_combine<GnLoadAgent>(d.gn_stats + (long)b * (HW >> 6) * (C >> 2) * 2, C, n0 / cpg, min(TBN, C - n0) / cpg,
+                              HW, 256, tid, d.gnf_eps, gm, gr);
       __syncthreads();
-      const int nqc = (lane >> 4) * 4;
-#pragma unroll
-      for (int tn = 0; tn < NT; ++tn) {
-        const int n = n0 + wn * WTN + tn * 16 + nqc;
-        if (n >= C) continue;
-        const int gl = (n - n0) / cpg;
-        const float mean = gm[gl], rstd = gr[gl];
-        const f32x4 ga = *reinterpret_cast<const f32x4*>(d.gnf_gamma + n);
-        const f32x4 be = *reinterpret_cast<const f32x4*>(d.gnf_beta + n);
+      gn_finish_store<F16, NT>(d, m0 + wm * 64, n0 + wn * WTN, n0, lane, gm, gr, [&](int tn, int tm, int n) {
+        // the value the epilogue would have stored: (acc + bias) + per-item bias, scaled (same order of operations)
         const f32x4 bias4 = d.bias ? *reinterpret_cast<const f32x4*>(d.bias + (n % d.bias_mod)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 v = acc[tn][tm] + bias4;
+        if (d.bbias) v += *reinterpret_cast<const f32x4*>(d.bbias + (long)b * d.bbias_stride + n);
 #pragma unroll
-        for (int tm = 0; tm < 4; ++tm) {
-          const int m = m0 + wm * 64 + tm * 16 + (lane & 15);
-          if (m >= d.M) continue;
-          // the value the epilogue would have stored: (acc + bias) + per-item bias, scaled (same order of operations)
-          f32x4 v = acc[tn][tm] + bias4;
-          if (d.bbias) v += *reinterpret_cast<const f32x4*>(d.bbias + (long)b * d.bbias_stride + n);
-          op16x4 h;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            float vk = v[k] * d.out_scale;
-            asm volatile("" : "+v"(vk));  // (rounded on its own, as the stored fp32 tensor would hold it)
-            float tt = (vk - mean) * rstd * ga[k] + be[k];
-            h[k] = to_op16(d.gnf_silu ? dsn_silu(tt) : tt, F16);
-          }
-          *reinterpret_cast<op16x4*>(d.gnf_out + (long)m * C + n) = h;
+        for (int k = 0; k < 4; ++k) {
+          float vk = v[k] * d.out_scale;
+          asm volatile("" : "+v"(vk));  // (rounded on its own, as the stored fp32 tensor would hold it)
+          v[k] = vk;
         }
-      }
+        return v;
+      });
     }
   }
 }
@@ -1245,71 +1228,16 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
       }
     }
     __syncthreads();
-    // (mean, rstd) of the groups of this column tile -> LDS (the ring is free).  The combine is gn_apply_kernel's, lane
-    // for lane -- TPG lanes per group, lane-local sums in index order, xor tree; its block is 256 threads wide, which
-    // fixes TPG -- so both paths normalise with the same bits.
+    // (mean, rstd) of the groups of this column tile -> LDS (the ring is free), by gn_combine -- the combine gn_apply_kernel
+    // runs, in a block of the same 256 threads -- so both paths normalise with the same bits
     float* const gm = reinterpret_cast<float*>(lds);
     float* const gr = gm + 64;
-    const int C = d.N, nq_all = C >> 2;
-    const int G = min(C >> 2, 32), cpg = C / G, qpg = cpg >> 2;
-    const int S = HW >> 6;
-    int tpg = 1;
-    while (tpg < 64 && G * tpg * 2 <= 256) tpg *= 2;
-    const int ngt = min(TBN, C - n0) / cpg;  // groups of this column tile
-    {
-      const int gl = tid / tpg, sub = tid - gl * tpg;
-      const bool live = gl < ngt;
-      const float* sp = d.gn_stats + ((long)b * S * nq_all + (long)(n0 / cpg + (live ? gl : 0)) * qpg) * 2;
-      const int items = S * qpg;
-      const float cnt = 256.f;  // 64 rows x 4 channels per partial (whole slices: HW % 64 == 0)
-      float wsum = 0.f;
-      if (live)
-        for (int it = sub; it < items; it += tpg) {
-          const int sl = it / qpg, q = it - sl * qpg;
-          wsum += cnt * __hip_atomic_load(sp + ((long)sl * nq_all + q) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      for (int o = tpg >> 1; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
-      const float ntot = (float)HW * (float)cpg;
-      const float mean = wsum / ntot;
-      float m2 = 0.f;
-      if (live)
-        for (int it = sub; it < items; it += tpg) {
-          const int sl = it / qpg, q = it - sl * qpg;
-          const float* pp = sp + ((long)sl * nq_all + q) * 2;
-          const float px = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float py = __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float dm = px - mean;
-          m2 += py + cnt * dm * dm;
-        }
-      for (int o = tpg >> 1; o >= 1; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-      if (live && sub == 0) {
-        gm[gl] = mean;
-        gr[gl] = rsqrtf(m2 / ntot + d.gnf_eps);
-      }
-    }
+    const int C = d.N, cpg = gn_geom(C).cpg;
+    gn_combine<GnLoadAgent>(d.gn_stats + (long)b * (HW >> 6) * (C >> 2) * 2, C, n0 / cpg, min(TBN, C - n0) / cpg, HW,
+                            256, tid, d.gnf_eps, gm, gr);
     __syncthreads();
-    const int nqc = (lane >> 4) * 4;
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-      const int n = n0 + wn * 64 + tn * 16 + nqc;
-      if (n >= C) continue;
-      const int gl = (n - n0) / cpg;
-      const float mean = gm[gl], rstd = gr[gl];
-      const f32x4 ga = *reinterpret_cast<const f32x4*>(d.gnf_gamma + n);
-      const f32x4 be = *reinterpret_cast<const f32x4*>(d.gnf_beta + n);
-#pragma unroll
-      for (int tm = 0; tm < 4; ++tm) {
-        const int m = m0 + wm * 64 + tm * 16 + (lane & 15);
-        const f32x4 v = acc[tn][tm] * d.out_scale;
-        op16x4 h;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float t = (v[k] - mean) * rstd * ga[k] + be[k];
-          h[k] = to_op16(d.gnf_silu ? dsn_silu(t) : t, F16);
-        }
-        *reinterpret_cast<op16x4*>(d.gnf_out + (long)m * C + n) = h;
-      }
-    }
+    gn_finish_store<F16, 4>(d, m0 + wm * 64, n0 + wn * 64, n0, lane, gm, gr,
+                            [&](int tn, int tm, int) { return acc[tn][tm] * d.out_scale; });
   }
 }
 
@@ -1925,16 +1853,14 @@ bool igemm2_gnfin_ok(const GemmDesc& d, int pl) {
       d.N % 64 != 0 || d.N > 1024 || d.Cin % 64 != 0 || d.ksplit > 1 || d.resid || d.out_scale != 1.f || d.swiglu ||
       d.rope_cos || d.qkv_D > 0)
     return false;
-  const int G = std::min(d.N / 4, 32), cpg = d.N / G;
-  return cpg % 4 == 0 && 64 % cpg == 0;
+  return gn_groups_fit(d.N, 64);
 }
 bool igemm_halo3x3_eligible(const GemmDesc& d, int pl) { return igemm_halo3x3_tile(d, pl) != 0; }
 bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl) {
   const bool off = getenv("DSN_NO_GN_FIN") != nullptr;  // (per call: tests flip it)
   const int v = igemm_halo3x3_tile(d, pl);
   if (off || !v || !d.gn_stats || d.N % 32 != 0 || d.N > 1024 || d.rows_per_b % v != 0 || d.out_scale != 1.f) return false;
-  const int G = std::min(d.N / 4, 32), cpg = d.N / G;
-  if (cpg % 4 != 0 || 128 % cpg != 0) return false;  // groups made of whole quads, never across a column tile
+  if (!gn_groups_fit(d.N, 128)) return false;
   static int cap[2][2] = {{-1, -1}, {-1, -1}};
   int& c = cap[PL_F16(pl) ? 1 : 0][v == 256 ? 1 : 0];
   if (c < 0)

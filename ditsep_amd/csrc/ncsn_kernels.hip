@@ -97,51 +97,19 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
 }
 
 // y = (x - mean) * rstd * gamma + beta [, SiLU]  ->  contiguous [B][HW][C] fp32 and/or planes.
-// grid (row chunks, B): a block first combines the slice partials of its item's G groups (fixed order, Chan's
-// parallel formula: M2 = sum M2_p + sum n_p (mean_p - mean)^2) into LDS, then streams its rows.
-__global__ void gn_apply_kernel(const float* __restrict__ x, long bstride, int rstride, int C, int G, int HW,
+// grid (row chunks, B): a block first combines the slice partials of its item's G groups into LDS (gn_combine), then
+// streams its rows.
+__global__ void gn_apply_kernel(const float* __restrict__ x, long bstride, int rstride, int C, int HW,
                                 const float* __restrict__ stats, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, float eps, int silu, float* __restrict__ of,
                                 op16_t* __restrict__ op, long ps, int planes, int rows_per_block) {
   __shared__ float gm[64], gr[64];
   const int nq = C >> 2;
-  const int cpg = C / G, qpg = cpg >> 2;
+  const GnGeom gg = gn_geom(C);
+  const int cpg = gg.cpg;
   const int S = (HW + 63) >> 6;
   const int b = blockIdx.y;
-  {
-    // statistics prologue: TPG lanes per group share the (slice, quad) partials; lane-local sums in index order, then a
-    // fixed xor tree -- the same bits on every launch.  Two passes (mean, then M2 about it: Chan's combine).
-    int tpg = 1;
-    while (tpg < 64 && G * tpg * 2 <= (int)blockDim.x) tpg *= 2;
-    const int g = threadIdx.x / tpg, sub = threadIdx.x - g * tpg;
-    const bool live = g < G;
-    const float2* sp = reinterpret_cast<const float2*>(stats) + (long)b * S * nq + (live ? g : 0) * qpg;
-    const int items = S * qpg;
-    float wsum = 0.f;
-    if (live)
-      for (int it = sub; it < items; it += tpg) {
-        const int sl = it / qpg, q = it - sl * qpg;
-        const float cnt = (float)((min(sl * 64 + 64, HW) - sl * 64) * 4);
-        wsum += cnt * sp[(long)sl * nq + q].x;
-      }
-    for (int o = tpg >> 1; o >= 1; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
-    const float ntot = (float)HW * (float)cpg;
-    const float mean = wsum / ntot;
-    float m2 = 0.f;
-    if (live)
-      for (int it = sub; it < items; it += tpg) {
-        const int sl = it / qpg, q = it - sl * qpg;
-        const float cnt = (float)((min(sl * 64 + 64, HW) - sl * 64) * 4);
-        const float2 pr = sp[(long)sl * nq + q];
-        const float dm = pr.x - mean;
-        m2 += pr.y + cnt * dm * dm;
-      }
-    for (int o = tpg >> 1; o >= 1; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-    if (live && sub == 0) {
-      gm[g] = mean;
-      gr[g] = rsqrtf(m2 / ntot + eps);
-    }
-  }
+  gn_combine<GnLoadPlain>(stats + (long)b * S * nq * 2, C, 0, gg.G, HW, blockDim.x, threadIdx.x, eps, gm, gr);
   __syncthreads();
   const int r_begin = blockIdx.x * rows_per_block, r_end = min(r_begin + rows_per_block, HW);
   const int total4 = (r_end - r_begin) * nq;
@@ -277,20 +245,19 @@ void launch_ncsn_pack(const float* xt, const float* mix, int B, int n, int H, in
   hipLaunchKernelGGL(ncsn_pack_kernel, dim3(grid_for(total)), dim3(TPB), 0, st, xt, mix, n, H, T, Wp, Cp, of, op, ps,
                      planes, total);
 }
-void launch_gn_stats(const float* x, long bstride, int rstride, int C, int G, int B, int HW, float* stats,
-                     hipStream_t st) {
-  if (G > 64 || C % (4 * G) != 0) return;  // unsupported shape: caller validates (engine: C <= 1024)
+void launch_gn_stats(const float* x, long bstride, int rstride, int C, int B, int HW, float* stats, hipStream_t st) {
+  if (!gn_groups_fit(C, C)) return;  // unsupported shape: caller validates (engine: C <= 1024)
   const int S = (HW + 63) / 64;
   const long items = (long)S * cdiv(C / 4, 16);  // one wave each
   hipLaunchKernelGGL(gn_stats_kernel, dim3(cdiv(items, 4), B), dim3(256), 0, st, x, bstride, rstride, C, HW, stats);
 }
-void launch_gn_apply(const float* x, long bstride, int rstride, int C, int G, int B, int HW, const float* stats,
+void launch_gn_apply(const float* x, long bstride, int rstride, int C, int B, int HW, const float* stats,
                      const float* gamma, const float* beta, float eps, int silu, float* of, op16_t* op, long ps,
                      int planes, hipStream_t st) {
   // enough blocks to fill the chip, each with at least ~4k elements behind its statistics prologue
   const int rows_per_block = std::max(cdiv(4096, C), cdiv((long)HW * B, 2048));
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(HW, rows_per_block), B), dim3(TPB), 0, st, x, bstride, rstride, C, G, HW,
-                     stats, gamma, beta, eps, silu, of, op, ps, planes, rows_per_block);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(HW, rows_per_block), B), dim3(TPB), 0, st, x, bstride, rstride, C, HW, stats,
+                     gamma, beta, eps, silu, of, op, ps, planes, rows_per_block);
 }
 void launch_fir2d(const float* x, long bstride, int rstride, int C, int B, int H, int W, int up, const float* add,
                   float* of, op16_t* op, long ps, int planes, hipStream_t st) {
