@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <map>
+#include <numeric>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -160,6 +161,12 @@ struct dsn_ctx {
   std::vector<void*> allocs;
   std::map<std::string, std::pair<void*, size_t>> ws;
   uint64_t ws_epoch = 0;  // bumped on every workspace (re)allocation -> graphs invalid
+  // dsn_stoi: the 10 kHz resampling filter per signal rate (taps in the workspace buffer "stoi_taps_<fs>")
+  struct StoiFilter {
+    double* taps = nullptr;
+    int ntaps = 0, up = 1, down = 1, n_pre_pad = 0, n_pre_remove = 0;
+  };
+  std::map<int, StoiFilter> stoi_filters;
 
   // DiT
   float* tf_w = nullptr;
@@ -2395,6 +2402,148 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
         if (si_sar_out) si_sar_out[o] = (float)sar[bestp[i]];
         if (perm_out) perm_out[o] = bestp[i];
       }
+    }
+  });
+}
+
+// Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
+static double bessel_i0(double x) {
+  double s = 1.0, t = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    t *= (x / (2.0 * k)) * (x / (2.0 * k));
+    s += t;
+    if (t < s * 1e-17) break;
+  }
+  return s;
+}
+
+// The resampler pystoi.stoi applies when fs != 10000: scipy.signal.resample_poly(x, 10000, fs, window=h / sum(h))
+// with h the Octave-style Kaiser-windowed sinc of pystoi.utils._resample_window_oct (60 dB rejection), designed in
+// double precision.  resample_poly scales the window by `up` and aligns the output by n_pre_pad / n_pre_remove.
+static constexpr int kStoiMaxTaps = 1 << 16;
+static const dsn_ctx::StoiFilter& stoi_filter(dsn_ctx* ctx, int fs) {
+  auto it = ctx->stoi_filters.find(fs);
+  if (it != ctx->stoi_filters.end()) return it->second;
+  const int g = std::gcd(10000, fs);
+  const int p = 10000 / g, q = fs / g;
+  const double cutoff = 1.0 / (2.0 * std::max(p, q));
+  const double roll_off = cutoff / 10.0;
+  const double Ld = ceil((60.0 - 8.0) / (28.714 * roll_off));
+  if (2.0 * Ld + 1.0 > kStoiMaxTaps)
+    fail(DSN_EINVAL, "dsn_stoi: fs = %d needs a %.0f-tap resampling filter (at most %d; 10000/fs reduces to %d/%d)", fs,
+         2.0 * Ld + 1.0, kStoiMaxTaps, p, q);
+  const int L = (int)Ld, ntaps = 2 * L + 1;
+  const double beta = 0.1102 * (60.0 - 8.7), i0b = bessel_i0(beta);
+  std::vector<double> h(ntaps);
+  double sum = 0.0;
+  for (int i = 0; i < ntaps; ++i) {
+    const double t = i - L;
+    const double r = t / L;
+    const double win = bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    const double xs = 2.0 * cutoff * t;
+    const double sinc = t == 0 ? 1.0 : sin(M_PI * xs) / (M_PI * xs);
+    h[i] = win * 2.0 * p * cutoff * sinc;
+    sum += h[i];
+  }
+  for (double& v : h) v = v / sum * p;
+  dsn_ctx::StoiFilter f;
+  f.ntaps = ntaps;
+  f.up = p;
+  f.down = q;
+  f.n_pre_pad = q - L % q;
+  f.n_pre_remove = (L + f.n_pre_pad) / q;
+  f.taps = ctx->wsbuf<double>("stoi_taps_" + std::to_string(fs), ntaps);
+  HIPCHK(hipMemcpy(f.taps, h.data(), sizeof(double) * ntaps, hipMemcpyHostToDevice));
+  return ctx->stoi_filters[fs] = f;
+}
+
+// STOI / ESTOI of every estimate against its reference (pystoi.stoi(ref, est, fs, extended), restated in
+// tests/stoi_restatement.py).  Device: resampling, silent-frame removal, STFT envelopes and segment scores
+// (stoi.hip); host: the filter design, the band table and the permutation map.
+int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, int extended,
+             const int* perm, float* out, int* frames_out, void* stream) {
+  return guarded(ctx, [&] {
+    if (!ref || !est || !out || B <= 0 || n <= 0 || L <= 0)
+      fail(DSN_EINVAL, "dsn_stoi: bad arguments (ref, est, out non-null, B, n, L > 0)");
+    if (n > 4) fail(DSN_EINVAL, "dsn_stoi: n = %d sources (at most 4)", n);
+    if (fs <= 0) fail(DSN_EINVAL, "dsn_stoi: fs = %d (must be positive)", fs);
+    if (extended != 0 && extended != 1) fail(DSN_EINVAL, "dsn_stoi: extended = %d (0 or 1)", extended);
+    const int items = B * n;
+    std::vector<int> ymap;
+    if (perm) {
+      ymap.resize(items);
+      for (int b = 0; b < B; ++b)
+        for (int i = 0; i < n; ++i) {
+          const int p = perm[b * n + i];
+          if (p < 0 || p >= n) fail(DSN_EINVAL, "dsn_stoi: perm[%d] = %d outside [0, %d)", b * n + i, p, n);
+          ymap[b * n + i] = b * n + p;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int* dmap = nullptr;
+    if (perm) {
+      dmap = ctx->wsbuf<int>("stoi_map", items);
+      HIPCHK(hipMemcpyAsync(dmap, ymap.data(), sizeof(int) * items, hipMemcpyHostToDevice, st));
+    }
+    // the 10 kHz signals: the inputs themselves, or their resampled copies [2][items][n10]
+    const float* xs = ref;
+    const float* ys = est;
+    const int* xymap = dmap;
+    long n10 = L;
+    if (fs != 10000) {
+      const dsn_ctx::StoiFilter& f = stoi_filter(ctx, fs);
+      n10 = ((long)L * f.up + f.down - 1) / f.down;
+      if (n10 > (1L << 30)) fail(DSN_EINVAL, "dsn_stoi: %ld samples at 10 kHz (L = %d too long)", n10, L);
+      float* rs = ctx->wsbuf<float>("stoi_rs", 2 * items * n10);
+      launch_stoi_resample(ref, est, dmap, items, L, f.taps, f.ntaps, f.up, f.down, f.n_pre_pad, f.n_pre_remove,
+                           (int)n10, rs, st);
+      xs = rs;
+      ys = rs + items * n10;
+      xymap = nullptr;  // the resampler already placed est source perm[i] at row i
+    }
+    const int F = n10 >= 256 ? (int)((n10 - 256) / 128 + 1) : 0;
+    if (F == 0) {  // not one frame: no STFT frames at all
+      for (int i = 0; i < items; ++i) {
+        out[i] = 1e-5f;
+        if (frames_out) frames_out[i] = 0;
+      }
+      return;
+    }
+    // one-third-octave bands of pystoi.utils.thirdoct: edges 150 * 2^((2k -+ 1)/6) Hz snapped to the nearest of the
+    // bins linspace(0, 10000, 513)[:257] (first bin on a tie)
+    StoiBands bands;
+    for (int k = 0; k < 15; ++k)
+      for (int e = 0; e < 2; ++e) {
+        const double fe = 150.0 * pow(2.0, (2.0 * k + (e ? 1.0 : -1.0)) / 6.0);
+        int best = 0;
+        double bd = 1e300;
+        for (int bin = 0; bin <= 256; ++bin) {
+          const double d = bin * (10000.0 / 512.0) - fe;
+          if (d * d < bd) {
+            bd = d * d;
+            best = bin;
+          }
+        }
+        (e ? bands.hi : bands.lo)[k] = best;
+      }
+    const long Fs = std::max(F - 1, 1), Jmax = std::max(F - 30, 1);
+    double* en = ctx->wsbuf<double>("stoi_en", (long)items * F);
+    int* idx = ctx->wsbuf<int>("stoi_idx", (long)items * F);
+    int* Kc = ctx->wsbuf<int>("stoi_K", items);
+    double* tob = ctx->wsbuf<double>("stoi_tob", (long)items * 2 * 15 * Fs);
+    double* part = ctx->wsbuf<double>("stoi_part", (long)items * Jmax);
+    double* score = ctx->wsbuf<double>("stoi_score", items);
+    int* frames = ctx->wsbuf<int>("stoi_frames", items);
+    launch_stoi_frames(xs, ys, n10, xymap, items, F, bands, extended, en, idx, Kc, tob, part, score, frames, st);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hs(items);
+    std::vector<int> hf(items);
+    HIPCHK(hipMemcpyAsync(hs.data(), score, sizeof(double) * items, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hf.data(), frames, sizeof(int) * items, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < items; ++i) {
+      out[i] = (float)hs[i];
+      if (frames_out) frames_out[i] = hf[i];
     }
   });
 }

@@ -126,3 +126,21 @@ void launch_ncsn_output(const float* pyr, int Cp, const float* t, const float* w
 // ---- metrics -----------------------------------------------------------------------------------------
 // out[(b*n + i)*n + j][3] = (<ref_i, est_j>, |ref_i|^2, |est_j|^2) in fp64
 void launch_sisdr_dots(const float* ref, const float* est, int B, int n, int L, double* out, hipStream_t s);
+
+// ---- STOI / ESTOI (stoi.hip) ----------------------------------------------------------------------------
+// one-third-octave band b covers the 512-point FFT bins [lo[b], hi[b])
+struct StoiBands {
+  int lo[15], hi[15];
+};
+// polyphase resampling of ref and est [items][n_in] (est row ymap[item], or item when ymap is null) to
+// out [2][items][n_out] with fp64 taps [ntaps] already scaled by `up` (scipy.signal.resample_poly's alignment)
+void launch_stoi_resample(const float* ref, const float* est, const int* ymap, int items, int n_in,
+                          const double* taps, int ntaps, int up, int down, int n_pre_pad, int n_pre_remove, int n_out,
+                          float* out, hipStream_t s);
+// the rest of STOI (extended = 0) or ESTOI (1) on 10 kHz signals x = xs + item*stride, y = ys + ymap[item]*stride
+// (ymap nullable) with F = (len - 256)/128 + 1 frames each.  Work buffers: en [items*F] f64, idx [items*F],
+// Kc [items], tob [items*2*15*max(F-1,1)] f64, part [items*max(F-30,1)] f64.  -> score [items] f64 and the STFT
+// frame count left after silent-frame removal, frames [items].
+void launch_stoi_frames(const float* xs, const float* ys, long stride, const int* ymap, int items, int F,
+                        StoiBands bands, int extended, double* en, int* idx, int* Kc, double* tob, double* part,
+                        double* score, int* frames, hipStream_t s);

@@ -4,8 +4,11 @@ sampler + decode (with a device sync, which the reference lacks :273-277), then 
 SI-SDR / SI-SIR / SI-SAR on the device (dsn_si_bss_eval: the bss_eval decomposition with a one-tap filter, the
 permutation chosen on SIR as the reference's `fast_bss_eval.si_bss_eval_sources(..., compute_permutation=True)`
 does, :118-124), one result record per utterance with the reference's JSON fields (:294-304) and the mean
-summary (:139-156).  PESQ / STOI come from third-party packages that are neither vendored nor installed
-(pesq, pystoi) and are emitted as null."""
+summary (:139-156).  With stoi=True the "stoi" field holds extended STOI (the reference calls pystoi.stoi(...,
+extended=True); stoi_extended=False gives classic STOI, its stoi_no_extended) from the device (dsn_stoi), scored on
+the SIR permutation as the reference orders the estimates by perm before calling stoi; parity with the pystoi package
+is unpinned (the float64 restatement in tests/stoi_restatement.py is the contract).  By default, and always for PESQ
+(ITU-T P.862, not implemented), the field is null."""
 from __future__ import annotations
 
 import json
@@ -17,8 +20,10 @@ import torch
 
 
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
-                     snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0) -> dict:
-    """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}."""
+                     snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
+                     stoi: bool = False, stoi_extended: bool = True) -> dict:
+    """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
+    with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise."""
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
     N = N if N is not None else cfg_s.get("N", model.sde.N)
     corrector_steps = corrector_steps if corrector_steps is not None else cfg_s.get("corrector_steps", 1)
@@ -38,12 +43,13 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
         torch.cuda.synchronize(dev)
         t_proc = time.perf_counter() - t_s
         si_sdr, si_sir, si_sar, perm = model.engine.si_bss_eval(target, x_result, perm_by="sir", clamp_db=100.0)
+        st = model.engine.stoi(target, x_result, fs, extended=stoi_extended, perm=perm) if stoi else None
         B = mix.shape[0]
         for b in range(B):
             results[idx] = {"batch_idx": idx, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
                             "si_sar": si_sar[b].tolist(),
-                            "pesq": None, "stoi": None, "nfe": nfe, "runtime": t_proc / B, "len_s": L / fs,
-                            "perm": perm[b].tolist()}
+                            "pesq": None, "stoi": None if st is None else st[b].tolist(),
+                            "nfe": nfe, "runtime": t_proc / B, "len_s": L / fs, "perm": perm[b].tolist()}
             idx += 1
     return results
 
@@ -76,6 +82,8 @@ def write_results(path: str, results: dict):
     # summary: SI-SDR / SI-SIR / SI-SAR are this build's own device kernels (dsn_si_bss_eval), checked against the
     # definition-level CPU restatement only -- fast_bss_eval, which the reference calls, is not installed here
     summary["si_bss_impl"] = "native (dsn_si_bss_eval); parity unpinned vs fast_bss_eval"
+    if any(rec.get("stoi") is not None for rec in results.values()):
+        summary["stoi_impl"] = "native (dsn_stoi); parity unpinned vs pystoi"
     summary["nfe_note"] = "nfe = N * (corrector_steps + 1), the reference's bookkeeping (not a count of score calls)"
     with open(path.replace(".json", "_summary.json"), "w") as fh:
         json.dump(summary, fh, indent=2)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from typing import Mapping, Optional
 
 import torch
@@ -30,6 +31,7 @@ EXPORTS = [
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
     "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
+    "dsn_stoi",
 ]
 
 
@@ -152,6 +154,7 @@ def load_library() -> C.CDLL:
     lib.dsn_test_gemm.argtypes = [vp, C.POINTER(DsnTestGemm), vp]
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
+    lib.dsn_stoi.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -440,6 +443,34 @@ class Engine:
                                              float(clamp_db), *bufs, perm, self._stream()), "dsn_si_bss_eval")
         out = [torch.tensor(list(b), dtype=torch.float32).reshape(B, n) for b in bufs]
         return (*out, torch.tensor(list(perm), dtype=torch.long).reshape(B, n))
+
+    def stoi(self, ref, est, fs: int, extended: bool = True, perm=None, return_frames: bool = False):
+        """ref, est [B,n,L] -> [B,n] float32 STOI (extended=False) or extended STOI (True) of est against ref, as
+        pystoi.stoi(ref, est, fs, extended) defines it (restated in tests/stoi_restatement.py; parity with the pystoi
+        package unpinned).  perm [B,n] (optional): est source perm[b,i] is scored against ref source i.  Items with
+        fewer than 30 STFT frames left after silent-frame removal score 1e-5 with a RuntimeWarning, as in pystoi;
+        return_frames=True also returns those frame counts [B,n]."""
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        if ref.dim() != 3 or est.shape != ref.shape:
+            raise ValueError(f"ref and est must both be [B,n,L] (got {tuple(ref.shape)} and {tuple(est.shape)})")
+        B, n, L = ref.shape
+        out = (C.c_float * (B * n))()
+        frames = (C.c_int * (B * n))()
+        cperm = None
+        if perm is not None:
+            p = torch.as_tensor(perm, dtype=torch.int32).reshape(-1).tolist()
+            if len(p) != B * n:
+                raise ValueError(f"perm must hold B*n = {B * n} entries (got {len(p)})")
+            cperm = (C.c_int * (B * n))(*p)
+        self._check(self.lib.dsn_stoi(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), int(bool(extended)), cperm,
+                                      out, frames, self._stream()), "dsn_stoi")
+        score = torch.tensor(list(out), dtype=torch.float32).reshape(B, n)
+        nfr = torch.tensor(list(frames), dtype=torch.long).reshape(B, n)
+        short = (nfr < 30).nonzero().tolist()
+        if short:
+            warnings.warn(f"stoi: {len(short)} item(s) [b, i] {short[:8]} have fewer than 30 frames after silent-frame "
+                          f"removal; their score is 1e-5", RuntimeWarning, stacklevel=2)
+        return (score, nfr) if return_frames else score
 
     def debug_read(self, name: str, shape):
         out = torch.empty(shape, dtype=torch.float32)

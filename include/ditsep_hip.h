@@ -209,6 +209,15 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
 int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int perm_by, float clamp_db,
                     float* si_sdr_out, float* si_sir_out, float* si_sar_out, int* perm_out, void* stream);
 
+/* STOI (extended = 0) or ESTOI (extended = 1) of est against ref as pystoi.stoi(ref, est, fs, extended)
+ * defines it (restated in tests/; parity with the pystoi package unpinned).  ref, est [B,n,L] fp32 (device),
+ * fs the signal rate.  perm [B*n] host, may be NULL: est source perm[b*n+i] is scored against ref source i
+ * (the dsn_si_bss_eval convention).  out [B*n] host.  frames_out [B*n] host, may be NULL: STFT frames left
+ * after silent-frame removal (< 30 -> out = 1e-5).  n <= 4; a signal rate whose resampling filter to 10 kHz
+ * would exceed 65536 taps is refused (10000/fs must reduce to a small ratio, as it does for 8, 16, 44.1, 48 kHz). */
+int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, int extended,
+             const int* perm, float* out, int* frames_out, void* stream);
+
 /* introspection for benchmarks / tests */
 int dsn_enable_graphs(dsn_ctx* ctx, int enable);          /* hipGraph replay of sample/decode */
 int64_t dsn_workspace_bytes(const dsn_ctx* ctx);
