@@ -167,6 +167,7 @@ struct dsn_ctx {
     int ntaps = 0, up = 1, down = 1, n_pre_pad = 0, n_pre_remove = 0;
   };
   std::map<int, StoiFilter> stoi_filters;
+  OdeCtl* ode_host = nullptr;  // dsn_ode_sample: pinned host image of the solver state (upload / per-attempt poll)
 
   // DiT
   float* tf_w = nullptr;
@@ -1902,6 +1903,7 @@ void dsn_destroy(dsn_ctx* ctx) {
   for (auto& kv : ctx->ws) (void)hipFree(kv.second.first);
   for (auto& kv : ctx->gnf_sync) (void)hipFree(kv.second.first);
   if (ctx->fin_err_host) (void)hipHostFree(ctx->fin_err_host);
+  if (ctx->ode_host) (void)hipHostFree(ctx->ode_host);
   delete ctx;
 }
 
@@ -2133,6 +2135,184 @@ int dsn_sb_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t see
     });
     if (!res) res = ctx->wsbuf<float>("pc_x", sz);
     HIPCHK(hipMemcpyAsync(x_out, res, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    ctx->leave(caller, st);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// ---------------------------------------------------------------- probability-flow ODE sampler
+// Butcher tableaux of scipy's RK45 (Dormand-Prince 5(4)) and RK23 (Bogacki-Shampine 3(2)), scipy/integrate/_ivp/rk.py
+static OdeTableau ode_tableau(int method) {
+  OdeTableau t;
+  memset(&t, 0, sizeof t);
+  if (method == DSN_ODE_RK45) {
+    t.stages = 6;
+    t.err_order = 4;
+    const double c[6] = {0, 1. / 5, 3. / 10, 4. / 5, 8. / 9, 1};
+    const double a[6][5] = {{0, 0, 0, 0, 0},
+                            {1. / 5, 0, 0, 0, 0},
+                            {3. / 40, 9. / 40, 0, 0, 0},
+                            {44. / 45, -56. / 15, 32. / 9, 0, 0},
+                            {19372. / 6561, -25360. / 2187, 64448. / 6561, -212. / 729, 0},
+                            {9017. / 3168, -355. / 33, 46732. / 5247, 49. / 176, -5103. / 18656}};
+    const double b[6] = {35. / 384, 0, 500. / 1113, 125. / 192, -2187. / 6784, 11. / 84};
+    const double e[7] = {-71. / 57600, 0, 71. / 16695, -71. / 1920, 17253. / 339200, -22. / 525, 1. / 40};
+    for (int i = 0; i < 6; ++i) {
+      t.c[i] = c[i];
+      t.b[i] = b[i];
+      for (int j = 0; j < 5; ++j) t.a[i][j] = a[i][j];
+    }
+    for (int i = 0; i < 7; ++i) t.e[i] = e[i];
+  } else {
+    t.stages = 3;
+    t.err_order = 2;
+    const double c[3] = {0, 1. / 2, 3. / 4};
+    const double b[3] = {2. / 9, 1. / 3, 4. / 9};
+    const double e[4] = {5. / 72, -1. / 12, -1. / 9, 1. / 8};
+    for (int i = 0; i < 3; ++i) {
+      t.c[i] = c[i];
+      t.b[i] = b[i];
+    }
+    t.a[1][0] = 1. / 2;
+    t.a[2][1] = 3. / 4;
+    for (int i = 0; i < 4; ++i) t.e[i] = e[i];
+  }
+  return t;
+}
+
+int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
+                   const DsnOdeOpts* o, DsnOdeStats* stats, void* stream) {
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->status = -1;
+  }
+  return guarded(ctx, [&] {
+    if (!y || !x_out || !o || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_ode_sample: bad arguments");
+    if (o->method != DSN_ODE_RK45 && o->method != DSN_ODE_RK23)
+      fail(DSN_EINVAL, "dsn_ode_sample: method %d is neither DSN_ODE_RK45 nor DSN_ODE_RK23", o->method);
+    if (!(o->t_eps > 0 && o->t_eps < 1)) fail(DSN_EINVAL, "dsn_ode_sample: t_eps must lie in (0, 1)");
+    if (!(o->rtol > 0) || !(o->atol >= 0) || std::isnan(o->max_step))
+      fail(DSN_EINVAL, "dsn_ode_sample: need rtol > 0, atol >= 0 and a max_step that is not NaN");
+    if (o->max_attempts <= 0) fail(DSN_EINVAL, "dsn_ode_sample: max_attempts must be positive");
+    if (o->denoise && o->N <= 0) fail(DSN_EINVAL, "dsn_ode_sample: denoise needs N > 0");
+    const double interval = 1.0 - o->t_eps;
+    const float t_eps32 = (float)o->t_eps;
+    if (!(o->first_step >= 0 && o->first_step <= interval))   // (NaN fails too)
+      fail(DSN_EINVAL, "dsn_ode_sample: first_step must lie in (0, 1 - t_eps] (0 = automatic)");
+    if (!ctx->finalized) fail(DSN_ESTATE, "weights not finalized");
+    const dsn_config& cfg = ctx->cfg;
+    const int n = cfg.n_src, Dl = cfg.latent_dim;
+    const long ysz = (long)B * Dl * T, sz = ysz * n;
+    const OdeTableau tab = ode_tableau(o->method);
+    const int S = tab.stages;
+    OdeSde q;
+    q.theta = cfg.sde_theta;
+    q.sigma_min = cfg.sde_sigma_min;
+    q.ratio = (double)cfg.sde_sigma_max / (double)cfg.sde_sigma_min;
+    q.logratio = log(q.ratio);
+    const bool auto_h = o->first_step == 0;
+    // rtol below 100 eps is raised to it (scipy common.validate_tol)
+    const double rtol = std::max(o->rtol, 100 * 2.220446049250313e-16);
+
+    hipStream_t caller = (hipStream_t)stream;
+    float* yb = ctx->wsbuf<float>("ode_ymix", ysz);
+    float* nz = ctx->wsbuf<float>("ode_noise", sz);
+    double* ys = ctx->wsbuf<double>("ode_y", sz);
+    double* yn = ctx->wsbuf<double>("ode_ynew", sz);
+    double* xs64 = ctx->wsbuf<double>("ode_xs64", sz);
+    double* K = ctx->wsbuf<double>("ode_K", (long)(S + 1) * sz);
+    float* xs32 = ctx->wsbuf<float>("ode_xs32", sz);
+    float* xo = ctx->wsbuf<float>("ode_out", sz);
+    float* zero = o->denoise ? ctx->wsbuf<float>("ode_zero", sz) : nullptr;
+    float* tv = ctx->wsbuf<float>("ode_t", B);
+    double* part = ctx->wsbuf<double>("ode_part", 2L * ode_grid(sz));
+    OdeCtl* ctl = ctx->wsbuf<OdeCtl>("ode_ctl", 1);
+    if (!ctx->ode_host) HIPCHK(hipHostMalloc((void**)&ctx->ode_host, sizeof(OdeCtl), hipHostMallocDefault));
+    OdeCtl* hc = ctx->ode_host;
+    memset(hc, 0, sizeof *hc);
+    hc->t = 1.0;
+    hc->t_bound = o->t_eps;
+    hc->direction = -1.0;
+    hc->max_step = (o->max_step > 0) ? o->max_step : INFINITY;
+    hc->first_step = o->first_step;
+    hc->rtol = rtol;
+    hc->atol = o->atol;
+    hc->status = -1;
+    hc->max_attempts = o->max_attempts;
+
+    hipStream_t st = ctx->enter(caller);
+    HIPCHK(hipMemcpyAsync(ctl, hc, sizeof(OdeCtl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
+    if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    else launch_randn(nz, sz, seed, 0, st);  // draw 0 of the stream dsn_pc_sample uses: the same x_T for a seed
+    const float stdT = ctx->ouve_std(1.f);
+    char key[160];
+    // prior, f0 = fun(t0, y0) and the initial step (scipy select_initial_step: one more evaluation)
+    snprintf(key, sizeof key, "ode_init:%d:%d:%d:%d", B, T, o->method, (int)auto_h);
+    ctx->run_graphed(key, st, [&](hipStream_t s2) {
+      launch_ode_prior(yb, nz, ys, xs32, tv, stdT, B, n, Dl, T, s2);
+      const float* sc = ctx->score_tokens(xs32, tv, yb, B, T, s2);
+      launch_ode_init_f0(q, ctl, yb, sc, ys, K, part, B, n, Dl, T, s2);
+      launch_ode_init_h0(ctl, part, sz, s2);
+      if (auto_h) {
+        launch_ode_init_y1(ctl, ys, K, xs64, xs32, tv, B, sz, s2);
+        sc = ctx->score_tokens(xs32, tv, yb, B, T, s2);
+        launch_ode_init_f1(q, ctl, yb, sc, ys, K, xs64, part, B, n, Dl, T, s2);
+        launch_ode_init_h1(ctl, part, sz, tab.err_order, s2);
+      }
+    });
+    // step attempts: one launch sequence, replayed until the controller sets `done` (polled after every attempt)
+    snprintf(key, sizeof key, "ode_step:%d:%d:%d", B, T, o->method);
+    for (int k = 0;; ++k) {
+      ctx->run_graphed(key, st, [&](hipStream_t s2) {
+        launch_ode_prep(tab, ctl, ys, yn, K, xs64, xs32, tv, B, sz, s2);
+        for (int i = 1; i <= S; ++i) {
+          const float* sc = ctx->score_tokens(xs32, tv, yb, B, T, s2);
+          launch_ode_stage(tab, q, ctl, i, yb, sc, ys, yn, K, xs64, xs32, tv, part, B, n, Dl, T, s2);
+        }
+        launch_ode_control(ctl, part, sz, S, tab.err_order, s2);
+      });
+      HIPCHK(hipMemcpyAsync(hc, ctl, sizeof(OdeCtl), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (hc->done) break;
+      if (k + 1 >= o->max_attempts) {  // the controller stops at max_attempts: not reached unless the state is corrupt
+        ctx->leave(caller, st);
+        fail(DSN_ESOLVER, "dsn_ode_sample: the solver did not stop after max_attempts = %d attempts", o->max_attempts);
+      }
+    }
+    if (stats) {
+      stats->nfev = hc->nfev;
+      stats->n_accepted = hc->accepted;
+      stats->n_rejected = hc->rejected;
+      stats->t_final = hc->t;
+      stats->status = hc->status;
+    }
+    if (hc->status == DSN_ODE_STEP_TOO_SMALL) {
+      ctx->leave(caller, st);
+      fail(DSN_ESOLVER, "dsn_ode_sample: required step size is less than spacing between numbers (t = %.17g, h = %g)",
+           hc->t, hc->h_abs);
+    }
+    if (hc->status == DSN_ODE_TOO_MANY_ATTEMPTS) {
+      ctx->leave(caller, st);
+      fail(DSN_ESOLVER, "dsn_ode_sample: t = %.17g not reached after max_attempts = %d step attempts (%d accepted)",
+           hc->t, hc->attempts, hc->accepted);
+    }
+    // final state (fp32), then the optional noise-free reverse-diffusion step at t_eps (dt = 1/N)
+    const float dt = o->denoise ? (float)(1.0 / o->N) : 0.f;
+    const double smin = cfg.sde_sigma_min, smax = cfg.sde_sigma_max, ls = log(smax / smin);
+    const float sigma = (float)smin * powf((float)(smax / smin), t_eps32);
+    const float G = sigma * (float)sqrt(2.0 * ls) * sqrtf(dt);
+    snprintf(key, sizeof key, "ode_out:%d:%d:%d:%a:%a", B, T, o->denoise, t_eps32, dt);
+    ctx->run_graphed(key, st, [&](hipStream_t s2) {
+      launch_ode_emit(ctl, ys, yn, xo, tv, t_eps32, B, sz, s2);
+      if (o->denoise) {
+        const float* sc = ctx->score_tokens(xo, tv, yb, B, T, s2);
+        // pc_predictor_kernel itself with z = 0: x_mean -> xs32 (x <- x_mean + G * 0 in xo)
+        HIPCHK(hipMemsetAsync(zero, 0, sizeof(float) * sz, s2));
+        launch_pc_predictor(xo, xs32, yb, sc, zero, cfg.sde_theta, dt, G, 0.f, 0, B, n, Dl, T, s2);
+      }
+    });
+    HIPCHK(hipMemcpyAsync(x_out, o->denoise ? xs32 : xo, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
     ctx->leave(caller, st);
     HIPCHK(hipGetLastError());
   });

@@ -144,3 +144,51 @@ void launch_stoi_resample(const float* ref, const float* est, const int* ymap, i
 void launch_stoi_frames(const float* xs, const float* ys, long stride, const int* ymap, int items, int F,
                         StoiBands bands, int extended, double* en, int* idx, int* Kc, double* tob, double* part,
                         double* score, int* frames, hipStream_t s);
+
+// ---- probability-flow ODE sampler (ode.hip) ---------------------------------------------------------------
+// Explicit embedded Runge-Kutta pair with scipy 1.15's solve_ivp step control on the fp64 state y [B,n,D,T].
+// Stages: K[0] = f(t, y), K[1 .. stages-1] the intermediate stages, K[stages] = f(t + h, y_new) (FSAL); K holds
+// stages + 1 rows of `total` doubles.
+#define DSN_ODE_MAX_ROWS 7
+struct OdeTableau {
+  int stages;                                          // 6 (RK45), 3 (RK23)
+  int err_order;                                       // error-estimator order: 4 (RK45), 2 (RK23)
+  double a[DSN_ODE_MAX_ROWS][DSN_ODE_MAX_ROWS];        // a[i][j], j < i < stages
+  double b[DSN_ODE_MAX_ROWS];                          // [stages]
+  double c[DSN_ODE_MAX_ROWS];                          // [stages]
+  double e[DSN_ODE_MAX_ROWS];                          // [stages + 1]
+};
+// OUVE parameters of the drift theta (y - x) - 1/2 g(t)^2 s, g(t)^2 = (sigma_min ratio^t)^2 2 log(ratio)
+struct OdeSde {
+  double theta, sigma_min, ratio, logratio;
+};
+// solver state in device memory (written by the one-thread controller kernels only)
+struct OdeCtl {
+  double t, t_new, h, h_abs, min_step, t_bound, direction, max_step, first_step, rtol, atol, h0, d1;
+  int step_rejected, accept_pending, done, status;     // status: DSN_ODE_* (include/ditsep_hip.h), -1 running
+  int nfev, accepted, rejected, attempts, max_attempts;
+};
+int ode_grid(long total);   // workgroups of the grid kernels = number of error-norm partials
+// prior x_T = y + stdT z by launch_pc_prior itself -> xs32 (score input), widened to y64 (fp64 state); tv [B] = 1
+void launch_ode_prior(const float* ymix, const float* z, double* y, float* xs32, float* tv, float stdT, int B, int n,
+                      int D, int T, hipStream_t s);
+// select_initial_step (scipy common.py): f0 -> K0 and the d0 / d1 partials; h0; y1 = y0 + h0 dir f0; f1 partials; h1
+void launch_ode_init_f0(const OdeSde& q, const OdeCtl* ctl, const float* ymix, const float* sc, const double* y,
+                        double* K0, double* part, int B, int n, int D, int T, hipStream_t s);
+void launch_ode_init_h0(OdeCtl* ctl, const double* part, long total, hipStream_t s);
+void launch_ode_init_y1(const OdeCtl* ctl, const double* y, const double* K0, double* xs64, float* xs32, float* tv,
+                        int B, long total, hipStream_t s);
+void launch_ode_init_f1(const OdeSde& q, const OdeCtl* ctl, const float* ymix, const float* sc, const double* y,
+                        const double* K0, const double* xs64, double* part, int B, int n, int D, int T, hipStream_t s);
+void launch_ode_init_h1(OdeCtl* ctl, const double* part, long total, int err_order, hipStream_t s);
+// one attempt: prep (apply the last acceptance, first stage point), then per stage `st` = 1 .. stages the score call
+// on xs32 / tv followed by launch_ode_stage(st), then launch_ode_control.  Every kernel is a no-op once ctl->done.
+void launch_ode_prep(const OdeTableau& tab, const OdeCtl* ctl, double* y, const double* yn, double* K, double* xs64,
+                     float* xs32, float* tv, int B, long total, hipStream_t s);
+void launch_ode_stage(const OdeTableau& tab, const OdeSde& q, const OdeCtl* ctl, int stage, const float* ymix,
+                      const float* sc, const double* y, double* yn, double* K, double* xs64, float* xs32, float* tv,
+                      double* part, int B, int n, int D, int T, hipStream_t s);
+void launch_ode_control(OdeCtl* ctl, const double* part, long total, int stages, int err_order, hipStream_t s);
+// final state as fp32 -> out; tv = t_eps (the denoising step is launch_pc_predictor with zero noise: its x_mean)
+void launch_ode_emit(const OdeCtl* ctl, const double* y, const double* yn, float* out, float* tv, float t_eps, int B,
+                     long total, hipStream_t s);

@@ -239,6 +239,37 @@ class LatentDiffSep:
 
         return batched_sampling_fn
 
+    def get_ode_sampler(self, y, N=None, minibatch=1, **kwargs):
+        """reference src/diffsep.py:697-725: the probability-flow ODE sampler (sdes.get_ode_sampler) with this model's
+        SDE (N: the denoising step's dt = 1/N) and t_eps.  minibatch=None: the whole batch under one step-size
+        controller; an integer splits the batch into independently integrated minibatches and returns
+        (x, [nfe per minibatch]).  An explicit `seed` is offset by the minibatch index, as in get_pc_sampler;
+        `noise` [B,n,D,T] is sliced per minibatch."""
+        N = self.sde.N if N is None else N
+        sde = self.sde.copy()
+        sde.N = N
+        kwargs = {"eps": self.t_eps, "n_spkrs": self.n_src, **kwargs}
+        if minibatch is None:
+            return sdes.get_ode_sampler(sde, self, y=y, **kwargs)
+        M = y.shape[0]
+        noise = kwargs.pop("noise", None)
+        if noise is not None and noise.dim() == 5:
+            noise = noise[0]
+        seed = kwargs.pop("seed", None)
+
+        def batched_sampling_fn():
+            samples, ns = [], []
+            for i in range(int(math.ceil(M / minibatch))):
+                sl = slice(i * minibatch, (i + 1) * minibatch)
+                sampler = sdes.get_ode_sampler(sde, self, y=y[sl], noise=None if noise is None else noise[sl],
+                                               seed=None if seed is None else int(seed) + i, **kwargs)
+                s, n = sampler()
+                samples.append(s)
+                ns.append(n)
+            return torch.cat(samples, dim=0), ns
+
+        return batched_sampling_fn
+
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, **kwargs):
         if not latent:

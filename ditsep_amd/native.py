@@ -7,6 +7,7 @@ fallback: if the library is missing or a call fails, a RuntimeError is raised.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import warnings
 from typing import Mapping, Optional
@@ -31,7 +32,7 @@ EXPORTS = [
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
     "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
-    "dsn_stoi",
+    "dsn_stoi", "dsn_ode_sample",
 ]
 
 
@@ -55,6 +56,22 @@ class DsnMixOpts(C.Structure):
     ]
 
 
+class DsnOdeOpts(C.Structure):
+    _fields_ = [
+        ("method", C.c_int), ("rtol", C.c_double), ("atol", C.c_double), ("t_eps", C.c_double), ("denoise", C.c_int),
+        ("N", C.c_int), ("first_step", C.c_double), ("max_step", C.c_double), ("max_attempts", C.c_int),
+    ]
+
+
+class DsnOdeStats(C.Structure):
+    _fields_ = [
+        ("nfev", C.c_int), ("n_accepted", C.c_int), ("n_rejected", C.c_int), ("t_final", C.c_double),
+        ("status", C.c_int),
+    ]
+
+
+ODE_METHODS = {"RK45": 0, "RK23": 1}
+ODE_STATUS = {-1: "running", 0: "finished", 1: "step size too small", 2: "max_attempts reached"}
 MIX_CORRECTORS = {"ald2": 0, "none": 1}
 SB_TYPES = {"sde": 0, "ode": 1}
 
@@ -134,6 +151,8 @@ def load_library() -> C.CDLL:
                                      C.POINTER(ci), vp]
     lib.dsn_pc_sample_mix.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, C.POINTER(DsnMixOpts), C.POINTER(ci), vp]
     lib.dsn_sb_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, cf, cf, cf, cf, ci, vp]
+    lib.dsn_ode_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, C.POINTER(DsnOdeOpts), C.POINTER(DsnOdeStats),
+                                   vp]
     lib.dsn_decode.argtypes = [vp, vp, vp, ci, ci, ci, vp]
     lib.dsn_encode.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, vp]
     lib.dsn_decode_chunked.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
@@ -338,6 +357,35 @@ class Engine:
                                            float(sb_eps), float(t_eps), SB_TYPES[sampler_type], self._stream()),
                     "dsn_sb_sample")
         return x
+
+    def ode_sample(self, y, noise=None, *, method="RK45", rtol=1e-5, atol=1e-5, t_eps=0.03, denoise=True, N=30,
+                   first_step=None, max_step=math.inf, max_attempts=1000, seed=0, return_stats=False):
+        """Probability-flow ODE sampler (reference get_ode_sampler) on the latent state: y [B,1,D,T] ->
+        (x [B,n,D,T], nfev) with scipy solve_ivp's RK45 / RK23 step control on the device.  noise: the prior's
+        standard normals [B,n,D,T] (or [1,B,n,D,T], draw 0 of pc_sample's layout), else the device RNG (`seed`).
+        A step size underflow or more than `max_attempts` step attempts raise RuntimeError.  return_stats: also
+        return {nfev, n_accepted, n_rejected, t_final, status}."""
+        if method not in ODE_METHODS:
+            raise NotImplementedError(f"no native ODE solver {method!r}; implemented: {sorted(ODE_METHODS)}")
+        y = _dev32(y, self.device)
+        B, _, D, T = y.shape
+        if noise is not None:
+            noise = _dev32(noise, self.device)
+            if noise.dim() == 5 and noise.shape[0] == 1:
+                noise = noise[0].contiguous()
+            assert tuple(noise.shape) == (B, self.n_src, D, T), noise.shape
+        x = torch.empty((B, self.n_src, D, T), device=self.device, dtype=torch.float32)
+        o = DsnOdeOpts(ODE_METHODS[method], float(rtol), float(atol), float(t_eps), int(bool(denoise)), int(N),
+                       0.0 if first_step is None else float(first_step),
+                       0.0 if max_step is None or math.isinf(max_step) else float(max_step), int(max_attempts))
+        st = DsnOdeStats()
+        rc = self.lib.dsn_ode_sample(self.ctx, _ptr(y), _ptr(noise), seed, _ptr(x), B, T, C.byref(o), C.byref(st),
+                                     self._stream())
+        self._check(rc, "dsn_ode_sample")
+        if return_stats:
+            return x, st.nfev, {"nfev": st.nfev, "n_accepted": st.n_accepted, "n_rejected": st.n_rejected,
+                                "t_final": st.t_final, "status": ODE_STATUS.get(st.status, st.status)}
+        return x, st.nfev
 
     def decode(self, est, target_len: Optional[int] = None, chunked: bool = False, overlap: int = 32,
                chunk_size: int = 128):

@@ -200,6 +200,71 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=N
     return pc_sampler
 
 
+ODE_METHODS = ("RK45", "RK23")
+_SOLVE_IVP_METHODS = ("RK23", "RK45", "DOP853", "Radau", "BDF", "LSODA")
+_ODE_KWARGS = ("first_step", "max_step", "max_attempts")
+
+
+def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
+                    device="cuda", n_spkrs=2, noise=None, seed=None, **kwargs):
+    """Reference signature and defaults (src/sdes/__init__.py:196-281): returns `ode_sampler(z=None) -> (x, nfe)`.
+    The probability-flow ODE dx/dt = theta (y - x) - 1/2 g(t)^2 score is integrated from T = 1 to `eps` on the device
+    (dsn_ode_sample) with solve_ivp's RK45 / RK23 step control, then optionally denoised by one noise-free
+    reverse-diffusion step; nfe is solve_ivp's nfev.  `score_fn` must be a native-backed model (`.engine`).  Extra
+    keywords: `noise` (the prior's standard normals [B,n,D,T]) and `seed` (on-device Philox, the PC sampler's prior
+    draw for the same seed), and of solve_ivp's options `first_step`, `max_step` and `max_attempts` (attempt limit:
+    exceeding it raises).  Deviations, stated: a real-valued state with n_spkrs sources (the reference casts to
+    complex64 and draws the prior in y's one-source shape), and a step-size underflow raises RuntimeError where
+    solve_ivp returns success=False and the reference uses the last state."""
+    if method not in _SOLVE_IVP_METHODS:   # what solve_ivp itself raises for a name it does not know
+        raise ValueError(f"`method` must be one of {_SOLVE_IVP_METHODS} or OdeSolver class.")
+    if method not in ODE_METHODS:
+        raise NotImplementedError(f"ODE method '{method}': the native solver implements {', '.join(ODE_METHODS)}")
+    unsupported = sorted(k for k in kwargs if k not in _ODE_KWARGS)
+    if unsupported:
+        raise NotImplementedError(f"solve_ivp options {unsupported} are not implemented natively; the native solver "
+                                  f"takes rtol, atol, method and {', '.join(_ODE_KWARGS)}")
+    engine = getattr(score_fn, "engine", None)
+    if engine is None:
+        raise NotImplementedError("get_ode_sampler needs a native score model (object with `.engine`); "
+                                  "arbitrary Python score functions are not supported (no PyTorch fallback)")
+    if not isinstance(sde, OUVESDE):
+        raise NotImplementedError("the native ODE sampler implements the probability-flow ODE of OUVESDE only")
+    if n_spkrs != engine.n_src:
+        raise ValueError(f"n_spkrs={n_spkrs} but the engine was built for {engine.n_src} sources")
+    if (abs(sde.theta - engine.cfg.sde_theta) > 1e-6 or abs(sde.sigma_min - engine.cfg.sde_sigma_min) > 1e-6
+            or abs(sde.sigma_max - engine.cfg.sde_sigma_max) > 1e-6):
+        raise ValueError("sde parameters differ from the ones the engine was built with")
+    if not (0 < eps < sde.T):
+        raise ValueError(f"eps={eps} must lie in (0, {sde.T})")
+    if not rtol > 0 or atol < 0:
+        raise ValueError("rtol must be positive and atol non-negative")
+    first_step = kwargs.get("first_step")
+    if first_step is not None and not (0 < first_step <= sde.T - eps):
+        raise ValueError("`first_step` must be positive and must not exceed the interval (T - eps)")
+    max_step = kwargs.get("max_step", math.inf)
+    if max_step is None or not max_step > 0:
+        raise ValueError("`max_step` must be positive.")
+    max_attempts = int(kwargs.get("max_attempts", 1000))
+    if max_attempts <= 0:
+        raise ValueError("`max_attempts` must be positive")
+    counter = {"calls": 0}
+
+    def ode_sampler(z=None, **kw):
+        """z: the prior's standard normals (overrides `noise`)."""
+        s = seed if seed is not None else int(torch.randint(0, 2**31 - 1, (1,)).item()) + counter["calls"]
+        counter["calls"] += 1
+        nz = z if z is not None else noise
+        x, nfe = engine.ode_sample(y, nz, method=method, rtol=float(rtol), atol=float(atol), t_eps=float(eps),
+                                   denoise=bool(denoise), N=sde.N, first_step=first_step, max_step=max_step,
+                                   max_attempts=max_attempts, seed=s)
+        if inverse_scaler is not None:
+            x = inverse_scaler(x)
+        return x, nfe
+
+    return ode_sampler
+
+
 def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", pad_dim=None, noise=None, seed=None,
                    **kwargs):
     """Reference signature (src/sdes/__init__.py:284-389).  `model` must be a native-backed model (`.engine`); its

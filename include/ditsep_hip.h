@@ -28,6 +28,7 @@ extern "C" {
 #define DSN_EHIP (-2)     /* HIP runtime error                                     */
 #define DSN_ESTATE (-3)   /* weights missing / not finalized                       */
 #define DSN_ENOMEM (-4)
+#define DSN_ESOLVER (-5)  /* dsn_ode_sample: step size underflow or attempt limit      */
 
 #define DSN_PREC_BF16 1    /* bf16 MFMA operands, fp32 accumulate                  */
 #define DSN_PREC_BF16X3 2  /* split-bf16 (hi,lo) operands: 3 bf16 MFMAs per product */
@@ -162,6 +163,42 @@ int dsn_pc_sample_mix(dsn_ctx* ctx, const float* y, const float* noise, uint64_t
 enum { DSN_SB_SDE = 0, DSN_SB_ODE = 1 };
 int dsn_sb_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T, int N, float k,
                   float c, float sb_eps, float t_eps, int sampler_type, void* stream);
+
+/* ode_sampler() of sdes.get_ode_sampler (src/sdes/__init__.py:196-281): the probability-flow ODE
+ *   dx/dt = theta (y - x) - 1/2 g(t)^2 score(x, t, y)
+ * integrated from t = 1 down to t_eps by an explicit embedded Runge-Kutta pair with the step control of
+ * scipy 1.15's solve_ivp(method = "RK45" | "RK23", rtol, atol, first_step, max_step): one step size for the whole
+ * batch (the RMS error norm runs over the flattened [B,n_src,D,T] state), one score call per stage.  The state and the
+ * stages are fp64, the score network reads their fp32 cast.  The prior is y broadcast over the n_src sources plus
+ * std(1) z -- z = noise [B,n_src,D,T] or draw 0 of the on-device stream for `seed` -- drawn by dsn_pc_sample's own
+ * prior kernel, so the same noise or seed gives bit for bit the x_T dsn_pc_sample starts from.  denoise != 0: one
+ * noise-free reverse-diffusion step at t_eps with dt = 1/N, the PC sampler's predictor kernel with zero noise (not
+ * counted in nfev, as in the reference).  Deviations from the reference, stated: the state is real (not complex64) and has n_src sources (the
+ * reference draws the prior in y's one-source shape); where solve_ivp would return success=False (step size below
+ * 10 ulp of t) this call fails with DSN_ESOLVER, and so it does after max_attempts step attempts.  Either failure is
+ * reported by this call after it synchronised its stream; stats (may be NULL) are filled in every case.
+ * first_step == 0: scipy's select_initial_step (one extra evaluation); max_step <= 0 or inf: unbounded.  Under
+ * dsn_enable_graphs one step attempt is captured once per (B, T, method) and replayed. */
+enum { DSN_ODE_RK45 = 0, DSN_ODE_RK23 = 1 };
+enum { DSN_ODE_FINISHED = 0, DSN_ODE_STEP_TOO_SMALL = 1, DSN_ODE_TOO_MANY_ATTEMPTS = 2 };
+typedef struct DsnOdeOpts {
+  int method;                         /* DSN_ODE_RK45 | DSN_ODE_RK23 */
+  double rtol, atol;
+  double t_eps;                       /* the ODE runs from 1 to t_eps; the denoising step uses (float)t_eps */
+  int denoise;
+  int N;                              /* sde.N: dt = 1/N of the denoising step */
+  double first_step;                  /* 0 = automatic, else in (0, 1 - t_eps] */
+  double max_step;                    /* <= 0 or inf = unbounded */
+  int max_attempts;                   /* > 0 */
+} DsnOdeOpts;
+typedef struct DsnOdeStats {
+  int nfev;                           /* scipy's count: 1 + (1 if first_step is automatic) + stages x attempts */
+  int n_accepted, n_rejected;
+  double t_final;
+  int status;                         /* DSN_ODE_* */
+} DsnOdeStats;
+int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
+                   const DsnOdeOpts* o, DsnOdeStats* stats, void* stream);
 
 /* LatentDiffSep.decode: est [B,n_src,D,T] -> wav [B,n_src,target_len] (crop of hop*T;
  * target_len <= 0 means hop*T). */
