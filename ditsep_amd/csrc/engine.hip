@@ -2318,6 +2318,97 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
   });
 }
 
+int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t, const float* noise,
+                   const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out, float* t_out, float* sigma_out,
+                   float* z_out, int B, int T, const DsnLossOpts* o, void* stream) {
+  return guarded(ctx, [&] {
+    if (!y || !x0 || !o || B <= 0 || T <= 0 || B > 65535) fail(DSN_EINVAL, "dsn_score_loss: bad arguments");
+    if (o->mode != DSN_LOSS_DSM && o->mode != DSN_LOSS_INIT_PIT)
+      fail(DSN_EINVAL, "dsn_score_loss: mode %d is neither DSN_LOSS_DSM nor DSN_LOSS_INIT_PIT", o->mode);
+    if (o->reduction != DSN_LOSS_REDUCE_NONE && o->reduction != DSN_LOSS_REDUCE_MEAN)
+      fail(DSN_EINVAL, "dsn_score_loss: unknown reduction %d", o->reduction);
+    const bool pit = o->mode == DSN_LOSS_INIT_PIT;
+    if (pit && (t || perm)) fail(DSN_EINVAL, "dsn_score_loss: DSN_LOSS_INIT_PIT fixes t = 1 and takes no t / perm");
+    if (!pit && !t && !(o->t_eps > 0 && o->t_eps < 1)) fail(DSN_EINVAL, "dsn_score_loss: t_eps must lie in (0, 1)");
+    const dsn_config& cfg = ctx->cfg;
+    const int n = cfg.n_src, Dl = cfg.latent_dim;
+    if (n > 4) fail(DSN_EINVAL, "dsn_score_loss: n_src = %d (at most 4 sources)", n);
+    if (loss_out && !ctx->finalized) fail(DSN_ESTATE, "weights not finalized");
+    const long DT = (long)Dl * T, ysz = (long)B * DT, sz = ysz * n;
+    hipStream_t caller = (hipStream_t)stream;
+    // injected t / perm: checked on the host before anything is launched
+    if (t || perm) {
+      HIPCHK(hipStreamSynchronize(caller));
+      if (t) {
+        std::vector<float> ht((size_t)B);
+        HIPCHK(hipMemcpy(ht.data(), t, sizeof(float) * B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+          if (!(ht[b] > 0.f && ht[b] <= 1.f))
+            fail(DSN_EINVAL, "dsn_score_loss: t[%d] = %g lies outside (0, 1]", b, ht[b]);
+      }
+      if (perm) {
+        std::vector<int32_t> hp((size_t)B * n);
+        HIPCHK(hipMemcpy(hp.data(), perm, sizeof(int32_t) * hp.size(), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) {
+          unsigned seen = 0;
+          for (int s = 0; s < n; ++s) {
+            const int32_t v = hp[(size_t)b * n + s];
+            if (v < 0 || v >= n || (seen >> v & 1u))
+              fail(DSN_EINVAL, "dsn_score_loss: perm row %d is not a permutation of 0..%d", b, n - 1);
+            seen |= 1u << v;
+          }
+        }
+      }
+    }
+    LossSde q;
+    q.theta = cfg.sde_theta;
+    q.sigma_min = cfg.sde_sigma_min;
+    q.logsig = log((double)cfg.sde_sigma_max / (double)cfg.sde_sigma_min);
+    const int nj = pit ? n : 1, chunks = loss_chunks(Dl, T);
+    // stable workspace copies of the caller's tensors (graph replay needs fixed pointers)
+    float* yb = ctx->wsbuf<float>("loss_y", ysz);
+    float* xb = ctx->wsbuf<float>("loss_x0", sz);
+    float* nz = ctx->wsbuf<float>("loss_z", sz);
+    float* xt = ctx->wsbuf<float>("loss_xt", sz);
+    float* tin = ctx->wsbuf<float>("loss_tin", B);
+    float* tv = ctx->wsbuf<float>("loss_t", B);
+    float* sg = ctx->wsbuf<float>("loss_sigma", B);
+    int* pb = ctx->wsbuf<int>("loss_perm", (long)B * n);
+    double* part = ctx->wsbuf<double>("loss_part", (long)B * n * n * chunks);
+    double* rows = ctx->wsbuf<double>("loss_rows", (long)B * n);
+    float* lo = ctx->wsbuf<float>("loss_out", (long)B * n);
+    hipStream_t st = ctx->enter(caller);
+    HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(xb, x0, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    else launch_randn(nz, sz, seed, 0, st);  // draw 0 of the stream the samplers use
+    if (t) HIPCHK(hipMemcpyAsync(tin, t, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+    else if (!pit) launch_rand_uniform(tin, B, seed ^ 0x9E3779B97F4A7C15ULL, 0, o->t_eps, 1.f, st);
+    if (perm) HIPCHK(hipMemcpyAsync(pb, perm, sizeof(int) * B * n, hipMemcpyDeviceToDevice, st));
+    char key[160];
+    snprintf(key, sizeof key, "loss:%d:%d:%d:%d:%d:%d", B, T, o->mode, o->reduction, perm != nullptr,
+             loss_out != nullptr);
+    ctx->run_graphed(key, st, [&](hipStream_t s2) {
+      launch_loss_perturb(q, yb, xb, nz, pit ? nullptr : tin, 1.f, perm ? pb : nullptr, pit, xt, tv, sg, B, n, Dl, T,
+                          s2);
+      if (!loss_out) return;
+      const float* sc = ctx->score_tokens(xt, tv, yb, B, T, s2);
+      launch_loss_reduce(q, sc, nz, yb, xb, tv, sg, pit, part, B, n, Dl, T, s2);
+      launch_loss_combine(part, rows, lo, B, n, nj, chunks, DT, o->reduction == DSN_LOSS_REDUCE_MEAN, s2);
+    });
+    if (loss_out) {
+      const long cnt = o->reduction == DSN_LOSS_REDUCE_MEAN ? 1 : (long)B * n;
+      HIPCHK(hipMemcpyAsync(loss_out, lo, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
+    }
+    if (xt_out) HIPCHK(hipMemcpyAsync(xt_out, xt, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    if (t_out) HIPCHK(hipMemcpyAsync(t_out, tv, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+    if (sigma_out) HIPCHK(hipMemcpyAsync(sigma_out, sg, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+    if (z_out) HIPCHK(hipMemcpyAsync(z_out, nz, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
+    ctx->leave(caller, st);
+    HIPCHK(hipGetLastError());
+  });
+}
+
 int dsn_hop_length(const dsn_ctx* ctx) { return ctx ? ctx->hop() : DSN_EINVAL; }
 
 int dsn_latent_frames(const dsn_ctx* ctx, int L) {

@@ -192,3 +192,30 @@ void launch_ode_control(OdeCtl* ctl, const double* part, long total, int stages,
 // final state as fp32 -> out; tv = t_eps (the denoising step is launch_pc_predictor with zero noise: its x_mean)
 void launch_ode_emit(const OdeCtl* ctl, const double* y, const double* yn, float* out, float* tv, float t_eps, int B,
                      long total, hipStream_t s);
+
+// ---- denoising score-matching loss (loss.hip) ---------------------------------------------------------------
+// out[b] = lo + (hi - lo) u_b, clamped to hi; u_b = ((w >> 8) + 0.5) / 2^24 with w word 0 of the Philox4x32-10 block
+// of counter b + offset under key `seed` (randn_kernel's generator, kernels.hip)
+void launch_rand_uniform(float* out, long n, unsigned long long seed, unsigned long long offset, float lo, float hi,
+                         hipStream_t s);
+// OUVE marginal of x(t): mean = e x0 + (1 - e) y, e = exp(-theta t); sigma = OUVESDE._std(t)
+struct LossSde {
+  double theta, sigma_min, logsig;
+};
+#define DSN_LOSS_CHUNK 2048   // elements of one (item, source) row a workgroup sums
+inline int loss_chunks(int D, int T) { return (int)(((long)D * T + DSN_LOSS_CHUNK - 1) / DSN_LOSS_CHUNK); }
+// perturb, one launch over [B,n,D,T]:  pit = 0: x_t = (e x0[b, perm[b,s]] + (1 - e) y) + sigma(t_b) z  (perm nullable:
+// identity);  pit = 1: x_t = y + sigma(t_b) z.  Also writes tv [B] = t (the score call's time vector) and sigma [B].
+// t_in nullable: every item at t_const (pit mode: T = 1).
+void launch_loss_perturb(const LossSde& q, const float* y, const float* x0, const float* z, const float* t_in,
+                         float t_const, const int* perm, int pit, float* xt, float* tv, float* sigma, int B, int n,
+                         int D, int T, hipStream_t s);
+// reduce: part[((b n + s) nj + j) chunks + c] = fp64 sum over chunk c of row (b, s) of (sigma s_theta + z_j)^2 with
+// score token-major [B*T][n*D].  pit = 0: nj = 1, z_0 = z.  pit = 1: nj = n, z_j = z + (y - mean(x0[b, j])) / sigma.
+void launch_loss_reduce(const LossSde& q, const float* score_tok, const float* z, const float* y, const float* x0,
+                        const float* tv, const float* sigma, int pit, double* part, int B, int n, int D, int T,
+                        hipStream_t s);
+// combine (one workgroup, fixed order): row[b n + s] = min_j (sum_c part) / (D T); mean_reduction = 0: out [B n] =
+// (float)row, else out [1] = (float)(sum row / (B n)).  rows [B n] fp64 is scratch.
+void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, long DT,
+                         int mean_reduction, hipStream_t s);

@@ -797,6 +797,25 @@ __global__ void randn_kernel(float* __restrict__ out, long n, unsigned long long
   }
 }
 
+// one uniform per counter: out[i] = lo + (hi - lo) u, u from word 0 of block (i + offset) as randn_kernel maps it; the
+// top draw rounds to u = 1, so the value is clamped to hi
+__global__ void rand_uniform_kernel(float* __restrict__ out, long n, unsigned long long seed,
+                                    unsigned long long offset, float lo, float hi) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const unsigned long long ctr = (unsigned long long)i + offset;
+    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+      philox_round(c, k0, k1);
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const float u = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    out[i] = fminf(lo + (hi - lo) * u, hi);
+  }
+}
+
 // ------------------------------------------------------------------ weight packing
 __global__ void wn_scale_kernel(const float* __restrict__ v, const float* __restrict__ g, float* __restrict__ scale,
                                 int R, long inner) {
@@ -1098,6 +1117,10 @@ void launch_vae_sample(const float* enc, const float* noise, float* y, int S, in
 }
 void launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t st) {
   hipLaunchKernelGGL(randn_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, st, out, n, seed, offset);
+}
+void launch_rand_uniform(float* out, long n, unsigned long long seed, unsigned long long offset, float lo, float hi,
+                         hipStream_t st) {
+  hipLaunchKernelGGL(rand_uniform_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, out, n, seed, offset, lo, hi);
 }
 void launch_wn_scale(const float* v, const float* g, float* scale, int R, long inner, hipStream_t st) {
   hipLaunchKernelGGL(wn_scale_kernel, dim3(cdiv(R, 4)), dim3(TPB), 0, st, v, g, scale, R, inner);

@@ -21,9 +21,11 @@ import torch
 
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
-                     stoi: bool = False, stoi_extended: bool = True) -> dict:
+                     stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False) -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
-    with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise."""
+    with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
+    adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
+    call per batch on the encoded targets, t and z from the device stream of the utterance's seed)."""
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
     N = N if N is not None else cfg_s.get("N", model.sde.N)
     corrector_steps = corrector_steps if corrector_steps is not None else cfg_s.get("corrector_steps", 1)
@@ -36,6 +38,12 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
         mix_latent, _ = model.encode(mix, None, seed=seed + idx)
         sampler = model.get_pc_sampler("reverse_diffusion", "ald", mix_latent, N=N, denoise=denoise,
                                        corrector_steps=corrector_steps, snr=snr, seed=seed + idx)
+        sl = None
+        if score_loss:
+            B0, n0 = target.shape[:2]
+            tgt = model.engine.encode(target.reshape(B0 * n0, 1, L), None, seed=seed + idx + 1)
+            sl = model.engine.score_loss(mix_latent, tgt.reshape(B0, n0, *tgt.shape[2:]), reduction="none",
+                                         t_eps=model.t_eps, seed=seed + idx).cpu()
         torch.cuda.synchronize(dev)
         t_s = time.perf_counter()
         x_result, nfe = sampler()
@@ -50,6 +58,8 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                             "si_sar": si_sar[b].tolist(),
                             "pesq": None, "stoi": None if st is None else st[b].tolist(),
                             "nfe": nfe, "runtime": t_proc / B, "len_s": L / fs, "perm": perm[b].tolist()}
+            if sl is not None:
+                results[idx]["score_loss"] = sl[b].tolist()
             idx += 1
     return results
 

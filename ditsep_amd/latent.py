@@ -2,10 +2,12 @@
 
 Mirrors the inference surface of the reference Lightning module
 (reference src/diffsep_latent.py): `encode` :107-118, `decode` :120-128, `forward` :147-148,
-`get_pc_sampler` :406-469, `separate` :471-487, with the same config keys
-(`model.score_model`, `model.vae`, `model.sde`, `model.t_eps`, `model.sampler`,
-`model.n_speakers`) and the same state_dict naming (`score_model.*`, `vae.*`).
-Training, EMA and logging are out of scope.
+`get_pc_sampler` :406-469, `separate` :471-487, and the forward half of its loss code -- `sample_time`,
+`sample_prior`, `compute_score_loss`, `compute_score_loss_init_hack_pit`, `train_step_init_5` :130-208 and
+`validation_step` :251-273 -- with the same config keys (`model.score_model`, `model.vae`, `model.sde`,
+`model.t_eps`, `model.sampler`, `model.n_speakers`, `model.loss`, `model.init_hack`, `model.init_hack_p`,
+`model.valid_max_sep_batches`) and the same state_dict naming (`score_model.*`, `vae.*`).
+Gradients, training, EMA updates and logging are out of scope.
 """
 from __future__ import annotations
 
@@ -51,6 +53,31 @@ def _vae_arch(vae_cfg) -> dict:
                 vae_enc_latent_dim=int(_get(enc, "latent_dim", 128)) if enc is not None else 128,
                 vae_use_snake=bool(_get(src, "use_snake", False)), vae_final_tanh=bool(_get(dec, "final_tanh", True)),
                 vae_has_encoder=enc is not None, vae_has_decoder=dec is not None)
+
+
+def loss_config(config, sde_N: int) -> dict:
+    """The reference's reading of `model.loss`, `model.init_hack` and `model.init_hack_p`
+    (src/diffsep_latent.py:66-67, :79-85) -> {"init_hack", "init_hack_p", "reduction"}.  Only torch.nn.MSELoss has a
+    native reduction kernel: any other `_target_` raises NotImplementedError (no fallback).  A missing `model.loss`
+    reads as MSELoss()."""
+    init_hack = _get(config, "model.init_hack", False)
+    init_hack_p = float(_get(config, "model.init_hack_p", 1.0 / sde_N))
+    loss = _get(config, "model.loss")
+    target = str(_get(loss, "_target_", "torch.nn.MSELoss"))
+    if target not in ("torch.nn.MSELoss", "torch.nn.modules.loss.MSELoss"):
+        raise NotImplementedError(f"model.loss._target_ = '{target}': the native score loss implements "
+                                  "torch.nn.MSELoss only (no PyTorch fallback)")
+    reduction = _get(loss, "reduction")
+    if init_hack in (5, 6, 7):
+        if reduction is None:
+            reduction = "none"
+        elif reduction != "none":
+            raise ValueError("Reduction should 'none' for loss with init_hack == 5")     # reference :83
+    elif reduction is None:
+        reduction = "mean"
+    if reduction not in ("none", "mean"):
+        raise NotImplementedError(f"MSELoss(reduction='{reduction}') has no native kernel (none | mean)")
+    return {"init_hack": init_hack, "init_hack_p": init_hack_p, "reduction": reduction}
 
 
 _PRECISIONS = {"bf16": native.PREC_BF16, "bf16x3": native.PREC_BF16X3, "fp16": native.PREC_FP16,
@@ -112,6 +139,10 @@ class LatentDiffSep:
             self.score_model = None
         self.max_len_lat = 0
         self._finalized = False
+        lc = loss_config(config, self.sde.N)
+        self.init_hack, self.init_hack_p, self.loss_reduction = lc["init_hack"], lc["init_hack_p"], lc["reduction"]
+        self.valid_max_sep_batches = int(_get(config, "model.valid_max_sep_batches", 1))
+        self.n_batches_est_done = 0
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict: bool = True):
@@ -284,6 +315,128 @@ class LatentDiffSep:
         est, *others = sampler()
         est = self.decode(est, target_dim)
         return (est, *others)
+
+    # ------------------------------------------------------------------ score-matching loss (forward only)
+    @staticmethod
+    def _seed(seed):
+        return int(torch.randint(0, 2**31 - 1, (1,)).item()) if seed is None else int(seed)
+
+    def _loss_chunks(self, B, minibatch):
+        mb = B if minibatch is None else int(minibatch)
+        return [slice(i, min(i + mb, B)) for i in range(0, B, mb)]
+
+    def _score_loss(self, mode, reduction, y, x, time, noise, perm, seed, minibatch):
+        """One engine call per minibatch; an explicit seed is offset by the minibatch index (as get_pc_sampler)."""
+        seed = self._seed(seed)
+        outs, sizes = [], []
+        for i, sl in enumerate(self._loss_chunks(y.shape[0], minibatch)):
+            outs.append(self.engine.score_loss(
+                y[sl], x[sl], mode=mode, reduction=reduction, t_eps=self.t_eps, seed=seed + i,
+                time=None if time is None else time[sl], noise=None if noise is None else noise[sl],
+                perm=None if perm is None else perm[sl]))
+            sizes.append(outs[-1].shape[0] if reduction == "none" else sl.stop - sl.start)
+        if len(outs) == 1:
+            return outs[0]
+        if reduction == "none":
+            return torch.cat(outs, dim=0)
+        w = torch.tensor(sizes, device=outs[0].device, dtype=torch.float32)
+        return (torch.stack(outs) * w).sum() / w.sum()
+
+    @torch.no_grad()
+    def sample_time(self, x, seed=None):
+        """reference :130-132: t ~ U(t_eps, T) per item of x [B,n,D,T], from the device stream of `seed` (the t that
+        sample_prior / compute_score_loss draw for the same seed)."""
+        _, aux = self.engine.score_loss(x[:, :1], x, t_eps=self.t_eps, seed=self._seed(seed), loss=False,
+                                        return_aux=True)
+        return aux["t"]
+
+    @torch.no_grad()
+    def sample_prior(self, mix, target, time=None, noise=None, seed=None, perm=None):
+        """reference :134-145 -> (x_t, time, sigma [B,1,1,1], z).  time / noise: injected t [B] and z [B,n,D,T];
+        perm [B,n]: per-item source order of `target` (utils.shuffle_sources' indices)."""
+        _, aux = self.engine.score_loss(mix, target, t_eps=self.t_eps, time=time, noise=noise, perm=perm,
+                                        seed=self._seed(seed), loss=False, return_aux=True)
+        return aux["x_t"], aux["t"], aux["sigma"].reshape(-1, 1, 1, 1), aux["z"]
+
+    @torch.no_grad()
+    def compute_score_loss(self, y, x, time=None, noise=None, seed=None, perm=None, minibatch=None):
+        """reference :154-160 with ONE native call (dsn_score_loss): `loss(score(x_t, t, y) sigma, -z)` followed by
+        the reference's mean over the trailing axes -- a scalar for MSELoss(), **[B, n]** for
+        MSELoss(reduction="none") (the mean runs over (D, T) only; kept as the reference has it)."""
+        return self._score_loss("dsm", self.loss_reduction, y, x, time, noise, perm, seed, minibatch)
+
+    @torch.no_grad()
+    def compute_score_loss_init_hack_pit(self, mix, target, noise=None, seed=None, minibatch=None):
+        """reference :162-187 -> [B, n]: t = T, x_t = mix + sigma z0 and the minimum over all source permutations
+        **per (item, source slot)** (the reference's stack(dim=1).min(dim=1) on [B,n] losses).  The reference calls
+        the network n! times on identical inputs; this makes one call.  With MSELoss() the reference's stack of
+        scalars raises IndexError, and so does this."""
+        if self.loss_reduction != "none":
+            raise IndexError("Dimension out of range: compute_score_loss_init_hack_pit needs "
+                             "MSELoss(reduction='none'), as in the reference")
+        return self._score_loss("init_pit", "none", mix, target, None, noise, None, seed, minibatch)
+
+    @torch.no_grad()
+    def train_step_init_5(self, mix, target, pit_mask=None, perm=None, time=None, noise=None, seed=None,
+                          minibatch=None):
+        """reference :189-208 (forward value only): items with pit_mask go through the PIT variant, the rest through
+        shuffle_sources + compute_score_loss; torch.cat(losses).mean().  pit_mask [B] bool (default: a
+        Bernoulli(init_hack_p) draw), perm [B - n_pit, n] (default: argsort of a uniform draw per item) -- both host
+        draws from torch's generator, seeded by `seed` when given; time [B - n_pit] / noise [B,n,D,T] (z0 of the PIT
+        items, z of the rest) are injected into the engine calls."""
+        if self.loss_reduction != "none":
+            raise ValueError("Reduction should 'none' for loss with init_hack == 5")
+        B, n = target.shape[:2]
+        seed = self._seed(seed)
+        g = torch.Generator().manual_seed(seed)
+        if pit_mask is None:
+            pit_mask = torch.rand(B, generator=g) < self.init_hack_p
+        pit = torch.as_tensor(pit_mask).bool().cpu()
+        n_pit = int(pit.sum())
+
+        def take(a, mask):
+            return None if a is None else a[mask.to(a.device)]
+
+        losses = []
+        if n_pit > 0:
+            losses.append(self._score_loss("init_pit", "none", take(mix, pit), take(target, pit), None,
+                                           take(noise, pit), None, seed, minibatch))
+        if n_pit != B:
+            if perm is None:
+                perm = torch.argsort(torch.rand((B - n_pit, n), generator=g), dim=1)
+            losses.append(self._score_loss("dsm", "none", take(mix, ~pit), take(target, ~pit), time,
+                                           take(noise, ~pit), perm, seed + 7919, minibatch))
+        return torch.cat(losses).mean()
+
+    def on_validation_epoch_start(self):
+        self.n_batches_est_done = 0
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0, dataset_i=0, seed=None, **loss_kwargs):
+        """reference :251-273 as a dict instead of Lightning log calls: encode mix and targets, then
+        "val/score_loss" (train_step_init_5 when init_hack == 5, else compute_score_loss; loss_kwargs are passed
+        on) and, for the first `valid_max_sep_batches` calls since on_validation_epoch_start, "val/si_sdr": the
+        reference's SISDRLoss(zero_mean=false, clamp_db=30, sign_flip=true, reduction=mean) of separate()'s estimate,
+        from the device SI-SDR (dsn_si_sdr_pit).  That number is unpinned, like the other SI-SDR figures of this
+        build: the reference computes it with fast_bss_eval.si_sdr_pit_loss, which is not available to compare with.
+        "val/pesq" is not computed."""
+        mix, target = batch
+        seed = self._seed(seed)
+        y, x = self.encode(mix, target, seed=seed)
+        if self.init_hack == 5:
+            loss = self.train_step_init_5(y, x, seed=seed, **loss_kwargs)
+        else:
+            loss = self.compute_score_loss(y, x, seed=seed, **loss_kwargs)
+        out = {"val/score_loss": loss}
+        if self.n_batches_est_done < self.valid_max_sep_batches:
+            self.n_batches_est_done += 1
+            est, *_ = self.separate(y, latent=True, target_dim=target.shape[-1], seed=seed)
+            si_sdr, _ = self.engine.si_sdr_pit(target, est)
+            out["val/si_sdr"] = si_sdr.clamp(-30.0, 30.0).mean()
+        return out
+
+    def test_step(self, batch, batch_idx=0, dataset_i=None, **kwargs):
+        return self.validation_step(batch, batch_idx, dataset_i=dataset_i, **kwargs)
 
     def close(self):
         self.engine.close()

@@ -32,7 +32,7 @@ EXPORTS = [
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
     "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
-    "dsn_stoi", "dsn_ode_sample",
+    "dsn_stoi", "dsn_ode_sample", "dsn_score_loss",
 ]
 
 
@@ -70,6 +70,12 @@ class DsnOdeStats(C.Structure):
     ]
 
 
+class DsnLossOpts(C.Structure):
+    _fields_ = [("mode", C.c_int), ("reduction", C.c_int), ("t_eps", C.c_float)]
+
+
+LOSS_MODES = {"dsm": 0, "init_pit": 1}
+LOSS_REDUCTIONS = {"none": 0, "mean": 1}
 ODE_METHODS = {"RK45": 0, "RK23": 1}
 ODE_STATUS = {-1: "running", 0: "finished", 1: "step size too small", 2: "max_attempts reached"}
 MIX_CORRECTORS = {"ald2": 0, "none": 1}
@@ -153,6 +159,8 @@ def load_library() -> C.CDLL:
     lib.dsn_sb_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, cf, cf, cf, cf, ci, vp]
     lib.dsn_ode_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, C.POINTER(DsnOdeOpts), C.POINTER(DsnOdeStats),
                                    vp]
+    lib.dsn_score_loss.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, ci, ci,
+                                   C.POINTER(DsnLossOpts), vp]
     lib.dsn_decode.argtypes = [vp, vp, vp, ci, ci, ci, vp]
     lib.dsn_encode.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, vp]
     lib.dsn_decode_chunked.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
@@ -386,6 +394,50 @@ class Engine:
             return x, st.nfev, {"nfev": st.nfev, "n_accepted": st.n_accepted, "n_rejected": st.n_rejected,
                                 "t_final": st.t_final, "status": ODE_STATUS.get(st.status, st.status)}
         return x, st.nfev
+
+    def score_loss(self, y, x0, *, mode="dsm", reduction="none", t_eps=0.03, time=None, noise=None, perm=None, seed=0,
+                   loss=True, return_aux=False):
+        """Denoising score-matching loss with one score call (dsn_score_loss; reference sample_prior +
+        compute_score_loss, or compute_score_loss_init_hack_pit for mode="init_pit").  y [B,1,D,T], x0 [B,n,D,T] ->
+        loss [B,n] (reduction="none") or a scalar tensor ("mean"), float32 on the device.  time [B] in (0, 1], noise
+        [B,n,D,T] and perm [B,n] (slot s of item b holds source perm[b,s]) are injected when given; otherwise t and z
+        come from the device RNG for `seed`.  loss=False: the perturbation only, no score call (loss is None).
+        return_aux=True: (loss, {"x_t", "t", "sigma" [B], "z"})."""
+        if mode not in LOSS_MODES or reduction not in LOSS_REDUCTIONS:
+            raise ValueError(f"mode must be one of {sorted(LOSS_MODES)} and reduction one of {sorted(LOSS_REDUCTIONS)}")
+        y, x0 = _dev32(y, self.device), _dev32(x0, self.device)
+        if y.dim() != 4 or x0.dim() != 4 or y.shape[1] != 1:
+            raise ValueError(f"y must be [B,1,D,T] and x0 [B,n,D,T] (got {tuple(y.shape)} and {tuple(x0.shape)})")
+        B, _, D, T = y.shape
+        if tuple(x0.shape) != (B, self.n_src, D, T) or D != self.latent_dim:
+            raise ValueError(f"x0 must be [{B},{self.n_src},{self.latent_dim},{T}], got {tuple(x0.shape)}")
+        if time is not None:
+            time = _dev32(torch.as_tensor(time), self.device).reshape(-1)
+            if time.numel() != B:
+                raise ValueError(f"time must hold B = {B} values")
+        if noise is not None:
+            noise = _dev32(noise, self.device)
+            if tuple(noise.shape) != tuple(x0.shape):
+                raise ValueError(f"noise must be {tuple(x0.shape)}, got {tuple(noise.shape)}")
+        if perm is not None:
+            perm = torch.as_tensor(perm).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(perm.shape) != (B, self.n_src):
+                raise ValueError(f"perm must be [{B},{self.n_src}], got {tuple(perm.shape)}")
+        out = None
+        if loss:
+            out = torch.empty((B, self.n_src) if reduction == "none" else (1,), device=self.device, dtype=torch.float32)
+        aux = {}
+        if return_aux:
+            aux = {"x_t": torch.empty_like(x0), "t": torch.empty(B, device=self.device, dtype=torch.float32),
+                   "sigma": torch.empty(B, device=self.device, dtype=torch.float32), "z": torch.empty_like(x0)}
+        o = DsnLossOpts(LOSS_MODES[mode], LOSS_REDUCTIONS[reduction], float(t_eps))
+        self._check(self.lib.dsn_score_loss(self.ctx, _ptr(y), _ptr(x0), _ptr(time), _ptr(noise), _ptr(perm),
+                                            int(seed), _ptr(out), _ptr(aux.get("x_t")), _ptr(aux.get("t")),
+                                            _ptr(aux.get("sigma")), _ptr(aux.get("z")), B, T, C.byref(o),
+                                            self._stream()), "dsn_score_loss")
+        if out is not None and reduction == "mean":
+            out = out.reshape(())
+        return (out, aux) if return_aux else out
 
     def decode(self, est, target_len: Optional[int] = None, chunked: bool = False, overlap: int = 32,
                chunk_size: int = 128):

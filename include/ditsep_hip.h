@@ -200,6 +200,38 @@ typedef struct DsnOdeStats {
 int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
                    const DsnOdeOpts* o, DsnOdeStats* stats, void* stream);
 
+/* Denoising score-matching loss of a checkpoint on (mixture, target) latent pairs with ONE score call: the forward
+ * half of the reference's validation_step (src/diffsep_latent.py:130-187).  y [B,1,D,T], x0 [B,n_src,D,T].
+ *   DSN_LOSS_DSM       sample_prior + compute_score_loss: t_b ~ U(t_eps, 1), x_t = (e x0 + (1 - e) y) + sigma(t) z with
+ *                      e = exp(-theta t), sigma = OUVESDE._std(t); loss[b,s] = mean over (D,T) of (sigma score + z)^2.
+ *                      perm [B,n_src] int32 (device, may be NULL = identity): slot s of item b holds source perm[b,s]
+ *                      of x0 (utils.shuffle_sources).
+ *   DSN_LOSS_INIT_PIT  compute_score_loss_init_hack_pit: t = 1, x_t = y + sigma z0 and, per (item, slot), the minimum
+ *                      over the source j placed in the slot of mean (sigma score + z0 + (y - mean(x0[j])) / sigma)^2 --
+ *                      the reference's per-slot minimum over all n! permutations, which it evaluates with n! network
+ *                      calls on identical inputs.  t and perm must be NULL.
+ * reduction: DSN_LOSS_REDUCE_NONE -> loss_out [B,n_src] (what MSELoss(reduction="none") followed by the reference's
+ * mean over the last two axes leaves), DSN_LOSS_REDUCE_MEAN -> loss_out [1] (MSELoss()).
+ * t [B] (device, may be NULL): injected times in (0, 1]; else t_b = t_eps + (1 - t_eps) u_b with u_b word 0 of the
+ * Philox4x32-10 block of counter b under key seed ^ 0x9E3779B97F4A7C15 (same 24-bit mapping as the normals).
+ * noise [B,n_src,D,T] (device, may be NULL): z; else draw 0 of the samplers' normal stream under key `seed` (the z a
+ * sampler's prior would use for that seed).  Optional outputs (device, may be NULL): xt_out [B,n_src,D,T], t_out [B],
+ * sigma_out [B], z_out [B,n_src,D,T].  loss_out == NULL: perturb only (sample_prior), no score call.
+ * sigma and e are evaluated in fp64 per item and rounded once to fp32; x_t is fp32 in the reference's order; the
+ * loss terms are formed and summed in fp64 in a fixed order (bit-identical between runs), then rounded to fp32.
+ * Injected t / perm are checked on the host before any launch (this synchronises the stream); n_src <= 4.  Under
+ * dsn_enable_graphs the sequence perturb, score call, reduce, combine is captured once per (B, T, mode, reduction). */
+enum { DSN_LOSS_DSM = 0, DSN_LOSS_INIT_PIT = 1 };
+enum { DSN_LOSS_REDUCE_NONE = 0, DSN_LOSS_REDUCE_MEAN = 1 };
+typedef struct DsnLossOpts {
+  int mode;                           /* DSN_LOSS_DSM | DSN_LOSS_INIT_PIT */
+  int reduction;                      /* DSN_LOSS_REDUCE_NONE | DSN_LOSS_REDUCE_MEAN */
+  float t_eps;                        /* lower end of the time draw, in (0, 1) */
+} DsnLossOpts;
+int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t, const float* noise,
+                   const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out, float* t_out, float* sigma_out,
+                   float* z_out, int B, int T, const DsnLossOpts* opts, void* stream);
+
 /* LatentDiffSep.decode: est [B,n_src,D,T] -> wav [B,n_src,target_len] (crop of hop*T;
  * target_len <= 0 means hop*T). */
 int dsn_decode(dsn_ctx* ctx, const float* est, float* wav, int B, int T, int target_len, void* stream);
