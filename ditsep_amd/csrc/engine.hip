@@ -167,6 +167,14 @@ struct dsn_ctx {
     int ntaps = 0, up = 1, down = 1, n_pre_pad = 0, n_pre_remove = 0;
   };
   std::map<int, StoiFilter> stoi_filters;
+  // dsn_composite: the window and the critical-band filter table per signal rate (workspace buffers
+  // "comp_win_<fs>", "comp_bw_<fs>")
+  struct CompositeTables {
+    double* win = nullptr;
+    double* bweights = nullptr;
+    CompositeBands bands;
+  };
+  std::map<int, CompositeTables> composite_tables;
   OdeCtl* ode_host = nullptr;  // dsn_ode_sample: pinned host image of the solver state (upload / per-attempt poll)
 
   // DiT
@@ -2815,6 +2823,118 @@ int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int
     for (int i = 0; i < items; ++i) {
       out[i] = (float)hs[i];
       if (frames_out) frames_out[i] = hf[i];
+    }
+  });
+}
+
+// The window 0.5 (1 - cos(2 pi k / (win + 1))), k = 1 .. win, and the 25 critical-band filters of the WSS measure
+// (Klatt 1982; centre frequencies and bandwidths in Hz as tabulated by Hu & Loizou's composite measure): Gaussians
+// exp(-11 ((j - floor f0) / bw)^2 + ln(bw_min) - ln(bw_i)) over the FFT bins j < nfft / 2, entries at or below the
+// -30 dB factor exp(-30 / (2 * 2.303)) dropped.  The cut is made here, once, in fp64.
+static const dsn_ctx::CompositeTables& composite_tables(dsn_ctx* ctx, int fs, const CompositeShape& sh) {
+  auto it = ctx->composite_tables.find(fs);
+  if (it != ctx->composite_tables.end()) return it->second;
+  static const double cent[COMPOSITE_BANDS] = {50.0,    120.0,   190.0,   260.0,   330.0,   400.0,   470.0,
+                                               540.0,   617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30,
+                                               1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71,
+                                               2701.97, 2978.04, 3276.17, 3597.63};
+  static const double bwid[COMPOSITE_BANDS] = {70.0,    70.0,    70.0,    70.0,    70.0,    70.0,    70.0,
+                                               77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423,
+                                               153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255,
+                                               276.072, 298.126, 321.465, 346.136};
+  const int n2 = sh.nfft / 2;
+  const double max_freq = fs / 2.0, min_factor = exp(-30.0 / (2 * 2.303));
+  dsn_ctx::CompositeTables t;
+  std::vector<double> w;
+  for (int i = 0; i < COMPOSITE_BANDS; ++i) {
+    const double f0 = floor(cent[i] / max_freq * n2), bw = bwid[i] / max_freq * n2;
+    const double norm = log(bwid[0]) - log(bwid[i]);
+    t.bands.start[i] = 0;
+    t.bands.len[i] = 0;
+    t.bands.off[i] = (int)w.size();
+    for (int j = 0; j < n2; ++j) {
+      const double d = (j - f0) / bw, v = exp(-11.0 * (d * d) + norm);
+      if (!(v > min_factor)) continue;
+      if (t.bands.len[i] == 0) t.bands.start[i] = j;
+      if (j != t.bands.start[i] + t.bands.len[i]) fail(DSN_EINVAL, "dsn_composite: band %d is not contiguous", i);
+      ++t.bands.len[i];
+      w.push_back(v);
+    }
+  }
+  std::vector<double> win(sh.win);
+  for (int k = 0; k < sh.win; ++k) win[k] = 0.5 * (1.0 - cos(2.0 * M_PI * ((k + 1.0) / (sh.win + 1.0))));
+  t.win = ctx->wsbuf<double>("comp_win_" + std::to_string(fs), sh.win);
+  t.bweights = ctx->wsbuf<double>("comp_bw_" + std::to_string(fs), (long)std::max<size_t>(w.size(), 1));
+  HIPCHK(hipMemcpy(t.win, win.data(), sizeof(double) * sh.win, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t.bweights, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+  return ctx->composite_tables[fs] = t;
+}
+
+// LLR, WSS, segmental SNR and overall SNR of every estimate against its reference, and from them and a caller's PESQ
+// the composite scores (the reference's src/evaluate/evaluate_covl.py, restated in tests/composite_restatement.py).
+// Device: conditioning, the per-frame measures and their trimmed means (composite.hip); host: the window, the filter
+// table, k = round(0.95 F), the permutation map and the composite arithmetic.
+int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
+                  const float* pesq, const DsnCompositeOut* out, void* stream) {
+  return guarded(ctx, [&] {
+    if (!ref || !est || !out || B <= 0 || n <= 0 || L <= 0)
+      fail(DSN_EINVAL, "dsn_composite: bad arguments (ref, est, out non-null, B, n, L > 0)");
+    if (n > 4) fail(DSN_EINVAL, "dsn_composite: n = %d sources (at most 4)", n);
+    if ((long)B * n > 65535) fail(DSN_EINVAL, "dsn_composite: B * n = %ld items (at most 65535)", (long)B * n);
+    CompositeShape sh;
+    if (!composite_shape(fs, &sh)) fail(DSN_EINVAL, "dsn_composite: fs = %d (kernels exist for 8000 and 16000)", fs);
+    if ((out->csig || out->cbak || out->covl) && !pesq)
+      fail(DSN_EINVAL, "dsn_composite: csig / cbak / covl need pesq");
+    // the reference's int(L / hop - win / hop); win = 4 hop at the supported rates
+    const int F = L / sh.hop - sh.win / sh.hop;
+    if (F < 1)
+      fail(DSN_EINVAL, "dsn_composite: L = %d is shorter than one frame (%d samples needed at fs = %d)", L,
+           sh.win + sh.hop, fs);
+    const int k = (int)nearbyint(F * 0.95);  // Python's round(): half to even
+    const int items = B * n;
+    std::vector<int> ymap;
+    if (perm) {
+      ymap.resize(items);
+      for (int b = 0; b < B; ++b)
+        for (int i = 0; i < n; ++i) {
+          const int p = perm[b * n + i];
+          if (p < 0 || p >= n) fail(DSN_EINVAL, "dsn_composite: perm[%d] = %d outside [0, %d)", b * n + i, p, n);
+          ymap[b * n + i] = b * n + p;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dsn_ctx::CompositeTables& tab = composite_tables(ctx, fs, sh);
+    int* dmap = nullptr;
+    if (perm) {
+      dmap = ctx->wsbuf<int>("comp_map", items);
+      HIPCHK(hipMemcpyAsync(dmap, ymap.data(), sizeof(int) * items, hipMemcpyHostToDevice, st));
+    }
+    double* cond = ctx->wsbuf<double>("comp_cond", (long)items * COMPOSITE_COND);
+    double* fl = ctx->wsbuf<double>("comp_llr", (long)items * F);
+    double* fw = ctx->wsbuf<double>("comp_wss", (long)items * F);
+    double* fsn = ctx->wsbuf<double>("comp_ssnr", (long)items * F);
+    double* res = ctx->wsbuf<double>("comp_out", (long)items * 3);
+    launch_composite(fs, ref, est, dmap, items, L, F, k, tab.win, tab.bands, tab.bweights, cond, fl, fw, fsn, res, st);
+    HIPCHK(hipGetLastError());
+    std::vector<double> hc((size_t)items * COMPOSITE_COND), hr((size_t)items * 3);
+    HIPCHK(hipMemcpyAsync(hc.data(), cond, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hr.data(), res, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    auto mos = [](double v) { return std::isnan(v) ? v : std::min(std::max(v, 1.0), 5.0); };
+    for (int i = 0; i < items; ++i) {
+      // the composites are formed from the float results the caller sees
+      const float l = (float)hr[3 * i], w = (float)hr[3 * i + 1], s = (float)hr[3 * i + 2];
+      if (out->llr) out->llr[i] = l;
+      if (out->wss) out->wss[i] = w;
+      if (out->segsnr) out->segsnr[i] = s;
+      if (out->snr) out->snr[i] = (float)hc[(size_t)i * COMPOSITE_COND + 3];
+      if (out->frames) out->frames[i] = F;
+      if (pesq) {
+        const double q = pesq[i];
+        if (out->csig) out->csig[i] = (float)mos(3.093 - 1.029 * l + 0.603 * q - 0.009 * w);
+        if (out->cbak) out->cbak[i] = (float)mos(1.634 + 0.478 * q - 0.007 * w + 0.063 * s);
+        if (out->covl) out->covl[i] = (float)mos(1.594 + 0.805 * q - 0.512 * l - 0.007 * w);
+      }
     }
   });
 }

@@ -145,6 +145,28 @@ void launch_stoi_frames(const float* xs, const float* ys, long stride, const int
                         StoiBands bands, int extended, double* en, int* idx, int* Kc, double* tob, double* part,
                         double* score, int* frames, hipStream_t s);
 
+// ---- LLR / WSS / segmental SNR of the composite measures (composite.hip) ----------------------------------
+#define COMPOSITE_BANDS 25
+#define COMPOSITE_COND 4   // doubles per item of the condition stage: mean(ref), mean(est), scale, overall SNR (dB)
+// frame geometry of a signal rate
+struct CompositeShape {
+  int win, hop, nfft, order;
+};
+// false when no kernel is instantiated for fs (8000 and 16000 are)
+bool composite_shape(int fs, CompositeShape* s);
+// critical-band filter b weighs the FFT bins [start[b], start[b] + len[b]) (all below nfft / 2) by
+// bweights[off[b] ..]: the reference's Gaussian filters with the entries at or below the -30 dB factor left out
+struct CompositeBands {
+  int start[COMPOSITE_BANDS], len[COMPOSITE_BANDS], off[COMPOSITE_BANDS];
+};
+// ref, est [items][L] (est row ymap[item], or item when ymap is null), F >= 1 frames per item, win [shape.win] the
+// fp64 window, k = round(0.95 F).  Work buffers: cond [items*COMPOSITE_COND], llr / wss / ssnr [items*F] (the
+// per-frame values).  -> out [items][3] = LLR, WSS (means of the k smallest frames), segmental SNR (mean); the
+// overall SNR is cond[item][3].  All fp64.
+void launch_composite(int fs, const float* ref, const float* est, const int* ymap, int items, int L, int F, int k,
+                      const double* win, const CompositeBands& bands, const double* bweights, double* cond,
+                      double* llr, double* wss, double* ssnr, double* out, hipStream_t s);
+
 // ---- probability-flow ODE sampler (ode.hip) ---------------------------------------------------------------
 // Explicit embedded Runge-Kutta pair with scipy 1.15's solve_ivp step control on the fp64 state y [B,n,D,T].
 // Stages: K[0] = f(t, y), K[1 .. stages-1] the intermediate stages, K[stages] = f(t + h, y_new) (FSAL); K holds

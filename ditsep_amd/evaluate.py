@@ -8,7 +8,13 @@ summary (:139-156).  With stoi=True the "stoi" field holds extended STOI (the re
 extended=True); stoi_extended=False gives classic STOI, its stoi_no_extended) from the device (dsn_stoi), scored on
 the SIR permutation as the reference orders the estimates by perm before calling stoi; parity with the pystoi package
 is unpinned (the float64 restatement in tests/stoi_restatement.py is the contract).  By default, and always for PESQ
-(ITU-T P.862, not implemented), the field is null."""
+(ITU-T P.862, not implemented), the field is null.
+
+composite=True adds the measures of the reference's second evaluation stage (src/evaluate/evaluate_covl.py): "llr",
+"wss" and "segsnr" per source from the device (dsn_composite), scored on the SIR permutation like STOI.  PESQ is the
+caller's: with pesq_fn(fs, ref_1d, est_1d) -> float the "pesq" field is filled and the composite scores "csig", "cbak"
+and "covl" are added.  pesq_fn sees what the reference's PESQ call sees: eval_composite runs it after SSNR has, in
+place and in float32, removed both means and rescaled the estimate to the reference's peak (condition_for_pesq)."""
 from __future__ import annotations
 
 import json
@@ -21,11 +27,16 @@ import torch
 
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
-                     stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False) -> dict:
+                     stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False,
+                     composite: bool = False, pesq_fn=None) -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
     with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
     adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
-    call per batch on the encoded targets, t and z from the device stream of the utterance's seed)."""
+    call per batch on the encoded targets, t and z from the device stream of the utterance's seed).  composite=True
+    adds "llr", "wss" and "segsnr" (n floats each); with pesq_fn(fs, ref_1d, est_1d) -> float as well, "pesq" is filled
+    and "csig", "cbak" and "covl" are added."""
+    if pesq_fn is not None and not composite:
+        raise ValueError("pesq_fn is used by composite=True only")
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
     N = N if N is not None else cfg_s.get("N", model.sde.N)
     corrector_steps = corrector_steps if corrector_steps is not None else cfg_s.get("corrector_steps", 1)
@@ -53,6 +64,13 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
         si_sdr, si_sir, si_sar, perm = model.engine.si_bss_eval(target, x_result, perm_by="sir", clamp_db=100.0)
         st = model.engine.stoi(target, x_result, fs, extended=stoi_extended, perm=perm) if stoi else None
         B = mix.shape[0]
+        comp = pq = None
+        if composite:
+            if pesq_fn is not None:
+                tgt_h, est_h = target.cpu().numpy(), x_result.cpu().numpy()
+                pq = torch.tensor([[float(pesq_fn(fs, *condition_for_pesq(tgt_h[b, i], est_h[b, int(perm[b, i])])))
+                                    for i in range(target.shape[1])] for b in range(B)], dtype=torch.float32)
+            comp = model.engine.composite(target, x_result, fs, perm=perm, pesq=pq)
         for b in range(B):
             results[idx] = {"batch_idx": idx, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
                             "si_sar": si_sar[b].tolist(),
@@ -60,8 +78,25 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                             "nfe": nfe, "runtime": t_proc / B, "len_s": L / fs, "perm": perm[b].tolist()}
             if sl is not None:
                 results[idx]["score_loss"] = sl[b].tolist()
+            if comp is not None:
+                for k in ("llr", "wss", "segsnr") + (("csig", "cbak", "covl") if pq is not None else ()):
+                    results[idx][k] = comp[k][b].tolist()
+                if pq is not None:
+                    results[idx]["pesq"] = pq[b].tolist()
             idx += 1
     return results
+
+
+def condition_for_pesq(ref: np.ndarray, est: np.ndarray):
+    """The (ref, est) pair the reference hands to PESQ in eval_composite: its SSNR has by then, in place and in
+    float32, removed both means and scaled the estimate by max|ref| / max|est| of the mean-removed signals."""
+    r = np.array(ref, dtype=np.float32).reshape(-1)
+    e = np.array(est, dtype=np.float32).reshape(-1)
+    r -= r.mean()
+    e -= e.mean()
+    with np.errstate(all="ignore"):
+        e *= np.max(np.abs(r)) / np.max(np.abs(e))
+    return r, e
 
 
 def summarize(results: dict, ignore_inf: bool = True) -> dict:
@@ -94,6 +129,9 @@ def write_results(path: str, results: dict):
     summary["si_bss_impl"] = "native (dsn_si_bss_eval); parity unpinned vs fast_bss_eval"
     if any(rec.get("stoi") is not None for rec in results.values()):
         summary["stoi_impl"] = "native (dsn_stoi); parity unpinned vs pystoi"
+    if any("llr" in rec for rec in results.values()):
+        summary["composite_impl"] = ("native (dsn_composite): llr, wss, segsnr pinned to the reference's evaluate_covl.py; "
+                                     "pesq, where given, is the caller's")
     summary["nfe_note"] = "nfe = N * (corrector_steps + 1), the reference's bookkeeping (not a count of score calls)"
     with open(path.replace(".json", "_summary.json"), "w") as fh:
         json.dump(summary, fh, indent=2)

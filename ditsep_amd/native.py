@@ -32,7 +32,7 @@ EXPORTS = [
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
     "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
-    "dsn_stoi", "dsn_ode_sample", "dsn_score_loss",
+    "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite",
 ]
 
 
@@ -72,6 +72,11 @@ class DsnOdeStats(C.Structure):
 
 class DsnLossOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("reduction", C.c_int), ("t_eps", C.c_float)]
+
+
+class DsnCompositeOut(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_float)) for k in ("llr", "wss", "segsnr", "snr", "csig", "cbak", "covl")] + [
+        ("frames", C.POINTER(C.c_int))]
 
 
 LOSS_MODES = {"dsm": 0, "init_pit": 1}
@@ -182,6 +187,7 @@ def load_library() -> C.CDLL:
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
     lib.dsn_stoi.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
+    lib.dsn_composite.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(DsnCompositeOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -571,6 +577,38 @@ class Engine:
             warnings.warn(f"stoi: {len(short)} item(s) [b, i] {short[:8]} have fewer than 30 frames after silent-frame "
                           f"removal; their score is 1e-5", RuntimeWarning, stacklevel=2)
         return (score, nfr) if return_frames else score
+
+    def composite(self, ref, est, fs: int, perm=None, pesq=None) -> dict:
+        """ref, est [B,n,L] -> {"llr", "wss", "segsnr", "snr": [B,n] float32, "frames": [B,n] long}: the objective
+        measures of the Hu & Loizou composite scores as the reference's evaluate_covl.py computes them (restated in
+        tests/composite_restatement.py, pinned by tests/golden/composite.npz).  fs is 8000 or 16000.  perm [B,n]
+        (optional): est source perm[b,i] is scored against ref source i.  With pesq [B,n] (PESQ is not computed
+        here) the dict also holds "csig", "cbak" and "covl", each clipped to [1, 5].  A constant estimate gives NaN
+        for segsnr, snr and cbak (the reference rescales by max|est - mean| = 0); llr and wss stay defined."""
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        if ref.dim() != 3 or est.shape != ref.shape:
+            raise ValueError(f"ref and est must both be [B,n,L] (got {tuple(ref.shape)} and {tuple(est.shape)})")
+        B, n, L = ref.shape
+        keys = ["llr", "wss", "segsnr", "snr"] + (["csig", "cbak", "covl"] if pesq is not None else [])
+        bufs = {k: (C.c_float * (B * n))() for k in keys}
+        frames = (C.c_int * (B * n))()
+        out = DsnCompositeOut(frames=frames, **bufs)
+
+        def host(v, ctype, what):
+            if v is None:
+                return None
+            flat = torch.as_tensor(v).reshape(-1).tolist()
+            if len(flat) != B * n:
+                raise ValueError(f"{what} must hold B*n = {B * n} entries (got {len(flat)})")
+            return (ctype * (B * n))(*flat)
+
+        cperm = host(None if perm is None else torch.as_tensor(perm, dtype=torch.int32), C.c_int, "perm")
+        cpesq = host(None if pesq is None else torch.as_tensor(pesq, dtype=torch.float32), C.c_float, "pesq")
+        self._check(self.lib.dsn_composite(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), cperm, cpesq,
+                                           C.byref(out), self._stream()), "dsn_composite")
+        res = {k: torch.tensor(list(b), dtype=torch.float32).reshape(B, n) for k, b in bufs.items()}
+        res["frames"] = torch.tensor(list(frames), dtype=torch.long).reshape(B, n)
+        return res
 
     def debug_read(self, name: str, shape):
         out = torch.empty(shape, dtype=torch.float32)

@@ -287,6 +287,29 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
 int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, int extended,
              const int* perm, float* out, int* frames_out, void* stream);
 
+/* The objective measures behind the Hu & Loizou composite scores, as the reference's src/evaluate/evaluate_covl.py
+ * computes them per utterance (restated in tests/composite_restatement.py and pinned to the reference's own functions
+ * by tests/golden/composite.npz): the log-likelihood ratio of the LPC models (llr) and the weighted spectral slope
+ * (wss), each the mean of the round(0.95 F) smallest of the F per-frame values, the segmental SNR (segsnr, mean over
+ * the frames of the value clamped to [-10, 35] dB) and the overall SNR (snr), both on the mean-removed signals with
+ * the estimate rescaled to the reference's peak.  ref, est [B,n,L] fp32 (device); fs 8000 or 16000.  perm [B*n] host,
+ * may be NULL: est source perm[b*n+i] is scored against ref source i.  Every array of `out` is a host array of B*n
+ * entries and may be NULL; frames receives F.  With pesq [B*n] (host; PESQ itself is not computed here) the call
+ * also fills
+ *   csig = 3.093 - 1.029 llr + 0.603 pesq - 0.009 wss
+ *   cbak = 1.634 + 0.478 pesq - 0.007 wss + 0.063 segsnr
+ *   covl = 1.594 + 0.805 pesq - 0.512 llr - 0.007 wss
+ * each clipped to [1, 5]; asking for one of them without pesq is DSN_EINVAL.  Also DSN_EINVAL, before any launch:
+ * n > 4, a perm entry outside [0, n), another fs, L shorter than one frame plus one hop (F < 1).
+ * A constant estimate (all zeros included) has no peak to rescale to: the conditioning divides by max|est - mean| = 0
+ * as the reference does, and segsnr, snr and cbak are NaN; llr and wss read the raw signals and stay defined. */
+typedef struct DsnCompositeOut {
+  float *llr, *wss, *segsnr, *snr, *csig, *cbak, *covl;
+  int* frames;
+} DsnCompositeOut;
+int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
+                  const float* pesq, const DsnCompositeOut* out, void* stream);
+
 /* introspection for benchmarks / tests */
 int dsn_enable_graphs(dsn_ctx* ctx, int enable);          /* hipGraph replay of sample/decode */
 int64_t dsn_workspace_bytes(const dsn_ctx* ctx);
