@@ -4,17 +4,21 @@ The compute lives in libditsep_hip.so (ditsep_amd/csrc, C-ABI include/ditsep_hip
 importing this package does not load it -- the first Engine / LatentDiffSep does, and
 fails loudly if it is missing."""
 
-__all__ = ["LatentDiffSep", "Engine", "sdes", "synthetic", "distributed"]
+__all__ = ["LatentDiffSep", "LDM", "Engine", "sdes", "synthetic", "distributed"]
 
 
 def __getattr__(name):
     if name == "LatentDiffSep":
         from .latent import LatentDiffSep
         return LatentDiffSep
+    if name == "LDM":
+        from .latent import LDM
+        return LDM
     if name == "Engine":
         from .native import Engine
         return Engine
-    if name in ("sdes", "synthetic", "distributed", "native", "latent", "score_models", "checkpoint", "evaluate"):
+    if name in ("sdes", "synthetic", "distributed", "native", "latent", "score_models", "checkpoint", "evaluate",
+                "aweight"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -175,6 +175,7 @@ struct dsn_ctx {
     CompositeBands bands;
   };
   std::map<int, CompositeTables> composite_tables;
+  std::map<long, float*> mrstft_windows;  // dsn_mrstft_loss: (fft << 16 | win_length) -> zero-padded window [fft]
   OdeCtl* ode_host = nullptr;  // dsn_ode_sample: pinned host image of the solver state (upload / per-attempt poll)
 
   // DiT
@@ -2936,6 +2937,92 @@ int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n
         if (out->covl) out->covl[i] = (float)mos(1.594 + 0.805 * q - 0.512 * l - 0.007 * w);
       }
     }
+  });
+}
+
+// torch.hann_window(win) (periodic: 0.5 - 0.5 cos(2 pi k / win)) centred in fft zeros as torch.stft pads it,
+// (fft - win) / 2 on the left.  The reference's window is a float32 tensor, so it is formed in float32 the way torch
+// forms it (k times the rounded step, cos, times -0.5, plus 0.5): the leakage floor of a spectrum follows the window's
+// rounding, and the log-magnitude term sees that floor.
+static const float* mrstft_window(dsn_ctx* ctx, int fft, int win) {
+  const long key = ((long)fft << 16) | win;
+  auto it = ctx->mrstft_windows.find(key);
+  if (it != ctx->mrstft_windows.end()) return it->second;
+  std::vector<float> w(fft, 0.f);
+  const int left = (fft - win) / 2;
+  const float step = (float)(M_PI * 2.0 / (double)win);
+  for (int k = 0; k < win; ++k) w[left + k] = win == 1 ? 1.f : cosf((float)k * step) * -0.5f + 0.5f;
+  float* d = ctx->wsbuf<float>("mrstft_win_" + std::to_string(fft) + "_" + std::to_string(win), fft);
+  HIPCHK(hipMemcpy(d, w.data(), sizeof(float) * fft, hipMemcpyHostToDevice));
+  return ctx->mrstft_windows[key] = d;
+}
+
+// Pair tables of the multi-resolution STFT loss and of the L1 / L2 waveform losses (the reference's
+// auraloss.py::MultiResolutionSTFTLoss and losses.py::L1Loss / MSELoss under PITLoss, restated in
+// tests/mrstft_restatement.py).  Device: prefilter, spectra and every sum (mrstft.hip); host: the windows, the launch
+// plan and the zeroing of the terms whose weight is zero.
+int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int B, int n, int L,
+                    const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream) {
+  return guarded(ctx, [&] {
+    if (!reals || !decoded || !cfg || !out || B <= 0 || n <= 0 || L <= 0)
+      fail(DSN_EINVAL, "dsn_mrstft_loss: bad arguments (reals, decoded, cfg, out non-null, B, n, L > 0)");
+    if (n > MRSTFT_MAX_SRC) fail(DSN_EINVAL, "dsn_mrstft_loss: n = %d sources (at most %d)", n, MRSTFT_MAX_SRC);
+    if (B > 65535) fail(DSN_EINVAL, "dsn_mrstft_loss: B = %d items (at most 65535)", B);
+    const int R = cfg->n_res;
+    if (R < 0 || R > MRSTFT_MAX_RES) fail(DSN_EINVAL, "dsn_mrstft_loss: %d resolutions (0 .. %d)", R, MRSTFT_MAX_RES);
+    if (R > 0 && (!cfg->fft || !cfg->hop || !cfg->win)) fail(DSN_EINVAL, "dsn_mrstft_loss: fft / hop / win missing");
+    int max_fft = 0;
+    for (int r = 0; r < R; ++r) {
+      if (!mrstft_fft_ok(cfg->fft[r]))
+        fail(DSN_EINVAL, "dsn_mrstft_loss: fft[%d] = %d (a power of two from 32 to 2048)", r, cfg->fft[r]);
+      if (cfg->win[r] < 1 || cfg->win[r] > cfg->fft[r])
+        fail(DSN_EINVAL, "dsn_mrstft_loss: win[%d] = %d outside [1, fft = %d]", r, cfg->win[r], cfg->fft[r]);
+      if (cfg->hop[r] < 1) fail(DSN_EINVAL, "dsn_mrstft_loss: hop[%d] = %d (must be positive)", r, cfg->hop[r]);
+      max_fft = std::max(max_fft, cfg->fft[r]);
+    }
+    if (L <= max_fft / 2)
+      fail(DSN_EINVAL, "dsn_mrstft_loss: L = %d needs reflect padding of %d samples (L must exceed it)", L, max_fft / 2);
+    const bool filter = R > 0 && cfg->taps != nullptr;
+    if (filter && (cfg->n_taps < 1 || cfg->n_taps % 2 == 0 || cfg->n_taps > MRSTFT_MAX_TAPS))
+      fail(DSN_EINVAL, "dsn_mrstft_loss: %d prefilter taps (odd, at most %d)", cfg->n_taps, MRSTFT_MAX_TAPS);
+    hipStream_t st = (hipStream_t)stream;
+    const long per = (long)B * n * n, sig = (long)B * n * L;
+    MrstftPlan plan;
+    plan.R = R;
+    for (int r = 0; r < R; ++r) mrstft_plan_resolution(&plan, r, cfg->fft[r], cfg->hop[r], B, L);
+    const long nparts = R ? plan.off[R - 1] + (long)B * plan.wgs[R - 1] * MRSTFT_SACC : 1;
+    std::vector<const float*> wins(R);
+    for (int r = 0; r < R; ++r) wins[r] = mrstft_window(ctx, cfg->fft[r], cfg->win[r]);
+    double* part = ctx->wsbuf<double>("mrstft_part", nparts);
+    double* tpart = ctx->wsbuf<double>("mrstft_tpart", (long)B * mrstft_time_chunks(L) * MRSTFT_TACC);
+    double* tabs = ctx->wsbuf<double>("mrstft_tables", per * (3 * std::max(R, 1) + 2));
+    double *d_sc = tabs, *d_lg = tabs + per * std::max(R, 1), *d_lin = d_lg + per * std::max(R, 1);
+    double *d_l1 = d_lin + per * std::max(R, 1), *d_l2 = d_l1 + per;
+    float* dtaps = nullptr;
+    double *xf = nullptr, *yf = nullptr;  // the prefiltered signals, fp64 (mrstft.hip says why)
+    if (filter) {
+      dtaps = ctx->wsbuf<float>("mrstft_taps", MRSTFT_MAX_TAPS);
+      xf = ctx->wsbuf<double>("mrstft_filtered", 2 * sig);
+      yf = xf + sig;
+      HIPCHK(hipMemcpyAsync(dtaps, cfg->taps, sizeof(float) * cfg->n_taps, hipMemcpyHostToDevice, st));
+    }
+    launch_mrstft_time(reals, decoded, B, n, L, dtaps, filter ? cfg->n_taps : 0, xf, yf, tpart, st);
+    for (int r = 0; r < R; ++r) launch_mrstft_spec(plan, r, reals, decoded, xf, yf, wins[r], B, n, L, part, st);
+    launch_mrstft_finish(plan, part, tpart, B, n, L, d_sc, d_lg, d_lin, d_l1, d_l2, st);
+    HIPCHK(hipGetLastError());
+    // a term whose weight is zero is the reference's constant 0.0 (STFTLoss.forward skips it)
+    const struct { double* host; const double* dev; long count; bool on; } copies[5] = {
+        {out->sc, d_sc, per * R, cfg->w_sc != 0.f},
+        {out->log_mag, d_lg, per * R, cfg->w_log_mag != 0.f},
+        {out->lin_mag, d_lin, per * R, cfg->w_lin_mag != 0.f},
+        {out->l1, d_l1, per, true},
+        {out->l2, d_l2, per, true}};
+    for (const auto& c : copies) {
+      if (!c.host || c.count == 0) continue;
+      if (c.on) HIPCHK(hipMemcpyAsync(c.host, c.dev, sizeof(double) * c.count, hipMemcpyDeviceToHost, st));
+      else std::fill(c.host, c.host + c.count, 0.0);
+    }
+    HIPCHK(hipStreamSynchronize(st));
   });
 }
 

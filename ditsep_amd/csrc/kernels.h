@@ -167,6 +167,37 @@ void launch_composite(int fs, const float* ref, const float* est, const int* yma
                       const double* win, const CompositeBands& bands, const double* bweights, double* cond,
                       double* llr, double* wss, double* ssnr, double* out, hipStream_t s);
 
+// ---- multi-resolution STFT and time-domain reconstruction losses (mrstft.hip) -------------------------------
+#define MRSTFT_MAX_SRC 4
+#define MRSTFT_MAX_RES 16
+#define MRSTFT_MAX_TAPS 127   // prefilter taps (odd)
+#define MRSTFT_TCHUNK 1024    // samples of an item one workgroup of the time stage takes
+#define MRSTFT_TACC (MRSTFT_MAX_SRC * MRSTFT_MAX_SRC * 2)                    // doubles per time-stage partial
+#define MRSTFT_SACC (MRSTFT_MAX_SRC * MRSTFT_MAX_SRC * 3 + MRSTFT_MAX_SRC)   // doubles per spectral partial
+// per resolution r < R: FFT length, hop, frames 1 + L / hop, frame groups per workgroup, workgroups per item and the
+// offset (in doubles) of its partials [B][wgs][MRSTFT_SACC] in the partials buffer
+struct MrstftPlan {
+  int R;
+  int fft[MRSTFT_MAX_RES], hop[MRSTFT_MAX_RES], frames[MRSTFT_MAX_RES], gpw[MRSTFT_MAX_RES], wgs[MRSTFT_MAX_RES];
+  long off[MRSTFT_MAX_RES];
+};
+bool mrstft_fft_ok(int fft);   // a power of two in [32, 2048]
+int mrstft_time_chunks(int L);
+// fills entry r (entries 0 .. r-1 must be filled: off accumulates)
+void mrstft_plan_resolution(MrstftPlan* plan, int r, int fft, int hop, int B, int L);
+// x = reals, y = decoded [B][n][L] -> tpart [B][chunks][MRSTFT_TACC] (sum |r_i - d_j|, sum (r_i - d_j)^2) and, with
+// taps [ntaps] (device, fp32, ntaps odd <= MRSTFT_MAX_TAPS), xf / yf [B][n][L] = conv1d(., taps, padding = ntaps / 2)
+// in fp64
+void launch_mrstft_time(const float* x, const float* y, int B, int n, int L, const float* taps, int ntaps, double* xf,
+                        double* yf, double* tpart, hipStream_t s);
+// resolution r: the signals [B][n][L] are xr64 / xd64 (the prefiltered ones) or, when those are null, xr / xd;
+// win [fft] the window zero-padded to the FFT length -> part + plan.off[r]
+void launch_mrstft_spec(const MrstftPlan& plan, int r, const float* xr, const float* xd, const double* xr64,
+                        const double* xd64, const float* win, int B, int n, int L, double* part, hipStream_t s);
+// partials -> sc / lg / lin [R][B][n][n], l1 / l2 [B][n][n] (fp64, device)
+void launch_mrstft_finish(const MrstftPlan& plan, const double* part, const double* tpart, int B, int n, int L,
+                          double* sc, double* lg, double* lin, double* l1, double* l2, hipStream_t s);
+
 // ---- probability-flow ODE sampler (ode.hip) ---------------------------------------------------------------
 // Explicit embedded Runge-Kutta pair with scipy 1.15's solve_ivp step control on the fp64 state y [B,n,D,T].
 // Stages: K[0] = f(t, y), K[1 .. stages-1] the intermediate stages, K[stages] = f(t + h, y_new) (FSAL); K holds

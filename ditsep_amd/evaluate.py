@@ -14,7 +14,11 @@ composite=True adds the measures of the reference's second evaluation stage (src
 "wss" and "segsnr" per source from the device (dsn_composite), scored on the SIR permutation like STOI.  PESQ is the
 caller's: with pesq_fn(fs, ref_1d, est_1d) -> float the "pesq" field is filled and the composite scores "csig", "cbak"
 and "covl" are added.  pesq_fn sees what the reference's PESQ call sees: eval_composite runs it after SSNR has, in
-place and in float32, removed both means and rescaled the estimate to the reference's peak (condition_for_pesq)."""
+place and in float32, removed both means and rescaled the estimate to the reference's peak (condition_for_pesq).
+
+mrstft=True adds "mrstft" and "l1" per source from the device (dsn_mrstft_loss): the A-weighted multi-resolution STFT
+distance (the reference's LDM objective, src/config/ldm/training/default.yaml, unweighted) and the mean absolute
+waveform error of each reference source against the estimate the SIR permutation assigns to it."""
 from __future__ import annotations
 
 import json
@@ -28,13 +32,15 @@ import torch
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
                      stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False,
-                     composite: bool = False, pesq_fn=None) -> dict:
+                     composite: bool = False, pesq_fn=None, mrstft: bool = False) -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
     with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
     adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
     call per batch on the encoded targets, t and z from the device stream of the utterance's seed).  composite=True
     adds "llr", "wss" and "segsnr" (n floats each); with pesq_fn(fs, ref_1d, est_1d) -> float as well, "pesq" is filled
-    and "csig", "cbak" and "covl" are added."""
+    and "csig", "cbak" and "covl" are added.  mrstft=True adds "mrstft" and "l1" (n floats each, unweighted): the
+    diagonal, under the SIR permutation, of the pair tables of Engine.mrstft_loss at its defaults (seven resolutions,
+    A-weighting of `fs`, spectral convergence plus log magnitude)."""
     if pesq_fn is not None and not composite:
         raise ValueError("pesq_fn is used by composite=True only")
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
@@ -71,6 +77,14 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                 pq = torch.tensor([[float(pesq_fn(fs, *condition_for_pesq(tgt_h[b, i], est_h[b, int(perm[b, i])])))
                                     for i in range(target.shape[1])] for b in range(B)], dtype=torch.float32)
             comp = model.engine.composite(target, x_result, fs, perm=perm, pesq=pq)
+        mr = None
+        if mrstft:
+            tabs = model.engine.mrstft_loss(target, x_result, fs, pit=None)
+            n_src = target.shape[1]
+            rows = torch.arange(n_src)
+            spec = (tabs["sc"] + tabs["log_mag"]).mean(0)                        # [B,n,n]: mean over the resolutions
+            mr = {"mrstft": torch.stack([spec[b, rows, perm[b]] for b in range(B)]),
+                  "l1": torch.stack([tabs["l1"][b, rows, perm[b]] for b in range(B)])}
         for b in range(B):
             results[idx] = {"batch_idx": idx, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
                             "si_sar": si_sar[b].tolist(),
@@ -83,6 +97,9 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                     results[idx][k] = comp[k][b].tolist()
                 if pq is not None:
                     results[idx]["pesq"] = pq[b].tolist()
+            if mr is not None:
+                for k in ("mrstft", "l1"):
+                    results[idx][k] = mr[k][b].tolist()
             idx += 1
     return results
 
@@ -132,6 +149,9 @@ def write_results(path: str, results: dict):
     if any("llr" in rec for rec in results.values()):
         summary["composite_impl"] = ("native (dsn_composite): llr, wss, segsnr pinned to the reference's evaluate_covl.py; "
                                      "pesq, where given, is the caller's")
+    if any("mrstft" in rec for rec in results.values()):
+        summary["mrstft_impl"] = ("native (dsn_mrstft_loss): pinned to the reference's auraloss.MultiResolutionSTFTLoss "
+                                  "(A-weighted, 7 resolutions) and L1; per source under the SIR permutation")
     summary["nfe_note"] = "nfe = N * (corrector_steps + 1), the reference's bookkeeping (not a count of score calls)"
     with open(path.replace(".json", "_summary.json"), "w") as fh:
         json.dump(summary, fh, indent=2)

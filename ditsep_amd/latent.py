@@ -440,3 +440,70 @@ class LatentDiffSep:
 
     def close(self):
         self.engine.close()
+
+
+def reconstruction_loss_config(config) -> dict:
+    """The reference's reading of `training.loss` in LDM.__init__ (src/ldm.py:92-154) -> the keyword arguments of
+    Engine.mrstft_loss (without `fs`-independent defaults changed): `spectral.config` (the MultiResolutionSTFTLoss
+    keywords; `sample_rate` becomes "fs"), `spectral.weights.mrstft`, `spectral.decay`, `time.weights.l1` / `l2`.
+    A discriminator (`training.discriminator` together with `training.loss.discriminator`, :92) raises
+    NotImplementedError, as does any MultiResolutionSTFTLoss option without a native kernel."""
+    tr = _get(config, "training")
+    loss = _get(tr, "loss")
+    if loss is None or _get(loss, "spectral") is None:
+        raise ValueError("training.loss.spectral is missing: LDM needs the reference's loss section (src/ldm.py:100-130)")
+    if _get(tr, "discriminator") is not None and _get(loss, "discriminator") is not None:
+        raise NotImplementedError("training.discriminator: the adversarial and feature-matching terms are not "
+                                  "implemented natively (forward value of the reconstruction terms only)")
+    spec = dict(_get(loss, "spectral.config", {}) or {})
+    target = str(spec.pop("_target_", "stable_audio_tools.training.losses.auraloss.MultiResolutionSTFTLoss"))
+    if not target.endswith("MultiResolutionSTFTLoss"):
+        raise NotImplementedError(f"training.loss.spectral.config._target_ = '{target}': only "
+                                  "MultiResolutionSTFTLoss is implemented natively")
+    kw = dict(fs=spec.pop("sample_rate", None),
+              # auraloss.py:475-491, the constructor's defaults
+              fft_sizes=tuple(spec.pop("fft_sizes", (1024, 2048, 512))),
+              hop_sizes=tuple(spec.pop("hop_sizes", (120, 240, 50))),
+              win_lengths=tuple(spec.pop("win_lengths", (600, 1200, 240))),
+              perceptual_weighting=bool(spec.pop("perceptual_weighting", False)),
+              w_sc=float(spec.pop("w_sc", 1.0)), w_log_mag=float(spec.pop("w_log_mag", 1.0)),
+              w_lin_mag=float(spec.pop("w_lin_mag", 0.0)),
+              mrstft_weight=float(_get(loss, "spectral.weights.mrstft", 1.0)),
+              l1_weight=float(_get(loss, "time.weights.l1", 0.0)), l2_weight=float(_get(loss, "time.weights.l2", 0.0)))
+    if spec.get("n_bins") is None:
+        spec.pop("n_bins", None)
+    native.mrstft_unsupported(decay=_get(loss, "spectral.decay", 1.0), **spec)
+    if kw["perceptual_weighting"] and kw["fs"] is None:
+        raise ValueError("`sample_rate` must be supplied when `perceptual_weighting = True`.")      # auraloss.py:362
+    return kw
+
+
+class LDM(LatentDiffSep):
+    """The reference's second latent module (src/ldm.py), which fine-tunes the decoder through the frozen sampler:
+    the inference surface is LatentDiffSep's (`LDM.separate` is the same code), and `losses_gen` is the forward value
+    of its generator objective, read from `config.training.loss` as LDM.__init__ reads it (ldm.py:100-154).
+    Gradients, the discriminator terms, warm-up and training are out of scope."""
+
+    def __init__(self, config, device: int = 0, precision: str = "fp16", pit="batch"):
+        self.loss_kwargs = reconstruction_loss_config(config)       # before the engine exists: a bad section fails early
+        self.loss_fs = self.loss_kwargs.pop("fs")
+        self.pit = pit
+        super().__init__(config, device=device, precision=precision)
+
+    @torch.no_grad()
+    def losses_gen(self, decoded, reals):
+        """reference ldm.py:154 `self.losses_gen({"reals": reals, "decoded": decoded})` -> (loss, losses) with the
+        MultiLoss keys "pit_mrstft_loss", "pit_l1_loss", "pit_l2_loss" (the latter two with a positive weight only).
+        `self.last_loss_tables` keeps the whole Engine.mrstft_loss result (pair tables, chosen permutations)."""
+        res = self.engine.mrstft_loss(reals, decoded, self.loss_fs if self.loss_fs is not None else 0,
+                                      pit=self.pit, **self.loss_kwargs)
+        self.last_loss_tables = res
+        losses = {k: res[k] for k in ("pit_mrstft_loss", "pit_l1_loss", "pit_l2_loss") if k in res}
+        return res["loss"], losses
+
+    @torch.no_grad()
+    def generator_loss(self, mix, reals, **sampler_kwargs):
+        """separate(mix) followed by losses_gen against `reals` [B,n,L] -> (loss, losses, decoded)."""
+        decoded, *_ = self.separate(mix, target_dim=reals.shape[-1], **sampler_kwargs)
+        loss, losses = self.losses_gen(decoded, reals)
+        return loss, losses, decoded

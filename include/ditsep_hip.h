@@ -310,6 +310,38 @@ typedef struct DsnCompositeOut {
 int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
                   const float* pesq, const DsnCompositeOut* out, void* stream);
 
+/* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
+ * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
+ * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
+ * tests/mrstft_restatement.py and pinned to the reference's own modules by tests/golden/mrstft.npz).  The reference
+ * evaluates a loss once per source permutation; every term of every permutation is a mean of the values below, so this
+ * call forms each spectrum once.  reals, decoded [B,n,L] fp32 (device), n <= 4.  For item b, reference source i and
+ * estimate source j, with mag = sqrt(max(re^2 + im^2, 1e-8)) of torch.stft(x, fft, hop, win, hann_window(win)) (its
+ * defaults: center, reflect padding, 1 + L / hop frames, no normalisation) of the signals, which are first filtered
+ * with `taps` (conv1d with padding n_taps / 2, i.e. cross-correlation) when taps is non-null:
+ *   sc      [R,B,n,n] = |mag_d_j - mag_r_i|_F / |mag_d_j|_F    (the reference hands (reals, decoded) to auraloss as
+ *                                                               (input, target): the norm below is the estimate's)
+ *   log_mag [R,B,n,n] = mean |log mag_r_i - log mag_d_j|
+ *   lin_mag [R,B,n,n] = mean |mag_r_i - mag_d_j|
+ *   l1, l2  [B,n,n]   = mean |r_i - d_j|, mean (r_i - d_j)^2 of the unfiltered signals
+ * all fp64 host arrays; each may be NULL.  A table whose weight (w_sc, w_log_mag, w_lin_mag) is zero is filled with
+ * zeros: the reference does not evaluate that term.  Every sum has a fixed order: two calls give identical bits.
+ * DSN_EINVAL, before any launch: n > 4; more than 16 resolutions; an FFT size that is not a power of two from 32 to
+ * 2048; win outside [1, fft]; hop < 1; L <= max(fft) / 2 (reflect padding undefined); an even tap count or more
+ * than 127 taps. */
+typedef struct DsnMrstftConfig {
+  int n_res;
+  const int *fft, *hop, *win;      /* host arrays [n_res] */
+  float w_sc, w_log_mag, w_lin_mag;
+  const float* taps;               /* host [n_taps]; NULL: no prefilter */
+  int n_taps;
+} DsnMrstftConfig;
+typedef struct DsnMrstftOut {
+  double *sc, *log_mag, *lin_mag, *l1, *l2;
+} DsnMrstftOut;
+int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int B, int n, int L,
+                    const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream);
+
 /* introspection for benchmarks / tests */
 int dsn_enable_graphs(dsn_ctx* ctx, int enable);          /* hipGraph replay of sample/decode */
 int64_t dsn_workspace_bytes(const dsn_ctx* ctx);
