@@ -371,23 +371,28 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
   }
 }
 
+// largest dynamic LDS request the kernels are allowed (the CU's 160 KB)
+constexpr size_t ATT_LDS_LIMIT = 160 * 1024;
+
 template <int P, int F16, int DH>
-void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S, int H, unsigned char* o8s,
-              hipStream_t st) {
+hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S, int H, unsigned char* o8s,
+                    hipStream_t st) {
   const int nkt = (S + 15) / 16;
-  if (nkt > 16) {  // more than 256 keys: blocked keys + online softmax
+  const size_t sm = (size_t)P * nkt * 16 * DH * sizeof(op16_t);
+  // more than 256 keys, or a whole-sequence V that does not fit in LDS (two planes of a 256-wide head beyond 160 keys:
+  // nkt x 16 KB): blocked keys + online softmax, at most 128 KB
+  if (nkt > 16 || sm > ATT_LDS_LIMIT) {
     const size_t sml = (size_t)P * 128 * DH * sizeof(op16_t);
     static std::atomic<unsigned long long> attr_l{0};
     if (dsn_first_use_on_device(attr_l)) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<P, F16, DH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
     }
     const int W = 4;  // measured (1 / 2 / 4 / 8): NCSN++ 944 tokens 7.48 / 7.17 / 7.14 / 7.31 ms per call, DiT 301 tokens 32.5 / 26.5 / 23.4 / 25.0 us
     hipLaunchKernelGGL((attention_long_kernel<P, F16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sml, st, qkv, ps,
                        out, out_ps, S, H, o8s);
-    return;
+    return hipGetLastError();
   }
-  const size_t sm = (size_t)P * nkt * 16 * DH * sizeof(op16_t);
   if (nkt <= 4) {
     // waves per workgroup: each takes one query tile of the same (item, head) and they stage V once
     const int W = 3;  // measured at S = 33 (3 query tiles): 12.9 / 12.6 / 12.3 / 12.5 us for 1..4
@@ -397,7 +402,7 @@ void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S
     static std::atomic<unsigned long long> attr{0};
     if (dsn_first_use_on_device(attr)) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel<P, F16, 16, DH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
     }
     // wide heads stage a large V block (DH * nkt * 32 B): share it between the query tiles' waves
     // the query tiles of an (item, head) share workgroups of up to 8 waves: V is staged once per workgroup (it used to be
@@ -407,26 +412,28 @@ void launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S
     hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st,
                        qkv, ps, out, out_ps, S, H, o8s);
   }
+  return hipGetLastError();
 }
 
 template <int DH>
-void launch_dh(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H, unsigned char* o8s,
-               hipStream_t st) {
+hipError_t launch_dh(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H,
+                     unsigned char* o8s, hipStream_t st) {
   const int P = PL_COUNT(pl), f16 = PL_F16(pl);
-  if (P == 1 && !f16) launch_t<1, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  else if (P == 2 && !f16) launch_t<2, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  else if (P == 1) launch_t<1, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  else launch_t<2, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
+  if (P == 1 && !f16) return launch_t<1, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
+  if (P == 2 && !f16) return launch_t<2, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
+  if (P == 1) return launch_t<1, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
+  return launch_t<2, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
 }
 
 }  // namespace
 
-// dh = head width (64: DiT; 64/128/256: the single-head NCSN++ attention blocks)
-int launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H, int dh,
-                          hipStream_t st, unsigned char* out_fp8_scale) {
-  if (dh == 64) launch_dh<64>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
-  else if (dh == 128) launch_dh<128>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
-  else if (dh == 256) launch_dh<256>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
-  else return -1;
-  return 0;
+// dh = head width (64: DiT; 64/128/256: the single-head NCSN++ attention blocks).  Returns the launch status
+// (hipErrorNotSupported: no kernel for this head width).
+hipError_t launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H, int dh,
+                                 hipStream_t st, unsigned char* out_fp8_scale) {
+  if (B < 1 || S < 1 || H < 1) return hipErrorInvalidValue;
+  if (dh == 64) return launch_dh<64>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
+  if (dh == 128) return launch_dh<128>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
+  if (dh == 256) return launch_dh<256>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
+  return hipErrorNotSupported;
 }

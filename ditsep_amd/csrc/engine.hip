@@ -1180,7 +1180,10 @@ struct dsn_ctx {
         }
       }
       prof_launch("dit.attention", (double)M * D * 2.0 * P * 4.0, st,
-                  [&] { launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8); });
+                  [&] {
+                    const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8);
+                    if (e != hipSuccess) fail(DSN_EHIP, "dit attention launch failed: %s", hipGetErrorString(e));
+                  });
       }
       {
         Tag tg(this, "dit.attn_out");
@@ -3280,6 +3283,135 @@ int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream) {
       }
       default:
         fail(DSN_EINVAL, "test_gemm: unknown kernel %d", t->kernel);
+    }
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// Test hook: one launch wrapper of the non-GEMM kernels with the caller's arguments (include/ditsep_hip.h).
+int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
+  return guarded(ctx, [&] {
+    hipStream_t st = (hipStream_t)stream;
+    const int P = ctx->P, PL = ctx->PL;
+    if (!t) fail(DSN_EINVAL, "test_kernel: null descriptor");
+    // fp32 operand -> the engine's operand planes (plane stride = numel)
+    auto planes_of = [&](const char* name, const float* src, long n) {
+      if (!src || n <= 0 || n % 4 != 0) fail(DSN_EINVAL, "test_kernel: operand %s missing or its numel %% 4 != 0", name);
+      op16_t* p = ctx->wsbuf<op16_t>(name, n * P);
+      launch_to_planes(src, p, n, PL, n, st);
+      return p;
+    };
+    op16_t* oplanes = reinterpret_cast<op16_t*>(t->out_planes);
+    switch (t->kind) {
+      case DSN_TK_ATTENTION: {
+        if (t->B < 1 || t->S < 1 || t->H < 1) fail(DSN_EINVAL, "test_kernel attention: B, S, H must be positive");
+        const long D = (long)t->H * t->dh, n = (long)t->B * t->S * 3 * D;
+        if (t->a_numel != n) fail(DSN_EINVAL, "test_kernel attention: a_numel %ld != B*S*3*H*dh = %ld", (long)t->a_numel, n);
+        if (!!t->out_fp8 != !!t->out_fp8_scale || (!t->out_fp8 && !oplanes))
+          fail(DSN_EINVAL, "test_kernel attention: needs out_planes, or out_fp8 with out_fp8_scale");
+        if (t->out_fp8 && D % 32 != 0) fail(DSN_EINVAL, "test_kernel attention: fp8 output needs H*dh %% 32 == 0");
+        const op16_t* qkv = planes_of("tk_a", t->a, n);
+        const hipError_t e = launch_attention_mfma(qkv, n, t->out_fp8 ? reinterpret_cast<op16_t*>(t->out_fp8) : oplanes,
+                                                   t->out_ps, PL, t->B, t->S, t->H, t->dh, st, t->out_fp8_scale);
+        if (e == hipErrorNotSupported) fail(DSN_EINVAL, "test_kernel attention: unsupported head width %d", t->dh);
+        if (e != hipSuccess) fail(DSN_EHIP, "test_kernel attention: launch failed: %s", hipGetErrorString(e));
+        break;
+      }
+      case DSN_TK_QKV_ATTENTION: {
+        if (t->B < 1 || t->S < 1 || t->D < 4) fail(DSN_EINVAL, "test_kernel qkv_attention: B, S, D must be positive");
+        const long M = (long)t->B * t->S;
+        if (t->a_numel != M * t->D || t->w_numel != 3L * t->D * t->D)
+          fail(DSN_EINVAL, "test_kernel qkv_attention: a_numel / w_numel do not match [B*S][D] / [3 D][D]");
+        if (!t->rope_cos || !t->rope_sin) fail(DSN_EINVAL, "test_kernel qkv_attention: rope_cos / rope_sin [S][32] missing");
+        QkvAttnDesc q;
+        memset(&q, 0, sizeof q);
+        q.A = planes_of("tk_a", t->a, t->a_numel);
+        q.W = planes_of("tk_w", t->w, t->w_numel);
+        launch_rope_tables(t->rope_cos, t->rope_sin, t->S, 32, st);
+        q.bias = t->bias;
+        q.rope_cos = t->rope_cos;
+        q.rope_sin = t->rope_sin;
+        q.out = t->out_fp8 ? nullptr : oplanes;
+        q.out8 = t->out_fp8;
+        q.out8_scale = t->out_fp8_scale;
+        q.M = (int)M;
+        q.D = t->D;
+        q.H = t->H;
+        q.S = t->S;
+        q.ipp = t->ipp;
+        q.q_scale = 0.125f;
+        const hipError_t e = qkv_attention_launch(q, PL, st);
+        if (e != hipSuccess)
+          fail(DSN_EHIP, "test_kernel qkv_attention: refused or failed: %s (D=%d H=%d S=%d ipp=%d planes=%d)",
+               hipGetErrorString(e), t->D, t->H, t->S, t->ipp, P);
+        break;
+      }
+      case DSN_TK_RESIDUAL_NORM: {
+        if (!t->x || t->rows < 1 || t->D < 4 || t->D % 4 != 0 || t->D > 4096)
+          fail(DSN_EINVAL, "test_kernel residual_norm: needs x, rows >= 1, D %% 4 == 0, D <= 4096 (D=%d)", t->D);
+        if (t->nslab < 0 || t->nslab > 8 || (t->nslab > 0 && !t->slabs))
+          fail(DSN_EINVAL, "test_kernel residual_norm: nslab %d outside [0, 8] or slabs missing", t->nslab);
+        if (t->do_norm && !t->gamma) fail(DSN_EINVAL, "test_kernel residual_norm: do_norm needs gamma");
+        if (!!t->out_fp8 != !!t->out_fp8_scale || (!t->out_fp8 && !oplanes))
+          fail(DSN_EINVAL, "test_kernel residual_norm: needs out_planes, or out_fp8 with out_fp8_scale");
+        if (t->out_fp8 && t->D % 32 != 0) fail(DSN_EINVAL, "test_kernel residual_norm: fp8 output needs D %% 32 == 0");
+        launch_residual_norm(t->x, t->slabs, t->nslab, t->slab_stride, t->bias, t->gamma, t->beta,
+                             t->out_fp8 ? reinterpret_cast<op16_t*>(t->out_fp8) : oplanes, t->out_ps, PL, t->rows, t->D,
+                             t->eps, t->do_norm, st, t->out_fp8_scale);
+        break;
+      }
+      case DSN_TK_GN_STATS:
+      case DSN_TK_GN_APPLY: {
+        if (!t->x || t->B < 1 || t->HW < 1 || t->C % 4 != 0 || !gn_groups_fit(t->C, t->C) || t->C > 1024 ||
+            t->rstride < t->C || t->rstride % 4 != 0)
+          fail(DSN_EINVAL, "test_kernel group norm: unsupported view (C=%d rstride=%d HW=%d)", t->C, t->rstride, t->HW);
+        if (t->kind == DSN_TK_GN_STATS) {
+          if (!t->out_f32) fail(DSN_EINVAL, "test_kernel gn_stats: out_f32 (the statistics) missing");
+          launch_gn_stats(t->x, t->bstride, t->rstride, t->C, t->B, t->HW, t->out_f32, st);
+        } else {
+          if (!t->stats || !t->gamma || !t->beta || (!t->out_f32 && !oplanes))
+            fail(DSN_EINVAL, "test_kernel gn_apply: stats, gamma, beta and an output are required");
+          launch_gn_apply(t->x, t->bstride, t->rstride, t->C, t->B, t->HW, t->stats, t->gamma, t->beta, t->eps, t->silu,
+                          t->out_f32, oplanes, t->out_ps, PL, st);
+        }
+        break;
+      }
+      case DSN_TK_FIR2D: {
+        if (!t->x || t->B < 1 || t->C < 4 || t->C % 4 != 0 || t->rstride < t->C || t->rstride % 4 != 0 || t->img_h < 1 ||
+            t->img_w < 1 || (!t->up && ((t->img_h | t->img_w) & 1)) || (!t->out_f32 && !oplanes))
+          fail(DSN_EINVAL, "test_kernel fir2d: unsupported view (C=%d rstride=%d %d x %d up=%d)", t->C, t->rstride,
+               t->img_h, t->img_w, t->up);
+        launch_fir2d(t->x, t->bstride, t->rstride, t->C, t->B, t->img_h, t->img_w, t->up, t->add, t->out_f32, oplanes,
+                     t->out_ps, PL, st);
+        break;
+      }
+      case DSN_TK_CONV_OUT1: {
+        // (the generic kernel reads 8-channel chunks and splits C into 4 quarters of whole float4s)
+        if (t->B < 1 || t->L < 1 || t->ktaps < 1 || (t->ktaps & 1) == 0 || t->C < 16 || t->C % 16 != 0 || !t->w ||
+            !t->out_f32)
+          fail(DSN_EINVAL, "test_kernel conv_out1: needs odd ktaps, C %% 16 == 0, w and out_f32 (C=%d ktaps=%d)", t->C,
+               t->ktaps);
+        const long n = (long)t->B * t->L * t->C;
+        if (t->a_numel != n) fail(DSN_EINVAL, "test_kernel conv_out1: a_numel != B*L*C");
+        if (((size_t)(64 + t->ktaps - 1) * (t->C + 4) + (size_t)t->ktaps * t->C + 256) * sizeof(float) > 160 * 1024)
+          fail(DSN_EINVAL, "test_kernel conv_out1: C=%d ktaps=%d does not fit in LDS", t->C, t->ktaps);
+        const op16_t* a = planes_of("tk_a", t->a, n);
+        launch_conv_out1(a, n, PL, t->w, t->out_f32, t->B, t->L, t->C, t->ktaps, t->apply_tanh, st);
+        break;
+      }
+      case DSN_TK_CONV_IN1: {
+        if (!t->x || !t->w || t->B < 1 || t->L < 1 || t->C < 1 || t->ktaps < 1 || (t->ktaps & 1) == 0 ||
+            (!t->out_f32 && !oplanes))
+          fail(DSN_EINVAL, "test_kernel conv_in1: needs wav (x), w, odd ktaps and an output (C=%d ktaps=%d)", t->C, t->ktaps);
+        if (t->act != DSN_ACT_NONE && t->act != DSN_ACT_ELU && t->act != DSN_ACT_SNAKE)
+          fail(DSN_EINVAL, "test_kernel conv_in1: unsupported activation %d", t->act);
+        if (t->act == DSN_ACT_SNAKE && (!t->act_a || !t->act_b)) fail(DSN_EINVAL, "test_kernel conv_in1: Snake needs act_a / act_b");
+        launch_conv_in1(t->x, t->w, t->bias, t->B, t->L, t->C, t->ktaps, t->out_f32, oplanes, t->out_ps, PL, t->act,
+                        t->act_a, t->act_b, st);
+        break;
+      }
+      default:
+        fail(DSN_EINVAL, "test_kernel: unknown kind %d", t->kind);
     }
     HIPCHK(hipGetLastError());
   });

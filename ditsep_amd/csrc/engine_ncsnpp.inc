@@ -412,8 +412,11 @@ void ncs_attention(const NcsnAttn& a, const View& x, int B, int HW, hipStream_t 
     d.q_scale = 1.f / sqrtf((float)a.c);
     run(d, st);
   }
-  if (launch_attention_mfma(qkv, rows * 3 * a.c, n.p, n.pps, PL, B, HW, 1, a.c, st) != 0)
-    fail(DSN_EINVAL, "unsupported attention width %d", a.c);
+  {
+    const hipError_t e = launch_attention_mfma(qkv, rows * 3 * a.c, n.p, n.pps, PL, B, HW, 1, a.c, st);
+    if (e == hipErrorNotSupported) fail(DSN_EINVAL, "unsupported attention width %d", a.c);
+    if (e != hipSuccess) fail(DSN_EHIP, "ncsnpp attention launch failed (%d keys, width %d): %s", HW, a.c, hipGetErrorString(e));
+  }
   {
     GemmDesc d = base_desc(n.p, n.pps, a.out, B, HW, HW);
     set_out(d, x, x.f != nullptr, x.p != nullptr);

@@ -54,12 +54,13 @@ void launch_residual_norm(float* x, const float* slabs, int nslab, long slab_str
 // FourierFeatures: t[B], w[half] -> planes [B][2*half] = [cos(2 pi t w), sin(2 pi t w)]
 void launch_timestep_features(const float* t, const float* w, int B, int half, op16_t* out, long ps,
                               int planes, hipStream_t s);
-// MFMA attention over operand planes q|k|v [B*S][3*H*64] written by the fused QKV epilogue
-// (attention.hip); S <= 256.
+// MFMA attention over operand planes q|k|v [B*S][3*H*dh] written by the fused QKV epilogue (attention.hip): whole
+// sequences of up to 256 keys in registers where their V fits in LDS, blocked keys with an online softmax otherwise.
 // out_fp8_scale != null: `out` receives fp8 (e4m3) bytes [B*S][H*dh] and out_fp8_scale the E8M0 block scales
 // [B*S][H*dh/32] (MX operand of the fp8 out-projection) instead of 16-bit planes.
-int launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H, int dh,
-                          hipStream_t s, unsigned char* out_fp8_scale = nullptr);   // dh in {64,128,256}; -1: unsupported width
+// dh in {64,128,256} (hipErrorNotSupported otherwise); returns the launch status
+hipError_t launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H,
+                                 int dh, hipStream_t s, unsigned char* out_fp8_scale = nullptr);
 void launch_rope_tables(float* cos_t, float* sin_t, int S, int rot, hipStream_t s);
 
 // ---- Oobleck edges -------------------------------------------------------------

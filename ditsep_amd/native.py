@@ -31,7 +31,7 @@ EXPORTS = [
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
-    "dsn_test_gemm", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
+    "dsn_test_gemm", "dsn_test_kernel", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
 ]
 
@@ -143,6 +143,28 @@ class DsnTestGemm(C.Structure):
     ]
 
 
+# dsn_test_kernel (include/ditsep_hip.h): which launch wrapper of the non-GEMM kernels runs
+TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn_stats": 4, "gn_apply": 5, "fir2d": 6,
+                     "conv_out1": 7, "conv_in1": 8}
+
+
+class DsnTestKernel(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int), ("B", C.c_int), ("S", C.c_int), ("H", C.c_int), ("dh", C.c_int), ("D", C.c_int),
+        ("ipp", C.c_int), ("rows", C.c_int), ("nslab", C.c_int), ("do_norm", C.c_int), ("eps", C.c_float),
+        ("slab_stride", C.c_int64),
+        ("C", C.c_int), ("HW", C.c_int), ("rstride", C.c_int), ("img_h", C.c_int), ("img_w", C.c_int), ("up", C.c_int),
+        ("silu", C.c_int), ("bstride", C.c_int64),
+        ("L", C.c_int), ("ktaps", C.c_int), ("apply_tanh", C.c_int), ("act", C.c_int),
+        ("a", C.c_void_p), ("a_numel", C.c_int64), ("w", C.c_void_p), ("w_numel", C.c_int64), ("x", C.c_void_p),
+        ("slabs", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("stats", C.c_void_p),
+        ("add", C.c_void_p), ("act_a", C.c_void_p), ("act_b", C.c_void_p), ("rope_cos", C.c_void_p),
+        ("rope_sin", C.c_void_p),
+        ("out_f32", C.c_void_p), ("out_planes", C.c_void_p), ("out_ps", C.c_int64), ("out_fp8", C.c_void_p),
+        ("out_fp8_scale", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -196,6 +218,7 @@ def load_library() -> C.CDLL:
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.dsn_test_igemm.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.dsn_test_gemm.argtypes = [vp, C.POINTER(DsnTestGemm), vp]
+    lib.dsn_test_kernel.argtypes = [vp, C.POINTER(DsnTestKernel), vp]
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
     lib.dsn_stoi.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
@@ -805,6 +828,28 @@ class Engine:
             elif v is not None:
                 setattr(t, k, v)
         self._check(self.lib.dsn_test_gemm(self.ctx, C.byref(t), self._stream()), f"dsn_test_gemm({kernel})")
+
+    def test_kernel(self, kind, **kw):
+        """Run one launch wrapper of the non-GEMM kernels (dsn_test_kernel, include/ditsep_hip.h) on caller-owned device
+        tensors.  Every keyword is the DsnTestKernel field of the same name; tensors are passed by pointer (fp32, but
+        out_planes int16 [P][out_ps] and out_fp8 / out_fp8_scale uint8), `a` / `w` also set a_numel / w_numel."""
+        t = DsnTestKernel()
+        t.kind = TEST_KERNEL_KINDS[kind]
+        keep = []
+        dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8}
+        for k, v in kw.items():
+            if isinstance(v, torch.Tensor):
+                assert v.is_cuda and v.dtype == dtypes.get(k, torch.float32), k
+                assert v.is_contiguous() or k == "x", k      # (x may be a view into a wider buffer: its base pointer)
+                keep.append(v)
+                setattr(t, k, v.data_ptr())
+                if k in ("a", "w"):
+                    setattr(t, k + "_numel", v.numel())
+                if k == "out_planes" and "out_ps" not in kw:
+                    t.out_ps = v.shape[-1] if v.dim() > 1 else v.numel()
+            elif v is not None:
+                setattr(t, k, v)
+        self._check(self.lib.dsn_test_kernel(self.ctx, C.byref(t), self._stream()), f"dsn_test_kernel({kind})")
 
     def decode_planes(self, raw):
         """int16 operand planes [P][n] as written by a GEMM epilogue -> float64 values (hi, or hi + lo)."""

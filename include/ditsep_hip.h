@@ -363,7 +363,7 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
                      int64_t* launches);
 
 /* ---- NOT PART OF THE ABI ------------------------------------------------------------------------------------
- * dsn_test_igemm, dsn_test_gemm, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests, repro scripts and
+ * dsn_test_igemm, dsn_test_gemm, dsn_test_kernel, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests, repro scripts and
  * kernel sweeps.  They name internal workspace buffers and kernel variants, change without notice, and a binding of
  * the reference-facing interface must not use them. */
 /* Test hook: run the implicit-GEMM kernel on caller-provided fp32 operands.
@@ -427,6 +427,53 @@ typedef struct DsnTestGemm {
   int64_t slab_stride;
 } DsnTestGemm;
 int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream);
+
+/* Test hook: run ONE launch wrapper of the non-GEMM kernels (ditsep_amd/csrc/kernels.h, qkv_attention_launch) with the
+ * caller's arguments on caller-owned device tensors.  Which kernel runs is the wrapper's own dispatch.  `a` (and `w` of
+ * QKV_ATTENTION) are fp32 tensors rounded to the engine's operand planes first; every other tensor is passed through.
+ * Outputs land in caller-owned buffers.  An argument the wrapper does not support fails the call by name. */
+enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3, DSN_TK_GN_STATS = 4,
+       DSN_TK_GN_APPLY = 5, DSN_TK_FIR2D = 6, DSN_TK_CONV_OUT1 = 7, DSN_TK_CONV_IN1 = 8 };
+typedef struct DsnTestKernel {
+  int kind;                   /* DSN_TK_* */
+  /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
+   * QKV_ATTENTION: a = LayerNorm output [B*S][D], w = to_qkv [3*D][D], bias [3*D] (optional), rope_cos / rope_sin
+   *   [S][32] caller-owned buffers that launch_rope_tables fills here, ipp items per panel; q scale 1/8 */
+  int B, S, H, dh, D, ipp;
+  /* RESIDUAL_NORM: x [rows][D] (updated in place), slabs nslab x slab_stride, bias / gamma / beta [D] */
+  int rows, nslab, do_norm;
+  float eps;
+  int64_t slab_stride;
+  /* GN_STATS / GN_APPLY / FIR2D: view x + b*bstride + row*rstride + channel of B items, HW rows (FIR2D: img_h x img_w),
+   * C channels.  GN_STATS -> out_f32 = stats; GN_APPLY reads `stats`; FIR2D: `up`, `add` (optional, output shape) */
+  int C, HW, rstride, img_h, img_w, up, silu;
+  int64_t bstride;
+  /* CONV_OUT1: a = input [B*L][C] (planes), w [ktaps][C] fp32 -> out_f32 [B*L].  CONV_IN1: x = wav [B][L], w [C][ktaps],
+   * bias [C] -> out_f32 / out_planes [B*L][C], act (0 none, 1 ELU, 2 Snake with act_a / act_b [C]) */
+  int L, ktaps, apply_tanh, act;
+  const float* a;
+  int64_t a_numel;            /* a multiple of 4 */
+  const float* w;
+  int64_t w_numel;
+  float* x;
+  const float* slabs;
+  const float* bias;
+  const float* gamma;
+  const float* beta;
+  const float* stats;
+  const float* add;
+  const float* act_a;
+  const float* act_b;
+  float* rope_cos;
+  float* rope_sin;
+  /* outputs */
+  float* out_f32;
+  int16_t* out_planes;        /* P planes of out_ps elements each, raw 16-bit operand bits */
+  int64_t out_ps;
+  uint8_t* out_fp8;           /* e4m3 bytes instead of planes, with out_fp8_scale (E8M0, one per 32 columns) */
+  uint8_t* out_fp8_scale;
+} DsnTestKernel;
+int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 
 /* Development hook: copy `count` floats of a named workspace buffer to host memory. */
 int dsn_debug_read(dsn_ctx* ctx, const char* name, float* host, int64_t count);

@@ -99,10 +99,8 @@ def test_gemm_kernel_tests_cover_every_instantiation():
     assert sorted(int(m) for m in re.findall(r"\bSK\((\d+)\)", sk)) == SKINNY_MT
 
 
-def test_test_gemm_struct_matches_header():
-    """native.DsnTestGemm mirrors struct DsnTestGemm of include/ditsep_hip.h field by field"""
-    hdr = open(os.path.join(ROOT, "include", "ditsep_hip.h")).read()
-    body = hdr[hdr.index("typedef struct DsnTestGemm {"):hdr.index("} DsnTestGemm;")]
+def _header_struct_fields(hdr, struct):
+    body = hdr[hdr.index("typedef struct %s {" % struct):hdr.index("} %s;" % struct)]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
     names = []
     for decl in body.split(";"):
@@ -110,7 +108,23 @@ def test_test_gemm_struct_matches_header():
         if decl:
             names += [re.sub(r"^.*?[\s*]+(\w+)$", r"\1", d.strip()) if i == 0 else d.strip().lstrip("*")
                       for i, d in enumerate(decl.split(","))]
-    assert names == [f[0] for f in native.DsnTestGemm._fields_]
+    return names
+
+
+def test_test_gemm_struct_matches_header():
+    """native.DsnTestGemm mirrors struct DsnTestGemm of include/ditsep_hip.h field by field"""
+    hdr = open(os.path.join(ROOT, "include", "ditsep_hip.h")).read()
+    assert _header_struct_fields(hdr, "DsnTestGemm") == [f[0] for f in native.DsnTestGemm._fields_]
+
+
+def test_test_kernel_struct_matches_header():
+    """native.DsnTestKernel mirrors struct DsnTestKernel field by field, and TEST_KERNEL_KINDS the DSN_TK_* values"""
+    hdr = open(os.path.join(ROOT, "include", "ditsep_hip.h")).read()
+    assert _header_struct_fields(hdr, "DsnTestKernel") == [f[0] for f in native.DsnTestKernel._fields_]
+    kinds = dict(re.findall(r"DSN_TK_(\w+) = (\d+)", hdr))
+    assert {k.lower(): int(v) for k, v in kinds.items()} == native.TEST_KERNEL_KINDS
+    # same layout as the C struct: ints and floats 4 bytes, pointers and int64 8, natural alignment
+    assert ctypes.sizeof(native.DsnTestKernel) % 8 == 0
 
 
 def test_missing_library_fails_loudly(monkeypatch):

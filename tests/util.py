@@ -12,6 +12,26 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm())
 
 
+def mx_exponent(x: torch.Tensor) -> torch.Tensor:
+    """E8M0 exponent k of each block of 32 along the last dim: 2^k >= amax/448, k from the float exponent exactly as
+    csrc/common.h::dsn_mx_exp (int32, one per block, flattened)"""
+    amax = x.float().reshape(-1, 32).abs().amax(dim=1)
+    scaled = (amax * torch.tensor(1.0 / 448.0, dtype=torch.float32)).float()
+    bits = scaled.view(torch.int32)
+    k = ((bits >> 23) & 0xff) - 127 + ((bits & 0x7fffff) != 0).to(torch.int32)
+    return k.clamp(-126, 126)
+
+
+def mx_quant(x: torch.Tensor) -> torch.Tensor:
+    """CPU emulation of the device's fp8 operand format: blocks of 32 along the last dim, E8M0 scale 2^k with
+    2^k >= amax/448 (mx_exponent), e4m3 round-to-nearest."""
+    shp = x.shape
+    xb = x.float().reshape(-1, 32)
+    k = mx_exponent(x).float()
+    q = (xb * torch.exp2(-k)[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).float() * torch.exp2(k)[:, None]
+    return q.reshape(shp)
+
+
 def make_engine(dcfg=None, dsd=None, vcfg=None, vsd=None, precision=2, ncfg=None, nsd=None, **kw):
     from ditsep_amd import native
 
