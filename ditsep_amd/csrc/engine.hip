@@ -3410,6 +3410,43 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
                         t->act_a, t->act_b, st);
         break;
       }
+      case DSN_TK_RU_FUSED: {
+        if (t->B < 1 || t->L < 1) fail(DSN_EINVAL, "test_kernel ru_fused: B and L must be positive (B=%d L=%d)", t->B, t->L);
+        const long n = (long)t->B * t->L * 128;
+        if (t->a_numel != n || t->w_numel != 128L * 7 * 128 || t->w2_numel != 128L * 128)
+          fail(DSN_EINVAL, "test_kernel ru_fused: a_numel / w_numel / w2_numel do not match [B][L][128] / [128][7*128] / "
+                           "[128][128]");
+        if (!t->x || !t->bias || !t->bias2) fail(DSN_EINVAL, "test_kernel ru_fused: x, bias or bias2 missing");
+        if (oplanes && t->out_ps < n) fail(DSN_EINVAL, "test_kernel ru_fused: out_ps %ld < B*L*128", (long)t->out_ps);
+        RuDesc d;
+        memset(&d, 0, sizeof d);
+        d.A = planes_of("tk_a", t->a, n);
+        d.a_ps = n;
+        d.W7 = planes_of("tk_w", t->w, t->w_numel);
+        d.w7_ps = t->w_numel;
+        d.W1 = planes_of("tk_w2", t->w2, t->w2_numel);
+        d.w1_ps = t->w2_numel;
+        d.X = t->x;
+        d.b7 = t->bias;
+        d.b1 = t->bias2;
+        d.out_f32 = t->out_f32;
+        d.out_planes = oplanes;
+        d.out_ps = t->out_ps;
+        d.act_mid = t->act;
+        d.mid_a = t->act_a;
+        d.mid_b = t->act_b;
+        d.act_out = t->act_out;
+        d.out_a = t->out_act_a;
+        d.out_b = t->out_act_b;
+        d.S = t->B;
+        d.L = t->L;
+        d.dil = t->dil;
+        const hipError_t e = ru_fused_launch(d, PL, st);
+        if (e != hipSuccess)
+          fail(DSN_EHIP, "test_kernel ru_fused: refused or failed: %s (S=%d L=%d dil=%d act %d / %d)", hipGetErrorString(e),
+               t->B, t->L, t->dil, t->act, t->act_out);
+        break;
+      }
       default:
         fail(DSN_EINVAL, "test_kernel: unknown kind %d", t->kind);
     }

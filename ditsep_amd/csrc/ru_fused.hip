@@ -17,6 +17,7 @@
 #include "igemm.h"
 #include "kernels.h"
 #include <cstdlib>
+#include <functional>
 
 namespace {
 
@@ -472,9 +473,26 @@ hipError_t launch2_t(const RuDesc& d, hipStream_t st) {
   return hipGetLastError();
 }
 
+// what the kernels do with an activation: none / ELU / Snake, and Snake reads both of its per-channel vectors
+static bool ru_act_ok(int kind, const float* a, const float* b) {
+  if (kind == DSN_ACT_SNAKE) return a && b;
+  return kind == DSN_ACT_NONE || kind == DSN_ACT_ELU;
+}
+
 hipError_t ru_fused_launch(const RuDesc& d, int pl, hipStream_t st) {
   if (d.dil < 1 || d.dil > 9 || d.S <= 0 || d.L <= 0) return hipErrorInvalidValue;
+  if (!d.A || !d.X || !d.W7 || !d.W1 || !d.b7 || !d.b1 || (!d.out_f32 && !d.out_planes)) return hipErrorInvalidValue;
+  if (!ru_act_ok(d.act_mid, d.mid_a, d.mid_b)) return hipErrorInvalidValue;
+  if (d.out_planes && !ru_act_ok(d.act_out, d.out_a, d.out_b)) return hipErrorInvalidValue;
   const int P = PL_COUNT(pl), f16 = PL_F16(pl);
+  if (d.out_planes) {  // a workgroup's neighbours read its rows of A as their halo: no plane of the output may overlap one
+    const long n = (long)d.S * d.L * C;
+    for (int p = 0; p < P; ++p)
+      for (int q = 0; q < P; ++q) {
+        const op16_t *a = d.A + p * d.a_ps, *o = d.out_planes + q * d.out_ps;
+        if (std::less<const op16_t*>()(a, o + n) && std::less<const op16_t*>()(o, a + n)) return hipErrorInvalidValue;
+      }
+  }
   const bool v1 = getenv("DSN_RU_V1") != nullptr;  // read per launch: tests flip it inside one process
   if (P == 1 && !v1) return f16 ? launch2_t<1>(d, st) : launch2_t<0>(d, st);
   if (P == 1) return f16 ? launch_t<1, 1>(d, st) : launch_t<1, 0>(d, st);

@@ -145,7 +145,7 @@ class DsnTestGemm(C.Structure):
 
 # dsn_test_kernel (include/ditsep_hip.h): which launch wrapper of the non-GEMM kernels runs
 TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn_stats": 4, "gn_apply": 5, "fir2d": 6,
-                     "conv_out1": 7, "conv_in1": 8}
+                     "conv_out1": 7, "conv_in1": 8, "ru_fused": 9}
 
 
 class DsnTestKernel(C.Structure):
@@ -156,10 +156,12 @@ class DsnTestKernel(C.Structure):
         ("C", C.c_int), ("HW", C.c_int), ("rstride", C.c_int), ("img_h", C.c_int), ("img_w", C.c_int), ("up", C.c_int),
         ("silu", C.c_int), ("bstride", C.c_int64),
         ("L", C.c_int), ("ktaps", C.c_int), ("apply_tanh", C.c_int), ("act", C.c_int),
-        ("a", C.c_void_p), ("a_numel", C.c_int64), ("w", C.c_void_p), ("w_numel", C.c_int64), ("x", C.c_void_p),
-        ("slabs", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("stats", C.c_void_p),
-        ("add", C.c_void_p), ("act_a", C.c_void_p), ("act_b", C.c_void_p), ("rope_cos", C.c_void_p),
-        ("rope_sin", C.c_void_p),
+        ("dil", C.c_int), ("act_out", C.c_int),
+        ("a", C.c_void_p), ("a_numel", C.c_int64), ("w", C.c_void_p), ("w_numel", C.c_int64), ("w2", C.c_void_p),
+        ("w2_numel", C.c_int64), ("x", C.c_void_p),
+        ("slabs", C.c_void_p), ("bias", C.c_void_p), ("bias2", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+        ("stats", C.c_void_p), ("add", C.c_void_p), ("act_a", C.c_void_p), ("act_b", C.c_void_p),
+        ("out_act_a", C.c_void_p), ("out_act_b", C.c_void_p), ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
         ("out_f32", C.c_void_p), ("out_planes", C.c_void_p), ("out_ps", C.c_int64), ("out_fp8", C.c_void_p),
         ("out_fp8_scale", C.c_void_p),
     ]
@@ -832,7 +834,7 @@ class Engine:
     def test_kernel(self, kind, **kw):
         """Run one launch wrapper of the non-GEMM kernels (dsn_test_kernel, include/ditsep_hip.h) on caller-owned device
         tensors.  Every keyword is the DsnTestKernel field of the same name; tensors are passed by pointer (fp32, but
-        out_planes int16 [P][out_ps] and out_fp8 / out_fp8_scale uint8), `a` / `w` also set a_numel / w_numel."""
+        out_planes int16 [P][out_ps] and out_fp8 / out_fp8_scale uint8), `a` / `w` / `w2` also set their _numel field."""
         t = DsnTestKernel()
         t.kind = TEST_KERNEL_KINDS[kind]
         keep = []
@@ -843,7 +845,7 @@ class Engine:
                 assert v.is_contiguous() or k == "x", k      # (x may be a view into a wider buffer: its base pointer)
                 keep.append(v)
                 setattr(t, k, v.data_ptr())
-                if k in ("a", "w"):
+                if k in ("a", "w", "w2"):
                     setattr(t, k + "_numel", v.numel())
                 if k == "out_planes" and "out_ps" not in kw:
                     t.out_ps = v.shape[-1] if v.dim() > 1 else v.numel()

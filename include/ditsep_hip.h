@@ -428,12 +428,13 @@ typedef struct DsnTestGemm {
 } DsnTestGemm;
 int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream);
 
-/* Test hook: run ONE launch wrapper of the non-GEMM kernels (ditsep_amd/csrc/kernels.h, qkv_attention_launch) with the
- * caller's arguments on caller-owned device tensors.  Which kernel runs is the wrapper's own dispatch.  `a` (and `w` of
- * QKV_ATTENTION) are fp32 tensors rounded to the engine's operand planes first; every other tensor is passed through.
+/* Test hook: run ONE launch wrapper of the non-GEMM kernels (ditsep_amd/csrc/kernels.h, qkv_attention_launch,
+ * ru_fused_launch) with the caller's arguments on caller-owned device tensors.  Which kernel runs is the wrapper's own
+ * dispatch.  `a` (and `w` of QKV_ATTENTION, `w` / `w2` of RU_FUSED) are fp32 tensors rounded to the engine's operand planes
+ * first; every other tensor is passed through.
  * Outputs land in caller-owned buffers.  An argument the wrapper does not support fails the call by name. */
 enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3, DSN_TK_GN_STATS = 4,
-       DSN_TK_GN_APPLY = 5, DSN_TK_FIR2D = 6, DSN_TK_CONV_OUT1 = 7, DSN_TK_CONV_IN1 = 8 };
+       DSN_TK_GN_APPLY = 5, DSN_TK_FIR2D = 6, DSN_TK_CONV_OUT1 = 7, DSN_TK_CONV_IN1 = 8, DSN_TK_RU_FUSED = 9 };
 typedef struct DsnTestKernel {
   int kind;                   /* DSN_TK_* */
   /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
@@ -451,19 +452,29 @@ typedef struct DsnTestKernel {
   /* CONV_OUT1: a = input [B*L][C] (planes), w [ktaps][C] fp32 -> out_f32 [B*L].  CONV_IN1: x = wav [B][L], w [C][ktaps],
    * bias [C] -> out_f32 / out_planes [B*L][C], act (0 none, 1 ELU, 2 Snake with act_a / act_b [C]) */
   int L, ktaps, apply_tanh, act;
+  /* RU_FUSED: a = activated input [B][L][128] (planes), w = k7 weight [128][7*128] (k = tap*128 + cin) and w2 = 1x1
+   * weight [128][128] (planes), bias / bias2 [128], x = fp32 residual stream [B][L][128], dilation dil, act / act_a /
+   * act_b after the k7 conv, act_out / out_act_a / out_act_b on the output planes -> out_f32 (may be null, may be x)
+   * and / or out_planes, both [B][L][128] */
+  int dil, act_out;
   const float* a;
   int64_t a_numel;            /* a multiple of 4 */
   const float* w;
   int64_t w_numel;
+  const float* w2;
+  int64_t w2_numel;
   float* x;
   const float* slabs;
   const float* bias;
+  const float* bias2;
   const float* gamma;
   const float* beta;
   const float* stats;
   const float* add;
   const float* act_a;
   const float* act_b;
+  const float* out_act_a;
+  const float* out_act_b;
   float* rope_cos;
   float* rope_sin;
   /* outputs */
