@@ -270,24 +270,37 @@ struct dsn_ctx {
     if (e != hipSuccess) fail(DSN_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     HIPCHK(hipGraphLaunch(g.exec, st));
   }
-  // stream the engine enqueues on: the caller's in eager mode, its own (ordered after the
-  // caller's by an event) in graph mode
-  hipStream_t enter(hipStream_t caller, int which = 0) {
-    if (!use_graphs || profiling) return caller;
-    if (!own[which]) {
-      HIPCHK(hipStreamCreateWithFlags(&own[which], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&ev_in[which], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&ev_out[which], hipEventDisableTiming));
+  // `st` is the stream the engine enqueues on: the caller's in eager mode, its own (ordered after the
+  // caller's by an event) in graph mode.  leave() makes the caller's stream wait for that work; an exit by
+  // exception joins too (unchecked), so the caller is never left unordered with what was already enqueued.
+  struct StreamScope {
+    dsn_ctx* c;
+    hipStream_t caller, st;
+    int which;
+    bool joined = false;
+    StreamScope(dsn_ctx* ctx, hipStream_t caller_, int which_ = 0) : c(ctx), caller(caller_), st(caller_), which(which_) {
+      if (!c->use_graphs || c->profiling) return;
+      if (!c->own[which]) {
+        HIPCHK(hipStreamCreateWithFlags(&c->own[which], hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_in[which], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_out[which], hipEventDisableTiming));
+      }
+      HIPCHK(hipEventRecord(c->ev_in[which], caller));
+      HIPCHK(hipStreamWaitEvent(c->own[which], c->ev_in[which], 0));
+      st = c->own[which];
     }
-    HIPCHK(hipEventRecord(ev_in[which], caller));
-    HIPCHK(hipStreamWaitEvent(own[which], ev_in[which], 0));
-    return own[which];
-  }
-  void leave(hipStream_t caller, hipStream_t used, int which = 0) {
-    if (used == caller) return;
-    HIPCHK(hipEventRecord(ev_out[which], used));
-    HIPCHK(hipStreamWaitEvent(caller, ev_out[which], 0));
-  }
+    StreamScope(const StreamScope&) = delete;
+    void leave() {
+      joined = true;
+      if (st == caller) return;
+      HIPCHK(hipEventRecord(c->ev_out[which], st));
+      HIPCHK(hipStreamWaitEvent(caller, c->ev_out[which], 0));
+    }
+    ~StreamScope() {
+      if (joined || st == caller) return;
+      if (hipEventRecord(c->ev_out[which], st) == hipSuccess) (void)hipStreamWaitEvent(caller, c->ev_out[which], 0);
+    }
+  };
 
   // ---------------------------------------------------------------- memory
   void* dmalloc(size_t bytes) {
@@ -1339,21 +1352,24 @@ struct dsn_ctx {
     const float num = (float)(smin * smin) * a * b * (float)ls;
     return sqrtf(num / (float)(th + ls));
   }
+  // torch.linspace(start, end, steps) in fp32: step = (end-start)/(steps-1); symmetric fill
+  static std::vector<float> linspace32(float start, float end, int steps) {
+    std::vector<float> v((size_t)steps);
+    const float stp = steps > 1 ? (end - start) / (float)(steps - 1) : 0.f;
+    const int halfway = steps / 2;
+    for (int i = 0; i < steps; ++i) v[i] = i < halfway ? start + stp * (float)i : end - stp * (float)(steps - 1 - i);
+    return v;
+  }
   std::vector<float> t_override;  // scheduled sampler: explicit timesteps (first N used), empty = linspace
   Sched schedule(int N, float t_eps, float snr) const {
     Sched s;
     const double smin = cfg.sde_sigma_min, smax = cfg.sde_sigma_max, ls = log(smax / smin);
-    s.t.resize(N);
+    s.t = linspace32(1.f, t_eps, N);
     s.std.resize(N);
     s.step.resize(N);
     s.gain.resize(N);
     s.G.resize(N);
     s.g.resize(N);
-    // torch.linspace(1, eps, N) in fp32: step = (end-start)/(N-1); symmetric fill
-    const float start = 1.f, end = t_eps;
-    const float stp = N > 1 ? (end - start) / (float)(N - 1) : 0.f;
-    const int halfway = N / 2;
-    for (int i = 0; i < N; ++i) s.t[i] = i < halfway ? start + stp * (float)i : end - stp * (float)(N - 1 - i);
     if ((int)t_override.size() >= N)
       for (int i = 0; i < N; ++i) s.t[i] = t_override[i];
     const float sqdt = sqrtf((float)(1.0 / N));
@@ -1373,12 +1389,12 @@ struct dsn_ctx {
 
   // ---------------------------------------------------------------- sampler
   // y [B,1,Dl,T]; noise [(1+N(c+1))][B,n,Dl,T]; returns device pointer of the result
-  // vec_t = ones(B) * timesteps[i] for every step, uploaded once per (B, schedule)
-  void upload_timesteps(int B, int N, float t_eps, float snr, hipStream_t st) {
-    const Sched s = schedule(N, t_eps, snr);
+  // vec_t = ones(B) * t_per_step[i] for every step ("pc_t", [N][B]), uploaded once per (B, table)
+  void upload_step_times(const std::vector<float>& t_per_step, int B, hipStream_t st) {
+    const int N = (int)t_per_step.size();
     std::vector<float> ht((size_t)B * N);
     for (int i = 0; i < N; ++i)
-      for (int b = 0; b < B; ++b) ht[(size_t)i * B + b] = s.t[i];
+      for (int b = 0; b < B; ++b) ht[(size_t)i * B + b] = t_per_step[i];
     float* tv = wsbuf<float>("pc_t", (long)B * N);
     if (ht == tv_host && tv_B == B) return;
     HIPCHK(hipMemcpyAsync(tv, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice, st));
@@ -1386,6 +1402,25 @@ struct dsn_ctx {
     tv_host = ht;
     tv_B = B;
   }
+  // Every step's time embedding in one batch, off the per-call path (-1.3 % sampler time).  time_cache is only
+  // valid while the sampler pass that holds this object (or its graph capture) runs.
+  struct TimeEmbedPass {
+    TimeCache& cache;
+    TimeEmbedPass(dsn_ctx* c, const float* tv, int N, int B, hipStream_t st) : cache(c->time_cache) {
+      const bool dit = c->cfg.score_kind == DSN_SCORE_DIT;
+      const int width = dit ? c->cfg.dit_embed_dim : c->ncs_dense_total;
+      float* all = c->wsbuf<float>("te_all", (long)N * B * width);
+      Tag tg(c, "score.time_embed");
+      if (dit) c->dit_time_embed(tv, N * B, all, st);
+      else c->ncs_time_dense(tv, N * B, all, st);
+      cache.t0 = tv;
+      cache.rows = (long)N * B;
+      cache.data = all;
+      cache.width = width;
+    }
+    TimeEmbedPass(const TimeEmbedPass&) = delete;
+    ~TimeEmbedPass() { cache = TimeCache(); }
+  };
   struct PcOpts {
     int pred = DSN_PRED_REVERSE_DIFFUSION, corr = DSN_CORR_ALD, c = 1, denoise = 1;
     float snr = 0.5f, t_eps = 0.03f;
@@ -1403,22 +1438,7 @@ struct dsn_ctx {
     const Sched s = schedule(N, o.t_eps, o.snr);
     const float dt = (float)(1.0 / N);
     const float* z = noise;
-    struct CacheScope {  // the cache is only valid while this pass (or its graph capture) runs
-      TimeCache& c;
-      ~CacheScope() { c = TimeCache(); }
-    } cache_scope{time_cache};
-    {  // every step's time embedding in one batch, off the per-call path (-1.3 % sampler time)
-      const bool dit = cfg.score_kind == DSN_SCORE_DIT;
-      const int width = dit ? cfg.dit_embed_dim : ncs_dense_total;
-      float* all = wsbuf<float>("te_all", (long)N * B * width);
-      Tag tg(this, "score.time_embed");
-      if (dit) dit_time_embed(tv, N * B, all, st);
-      else ncs_time_dense(tv, N * B, all, st);
-      time_cache.t0 = tv;
-      time_cache.rows = (long)N * B;
-      time_cache.data = all;
-      time_cache.width = width;
-    }
+    TimeEmbedPass te(this, tv, N, B, st);
     launch_pc_prior(o.prior_mean ? o.prior_mean : y, o.prior_mean != nullptr, z, x, s.stdT, B, n, Dl, T, st);
     z += sz;
     const bool keep_mean = o.inter != nullptr;  // only `intermediate` reads the corrector's x_mean
@@ -1476,22 +1496,7 @@ struct dsn_ctx {
     const Sched s = schedule(N, o.t_eps, o.snr);  // timesteps = linspace(1, eps, N)
     const float dt = (float)(1.0 / N), sqdt = sqrtf(dt);
     const double ratio = (double)o.sigma_max / o.sigma_min, logsig = log(ratio);
-    struct CacheScope {
-      TimeCache& c;
-      ~CacheScope() { c = TimeCache(); }
-    } cache_scope{time_cache};
-    {
-      const bool dit = cfg.score_kind == DSN_SCORE_DIT;
-      const int width = dit ? cfg.dit_embed_dim : ncs_dense_total;
-      float* all = wsbuf<float>("te_all", (long)N * B * width);
-      Tag tg(this, "score.time_embed");
-      if (dit) dit_time_embed(tv, N * B, all, st);
-      else ncs_time_dense(tv, N * B, all, st);
-      time_cache.t0 = tv;
-      time_cache.rows = (long)N * B;
-      time_cache.data = all;
-      time_cache.width = width;
-    }
+    TimeEmbedPass te(this, tv, N, B, st);
     if (smix) launch_sigma_mix(y, smix, B, Dl * T, o.avg_len, st);
     const float* z = noise;
     float ev1, ev2;
@@ -1531,22 +1536,7 @@ struct dsn_ctx {
     const long sz = (long)B * n * Dl * T;
     float* x = wsbuf<float>("pc_x", sz);
     float* tv = wsbuf<float>("pc_t", (long)B * N);
-    struct CacheScope {
-      TimeCache& c;
-      ~CacheScope() { c = TimeCache(); }
-    } cache_scope{time_cache};
-    {
-      const bool dit = cfg.score_kind == DSN_SCORE_DIT;
-      const int width = dit ? cfg.dit_embed_dim : ncs_dense_total;
-      float* all = wsbuf<float>("te_all", (long)N * B * width);
-      Tag tg(this, "score.time_embed");
-      if (dit) dit_time_embed(tv, N * B, all, st);
-      else ncs_time_dense(tv, N * B, all, st);
-      time_cache.t0 = tv;
-      time_cache.rows = (long)N * B;
-      time_cache.data = all;
-      time_cache.width = width;
-    }
+    TimeEmbedPass te(this, tv, N, B, st);
     auto sig = [&](float t) { return sqrtf((c * (powf(k, 2.f * t) - 1.f)) / (2.f * logf(k))); };
     const std::vector<float> ts = sb_times(N, t_eps);
     const float sig_T = sig(1.f);
@@ -1574,13 +1564,45 @@ struct dsn_ctx {
     }
     return x;
   }
-  // torch.linspace(1, eps, N + 1) in fp32 (symmetric fill), entries 0..N
-  static std::vector<float> sb_times(int N, float t_eps) {
-    std::vector<float> ts((size_t)N + 1);
-    const int steps = N + 1;
-    const float stp = (t_eps - 1.f) / (float)(steps - 1);
-    for (int i = 0; i < steps; ++i) ts[i] = i < steps / 2 ? 1.f + stp * (float)i : t_eps - stp * (float)(steps - 1 - i);
-    return ts;
+  // torch.linspace(1, eps, N + 1), entries 0..N
+  static std::vector<float> sb_times(int N, float t_eps) { return linspace32(1.f, t_eps, N + 1); }
+
+  // injected standard normals, else draws 0.. of the device RNG stream for `seed`
+  static void stage_noise(float* dst, const float* src, long count, uint64_t seed, hipStream_t st) {
+    if (src) HIPCHK(hipMemcpyAsync(dst, src, sizeof(float) * count, hipMemcpyDeviceToDevice, st));
+    else launch_randn(dst, count, seed, 0, st);
+  }
+  // One call of dsn_pc_sample_ex / dsn_pc_sample_mix / dsn_sb_sample: stable workspace copies of the caller's
+  // tensors (graph replay needs fixed pointers), the step-time table, then `body(y, noise, prior_mean, stream)`
+  // eagerly or as the graph cached under `key`.  `result` names the buffer body returns (a replayed graph wrote
+  // the same one).
+  struct SamplerCall {
+    const float *y, *noise, *prior_mean;
+    uint64_t seed;
+    float* x_out;
+    int B, T;
+    long draws;
+    hipStream_t caller;
+  };
+  template <class F>
+  void run_sampler(const SamplerCall& a, const std::vector<float>& t_per_step, const char* key, const char* result,
+                   F&& body) {
+    if (!finalized) fail(DSN_ESTATE, "weights not finalized");
+    const long ysz = (long)a.B * cfg.latent_dim * a.T, sz = ysz * cfg.n_src;
+    float* yb = wsbuf<float>("pc_y", ysz);
+    float* nz = a.draws ? wsbuf<float>("pc_noise", sz * a.draws) : nullptr;
+    float* pm = a.prior_mean ? wsbuf<float>("pc_prior_mean", sz) : nullptr;
+    upload_step_times(t_per_step, a.B, a.caller);
+    StreamScope sc(this, a.caller);
+    HIPCHK(hipMemcpyAsync(yb, a.y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, sc.st));
+    if (pm) HIPCHK(hipMemcpyAsync(pm, a.prior_mean, sizeof(float) * sz, hipMemcpyDeviceToDevice, sc.st));
+    if (a.draws) stage_noise(nz, a.noise, sz * a.draws, a.seed, sc.st);
+    float* res = nullptr;
+    run_graphed(key, sc.st, [&](hipStream_t s2) { res = body(yb, nz, pm, s2); });
+    if (!res) res = wsbuf<float>(result, sz);
+    HIPCHK(hipMemcpyAsync(a.x_out, res, sizeof(float) * sz, hipMemcpyDeviceToDevice, sc.st));
+    sc.leave();
+    HIPCHK(hipGetLastError());
   }
 
   // ---------------------------------------------------------------- decoder
@@ -1992,10 +2014,6 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
     o.snr = opts->snr;
     o.t_eps = opts->timesteps ? opts->timesteps[N - 1] : opts->t_eps;
     o.inter = opts->intermediates;
-    hipStream_t caller = (hipStream_t)stream;
-    const int n = ctx->cfg.n_src, Dl = ctx->cfg.latent_dim;
-    const long ysz = (long)B * Dl * T, sz = ysz * n;
-    const long draws = o.draws(N);
     // free-form schedules / intermediates are not worth a graph cache entry each
     const bool graphs = ctx->use_graphs;
     if (opts->timesteps) ctx->t_override.assign(opts->timesteps, opts->timesteps + N);
@@ -2008,29 +2026,16 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
         c->t_override.clear();
       }
     } restore{ctx, graphs};
-    // stable workspace copies of the caller's tensors (graph replay needs fixed pointers)
-    float* yb = ctx->wsbuf<float>("pc_y", ysz);
-    float* nz = ctx->wsbuf<float>("pc_noise", sz * draws);
-    float* pm = opts->prior_mean ? ctx->wsbuf<float>("pc_prior_mean", sz) : nullptr;
-    o.prior_mean = pm;
-    ctx->upload_timesteps(B, N, o.t_eps, o.snr, caller);
-    hipStream_t st = ctx->enter(caller);
-    HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
-    if (pm) HIPCHK(hipMemcpyAsync(pm, opts->prior_mean, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    if (noise)
-      HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz * draws, hipMemcpyDeviceToDevice, st));
-    else
-      launch_randn(nz, sz * draws, seed, 0, st);
     char key[192];
     snprintf(key, sizeof key, "pc:%d:%d:%d:%d:%a:%a:%d:%d:%d:%d", B, T, N, o.c, o.snr, o.t_eps, o.denoise, o.pred,
-             o.corr, pm != nullptr);
-    float* res = nullptr;
-    ctx->run_graphed(key, st, [&](hipStream_t s2) { res = ctx->pc_sample(yb, nz, B, T, N, o, s2); });
-    if (!res) res = ctx->wsbuf<float>(o.denoise ? "pc_xm" : "pc_x", sz);  // replayed graph: same buffers
-    HIPCHK(hipMemcpyAsync(x_out, res, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st);
+             o.corr, opts->prior_mean != nullptr);
+    ctx->run_sampler({y, noise, opts->prior_mean, seed, x_out, B, T, o.draws(N), (hipStream_t)stream},
+                     ctx->schedule(N, o.t_eps, o.snr).t, key, o.denoise ? "pc_xm" : "pc_x",
+                     [&](const float* yb, const float* nz, const float* pm, hipStream_t s2) {
+                       o.prior_mean = pm;
+                       return ctx->pc_sample(yb, nz, B, T, N, o, s2);
+                     });
     if (nfe_out) *nfe_out = N * (o.c + 1);
-    HIPCHK(hipGetLastError());
   });
 }
 
@@ -2068,7 +2073,7 @@ int dsn_pc_sample_mix(dsn_ctx* ctx, const float* y, const float* noise, uint64_t
       fail(DSN_EINVAL, "dsn_pc_sample_mix: bad arguments");
     if (opts->predictor < 0 || opts->predictor > DSN_PRED_NONE || opts->corrector < 0 || opts->corrector > DSN_MIXCORR_NONE)
       fail(DSN_EINVAL, "dsn_pc_sample_mix: unknown predictor %d / corrector %d", opts->predictor, opts->corrector);
-    const int n = ctx->cfg.n_src, Dl = ctx->cfg.latent_dim;
+    const int n = ctx->cfg.n_src;
     if (n > 4) fail(DSN_EINVAL, "dsn_pc_sample_mix: at most 4 sources");
     if (!opts->prior_mix && n != 2)
       fail(DSN_EINVAL, "MixSDE.prior_sampling is written for 2 sources (reference sdes.py:347); use PriorMixSDE");
@@ -2086,25 +2091,15 @@ int dsn_pc_sample_mix(dsn_ctx* ctx, const float* y, const float* noise, uint64_t
     o.sigma_max = opts->sigma_max;
     o.snr = opts->snr;
     o.t_eps = opts->t_eps;
-    hipStream_t caller = (hipStream_t)stream;
-    const long ysz = (long)B * Dl * T, sz = ysz * n, draws = o.draws(N);
-    float* yb = ctx->wsbuf<float>("pc_y", ysz);
-    float* nz = ctx->wsbuf<float>("pc_noise", sz * draws);
-    ctx->upload_timesteps(B, N, o.t_eps, o.snr, caller);
-    hipStream_t st = ctx->enter(caller);
-    HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
-    if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz * draws, hipMemcpyDeviceToDevice, st));
-    else launch_randn(nz, sz * draws, seed, 0, st);
     char key[224];
     snprintf(key, sizeof key, "pcmix:%d:%d:%d:%d:%d:%d:%d:%d:%a:%a:%a:%a:%a:%d", B, T, N, o.prior_mix, o.avg_len, o.pred,
              o.corr, o.c, o.d_lambda, o.sigma_min, o.sigma_max, o.snr, o.t_eps, o.denoise);
-    float* res = nullptr;
-    ctx->run_graphed(key, st, [&](hipStream_t s2) { res = ctx->pc_sample_mix(yb, nz, B, T, N, o, s2); });
-    if (!res) res = ctx->wsbuf<float>(o.denoise ? "pc_xm" : "pc_x", sz);
-    HIPCHK(hipMemcpyAsync(x_out, res, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st);
+    ctx->run_sampler({y, noise, nullptr, seed, x_out, B, T, o.draws(N), (hipStream_t)stream},
+                     ctx->schedule(N, o.t_eps, o.snr).t, key, o.denoise ? "pc_xm" : "pc_x",
+                     [&](const float* yb, const float* nz, const float*, hipStream_t s2) {
+                       return ctx->pc_sample_mix(yb, nz, B, T, N, o, s2);
+                     });
     if (nfe_out) *nfe_out = N * (o.c + 1);
-    HIPCHK(hipGetLastError());
   });
 }
 
@@ -2114,41 +2109,16 @@ int dsn_sb_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t see
     if (!y || !x_out || B <= 0 || T <= 0 || N <= 0) fail(DSN_EINVAL, "dsn_sb_sample: bad arguments");
     if (sampler_type != DSN_SB_SDE && sampler_type != DSN_SB_ODE) fail(DSN_EINVAL, "Invalid type. Choose 'ode' or 'sde'.");
     if (!(k > 0) || k == 1.f || !(c > 0)) fail(DSN_EINVAL, "SBVESDE: need k > 0, k != 1, c > 0");
-    const int n = ctx->cfg.n_src, Dl = ctx->cfg.latent_dim;
-    hipStream_t caller = (hipStream_t)stream;
-    const long ysz = (long)B * Dl * T, sz = ysz * n;
     const long draws = sampler_type == DSN_SB_SDE ? N : 0;
-    float* yb = ctx->wsbuf<float>("pc_y", ysz);
-    float* nz = draws ? ctx->wsbuf<float>("pc_noise", sz * draws) : nullptr;
-    {  // step times t_1 .. t_N of linspace(1, eps, N + 1) as the network's time input
-      const std::vector<float> ts = dsn_ctx::sb_times(N, t_eps);
-      std::vector<float> ht((size_t)B * N);
-      for (int i = 0; i < N; ++i)
-        for (int b = 0; b < B; ++b) ht[(size_t)i * B + b] = ts[i + 1];
-      float* tv = ctx->wsbuf<float>("pc_t", (long)B * N);
-      if (!(ht == ctx->tv_host && ctx->tv_B == B)) {
-        HIPCHK(hipMemcpyAsync(tv, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice, caller));
-        HIPCHK(hipStreamSynchronize(caller));
-        ctx->tv_host = ht;
-        ctx->tv_B = B;
-      }
-    }
-    hipStream_t st = ctx->enter(caller);
-    HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
-    if (draws) {
-      if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz * draws, hipMemcpyDeviceToDevice, st));
-      else launch_randn(nz, sz * draws, seed, 0, st);
-    }
+    // step times t_1 .. t_N of linspace(1, eps, N + 1) as the network's time input
+    const std::vector<float> ts = dsn_ctx::sb_times(N, t_eps);
     char key[160];
     snprintf(key, sizeof key, "sb:%d:%d:%d:%a:%a:%a:%a:%d", B, T, N, k, c, sb_eps, t_eps, sampler_type);
-    float* res = nullptr;
-    ctx->run_graphed(key, st, [&](hipStream_t s2) {
-      res = ctx->sb_sample(yb, nz, B, T, N, k, c, sb_eps, t_eps, sampler_type == DSN_SB_ODE, s2);
-    });
-    if (!res) res = ctx->wsbuf<float>("pc_x", sz);
-    HIPCHK(hipMemcpyAsync(x_out, res, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st);
-    HIPCHK(hipGetLastError());
+    ctx->run_sampler({y, noise, nullptr, seed, x_out, B, T, draws, (hipStream_t)stream},
+                     std::vector<float>(ts.begin() + 1, ts.end()), key, "pc_x",
+                     [&](const float* yb, const float* nz, const float*, hipStream_t s2) {
+                       return ctx->sb_sample(yb, nz, B, T, N, k, c, sb_eps, t_eps, sampler_type == DSN_SB_ODE, s2);
+                     });
   });
 }
 
@@ -2252,11 +2222,11 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
     hc->status = -1;
     hc->max_attempts = o->max_attempts;
 
-    hipStream_t st = ctx->enter(caller);
+    dsn_ctx::StreamScope sc(ctx, caller);
+    hipStream_t st = sc.st;
     HIPCHK(hipMemcpyAsync(ctl, hc, sizeof(OdeCtl), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
-    if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    else launch_randn(nz, sz, seed, 0, st);  // draw 0 of the stream dsn_pc_sample uses: the same x_T for a seed
+    dsn_ctx::stage_noise(nz, noise, sz, seed, st);  // draw 0 of the stream dsn_pc_sample uses: the same x_T for a seed
     const float stdT = ctx->ouve_std(1.f);
     char key[160];
     // prior, f0 = fun(t0, y0) and the initial step (scipy select_initial_step: one more evaluation)
@@ -2287,10 +2257,8 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
       HIPCHK(hipMemcpyAsync(hc, ctl, sizeof(OdeCtl), hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       if (hc->done) break;
-      if (k + 1 >= o->max_attempts) {  // the controller stops at max_attempts: not reached unless the state is corrupt
-        ctx->leave(caller, st);
+      if (k + 1 >= o->max_attempts)  // the controller stops at max_attempts: not reached unless the state is corrupt
         fail(DSN_ESOLVER, "dsn_ode_sample: the solver did not stop after max_attempts = %d attempts", o->max_attempts);
-      }
     }
     if (stats) {
       stats->nfev = hc->nfev;
@@ -2299,16 +2267,12 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
       stats->t_final = hc->t;
       stats->status = hc->status;
     }
-    if (hc->status == DSN_ODE_STEP_TOO_SMALL) {
-      ctx->leave(caller, st);
+    if (hc->status == DSN_ODE_STEP_TOO_SMALL)
       fail(DSN_ESOLVER, "dsn_ode_sample: required step size is less than spacing between numbers (t = %.17g, h = %g)",
            hc->t, hc->h_abs);
-    }
-    if (hc->status == DSN_ODE_TOO_MANY_ATTEMPTS) {
-      ctx->leave(caller, st);
+    if (hc->status == DSN_ODE_TOO_MANY_ATTEMPTS)
       fail(DSN_ESOLVER, "dsn_ode_sample: t = %.17g not reached after max_attempts = %d step attempts (%d accepted)",
            hc->t, hc->attempts, hc->accepted);
-    }
     // final state (fp32), then the optional noise-free reverse-diffusion step at t_eps (dt = 1/N)
     const float dt = o->denoise ? (float)(1.0 / o->N) : 0.f;
     const double smin = cfg.sde_sigma_min, smax = cfg.sde_sigma_max, ls = log(smax / smin);
@@ -2325,7 +2289,7 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
       }
     });
     HIPCHK(hipMemcpyAsync(x_out, o->denoise ? xs32 : xo, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st);
+    sc.leave();
     HIPCHK(hipGetLastError());
   });
 }
@@ -2389,11 +2353,11 @@ int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t
     double* part = ctx->wsbuf<double>("loss_part", (long)B * n * n * chunks);
     double* rows = ctx->wsbuf<double>("loss_rows", (long)B * n);
     float* lo = ctx->wsbuf<float>("loss_out", (long)B * n);
-    hipStream_t st = ctx->enter(caller);
+    dsn_ctx::StreamScope sc(ctx, caller);
+    hipStream_t st = sc.st;
     HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(xb, x0, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    if (noise) HIPCHK(hipMemcpyAsync(nz, noise, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    else launch_randn(nz, sz, seed, 0, st);  // draw 0 of the stream the samplers use
+    dsn_ctx::stage_noise(nz, noise, sz, seed, st);  // draw 0 of the stream the samplers use
     if (t) HIPCHK(hipMemcpyAsync(tin, t, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
     else if (!pit) launch_rand_uniform(tin, B, seed ^ 0x9E3779B97F4A7C15ULL, 0, o->t_eps, 1.f, st);
     if (perm) HIPCHK(hipMemcpyAsync(pb, perm, sizeof(int) * B * n, hipMemcpyDeviceToDevice, st));
@@ -2416,7 +2380,7 @@ int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t
     if (t_out) HIPCHK(hipMemcpyAsync(t_out, tv, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
     if (sigma_out) HIPCHK(hipMemcpyAsync(sigma_out, sg, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
     if (z_out) HIPCHK(hipMemcpyAsync(z_out, nz, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st);
+    sc.leave();
     HIPCHK(hipGetLastError());
   });
 }
@@ -2429,27 +2393,64 @@ int dsn_latent_frames(const dsn_ctx* ctx, int L) {
   return (L + (h - L % h)) / h;  // reference utils.pad: a full extra hop when L % hop == 0
 }
 
-int dsn_decode(dsn_ctx* ctx, const float* est, float* wav, int B, int T, int target_len, void* stream) {
+// dsn_decode (one graphed decode of all T frames) and dsn_decode_chunked (`chunked`: decode_chunked, whose chunks
+// are graphed one by one)
+static int decode_call(dsn_ctx* ctx, const char* who, const float* est, float* wav, int B, int T, int target_len,
+                       bool chunked, int chunk_size, int overlap, void* stream) {
   return guarded(ctx, [&] {
-    if (!est || !wav || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_decode: bad arguments");
-    hipStream_t caller = (hipStream_t)stream;
+    if (!est || !wav || B <= 0 || T <= 0) fail(DSN_EINVAL, "%s: bad arguments", who);
     const int S = B * ctx->cfg.n_src;
     const long Lfull = (long)ctx->hop() * T;
     const long Lt = target_len > 0 ? target_len : Lfull;
     if (Lt > Lfull) fail(DSN_EINVAL, "target_len %ld > decoded length %ld", Lt, Lfull);
     const long esz = (long)S * ctx->cfg.latent_dim * T;
     float* eb = ctx->wsbuf<float>("dec_est", esz);
-    hipStream_t st = ctx->enter(caller, 1);
-    HIPCHK(hipMemcpyAsync(eb, est, sizeof(float) * esz, hipMemcpyDeviceToDevice, st));
-    char key[64];
-    snprintf(key, sizeof key, "dec:%d:%d", S, T);
+    dsn_ctx::StreamScope sc(ctx, (hipStream_t)stream, 1);
+    HIPCHK(hipMemcpyAsync(eb, est, sizeof(float) * esz, hipMemcpyDeviceToDevice, sc.st));
     float* w = nullptr;
-    ctx->run_graphed(key, st, [&](hipStream_t s2) { w = ctx->decode(eb, S, T, s2); });
-    if (!w) w = ctx->wsbuf<float>("dec_wav", (long)S * Lfull);
+    if (chunked) {
+      w = ctx->decode_chunked(eb, S, T, chunk_size, overlap, sc.st);
+    } else {
+      char key[64];
+      snprintf(key, sizeof key, "dec:%d:%d", S, T);
+      ctx->run_graphed(key, sc.st, [&](hipStream_t s2) { w = ctx->decode(eb, S, T, s2); });
+      if (!w) w = ctx->wsbuf<float>("dec_wav", (long)S * Lfull);
+    }
     HIPCHK(hipMemcpy2DAsync(wav, sizeof(float) * Lt, w, sizeof(float) * Lfull, sizeof(float) * Lt, S,
-                            hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st, 1);
+                            hipMemcpyDeviceToDevice, sc.st));
+    sc.leave();
   });
+}
+
+int dsn_decode(dsn_ctx* ctx, const float* est, float* wav, int B, int T, int target_len, void* stream) {
+  return decode_call(ctx, "dsn_decode", est, wav, B, T, target_len, false, 0, 0, stream);
+}
+
+// zero-padded copy of the mixture ("enc_wav", T frames of hop() samples) and the VAE noise, drawn into
+// "enc_noise" unless injected
+struct EncodeIn {
+  float* padded;
+  const float* vae_noise;
+  int T;
+  long Lp;
+};
+static EncodeIn stage_encode(dsn_ctx* ctx, const float* mix, const float* vae_noise, uint64_t seed, int B, int L,
+                             hipStream_t st) {
+  const int h = ctx->hop();
+  const int T = dsn_latent_frames(ctx, L);
+  const long Lp = (long)T * h;
+  float* padded = ctx->wsbuf<float>("enc_wav", (long)B * Lp);
+  HIPCHK(hipMemsetAsync(padded, 0, sizeof(float) * B * Lp, st));
+  if (L > 0)
+    HIPCHK(hipMemcpy2DAsync(padded, sizeof(float) * Lp, mix, sizeof(float) * L, sizeof(float) * L, B,
+                            hipMemcpyDeviceToDevice, st));
+  const long nsz = (long)B * ctx->cfg.latent_dim * T;
+  if (!vae_noise) {
+    float* nz = ctx->wsbuf<float>("enc_noise", nsz);
+    launch_randn(nz, nsz, seed ^ 0x5851F42D4C957F2DULL, 0, st);
+    vae_noise = nz;
+  }
+  return {padded, vae_noise, T, Lp};
 }
 
 int dsn_encode(dsn_ctx* ctx, const float* mix, const float* vae_noise, uint64_t seed, float* y, int B, int L,
@@ -2457,43 +2458,15 @@ int dsn_encode(dsn_ctx* ctx, const float* mix, const float* vae_noise, uint64_t 
   return guarded(ctx, [&] {
     if (!mix || !y || B <= 0 || L < 0) fail(DSN_EINVAL, "dsn_encode: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const int h = ctx->hop();
-    const int T = dsn_latent_frames(ctx, L);
-    const long Lp = (long)T * h;
-    float* padded = ctx->wsbuf<float>("enc_wav", (long)B * Lp);
-    HIPCHK(hipMemsetAsync(padded, 0, sizeof(float) * B * Lp, st));
-    if (L > 0)
-      HIPCHK(hipMemcpy2DAsync(padded, sizeof(float) * Lp, mix, sizeof(float) * L, sizeof(float) * L, B,
-                              hipMemcpyDeviceToDevice, st));
-    const long nsz = (long)B * ctx->cfg.latent_dim * T;
-    if (!vae_noise) {
-      float* nz = ctx->wsbuf<float>("enc_noise", nsz);
-      launch_randn(nz, nsz, seed ^ 0x5851F42D4C957F2DULL, 0, st);
-      vae_noise = nz;
-    }
-    ctx->encode(padded, vae_noise, y, B, (int)Lp, st);
+    const EncodeIn in = stage_encode(ctx, mix, vae_noise, seed, B, L, st);
+    ctx->encode(in.padded, in.vae_noise, y, B, (int)in.Lp, st);
     HIPCHK(hipGetLastError());
   });
 }
 
 int dsn_decode_chunked(dsn_ctx* ctx, const float* est, float* wav, int B, int T, int target_len, int chunk_size,
                        int overlap, void* stream) {
-  return guarded(ctx, [&] {
-    if (!est || !wav || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_decode_chunked: bad arguments");
-    hipStream_t caller = (hipStream_t)stream;
-    const int S = B * ctx->cfg.n_src;
-    const long Lfull = (long)ctx->hop() * T;
-    const long Lt = target_len > 0 ? target_len : Lfull;
-    if (Lt > Lfull) fail(DSN_EINVAL, "target_len %ld > decoded length %ld", Lt, Lfull);
-    const long esz = (long)S * ctx->cfg.latent_dim * T;
-    float* eb = ctx->wsbuf<float>("dec_est", esz);
-    hipStream_t st = ctx->enter(caller, 1);
-    HIPCHK(hipMemcpyAsync(eb, est, sizeof(float) * esz, hipMemcpyDeviceToDevice, st));
-    float* w = ctx->decode_chunked(eb, S, T, chunk_size, overlap, st);
-    HIPCHK(hipMemcpy2DAsync(wav, sizeof(float) * Lt, w, sizeof(float) * Lfull, sizeof(float) * Lt, S,
-                            hipMemcpyDeviceToDevice, st));
-    ctx->leave(caller, st, 1);
-  });
+  return decode_call(ctx, "dsn_decode_chunked", est, wav, B, T, target_len, true, chunk_size, overlap, stream);
 }
 
 int dsn_encode_chunked(dsn_ctx* ctx, const float* mix, const float* vae_noise, uint64_t seed, float* y, int B, int L,
@@ -2501,22 +2474,9 @@ int dsn_encode_chunked(dsn_ctx* ctx, const float* mix, const float* vae_noise, u
   return guarded(ctx, [&] {
     if (!mix || !y || B <= 0 || L < 0) fail(DSN_EINVAL, "dsn_encode_chunked: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const int h = ctx->hop();
-    const int T = dsn_latent_frames(ctx, L);
-    const long Lp = (long)T * h;
-    float* padded = ctx->wsbuf<float>("enc_wav", (long)B * Lp);
-    HIPCHK(hipMemsetAsync(padded, 0, sizeof(float) * B * Lp, st));
-    if (L > 0)
-      HIPCHK(hipMemcpy2DAsync(padded, sizeof(float) * Lp, mix, sizeof(float) * L, sizeof(float) * L, B,
-                              hipMemcpyDeviceToDevice, st));
-    const long nsz = (long)B * ctx->cfg.latent_dim * T;
-    if (!vae_noise) {
-      float* nz = ctx->wsbuf<float>("enc_noise", nsz);
-      launch_randn(nz, nsz, seed ^ 0x5851F42D4C957F2DULL, 0, st);
-      vae_noise = nz;
-    }
-    float* enc = ctx->encode_chunked(padded, B, T, chunk_size, overlap, st);
-    launch_vae_sample(enc, vae_noise, y, B, ctx->cfg.latent_dim, T, st);
+    const EncodeIn in = stage_encode(ctx, mix, vae_noise, seed, B, L, st);
+    float* enc = ctx->encode_chunked(in.padded, B, in.T, chunk_size, overlap, st);
+    launch_vae_sample(enc, in.vae_noise, y, B, ctx->cfg.latent_dim, in.T, st);
     HIPCHK(hipGetLastError());
   });
 }
