@@ -3407,6 +3407,92 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
                t->B, t->L, t->dil, t->act, t->act_out);
         break;
       }
+      // ---- the sampler's kernels between two score calls: fp32 tensors passed through, every refusal before the launch
+      case DSN_TK_PC_PRIOR:
+      case DSN_TK_PC_CORRECTOR:
+      case DSN_TK_PC_PREDICTOR:
+      case DSN_TK_MIX_PRIOR:
+      case DSN_TK_MIX_CORRECTOR:
+      case DSN_TK_MIX_PREDICTOR:
+      case DSN_TK_SB_UPDATE:
+      case DSN_TK_REPEAT_SOURCES: {
+        static const char* const names[] = {"pc_prior", "pc_corrector", "", "pc_predictor", "", "mix_prior",
+                                            "mix_corrector", "mix_predictor", "sb_update", "repeat_sources"};
+        const char* nm = names[t->kind - DSN_TK_PC_PRIOR];
+        const int k = t->kind;
+        if (t->B < 1 || t->n < 1 || t->D < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel %s: B, n, D, T must be positive (B=%d n=%d D=%d T=%d)", nm, t->B, t->n, t->D, t->T);
+        const bool mix = k == DSN_TK_MIX_PRIOR || k == DSN_TK_MIX_CORRECTOR || k == DSN_TK_MIX_PREDICTOR;
+        if (mix && t->n > 4) fail(DSN_EINVAL, "test_kernel %s: n = %d sources, the kernel holds at most 4", nm, t->n);
+        auto need = [&](const void* p, const char* what) {
+          if (!p) fail(DSN_EINVAL, "test_kernel %s: %s missing", nm, what);
+        };
+        need(t->x, "x");
+        const bool wants_y = k == DSN_TK_PC_PRIOR || k == DSN_TK_PC_PREDICTOR || k == DSN_TK_MIX_PRIOR ||
+                             k == DSN_TK_REPEAT_SOURCES;
+        const bool wants_sc = k == DSN_TK_PC_CORRECTOR || k == DSN_TK_PC_PREDICTOR || k == DSN_TK_MIX_CORRECTOR ||
+                              k == DSN_TK_MIX_PREDICTOR || k == DSN_TK_SB_UPDATE;
+        const bool wants_z = k != DSN_TK_SB_UPDATE && k != DSN_TK_REPEAT_SOURCES;
+        const bool wants_xm = k == DSN_TK_PC_PREDICTOR || k == DSN_TK_MIX_PREDICTOR;
+        if (wants_y) need(t->y, "y");
+        if (wants_sc) need(t->score, "score");
+        if (wants_z) need(t->z, "z");
+        if (wants_xm) need(t->xmean, "xmean");
+        const int B = t->B, n = t->n, D = t->D, T = t->T;
+        switch (k) {
+          case DSN_TK_PC_PRIOR: launch_pc_prior(t->y, t->mean_full, t->z, t->x, t->stdT, B, n, D, T, st); break;
+          case DSN_TK_PC_CORRECTOR:
+            launch_pc_corrector(t->x, t->xmean, t->score, t->z, t->step, t->gain, t->norms, t->snr, B, n, D, T, st);
+            break;
+          case DSN_TK_PC_PREDICTOR:
+            launch_pc_predictor(t->x, t->xmean, t->y, t->score, t->z, t->theta, t->dt, t->G, t->g, t->em, B, n, D, T, st);
+            break;
+          case DSN_TK_MIX_PRIOR: launch_mix_prior(t->y, t->z, t->x, t->smix, t->s1, t->s2, B, n, D, T, st); break;
+          case DSN_TK_MIX_CORRECTOR:
+            launch_mix_corrector(t->x, t->xmean, t->score, t->z, t->smix, t->s1, t->s2, t->snr, B, n, D, T, st);
+            break;
+          case DSN_TK_MIX_PREDICTOR:
+            launch_mix_predictor(t->x, t->xmean, t->score, t->z, t->smix, t->lam, t->dt, t->g, t->sqdt, t->em, B, n, D, T,
+                                 st);
+            break;
+          case DSN_TK_SB_UPDATE:
+            launch_sb_update(t->x, t->score, t->third_is_y ? t->y : t->z, t->w_prev, t->w_est, t->w3, t->third_is_y, B, n,
+                             D, T, st);
+            break;
+          default: launch_repeat_sources(t->y, t->x, B, n, D, T, st); break;
+        }
+        break;
+      }
+      case DSN_TK_PC_ITEM_NORMS: {
+        if (t->B < 1 || t->count < 1)
+          fail(DSN_EINVAL, "test_kernel pc_item_norms: B and count must be positive (B=%d count=%ld)", t->B, (long)t->count);
+        if (!t->x || !t->out_f32) fail(DSN_EINVAL, "test_kernel pc_item_norms: x or out_f32 missing");
+        launch_pc_item_norms(t->x, (long)t->count, t->B, t->out_f32, st);
+        break;
+      }
+      case DSN_TK_SIGMA_MIX: {
+        if (t->B < 1 || t->L < 1) fail(DSN_EINVAL, "test_kernel sigma_mix: B and L must be positive (B=%d L=%d)", t->B, t->L);
+        if (t->avg_len < 1) fail(DSN_EINVAL, "test_kernel sigma_mix: avg_len %d < 1", t->avg_len);
+        if (!t->y || !t->out_f32) fail(DSN_EINVAL, "test_kernel sigma_mix: y or out_f32 missing");
+        launch_sigma_mix(t->y, t->out_f32, t->B, t->L, t->avg_len, st);
+        break;
+      }
+      case DSN_TK_VAE_SAMPLE: {
+        if (t->B < 1 || t->D < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel vae_sample: B, D, T must be positive (B=%d D=%d T=%d)", t->B, t->D, t->T);
+        if (!t->x || !t->z || !t->out_f32) fail(DSN_EINVAL, "test_kernel vae_sample: x (encoder output), z or out_f32 missing");
+        launch_vae_sample(t->x, t->z, t->out_f32, t->B, t->D, t->T, st);
+        break;
+      }
+      case DSN_TK_RANDN:
+      case DSN_TK_RAND_UNIFORM: {
+        const char* nm = t->kind == DSN_TK_RANDN ? "randn" : "rand_uniform";
+        if (t->count < 1) fail(DSN_EINVAL, "test_kernel %s: count %ld must be positive", nm, (long)t->count);
+        if (!t->out_f32) fail(DSN_EINVAL, "test_kernel %s: out_f32 missing", nm);
+        if (t->kind == DSN_TK_RANDN) launch_randn(t->out_f32, (long)t->count, t->seed, t->offset, st);
+        else launch_rand_uniform(t->out_f32, (long)t->count, t->seed, t->offset, t->lo, t->hi, st);
+        break;
+      }
       default:
         fail(DSN_EINVAL, "test_kernel: unknown kind %d", t->kind);
     }

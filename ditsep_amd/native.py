@@ -145,7 +145,10 @@ class DsnTestGemm(C.Structure):
 
 # dsn_test_kernel (include/ditsep_hip.h): which launch wrapper of the non-GEMM kernels runs
 TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn_stats": 4, "gn_apply": 5, "fir2d": 6,
-                     "conv_out1": 7, "conv_in1": 8, "ru_fused": 9}
+                     "conv_out1": 7, "conv_in1": 8, "ru_fused": 9,
+                     "pc_prior": 10, "pc_corrector": 11, "pc_item_norms": 12, "pc_predictor": 13, "sigma_mix": 14,
+                     "mix_prior": 15, "mix_corrector": 16, "mix_predictor": 17, "sb_update": 18, "repeat_sources": 19,
+                     "vae_sample": 20, "randn": 21, "rand_uniform": 22}
 
 
 class DsnTestKernel(C.Structure):
@@ -164,6 +167,16 @@ class DsnTestKernel(C.Structure):
         ("out_act_a", C.c_void_p), ("out_act_b", C.c_void_p), ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
         ("out_f32", C.c_void_p), ("out_planes", C.c_void_p), ("out_ps", C.c_int64), ("out_fp8", C.c_void_p),
         ("out_fp8_scale", C.c_void_p),
+        # the sampler's kernels (fp32 only)
+        ("n", C.c_int), ("T", C.c_int), ("avg_len", C.c_int), ("em", C.c_int), ("mean_full", C.c_int),
+        ("third_is_y", C.c_int),
+        ("stdT", C.c_float), ("step", C.c_float), ("gain", C.c_float), ("snr", C.c_float), ("theta", C.c_float),
+        ("dt", C.c_float), ("G", C.c_float), ("g", C.c_float), ("s1", C.c_float), ("s2", C.c_float), ("lam", C.c_float),
+        ("sqdt", C.c_float), ("w_prev", C.c_float), ("w_est", C.c_float), ("w3", C.c_float), ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("seed", C.c_uint64), ("offset", C.c_uint64), ("count", C.c_int64),
+        ("y", C.c_void_p), ("score", C.c_void_p), ("z", C.c_void_p), ("smix", C.c_void_p), ("norms", C.c_void_p),
+        ("xmean", C.c_void_p),
     ]
 
 

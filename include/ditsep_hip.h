@@ -429,12 +429,17 @@ typedef struct DsnTestGemm {
 int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream);
 
 /* Test hook: run ONE launch wrapper of the non-GEMM kernels (ditsep_amd/csrc/kernels.h, qkv_attention_launch,
- * ru_fused_launch) with the caller's arguments on caller-owned device tensors.  Which kernel runs is the wrapper's own
+ * ru_fused_launch) with the caller's arguments on caller-owned device tensors -- the sampler update, prior, noise and
+ * VAE-sample kernels included, see the end of the struct.  Which kernel runs is the wrapper's own
  * dispatch.  `a` (and `w` of QKV_ATTENTION, `w` / `w2` of RU_FUSED) are fp32 tensors rounded to the engine's operand planes
  * first; every other tensor is passed through.
  * Outputs land in caller-owned buffers.  An argument the wrapper does not support fails the call by name. */
 enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3, DSN_TK_GN_STATS = 4,
-       DSN_TK_GN_APPLY = 5, DSN_TK_FIR2D = 6, DSN_TK_CONV_OUT1 = 7, DSN_TK_CONV_IN1 = 8, DSN_TK_RU_FUSED = 9 };
+       DSN_TK_GN_APPLY = 5, DSN_TK_FIR2D = 6, DSN_TK_CONV_OUT1 = 7, DSN_TK_CONV_IN1 = 8, DSN_TK_RU_FUSED = 9,
+       DSN_TK_PC_PRIOR = 10, DSN_TK_PC_CORRECTOR = 11, DSN_TK_PC_ITEM_NORMS = 12, DSN_TK_PC_PREDICTOR = 13,
+       DSN_TK_SIGMA_MIX = 14, DSN_TK_MIX_PRIOR = 15, DSN_TK_MIX_CORRECTOR = 16, DSN_TK_MIX_PREDICTOR = 17,
+       DSN_TK_SB_UPDATE = 18, DSN_TK_REPEAT_SOURCES = 19, DSN_TK_VAE_SAMPLE = 20, DSN_TK_RANDN = 21,
+       DSN_TK_RAND_UNIFORM = 22 };
 typedef struct DsnTestKernel {
   int kind;                   /* DSN_TK_* */
   /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
@@ -483,6 +488,33 @@ typedef struct DsnTestKernel {
   int64_t out_ps;
   uint8_t* out_fp8;           /* e4m3 bytes instead of planes, with out_fp8_scale (E8M0, one per 32 columns) */
   uint8_t* out_fp8_scale;
+  /* The sampler's kernels between two score calls (fp32 only, nothing is rounded to planes).  State x [B,n,D,T]
+   * (updated in place, or the output of the priors and REPEAT_SOURCES), y [B,1,D,T], score [B*T][n*D] token-major,
+   * z [B,n,D,T], smix [B][D*T] (null = 1), xmean [B,n,D,T]:
+   *   PC_PRIOR       x = mean + stdT z; mean = y broadcast over the sources, or y itself [B,n,D,T] with mean_full
+   *   PC_CORRECTOR   x, xmean (may be null), score, z; step and gain, or norms [2 B] (|score| then |z| per item) and snr
+   *   PC_ITEM_NORMS  x = a [B][count] -> out_f32 [B]
+   *   PC_PREDICTOR   x, xmean, y, score, z; theta, dt, G, g, em
+   *   SIGMA_MIX      y [B][L], avg_len -> out_f32 [B][L]
+   *   MIX_PRIOR      y, z, smix -> x; s1, s2
+   *   MIX_CORRECTOR  x, xmean (may be null), score, z, smix; s1, s2 (square roots of the two eigenvalues), snr
+   *   MIX_PREDICTOR  x, xmean, score, z, smix; lam, dt, g, sqdt, em
+   *   SB_UPDATE      x = w_prev x + w_est score + w3 (third_is_y ? y : z); that tensor null: no third term
+   *   REPEAT_SOURCES y -> x
+   *   VAE_SAMPLE     x = encoder output [B][T][2 D] (mean ++ scale), z = noise [B,D,T] -> out_f32 [B,D,T]
+   *   RANDN, RAND_UNIFORM  count values of the stream (seed, offset) -> out_f32; RAND_UNIFORM: lo, hi
+   * Refused by name before any launch: a missing tensor, a non-positive B, n, D, T, L or count, avg_len < 1, and
+   * n > 4 for the three MIX_* kernels (they hold the sources of a position in four-element arrays). */
+  int n, T, avg_len, em, mean_full, third_is_y;
+  float stdT, step, gain, snr, theta, dt, G, g, s1, s2, lam, sqdt, w_prev, w_est, w3, lo, hi;
+  uint64_t seed, offset;
+  int64_t count;
+  const float* y;
+  const float* score;
+  const float* z;
+  const float* smix;
+  const float* norms;
+  float* xmean;
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 
