@@ -60,6 +60,18 @@ struct Packed {  // K-major packed operand planes of one contraction
   int bias_mod = 1;
 };
 
+// a caller's plain [N][taps * Cin] weight planes, no bias (test and benchmark hooks)
+static Packed plain_packed(op16_t* w, long ps, int N, int Cin, int taps) {
+  Packed p;
+  p.w = w;
+  p.ps = ps;
+  p.N = N;
+  p.Cin = Cin;
+  p.taps = taps;
+  p.K = taps * Cin;
+  return p;
+}
+
 struct ActP {  // producer-side activation
   int kind = DSN_ACT_NONE;
   float* a = nullptr;
@@ -104,13 +116,13 @@ struct Graph {
   bool warmed = false;
 };
 
-struct ProfRec {
-  hipEvent_t a, b;
-  double flops;
-  double hbm_bytes = 0;  // algorithmic HBM bytes of the launch (0 = not stated)
+struct ProfRec {  // what a call site states (in this order) and the events dsn_ctx::profiled adds
   const char* tag = "";  // call-site label (static string): rows of dsn_profile_rows
+  double flops = 0;
+  double hbm_bytes = 0;  // algorithmic HBM bytes of the launch (0 = not stated)
   bool gemm = true;      // counted in the implicit-GEMM family totals of dsn_profile_end
   bool hbm_bound = false;  // the HBM-bound member of that family (fused ResidualUnit): dsn_profile_hbm
+  hipEvent_t a = nullptr, b = nullptr;
 };
 
 struct ProfRow {
@@ -209,24 +221,30 @@ struct dsn_ctx {
     Tag(dsn_ctx* ctx, const char* t) : c(ctx), prev(ctx->cur_tag) { c->cur_tag = t; }
     ~Tag() { c->cur_tag = prev; }
   };
-  // bracket a non-GEMM launch with events when profiling (algorithmic HBM bytes given by the caller)
+  // The profiling bracket: `launch()` between two events of a record that carries what `spec` states.  Returns what
+  // `launch` returns -- a launch error is the caller's to report, after the end event.  On every way out, a throw
+  // included, the end event is recorded and the record kept: dsn_profile_begin / _end destroy the events of all records.
+  template <class F>
+  auto profiled(const ProfRec& spec, hipStream_t st, F&& launch) -> decltype(launch()) {
+    if (!profiling) return launch();
+    struct Bracket {
+      dsn_ctx* c;
+      ProfRec pr;
+      hipStream_t st;
+      ~Bracket() {
+        (void)hipEventRecord(pr.b, st);  // (a failure shows in dsn_profile_end's hipEventElapsedTime)
+        c->prof.push_back(pr);
+      }
+    } br{this, spec, st};
+    HIPCHK(hipEventCreate(&br.pr.a));
+    HIPCHK(hipEventCreate(&br.pr.b));
+    HIPCHK(hipEventRecord(br.pr.a, st));
+    return launch();
+  }
+  // a non-GEMM launch (algorithmic HBM bytes given by the caller)
   template <class F>
   void prof_launch(const char* tag, double bytes, hipStream_t st, F&& f) {
-    if (!profiling) {
-      f();
-      return;
-    }
-    ProfRec pr;
-    HIPCHK(hipEventCreate(&pr.a));
-    HIPCHK(hipEventCreate(&pr.b));
-    pr.flops = 0;
-    pr.hbm_bytes = bytes;
-    pr.tag = tag;
-    pr.gemm = false;
-    HIPCHK(hipEventRecord(pr.a, st));
-    f();
-    HIPCHK(hipEventRecord(pr.b, st));
-    prof.push_back(pr);
+    profiled({tag, 0, bytes, false}, st, f);
   }
   std::vector<float> tv_host;  // uploaded timestep table signature
   int tv_B = -1;
@@ -862,21 +880,18 @@ struct dsn_ctx {
   void run(const GemmDesc& d, hipStream_t st, int panel_bn = 0, bool skinny = false) {
     static const bool audit = getenv("DSN_AUDIT") != nullptr;
     if (audit) audit_desc(d);
-    ProfRec pr;
-    if (profiling) {
-      HIPCHK(hipEventCreate(&pr.a));
-      HIPCHK(hipEventCreate(&pr.b));
-      pr.flops = 2.0 * (double)d.M * (double)d.N * ((double)d.taps * (double)d.Cin + (d.sc_A ? (double)d.sc_Cin : 0.0));
-      pr.tag = cur_tag;
-      HIPCHK(hipEventRecord(pr.a, st));
-    }
+    const double flops = 2.0 * (double)d.M * (double)d.N * ((double)d.taps * (double)d.Cin + (d.sc_A ? (double)d.sc_Cin : 0.0));
     // NCSN++ convs of single mixtures: a handful of 128 x 128 tiles each walking a long K alone -> split-K over enough
     // workgroups for a quarter of the chip, then the slab epilogue (B = 1, T = 16: score call 3.07 -> see DESIGN 5)
     const long ctiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-    if (P == 1 && cfg.score_kind == DSN_SCORE_NCSNPP && !skinny && panel_bn == 0 && d.ksplit <= 1 &&
+    const bool split = P == 1 && cfg.score_kind == DSN_SCORE_NCSNPP && !skinny && panel_bn == 0 && d.ksplit <= 1 &&
         d.Cin % 32 == 0 && d.N % 64 == 0 && ctiles <= 32 && d.taps * d.Cin >= 512 && !d.swiglu && !d.rope_cos &&
         (d.out_f32 || d.out_planes) && d.out_off >= 0 && d.tap_dil >= 0 && d.in_stride == 1 &&
-        (d.img_w > 0 || (d.taps == 1 && d.in_pad == 0))) {
+        (d.img_w > 0 || (d.taps == 1 && d.in_pad == 0));
+    const hipError_t e = profiled({cur_tag, flops}, st, [&] {
+      if (!split)
+        return skinny ? igemm_skinny_launch(d, PL, st)
+                      : (panel_bn > 0 ? igemm_panel_launch(d, PL, panel_bn, st) : igemm2_launch(d, PL, st));
       const int nkt = d.taps * d.Cin / 32;
       const int ks = (int)std::max(2L, std::min<long>(std::min<long>(8, nkt / 4), 64 / ctiles));
       const long span = (long)cdiv(d.M, d.rows_per_b) * d.out_bstride;  // floats one slab covers: the output view
@@ -894,32 +909,16 @@ struct dsn_ctx {
       g.cfg_bk = 32;
       hipError_t e1 = igemm2_launch(g, PL, st);
       if (e1 == hipSuccess) e1 = igemm_slab_epilogue_launch(d, PL, slabs, ks, span, st);
-      if (profiling) {
-        HIPCHK(hipEventRecord(pr.b, st));
-        prof.push_back(pr);
-      }
-      if (e1 != hipSuccess) fail(DSN_EHIP, "split conv launch failed: %s", hipGetErrorString(e1));
-      return;
-    }
-    hipError_t e = skinny ? igemm_skinny_launch(d, PL, st)
-                          : (panel_bn > 0 ? igemm_panel_launch(d, PL, panel_bn, st) : igemm2_launch(d, PL, st));
-    if (profiling) {
-      HIPCHK(hipEventRecord(pr.b, st));
-      prof.push_back(pr);
-    }
+      return e1;
+    });
+    if (e != hipSuccess && split) fail(DSN_EHIP, "split conv launch failed: %s", hipGetErrorString(e));
     if (e != hipSuccess) fail(DSN_EHIP, "igemm launch failed: %s (M=%d N=%d Cin=%d taps=%d)", hipGetErrorString(e),
                               d.M, d.N, d.Cin, d.taps);
   }
 
   // descriptor of an fp8 (MX) row-major GEMM: A8 [M][K] bytes + scales [M][K/32], weight w
   GemmDesc fp8_desc(const unsigned char* A8, const unsigned char* SA, const Packed8& w, int M) {
-    Packed pk;
-    pk.w = reinterpret_cast<op16_t*>(w.w);
-    pk.ps = 0;
-    pk.N = w.N;
-    pk.Cin = w.K / 2;  // byte pairs
-    pk.K = w.K / 2;
-    pk.taps = 1;
+    Packed pk = plain_packed(reinterpret_cast<op16_t*>(w.w), 0, w.N, w.K / 2, 1);  // Cin in byte pairs
     pk.bias = w.bias;
     pk.bias_mod = w.N;
     GemmDesc d = base_desc(reinterpret_cast<const op16_t*>(A8), 0, pk, 1, M, M);
@@ -929,19 +928,8 @@ struct dsn_ctx {
     return d;
   }
   void run_fp8(const GemmDesc& d, hipStream_t st, int bn) {
-    ProfRec pr;
-    if (profiling) {
-      HIPCHK(hipEventCreate(&pr.a));
-      HIPCHK(hipEventCreate(&pr.b));
-      pr.flops = 2.0 * (double)d.M * (double)d.N * 2.0 * (double)d.Cin;
-      pr.tag = cur_tag;
-      HIPCHK(hipEventRecord(pr.a, st));
-    }
-    hipError_t e = igemm_panel_fp8_launch(d, bn, st);
-    if (profiling) {
-      HIPCHK(hipEventRecord(pr.b, st));
-      prof.push_back(pr);
-    }
+    const hipError_t e = profiled({cur_tag, 2.0 * (double)d.M * (double)d.N * 2.0 * (double)d.Cin}, st,
+                                  [&] { return igemm_panel_fp8_launch(d, bn, st); });
     if (e != hipSuccess) fail(DSN_EHIP, "fp8 igemm launch failed: %s (M=%d N=%d K=%d rows=%d bn=%d)", hipGetErrorString(e),
                               d.M, d.N, 2 * d.Cin, d.panel_rows, bn);
   }
@@ -976,24 +964,44 @@ struct dsn_ctx {
     d.S = S;
     d.L = (int)L;
     d.dil = r.dil;
-    ProfRec pr;
-    if (profiling) {
-      HIPCHK(hipEventCreate(&pr.a));
-      HIPCHK(hipEventCreate(&pr.b));
-      pr.flops = 2.0 * (double)S * (double)L * 128.0 * 128.0 * 8.0;
-      // algorithmic HBM bytes: planes in, fp32 residual in, fp32 out (when kept), planes out
-      pr.hbm_bytes = (double)S * (double)L * 128.0 * (2.0 * P + 4.0 + (out_f32 ? 4.0 : 0.0) + 2.0 * P);
-      pr.tag = "vae.residual_unit_fused";
-      pr.hbm_bound = true;
-      HIPCHK(hipEventRecord(pr.a, st));
-    }
-    hipError_t e = ru_fused_launch(d, PL, st);
-    if (profiling) {
-      HIPCHK(hipEventRecord(pr.b, st));
-      prof.push_back(pr);
-    }
+    const double flops = 2.0 * (double)S * (double)L * 128.0 * 128.0 * 8.0;
+    // algorithmic HBM bytes: planes in, fp32 residual in, fp32 out (when kept), planes out
+    const double bytes = (double)S * (double)L * 128.0 * (2.0 * P + 4.0 + (out_f32 ? 4.0 : 0.0) + 2.0 * P);
+    const hipError_t e = profiled({"vae.residual_unit_fused", flops, bytes, true, true}, st,
+                                  [&] { return ru_fused_launch(d, PL, st); });
     if (e != hipSuccess) fail(DSN_EHIP, "fused residual unit launch failed: %s (S=%d L=%ld dil=%d)",
                               hipGetErrorString(e), S, L, r.dil);
+  }
+
+  // One ResidualUnit of the coders on the stream planes `x` (plane stride ps, fp32 copy in xf) with scratch planes `h`:
+  // the fused kernel x -> h, after which the two trade places, or a dilated k7 conv into h and a k1 conv + residual back
+  // into x.  keep_f32: a further unit of the block reads the fp32 stream; `next`: the activation of x's consumer.
+  void res_unit(const ResUnit& r, op16_t*& x, op16_t*& h, long ps, float* xf, bool keep_f32, const ActP& next, int S,
+                long L, hipStream_t st) {
+    if (ru_fusable(r)) {
+      run_ru(r, x, ps, xf, keep_f32 ? xf : nullptr, h, next, S, L, st);
+      std::swap(x, h);
+      return;
+    }
+    Tag tg(this, "vae.residual_unit_2gemm");
+    {
+      GemmDesc d = base_desc(x, ps, r.conv7, S, (int)L, (int)L);
+      d.tap_dil = r.dil;
+      d.in_pad = r.dil * (r.conv7.taps - 1) / 2;
+      d.out_planes = h;
+      d.out_ps = ps;
+      set_act(d, r.act2);
+      run(d, st);
+    }
+    {
+      GemmDesc d = base_desc(h, ps, r.conv1, S, (int)L, (int)L);
+      d.resid = xf;
+      d.out_planes = x;
+      d.out_ps = ps;
+      if (keep_f32) d.out_f32 = xf;
+      set_act(d, next);
+      run(d, st);
+    }
   }
 
   // ---------------------------------------------------------------- DiT score
@@ -1043,9 +1051,6 @@ struct dsn_ctx {
     unsigned char* H8 = fp8 ? wsbuf<unsigned char>("dit_H8", M * 4 * D) : nullptr;
     unsigned char* SH8 = fp8 ? wsbuf<unsigned char>("dit_SH8", M * 4 * D / 32) : nullptr;
     op16_t* lnout = fp8 ? reinterpret_cast<op16_t*>(A8) : Ap;
-    // folded ff_norm (single-plane modes, panels of at most 80 rows fill whole rounds): to_out runs WITHOUT split-K in
-    // 128-column tiles, adds the residual itself and writes x' (fp32), its raw operand plane and per-row statistics;
-    // FF-in then applies the LayerNorm algebraically in its epilogue -- the LayerNorm launch between them is gone
     // single mixtures and pairs (up to 80 token rows = 5 sub-tiles; DSN_SKINNY_MAX moves the limit, at most 128): weight-streaming skinny kernels, split-K 8 for
     // the two N = D GEMMs so that every CU streams a share of their weights.  Measured (scripts/score_time.py, one
     // score call): M = 33: 1.52 ms vs 2.27 ms with the panel kernels; M = 17 (config C1): 1.37 vs 2.02 ms; M = 9:
@@ -1056,6 +1061,9 @@ struct dsn_ctx {
     const bool skinny = P == 1 && !fp8 && M <= skinny_max && D % 256 == 0;
     const int skinny_ks = 8;
     const bool use_panel = D % 64 == 0;  // row-panel kernels
+    // folded ff_norm (single-plane modes, panels of at most 80 rows fill whole rounds): to_out runs WITHOUT split-K in
+    // 128-column tiles, adds the residual itself and writes x' (fp32), its raw operand plane and per-row statistics;
+    // FF-in then applies the LayerNorm algebraically in its epilogue -- the LayerNorm launch between them is gone
     int fold_rows = 0;
     if ((fold_ln || fold_ln8) && use_panel && !skinny) {
       for (int rounds = 1; rounds <= 4 && !fold_rows; ++rounds) {
@@ -1129,6 +1137,39 @@ struct dsn_ctx {
     int pend_n = 0;
     const float* pend_bias = nullptr;
     const long slab_stride = M * D;
+    // A layer GEMM's descriptor over M token rows: the fp8 operand with its scales and weight in the fp8 mode, else the
+    // 16-bit planes and weight
+    auto layer_desc = [&](const op16_t* A16, const unsigned char* A8b, const unsigned char* SA, const Packed& w,
+                          const Packed8& w8) {
+      return fp8 ? fp8_desc(A8b, SA, w8, (int)M) : base_desc(A16, M * w.Cin, w, 1, (int)M, (int)M);
+    };
+    // ... and its kernel family: fp8 row panels, the weight-streaming skinny kernel, or the 16-bit kernels (row panels in
+    // bn-column tiles where `panel`)
+    auto layer_gemm = [&](const GemmDesc& d, int bn, bool panel) {
+      if (fp8) run_fp8(d, st, bn);
+      else if (skinny) run(d, st, 0, true);
+      else run(d, st, panel ? bn : 0);
+    };
+    // A residual-stream GEMM (out-proj, FF-out) in bn-column tiles: split-K (skinny: 8, short panels and fp8: ks) into
+    // fp32 slabs, whose reduction + bias + residual the following residual_norm does (pend_n, pend_bias); without
+    // split-K it adds the residual and writes X itself.  (to_out has no bias: pack_linear gives it none to defer.)
+    auto stream_gemm = [&](GemmDesc& d, int bn, int ks, int max_rows) {
+      d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? ks : pick_ksplit(d));
+      if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, bn) * ks, max_rows);
+      if (d.ksplit > 1) {
+        slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
+        d.out_f32 = slabs;
+        d.slab_stride = slab_stride;
+        pend_bias = d.bias;
+        d.bias = nullptr;
+      } else {
+        d.resid = X;
+        d.out_f32 = X;
+        pend_bias = nullptr;
+      }
+      layer_gemm(d, bn, short_panel);
+      pend_n = d.ksplit > 1 ? d.ksplit : 0;
+    };
     for (int i = 0; i < cfg.dit_depth; ++i) {
       const DitLayer& L = layers[i];
       // algorithmic bytes of the fused reduce + LayerNorm: x in/out (when slabs are pending), slabs in, planes out
@@ -1156,52 +1197,33 @@ struct dsn_ctx {
         q.S = S;
         q.ipp = qa_ipp;
         q.q_scale = 0.125f;
-        ProfRec pr;
-        if (profiling) {
-          HIPCHK(hipEventCreate(&pr.a));
-          HIPCHK(hipEventCreate(&pr.b));
-          pr.flops = 2.0 * (double)M * 3.0 * D * D + 4.0 * (double)B * H * (double)S * S * 64.0;
-          pr.tag = "dit.qkv_attention";
-          HIPCHK(hipEventRecord(pr.a, st));
-        }
-        const hipError_t e = qkv_attention_launch(q, PL, st);
-        if (profiling) {
-          HIPCHK(hipEventRecord(pr.b, st));
-          prof.push_back(pr);
-        }
+        const double flops = 2.0 * (double)M * 3.0 * D * D + 4.0 * (double)B * H * (double)S * S * 64.0;
+        const hipError_t e = profiled({"dit.qkv_attention", flops}, st, [&] { return qkv_attention_launch(q, PL, st); });
         if (e != hipSuccess) fail(DSN_EHIP, "qkv_attention launch failed: %s", hipGetErrorString(e));
       } else {
-      {  // q|k|v operand planes: rotary + 1/sqrt(dh) fused into the epilogue
-        Tag tg(this, "dit.qkv");
-        GemmDesc d = fp8 ? fp8_desc(A8, SA8, L.qkv8, (int)M) : base_desc(Ap, M * D, L.qkv, 1, (int)M, (int)M);
-        d.out_planes = QKVp;
-        d.out_ps = M * 3 * D;
-        d.rope_cos = rc;
-        d.rope_sin = rs;
-        d.rope_S = S;
-        d.qkv_D = D;
-        d.q_scale = 0.125f;
-        d.m_fast = 1;
-        if (qkv_panel) d.panel_rows = panel_rows_for(cdiv(3 * D, qkv_panel));
-        if (fp8) {
-          d.panel_rows = panel_rows_for(cdiv(3 * D, 256), 208);
-          run_fp8(d, st, 256);
-        } else if (skinny) {
-          run(d, st, 0, true);
-        } else {
-          run(d, st, qkv_panel);
+        {  // q|k|v operand planes: rotary + 1/sqrt(dh) fused into the epilogue
+          Tag tg(this, "dit.qkv");
+          GemmDesc d = layer_desc(Ap, A8, SA8, L.qkv, L.qkv8);
+          d.out_planes = QKVp;
+          d.out_ps = M * 3 * D;
+          d.rope_cos = rc;
+          d.rope_sin = rs;
+          d.rope_S = S;
+          d.qkv_D = D;
+          d.q_scale = 0.125f;
+          d.m_fast = 1;
+          if (qkv_panel) d.panel_rows = panel_rows_for(cdiv(3 * D, qkv_panel));
+          if (fp8) d.panel_rows = panel_rows_for(cdiv(3 * D, 256), 208);
+          layer_gemm(d, 256, short_panel);
         }
-      }
-      prof_launch("dit.attention", (double)M * D * 2.0 * P * 4.0, st,
-                  [&] {
-                    const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8);
-                    if (e != hipSuccess) fail(DSN_EHIP, "dit attention launch failed: %s", hipGetErrorString(e));
-                  });
+        prof_launch("dit.attention", (double)M * D * 2.0 * P * 4.0, st, [&] {
+          const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8);
+          if (e != hipSuccess) fail(DSN_EHIP, "dit attention launch failed: %s", hipGetErrorString(e));
+        });
       }
       {
         Tag tg(this, "dit.attn_out");
-        GemmDesc d = fp8 ? fp8_desc(A8, SA8, L.out8, (int)M)
-                         : base_desc(qa_ipp ? AOp : Ap, M * D, L.out, 1, (int)M, (int)M);
+        GemmDesc d = layer_desc(qa_ipp ? AOp : Ap, A8, SA8, L.out, L.out8);
         if (fold_rows) {
           d.panel_rows = fold_rows;
           d.resid = X;
@@ -1214,28 +1236,11 @@ struct dsn_ctx {
           d.stat_np = D / 64;
           d.m_fast = 0;  // an XCD's share walks ACROSS the 8 column tiles of a few row panels: the whole
                          // 2 MB weight and 4 panels fit its L2 (m_fast = 1: every XCD re-fetches all of A)
-          if (fp8) run_fp8(d, st, 128);
-          else run(d, st, 128);
+          layer_gemm(d, 128, true);  // (never skinny: fold_rows excludes it)
           pend_n = 0;
           pend_bias = nullptr;
         } else {
-        const int obn = 128, oks = 2;
-        d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? oks : pick_ksplit(d));
-        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, obn) * oks);
-        if (d.ksplit > 1) {
-          slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
-          d.out_f32 = slabs;
-          d.slab_stride = slab_stride;
-          d.bias = nullptr;
-        } else {
-          d.resid = X;
-          d.out_f32 = X;
-        }
-        if (fp8) run_fp8(d, st, obn);
-        else if (skinny) run(d, st, 0, true);
-        else run(d, st, short_panel ? obn : 0);
-        pend_n = d.ksplit > 1 ? d.ksplit : 0;
-        pend_bias = nullptr;
+          stream_gemm(d, 128, 2, 272);
         }
       }
       if (!fold_rows)
@@ -1247,9 +1252,7 @@ struct dsn_ctx {
         // FF-in through the row-panel kernel: ceil(M/272) equal row panels x 256-column tiles -- for the
         // benchmark shape (M = 2112 -> 8 panels of 264 rows, N = 8192) exactly 256 workgroups, one round.
         Tag tg(this, "dit.ff_in");
-        GemmDesc d = fp8 ? (fold_rows ? fp8_desc(X8, SX8, L.ff1f8, (int)M) : fp8_desc(A8, SA8, L.ff1_8, (int)M))
-                         : (fold_rows ? base_desc(Xp, M * D, L.ff1f, 1, (int)M, (int)M)
-                                      : base_desc(Ap, M * D, L.ff1, 1, (int)M, (int)M));
+        GemmDesc d = fold_rows ? layer_desc(Xp, X8, SX8, L.ff1f, L.ff1f8) : layer_desc(Ap, A8, SA8, L.ff1, L.ff1_8);
         d.swiglu = 1;
         if (fold_rows) {
           d.ln_stats = ST;
@@ -1272,37 +1275,14 @@ struct dsn_ctx {
           const int np = cdiv(M, 272);
           d.panel_rows = short_panel ? panel_rows_for(cdiv(4 * D * 2, 256)) : (cdiv(M, np) + 7) / 8 * 8;
         }
-        if (fp8) {
-          // 256-column fp8 tiles up to 17 row sub-tiles (8 waves x 256 registers, branch-free main loop): one round at C2
-          d.panel_rows = panel_rows_for(cdiv(4 * D * 2, 256));
-          run_fp8(d, st, 256);
-        } else if (skinny) {
-          run(d, st, 0, true);
-        } else {
-          run(d, st, use_panel ? 256 : 0);
-        }
+        // fp8: 256-column tiles up to 17 row sub-tiles (8 waves x 256 registers, branch-free main loop): one round at C2
+        if (fp8) d.panel_rows = panel_rows_for(cdiv(4 * D * 2, 256));
+        layer_gemm(d, 256, use_panel);
       }
       {
         Tag tg(this, "dit.ff_out");
-        GemmDesc d = fp8 ? fp8_desc(H8, SH8, L.ff2_8, (int)M) : base_desc(FF, M * 4 * D, L.ff2, 1, (int)M, (int)M);
-        const int fbn = 256, fks = 4;
-        d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? fks : pick_ksplit(d));
-        if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, fbn) * fks, fp8 ? 208 : 272);
-        if (d.ksplit > 1) {
-          slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
-          d.out_f32 = slabs;
-          d.slab_stride = slab_stride;
-          pend_bias = d.bias;
-          d.bias = nullptr;
-        } else {
-          d.resid = X;
-          d.out_f32 = X;
-          pend_bias = nullptr;
-        }
-        if (fp8) run_fp8(d, st, fbn);
-        else if (skinny) run(d, st, 0, true);
-        else run(d, st, short_panel ? fbn : 0);
-        pend_n = d.ksplit > 1 ? d.ksplit : 0;
+        GemmDesc d = layer_desc(FF, H8, SH8, L.ff2, L.ff2_8);
+        stream_gemm(d, 256, 4, fp8 ? 208 : 272);
       }
     }
     // final residual update + planes of X (no norm before project_out)
@@ -1664,30 +1644,7 @@ struct dsn_ctx {
       for (int j = 0; j < 3; ++j) {
         const ResUnit& r = b.ru[j];
         const ActP& next = j < 2 ? b.ru[j + 1].act0 : (bi + 1 < dec_blocks.size() ? dec_blocks[bi + 1].act : dec_final_act);
-        if (ru_fusable(r)) {  // pb -> ph, then the two trade places
-          run_ru(r, pb, o_ps, xf, j < 2 ? xf : nullptr, ph, next, S, Lo, st);
-          std::swap(pb, ph);
-          continue;
-        }
-        Tag tg(this, "vae.residual_unit_2gemm");
-        {
-          GemmDesc d = base_desc(pb, o_ps, r.conv7, S, (int)Lo, (int)Lo);
-          d.tap_dil = r.dil;
-          d.in_pad = r.dil * (r.conv7.taps - 1) / 2;
-          d.out_planes = ph;
-          d.out_ps = o_ps;
-          set_act(d, r.act2);
-          run(d, st);
-        }
-        {
-          GemmDesc d = base_desc(ph, o_ps, r.conv1, S, (int)Lo, (int)Lo);
-          d.resid = xf;
-          d.out_planes = pb;
-          d.out_ps = o_ps;
-          if (j < 2) d.out_f32 = xf;
-          set_act(d, next);
-          run(d, st);
-        }
+        res_unit(r, pb, ph, o_ps, xf, j < 2, next, S, Lo, st);
       }
       std::swap(pa, pb);
       a_ps = o_ps;
@@ -1734,30 +1691,7 @@ struct dsn_ctx {
       for (int j = 0; j < 3; ++j) {
         const ResUnit& r = b.ru[j];
         const ActP& next = j < 2 ? b.ru[j + 1].act0 : b.act;
-        if (ru_fusable(r)) {  // pa -> ph, then the two trade places
-          run_ru(r, pa, a_ps, xf, j < 2 ? xf : nullptr, ph, next, S, l, st);
-          std::swap(pa, ph);
-          continue;
-        }
-        Tag tg(this, "vae.residual_unit_2gemm");
-        {
-          GemmDesc d = base_desc(pa, a_ps, r.conv7, S, (int)l, (int)l);
-          d.tap_dil = r.dil;
-          d.in_pad = r.dil * (r.conv7.taps - 1) / 2;
-          d.out_planes = ph;
-          d.out_ps = a_ps;
-          set_act(d, r.act2);
-          run(d, st);
-        }
-        {
-          GemmDesc d = base_desc(ph, a_ps, r.conv1, S, (int)l, (int)l);
-          d.resid = xf;
-          d.out_planes = pa;
-          d.out_ps = a_ps;
-          if (j < 2) d.out_f32 = xf;
-          set_act(d, next);
-          run(d, st);
-        }
+        res_unit(r, pa, ph, a_ps, xf, j < 2, next, S, l, st);
       }
       const long lo = l / b.stride;
       const long o_ps = (long)S * lo * b.cout;
@@ -3099,13 +3033,7 @@ int dsn_test_igemm(dsn_ctx* ctx, const float* a, const float* w, float* out, int
     op16_t* wp = ctx->wsbuf<op16_t>("t_w", wn * P);
     launch_to_planes(a, ap, an, PL, an, st);
     launch_to_planes(w, wp, wn, PL, wn, st);
-    Packed pk;
-    pk.w = wp;
-    pk.ps = wn;
-    pk.N = N;
-    pk.Cin = Cin;
-    pk.taps = taps;
-    pk.K = taps * Cin;
+    const Packed pk = plain_packed(wp, wn, N, Cin, taps);
     GemmDesc d = ctx->base_desc(ap, an, pk, B, rows_per_b, Lin);
     d.in_stride = in_stride;
     d.tap_dil = tap_dil;
@@ -3133,13 +3061,7 @@ int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream) {
     op16_t* wp = ctx->wsbuf<op16_t>("tg_w", wn * P);
     launch_to_planes(t->a, ap, t->a_numel, PL, t->a_numel, st);
     launch_to_planes(t->w, wp, wn, PL, wn, st);
-    Packed pk;
-    pk.w = wp;
-    pk.ps = wn;
-    pk.N = t->N;
-    pk.Cin = t->Cin;
-    pk.taps = t->taps;
-    pk.K = t->taps * t->Cin;
+    Packed pk = plain_packed(wp, wn, t->N, t->Cin, t->taps);
     pk.bias = const_cast<float*>(t->bias);
     pk.bias_mod = t->bias ? (t->bias_mod > 0 ? t->bias_mod : t->N) : 1;
     GemmDesc d = ctx->base_desc(ap + t->a_off, t->a_numel, pk, t->B, t->rows_per_b, t->Lin);
@@ -3515,13 +3437,7 @@ int dsn_bench_igemm(dsn_ctx* ctx, int B, int Lin, int Cin, int N, int taps, int 
     launch_randn(wf, wn, 2, 0, nullptr);
     launch_to_planes(af, ap, an, PL, an, nullptr);
     launch_to_planes(wf, wp, wn, PL, wn, nullptr);
-    Packed pk;
-    pk.w = wp;
-    pk.ps = wn;
-    pk.N = N;
-    pk.Cin = Cin;
-    pk.taps = taps;
-    pk.K = taps * Cin;
+    const Packed pk = plain_packed(wp, wn, N, Cin, taps);
     GemmDesc d = ctx->base_desc(ap, an, pk, B, Lin, Lin);
     d.tap_dil = tap_dil;
     d.in_pad = in_pad;
