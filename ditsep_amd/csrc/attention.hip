@@ -1,6 +1,8 @@
 // MFMA attention for the score networks on gfx950: 64-wide DiT heads / one 64-256 wide NCSN++ head.  Sequences up
 // to 256 tokens keep every score in registers (attention_mfma_kernel); longer ones walk the keys in blocks with an
-// online softmax (attention_long_kernel).
+// online softmax (attention_long_kernel).  VARLEN instantiations of both take the valid token count of every item
+// (ragged batches padded to S): keys >= lens[item] are masked and key tiles wholly past it are neither loaded nor
+// multiplied -- the item is uniform for the workgroup, so the branch is too.
 //
 // Inputs are the operand planes the fused QKV GEMM epilogue wrote: q (rotary applied,
 // pre-scaled by 1/sqrt(dh)) | k (rotary applied) | v, token-major [B*S][3*D].
@@ -68,10 +70,11 @@ __device__ __forceinline__ void store_query_out(op16_t* __restrict__ out, long o
   }
 }
 
-template <int P, int F16, int NKT, int DH>
+template <int P, int F16, int NKT, int DH, bool VARLEN = false>
 __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __restrict__ qkv, long ps,
                                                              op16_t* __restrict__ out, long out_ps, int S, int H,
-                                                             unsigned char* __restrict__ o8s) {
+                                                             unsigned char* __restrict__ o8s,
+                                                             const int* __restrict__ lens) {
   // blockDim.x / 64 waves per workgroup: they stage V once and each take query tiles of the same (item, head)
   extern __shared__ __attribute__((aligned(16))) op16_t vlds[];  // [P][nkt*16][DH]
   const int lane = threadIdx.x & 63;
@@ -84,6 +87,10 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
   const op16_t* vb = qb + 2 * D;
   const int nkt = (S + 15) >> 4;
   const int vrows = nkt * 16;
+  // keys of this item: all S tokens, or (VARLEN) its first lens[b]; query rows stay all S (padded rows attend to the
+  // item's valid keys, their values are unspecified but finite)
+  const int Sk = VARLEN ? min(max(__builtin_amdgcn_readfirstlane(lens[b]), 1), S) : S;
+  const int nk = VARLEN ? (Sk + 15) >> 4 : nkt;  // key tiles that hold a valid key
 
   const int r16 = lane & 15, g = lane >> 4;
   const int tq = r16 >> 2, tp = r16 & 3;  // role inside a 16-lane transposed-read group
@@ -101,20 +108,21 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
         pq[p][ks] = *reinterpret_cast<const op16x8*>(qb + p * ps + qrow0 * rs + ks * 32 + g * 8);
 #pragma unroll
         for (int kt = 0; kt < (PREFETCH ? NKT : 1); ++kt) {
-          const int krow = min(kt * 16 + r16, S - 1);
-          pk[kt][p][ks] = *reinterpret_cast<const op16x8*>(kb + p * ps + krow * rs + ks * 32 + g * 8);
+          const int krow = min(kt * 16 + r16, Sk - 1);
+          if (!VARLEN || kt < nk)
+            pk[kt][p][ks] = *reinterpret_cast<const op16x8*>(kb + p * ps + krow * rs + ks * 32 + g * 8);
         }
       }
   }
 
-  // stage V (zero beyond S) -- DH/8 lanes x 16 B per token row
+  // stage V (zero beyond the last key) -- DH/8 lanes x 16 B per token row; VARLEN: only the tiles that hold a key
   constexpr int CPRV = DH / 8;
   const op16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int idx = threadIdx.x; idx < vrows * CPRV; idx += blockDim.x) {
+  for (int idx = threadIdx.x; idx < (VARLEN ? nk * 16 : vrows) * CPRV; idx += blockDim.x) {
     const int row = idx / CPRV, c = idx % CPRV;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      const op16x8 v = row < S ? *reinterpret_cast<const op16x8*>(vb + p * ps + row * rs + c * 8) : zero8;
+      const op16x8 v = row < Sk ? *reinterpret_cast<const op16x8*>(vb + p * ps + row * rs + c * 8) : zero8;
       *reinterpret_cast<op16x8*>(vlds + ((long)p * vrows + row) * DH + c * 8) = v;
     }
   }
@@ -138,8 +146,8 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (kt < nkt) {
-        const int krow = min(kt * 16 + r16, S - 1);
+      if (kt < nk) {
+        const int krow = min(kt * 16 + r16, Sk - 1);
 #pragma unroll
         for (int ks = 0; ks < KSD; ++ks) {
           op16x8 fk[P];
@@ -159,10 +167,10 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < nkt) {
+      if (kt < nk) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if (kt * 16 + 4 * g + r >= S) sc[kt][r] = -INFINITY;
+          if (kt * 16 + 4 * g + r >= Sk) sc[kt][r] = -INFINITY;
           mx = fmaxf(mx, sc[kt][r]);
         }
       }
@@ -174,7 +182,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
     for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pv = kt < nkt ? expf(sc[kt][r] - mx) : 0.f;  // exp(-inf) = 0 for masked keys
+        const float pv = kt < nk ? expf(sc[kt][r] - mx) : 0.f;  // exp(-inf) = 0 for masked keys
         sc[kt][r] = pv;
         lsum += pv;
       }
@@ -189,7 +197,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
     for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < NKT / 2; ++u) {
-      if (2 * u < nkt) {
+      if (2 * u < nk) {
         op16x8 fp[P];
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
           fp[0][jj] = hi;
           if (P == 2) fp[P - 1][jj] = lo;
         }
-        const bool second = 2 * u + 1 < nkt;
+        const bool second = 2 * u + 1 < nk;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
           op16x8 fv[P];
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
             const op16_t* base = vlds + (long)p * vrows * DH + dt * 16 + 4 * tp;
             const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                 (__attribute__((address_space(3))) s16x4*)(base + ((2 * u) * 16 + 4 * g + tq) * DH));
-            // rows of a tile past the sequence end are zero-filled in LDS; clamp the address only
+            // rows of a tile past the last key are zero-filled in LDS; clamp the address only
             const int t1 = second ? 2 * u + 1 : 2 * u;
             s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                 (__attribute__((address_space(3))) s16x4*)(base + (t1 * 16 + 4 * g + tq) * DH));
@@ -237,10 +245,11 @@ __global__ __launch_bounds__(512) void attention_mfma_kernel(const op16_t* __res
 // fragment scheme, but keys are walked in blocks of KBT tiles with an online softmax (running max m, running sum l,
 // accumulator rescaled by exp(m_old - m_new) per block), V staged per block -- registers and LDS no longer grow
 // with S.  One wave per (item, head, 16-query tile).
-template <int P, int F16, int DH>
+template <int P, int F16, int DH, bool VARLEN = false>
 __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __restrict__ qkv, long ps,
                                                             op16_t* __restrict__ out, long out_ps, int S, int H,
-                                                            unsigned char* __restrict__ o8s) {
+                                                            unsigned char* __restrict__ o8s,
+                                                            const int* __restrict__ lens) {
   constexpr int KBT = 8;         // key tiles per block
   constexpr int KB = KBT * 16;   // keys per block
   extern __shared__ __attribute__((aligned(16))) op16_t vlds[];  // [P][KB][DH]
@@ -256,6 +265,7 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
   const op16_t* kb = qb + D;
   const op16_t* vb = qb + 2 * D;
   const int nqt = (S + 15) >> 4;
+  const int Sk = VARLEN ? min(max(__builtin_amdgcn_readfirstlane(lens[b]), 1), S) : S;  // keys of this item
   const int r16 = lane & 15, g = lane >> 4;
   const int tq = r16 >> 2, tp = r16 & 3;
   constexpr int KSD = DH / 32, NDT = DH / 16, CPRV = DH / 8;
@@ -275,13 +285,13 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    for (int k0 = 0; k0 < S; k0 += KB) {
+    for (int k0 = 0; k0 < Sk; k0 += KB) {
       __syncthreads();  // the previous block's V reads are done
       for (int idx = threadIdx.x; idx < KB * CPRV; idx += blockDim.x) {
         const int row = idx / CPRV, c = idx % CPRV;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-          const op16x8 v = k0 + row < S ? *reinterpret_cast<const op16x8*>(vb + p * ps + (long)(k0 + row) * rs + c * 8) : zero8;
+          const op16x8 v = k0 + row < Sk ? *reinterpret_cast<const op16x8*>(vb + p * ps + (long)(k0 + row) * rs + c * 8) : zero8;
           *reinterpret_cast<op16x8*>(vlds + ((long)p * KB + row) * DH + c * 8) = v;
         }
       }
@@ -292,22 +302,24 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
 #pragma unroll
       for (int kt = 0; kt < KBT; ++kt) {
         sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int krow = min(k0 + kt * 16 + r16, S - 1);
+        const int krow = min(k0 + kt * 16 + r16, Sk - 1);
+        if (!VARLEN || k0 + kt * 16 < Sk) {  // (VARLEN: a tile wholly past the item's keys is not loaded)
 #pragma unroll
-        for (int ks = 0; ks < KSD; ++ks) {
-          op16x8 fk[P];
+          for (int ks = 0; ks < KSD; ++ks) {
+            op16x8 fk[P];
 #pragma unroll
-          for (int p = 0; p < P; ++p)
-            fk[p] = *reinterpret_cast<const op16x8*>(kb + p * ps + (long)krow * rs + ks * 32 + g * 8);
-          if (P == 2) {
-            sc[kt] = mfma16<F16>(fk[P - 1], fq[0][ks], sc[kt]);
-            sc[kt] = mfma16<F16>(fk[0], fq[P - 1][ks], sc[kt]);
+            for (int p = 0; p < P; ++p)
+              fk[p] = *reinterpret_cast<const op16x8*>(kb + p * ps + (long)krow * rs + ks * 32 + g * 8);
+            if (P == 2) {
+              sc[kt] = mfma16<F16>(fk[P - 1], fq[0][ks], sc[kt]);
+              sc[kt] = mfma16<F16>(fk[0], fq[P - 1][ks], sc[kt]);
+            }
+            sc[kt] = mfma16<F16>(fk[0], fq[0][ks], sc[kt]);
           }
-          sc[kt] = mfma16<F16>(fk[0], fq[0][ks], sc[kt]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if (k0 + kt * 16 + 4 * g + r >= S) sc[kt][r] = -INFINITY;
+          if (k0 + kt * 16 + 4 * g + r >= Sk) sc[kt][r] = -INFINITY;
           bm = fmaxf(bm, sc[kt][r]);
         }
       }
@@ -333,6 +345,7 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
       // O^T += V^T P^T over the block's key-tile pairs
 #pragma unroll
       for (int u = 0; u < KBT / 2; ++u) {
+        if (VARLEN && k0 + 2 * u * 16 >= Sk) continue;  // both tiles of the pair carry probability 0
         op16x8 fp[P];
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
@@ -374,9 +387,10 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const op16_t* __res
 // largest dynamic LDS request the kernels are allowed (the CU's 160 KB)
 constexpr size_t ATT_LDS_LIMIT = 160 * 1024;
 
-template <int P, int F16, int DH>
+// VL: the length-aware instantiations (lens != null); kernel choice, grid and LDS depend on (B, S, H) alone
+template <int P, int F16, int DH, bool VL>
 hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B, int S, int H, unsigned char* o8s,
-                    hipStream_t st) {
+                    const int* lens, hipStream_t st) {
   const int nkt = (S + 15) / 16;
   const size_t sm = (size_t)P * nkt * 16 * DH * sizeof(op16_t);
   // more than 256 keys, or a whole-sequence V that does not fit in LDS (two planes of a 256-wide head beyond 160 keys:
@@ -385,23 +399,23 @@ hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B,
     const size_t sml = (size_t)P * 128 * DH * sizeof(op16_t);
     static std::atomic<unsigned long long> attr_l{0};
     if (dsn_first_use_on_device(attr_l)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<P, F16, DH>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<P, F16, DH, VL>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
     }
     const int W = 4;  // measured (1 / 2 / 4 / 8): NCSN++ 944 tokens 7.48 / 7.17 / 7.14 / 7.31 ms per call, DiT 301 tokens 32.5 / 26.5 / 23.4 / 25.0 us
-    hipLaunchKernelGGL((attention_long_kernel<P, F16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sml, st, qkv, ps,
-                       out, out_ps, S, H, o8s);
+    hipLaunchKernelGGL((attention_long_kernel<P, F16, DH, VL>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sml, st, qkv, ps,
+                       out, out_ps, S, H, o8s, lens);
     return hipGetLastError();
   }
   if (nkt <= 4) {
     // waves per workgroup: each takes one query tile of the same (item, head) and they stage V once
     const int W = 3;  // measured at S = 33 (3 query tiles): 12.9 / 12.6 / 12.3 / 12.5 us for 1..4
-    hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 4, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st, qkv,
-                       ps, out, out_ps, S, H, o8s);
+    hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 4, DH, VL>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st, qkv,
+                       ps, out, out_ps, S, H, o8s, lens);
   } else {
     static std::atomic<unsigned long long> attr{0};
     if (dsn_first_use_on_device(attr)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel<P, F16, 16, DH>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel<P, F16, 16, DH, VL>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
     }
     // wide heads stage a large V block (DH * nkt * 32 B): share it between the query tiles' waves
@@ -409,29 +423,32 @@ hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B,
     // one wave per workgroup for 64-wide heads: at S = 236 every one of the 15 query tiles staged the 30 KB of V
     // again -- 44 -> 23 us per launch at the C5 shape)
     const int W = nkt >= 8 ? 8 : (nkt >= 4 ? 4 : 1);
-    hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 16, DH>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st,
-                       qkv, ps, out, out_ps, S, H, o8s);
+    hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 16, DH, VL>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st,
+                       qkv, ps, out, out_ps, S, H, o8s, lens);
   }
   return hipGetLastError();
 }
 
-template <int DH>
+template <int DH, bool VL = false>
 hipError_t launch_dh(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H,
-                     unsigned char* o8s, hipStream_t st) {
+                     unsigned char* o8s, hipStream_t st, const int* lens = nullptr) {
   const int P = PL_COUNT(pl), f16 = PL_F16(pl);
-  if (P == 1 && !f16) return launch_t<1, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  if (P == 2 && !f16) return launch_t<2, 0, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  if (P == 1) return launch_t<1, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
-  return launch_t<2, 1, DH>(qkv, ps, out, out_ps, B, S, H, o8s, st);
+  if (P == 1 && !f16) return launch_t<1, 0, DH, VL>(qkv, ps, out, out_ps, B, S, H, o8s, lens, st);
+  if (P == 2 && !f16) return launch_t<2, 0, DH, VL>(qkv, ps, out, out_ps, B, S, H, o8s, lens, st);
+  if (P == 1) return launch_t<1, 1, DH, VL>(qkv, ps, out, out_ps, B, S, H, o8s, lens, st);
+  return launch_t<2, 1, DH, VL>(qkv, ps, out, out_ps, B, S, H, o8s, lens, st);
 }
 
 }  // namespace
 
 // dh = head width (64: DiT; 64/128/256: the single-head NCSN++ attention blocks).  Returns the launch status
-// (hipErrorNotSupported: no kernel for this head width).
+// (hipErrorNotSupported: no kernel for this head width).  lens: the length-aware instantiations, built for the DiT's
+// 64-wide heads only (the NCSN++ blocks never see a ragged batch).
 hipError_t launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H, int dh,
-                                 hipStream_t st, unsigned char* out_fp8_scale) {
+                                 hipStream_t st, unsigned char* out_fp8_scale, const int* lens) {
   if (B < 1 || S < 1 || H < 1) return hipErrorInvalidValue;
+  if (lens) return dh == 64 ? launch_dh<64, true>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st, lens)
+                            : hipErrorNotSupported;
   if (dh == 64) return launch_dh<64>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
   if (dh == 128) return launch_dh<128>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);
   if (dh == 256) return launch_dh<256>(qkv, ps, out, out_ps, pl, B, S, H, out_fp8_scale, st);

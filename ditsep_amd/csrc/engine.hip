@@ -248,6 +248,8 @@ struct dsn_ctx {
   }
   std::vector<float> tv_host;  // uploaded timestep table signature
   int tv_B = -1;
+  std::vector<int> lens_host;  // uploaded ragged token counts and where they went
+  const int* lens_dev = nullptr;
 
   // Run `body(stream)` -- a pure sequence of kernel launches over workspace pointers --
   // either eagerly or as a cached hipGraph.  The first call with a given key runs
@@ -1034,7 +1036,11 @@ struct dsn_ctx {
     }
   } time_cache;
 
-  float* dit_forward(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st) {
+  // lens (device int [B], null = dense): a ragged batch padded to T frames -- tokens per item, 1 + its frame count.
+  // The kernel-family choice below is that of (B, T); only the attention launch takes its length-aware variant (every
+  // other operation acts per token, so an item's valid rows come out as in a call of its own).
+  float* dit_forward(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st,
+                     const int* lens = nullptr) {
     const int n = cfg.n_src, Dl = cfg.latent_dim, D = cfg.dit_embed_dim, H = cfg.dit_heads;
     const int io = n * Dl, din = io + Dl, S = T + 1;
     const long Mt = (long)B * T, M = (long)B * S;
@@ -1198,7 +1204,7 @@ struct dsn_ctx {
         q.ipp = qa_ipp;
         q.q_scale = 0.125f;
         const double flops = 2.0 * (double)M * 3.0 * D * D + 4.0 * (double)B * H * (double)S * S * 64.0;
-        const hipError_t e = profiled({"dit.qkv_attention", flops}, st, [&] { return qkv_attention_launch(q, PL, st); });
+        const hipError_t e = profiled({"dit.qkv_attention", flops}, st, [&] { return qkv_attention_launch(q, PL, st, lens); });
         if (e != hipSuccess) fail(DSN_EHIP, "qkv_attention launch failed: %s", hipGetErrorString(e));
       } else {
         {  // q|k|v operand planes: rotary + 1/sqrt(dh) fused into the epilogue
@@ -1217,7 +1223,7 @@ struct dsn_ctx {
           layer_gemm(d, 256, short_panel);
         }
         prof_launch("dit.attention", (double)M * D * 2.0 * P * 4.0, st, [&] {
-          const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8);
+          const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8, lens);
           if (e != hipSuccess) fail(DSN_EHIP, "dit attention launch failed: %s", hipGetErrorString(e));
         });
       }
@@ -1310,9 +1316,11 @@ struct dsn_ctx {
 
 #include "engine_ncsnpp.inc"
 
-  float* score_tokens(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st) {
+  float* score_tokens(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st,
+                      const int* lens = nullptr) {
     if (!finalized) fail(DSN_ESTATE, "weights not finalized");
-    if (cfg.score_kind == DSN_SCORE_DIT) return dit_forward(xt, t, mix, B, T, st);
+    if (cfg.score_kind == DSN_SCORE_DIT) return dit_forward(xt, t, mix, B, T, st, lens);
+    if (lens) fail(DSN_EINVAL, "ragged batches need the DiT score network");
     if (cfg.score_kind == DSN_SCORE_NCSNPP) {
       Tag tg(this, "ncsnpp.conv");
       return ncsnpp_forward(xt, t, mix, B, T, st);
@@ -1382,6 +1390,29 @@ struct dsn_ctx {
     tv_host = ht;
     tv_B = B;
   }
+  // Ragged batches.  check_frames: the refusals, before anything is allocated or launched.  upload_lens: the token
+  // counts 1 + frames[b] into the fixed workspace buffer "ragged_lens" the length-aware attention kernels read --
+  // outside any capture, so the lengths are data of a cached graph, not constants of it.
+  void check_frames(const char* who, const int32_t* frames, int B, int T) const {
+    if (!frames) fail(DSN_EINVAL, "%s: frames is null", who);
+    if (cfg.score_kind != DSN_SCORE_DIT)
+      fail(DSN_EINVAL, "%s: ragged batches need the DiT score network (NCSN++ convolves across time: padding would "
+           "change an item's result)", who);
+    for (int b = 0; b < B; ++b)
+      if (frames[b] < 1 || frames[b] > T)
+        fail(DSN_EINVAL, "%s: frame count frames[%d] = %d outside [1, T = %d]", who, b, (int)frames[b], T);
+  }
+  const int* upload_lens(const int32_t* frames, int B, hipStream_t st) {
+    std::vector<int> h((size_t)B);
+    for (int b = 0; b < B; ++b) h[b] = 1 + frames[b];
+    int* d = wsbuf<int>("ragged_lens", B);
+    if (h == lens_host && d == lens_dev) return d;
+    HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    lens_host = h;
+    lens_dev = d;
+    return d;
+  }
   // Every step's time embedding in one batch, off the per-call path (-1.3 % sampler time).  time_cache is only
   // valid while the sampler pass that holds this object (or its graph capture) runs.
   struct TimeEmbedPass {
@@ -1408,7 +1439,10 @@ struct dsn_ctx {
     float* inter = nullptr;
     long draws(int N) const { return 1 + (long)N * (c + (pred == DSN_PRED_NONE ? 0 : 1)); }
   };
-  float* pc_sample(const float* y, const float* noise, int B, int T, int N, const PcOpts& o, hipStream_t st) {
+  // lens (device, null = dense): ragged batch -- every score call takes it, and the result's frames past an item's
+  // length are written as zero (the update kernels are elementwise: padding costs them the padded positions only)
+  float* pc_sample(const float* y, const float* noise, int B, int T, int N, const PcOpts& o, hipStream_t st,
+                   const int* lens = nullptr) {
     const int n = cfg.n_src, Dl = cfg.latent_dim;
     const long sz = (long)B * n * Dl * T;
     float* x = wsbuf<float>("pc_x", sz);
@@ -1425,7 +1459,7 @@ struct dsn_ctx {
     for (int i = 0; i < N; ++i) {
       const float* ti = tv + (long)i * B;
       for (int k = 0; k < o.c; ++k) {
-        float* sc = score_tokens(x, ti, y, B, T, st);
+        float* sc = score_tokens(x, ti, y, B, T, st, lens);
         if (norms) {
           launch_pc_item_norms(sc, (long)n * Dl * T, B, norms, st);
           launch_pc_item_norms(z, (long)n * Dl * T, B, norms + B, st);
@@ -1442,11 +1476,12 @@ struct dsn_ctx {
         if (o.denoise && i == N - 1) HIPCHK(hipMemcpyAsync(xm, x, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
         continue;
       }
-      float* sc = score_tokens(x, ti, y, B, T, st);
+      float* sc = score_tokens(x, ti, y, B, T, st, lens);
       launch_pc_predictor(x, xm, y, sc, z, cfg.sde_theta, dt, s.G[i], s.g[i], o.pred == DSN_PRED_EULER_MARUYAMA, B, n,
                           Dl, T, st);
       z += sz;
     }
+    if (lens) launch_zero_tail(o.denoise ? xm : x, lens, B, n, Dl, T, st);
     return o.denoise ? xm : x;
   }
 
@@ -1932,14 +1967,38 @@ int dsn_ouve_schedule(const dsn_ctx* ctx, int N, float t_eps, float snr, float* 
   return DSN_OK;
 }
 
-int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
-                     int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
+int dsn_score_ragged(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
+                     int B, int T, void* stream) {
+  return guarded(ctx, [&] {
+    if (!xt || !t || !mix || !out || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_score_ragged: bad arguments");
+    ctx->check_frames("dsn_score_ragged", frames, B, T);
+    hipStream_t st = (hipStream_t)stream;
+    const int* lens = ctx->upload_lens(frames, B, st);
+    float* sc = ctx->score_tokens(xt, t, mix, B, T, st, lens);
+    launch_unpack_tokens(sc, out, B, ctx->cfg.n_src * ctx->cfg.latent_dim, T, st);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// dsn_pc_sample_ex (frames == null) and dsn_pc_sample_ragged
+static int pc_sample_call(dsn_ctx* ctx, const float* y, const int32_t* frames, bool ragged, const float* noise,
+                          uint64_t seed, float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out,
+                          void* stream) {
   return guarded(ctx, [&] {
     if (!y || !x_out || !opts || B <= 0 || T <= 0 || N <= 0 || opts->corrector_steps < 0)
       fail(DSN_EINVAL, "dsn_pc_sample: bad arguments");
     if (opts->predictor < 0 || opts->predictor > DSN_PRED_NONE || opts->corrector < 0 ||
         opts->corrector > DSN_CORR_LANGEVIN)
       fail(DSN_EINVAL, "dsn_pc_sample: unknown predictor %d / corrector %d", opts->predictor, opts->corrector);
+    const int* lens = nullptr;
+    if (ragged) {
+      ctx->check_frames("dsn_pc_sample_ragged", frames, B, T);
+      if (opts->corrector == DSN_CORR_LANGEVIN)
+        fail(DSN_EINVAL, "dsn_pc_sample_ragged: the langevin corrector (DSN_CORR_LANGEVIN) has no ragged form: its "
+             "per-item norms would run over the padding");
+      if (!ctx->finalized) fail(DSN_ESTATE, "weights not finalized");
+      lens = ctx->upload_lens(frames, B, (hipStream_t)stream);
+    }
     dsn_ctx::PcOpts o;
     o.pred = opts->predictor;
     o.corr = opts->corrector;
@@ -1961,16 +2020,27 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
       }
     } restore{ctx, graphs};
     char key[192];
-    snprintf(key, sizeof key, "pc:%d:%d:%d:%d:%a:%a:%d:%d:%d:%d", B, T, N, o.c, o.snr, o.t_eps, o.denoise, o.pred,
-             o.corr, opts->prior_mean != nullptr);
+    // (the last field marks a ragged call: the same graph whatever the lengths, another one than the dense call's)
+    snprintf(key, sizeof key, "pc:%d:%d:%d:%d:%a:%a:%d:%d:%d:%d:%d", B, T, N, o.c, o.snr, o.t_eps, o.denoise, o.pred,
+             o.corr, opts->prior_mean != nullptr, lens != nullptr);
     ctx->run_sampler({y, noise, opts->prior_mean, seed, x_out, B, T, o.draws(N), (hipStream_t)stream},
                      ctx->schedule(N, o.t_eps, o.snr).t, key, o.denoise ? "pc_xm" : "pc_x",
                      [&](const float* yb, const float* nz, const float* pm, hipStream_t s2) {
                        o.prior_mean = pm;
-                       return ctx->pc_sample(yb, nz, B, T, N, o, s2);
+                       return ctx->pc_sample(yb, nz, B, T, N, o, s2, lens);
                      });
     if (nfe_out) *nfe_out = N * (o.c + 1);
   });
+}
+
+int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
+                     int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
+  return pc_sample_call(ctx, y, nullptr, false, noise, seed, x_out, B, T, N, opts, nfe_out, stream);
+}
+
+int dsn_pc_sample_ragged(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
+                         float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
+  return pc_sample_call(ctx, y, frames, true, noise, seed, x_out, B, T, N, opts, nfe_out, stream);
 }
 
 int dsn_pc_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T, int N,
@@ -3184,6 +3254,17 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
       return p;
     };
     op16_t* oplanes = reinterpret_cast<op16_t*>(t->out_planes);
+    // ATTENTION / QKV_ATTENTION with `lens`: checked on the host (this synchronises the stream), then passed through
+    auto checked_lens = [&](const char* who) -> const int* {
+      if (!t->lens) return nullptr;
+      std::vector<int32_t> h((size_t)t->B);
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpy(h.data(), t->lens, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+      for (int b = 0; b < t->B; ++b)
+        if (h[b] < 1 || h[b] > t->S)
+          fail(DSN_EINVAL, "test_kernel %s: lens[%d] = %d outside [1, S = %d]", who, b, (int)h[b], t->S);
+      return reinterpret_cast<const int*>(t->lens);
+    };
     switch (t->kind) {
       case DSN_TK_ATTENTION: {
         if (t->B < 1 || t->S < 1 || t->H < 1) fail(DSN_EINVAL, "test_kernel attention: B, S, H must be positive");
@@ -3192,10 +3273,12 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         if (!!t->out_fp8 != !!t->out_fp8_scale || (!t->out_fp8 && !oplanes))
           fail(DSN_EINVAL, "test_kernel attention: needs out_planes, or out_fp8 with out_fp8_scale");
         if (t->out_fp8 && D % 32 != 0) fail(DSN_EINVAL, "test_kernel attention: fp8 output needs H*dh %% 32 == 0");
+        const int* lens = checked_lens("attention");
         const op16_t* qkv = planes_of("tk_a", t->a, n);
         const hipError_t e = launch_attention_mfma(qkv, n, t->out_fp8 ? reinterpret_cast<op16_t*>(t->out_fp8) : oplanes,
-                                                   t->out_ps, PL, t->B, t->S, t->H, t->dh, st, t->out_fp8_scale);
-        if (e == hipErrorNotSupported) fail(DSN_EINVAL, "test_kernel attention: unsupported head width %d", t->dh);
+                                                   t->out_ps, PL, t->B, t->S, t->H, t->dh, st, t->out_fp8_scale, lens);
+        if (e == hipErrorNotSupported)
+          fail(DSN_EINVAL, "test_kernel attention: unsupported head width %d%s", t->dh, lens ? " with lens (64 only)" : "");
         if (e != hipSuccess) fail(DSN_EHIP, "test_kernel attention: launch failed: %s", hipGetErrorString(e));
         break;
       }
@@ -3205,6 +3288,7 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         if (t->a_numel != M * t->D || t->w_numel != 3L * t->D * t->D)
           fail(DSN_EINVAL, "test_kernel qkv_attention: a_numel / w_numel do not match [B*S][D] / [3 D][D]");
         if (!t->rope_cos || !t->rope_sin) fail(DSN_EINVAL, "test_kernel qkv_attention: rope_cos / rope_sin [S][32] missing");
+        const int* lens = checked_lens("qkv_attention");
         QkvAttnDesc q;
         memset(&q, 0, sizeof q);
         q.A = planes_of("tk_a", t->a, t->a_numel);
@@ -3222,7 +3306,7 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         q.S = t->S;
         q.ipp = t->ipp;
         q.q_scale = 0.125f;
-        const hipError_t e = qkv_attention_launch(q, PL, st);
+        const hipError_t e = qkv_attention_launch(q, PL, st, lens);
         if (e != hipSuccess)
           fail(DSN_EHIP, "test_kernel qkv_attention: refused or failed: %s (D=%d H=%d S=%d ipp=%d planes=%d)",
                hipGetErrorString(e), t->D, t->H, t->S, t->ipp, P);

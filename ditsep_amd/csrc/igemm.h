@@ -168,7 +168,9 @@ struct QkvAttnDesc {
   int panels;             // set by the launcher
   float q_scale;          // 1 / sqrt(64)
 };
-hipError_t qkv_attention_launch(const QkvAttnDesc& d, int pl, hipStream_t stream);
+// lens != null (device, int [M / S], 1 <= lens[item] <= S; the caller validates): the length-aware instantiations,
+// which mask keys >= lens[item] -- same tile choice and grid as the dense launch
+hipError_t qkv_attention_launch(const QkvAttnDesc& d, int pl, hipStream_t stream, const int* lens = nullptr);
 int qkv_attention_max_rows();            // tallest panel (240)
 int qkv_attention_panel_rows(int rows);   // tile height the launcher picks for panels of `rows` rows (144 | 240)
 

@@ -43,6 +43,9 @@ void launch_mix_predictor(float* x, float* x_mean, const float* score_tok, const
 void launch_sb_update(float* x, const float* est_tok, const float* third, float w_prev, float w_est, float w3,
                       int third_is_y, int B, int n, int D, int T, hipStream_t s);
 void launch_repeat_sources(const float* y, float* x, int B, int n, int D, int T, hipStream_t s);
+// ragged batches: x [B,n,D,T], x[b, :, :, t] = 0 for t >= lens[b] - 1; lens (device, [B]) counts an item's tokens
+// including the DiT's timestep token, as the attention kernels take it
+void launch_zero_tail(float* x, const int* lens, int B, int n, int D, int T, hipStream_t s);
 
 // ---- DiT pieces ---------------------------------------------------------------
 // x += bias + sum(split-K slabs) (written back when nslab > 0), then LayerNorm (do_norm) or a
@@ -59,8 +62,12 @@ void launch_timestep_features(const float* t, const float* w, int B, int half, o
 // out_fp8_scale != null: `out` receives fp8 (e4m3) bytes [B*S][H*dh] and out_fp8_scale the E8M0 block scales
 // [B*S][H*dh/32] (MX operand of the fp8 out-projection) instead of 16-bit planes.
 // dh in {64,128,256} (hipErrorNotSupported otherwise); returns the launch status
+// lens != null (device, int [B], 1 <= lens[b] <= S; the caller validates): ragged batch of items padded to S tokens --
+// the length-aware instantiations mask keys >= lens[b] and skip key tiles wholly past it; same kernel choice and grid
+// as the dense launch for (B, S, H).  Query rows >= lens[b] are still computed over the item's valid keys.
 hipError_t launch_attention_mfma(const op16_t* qkv, long ps, op16_t* out, long out_ps, int pl, int B, int S, int H,
-                                 int dh, hipStream_t s, unsigned char* out_fp8_scale = nullptr);
+                                 int dh, hipStream_t s, unsigned char* out_fp8_scale = nullptr,
+                                 const int* lens = nullptr);
 void launch_rope_tables(float* cos_t, float* sin_t, int S, int rot, hipStream_t s);
 
 // ---- Oobleck edges -------------------------------------------------------------

@@ -299,6 +299,15 @@ __global__ void repeat_sources_kernel(const float* __restrict__ y, float* __rest
     x[i] = y[pc_index(i, n, D, T).yi];
 }
 
+// ragged batches: x[b, :, t] = 0 for t >= lens[b] - 1 (lens counts the DiT's timestep token too); rows = n * D
+__global__ void zero_tail_kernel(float* __restrict__ x, const int* __restrict__ lens, int rows, int T, long total) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int t = (int)(i % T);
+    const int b = (int)(i / ((long)rows * T));
+    if (t >= lens[b] - 1) x[i] = 0.f;
+  }
+}
+
 // ------------------------------------------------------------------ LayerNorm
 // Residual-stream update fused with the next LayerNorm: x[row] += bias + sum of the split-K
 // partial slabs of the preceding GEMM (written back when any were added), then LayerNorm
@@ -1029,6 +1038,10 @@ void launch_sb_update(float* x, const float* est, const float* third, float w_pr
 void launch_repeat_sources(const float* y, float* x, int B, int n, int D, int T, hipStream_t st) {
   const long total = (long)B * n * D * T;
   hipLaunchKernelGGL(repeat_sources_kernel, dim3(grid_for(total)), dim3(TPB), 0, st, y, x, n, D, T, total);
+}
+void launch_zero_tail(float* x, const int* lens, int B, int n, int D, int T, hipStream_t st) {
+  const long total = (long)B * n * D * T;
+  hipLaunchKernelGGL(zero_tail_kernel, dim3(grid_for(total)), dim3(TPB), 0, st, x, lens, n * D, T, total);
 }
 void launch_residual_norm(float* x, const float* slabs, int nslab, long slab_stride, const float* bias,
                           const float* gamma, const float* beta, op16_t* out, long ps, int planes, int rows, int D,

@@ -12,6 +12,11 @@
 //
 // Tile: 144 rows x 192 columns, 8 waves as 2 (rows: 5 + 4 sub-tiles) x 4 (48 columns each), BK = 64, NST-stage ring.
 // Single-plane 16-bit operand modes only (fp16 / bf16); 64-wide heads.
+//
+// VARLEN instantiations (ragged batches padded to S tokens): the GEMM, rotary and scale run for every row as above;
+// the attention of an item masks keys >= lens[item], skips the key tiles wholly past it (a job's item is uniform for
+// its wave) and the V image holds zeros in the rows past it, so a masked key's probability 0 never meets a non-finite
+// value.  Query rows past lens[item] are computed over the item's valid keys.
 #include "igemm.h"
 #include "kernels.h"
 
@@ -29,8 +34,9 @@ __device__ __forceinline__ int qa_off(int row, int c) { return row * 64 + ((((c 
 
 // QA_TM: panel rows of the tile -- 144 (9 row sub-tiles as 5 + 4, 3-stage ring) for the 4 s shapes, 240 (15 as 8 + 7,
 // 2-stage ring: 111 KB) for one long-form item of up to 240 tokens (BASELINE config 5: 236)
-template <int F16, int NST, int NKT, int QA_TM = 144>
-__global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc d, const op16_t* __restrict__ zero_page) {
+template <int F16, int NST, int NKT, int QA_TM = 144, bool VARLEN = false>
+__global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc d, const op16_t* __restrict__ zero_page,
+                                                               const int* __restrict__ lens) {
   extern __shared__ __attribute__((aligned(16))) op16_t lds[];  // [NST][QA_TM + 192][64] ring | dummy [8][64]
   constexpr int QA_ROWS = QA_TM + QA_TN;          // staged rows per k-tile: A rows then W rows
   constexpr int QA_STAGE = QA_ROWS * QA_BK;       // elements per ring stage
@@ -162,6 +168,11 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
   for (int tm = 0; tm < MTW; ++tm) {
     if (tm >= mtw) continue;
     const int row = row0 + tm * 16 + r16;          // row inside the panel
+    bool vpad = false;                             // VARLEN: a token past its item's length -> its V row is zero
+    if (VARLEN && row < rows_here) {
+      const int itr = row / S;
+      vpad = row - itr * S >= min(max(lens[panel * d.ipp + itr], 1), S);
+    }
     if (d.bias) {
 #pragma unroll
       for (int tn = 0; tn < 3; ++tn) {
@@ -192,6 +203,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
       const int sec = col >> 6, c = col & 63;
       f32x4 v = acc[tn][tm];
       if (sec == 0) v *= d.q_scale;
+      if (VARLEN && sec == 2 && vpad) v = f32x4{0.f, 0.f, 0.f, 0.f};
       op16x4 h;
 #pragma unroll
       for (int r = 0; r < 4; ++r) h[r] = to_op16(v[r], F16);
@@ -210,6 +222,9 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
   for (int job = wave; job < items * nqt; job += 8) {
     const int it = job / nqt, qt = job - it * nqt;
     const int base = it * S;
+    // keys of this item: all S tokens, or (VARLEN) its first lens[item] in nk key tiles -- uniform for the wave
+    const int Sk = VARLEN ? min(max(__builtin_amdgcn_readfirstlane(lens[panel * d.ipp + it]), 1), S) : S;
+    const int nk = VARLEN ? (Sk + 15) >> 4 : nqt;
     const int qrow = base + min(qt * 16 + r16, S - 1);
     op16x8 fq[2];
 #pragma unroll
@@ -218,8 +233,8 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (kt < nqt) {
-        const int krow = base + min(kt * 16 + r16, S - 1);
+      if (kt < nk) {
+        const int krow = base + min(kt * 16 + r16, Sk - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const op16x8 fk = *reinterpret_cast<const op16x8*>(kl + qa_off(krow, (ks * 4 + g4) * 8));
@@ -231,10 +246,10 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < nqt) {
+      if (kt < nk) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if (kt * 16 + 4 * g4 + r >= S) sc[kt][r] = -INFINITY;
+          if (kt * 16 + 4 * g4 + r >= Sk) sc[kt][r] = -INFINITY;
           mx = fmaxf(mx, sc[kt][r]);
         }
       }
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
     for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pv = kt < nqt ? expf(sc[kt][r] - mx) : 0.f;
+        const float pv = kt < nk ? expf(sc[kt][r] - mx) : 0.f;
         sc[kt][r] = pv;
         lsum += pv;
       }
@@ -261,7 +276,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
     for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < (NKT + 1) / 2; ++u) {
-      if (2 * u < nqt) {
+      if (2 * u < nk) {
         op16x8 fp;
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
@@ -336,15 +351,25 @@ const op16_t* qa_zero_page() {
   return z;
 }
 
-template <int F16, int NST, int NKT, int TM>
-hipError_t qa_launch_t(const QkvAttnDesc& d, const op16_t* zp, hipStream_t stream) {
+template <int F16, int NST, int NKT, int TM, bool VL>
+hipError_t qa_launch_t(const QkvAttnDesc& d, const op16_t* zp, const int* lens, hipStream_t stream) {
   static std::atomic<unsigned long long> attr{0};
   if (dsn_first_use_on_device(attr))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qkv_attention_kernel<F16, NST, NKT, TM>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qkv_attention_kernel<F16, NST, NKT, TM, VL>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const size_t smem = (size_t)(NST * (TM + QA_TN) * QA_BK + 8 * QA_BK) * sizeof(op16_t);
-  hipLaunchKernelGGL((qkv_attention_kernel<F16, NST, NKT, TM>), dim3(d.panels * d.H), dim3(512), smem, stream, d, zp);
+  hipLaunchKernelGGL((qkv_attention_kernel<F16, NST, NKT, TM, VL>), dim3(d.panels * d.H), dim3(512), smem, stream, d, zp,
+                     lens);
   return hipGetLastError();
+}
+// F16 and VL (lens given) are run-time choices of the same tile
+template <int NST, int NKT, int TM>
+hipError_t qa_launch_f(const QkvAttnDesc& d, const op16_t* zp, int f16, const int* lens, hipStream_t stream) {
+  if (lens)
+    return f16 ? qa_launch_t<1, NST, NKT, TM, true>(d, zp, lens, stream)
+               : qa_launch_t<0, NST, NKT, TM, true>(d, zp, lens, stream);
+  return f16 ? qa_launch_t<1, NST, NKT, TM, false>(d, zp, nullptr, stream)
+             : qa_launch_t<0, NST, NKT, TM, false>(d, zp, nullptr, stream);
 }
 
 }  // namespace
@@ -352,7 +377,7 @@ hipError_t qa_launch_t(const QkvAttnDesc& d, const op16_t* zp, hipStream_t strea
 int qkv_attention_max_rows() { return QA_TM_MAX; }
 int qkv_attention_panel_rows(int rows) { return rows <= 144 ? 144 : QA_TM_MAX; }
 
-hipError_t qkv_attention_launch(const QkvAttnDesc& din, int pl, hipStream_t stream) {
+hipError_t qkv_attention_launch(const QkvAttnDesc& din, int pl, hipStream_t stream, const int* lens) {
   QkvAttnDesc d = din;
   if (PL_COUNT(pl) != 1 || d.D != d.H * 64 || d.D % QA_BK != 0 || d.S < 1 || d.ipp < 1 || d.ipp * d.S > QA_TM_MAX ||
       d.M <= 0 || d.M % d.S != 0 || !d.A || !d.W || (!d.out && !d.out8) || (d.out8 && !d.out8_scale) || !d.rope_cos ||
@@ -363,8 +388,7 @@ hipError_t qkv_attention_launch(const QkvAttnDesc& din, int pl, hipStream_t stre
   if (!zp) return hipErrorOutOfMemory;
   const int nqt = (d.S + 15) / 16;
   const int f16 = PL_F16(pl);
-#define QA(NST_, NKT_, TM_) \
-  return f16 ? qa_launch_t<1, NST_, NKT_, TM_>(d, zp, stream) : qa_launch_t<0, NST_, NKT_, TM_>(d, zp, stream);
+#define QA(NST_, NKT_, TM_) return qa_launch_f<NST_, NKT_, TM_>(d, zp, f16, lens, stream);
   if (d.ipp * d.S <= 144) {
     if (nqt <= 3) { QA(3, 3, 144) }
     if (nqt <= 5) { QA(3, 5, 144) }

@@ -18,7 +18,11 @@ place and in float32, removed both means and rescaled the estimate to the refere
 
 mrstft=True adds "mrstft" and "l1" per source from the device (dsn_mrstft_loss): the A-weighted multi-resolution STFT
 distance (the reference's LDM objective, src/config/ldm/training/default.yaml, unweighted) and the mean absolute
-waveform error of each reference source against the estimate the SIR permutation assigns to it."""
+waveform error of each reference source against the estimate the SIR permutation assigns to it.
+
+Utterances of different lengths (the reference evaluates them one at a time, :238): a batch whose `mix` and `target`
+are lists of differently long tensors takes the ragged route -- `length_batches` cuts a data set into such batches
+with little padding -- in which every utterance gets what it gets alone (LatentDiffSep.separate_batch)."""
 from __future__ import annotations
 
 import json
@@ -27,6 +31,51 @@ from typing import Iterable, Optional
 
 import numpy as np
 import torch
+
+
+def length_batches(lengths, batch_size: int) -> list:
+    """Index lists that cut a data set into batches of `batch_size` utterances of similar length: the indices sorted by
+    length (ties by index), then cut in order, so a batch's padding stays small.  Every index appears exactly once."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def _same_length_groups(lengths) -> dict:
+    groups: dict = {}
+    for i, L in enumerate(lengths):
+        groups.setdefault(int(L), []).append(i)
+    return groups
+
+
+def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended) -> dict:
+    """One batch of differently long utterances: mixes list of [1, L_b], targets list of [n, L_b].  The timed region is
+    sampler + decode as in the dense route; the metric kernels run per group of equal L."""
+    eng, dev = model.engine, model.engine.device
+    B = len(mixes)
+    y, frames = eng.encode_ragged(mixes, None, seed=seed + idx)
+    sampler = model.get_pc_sampler("reverse_diffusion", "ald", y, N=N, denoise=denoise, corrector_steps=corrector_steps,
+                                   snr=snr, seed=seed + idx, frames=frames)
+    lens = [int(t.shape[-1]) for t in targets]
+    torch.cuda.synchronize(dev)
+    t_s = time.perf_counter()
+    x_result, nfe = sampler()
+    est = eng.decode_ragged(x_result, frames, lens)
+    torch.cuda.synchronize(dev)
+    t_proc = time.perf_counter() - t_s
+    records = {}
+    for L, members in _same_length_groups(lens).items():
+        tgt = torch.stack([targets[i].to(dev) for i in members])
+        xr = torch.stack([est[i] for i in members])
+        si_sdr, si_sir, si_sar, perm = eng.si_bss_eval(tgt, xr, perm_by="sir", clamp_db=100.0)
+        st = eng.stoi(tgt, xr, fs, extended=stoi_extended, perm=perm) if stoi else None
+        for j, i in enumerate(members):
+            records[idx + i] = {"batch_idx": idx + i, "si_sdr": si_sdr[j].tolist(), "si_sir": si_sir[j].tolist(),
+                                "si_sar": si_sar[j].tolist(), "pesq": None,
+                                "stoi": None if st is None else st[j].tolist(), "nfe": nfe, "runtime": t_proc / B,
+                                "len_s": L / fs, "perm": perm[j].tolist()}
+    return {k: records[k] for k in sorted(records)}
 
 
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
@@ -40,7 +89,12 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     adds "llr", "wss" and "segsnr" (n floats each); with pesq_fn(fs, ref_1d, est_1d) -> float as well, "pesq" is filled
     and "csig", "cbak" and "covl" are added.  mrstft=True adds "mrstft" and "l1" (n floats each, unweighted): the
     diagonal, under the SIR permutation, of the pair tables of Engine.mrstft_loss at its defaults (seven resolutions,
-    A-weighting of `fs`, spectral convergence plus log magnitude)."""
+    A-weighting of `fs`, spectral convergence plus log magnitude).
+
+    A batch may also be (list of mix [1,L_b], list of target [n,L_b]) with differing L_b: it takes the ragged route
+    (one sampler call on the padded batch, codec and metric kernels per group of equal length); each record carries
+    its own "len_s", "runtime" stays the batch time divided by B.  score_loss, composite and mrstft have no ragged
+    form (NotImplementedError)."""
     if pesq_fn is not None and not composite:
         raise ValueError("pesq_fn is used by composite=True only")
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
@@ -50,6 +104,13 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     results, idx = {}, start_idx
     dev = model.engine.device
     for mix, target in batches:
+        if isinstance(mix, (list, tuple)):
+            if score_loss or composite or mrstft:
+                raise NotImplementedError("score_loss / composite / mrstft are not implemented for ragged batches")
+            results.update(_evaluate_ragged(model, list(mix), list(target), fs, idx, seed, N, corrector_steps, snr,
+                                            denoise, stoi, stoi_extended))
+            idx += len(mix)
+            continue
         mix, target = mix.to(dev), target.to(dev)
         L = target.shape[-1]
         mix_latent, _ = model.encode(mix, None, seed=seed + idx)

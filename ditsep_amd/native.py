@@ -27,7 +27,7 @@ MAX_VAE_BLOCKS = 8
 
 EXPORTS = [
     "dsn_create", "dsn_destroy", "dsn_last_error", "dsn_load_tensor", "dsn_finalize_weights", "dsn_finalize_weights_ex",
-    "dsn_score", "dsn_ouve_schedule", "dsn_pc_sample", "dsn_pc_sample_sched", "dsn_pc_sample_ex", "dsn_pc_sample_mix", "dsn_sb_sample", "dsn_decode",
+    "dsn_score", "dsn_score_ragged", "dsn_pc_sample_ragged", "dsn_ouve_schedule", "dsn_pc_sample", "dsn_pc_sample_sched", "dsn_pc_sample_ex", "dsn_pc_sample_mix", "dsn_sb_sample", "dsn_decode",
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
@@ -177,7 +177,48 @@ class DsnTestKernel(C.Structure):
         ("seed", C.c_uint64), ("offset", C.c_uint64), ("count", C.c_int64),
         ("y", C.c_void_p), ("score", C.c_void_p), ("z", C.c_void_p), ("smix", C.c_void_p), ("norms", C.c_void_p),
         ("xmean", C.c_void_p),
+        ("lens", C.c_void_p),
     ]
+
+
+def latent_frames_of(L: int, hop: int) -> int:
+    """Latent frames of an L-sample mixture under the reference's pad rule (utils.pad / dsn_latent_frames): pad to the
+    next multiple of hop, a full extra hop when L % hop == 0."""
+    return int(L) // int(hop) + 1
+
+
+def ragged_extended_length(L: int, hop: int) -> int:
+    """Samples an item of a ragged batch is zero-extended to before its group is encoded: latent_frames_of(L) * hop - 1,
+    the longest length with the same frame count.  dsn_encode's own pad rule then adds the one remaining zero, so the
+    encoder sees exactly the padded signal it sees for the item alone (L <= T hop - 1 always holds)."""
+    return latent_frames_of(L, hop) * int(hop) - 1
+
+
+def frame_groups(frames) -> dict:
+    """{frame count: [item indices]} in order of first appearance: the codec runs once per group (its convolutions see
+    zero padding at an item's end when it runs alone, non-zero activations in a padded batch)."""
+    groups: dict = {}
+    for i, f in enumerate(frames):
+        groups.setdefault(int(f), []).append(i)
+    return groups
+
+
+def check_ragged(score_kind: int, frames, B: int, T: int, corrector: str = "ald") -> list:
+    """The refusals of the ragged entry points (include/ditsep_hip.h), raised by name before the library is touched:
+    a score network other than the DiT, a frame count outside [1, T] (or not one per item), the langevin corrector.
+    Returns the frame counts as a list of ints."""
+    if score_kind != SCORE_DIT:
+        raise ValueError("ragged batches need the DiT score network: NCSN++ convolves across time, so padding would "
+                         "change an item's result")
+    fr = [int(f) for f in frames]
+    if len(fr) != B:
+        raise ValueError(f"frames must hold one frame count per item (B = {B}), got {len(fr)}")
+    for b, f in enumerate(fr):
+        if f < 1 or f > T:
+            raise ValueError(f"frame count frames[{b}] = {f} outside [1, T = {T}]")
+    if corrector == "langevin":
+        raise ValueError("the langevin corrector has no ragged form: its per-item norms would run over the padding")
+    return fr
 
 
 _lib = None
@@ -204,6 +245,9 @@ def load_library() -> C.CDLL:
     lib.dsn_finalize_weights.argtypes = [vp]
     lib.dsn_finalize_weights_ex.argtypes = [vp, ci]
     lib.dsn_score.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp]
+    lib.dsn_score_ragged.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, vp]
+    lib.dsn_pc_sample_ragged.argtypes = [vp, vp, C.POINTER(C.c_int32), vp, C.c_uint64, vp, ci, ci, ci,
+                                         C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
     lib.dsn_ouve_schedule.argtypes = [vp, ci, cf, cf, fp, fp, fp, fp, fp, fp]
     lib.dsn_pc_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, ci, cf, cf, ci, C.POINTER(ci), vp]
     lib.dsn_pc_sample_sched.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, fp, ci, cf, ci, C.POINTER(ci), vp]
@@ -404,10 +448,18 @@ class Engine:
         self._check(self.lib.dsn_finalize_weights_ex(self.ctx, int(strict)), "dsn_finalize_weights")
 
     # ------------------------------------------------------------------ path
-    def score(self, xt, t, mix):
+    def score(self, xt, t, mix, frames=None):
+        """frames (sequence of B ints, optional): a ragged batch padded to T frames -- item b's score over its first
+        frames[b] frames is what it gets alone; the padded region of the output is unspecified (dsn_score_ragged)."""
+        if frames is not None:
+            frames = check_ragged(self.cfg.score_kind, frames, xt.shape[0], xt.shape[-1])
         xt, t, mix = (_dev32(a, self.device) for a in (xt, t, mix))
         B, n, D, T = xt.shape
         out = torch.empty_like(xt)
+        if frames is not None:
+            self._check(self.lib.dsn_score_ragged(self.ctx, _ptr(xt), _ptr(t), _ptr(mix), (C.c_int32 * B)(*frames),
+                                                  _ptr(out), B, T, self._stream()), "dsn_score_ragged")
+            return out
         self._check(self.lib.dsn_score(self.ctx, _ptr(xt), _ptr(t), _ptr(mix), _ptr(out), B, T, self._stream()),
                     "dsn_score")
         return out
@@ -423,12 +475,16 @@ class Engine:
 
     def pc_sample(self, y, noise=None, *, N=30, corrector_steps=1, snr=0.5, t_eps=0.03, denoise=True, seed=0,
                   timesteps=None, predictor="reverse_diffusion", corrector="ald", prior_mean=None,
-                  intermediate=False):
+                  intermediate=False, frames=None):
         """timesteps: optional explicit schedule (>= N floats, host) -> the scheduled sampler.
         predictor / corrector: the reference's registered names (the ones with a native kernel).
-        prior_mean: `true_mean` [B,n,D,T].  intermediate: also return the per-step (x, x_mean) list."""
+        prior_mean: `true_mean` [B,n,D,T].  intermediate: also return the per-step (x, x_mean) list.
+        frames (sequence of B ints, optional): a ragged batch -- y and noise keep their padded shapes, item b consumes
+        noise[..., :frames[b]] and gets what it gets alone; x[b, :, :, frames[b]:] is zero (dsn_pc_sample_ragged)."""
         if predictor not in PREDICTORS or corrector not in CORRECTORS:
             raise NotImplementedError(f"no native kernel for predictor {predictor!r} / corrector {corrector!r}")
+        if frames is not None:
+            frames = check_ragged(self.cfg.score_kind, frames, y.shape[0], y.shape[-1], corrector)
         y = _dev32(y, self.device)
         B, _, D, T = y.shape
         draws = 1 + N * (corrector_steps + (0 if predictor == "none" else 1))
@@ -437,7 +493,8 @@ class Engine:
             assert tuple(noise.shape) == (draws, B, self.n_src, D, T), noise.shape
         x = torch.empty((B, self.n_src, D, T), device=self.device, dtype=torch.float32)
         nfe = C.c_int()
-        plain = (predictor == "reverse_diffusion" and corrector == "ald" and prior_mean is None and not intermediate)
+        plain = (predictor == "reverse_diffusion" and corrector == "ald" and prior_mean is None and not intermediate
+                 and frames is None)
         if plain and timesteps is None:
             self._check(self.lib.dsn_pc_sample(self.ctx, _ptr(y), _ptr(noise), seed, _ptr(x), B, T, N,
                                                corrector_steps, snr, t_eps, int(denoise), C.byref(nfe),
@@ -457,8 +514,13 @@ class Engine:
         o = DsnSamplerOpts(PREDICTORS[predictor], CORRECTORS[corrector], int(corrector_steps), float(snr),
                            float(t_eps), int(denoise), ts if ts is not None else None,
                            None if pm is None else pm.data_ptr(), None if im is None else im.data_ptr())
-        self._check(self.lib.dsn_pc_sample_ex(self.ctx, _ptr(y), _ptr(noise), seed, _ptr(x), B, T, N, C.byref(o),
-                                              C.byref(nfe), self._stream()), "dsn_pc_sample_ex")
+        if frames is not None:
+            self._check(self.lib.dsn_pc_sample_ragged(self.ctx, _ptr(y), (C.c_int32 * B)(*frames), _ptr(noise), seed,
+                                                      _ptr(x), B, T, N, C.byref(o), C.byref(nfe), self._stream()),
+                        "dsn_pc_sample_ragged")
+        else:
+            self._check(self.lib.dsn_pc_sample_ex(self.ctx, _ptr(y), _ptr(noise), seed, _ptr(x), B, T, N, C.byref(o),
+                                                  C.byref(nfe), self._stream()), "dsn_pc_sample_ex")
         if intermediate:
             return x, nfe.value, [(im[i, 0], im[i, 1]) for i in range(N)]
         return x, nfe.value
@@ -618,6 +680,50 @@ class Engine:
                                           corrector_steps, snr, t_eps, int(denoise), C.byref(nfe),
                                           self._stream()), "dsn_separate")
         return wav, nfe.value
+
+    # ------------------------------------------------------------------ ragged batches
+    def encode_ragged(self, mixes, vae_noise=None, seed=0):
+        """mixes: list of [1, L_b] mixtures of different lengths -> (y [B,1,D,Tmax] zero beyond each item's frames,
+        frames).  Items are grouped by T_b = latent_frames(L_b); each item of a group is zero-extended to
+        T_b * hop - 1 samples (ragged_extended_length) and the group is encoded by one `encode` call, which is what
+        each item gets alone.  vae_noise: list of [D, T_b] (not extended with the samples); absent: group g draws
+        with seed + g."""
+        hop = self.hop_length
+        lens = [int(m.shape[-1]) for m in mixes]
+        frames = [latent_frames_of(L, hop) for L in lens]
+        B, Tmax = len(mixes), max(frames)
+        y = torch.zeros((B, 1, self.latent_dim, Tmax), device=self.device, dtype=torch.float32)
+        for g, (Tb, idx) in enumerate(frame_groups(frames).items()):
+            Lx = ragged_extended_length(lens[idx[0]], hop)
+            grp = torch.zeros((len(idx), 1, Lx), device=self.device, dtype=torch.float32)
+            for j, i in enumerate(idx):
+                grp[j, 0, :lens[i]] = _dev32(mixes[i], self.device).reshape(-1)
+            vn = None if vae_noise is None else torch.stack([_dev32(vae_noise[i], self.device) for i in idx])
+            y[idx, :, :, :Tb] = self.encode(grp, vn, seed=seed + g)
+        return y, frames
+
+    def decode_ragged(self, x, frames, target_lens):
+        """x [B,n,D,Tmax], frames and target_lens per item -> list of [n, L_b]: one `decode` per group of equal frame
+        count on x[group][..., :T_b], each item cropped to its length."""
+        x = _dev32(x, self.device)
+        out = [None] * x.shape[0]
+        for Tb, idx in frame_groups(frames).items():
+            wav = self.decode(x[idx][..., :Tb].contiguous(), None)
+            for j, i in enumerate(idx):
+                out[i] = wav[j, :, :int(target_lens[i])]
+        return out
+
+    def separate_ragged(self, mixes, *, vae_noise=None, noise=None, seed=0, N=30, corrector_steps=1, snr=0.5,
+                        t_eps=0.03, denoise=True):
+        """Mixtures of different lengths in one batch: list of [1, L_b] -> (list of [n, L_b], nfe).  The codec runs
+        per group of equal frame count, the sampler once on the padded batch (pc_sample with frames).  noise
+        [draws,B,n,D,Tmax]: item b consumes noise[..., :frames[b]]."""
+        # (refused before anything is encoded)
+        check_ragged(self.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
+        y, frames = self.encode_ragged(mixes, vae_noise, seed=seed)
+        x, nfe = self.pc_sample(y, noise, N=N, corrector_steps=corrector_steps, snr=snr, t_eps=t_eps, denoise=denoise,
+                                seed=seed, frames=frames)
+        return self.decode_ragged(x, frames, [int(m.shape[-1]) for m in mixes]), nfe
 
     @property
     def hop_length(self) -> int:
@@ -847,11 +953,12 @@ class Engine:
     def test_kernel(self, kind, **kw):
         """Run one launch wrapper of the non-GEMM kernels (dsn_test_kernel, include/ditsep_hip.h) on caller-owned device
         tensors.  Every keyword is the DsnTestKernel field of the same name; tensors are passed by pointer (fp32, but
-        out_planes int16 [P][out_ps] and out_fp8 / out_fp8_scale uint8), `a` / `w` / `w2` also set their _numel field."""
+        out_planes int16 [P][out_ps], out_fp8 / out_fp8_scale uint8 and lens int32), `a` / `w` / `w2` also set their
+        _numel field."""
         t = DsnTestKernel()
         t.kind = TEST_KERNEL_KINDS[kind]
         keep = []
-        dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8}
+        dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8, "lens": torch.int32}
         for k, v in kw.items():
             if isinstance(v, torch.Tensor):
                 assert v.is_cuda and v.dtype == dtypes.get(k, torch.float32), k

@@ -143,10 +143,11 @@ class NoneCorrector:
 
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=None, denoise=True, eps=3e-2,
                    snr=0.1, corrector_steps=1, probability_flow=False, intermediate=False, n_spkrs=2,
-                   noise=None, seed=None, **kwargs):
+                   noise=None, seed=None, frames=None, **kwargs):
     """Same arguments as the reference; `score_fn` must be a native-backed model (an object exposing
     `.engine`, e.g. ditsep_amd.LatentDiffSep).  Extra keywords: `noise` (the injected standard-normal
-    draws in reference order, for bit-comparable parity runs) and `seed` (on-device Philox)."""
+    draws in reference order, for bit-comparable parity runs), `seed` (on-device Philox) and `frames` (a ragged
+    batch: the latent frame count of every item of the padded y, OUVE SDE with a DiT only -- Engine.pc_sample)."""
     PredictorRegistry.get_by_name(predictor_name)      # ValueError for unknown names, as the reference
     CorrectorRegistry.get_by_name(corrector_name)
     engine = getattr(score_fn, "engine", None)
@@ -159,6 +160,8 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=N
                                       "runs ald2 (or none) there")
         if true_mean is not None or intermediate:
             raise NotImplementedError("true_mean / intermediate are implemented for the OUVE SDE only")
+        if frames is not None:
+            raise NotImplementedError(f"{type(sde).__name__} has no ragged sampler: it reduces over the latent")
         if sde.ndim != engine.n_src or n_spkrs != engine.n_src:
             raise ValueError(f"sde.ndim={sde.ndim} / n_spkrs={n_spkrs} but the engine was built for {engine.n_src} sources")
         mix_counter = {"calls": 0}
@@ -195,7 +198,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=N
         counter["calls"] += 1
         return engine.pc_sample(y, noise, N=sde.N, corrector_steps=c_steps, snr=float(snr), t_eps=float(eps),
                                 denoise=bool(denoise), seed=s, timesteps=timesteps, predictor=predictor_name,
-                                corrector=corr, prior_mean=true_mean, intermediate=bool(intermediate))
+                                corrector=corr, prior_mean=true_mean, intermediate=bool(intermediate), frames=frames)
 
     return pc_sampler
 

@@ -138,6 +138,30 @@ typedef struct dsn_sampler_opts {
 int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T,
                      int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream);
 
+/* Ragged batches (DiT score network only): B mixtures of different lengths in tensors padded to the longest, T frames.
+ * frames [B] (HOST int32): item b's latent frame count, 1 <= frames[b] <= T; its valid frames are the prefix
+ * [..., :frames[b]].  Every DiT operation but self-attention acts per token, and attention masks each item's keys at
+ * its own 1 + frames[b] tokens (the timestep token first), so item b's result over its valid frames is what the item
+ * gets in a call of its own with T = frames[b].  The padded region of y / xt may hold anything finite.
+ *   dsn_score_ragged      as dsn_score; out[b, :, :, frames[b]:] is unspecified (finite for finite inputs).
+ *   dsn_pc_sample_ragged  as dsn_pc_sample_ex (OUVE; all three predictors, DSN_CORR_ALD, caller timesteps, prior_mean,
+ *                         intermediates -- whose padded region is unspecified).  y and noise keep their padded shapes
+ *                         [B,1,D,T] and [draws,B,n_src,D,T]: item b consumes noise[..., :frames[b]].
+ *                         x_out[b, :, :, frames[b]:] is written as zero.  nfe_out as in dsn_pc_sample_ex.
+ *                         With the on-device RNG (noise == NULL) an item's draws are indexed by its position in the
+ *                         padded tensor: the result is a valid sample, but NOT the sample the item alone would draw
+ *                         for that seed.
+ * DSN_EINVAL, by name and before any launch: a score network other than the DiT (NCSN++ convolves across time, so
+ * padding changes an item's result); a frame count outside [1, T]; DSN_CORR_LANGEVIN (its per-item norms would run
+ * over the padding).  The Mix / PriorMix, Schroedinger-bridge and ODE samplers and dsn_score_loss have no ragged form:
+ * each reduces over the latent or couples the batch.  The codec has none either (its convolutions see an item's end):
+ * encode and decode run per group of equal frame count.  Under dsn_enable_graphs the lengths are data of the captured
+ * graph, not part of its key: one graph per (B, T, options) serves every set of lengths. */
+int dsn_score_ragged(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
+                     int B, int T, void* stream);
+int dsn_pc_sample_ragged(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
+                         float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream);
+
 /* The secondary SDE family of the reference's sampler package on the latent state read as [B, n_src, D*T]:
  * MixSDE (sdes.py:182-352) / PriorMixSDE (:355-593; diffusion scaled by the running RMS of the mixture over `avg_len`
  * flattened latent samples) through the same predictor-corrector loop, predictors as above, corrector
@@ -444,7 +468,8 @@ typedef struct DsnTestKernel {
   int kind;                   /* DSN_TK_* */
   /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
    * QKV_ATTENTION: a = LayerNorm output [B*S][D], w = to_qkv [3*D][D], bias [3*D] (optional), rope_cos / rope_sin
-   *   [S][32] caller-owned buffers that launch_rope_tables fills here, ipp items per panel; q scale 1/8 */
+   *   [S][32] caller-owned buffers that launch_rope_tables fills here, ipp items per panel; q scale 1/8
+   * both: `lens` (last field; device int32 [B], 1 <= lens[b] <= S, checked here) runs the length-aware variant */
   int B, S, H, dh, D, ipp;
   /* RESIDUAL_NORM: x [rows][D] (updated in place), slabs nslab x slab_stride, bias / gamma / beta [D] */
   int rows, nslab, do_norm;
@@ -515,6 +540,7 @@ typedef struct DsnTestKernel {
   const float* smix;
   const float* norms;
   float* xmean;
+  const int32_t* lens;        /* ATTENTION / QKV_ATTENTION: valid tokens per item (null: dense) */
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 
