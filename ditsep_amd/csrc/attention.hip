@@ -397,11 +397,7 @@ hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B,
   // nkt x 16 KB): blocked keys + online softmax, at most 128 KB
   if (nkt > 16 || sm > ATT_LDS_LIMIT) {
     const size_t sml = (size_t)P * 128 * DH * sizeof(op16_t);
-    static std::atomic<unsigned long long> attr_l{0};
-    if (dsn_first_use_on_device(attr_l)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<P, F16, DH, VL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
-    }
+    dsn_allow_lds<attention_long_kernel<P, F16, DH, VL>>((int)ATT_LDS_LIMIT);
     const int W = 4;  // measured (1 / 2 / 4 / 8): NCSN++ 944 tokens 7.48 / 7.17 / 7.14 / 7.31 ms per call, DiT 301 tokens 32.5 / 26.5 / 23.4 / 25.0 us
     hipLaunchKernelGGL((attention_long_kernel<P, F16, DH, VL>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sml, st, qkv, ps,
                        out, out_ps, S, H, o8s, lens);
@@ -413,11 +409,7 @@ hipError_t launch_t(const op16_t* qkv, long ps, op16_t* out, long out_ps, int B,
     hipLaunchKernelGGL((attention_mfma_kernel<P, F16, 4, DH, VL>), dim3(B * H, (nkt + W - 1) / W), dim3(64 * W), sm, st, qkv,
                        ps, out, out_ps, S, H, o8s, lens);
   } else {
-    static std::atomic<unsigned long long> attr{0};
-    if (dsn_first_use_on_device(attr)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_mfma_kernel<P, F16, 16, DH, VL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_LIMIT);
-    }
+    dsn_allow_lds<attention_mfma_kernel<P, F16, 16, DH, VL>>((int)ATT_LDS_LIMIT);
     // wide heads stage a large V block (DH * nkt * 32 B): share it between the query tiles' waves
     // the query tiles of an (item, head) share workgroups of up to 8 waves: V is staged once per workgroup (it used to be
     // one wave per workgroup for 64-wide heads: at S = 236 every one of the 15 query tiles staged the 30 KB of V

@@ -210,3 +210,10 @@ inline bool dsn_first_use_on_device(std::atomic<unsigned long long>& mask) {
   mask.fetch_or(bit, std::memory_order_relaxed);
   return true;
 }
+// Lets `Kernel` request up to `bytes` of dynamic LDS (default: the CU's 160 KB); set once per device and kernel.
+template <auto Kernel>
+inline void dsn_allow_lds(int bytes = 160 * 1024) {
+  static std::atomic<unsigned long long> done{0};
+  if (dsn_first_use_on_device(done))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}

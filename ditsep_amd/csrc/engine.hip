@@ -1856,6 +1856,23 @@ int guarded(dsn_ctx* ctx, F&& f) {
     return DSN_EINVAL;
   }
 }
+
+// The permutation p of 0 .. n-1 with the largest score(p), in lexicographic order; the first one wins a tie.
+template <class Score>
+std::vector<int> best_permutation(int n, Score score) {
+  std::vector<int> p(n);
+  std::iota(p.begin(), p.end(), 0);
+  std::vector<int> bestp = p;
+  double best = -1e300;
+  do {
+    const double s = score(p);
+    if (s > best) {
+      best = s;
+      bestp = p;
+    }
+  } while (std::next_permutation(p.begin(), p.end()));
+  return bestp;
+}
 }  // namespace
 
 extern "C" {
@@ -2519,7 +2536,6 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
     std::vector<double> h((size_t)B * n * n * 3);
     HIPCHK(hipMemcpyAsync(h.data(), dd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    std::vector<int> p(n);
     for (int b = 0; b < B; ++b) {
       // sdr[i][j]: est_j scored against ref_i
       double sdr[4][4];
@@ -2532,18 +2548,11 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
           const double noise = v[2] - 2.0 * alpha * v[0] + tgt;
           sdr[i][j] = 10.0 * log10((tgt + eps) / (noise + eps));
         }
-      for (int i = 0; i < n; ++i) p[i] = i;
-      double best = -1e300;
-      std::vector<int> bestp = p;
-      do {
+      const std::vector<int> bestp = best_permutation(n, [&](const std::vector<int>& p) {
         double s = 0;
         for (int i = 0; i < n; ++i) s += sdr[i][p[i]];
-        s /= n;
-        if (s > best) {
-          best = s;
-          bestp = p;
-        }
-      } while (std::next_permutation(p.begin(), p.end()));
+        return s / n;
+      });
       for (int i = 0; i < n; ++i) {
         if (si_sdr_out) si_sdr_out[(size_t)b * n + i] = (float)sdr[i][bestp[i]];
         if (perm_out) perm_out[(size_t)b * n + i] = bestp[i];
@@ -2581,7 +2590,6 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
       double v = 10.0 * log10(std::max(num, tiny) / std::max(den, tiny));
       return std::min(clamp, std::max(-clamp, v));
     };
-    std::vector<int> p(n);
     for (int b = 0; b < B; ++b) {
       double G[4][4], X[4][4], ee[4], sdr[4][4], sir[4][4], sar[4];
       for (int i = 0; i < n; ++i)
@@ -2631,17 +2639,11 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
           sir[i][j] = db(et, pe - et);
         }
       }
-      for (int i = 0; i < n; ++i) p[i] = i;
-      double best = -1e300;
-      std::vector<int> bestp = p;
-      do {
+      const std::vector<int> bestp = best_permutation(n, [&](const std::vector<int>& p) {
         double sc = 0;
         for (int i = 0; i < n; ++i) sc += perm_by ? sir[i][p[i]] : sdr[i][p[i]];
-        if (sc > best) {
-          best = sc;
-          bestp = p;
-        }
-      } while (std::next_permutation(p.begin(), p.end()));
+        return sc;
+      });
       for (int i = 0; i < n; ++i) {
         const size_t o = (size_t)b * n + i;
         if (si_sdr_out) si_sdr_out[o] = (float)sdr[i][bestp[i]];
@@ -2704,6 +2706,22 @@ static const dsn_ctx::StoiFilter& stoi_filter(dsn_ctx* ctx, int fs) {
   return ctx->stoi_filters[fs] = f;
 }
 
+// perm [B][n] (estimate perm[b*n + i] is scored against reference i) as the item map b*n + perm[b*n + i], uploaded to
+// the workspace buffer `buf`; null when perm is null.  `who` prefixes the error of an entry outside [0, n).  The copy
+// is asynchronous on `st` from `ymap`, which the caller keeps alive until it has synchronised.
+static const int* upload_item_map(dsn_ctx* ctx, const char* who, const char* buf, const int* perm, int B, int n,
+                                  std::vector<int>& ymap, hipStream_t st) {
+  if (!perm) return nullptr;
+  ymap.resize(B * n);
+  for (int k = 0; k < B * n; ++k) {
+    if (perm[k] < 0 || perm[k] >= n) fail(DSN_EINVAL, "%s: perm[%d] = %d outside [0, %d)", who, k, perm[k], n);
+    ymap[k] = k / n * n + perm[k];
+  }
+  int* dmap = ctx->wsbuf<int>(buf, B * n);
+  HIPCHK(hipMemcpyAsync(dmap, ymap.data(), sizeof(int) * ymap.size(), hipMemcpyHostToDevice, st));
+  return dmap;
+}
+
 // STOI / ESTOI of every estimate against its reference (pystoi.stoi(ref, est, fs, extended), restated in
 // tests/stoi_restatement.py).  Device: resampling, silent-frame removal, STFT envelopes and segment scores
 // (stoi.hip); host: the filter design, the band table and the permutation map.
@@ -2716,22 +2734,9 @@ int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int
     if (fs <= 0) fail(DSN_EINVAL, "dsn_stoi: fs = %d (must be positive)", fs);
     if (extended != 0 && extended != 1) fail(DSN_EINVAL, "dsn_stoi: extended = %d (0 or 1)", extended);
     const int items = B * n;
-    std::vector<int> ymap;
-    if (perm) {
-      ymap.resize(items);
-      for (int b = 0; b < B; ++b)
-        for (int i = 0; i < n; ++i) {
-          const int p = perm[b * n + i];
-          if (p < 0 || p >= n) fail(DSN_EINVAL, "dsn_stoi: perm[%d] = %d outside [0, %d)", b * n + i, p, n);
-          ymap[b * n + i] = b * n + p;
-        }
-    }
     hipStream_t st = (hipStream_t)stream;
-    int* dmap = nullptr;
-    if (perm) {
-      dmap = ctx->wsbuf<int>("stoi_map", items);
-      HIPCHK(hipMemcpyAsync(dmap, ymap.data(), sizeof(int) * items, hipMemcpyHostToDevice, st));
-    }
+    std::vector<int> ymap;
+    const int* dmap = upload_item_map(ctx, "dsn_stoi", "stoi_map", perm, B, n, ymap, st);
     // the 10 kHz signals: the inputs themselves, or their resampled copies [2][items][n10]
     const float* xs = ref;
     const float* ys = est;
@@ -2860,23 +2865,10 @@ int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n
            sh.win + sh.hop, fs);
     const int k = (int)nearbyint(F * 0.95);  // Python's round(): half to even
     const int items = B * n;
-    std::vector<int> ymap;
-    if (perm) {
-      ymap.resize(items);
-      for (int b = 0; b < B; ++b)
-        for (int i = 0; i < n; ++i) {
-          const int p = perm[b * n + i];
-          if (p < 0 || p >= n) fail(DSN_EINVAL, "dsn_composite: perm[%d] = %d outside [0, %d)", b * n + i, p, n);
-          ymap[b * n + i] = b * n + p;
-        }
-    }
     hipStream_t st = (hipStream_t)stream;
+    std::vector<int> ymap;
+    const int* dmap = upload_item_map(ctx, "dsn_composite", "comp_map", perm, B, n, ymap, st);
     const dsn_ctx::CompositeTables& tab = composite_tables(ctx, fs, sh);
-    int* dmap = nullptr;
-    if (perm) {
-      dmap = ctx->wsbuf<int>("comp_map", items);
-      HIPCHK(hipMemcpyAsync(dmap, ymap.data(), sizeof(int) * items, hipMemcpyHostToDevice, st));
-    }
     double* cond = ctx->wsbuf<double>("comp_cond", (long)items * COMPOSITE_COND);
     double* fl = ctx->wsbuf<double>("comp_llr", (long)items * F);
     double* fw = ctx->wsbuf<double>("comp_wss", (long)items * F);
@@ -3091,33 +3083,6 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
     if (launches) launches[i] = r.launches;
   }
   return (int)ctx->prof_rows.size();
-}
-
-int dsn_test_igemm(dsn_ctx* ctx, const float* a, const float* w, float* out, int B, int Lin, int Cin, int N, int taps,
-                   int in_stride, int tap_dil, int in_pad, int rows_per_b, int panel_rows, int panel_bn, void* stream) {
-  return guarded(ctx, [&] {
-    hipStream_t st = (hipStream_t)stream;
-    const int P = ctx->P, PL = ctx->PL;
-    const long an = (long)B * Lin * Cin, wn = (long)N * taps * Cin;
-    op16_t* ap = ctx->wsbuf<op16_t>("t_a", an * P);
-    op16_t* wp = ctx->wsbuf<op16_t>("t_w", wn * P);
-    launch_to_planes(a, ap, an, PL, an, st);
-    launch_to_planes(w, wp, wn, PL, wn, st);
-    const Packed pk = plain_packed(wp, wn, N, Cin, taps);
-    GemmDesc d = ctx->base_desc(ap, an, pk, B, rows_per_b, Lin);
-    d.in_stride = in_stride;
-    d.tap_dil = tap_dil;
-    d.in_pad = in_pad;
-    d.out_f32 = out;
-    if (panel_rows > 0) {
-      d.panel_rows = panel_rows;
-      hipError_t e = igemm_panel_launch(d, PL, panel_bn, st);
-      if (e != hipSuccess) fail(DSN_EHIP, "panel launch: %s", hipGetErrorString(e));
-    } else {
-      ctx->run(d, st);
-    }
-    HIPCHK(hipGetLastError());
-  });
 }
 
 // Test hook: one chosen kernel of the implicit-GEMM family on a caller-built descriptor (include/ditsep_hip.h).

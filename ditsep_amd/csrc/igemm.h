@@ -126,6 +126,10 @@ struct GemmDesc {
   int m_fast;      // tile order inside an XCD's share: 1 = row panels fastest (few rows, many columns)
 };
 
+// 4096 zero bytes on the current device, the source of rows outside the sequence / image for the GEMM, fused
+// ResidualUnit and fused QKV + attention kernels (igemm.hip); null when it cannot be allocated and cleared
+const op16_t* dsn_zero_page();
+
 // launchers (igemm.hip)
 hipError_t igemm_launch(const GemmDesc& d, int pl, hipStream_t stream);   // v1: register-staged
 hipError_t igemm2_launch(const GemmDesc& d, int pl, hipStream_t stream);  // v2: glds ring + split-K, auto tile

@@ -1734,25 +1734,11 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const GemmDesc d) {
   epilogue_gen<1, F16, 2, MT>(d, acc, 0, d.M, n0, lane, z);
 }
 
-const op16_t* zero_page() {
-  static op16_t* zp[64] = {};
-  op16_t*& z = zp[dsn_current_device()];
-  if (!z) {
-    if (hipMalloc((void**)&z, 4096) != hipSuccess) return nullptr;
-    (void)hipMemset(z, 0, 4096);
-  }
-  return z;
-}
-
 template <int P, int F16, int TBM, int TBN, int NST, int TBK, int LEAN = 0, int WTN = 64>
 hipError_t launch_cfg(GemmDesc d, const op16_t* zp, hipStream_t stream) {
   d.tiles_m = cdiv(d.M, TBM);
   d.tiles_n = cdiv(d.N, TBN);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+  dsn_allow_lds<igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>>();
   const int grid = d.tiles_m * d.tiles_n * d.ksplit;
   const size_t smem = (size_t)NST * P * (TBM + TBN) * TBK * sizeof(op16_t);
   hipLaunchKernelGGL((igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>), dim3(grid), dim3((TBM / 64) * (TBN / WTN) * 64),
@@ -1762,6 +1748,21 @@ hipError_t launch_cfg(GemmDesc d, const op16_t* zp, hipStream_t stream) {
 
 }  // namespace
 
+// The page that out-of-range rows are read from, one per device (igemm.h).  Allocated on first use, which is an eager
+// warm-up call, never inside a capture.
+const op16_t* dsn_zero_page() {
+  static op16_t* zp[64] = {};
+  op16_t*& z = zp[dsn_current_device()];
+  if (!z) {
+    if (hipMalloc((void**)&z, 4096) != hipSuccess) return nullptr;
+    if (hipMemset(z, 0, 4096) != hipSuccess) {
+      (void)hipFree(z);
+      z = nullptr;
+    }
+  }
+  return z;
+}
+
 hipError_t igemm2_launch_cfg(const GemmDesc& din, int pl, int bm, int bn, int nst, int bk, hipStream_t stream) {
   const int planes = PL_COUNT(pl), f16 = PL_F16(pl);
   GemmDesc d = din;
@@ -1770,7 +1771,7 @@ hipError_t igemm2_launch_cfg(const GemmDesc& din, int pl, int bm, int bn, int ns
   if (d.Cin % bk != 0 || d.M <= 0 || d.N <= 0) return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 32 != 0)) return hipErrorInvalidValue;
   if (d.ksplit > 1 && (!d.out_f32 || d.swiglu)) return hipErrorInvalidValue;
-  const op16_t* zp = zero_page();
+  const op16_t* zp = dsn_zero_page();
   if (!zp) return hipErrorOutOfMemory;
   // conv-stack descriptors (Oobleck: bias / activation / residual / fp32 + plane outputs only) take the lean epilogue
   const bool lean = !d.rope_cos && d.qkv_D <= 0 && !d.swiglu && !d.gn_stats && !d.bbias && d.f32_op != DSN_F32_TANH &&
@@ -1805,19 +1806,18 @@ hipError_t igemm2_launch_cfg(const GemmDesc& din, int pl, int bm, int bn, int ns
 // halo-resident 3x3 conv: eligibility + launch (hipErrorNotSupported = not eligible, caller falls back)
 // MINW = 4: registers capped at 128 so that two 8-wave workgroups share a CU (123 VGPRs, no spills since the GroupNorm
 // partials are taken in one pass); MINW = 1 for the 4-wave 128-row variant.
+// dynamic LDS of igemm_halo3x3_kernel: [2][HRMAX][32] halo | [4][128][32] weights | dummy
+static constexpr size_t halo_lds_bytes(int tbm) {
+  const int hrmax = ((tbm + 2 * 33 + 15) / 16) * 16;
+  return (size_t)(2 * hrmax * 32 + 4 * 128 * 32 + 16 * 32) * sizeof(op16_t);
+}
 template <int F16, int TBM, int MINW, int SC = 0>
 static hipError_t launch_halo_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
   d.tiles_m = d.M / TBM;
   d.tiles_n = cdiv(d.N, 128);
-  constexpr int HRMAX = ((TBM + 2 * 33 + 15) / 16) * 16;
-  const size_t smem = (size_t)(2 * HRMAX * 32 + 4 * 128 * 32 + 16 * 32) * sizeof(op16_t);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_halo3x3_kernel<F16, TBM, MINW, SC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  hipLaunchKernelGGL((igemm_halo3x3_kernel<F16, TBM, MINW, SC>), dim3(d.tiles_m * d.tiles_n), dim3((TBM / 64) * 2 * 64), smem,
-                     stream, d, zp);
+  dsn_allow_lds<igemm_halo3x3_kernel<F16, TBM, MINW, SC>>();
+  hipLaunchKernelGGL((igemm_halo3x3_kernel<F16, TBM, MINW, SC>), dim3(d.tiles_m * d.tiles_n), dim3((TBM / 64) * 2 * 64),
+                     halo_lds_bytes(TBM), stream, d, zp);
   return hipGetLastError();
 }
 // 128-row images (NCSN++ level 2, 128 workgroups of 4 waves) measured slower than igemm2's 128 x 128 x BK 64 tiles
@@ -1832,16 +1832,11 @@ int igemm_halo3x3_tile(const GemmDesc& d, int pl) {
 }
 template <int F16, int TBM, int MINW>
 static int halo_resident_blocks() {
-  constexpr int HRMAX = ((TBM + 2 * 33 + 15) / 16) * 16;
-  const size_t smem = (size_t)(2 * HRMAX * 32 + 4 * 128 * 32 + 16 * 32) * sizeof(op16_t);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_halo3x3_kernel<F16, TBM, MINW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  dsn_allow_lds<igemm_halo3x3_kernel<F16, TBM, MINW>>();
   int per_cu = 0;
   hipDeviceProp_t prop;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, igemm_halo3x3_kernel<F16, TBM, MINW>, (TBM / 64) * 2 * 64,
-                                                   smem) != hipSuccess ||
+                                                   halo_lds_bytes(TBM)) != hipSuccess ||
       hipGetDeviceProperties(&prop, dsn_current_device()) != hipSuccess)
     return 0;
   return per_cu * prop.multiProcessorCount;
@@ -1876,7 +1871,7 @@ hipError_t igemm_halo3x3_launch(const GemmDesc& d, int pl, hipStream_t stream) {
   if (d.sc_A && (!d.sc_W || d.sc_Cin < 32 || d.sc_Cin % 32 != 0 || d.sc_row_elems < d.sc_Cin)) return hipErrorInvalidValue;
   const int tile = igemm_halo3x3_tile(d, pl);
   if (!tile) return hipErrorNotSupported;
-  const op16_t* zp = zero_page();
+  const op16_t* zp = dsn_zero_page();
   if (!zp) return hipErrorOutOfMemory;
   if (d.sc_A) {
     if (tile == 256) return f16 ? launch_halo_t<1, 256, 4, 1>(d, zp, stream) : launch_halo_t<0, 256, 4, 1>(d, zp, stream);
@@ -2007,11 +2002,7 @@ static hipError_t launch_panel_t(GemmDesc d, const op16_t* zp, hipStream_t strea
   constexpr int TBN = WN_ * 64;
   d.tiles_m = cdiv(d.M, d.panel_rows);
   d.tiles_n = cdiv(d.N, TBN);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_panel_kernel<P, F16, WN_, NST, TBK, MT, EPI, WM_>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+  dsn_allow_lds<igemm_panel_kernel<P, F16, WN_, NST, TBK, MT, EPI, WM_>>();
   const int grid = d.tiles_m * d.tiles_n * d.ksplit;
   const size_t smem = (size_t)NST * P * (MT * 16 + TBN) * TBK * sizeof(op16_t) + (d.ln_stats ? MT * 16 * 2 * sizeof(float) : 0);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
@@ -2026,11 +2017,7 @@ static hipError_t launch_panel_fp8_t(GemmDesc d, const op16_t* zp, hipStream_t s
   constexpr int TBN = WN_ * 64;
   d.tiles_m = cdiv(d.M, d.panel_rows);
   d.tiles_n = cdiv(d.N, TBN);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_panel_fp8_kernel<WM_, WN_, NST, MT, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+  dsn_allow_lds<igemm_panel_fp8_kernel<WM_, WN_, NST, MT, EPI>>();
   const int grid = d.tiles_m * d.tiles_n * d.ksplit;
   const size_t smem = (size_t)NST * ((MT * 16 + TBN) * 64 * sizeof(op16_t) + ((MT * 16 + TBN + 63) / 64 + 1) * 64 * sizeof(unsigned)) +
                       ((EPI & EPI_LNFOLD) ? MT * 16 * 2 * sizeof(float) : 0);
@@ -2055,7 +2042,7 @@ hipError_t igemm_panel_fp8_launch(const GemmDesc& din, int bn, hipStream_t strea
     return hipErrorInvalidValue;
   if (d.ln_stats && (!d.swiglu || !d.ln_colsum || d.ln_np <= 0 || (d.ln_np & 1) || !d.out_fp8 || !d.out_fp8_scale))
     return hipErrorInvalidValue;
-  const op16_t* zp = zero_page();
+  const op16_t* zp = dsn_zero_page();
   if (!zp) return hipErrorOutOfMemory;
 #define FCFGE(MT_, WM_, W_, NS_, E_) \
   if (d.panel_rows <= MT_ * 16 && bn == W_ * 64) return launch_panel_fp8_t<WM_, W_, NS_, MT_, E_>(d, zp, stream);
@@ -2114,7 +2101,7 @@ hipError_t igemm_panel_launch(const GemmDesc& din, int pl, int bn, hipStream_t s
   if (d.img_w > 0) return hipErrorInvalidValue;
   if (d.stat_out && (d.N % 64 != 0 || d.stat_np != d.N / 64 || d.swiglu || d.ksplit > 1)) return hipErrorInvalidValue;
   if (d.ln_stats && (!d.swiglu || !d.ln_colsum || d.ln_np <= 0 || d.taps != 1 || planes != 1)) return hipErrorInvalidValue;
-  const op16_t* zp = zero_page();
+  const op16_t* zp = dsn_zero_page();
   if (!zp) return hipErrorOutOfMemory;
   const int epi = (d.stat_out ? EPI_STATS : 0) | (d.ln_stats ? EPI_LNFOLD : 0);
 #define PCFGE(MT_, P_, W_, NS_, BK_, E_)                                                             \

@@ -313,11 +313,7 @@ template <int NFFT>
 void launch_spec(const float* xr, const float* xd, const double* xr64, const double* xd64, const float* win, int B,
                  int n, int L, int hop, int F, int wgs, int gpw, double* part, hipStream_t st) {
   const size_t smem = ((size_t)NFFT / 2 + (size_t)n * kPoints) * sizeof(double2);
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mrstft_spec_kernel<NFFT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((NFFT / 2 + kMaxSrc * kPoints) * sizeof(double2)));
+  dsn_allow_lds<mrstft_spec_kernel<NFFT>>((int)((NFFT / 2 + kMaxSrc * kPoints) * sizeof(double2)));
   hipLaunchKernelGGL((mrstft_spec_kernel<NFFT>), dim3(wgs, B), dim3(kSpecThreads), smem, st, xr, xd, xr64, xd64, win, n,
                      L, hop, F, gpw, part);
 }

@@ -341,22 +341,9 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
   }
 }
 
-const op16_t* qa_zero_page() {
-  static op16_t* zp[64] = {};
-  op16_t*& z = zp[dsn_current_device()];
-  if (!z) {
-    if (hipMalloc((void**)&z, 4096) != hipSuccess) return nullptr;
-    (void)hipMemset(z, 0, 4096);
-  }
-  return z;
-}
-
 template <int F16, int NST, int NKT, int TM, bool VL>
 hipError_t qa_launch_t(const QkvAttnDesc& d, const op16_t* zp, const int* lens, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr{0};
-  if (dsn_first_use_on_device(attr))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qkv_attention_kernel<F16, NST, NKT, TM, VL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  dsn_allow_lds<qkv_attention_kernel<F16, NST, NKT, TM, VL>>();
   const size_t smem = (size_t)(NST * (TM + QA_TN) * QA_BK + 8 * QA_BK) * sizeof(op16_t);
   hipLaunchKernelGGL((qkv_attention_kernel<F16, NST, NKT, TM, VL>), dim3(d.panels * d.H), dim3(512), smem, stream, d, zp,
                      lens);
@@ -384,7 +371,7 @@ hipError_t qkv_attention_launch(const QkvAttnDesc& din, int pl, hipStream_t stre
       !d.rope_sin || d.A == d.out)
     return hipErrorInvalidValue;
   d.panels = cdiv(d.M / d.S, d.ipp);
-  const op16_t* zp = qa_zero_page();
+  const op16_t* zp = dsn_zero_page();
   if (!zp) return hipErrorOutOfMemory;
   const int nqt = (d.S + 15) / 16;
   const int f16 = PL_F16(pl);

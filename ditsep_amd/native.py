@@ -30,7 +30,7 @@ EXPORTS = [
     "dsn_score", "dsn_score_ragged", "dsn_pc_sample_ragged", "dsn_ouve_schedule", "dsn_pc_sample", "dsn_pc_sample_sched", "dsn_pc_sample_ex", "dsn_pc_sample_mix", "dsn_sb_sample", "dsn_decode",
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
-    "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows", "dsn_test_igemm",
+    "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows",
     "dsn_test_gemm", "dsn_test_kernel", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
 ]
@@ -275,7 +275,6 @@ def load_library() -> C.CDLL:
     lib.dsn_profile_hbm.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.dsn_profile_rows.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.dsn_test_igemm.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.dsn_test_gemm.argtypes = [vp, C.POINTER(DsnTestGemm), vp]
     lib.dsn_test_kernel.argtypes = [vp, C.POINTER(DsnTestKernel), vp]
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
@@ -907,14 +906,16 @@ class Engine:
 
     def test_igemm(self, a, w, *, taps=1, in_stride=1, tap_dil=1, in_pad=0, rows_per_b=None, panel_rows=0,
                    panel_bn=256):
-        """a [B,Lin,Cin] channels-last, w [N, taps*Cin] -> [B, rows_per_b, N] (kernel test hook)."""
+        """a [B,Lin,Cin] channels-last, w [N, taps*Cin] -> [B, rows_per_b, N]: test_gemm with no epilogue, on the
+        row-panel kernel (panel_bn = 128 | 256 columns) when panel_rows > 0, else on the engine's own choice."""
         a, w = _dev32(a, self.device), _dev32(w, self.device)
         B, Lin, Cin = a.shape
         N = w.shape[0]
         rpb = rows_per_b or Lin
         out = torch.empty((B, rpb, N), device=self.device, dtype=torch.float32)
-        self._check(self.lib.dsn_test_igemm(self.ctx, _ptr(a), _ptr(w), _ptr(out), B, Lin, Cin, N, taps, in_stride,
-                                            tap_dil, in_pad, rpb, panel_rows, panel_bn, self._stream()), "dsn_test_igemm")
+        panel = dict(kernel="panel", panel_rows=panel_rows, panel_bn=panel_bn) if panel_rows > 0 else {}
+        self.test_gemm(a, w, B=B, Lin=Lin, Cin=Cin, N=N, taps=taps, rows_per_b=rpb, in_stride=in_stride,
+                       tap_dil=tap_dil, in_pad=in_pad, out_f32=out, **panel)
         return out
 
     # operand format of this context: (planes, fp16?) per precision code

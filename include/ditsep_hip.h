@@ -387,15 +387,9 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
                      int64_t* launches);
 
 /* ---- NOT PART OF THE ABI ------------------------------------------------------------------------------------
- * dsn_test_igemm, dsn_test_gemm, dsn_test_kernel, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests, repro scripts and
- * kernel sweeps.  They name internal workspace buffers and kernel variants, change without notice, and a binding of
+ * dsn_test_gemm, dsn_test_kernel, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests,
+ * repro scripts and kernel sweeps.  They name internal workspace buffers and kernel variants, change without notice, and a binding of
  * the reference-facing interface must not use them. */
-/* Test hook: run the implicit-GEMM kernel on caller-provided fp32 operands.
- * a [B][Lin][Cin] channels-last, w [N][taps*Cin]; out [B][rows_per_b][N] fp32 (no epilogue). */
-int dsn_test_igemm(dsn_ctx* ctx, const float* a, const float* w, float* out, int B, int Lin, int Cin, int N,
-                   int taps, int in_stride, int tap_dil, int in_pad, int rows_per_b, int panel_rows, int panel_bn,
-                   void* stream);   /* panel_rows > 0: row-panel kernel with panel_bn (128|256) columns */
-
 /* Test hook: run ONE chosen kernel of the implicit-GEMM family (ditsep_amd/csrc/igemm.h) on a descriptor built from
  * caller-owned fp32 device tensors, with any subset of the epilogue features.  Operands are rounded to the engine's
  * operand planes first.  A launcher that refuses the descriptor fails the call by name: there is no fall-back to another
