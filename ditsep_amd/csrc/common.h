@@ -120,6 +120,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// XCD-aware, bijective remap of the workgroup index of a 1-D grid: blocks b and b+8 share an XCD (L2), so every XCD
+// gets a contiguous run of the returned tile indices -- the workgroups that re-read the same operand rows then sit
+// behind the same L2.  The caller decodes the index with the operand it wants to keep resident varying slowest.
+__device__ __forceinline__ int xcd_remap() {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+}
+
 // ---- NCSN++ GroupNorm: one owner of the group geometry and of the statistics combine ----
 // The (mean, M2) partials of a tensor are laid out stats[item][S][C/4][2], S = ceil(HW / 64): one entry per 64-row slice
 // and 4-channel quad (GemmDesc::gn_stats, gn_stats_kernel).  Every consumer -- gn_apply_kernel and the GEMMs that

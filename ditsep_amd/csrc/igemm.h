@@ -122,7 +122,7 @@ struct GemmDesc {
   float gnf_eps;
   int gnf_silu;
   int cfg_bm, cfg_bn, cfg_nst, cfg_bk;  // explicit tile configuration for igemm2_launch (0 = heuristic)
-  int dbg;         // development: 1 = skip in-loop glds (compute only), 2 = skip MFMAs (staging only)
+  int dbg;         // read nowhere; it only keeps m_fast at its kernel-argument offset (goes with the next layout change)
   int m_fast;      // tile order inside an XCD's share: 1 = row panels fastest (few rows, many columns)
 };
 

@@ -1,26 +1,22 @@
-// Implicit-GEMM MFMA kernel for gfx950 (see igemm.h for the contraction).
+// Implicit-GEMM MFMA kernels for gfx950 (see igemm.h for the contraction).  Every kernel swaps the operands on the
+// matrix core: MFMA-A = weight rows (n), MFMA-B = activation rows (m), so each lane ends up holding FOUR CONSECUTIVE
+// CHANNELS of one output row -> 16-byte fp32 / 8-byte 16-bit channels-last stores and in-lane bias / activation /
+// SwiGLU epilogues (epilogue_gen, shared by all of them).
 //
-// Tile 128(m) x 128(n) x 32(k) per 256-thread workgroup (4 waves as 2x2, each
-// wave 64x64 = 4x4 v_mfma_f32_16x16x32_bf16 accumulators).  Operands are
-// swapped on the matrix core: MFMA-A = weight rows (n), MFMA-B = activation
-// rows (m), so each lane ends up holding FOUR CONSECUTIVE CHANNELS of one
-// output row -> 16-byte fp32 / 8-byte bf16 channels-last stores and in-lane
-// bias / activation / SwiGLU epilogues.
-//
-// K loop: taps outer, channel chunks inner; every (tap, chunk) stages a
-// [128][32] activation tile whose rows are the tap-shifted input rows
-// (zero-filled outside the sequence) and the matching weight tile.  Global ->
-// register -> LDS staging, LDS double buffered, one barrier per k-tile: the
-// loads of tile t+1 are issued before the MFMAs of tile t and written to the
-// other buffer after them.
-// LDS rows are 64 B; the 16-byte chunk index is XOR-swizzled with
-// (-(row>>2))&3 so that every 16-lane ds_read_b128 group touches 16 distinct
-// 16-byte slots of the 256-byte bank row.
+// Kernel families, in file order, and the launcher that picks each:
+//   igemm_kernel                v1, register-staged 128 x 128 x 32 tile.  igemm_launch; igemm2_launch takes it for
+//                               split-plane convs with K <= 256.
+//   igemm2_kernel               direct-to-LDS ring, 128 / 256-row and 64 / 128 / 256-column tiles, split-K.
+//                               igemm2_launch_cfg (explicit tile); igemm2_launch chooses the tile.
+//   igemm_halo3x3_kernel        3x3 convs on images up to 32 wide, activation halo resident in LDS.
+//                               igemm_halo3x3_launch; igemm2_launch tries it first for every 2-D descriptor.
+//   igemm_panel_kernel          row panels of d.panel_rows rows (the DiT's M = B (T + 1)).  igemm_panel_launch.
+//   igemm_panel_fp8_kernel      its fp8 (MX) twin.  igemm_panel_fp8_launch.
+//   igemm_skinny_kernel         M <= 128 rows, weights streamed straight into fragments.  igemm_skinny_launch.
+//   igemm_slab_epilogue_kernel  sums split-K slabs and runs the ordinary epilogue.  igemm_slab_epilogue_launch.
+// The four LDS-ring kernels (igemm2, halo3x3, panel, panel_fp8) share the prologue helpers of the "v2 core" section
+// (xcd_remap, tile_of, k_range, ring_wait, glds) and one host launch path (launch_ring, normalise).
 #include "igemm.h"
-
-#ifndef DSN_SETPRIO
-#define DSN_SETPRIO 0
-#endif
 
 namespace {
 
@@ -537,6 +533,11 @@ __device__ __forceinline__ void epilogue_tile(const GemmDesc& d, f32x4 (&acc)[4]
   epilogue_gen<P, F16, 4, 4, 0, LEAN>(d, acc, mw0, d.M, nw0, lane, z);
 }
 
+// v1: tile 128(m) x 128(n) x 32(k) per 256-thread workgroup (4 waves as 2x2, each 64x64 = 4x4 accumulators).  K loop:
+// taps outer, channel chunks inner; every (tap, chunk) stages a [128][32] activation tile of tap-shifted input rows
+// (zero-filled outside the sequence) and the matching weight tile, global -> register -> LDS, double buffered, one
+// barrier per k-tile: tile t+1 is loaded before the MFMAs of tile t and written to the other buffer after them.
+// LDS rows are 64 B; the 16-byte chunk index is XOR-swizzled (swz) so that a 16-lane ds_read_b128 group hits 16 slots.
 template <int P, int F16>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(const GemmDesc d) {
   // [buf][operand A=0/W=1][plane][row*32 + chunk*8]
@@ -547,12 +548,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const GemmDesc d) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // XCD-aware, bijective tile remap: blocks b and b+8 share an XCD (L2); give
-  // each XCD a contiguous run of tiles with tile_n fastest so the blocks that
-  // re-read one activation row panel sit behind the same L2.
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+  // tile_n fastest: the blocks that re-read one activation row panel sit behind the same L2
+  const int t = xcd_remap();
   const int tile_m = t / d.tiles_n, tile_n = t - tile_m * d.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -762,6 +759,65 @@ __device__ __forceinline__ int swzk(int row) {
   return TBK == 32 ? ((-(row >> 2)) & 3) : ((row >> 1) & 7);
 }
 
+// ---- prologue pieces shared by the ring kernels ----
+
+// direct-to-LDS load of BYTES (16, or 4 for the fp8 scale dwords) per lane: LDS destination = dst + lane * BYTES
+template <int BYTES = 16>
+__device__ __forceinline__ void glds(const void* src, void* dst) {
+  static_assert(BYTES == 16 || BYTES == 4, "glds sizes in use");
+  const auto* g = (const __attribute__((address_space(1))) void*)src;
+  auto* l = (__attribute__((address_space(3))) void*)dst;
+  if constexpr (BYTES == 16) __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);  // (the builtin wants a literal size)
+  else __builtin_amdgcn_global_load_lds(g, l, 4, 0, 0);
+}
+
+// (split-K slice, row tile, column tile) of this workgroup; the grid is tiles_m * tiles_n * ksplit workgroups
+struct TileId {
+  int z, tile_m, tile_n;
+};
+__device__ __forceinline__ TileId tile_of(const GemmDesc& d) {
+  const int t = xcd_remap();
+  const int ntiles = d.tiles_m * d.tiles_n;
+  const int z = t / ntiles;
+  const int tile = t - z * ntiles;
+  // m_fast: consecutive tiles (one XCD's share) walk DOWN the rows of a few column tiles, so the XCD's
+  // L2 keeps its weight columns and streams the (small) activation panels -- for GEMMs with few rows and
+  // many columns (DiT); default walks ACROSS the columns of a few row panels (conv stacks: huge M, small N).
+  const int tile_m = d.m_fast ? tile % d.tiles_m : tile / d.tiles_n;
+  const int tile_n = d.m_fast ? tile / d.tiles_m : tile - tile_m * d.tiles_n;
+  return TileId{z, tile_m, tile_n};
+}
+
+// k-tiles [begin, begin + count) of split-K slice z out of ksplit
+struct KRange {
+  int begin, count;
+};
+__device__ __forceinline__ KRange k_range(int nkt_all, int z, int ksplit) {
+  const int kt_begin = (int)((long)nkt_all * z / ksplit), kt_end = (int)((long)nkt_all * (z + 1) / ksplit);
+  return KRange{kt_begin, kt_end - kt_begin};
+}
+
+// Counted wait in front of a k-tile's barrier: the tile has landed once at most the loads of the `younger` (<= NST - 2)
+// tiles issued after it are outstanding, G_FULL wave-instructions each (G_SHORT for a wave with one row group less).
+// lgkmcnt(0): this wave's fragment reads of the previous tile have COMPLETED before the barrier lets another wave's
+// glds overwrite that stage -- hipcc will otherwise leave reads in flight across the barrier.
+template <int NST, int G_FULL, int G_SHORT = G_FULL>
+__device__ __forceinline__ void ring_wait(int younger, bool full = true) {
+  if (NST >= 4 && younger >= 2) {  // two younger tiles stay in flight
+    if (full)
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * G_FULL) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * G_SHORT) : "memory");
+  } else if (NST >= 3 && younger >= 1) {
+    if (full)
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G_FULL) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G_SHORT) : "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  }
+}
+
 // GroupNorm finished by the producing conv (GemmDesc::gnf_out), last step: silu(GroupNorm(out)) of a wave's NT x 4
 // sub-tiles (rows from mw0, columns from nw0) to the next conv's operand plane, straight from the accumulators.
 // val(tn, tm, n) = the value the epilogue would have stored in the fp32 tensor, in the caller's own order of operations;
@@ -794,6 +850,10 @@ __device__ __forceinline__ void gn_finish_store(const GemmDesc& d, int mw0, int 
   }
 }
 
+// dynamic LDS of igemm2_kernel: [NST][plane][A rows | W rows][TBK]
+constexpr size_t igemm2_lds_bytes(int planes, int tbm, int tbn, int nst, int tbk) {
+  return (size_t)nst * planes * (tbm + tbn) * tbk * sizeof(op16_t);
+}
 // WTN: columns of a wave tile (64, or 32 for the 128 x 64 workgroup tile that gives a GEMM of few rows twice the workgroups)
 template <int P, int F16, int TBM, int TBN, int NST, int TBK, int LEAN = 0, int WTN = 64>
 __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kernel(const GemmDesc d,
@@ -818,25 +878,13 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN_, wn = wave - wm * WN_;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
-  const int ntiles = d.tiles_m * d.tiles_n;
-  const int z = t / ntiles;
-  const int tile = t - z * ntiles;
-  // m_fast: consecutive tiles (one XCD's share) walk DOWN the rows of a few column tiles, so the XCD's
-  // L2 keeps its weight columns and streams the (small) activation panels -- for GEMMs with few rows and
-  // many columns (DiT); default walks ACROSS the columns of a few row panels (conv stacks: huge M, small N).
-  const int tile_m = d.m_fast ? tile % d.tiles_m : tile / d.tiles_n;
-  const int tile_n = d.m_fast ? tile / d.tiles_m : tile - tile_m * d.tiles_n;
-  const int m0 = tile_m * TBM, n0 = tile_n * TBN;
+  const TileId ti = tile_of(d);
+  const int z = ti.z, m0 = ti.tile_m * TBM, n0 = ti.tile_n * TBN;
 
   const int Ktot = d.taps * d.Cin;
   const int kc_per_tap = d.Cin / TBK;
-  const int nkt_all = d.taps * kc_per_tap;
-  const int kt_begin = (int)((long)nkt_all * z / d.ksplit);
-  const int kt_end = (int)((long)nkt_all * (z + 1) / d.ksplit);
-  const int nkt = kt_end - kt_begin;
+  const KRange kr = k_range(d.taps * kc_per_tap, z, d.ksplit);
+  const int kt_begin = kr.begin, nkt = kr.count;
 
   // ---- loader role: this wave stages row groups [wave*GPW, wave*GPW + GPW) ----
   const int rsub = lane / CPR, cpos = lane % CPR;
@@ -863,9 +911,7 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
 #pragma unroll
       for (int p = 0; p < P; ++p) {
         const op16_t* g = ok ? g0 + p * rl[gi].ps : zsrc;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(sbase + p * PLANE_ELEMS + gi * RPG * TBK),
-                                         16, 0, 0);
+        glds(g, sbase + p * PLANE_ELEMS + gi * RPG * TBK);
       }
     }
     if (++ikc == kc_per_tap) {
@@ -895,16 +941,7 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
     if (s < nkt) issue(s);
 
   for (int i = 0; i < nkt; ++i) {
-    // tile i has landed once at most the loads of the NST-2 younger tiles are outstanding; lgkmcnt(0): this wave's
-    // fragment reads of tile i-1 have completed (not merely been issued) before the barrier lets another wave's
-    // glds overwrite that stage -- hipcc will otherwise leave reads in flight across the barrier
-    const int younger = min(NST - 2, nkt - 1 - i);
-    if (NST >= 4 && younger >= 2)
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * G) : "memory");
-    else if (NST >= 3 && younger >= 1)
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    ring_wait<NST, G>(min(NST - 2, nkt - 1 - i));
     __builtin_amdgcn_s_barrier();  // everyone's part of tile i landed; everyone finished tile i-1
     if (i + NST - 1 < nkt) issue((i + NST - 1) % NST);
 
@@ -922,9 +959,6 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
         for (int k = 0; k < NT; ++k)
           fw[p][k] = *reinterpret_cast<const op16x8*>(base + p * PLANE_ELEMS + w_row_off + k * 16 * TBK + coff);
       }
-#if DSN_SETPRIO
-      __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
       for (int tn = 0; tn < NT; ++tn) {
 #pragma unroll
@@ -936,9 +970,6 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
           acc[tn][tm] = mfma16<F16>(fw[0][tn], fa[0][tm], acc[tn][tm]);
         }
       }
-#if DSN_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
     }
   }
   epilogue_gen<P, F16, NT, 4, 0, LEAN>(d, acc, m0 + wm * 64, d.M, n0 + wn * WTN, lane, z);
@@ -990,6 +1021,11 @@ __global__ __launch_bounds__((TBM / 64) * (TBN / WTN) * 64, 1) void igemm2_kerne
 // of chunk c, right before that iteration's weight tile, so for the next NSTW-2 iterations it is YOUNGER than the
 // weight tile being waited for and the allowed outstanding count is raised by its (wave-uniform) instruction count.
 // ============================================================================
+// dynamic LDS of igemm_halo3x3_kernel: [2][HRMAX][32] halo | [4][128][32] weights | dummy
+constexpr size_t halo_lds_bytes(int tbm) {
+  const int hrmax = ((tbm + 2 * 33 + 15) / 16) * 16;
+  return (size_t)(2 * hrmax * 32 + 4 * 128 * 32 + 16 * 32) * sizeof(op16_t);
+}
 // SC = 1: the variant that accumulates a 1x1 shortcut conv first (GemmDesc::sc_A) -- its own instantiation, so that the
 // plain convs keep their register allocation
 template <int F16, int TBM, int MINW, int SC = 0>
@@ -1012,9 +1048,7 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN_, wn = wave - wm * WN_;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+  const int t = xcd_remap();
   const int tile_m = t / d.tiles_n, tile_n = t - tile_m * d.tiles_n;
   const int m0 = tile_m * TBM, n0 = tile_n * TBN;
   const int HW = d.rows_per_b, W = d.img_w;
@@ -1059,15 +1093,12 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
       op16_t* ab = (cc & 1) ? hbuf + HBUF : hbuf;
       op16_t* wb2 = wring + (cc & 1) * WBUF;
 #pragma unroll
-      for (int gi = 0; gi < AG; ++gi)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[gi] + (long)cc * CK),
-                                         (__attribute__((address_space(3))) void*)(ab + (wave * AG + gi) * 16 * CK), 16, 0, 0);
+      for (int gi = 0; gi < AG; ++gi) glds(asrc[gi] + (long)cc * CK, ab + (wave * AG + gi) * 16 * CK);
 #pragma unroll
       for (int gi = 0; gi < GW; ++gi) {
         const int g = wave * GW + gi;
         op16_t* dst = g < TBN / 16 ? wb2 + g * 16 * CK : dummy;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w2src[gi] + (long)cc * w2step[gi]),
-                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        glds(w2src[gi] + (long)cc * w2step[gi], dst);
       }
     };
     issue2(0);
@@ -1126,8 +1157,7 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
     for (int gi = 0; gi < HGW; ++gi) {
       const op16_t* g = hsrc[gi] + (long)c * hstep[gi];
       op16_t* dst = hdst[gi] == dummy ? dummy : hdst[gi] + (base - hbuf);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      glds(g, dst);
     }
   };
   int wi_c = 0, wi_tap = 0;  // (chunk, tap) of the next weight tile to issue
@@ -1138,8 +1168,7 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
       const int g = wave * GW + gi;
       const op16_t* gp = wsrc[gi] + off * wstep[gi];
       op16_t* dst = g < TBN / 16 ? wring + slot * WBUF + g * 16 * CK : dummy;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      glds(gp, dst);
     }
     if (++wi_tap == 9) {
       wi_tap = 0;
@@ -1250,65 +1279,67 @@ __global__ __launch_bounds__((TBM / 64) * 2 * 64, MINW) void igemm_halo3x3_kerne
 // masked.  Staging / ring / swizzle as in igemm2_kernel (BK = 32); row groups are dealt round-robin
 // to the waves, so the per-wave glds count (and its vmcnt) differs by one between waves.
 // ============================================================================
+// Geometry shared by the 16-bit and the fp8 row-panel kernel.  WM_ wave rows x WN_ wave columns; the MT row sub-tiles
+// of a panel are dealt MT / WM_ (+1 for the first MT % WM_ wave rows) -- WM_ = 4: MT = 17: 5/4/4/4 = 272 rows (8 panels
+// of 264 for M = 2112); MT = 9: 3/2/2/2; MT = 7: 2/2/2/1 -- and every wave owns 4 column sub-tiles (64 columns).
+// (WM_ = 2: 8 waves with taller wave tiles -- fewer fragment bytes read from LDS per MFMA, 256 registers per lane.)
+template <int MT, int WM_, int WN_, int TBK>
+struct PanelGeom {
+  static constexpr int NWAVES = WM_ * WN_, TBN = WN_ * 64, AROWS = MT * 16;
+  static constexpr int MTW = (MT + WM_ - 1) / WM_;  // row sub-tiles of the tallest wave tile
+  static constexpr int ROWS = AROWS + TBN;          // staged rows per plane per k-tile (A rows then W rows)
+  static constexpr int CPR = TBK / 8;               // 16-byte chunks per row
+  static constexpr int RPG = 64 / CPR;              // rows filled by one glds wave-instruction (1 KiB)
+  static constexpr int GROUPS = ROWS / RPG;
+  static constexpr int GPW = (GROUPS + NWAVES - 1) / NWAVES;  // max groups per wave
+  static constexpr int REM = GROUPS % NWAVES;       // waves < REM carry GPW groups, the rest GPW-1 (REM==0: all GPW)
+  static constexpr int MBASE = MT / WM_, MREM = MT % WM_;
+};
+
+// dynamic LDS of igemm_panel_kernel: [NST][plane][A rows | W rows (TBN)][TBK], then (mean, rstd) of the panel's rows
+constexpr size_t panel_lds_bytes(int planes, int mt, int tbn, int nst, int tbk, bool ln_rows) {
+  return (size_t)nst * planes * (mt * 16 + tbn) * tbk * sizeof(op16_t) + (ln_rows ? mt * 16 * 2 * sizeof(float) : 0);
+}
 template <int P, int F16, int WN_, int NST, int TBK, int MT = 17, int EPI = 0, int WM_ = 4>
 __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const GemmDesc d,
                                                                          const op16_t* __restrict__ zero_page) {
-  // 4 wave rows x WN_ wave columns; the MT row sub-tiles of a panel are dealt MT/4 (+1 for the first MT%4 wave rows):
-  // MT = 17: 5/4/4/4 = 272 rows (8 panels of 264 for M = 2112); MT = 9: 3/2/2/2 = 144 rows (16 panels of 132);
-  // MT = 7: 2/2/2/1 = 112 rows.  Every wave owns 4 column sub-tiles (64 columns).
-  extern __shared__ __attribute__((aligned(16))) op16_t lds[];  // [NST][plane][A rows | W rows (TBN) | pad][TBK]
-  // (WM_ = 2: 8 waves with taller wave tiles -- fewer fragment bytes read from LDS per MFMA, 256 registers per lane)
-  constexpr int NWAVES = WM_ * WN_;
-  constexpr int MTW = (MT + WM_ - 1) / WM_;
-  constexpr int TBN = WN_ * 64;
-  constexpr int AROWS = MT * 16;
-  constexpr int ROWS = AROWS + TBN;
-  constexpr int PLANE_ELEMS = ROWS * TBK;
+  extern __shared__ __attribute__((aligned(16))) op16_t lds[];  // (panel_lds_bytes)
+  using PG = PanelGeom<MT, WM_, WN_, TBK>;
+  constexpr int MTW = PG::MTW, GPW = PG::GPW;
+  constexpr int PLANE_ELEMS = PG::ROWS * TBK;
   constexpr int STAGE_ELEMS = P * PLANE_ELEMS;
-  constexpr int CPR = TBK / 8;
-  constexpr int RPG = 64 / CPR;
-  constexpr int GROUPS = ROWS / RPG;
-  constexpr int GPW = (GROUPS + NWAVES - 1) / NWAVES;  // max groups per wave
-  constexpr int REM = GROUPS % NWAVES;                 // waves < REM carry GPW groups, the rest GPW-1 (REM==0: all GPW)
   constexpr int KS = TBK / 32;
+  static_assert(NST * STAGE_ELEMS * sizeof(op16_t) == panel_lds_bytes(P, MT, PG::TBN, NST, TBK, false), "ring size");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // (this wave's share, spelled out in both panel kernels: computed by a shared function, these values changed the
+  // register allocation of the MT = 9 and 17 instantiations; so did the residual seed and the LayerNorm rows below)
   const int wave_m = wave / WN_, wave_n = wave - wave_m * WN_;
-  constexpr int MBASE = MT / WM_, MREM = MT % WM_;
-  const int my_mt = MBASE + (wave_m < MREM ? 1 : 0);
-  const int my_row0 = 16 * (wave_m * MBASE + min(wave_m, MREM));
-  const int my_groups = (REM == 0 || wave < REM) ? GPW : GPW - 1;
+  const int my_mt = PG::MBASE + (wave_m < PG::MREM ? 1 : 0);
+  const int my_row0 = 16 * (wave_m * PG::MBASE + min(wave_m, PG::MREM));
+  const int my_groups = (PG::REM == 0 || wave < PG::REM) ? GPW : GPW - 1;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
-  const int ntiles = d.tiles_m * d.tiles_n;
-  const int z = t / ntiles;
-  const int tile = t - z * ntiles;
-  const int tile_m = d.m_fast ? tile % d.tiles_m : tile / d.tiles_n;
-  const int tile_n = d.m_fast ? tile / d.tiles_m : tile - tile_m * d.tiles_n;
-  const int m0 = tile_m * d.panel_rows, n0 = tile_n * TBN;
+  const TileId ti = tile_of(d);
+  const int z = ti.z, m0 = ti.tile_m * d.panel_rows, n0 = ti.tile_n * PG::TBN;
   const int m_end = min(m0 + d.panel_rows, d.M);
 
   const int Ktot = d.taps * d.Cin;
   const int kc_per_tap = d.Cin / TBK;
-  const int nkt_all = d.taps * kc_per_tap;
-  const int kt_begin = (int)((long)nkt_all * z / d.ksplit);
-  const int kt_end = (int)((long)nkt_all * (z + 1) / d.ksplit);
-  const int nkt = kt_end - kt_begin;
+  const KRange kr = k_range(d.taps * kc_per_tap, z, d.ksplit);
+  const int kt_begin = kr.begin, nkt = kr.count;
 
-  const int rsub = lane / CPR, cpos = lane % CPR;
+  const int rsub = lane / PG::CPR, cpos = lane % PG::CPR;
   RowLoad rl[GPW];
 #pragma unroll
   for (int gi = 0; gi < GPW; ++gi) {
-    const int g = wave + gi * NWAVES;  // round-robin deal
-    const bool is_a = g < AROWS / RPG;
-    const int row = (is_a ? g : g - AROWS / RPG) * RPG + rsub;
+    const int g = wave + gi * PG::NWAVES;  // round-robin deal
+    const bool is_a = g < PG::AROWS / PG::RPG;
+    const int row = (is_a ? g : g - PG::AROWS / PG::RPG) * PG::RPG + rsub;
     const int gchunk = cpos ^ swzk<TBK>(row);
     const int idx = (is_a ? m0 : n0) + row;
-    rl[gi] = make_row(d, is_a, idx, g < GROUPS && (is_a ? idx < m_end : idx < d.N), gchunk, Ktot);
+    rl[gi] = make_row(d, is_a, idx, g < PG::GROUPS && (is_a ? idx < m_end : idx < d.N), gchunk, Ktot);
   }
   const op16_t* zsrc = zero_page + cpos * 8;
   int itap = kt_begin / kc_per_tap, ikc = kt_begin - itap * kc_per_tap;
@@ -1319,15 +1350,13 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
 #pragma unroll
     for (int gi = 0; gi < GPW; ++gi) {
       if (gi < my_groups) {
-        const int g = wave + gi * NWAVES;
+        const int g = wave + gi * PG::NWAVES;
         const bool ok = (rl[gi].mask >> itap) & 1u;
         const op16_t* g0 = rl[gi].ptr + (rl[gi].is_a ? offa : offw);
 #pragma unroll
         for (int p = 0; p < P; ++p) {
           const op16_t* gp = ok ? g0 + p * rl[gi].ps : zsrc;
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
-                                           (__attribute__((address_space(3))) void*)(sbase + p * PLANE_ELEMS + g * RPG * TBK),
-                                           16, 0, 0);
+          glds(gp, sbase + p * PLANE_ELEMS + g * PG::RPG * TBK);
         }
       }
     }
@@ -1346,7 +1375,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
   const int frow = lane & 15, fchunk = lane >> 4;
   const int fsw = swzk<TBK>(frow);
   const int a_row_off = (my_row0 + frow) * TBK;
-  const int w_row_off = (AROWS + wave_n * 64 + frow) * TBK;
+  const int w_row_off = (PG::AROWS + wave_n * 64 + frow) * TBK;
 
 #pragma unroll
   for (int s2 = 0; s2 < NST - 1; ++s2)
@@ -1370,7 +1399,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
   // the epilogue reads them
   float* const ln_rows = reinterpret_cast<float*>(lds + NST * STAGE_ELEMS);
   if ((EPI & EPI_LNFOLD) && d.ln_stats) {
-    for (int r = tid; r < m_end - m0; r += NWAVES * 64) {
+    for (int r = tid; r < m_end - m0; r += PG::NWAVES * 64) {
       const f32x4* ps = reinterpret_cast<const f32x4*>(d.ln_stats + (long)(m0 + r) * d.ln_np * 2);  // 2 slices each
       float msum = 0.f, m2 = 0.f, q = 0.f;
       // sum of slice means, of slice M2s and of squared slice means in ONE pass (fixed order):
@@ -1390,20 +1419,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
   }
 
   for (int i = 0; i < nkt; ++i) {
-    const int younger = min(NST - 2, nkt - 1 - i);
-    if (NST >= 4 && younger >= 2) {  // two younger tiles stay in flight
-      if (REM == 0 || wave < REM)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * GPW * P) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * (GPW - 1) * P) : "memory");
-    } else if (NST >= 3 && younger >= 1) {
-      if (REM == 0 || wave < REM)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GPW * P) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((GPW - 1) * P) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
+    ring_wait<NST, GPW * P, (GPW - 1) * P>(min(NST - 2, nkt - 1 - i), PG::REM == 0 || wave < PG::REM);
     __builtin_amdgcn_s_barrier();
     if (i + NST - 1 < nkt) issue((i + NST - 1) % NST);
 
@@ -1437,10 +1453,10 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
     }
   }
   // rows m0 + my_row0 + tm*16 ...; wave rows 1..3 never touch their (unused) 5th sub-tile: mask it by row
-  epilogue_gen<P, F16, 4, MTW, EPI, LEAN_NO_NCSN>(d, acc, m0 + my_row0, min(m_end, m0 + my_row0 + my_mt * 16), n0 + wave_n * 64, lane,
-                                    z, ((EPI & EPI_LNFOLD) && d.ln_stats) ? ln_rows : nullptr, m0);
+  epilogue_gen<P, F16, 4, MTW, EPI, LEAN_NO_NCSN>(d, acc, m0 + my_row0, min(m_end, m0 + my_row0 + my_mt * 16),
+                                                  n0 + wave_n * 64, lane, z,
+                                                  ((EPI & EPI_LNFOLD) && d.ln_stats) ? ln_rows : nullptr, m0);
 }
-
 
 // ============================================================================
 // fp8 (MX) twin of the row-panel kernel (DSN_PREC_FP8: the four DiT layer GEMMs).  Same geometry and ring; a
@@ -1450,57 +1466,46 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_kernel(const Ge
 // glds per k-tile for the scale dwords of 64 staged rows (waves beyond the staged rows load a zero page), so the
 // counted vmcnt stays uniform; lane (r, q) then reads byte q of its row's dword.
 // ============================================================================
+// dynamic LDS of igemm_panel_fp8_kernel: [NST][A rows | W rows][64 pairs], then [NST][(scale groups + 1) * 64] u32,
+// then (mean, rstd) of the panel's rows
+constexpr size_t panel_fp8_lds_bytes(int mt, int tbn, int nst, bool ln_rows) {
+  return (size_t)nst * ((mt * 16 + tbn) * 64 * sizeof(op16_t) + ((mt * 16 + tbn + 63) / 64 + 1) * 64 * sizeof(unsigned)) +
+         (ln_rows ? mt * 16 * 2 * sizeof(float) : 0);
+}
 template <int WM_, int WN_, int NST, int MT, int EPI = EPI_FP8OUT>
 __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(const GemmDesc d,
                                                                              const op16_t* __restrict__ zero_page) {
-  extern __shared__ __attribute__((aligned(16))) op16_t lds[];  // [NST][A rows | W rows][64 pairs], then [NST][SROWS] u32
+  extern __shared__ __attribute__((aligned(16))) op16_t lds[];  // (panel_fp8_lds_bytes)
   constexpr int TBK = 64;  // byte PAIRS per row per k-tile (128 fp8)
-  // WM_ x WN_ waves (8 for the tall panels: the 32-byte fp8 fragments need the 256-register budget of 2 waves per
-  // SIMD); the MT row sub-tiles are dealt over the WM_ wave rows
-  constexpr int NWAVES = WM_ * WN_;
-  constexpr int MTW = (MT + WM_ - 1) / WM_;
-  constexpr int TBN = WN_ * 64;
-  constexpr int AROWS = MT * 16;
-  constexpr int ROWS = AROWS + TBN;
-  constexpr int STAGE_ELEMS = ROWS * TBK;
-  constexpr int CPR = TBK / 8;
-  constexpr int RPG = 64 / CPR;
-  constexpr int GROUPS = ROWS / RPG;
-  constexpr int GPW = (GROUPS + NWAVES - 1) / NWAVES;
-  constexpr int REM = GROUPS % NWAVES;
-  constexpr int SG = (ROWS + 63) / 64;             // 64-row scale groups that hold staged rows
+  // (8 waves for the tall panels: the 32-byte fp8 fragments need the 256-register budget of 2 waves per SIMD)
+  using PG = PanelGeom<MT, WM_, WN_, TBK>;
+  constexpr int NWAVES = PG::NWAVES, MTW = PG::MTW, AROWS = PG::AROWS, GPW = PG::GPW;
+  constexpr int STAGE_ELEMS = PG::ROWS * TBK;
+  constexpr int SG = (PG::ROWS + 63) / 64;         // 64-row scale groups that hold staged rows
   constexpr int SGW = (SG + NWAVES - 1) / NWAVES;  // scale groups per wave (uniform: tail slots load a zero page)
   constexpr int SROWS = (SG + 1) * 64;             // scale dwords per stage; slots >= SG land in the spare group
   constexpr bool PF = MTW < 8;                     // A fragments one row sub-tile ahead of their MFMAs
+  static_assert(NST * (STAGE_ELEMS * sizeof(op16_t) + SROWS * sizeof(unsigned)) ==
+                    panel_fp8_lds_bytes(MT, PG::TBN, NST, false), "ring size");
   unsigned* const slds = reinterpret_cast<unsigned*>(lds + NST * STAGE_ELEMS);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wave_m = wave / WN_, wave_n = wave - wave_m * WN_;
-  constexpr int MBASE = MT / WM_, MREM = MT % WM_;
-  const int my_mt = MBASE + (wave_m < MREM ? 1 : 0);
-  const int my_row0 = 16 * (wave_m * MBASE + min(wave_m, MREM));
-  const int my_groups = (REM == 0 || wave < REM) ? GPW : GPW - 1;
+  const int my_mt = PG::MBASE + (wave_m < PG::MREM ? 1 : 0);
+  const int my_row0 = 16 * (wave_m * PG::MBASE + min(wave_m, PG::MREM));
+  const int my_groups = (PG::REM == 0 || wave < PG::REM) ? GPW : GPW - 1;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
-  const int ntiles = d.tiles_m * d.tiles_n;
-  const int z = t / ntiles;
-  const int tile = t - z * ntiles;
-  const int tile_m = d.m_fast ? tile % d.tiles_m : tile / d.tiles_n;
-  const int tile_n = d.m_fast ? tile / d.tiles_m : tile - tile_m * d.tiles_n;
-  const int m0 = tile_m * d.panel_rows, n0 = tile_n * TBN;
+  const TileId ti = tile_of(d);
+  const int z = ti.z, m0 = ti.tile_m * d.panel_rows, n0 = ti.tile_n * PG::TBN;
   const int m_end = min(m0 + d.panel_rows, d.M);
 
   const int Ktot = d.Cin;             // byte pairs per row (taps == 1)
-  const int nkt_all = d.Cin / TBK;
-  const int kt_begin = (int)((long)nkt_all * z / d.ksplit);
-  const int kt_end = (int)((long)nkt_all * (z + 1) / d.ksplit);
-  const int nkt = kt_end - kt_begin;
+  const KRange kr = k_range(d.Cin / TBK, z, d.ksplit);
+  const int kt_begin = kr.begin, nkt = kr.count;
 
-  const int rsub = lane / CPR, cpos = lane % CPR;
+  const int rsub = lane / PG::CPR, cpos = lane % PG::CPR;
   // this lane's 16-byte slot of each staged row at k = 0, as a 32-bit element offset from the (wave-uniform) operand
   // base.  Rows outside M / N are CLAMPED to the last valid row instead of routed to a zero page: they only feed
   // accumulators of rows / columns the epilogue never stores, and a uniform base + 32-bit offset costs half the
@@ -1509,8 +1514,8 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
 #pragma unroll
   for (int gi = 0; gi < GPW; ++gi) {
     const int g = wave + gi * NWAVES;
-    const bool is_a = g < AROWS / RPG;
-    const int row = (is_a ? g : g - AROWS / RPG) * RPG + rsub;
+    const bool is_a = g < AROWS / PG::RPG;
+    const int row = (is_a ? g : g - AROWS / PG::RPG) * PG::RPG + rsub;
     const int gchunk = cpos ^ swzk<TBK>(row);
     const int idx = min((is_a ? m0 : n0) + row, (is_a ? m_end : d.N) - 1);
     roff[gi] = (unsigned)(idx * Ktot + gchunk * 8) * 2u;  // BYTES (no shift between the zero-extension and the add)
@@ -1524,7 +1529,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
     const int srow = (wave + j * NWAVES) * 64 + lane;
     const bool s_is_a = srow < AROWS;
     s_a[j] = s_is_a;
-    const int sidx = s_is_a ? min(m0 + srow, m_end - 1) : min(n0 + min(srow - AROWS, TBN - 1), d.N - 1);
+    const int sidx = s_is_a ? min(m0 + srow, m_end - 1) : min(n0 + min(srow - AROWS, PG::TBN - 1), d.N - 1);
     soff[j] = (unsigned)(sidx * d.mx_kblocks);
   }
   int kt_abs = kt_begin;
@@ -1536,17 +1541,14 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
     for (int gi = 0; gi < GPW; ++gi) {
       if (gi < my_groups) {
         const int g = wave + gi * NWAVES;
-        const char* gp = reinterpret_cast<const char*>(g < AROWS / RPG ? d.A : d.W) + (off + roff[gi]);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
-                                         (__attribute__((address_space(3))) void*)(sbase + g * RPG * TBK), 16, 0, 0);
+        const char* gp = reinterpret_cast<const char*>(g < AROWS / PG::RPG ? d.A : d.W) + (off + roff[gi]);
+        glds(gp, sbase + g * PG::RPG * TBK);
       }
     }
 #pragma unroll
     for (int j = 0; j < SGW; ++j) {
       const unsigned char* sp = (s_a[j] ? d.a_scale : d.w_scale) + (soff[j] + (unsigned)(4 * kt_abs));
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)sp,
-          (__attribute__((address_space(3))) void*)(slds + stage * SROWS + min(wave + j * NWAVES, SG) * 64), 4, 0, 0);
+      glds<4>(sp, slds + stage * SROWS + min(wave + j * NWAVES, SG) * 64);
     }
     ++kt_abs;
   };
@@ -1580,6 +1582,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
       }
     }
   }
+
   // folded LayerNorm: (mean, rstd) of the panel's rows from the producer's per-64-column partials (as in
   // igemm_panel_kernel; the row length is the fp8 K = 2 * Cin) -> LDS behind the scale ring
   float* const ln_rows = reinterpret_cast<float*>(slds + NST * SROWS);
@@ -1602,15 +1605,8 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
   }
 
   for (int i = 0; i < nkt; ++i) {
-    const int younger = min(NST - 2, nkt - 1 - i);
-    if (NST >= 3 && younger >= 1) {
-      if (REM == 0 || wave < REM)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GPW + SGW) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GPW - 1 + SGW) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
+    // (clamped stage count: this kernel never leaves two younger tiles in flight, not even with its 4-stage ring)
+    ring_wait<(NST < 3 ? NST : 3), GPW + SGW, GPW - 1 + SGW>(min(NST - 2, nkt - 1 - i), PG::REM == 0 || wave < PG::REM);
     __builtin_amdgcn_s_barrier();
     if (i + NST - 1 < nkt) issue((i + NST - 1) % NST);
 
@@ -1656,10 +1652,10 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, 1) void igemm_panel_fp8_kernel(cons
       sa = nsa;
     }
   }
-  epilogue_gen<1, 1, 4, MTW, EPI, LEAN_NO_NCSN>(d, acc, m0 + my_row0, min(m_end, m0 + my_row0 + my_mt * 16), n0 + wave_n * 64, lane, z,
-                                  ((EPI & EPI_LNFOLD) && d.ln_stats) ? ln_rows : nullptr, m0);
+  epilogue_gen<1, 1, 4, MTW, EPI, LEAN_NO_NCSN>(d, acc, m0 + my_row0, min(m_end, m0 + my_row0 + my_mt * 16),
+                                                n0 + wave_n * 64, lane, z,
+                                                ((EPI & EPI_LNFOLD) && d.ln_stats) ? ln_rows : nullptr, m0);
 }
-
 
 // ============================================================================
 // Skinny GEMM for M <= 48 rows (one mixture, or a handful: config C1 is 17 token rows): there the path is bound by
@@ -1734,16 +1730,58 @@ __global__ __launch_bounds__(256) void igemm_skinny_kernel(const GemmDesc d) {
   epilogue_gen<1, F16, 2, MT>(d, acc, 0, d.M, n0, lane, z);
 }
 
+// ---- host side of the ring kernels ----
+
+// The one launch of a ring kernel: `smem` bytes of dynamic LDS, refused beyond the CU's 160 KiB
+template <auto Kernel>
+hipError_t launch_ring(const GemmDesc& d, int grid, int block, size_t smem, const op16_t* zp, hipStream_t stream) {
+  dsn_allow_lds<Kernel>();
+  if (smem > 160 * 1024) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), smem, stream, d, zp);
+  return hipGetLastError();
+}
+
+// every ring launcher, before it picks a kernel: ksplit floor, split-K rule (raw fp32 partial sums), zero page
+hipError_t normalise(GemmDesc& d, const op16_t*& zp) {
+  if (d.ksplit < 1) d.ksplit = 1;
+  if (d.ksplit > 1 && (!d.out_f32 || d.swiglu)) return hipErrorInvalidValue;
+  zp = dsn_zero_page();
+  return zp ? hipSuccess : hipErrorOutOfMemory;
+}
+
 template <int P, int F16, int TBM, int TBN, int NST, int TBK, int LEAN = 0, int WTN = 64>
 hipError_t launch_cfg(GemmDesc d, const op16_t* zp, hipStream_t stream) {
   d.tiles_m = cdiv(d.M, TBM);
   d.tiles_n = cdiv(d.N, TBN);
-  dsn_allow_lds<igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>>();
-  const int grid = d.tiles_m * d.tiles_n * d.ksplit;
-  const size_t smem = (size_t)NST * P * (TBM + TBN) * TBK * sizeof(op16_t);
-  hipLaunchKernelGGL((igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>), dim3(grid), dim3((TBM / 64) * (TBN / WTN) * 64),
-                     smem, stream, d, zp);
-  return hipGetLastError();
+  return launch_ring<igemm2_kernel<P, F16, TBM, TBN, NST, TBK, LEAN, WTN>>(
+      d, d.tiles_m * d.tiles_n * d.ksplit, (TBM / 64) * (TBN / WTN) * 64, igemm2_lds_bytes(P, TBM, TBN, NST, TBK), zp, stream);
+}
+
+template <int F16, int TBM, int MINW, int SC = 0>
+hipError_t launch_halo_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
+  d.tiles_m = d.M / TBM;
+  d.tiles_n = cdiv(d.N, 128);
+  return launch_ring<igemm_halo3x3_kernel<F16, TBM, MINW, SC>>(d, d.tiles_m * d.tiles_n, (TBM / 64) * 2 * 64,
+                                                               halo_lds_bytes(TBM), zp, stream);
+}
+
+// d.panel_rows rows per workgroup (<= 272), WN_ * 64 columns
+template <int P, int F16, int WN_, int NST, int TBK, int MT = 17, int EPI = 0, int WM_ = 4>
+hipError_t launch_panel_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
+  d.tiles_m = cdiv(d.M, d.panel_rows);
+  d.tiles_n = cdiv(d.N, WN_ * 64);
+  return launch_ring<igemm_panel_kernel<P, F16, WN_, NST, TBK, MT, EPI, WM_>>(
+      d, d.tiles_m * d.tiles_n * d.ksplit, WM_ * WN_ * 64, panel_lds_bytes(P, MT, WN_ * 64, NST, TBK, d.ln_stats != nullptr),
+      zp, stream);
+}
+
+template <int WM_, int WN_, int NST, int MT, int EPI = EPI_FP8OUT>
+hipError_t launch_panel_fp8_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
+  d.tiles_m = cdiv(d.M, d.panel_rows);
+  d.tiles_n = cdiv(d.N, WN_ * 64);
+  return launch_ring<igemm_panel_fp8_kernel<WM_, WN_, NST, MT, EPI>>(
+      d, d.tiles_m * d.tiles_n * d.ksplit, WM_ * WN_ * 64, panel_fp8_lds_bytes(MT, WN_ * 64, NST, (EPI & EPI_LNFOLD) != 0), zp,
+      stream);
 }
 
 }  // namespace
@@ -1766,13 +1804,10 @@ const op16_t* dsn_zero_page() {
 hipError_t igemm2_launch_cfg(const GemmDesc& din, int pl, int bm, int bn, int nst, int bk, hipStream_t stream) {
   const int planes = PL_COUNT(pl), f16 = PL_F16(pl);
   GemmDesc d = din;
-
-  if (d.ksplit < 1) d.ksplit = 1;
   if (d.Cin % bk != 0 || d.M <= 0 || d.N <= 0) return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 32 != 0)) return hipErrorInvalidValue;
-  if (d.ksplit > 1 && (!d.out_f32 || d.swiglu)) return hipErrorInvalidValue;
-  const op16_t* zp = dsn_zero_page();
-  if (!zp) return hipErrorOutOfMemory;
+  const op16_t* zp;
+  if (const hipError_t e = normalise(d, zp); e != hipSuccess) return e;
   // conv-stack descriptors (Oobleck: bias / activation / residual / fp32 + plane outputs only) take the lean epilogue
   const bool lean = !d.rope_cos && d.qkv_D <= 0 && !d.swiglu && !d.gn_stats && !d.bbias && d.f32_op != DSN_F32_TANH &&
                     d.ksplit <= 1;
@@ -1806,20 +1841,6 @@ hipError_t igemm2_launch_cfg(const GemmDesc& din, int pl, int bm, int bn, int ns
 // halo-resident 3x3 conv: eligibility + launch (hipErrorNotSupported = not eligible, caller falls back)
 // MINW = 4: registers capped at 128 so that two 8-wave workgroups share a CU (123 VGPRs, no spills since the GroupNorm
 // partials are taken in one pass); MINW = 1 for the 4-wave 128-row variant.
-// dynamic LDS of igemm_halo3x3_kernel: [2][HRMAX][32] halo | [4][128][32] weights | dummy
-static constexpr size_t halo_lds_bytes(int tbm) {
-  const int hrmax = ((tbm + 2 * 33 + 15) / 16) * 16;
-  return (size_t)(2 * hrmax * 32 + 4 * 128 * 32 + 16 * 32) * sizeof(op16_t);
-}
-template <int F16, int TBM, int MINW, int SC = 0>
-static hipError_t launch_halo_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
-  d.tiles_m = d.M / TBM;
-  d.tiles_n = cdiv(d.N, 128);
-  dsn_allow_lds<igemm_halo3x3_kernel<F16, TBM, MINW, SC>>();
-  hipLaunchKernelGGL((igemm_halo3x3_kernel<F16, TBM, MINW, SC>), dim3(d.tiles_m * d.tiles_n), dim3((TBM / 64) * 2 * 64),
-                     halo_lds_bytes(TBM), stream, d, zp);
-  return hipGetLastError();
-}
 // 128-row images (NCSN++ level 2, 128 workgroups of 4 waves) measured slower than igemm2's 128 x 128 x BK 64 tiles
 // (62 vs 55 us): not eligible.  At least two 256-row workgroups per CU (MI355X: 256 CUs): 8-wave 256-row tiles;
 // fewer (NCSN++ level 1: 256): 128-row tiles of 4 waves, two of them per CU (whole score call 5.48 -> 5.38 ms).
@@ -1863,16 +1884,17 @@ bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl) {
                  : (PL_F16(pl) ? halo_resident_blocks<1, 128, 1>() : halo_resident_blocks<0, 128, 1>());
   return (long)(d.M / v) * cdiv(d.N, 128) <= c;  // every workgroup resident at once: they wait for each other
 }
-hipError_t igemm_halo3x3_launch(const GemmDesc& d, int pl, hipStream_t stream) {
+hipError_t igemm_halo3x3_launch(const GemmDesc& din, int pl, hipStream_t stream) {
   const int f16 = PL_F16(pl);
+  GemmDesc d = din;
   if (d.gnf_out && (!igemm_halo3x3_gnfin_ok(d, pl) || !d.gnf_gamma || !d.gnf_beta || !d.gnf_sync || !d.gnf_err ||
                     d.out_f32 || d.out_planes))
     return hipErrorInvalidValue;
   if (d.sc_A && (!d.sc_W || d.sc_Cin < 32 || d.sc_Cin % 32 != 0 || d.sc_row_elems < d.sc_Cin)) return hipErrorInvalidValue;
   const int tile = igemm_halo3x3_tile(d, pl);
   if (!tile) return hipErrorNotSupported;
-  const op16_t* zp = dsn_zero_page();
-  if (!zp) return hipErrorOutOfMemory;
+  const op16_t* zp;  // (an eligible descriptor has no split-K: only the zero page can fail here)
+  if (const hipError_t e = normalise(d, zp); e != hipSuccess) return e;
   if (d.sc_A) {
     if (tile == 256) return f16 ? launch_halo_t<1, 256, 4, 1>(d, zp, stream) : launch_halo_t<0, 256, 4, 1>(d, zp, stream);
     return f16 ? launch_halo_t<1, 128, 1, 1>(d, zp, stream) : launch_halo_t<0, 128, 1, 1>(d, zp, stream);
@@ -1996,54 +2018,22 @@ hipError_t igemm2_launch(const GemmDesc& d, int pl, hipStream_t stream) {
   return igemm2_launch_cfg(d, pl, bm, bn, nst, bk, stream);
 }
 
-// Row-panel launcher: d.panel_rows rows per workgroup (<= 272), bn in {128, 256}.
-template <int P, int F16, int WN_, int NST, int TBK, int MT = 17, int EPI = 0, int WM_ = 4>
-static hipError_t launch_panel_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
-  constexpr int TBN = WN_ * 64;
-  d.tiles_m = cdiv(d.M, d.panel_rows);
-  d.tiles_n = cdiv(d.N, TBN);
-  dsn_allow_lds<igemm_panel_kernel<P, F16, WN_, NST, TBK, MT, EPI, WM_>>();
-  const int grid = d.tiles_m * d.tiles_n * d.ksplit;
-  const size_t smem = (size_t)NST * P * (MT * 16 + TBN) * TBK * sizeof(op16_t) + (d.ln_stats ? MT * 16 * 2 * sizeof(float) : 0);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((igemm_panel_kernel<P, F16, WN_, NST, TBK, MT, EPI, WM_>), dim3(grid), dim3(WM_ * WN_ * 64), smem, stream,
-                     d, zp);
-  return hipGetLastError();
-}
-
-
-template <int WM_, int WN_, int NST, int MT, int EPI = EPI_FP8OUT>
-static hipError_t launch_panel_fp8_t(GemmDesc d, const op16_t* zp, hipStream_t stream) {
-  constexpr int TBN = WN_ * 64;
-  d.tiles_m = cdiv(d.M, d.panel_rows);
-  d.tiles_n = cdiv(d.N, TBN);
-  dsn_allow_lds<igemm_panel_fp8_kernel<WM_, WN_, NST, MT, EPI>>();
-  const int grid = d.tiles_m * d.tiles_n * d.ksplit;
-  const size_t smem = (size_t)NST * ((MT * 16 + TBN) * 64 * sizeof(op16_t) + ((MT * 16 + TBN + 63) / 64 + 1) * 64 * sizeof(unsigned)) +
-                      ((EPI & EPI_LNFOLD) ? MT * 16 * 2 * sizeof(float) : 0);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((igemm_panel_fp8_kernel<WM_, WN_, NST, MT, EPI>), dim3(grid), dim3(WM_ * WN_ * 64), smem, stream, d, zp);
-  return hipGetLastError();
-}
-
 hipError_t igemm_panel_fp8_launch(const GemmDesc& din, int bn, hipStream_t stream) {
   GemmDesc d = din;
-  if (d.ksplit < 1) d.ksplit = 1;
   // plain row-major GEMM only: one "batch item" of M rows, one tap, K = 2 * Cin fp8 per row, whole 128-wide k-tiles
   if (!d.a_scale || !d.w_scale || d.taps != 1 || d.in_stride != 1 || d.in_pad != 0 || d.rows_per_b != d.M ||
       d.img_w > 0 || d.Cin % 64 != 0 || d.mx_kblocks != d.Cin / 16 || d.M <= 0 || d.N <= 0 || d.panel_rows <= 0 ||
       d.panel_rows > 17 * 16 || (long)std::max(d.M, d.N) * d.Cin * 2 >= (1L << 32))
     return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 64 != 0)) return hipErrorInvalidValue;
-  if (d.ksplit > 1 && (!d.out_f32 || d.swiglu)) return hipErrorInvalidValue;
   // folded ff_norm: the producer (statistics + raw fp8 x') and the SwiGLU consumer, as in igemm_panel_launch
   if (d.stat_out && (d.N % 64 != 0 || d.stat_np != d.N / 64 || d.swiglu || d.ksplit > 1 || !d.resid || !d.out_f32 ||
                      !d.out_fp8 || !d.out_fp8_scale))
     return hipErrorInvalidValue;
   if (d.ln_stats && (!d.swiglu || !d.ln_colsum || d.ln_np <= 0 || (d.ln_np & 1) || !d.out_fp8 || !d.out_fp8_scale))
     return hipErrorInvalidValue;
-  const op16_t* zp = dsn_zero_page();
-  if (!zp) return hipErrorOutOfMemory;
+  const op16_t* zp;
+  if (const hipError_t e = normalise(d, zp); e != hipSuccess) return e;
 #define FCFGE(MT_, WM_, W_, NS_, E_) \
   if (d.panel_rows <= MT_ * 16 && bn == W_ * 64) return launch_panel_fp8_t<WM_, W_, NS_, MT_, E_>(d, zp, stream);
 #define FCFG(MT_, WM_, W_, NS_) FCFGE(MT_, WM_, W_, NS_, EPI_FP8OUT)
@@ -2093,16 +2083,14 @@ hipError_t igemm_skinny_launch(const GemmDesc& din, int pl, hipStream_t stream) 
 hipError_t igemm_panel_launch(const GemmDesc& din, int pl, int bn, hipStream_t stream) {
   const int planes = PL_COUNT(pl), f16 = PL_F16(pl);
   GemmDesc d = din;
-  if (d.ksplit < 1) d.ksplit = 1;
   if (d.Cin % 64 != 0 || d.M <= 0 || d.N <= 0 || d.panel_rows <= 0 || d.panel_rows > 17 * 16) return hipErrorInvalidValue;
   if (d.panel_wm == 2 && d.cfg_bk == 32 && d.Cin % 32 != 0) return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 32 != 0)) return hipErrorInvalidValue;
-  if (d.ksplit > 1 && (!d.out_f32 || d.swiglu)) return hipErrorInvalidValue;
   if (d.img_w > 0) return hipErrorInvalidValue;
   if (d.stat_out && (d.N % 64 != 0 || d.stat_np != d.N / 64 || d.swiglu || d.ksplit > 1)) return hipErrorInvalidValue;
   if (d.ln_stats && (!d.swiglu || !d.ln_colsum || d.ln_np <= 0 || d.taps != 1 || planes != 1)) return hipErrorInvalidValue;
-  const op16_t* zp = dsn_zero_page();
-  if (!zp) return hipErrorOutOfMemory;
+  const op16_t* zp;
+  if (const hipError_t e = normalise(d, zp); e != hipSuccess) return e;
   const int epi = (d.stat_out ? EPI_STATS : 0) | (d.ln_stats ? EPI_LNFOLD : 0);
 #define PCFGE(MT_, P_, W_, NS_, BK_, E_)                                                             \
   if (planes == P_ && bn == W_ * 64 && epi == E_)                                                     \

@@ -52,11 +52,9 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
   const int mtw = wm == 0 ? MT0 : MT - MT0;   // row sub-tiles of this wave
   const int row0 = wm == 0 ? 0 : MT0 * 16;    // first row of this wave inside the panel
 
-  // XCD-aware bijective remap; tiles ordered (head group of 4, panel, head in group): an XCD's contiguous share is a few
-  // heads x a few panels, so both its weight columns and its activation panels stay in its L2
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int t = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + loc;
+  // tiles ordered (head group of 4, panel, head in group): an XCD's contiguous share is a few heads x a few panels, so
+  // both its weight columns and its activation panels stay in its L2
+  const int t = xcd_remap();
   int head, panel;
   if ((d.H & 3) == 0) {
     const int per_group = d.panels * 4;

@@ -526,3 +526,7 @@ def test_refused_descriptor_fails_by_name(eng):
         run_case(eng[FP16], FP16, kernel="tile", bm=192, bn=128, nst=3, bk=32, B=1, Lin=64, Cin=32, N=64)
     with pytest.raises(RuntimeError, match="halo"):
         run_case(eng[FP16], FP16, kernel="halo", B=1, Lin=100, Cin=32, N=64, img=(10, 10))
+    # the split-K rule the ring launchers share: slices write raw partial sums, so no SwiGLU epilogue
+    with pytest.raises(RuntimeError, match="igemm2 split-K tile refused or failed: invalid argument"):
+        run_case(eng[FP16], FP16, kernel="splitk", ksplit=2, slabs=nan_f32(2 * 64 * 32), slab_stride=64 * 32, swiglu=True,
+                 bm=128, bn=128, nst=3, bk=32, B=1, Lin=64, Cin=64, N=64)
