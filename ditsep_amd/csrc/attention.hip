@@ -43,9 +43,7 @@ __device__ __forceinline__ void store_query_out(op16_t* __restrict__ out, long o
 #pragma unroll
         for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(v[u][r]));
       }
-      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-      const int k = dsn_mx_exp(amax);
+      const int k = dsn_mx_block_exp<16, 32>(amax);
       const float sc = dsn_pow2(-k);
 #pragma unroll
       for (int u = 0; u < 2; ++u)

@@ -70,6 +70,15 @@ __device__ __forceinline__ int dsn_mx_exp(float amax) {
   const int k = (int)((u >> 23) & 0xffu) - 127 + ((u & 0x7fffffu) ? 1 : 0);
   return min(max(k, -126), 126);
 }
+// the same k for one 32-element scale block spread over lanes: amax = this lane's share, MASKS = the xor distances to
+// the lanes that hold the rest (16, 32: a row of the MFMA accumulator layout; 1, 2, 4: 8 consecutive lanes with a quad
+// each; none: the lane holds the whole block).  Every lane of the block must call it; all of them get k.  The caller
+// stores its bytes scaled by dsn_pow2(-k) and, from one lane, the scale byte k + 127.
+template <int... MASKS>
+__device__ __forceinline__ int dsn_mx_block_exp(float amax) {
+  ((amax = fmaxf(amax, __shfl_xor(amax, MASKS, 64))), ...);
+  return dsn_mx_exp(amax);
+}
 __device__ __forceinline__ float dsn_pow2(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
 // 4 floats -> 4 saturated e4m3 bytes (byte r = element r)
 __device__ __forceinline__ unsigned dsn_fp8x4(const f32x4& v) {

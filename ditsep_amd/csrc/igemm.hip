@@ -177,9 +177,7 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
           for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(acc[2 * tp + u][tm][r]));
-          amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-          amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-          const int k = dsn_mx_exp(amax);
+          const int k = dsn_mx_block_exp<16, 32>(amax);
           const float inv = dsn_pow2(-k);
           const int nb = nw0 + tp * 32;
           if (nb < d.N) {
@@ -246,9 +244,7 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
           amax = fmaxf(amax, fabsf(h[tp][r]));
         }
       }
-      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-      const int k = dsn_mx_exp(amax);
+      const int k = dsn_mx_block_exp<16, 32>(amax);
       const float inv = dsn_pow2(-k);
       const long orow = (long)m * (d.N >> 1);
 #pragma unroll
@@ -451,9 +447,7 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
           amax = fmaxf(amax, fabsf(h[tp][r]));
         }
       }
-      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-      const int k = dsn_mx_exp(amax);
+      const int k = dsn_mx_block_exp<16, 32>(amax);
       const float inv = dsn_pow2(-k);
       if (nw0 < d.N) {
         const long orow = (long)m * (d.N >> 1);

@@ -415,10 +415,7 @@ __global__ __launch_bounds__(TPB) void residual_norm_kernel(float* __restrict__ 
         if (o8s) {
           // fp8 (MX) output: a 32-column scale block = the quads of 8 consecutive lanes (nv % 8 == 0: whole groups)
           float amax = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
-          amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-          amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-          amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
-          const int kx = dsn_mx_exp(amax);
+          const int kx = dsn_mx_block_exp<1, 2, 4>(amax);
           reinterpret_cast<unsigned*>(out)[(rbase >> 2) + i] = dsn_fp8x4(o * dsn_pow2(-kx));
           if ((lane & 7) == 0) o8s[(rbase >> 5) + (i >> 3)] = (unsigned char)(kx + 127);
           continue;
@@ -495,10 +492,7 @@ __global__ __launch_bounds__(TPB) void residual_norm_row_kernel(float* __restric
   }
   if (o8s) {  // fp8 (MX) output: a 32-column scale block = the quads of 8 consecutive lanes
     float amax = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
-    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-    amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
-    const int kx = dsn_mx_exp(amax);
+    const int kx = dsn_mx_block_exp<1, 2, 4>(amax);
     reinterpret_cast<unsigned*>(out)[(rbase >> 2) + i] = dsn_fp8x4(o * dsn_pow2(-kx));
     if ((lane & 7) == 0) o8s[(rbase >> 5) + (i >> 3)] = (unsigned char)(kx + 127);
     return;
@@ -899,7 +893,7 @@ __global__ void pack_weight_fp8_kernel(const float* __restrict__ src, unsigned c
 #pragma unroll
       for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(v[j][r]));
     }
-    const int kx = dsn_mx_exp(amax);
+    const int kx = dsn_mx_block_exp<>(amax);  // the thread holds the whole block
     const float inv = dsn_pow2(-kx);
     unsigned* dp = reinterpret_cast<unsigned*>(dst + (long)n * K + b * 32);
 #pragma unroll

@@ -315,9 +315,7 @@ __global__ __launch_bounds__(512, 1) void qkv_attention_kernel(const QkvAttnDesc
 #pragma unroll
           for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(v[u][r]));
         }
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const int k = dsn_mx_exp(amax);
+        const int k = dsn_mx_block_exp<16, 32>(amax);
         const float sc = dsn_pow2(-k);
         if (qt * 16 + r16 < S) {
 #pragma unroll
