@@ -250,6 +250,16 @@ struct dsn_ctx {
   int tv_B = -1;
   std::vector<int> lens_host;  // uploaded ragged token counts and where they went
   const int* lens_dev = nullptr;
+  // A ragged batch in the codec (null = dense): the frame counts of its B mixtures on the device ("codec_frames",
+  // upload_frames) and on the host (the profiled bytes), `rep` codec items per mixture (n_src in the decoder, 1 in the
+  // encoder).
+  struct CodecLens {
+    const int* frames;
+    const int32_t* host;
+    int rep;
+  };
+  std::vector<int> frames_host;
+  const int* frames_dev = nullptr;
 
   // Run `body(stream)` -- a pure sequence of kernel launches over workspace pointers --
   // either eagerly or as a cached hipGraph.  The first call with a given key runs
@@ -978,11 +988,13 @@ struct dsn_ctx {
   // One ResidualUnit of the coders on the stream planes `x` (plane stride ps, fp32 copy in xf) with scratch planes `h`:
   // the fused kernel x -> h, after which the two trade places, or a dilated k7 conv into h and a k1 conv + residual back
   // into x.  keep_f32: a further unit of the block reads the fp32 stream; `next`: the activation of x's consumer.
+  // cl (null = dense) / mul: ragged batch -- the unit's output rows past an item's end are cleared (tail_zero)
   void res_unit(const ResUnit& r, op16_t*& x, op16_t*& h, long ps, float* xf, bool keep_f32, const ActP& next, int S,
-                long L, hipStream_t st) {
+                long L, hipStream_t st, const CodecLens* cl = nullptr, long mul = 0) {
     if (ru_fusable(r)) {
       run_ru(r, x, ps, xf, keep_f32 ? xf : nullptr, h, next, S, L, st);
       std::swap(x, h);
+      if (cl) tail_zero(*cl, x, ps, keep_f32 ? xf : nullptr, nullptr, S, L, r.conv1.N, mul, st);
       return;
     }
     Tag tg(this, "vae.residual_unit_2gemm");
@@ -1004,6 +1016,21 @@ struct dsn_ctx {
       set_act(d, next);
       run(d, st);
     }
+    if (cl) tail_zero(*cl, x, ps, keep_f32 ? xf : nullptr, nullptr, S, L, r.conv1.N, mul, st);
+  }
+  // Ragged batch in the codec: rows [frames * mul, L) of every item of a layer's output [S][L][C] -- operand planes,
+  // fp32 stream and / or plain fp32 output, null where the layer wrote none -- are written as zero, so that the next
+  // convolution reads past an item's end what it reads for the item alone (include/ditsep_hip.h).  One
+  // launch whose grid depends on (S, L, C) alone.
+  void tail_zero(const CodecLens& cl, op16_t* planes, long ps, float* xf, float* out, int S, long L, int C, long mul,
+                 hipStream_t st) {
+    double rows = 0;  // algorithmic bytes: the tail rows of every destination, written once
+    for (int s = 0; s < S; ++s) rows += (double)std::max(0L, L - (long)cl.host[s / cl.rep] * mul);
+    const double bytes = rows * C * ((planes ? 2.0 * P : 0.0) + (xf ? 4.0 : 0.0) + (out ? 4.0 : 0.0));
+    prof_launch("vae.ragged_tail_zero", bytes, st, [&] {
+      const char* why = launch_codec_tail_zero(planes, ps, P, xf, out, S, (int)L, C, cl.frames, cl.rep, (int)mul, st);
+      if (why) fail(DSN_EINVAL, "ragged codec tail launch refused: %s (S=%d L=%ld C=%d mul=%ld)", why, S, L, C, mul);
+    });
   }
 
   // ---------------------------------------------------------------- DiT score
@@ -1393,11 +1420,22 @@ struct dsn_ctx {
   // Ragged batches.  check_frames: the refusals, before anything is allocated or launched.  upload_lens: the token
   // counts 1 + frames[b] into the fixed workspace buffer "ragged_lens" the length-aware attention kernels read --
   // outside any capture, so the lengths are data of a cached graph, not constants of it.
-  void check_frames(const char* who, const int32_t* frames, int B, int T) const {
+  // needs: what the call runs -- the DiT (the ragged score call and samplers), the encoder, the decoder
+  enum { RAGGED_DIT = 1, RAGGED_ENC = 2, RAGGED_DEC = 4 };
+  void check_frames(const char* who, const int32_t* frames, int B, int T, int needs = RAGGED_DIT) const {
     if (!frames) fail(DSN_EINVAL, "%s: frames is null", who);
-    if (cfg.score_kind != DSN_SCORE_DIT)
+    if ((needs & RAGGED_DIT) && cfg.score_kind != DSN_SCORE_DIT)
       fail(DSN_EINVAL, "%s: ragged batches need the DiT score network (NCSN++ convolves across time: padding would "
            "change an item's result)", who);
+    if ((needs & RAGGED_ENC) && !cfg.vae_has_encoder) fail(DSN_ESTATE, "%s: encoder not configured", who);
+    if ((needs & RAGGED_DEC) && !cfg.vae_has_decoder) fail(DSN_ESTATE, "%s: decoder not configured", who);
+    if ((needs & (RAGGED_ENC | RAGGED_DEC)) && !finalized) fail(DSN_ESTATE, "%s: weights not finalized", who);
+    // the tail launch of the ragged codec stores 16 bytes per lane: the waveform is cleared as rows of 8 samples
+    if ((needs & RAGGED_DEC) && hop() % 8 != 0)
+      fail(DSN_EINVAL, "%s: the ragged decoder needs a hop length that is a multiple of 8 (hop = %d)", who, hop());
+    if ((needs & (RAGGED_ENC | RAGGED_DEC)) && cfg.latent_dim % 8 != 0)
+      fail(DSN_EINVAL, "%s: the ragged codec needs a latent width that is a multiple of 8 (latent_dim = %d)", who,
+           cfg.latent_dim);
     for (int b = 0; b < B; ++b)
       if (frames[b] < 1 || frames[b] > T)
         fail(DSN_EINVAL, "%s: frame count frames[%d] = %d outside [1, T = %d]", who, b, (int)frames[b], T);
@@ -1411,6 +1449,17 @@ struct dsn_ctx {
     HIPCHK(hipStreamSynchronize(st));
     lens_host = h;
     lens_dev = d;
+    return d;
+  }
+  // the frame counts themselves into "codec_frames" (the codec's tail launches read them), outside any capture as well
+  const int* upload_frames(const int32_t* frames, int B, hipStream_t st) {
+    std::vector<int> h(frames, frames + B);
+    int* d = wsbuf<int>("codec_frames", B);
+    if (h == frames_host && d == frames_dev) return d;
+    HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    frames_host = h;
+    frames_dev = d;
     return d;
   }
   // Every step's time embedding in one batch, off the per-call path (-1.3 % sampler time).  time_cache is only
@@ -1627,7 +1676,8 @@ struct dsn_ctx {
     return h;
   }
   // est [S][Dl][T] (S = B*n) -> wav fp32 [S][hop*T] in ws "dec_wav"
-  float* decode(const float* est, int S, int T, hipStream_t st) {
+  // cl (null = dense): ragged batch, item s holds cl->frames[s / cl->rep] frames -- one tail_zero after every layer
+  float* decode(const float* est, int S, int T, hipStream_t st, const CodecLens* cl = nullptr) {
     if (!cfg.vae_has_decoder) fail(DSN_ESTATE, "decoder not configured");
     const int Dl = cfg.latent_dim;
     long maxel = (long)S * T * dec_in.N;
@@ -1644,7 +1694,9 @@ struct dsn_ctx {
     op16_t* ph = wsbuf<op16_t>("dec_ph", maxel * P);
     float* xf = wsbuf<float>("dec_x", maxel);
     launch_pack_tokens(est, Dl, nullptr, 0, S, T, nullptr, zp, (long)S * T * Dl, PL, st);
+    if (cl) tail_zero(*cl, zp, (long)S * T * Dl, nullptr, nullptr, S, T, Dl, 1, st);  // (est's padding holds anything)
     long L = T;
+    long mul = 1;  // rows per latent frame at the current level
     {
       Tag tg(this, "vae.dec_conv_in");
       GemmDesc d = base_desc(zp, (long)S * T * Dl, dec_in, S, T, T);
@@ -1654,6 +1706,7 @@ struct dsn_ctx {
       set_act(d, dec_blocks[0].act);
       run(d, st);
     }
+    if (cl) tail_zero(*cl, pa, (long)S * T * dec_in.N, nullptr, nullptr, S, T, dec_in.N, 1, st);
     long a_ps = (long)S * T * dec_in.N;
     for (size_t bi = 0; bi < dec_blocks.size(); ++bi) {
       const VaeBlock& b = dec_blocks[bi];
@@ -1676,10 +1729,12 @@ struct dsn_ctx {
         // the lean epilogue the default 256 x 256 x BK 64 tile wins again (6.2 vs 7.3 ms)
         run(d, st);
       }
+      mul *= b.stride;
+      if (cl) tail_zero(*cl, pb, o_ps, xf, nullptr, S, Lo, b.cout, mul, st);
       for (int j = 0; j < 3; ++j) {
         const ResUnit& r = b.ru[j];
         const ActP& next = j < 2 ? b.ru[j + 1].act0 : (bi + 1 < dec_blocks.size() ? dec_blocks[bi + 1].act : dec_final_act);
-        res_unit(r, pb, ph, o_ps, xf, j < 2, next, S, Lo, st);
+        res_unit(r, pb, ph, o_ps, xf, j < 2, next, S, Lo, st, cl, mul);
       }
       std::swap(pa, pb);
       a_ps = o_ps;
@@ -1690,17 +1745,22 @@ struct dsn_ctx {
       launch_conv_out1(pa, a_ps, PL, dec_out_w, wav, S, (int)L, dec_blocks.back().cout, dec_out_taps,
                        cfg.vae_final_tanh, st);
     });
+    if (cl) tail_zero(*cl, nullptr, 0, nullptr, wav, S, L / 8, 8, mul / 8, st);  // (rows of 8 samples: hop % 8 == 0)
     return wav;
   }
 
   // ---------------------------------------------------------------- encoder
   // wav [S][L] (L multiple of hop) + noise [S][Dl][T] -> y [S][Dl][T]
-  void encode(const float* wav, const float* noise, float* y, int S, int L, hipStream_t st) {
-    float* enc = encode_body(wav, S, L, st);
-    launch_vae_sample(enc, noise, y, S, cfg.latent_dim, L / hop(), st);
+  // cl (null = dense): ragged batch -- item s holds cl->frames[s] frames and its samples past them are zero;
+  // y[s, :, frames[s]:] is written as zero
+  void encode(const float* wav, const float* noise, float* y, int S, int L, hipStream_t st, const CodecLens* cl = nullptr) {
+    float* enc = encode_body(wav, S, L, st, cl);
+    if (cl) launch_vae_sample_ragged(enc, noise, cl->frames, y, S, cfg.latent_dim, L / hop(), st);
+    else launch_vae_sample(enc, noise, y, S, cfg.latent_dim, L / hop(), st);
   }
   // wav [S][L] -> encoder output (mean ++ scale) channels-last [S][L/hop][2*Dl] in ws "enc_out"
-  float* encode_body(const float* wav, int S, int L, hipStream_t st) {
+  // cl: as in encode -- one tail_zero after every layer
+  float* encode_body(const float* wav, int S, int L, hipStream_t st, const CodecLens* cl = nullptr) {
     if (!cfg.vae_has_encoder) fail(DSN_ESTATE, "encoder not configured");
     const int Dl = cfg.latent_dim, c0 = cfg.vae_channels;
     long maxel = (long)S * L * c0;
@@ -1721,12 +1781,14 @@ struct dsn_ctx {
       const ActP& a = enc_blocks[0].ru[0].act0;
       launch_conv_in1(wav, enc_in_w, enc_in_b, S, L, c0, 7, xf, pa, a_ps, PL, a.kind, a.a, a.ib, st);
     }
+    long mul = hop();  // rows per latent frame at the current level
+    if (cl) tail_zero(*cl, pa, a_ps, xf, nullptr, S, l, c0, mul, st);
     for (size_t bi = 0; bi < enc_blocks.size(); ++bi) {
       const VaeBlock& b = enc_blocks[bi];
       for (int j = 0; j < 3; ++j) {
         const ResUnit& r = b.ru[j];
         const ActP& next = j < 2 ? b.ru[j + 1].act0 : b.act;
-        res_unit(r, pa, ph, a_ps, xf, j < 2, next, S, l, st);
+        res_unit(r, pa, ph, a_ps, xf, j < 2, next, S, l, st, cl, mul);
       }
       const long lo = l / b.stride;
       const long o_ps = (long)S * lo * b.cout;
@@ -1745,6 +1807,8 @@ struct dsn_ctx {
         }
         run(d, st);
       }
+      mul /= b.stride;
+      if (cl) tail_zero(*cl, pb, o_ps, bi + 1 < enc_blocks.size() ? xf : nullptr, nullptr, S, lo, b.cout, mul, st);
       std::swap(pa, pb);
       a_ps = o_ps;
       l = lo;
@@ -1757,6 +1821,7 @@ struct dsn_ctx {
       d.out_f32 = enc;
       run(d, st);
     }
+    if (cl) tail_zero(*cl, nullptr, 0, nullptr, enc, S, l, enc_out.N, mul, st);
     if (enc_out.N != 2 * Dl) fail(DSN_EINVAL, "encoder latent %d != 2*latent_dim %d", enc_out.N, 2 * Dl);
     return enc;
   }
@@ -2520,6 +2585,70 @@ int dsn_separate(dsn_ctx* ctx, const float* mix, const float* vae_noise, const f
   if ((rc = dsn_pc_sample(ctx, y, noise, seed + 1, x, B, T, N, corrector_steps, snr, t_eps, denoise, nfe_out, stream)))
     return rc;
   return dsn_decode(ctx, x, wav, B, T, target_len > 0 ? target_len : L, stream);
+}
+
+// Ragged batches through the codec in one padded pass (include/ditsep_hip.h).  Every refusal comes from check_frames,
+// before the workspace is touched.
+int dsn_decode_ragged(dsn_ctx* ctx, const float* est, const int32_t* frames, float* wav, int B, int T, void* stream) {
+  return guarded(ctx, [&] {
+    if (!est || !wav || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_decode_ragged: bad arguments");
+    ctx->check_frames("dsn_decode_ragged", frames, B, T, dsn_ctx::RAGGED_DEC);
+    const int S = B * ctx->cfg.n_src;
+    const long Lfull = (long)ctx->hop() * T;
+    const long esz = (long)S * ctx->cfg.latent_dim * T;
+    float* eb = ctx->wsbuf<float>("dec_est", esz);
+    const dsn_ctx::CodecLens cl{ctx->upload_frames(frames, B, (hipStream_t)stream), frames, ctx->cfg.n_src};
+    dsn_ctx::StreamScope sc(ctx, (hipStream_t)stream, 1);
+    HIPCHK(hipMemcpyAsync(eb, est, sizeof(float) * esz, hipMemcpyDeviceToDevice, sc.st));
+    float* w = nullptr;
+    char key[64];
+    snprintf(key, sizeof key, "decr:%d:%d", S, T);  // (the lengths are data of the graph, not part of its key)
+    ctx->run_graphed(key, sc.st, [&](hipStream_t s2) { w = ctx->decode(eb, S, T, s2, &cl); });
+    if (!w) w = ctx->wsbuf<float>("dec_wav", (long)S * Lfull);
+    HIPCHK(hipMemcpyAsync(wav, w, sizeof(float) * S * Lfull, hipMemcpyDeviceToDevice, sc.st));
+    sc.leave();
+  });
+}
+
+int dsn_encode_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise, uint64_t seed,
+                      float* y, int B, int T, void* stream) {
+  return guarded(ctx, [&] {
+    if (!mix || !y || B <= 0 || T <= 0) fail(DSN_EINVAL, "dsn_encode_ragged: bad arguments");
+    ctx->check_frames("dsn_encode_ragged", frames, B, T, dsn_ctx::RAGGED_ENC);
+    hipStream_t st = (hipStream_t)stream;
+    const long Lp = (long)ctx->hop() * T;
+    if (!vae_noise) {  // (the dense call's stream: stage_encode)
+      const long nsz = (long)B * ctx->cfg.latent_dim * T;
+      float* nz = ctx->wsbuf<float>("enc_noise", nsz);
+      launch_randn(nz, nsz, seed ^ 0x5851F42D4C957F2DULL, 0, st);
+      vae_noise = nz;
+    }
+    const dsn_ctx::CodecLens cl{ctx->upload_frames(frames, B, st), frames, 1};
+    ctx->encode(mix, vae_noise, y, B, (int)Lp, st, &cl);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dsn_separate_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise, const float* noise,
+                        uint64_t seed, float* wav, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out,
+                        void* stream) {
+  float* y = nullptr;
+  float* x = nullptr;
+  int rc = guarded(ctx, [&] {
+    if (!mix || !wav || !opts || B <= 0 || T <= 0 || N <= 0) fail(DSN_EINVAL, "dsn_separate_ragged: bad arguments");
+    ctx->check_frames("dsn_separate_ragged", frames, B, T,
+                      dsn_ctx::RAGGED_DIT | dsn_ctx::RAGGED_ENC | dsn_ctx::RAGGED_DEC);
+    if (opts->corrector == DSN_CORR_LANGEVIN)
+      fail(DSN_EINVAL, "dsn_separate_ragged: the langevin corrector (DSN_CORR_LANGEVIN) has no ragged form: its "
+           "per-item norms would run over the padding");
+    const long ysz = (long)B * ctx->cfg.latent_dim * T;
+    y = ctx->wsbuf<float>("sep_y", ysz);
+    x = ctx->wsbuf<float>("sep_x", ysz * ctx->cfg.n_src);
+  });
+  if (rc) return rc;
+  if ((rc = dsn_encode_ragged(ctx, mix, frames, vae_noise, seed, y, B, T, stream))) return rc;
+  if ((rc = dsn_pc_sample_ragged(ctx, y, frames, noise, seed + 1, x, B, T, N, opts, nfe_out, stream))) return rc;
+  return dsn_decode_ragged(ctx, x, frames, wav, B, T, stream);
 }
 
 // Scale-invariant SDR with permutation-invariant assignment (the step right after the path in
@@ -3453,6 +3582,23 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
           fail(DSN_EINVAL, "test_kernel vae_sample: B, D, T must be positive (B=%d D=%d T=%d)", t->B, t->D, t->T);
         if (!t->x || !t->z || !t->out_f32) fail(DSN_EINVAL, "test_kernel vae_sample: x (encoder output), z or out_f32 missing");
         launch_vae_sample(t->x, t->z, t->out_f32, t->B, t->D, t->T, st);
+        break;
+      }
+      case DSN_TK_CODEC_TAIL_ZERO: {
+        if (t->B < 1 || t->L < 1 || t->rep < 1 || t->mul < 1 || !t->lens)
+          fail(DSN_EINVAL, "test_kernel codec_tail_zero: B, L, rep, mul must be positive and lens (the frame counts) given");
+        if (oplanes && t->out_ps < (long)t->B * t->L * t->C)
+          fail(DSN_EINVAL, "test_kernel codec_tail_zero: out_ps %ld < B*L*C", (long)t->out_ps);
+        std::vector<int32_t> h((size_t)cdiv(t->B, t->rep));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(h.data(), t->lens, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < h.size(); ++i)
+          if (h[i] < 0 || (long)h[i] * t->mul > t->L)
+            fail(DSN_EINVAL, "test_kernel codec_tail_zero: frames[%d] = %d: %ld rows outside [0, L = %d]", (int)i,
+                 (int)h[i], (long)h[i] * t->mul, t->L);
+        const char* why = launch_codec_tail_zero(oplanes, t->out_ps, P, t->x, t->out_f32, t->B, t->L, t->C,
+                                                 reinterpret_cast<const int*>(t->lens), t->rep, t->mul, st);
+        if (why) fail(DSN_EINVAL, "test_kernel codec_tail_zero: %s (C=%d)", why, t->C);
         break;
       }
       case DSN_TK_RANDN:

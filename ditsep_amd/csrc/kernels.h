@@ -81,6 +81,20 @@ void launch_conv_in1(const float* wav, const float* w, const float* bias, int S,
 // VAE bottleneck sample: enc fp32 token-major [S*T][2*D] (mean | scale) + noise [S][D][T] -> y [S][D][T]
 void launch_vae_sample(const float* enc_tok, const float* noise, float* y, int S, int D, int T, hipStream_t s);
 
+// ---- ragged batches through the codec (codec_ragged.hip) -------------------------------------------
+// Item s of S items padded to L rows of C channels ([S][L][C] row-major) has frames[s / rep] * mul valid rows: frames
+// (device, int [ceil(S / rep)]) counts latent frames, rep items share an entry (the n_src sources of a mixture on the
+// decoder side, 1 on the encoder side), mul is the level's rows per latent frame.  Rows [valid, L) of the item are
+// written as zero in each of the n_planes operand planes (plane stride ps), in the fp32 stream xf and in the plain fp32
+// output `out`; any of the three may be null.  Only tail rows are touched: an item with valid == L is left alone.  The
+// grid depends on (S, L, C) alone, so a captured launch serves every set of lengths.  16-byte stores: C % 8 == 0 and
+// 16-byte aligned destinations.  Returns null, or the reason the arguments were refused (nothing was launched).
+const char* launch_codec_tail_zero(op16_t* planes, long ps, int n_planes, float* xf, float* out, int S, int L, int C,
+                                   const int* frames, int rep, int mul, hipStream_t s);
+// launch_vae_sample with y[s, :, t] = 0 for t >= frames[s] (device, int [S])
+void launch_vae_sample_ragged(const float* enc_tok, const float* noise, const int* frames, float* y, int S, int D, int T,
+                              hipStream_t s);
+
 // ---- RNG ------------------------------------------------------------------------
 // Philox4x32-10 + Box-Muller standard normals
 void launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t s);

@@ -49,19 +49,21 @@ def _same_length_groups(lengths) -> dict:
     return groups
 
 
-def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended) -> dict:
+def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended,
+                     codec="grouped") -> dict:
     """One batch of differently long utterances: mixes list of [1, L_b], targets list of [n, L_b].  The timed region is
-    sampler + decode as in the dense route; the metric kernels run per group of equal L."""
+    sampler + decode as in the dense route; the metric kernels run per group of equal L.  codec: how the encoder and
+    the decoder take the batch (Engine.encode_ragged)."""
     eng, dev = model.engine, model.engine.device
     B = len(mixes)
-    y, frames = eng.encode_ragged(mixes, None, seed=seed + idx)
+    y, frames = eng.encode_ragged(mixes, None, seed=seed + idx, codec=codec)
     sampler = model.get_pc_sampler("reverse_diffusion", "ald", y, N=N, denoise=denoise, corrector_steps=corrector_steps,
                                    snr=snr, seed=seed + idx, frames=frames)
     lens = [int(t.shape[-1]) for t in targets]
     torch.cuda.synchronize(dev)
     t_s = time.perf_counter()
     x_result, nfe = sampler()
-    est = eng.decode_ragged(x_result, frames, lens)
+    est = eng.decode_ragged(x_result, frames, lens, codec=codec)
     torch.cuda.synchronize(dev)
     t_proc = time.perf_counter() - t_s
     records = {}
@@ -81,7 +83,7 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
                      stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False,
-                     composite: bool = False, pesq_fn=None, mrstft: bool = False) -> dict:
+                     composite: bool = False, pesq_fn=None, mrstft: bool = False, codec: str = "grouped") -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
     with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
     adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
@@ -94,7 +96,10 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     A batch may also be (list of mix [1,L_b], list of target [n,L_b]) with differing L_b: it takes the ragged route
     (one sampler call on the padded batch, codec and metric kernels per group of equal length); each record carries
     its own "len_s", "runtime" stays the batch time divided by B.  score_loss, composite and mrstft have no ragged
-    form (NotImplementedError)."""
+    form (NotImplementedError).  codec="padded" runs the codec of a ragged batch once on the padded batch instead of
+    once per group (Engine.encode_ragged / decode_ragged); dense batches ignore it."""
+    from .native import check_codec_mode
+    check_codec_mode(codec)
     if pesq_fn is not None and not composite:
         raise ValueError("pesq_fn is used by composite=True only")
     cfg_s = dict(getattr(model, "config", {}).get("model", {}).get("sampler", {})) if isinstance(getattr(model, "config", None), dict) else {}
@@ -108,7 +113,7 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
             if score_loss or composite or mrstft:
                 raise NotImplementedError("score_loss / composite / mrstft are not implemented for ragged batches")
             results.update(_evaluate_ragged(model, list(mix), list(target), fs, idx, seed, N, corrector_steps, snr,
-                                            denoise, stoi, stoi_extended))
+                                            denoise, stoi, stoi_extended, codec=codec))
             idx += len(mix)
             continue
         mix, target = mix.to(dev), target.to(dev)

@@ -317,25 +317,28 @@ class LatentDiffSep:
         return (est, *others)
 
     @torch.no_grad()
-    def separate_batch(self, mixes, target_dims=None, **sampler_kwargs):
+    def separate_batch(self, mixes, target_dims=None, codec="grouped", **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
         batch padded to the longest item with the score network masking each item's keys at its own length.
-        Keywords as `separate` (seed, vae_noise: list of [D, T_b], noise [draws,B,n,D,Tmax], N, snr, ...)."""
+        Keywords as `separate` (seed, vae_noise: list of [D, T_b], noise [draws,B,n,D,Tmax], N, snr, ...).
+        codec="padded": encoder and decoder run once on the padded batch as well (Engine.encode_ragged /
+        decode_ragged); per item the same result up to summation order, other device-RNG VAE draws."""
         eng = self.engine
+        native.check_codec_mode(codec)
         native.check_ragged(eng.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
         kwargs = dict(sampler_kwargs)
         seed = kwargs.get("seed")
         enc_seed = int(torch.randint(0, 2**31 - 1, (1,)).item()) if seed is None else int(seed)
-        y, frames = eng.encode_ragged(mixes, kwargs.pop("vae_noise", None), seed=enc_seed)
+        y, frames = eng.encode_ragged(mixes, kwargs.pop("vae_noise", None), seed=enc_seed, codec=codec)
         self.max_len_lat = max(self.max_len_lat, y.shape[-1])
         skw = dict(_get(self.config, "model.sampler", {}) or {})
         skw.update(kwargs)
         sampler = self.get_pc_sampler("reverse_diffusion", "ald", y, frames=frames, **skw)
         est, *others = sampler()
         dims = [int(m.shape[-1]) for m in mixes] if target_dims is None else list(target_dims)
-        return (eng.decode_ragged(est, frames, dims), *others)
+        return (eng.decode_ragged(est, frames, dims, codec=codec), *others)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -27,7 +27,8 @@ MAX_VAE_BLOCKS = 8
 
 EXPORTS = [
     "dsn_create", "dsn_destroy", "dsn_last_error", "dsn_load_tensor", "dsn_finalize_weights", "dsn_finalize_weights_ex",
-    "dsn_score", "dsn_score_ragged", "dsn_pc_sample_ragged", "dsn_ouve_schedule", "dsn_pc_sample", "dsn_pc_sample_sched", "dsn_pc_sample_ex", "dsn_pc_sample_mix", "dsn_sb_sample", "dsn_decode",
+    "dsn_score", "dsn_score_ragged", "dsn_pc_sample_ragged", "dsn_decode_ragged", "dsn_encode_ragged",
+    "dsn_separate_ragged", "dsn_ouve_schedule", "dsn_pc_sample", "dsn_pc_sample_sched", "dsn_pc_sample_ex", "dsn_pc_sample_mix", "dsn_sb_sample", "dsn_decode",
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows",
@@ -148,7 +149,7 @@ TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn
                      "conv_out1": 7, "conv_in1": 8, "ru_fused": 9,
                      "pc_prior": 10, "pc_corrector": 11, "pc_item_norms": 12, "pc_predictor": 13, "sigma_mix": 14,
                      "mix_prior": 15, "mix_corrector": 16, "mix_predictor": 17, "sb_update": 18, "repeat_sources": 19,
-                     "vae_sample": 20, "randn": 21, "rand_uniform": 22}
+                     "vae_sample": 20, "randn": 21, "rand_uniform": 22, "codec_tail_zero": 23}
 
 
 class DsnTestKernel(C.Structure):
@@ -178,6 +179,7 @@ class DsnTestKernel(C.Structure):
         ("y", C.c_void_p), ("score", C.c_void_p), ("z", C.c_void_p), ("smix", C.c_void_p), ("norms", C.c_void_p),
         ("xmean", C.c_void_p),
         ("lens", C.c_void_p),
+        ("rep", C.c_int), ("mul", C.c_int),
     ]
 
 
@@ -203,11 +205,50 @@ def frame_groups(frames) -> dict:
     return groups
 
 
-def check_ragged(score_kind: int, frames, B: int, T: int, corrector: str = "ald") -> list:
+CODEC_MODES = ("grouped", "padded")
+
+
+def check_codec_mode(codec: str) -> str:
+    """codec= of the ragged entry points: "grouped" (one codec call per group of equal frame count) or "padded" (one
+    pass over the padded batch, dsn_decode_ragged / dsn_encode_ragged)."""
+    if codec not in CODEC_MODES:
+        raise ValueError(f"codec must be one of {CODEC_MODES} (got {codec!r})")
+    return codec
+
+
+def codec_level_rows(strides, side: str) -> list:
+    """Rows per latent frame (`mul` of the tail launch) of every level of a ragged codec pass, in launch order.
+    "decoder": the latent (1), then the output of each up-sampling block, the product of the strides so far in the
+    decoder's order (the reversed `strides`); the last entry is the hop length, the waveform.  "encoder": the waveform
+    level (hop), then the output of each down-sampling block, hop divided by the product so far; the last entry is 1."""
+    st = [int(v) for v in strides]
+    if side == "decoder":
+        out = [1]
+        for v in reversed(st):
+            out.append(out[-1] * v)
+        return out
+    if side != "encoder":
+        raise ValueError(f"side must be 'decoder' or 'encoder' (got {side!r})")
+    out = [math.prod(st)]
+    for v in st:
+        out.append(out[-1] // v)
+    return out
+
+
+def codec_valid_rows(frames, rep: int, mul: int, S: int) -> list:
+    """Valid rows of each of the S codec items at a level: frames[s // rep] * mul (rep = n_src in the decoder, whose
+    S = B * n_src items share their mixture's length; 1 in the encoder)."""
+    if rep < 1 or mul < 1 or S != len(frames) * rep:
+        raise ValueError(f"S = {S} items need S / rep = {S / max(rep, 1):g} frame counts with rep, mul >= 1 "
+                         f"(got {len(frames)} counts, rep = {rep}, mul = {mul})")
+    return [int(frames[s // rep]) * mul for s in range(S)]
+
+
+def check_ragged(score_kind: int, frames, B: int, T: int, corrector: str = "ald", need_dit: bool = True) -> list:
     """The refusals of the ragged entry points (include/ditsep_hip.h), raised by name before the library is touched:
-    a score network other than the DiT, a frame count outside [1, T] (or not one per item), the langevin corrector.
-    Returns the frame counts as a list of ints."""
-    if score_kind != SCORE_DIT:
+    a score network other than the DiT (need_dit: the score call and the samplers, not the codec), a frame count
+    outside [1, T] (or not one per item), the langevin corrector.  Returns the frame counts as a list of ints."""
+    if need_dit and score_kind != SCORE_DIT:
         raise ValueError("ragged batches need the DiT score network: NCSN++ convolves across time, so padding would "
                          "change an item's result")
     fr = [int(f) for f in frames]
@@ -248,6 +289,10 @@ def load_library() -> C.CDLL:
     lib.dsn_score_ragged.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, vp]
     lib.dsn_pc_sample_ragged.argtypes = [vp, vp, C.POINTER(C.c_int32), vp, C.c_uint64, vp, ci, ci, ci,
                                          C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
+    lib.dsn_decode_ragged.argtypes = [vp, vp, C.POINTER(C.c_int32), vp, ci, ci, vp]
+    lib.dsn_encode_ragged.argtypes = [vp, vp, C.POINTER(C.c_int32), vp, C.c_uint64, vp, ci, ci, vp]
+    lib.dsn_separate_ragged.argtypes = [vp, vp, C.POINTER(C.c_int32), vp, vp, C.c_uint64, vp, ci, ci, ci,
+                                        C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
     lib.dsn_ouve_schedule.argtypes = [vp, ci, cf, cf, fp, fp, fp, fp, fp, fp]
     lib.dsn_pc_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, ci, cf, cf, ci, C.POINTER(ci), vp]
     lib.dsn_pc_sample_sched.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, ci, fp, ci, cf, ci, C.POINTER(ci), vp]
@@ -681,12 +726,40 @@ class Engine:
         return wav, nfe.value
 
     # ------------------------------------------------------------------ ragged batches
-    def encode_ragged(self, mixes, vae_noise=None, seed=0):
+    def _padded_mixes(self, mixes, vae_noise):
+        """-> (mix [B,1,hop*Tmax] zero past each item, vae noise [B,D,Tmax] or None, frames, lengths)"""
+        hop = self.hop_length
+        lens = [int(m.shape[-1]) for m in mixes]
+        frames = [latent_frames_of(L, hop) for L in lens]
+        B, Tmax = len(mixes), max(frames)
+        mix = torch.zeros((B, 1, hop * Tmax), device=self.device, dtype=torch.float32)
+        for b, m in enumerate(mixes):
+            mix[b, 0, :lens[b]] = _dev32(m, self.device).reshape(-1)
+        vn = None
+        if vae_noise is not None:
+            vn = torch.zeros((B, self.latent_dim, Tmax), device=self.device, dtype=torch.float32)
+            for b, v in enumerate(vae_noise):
+                if tuple(v.shape) != (self.latent_dim, frames[b]):
+                    raise ValueError(f"vae_noise[{b}] must be {(self.latent_dim, frames[b])}, got {tuple(v.shape)}")
+                vn[b, :, :frames[b]] = _dev32(v, self.device)
+        return mix, vn, frames, lens
+
+    def encode_ragged(self, mixes, vae_noise=None, seed=0, codec="grouped"):
         """mixes: list of [1, L_b] mixtures of different lengths -> (y [B,1,D,Tmax] zero beyond each item's frames,
-        frames).  Items are grouped by T_b = latent_frames(L_b); each item of a group is zero-extended to
-        T_b * hop - 1 samples (ragged_extended_length) and the group is encoded by one `encode` call, which is what
-        each item gets alone.  vae_noise: list of [D, T_b] (not extended with the samples); absent: group g draws
-        with seed + g."""
+        frames), T_b = latent_frames(L_b).  vae_noise: list of [D, T_b] (not extended with the samples).
+        codec="grouped" (default): items are grouped by T_b; each item of a group is zero-extended to T_b * hop - 1
+        samples (ragged_extended_length) and the group is encoded by one `encode` call, which is what each item gets
+        alone; without vae_noise group g draws with seed + g.
+        codec="padded": every item is zero-extended to Tmax * hop samples and the batch is encoded in one pass
+        (dsn_encode_ragged): the same result per item up to summation order; without vae_noise the draws are indexed by
+        position in the padded tensor -- a valid sample, but not the one the grouped mode draws for that seed."""
+        if check_codec_mode(codec) == "padded":
+            mix, vn, frames, _ = self._padded_mixes(mixes, vae_noise)
+            B, Tmax = len(frames), max(frames)
+            y = torch.empty((B, 1, self.latent_dim, Tmax), device=self.device, dtype=torch.float32)
+            self._check(self.lib.dsn_encode_ragged(self.ctx, _ptr(mix), (C.c_int32 * B)(*frames), _ptr(vn), seed,
+                                                   _ptr(y), B, Tmax, self._stream()), "dsn_encode_ragged")
+            return y, frames
         hop = self.hop_length
         lens = [int(m.shape[-1]) for m in mixes]
         frames = [latent_frames_of(L, hop) for L in lens]
@@ -701,9 +774,21 @@ class Engine:
             y[idx, :, :, :Tb] = self.encode(grp, vn, seed=seed + g)
         return y, frames
 
-    def decode_ragged(self, x, frames, target_lens):
-        """x [B,n,D,Tmax], frames and target_lens per item -> list of [n, L_b]: one `decode` per group of equal frame
-        count on x[group][..., :T_b], each item cropped to its length."""
+    def decode_ragged(self, x, frames, target_lens, codec="grouped"):
+        """x [B,n,D,Tmax], frames and target_lens per item -> list of [n, L_b], each item cropped to its length.
+        codec="grouped" (default): one `decode` per group of equal frame count on x[group][..., :T_b].
+        codec="padded": one pass over the padded batch (dsn_decode_ragged); x's padded region may hold anything
+        finite."""
+        if check_codec_mode(codec) == "padded":
+            B, n, D, T = x.shape
+            if n != self.n_src or D != self.latent_dim:
+                raise ValueError(f"x must be [B,{self.n_src},{self.latent_dim},T], got {tuple(x.shape)}")
+            fr = check_ragged(self.cfg.score_kind, frames, B, T, need_dit=False)
+            x = _dev32(x, self.device)
+            wav = torch.empty((B, n, self.hop_length * T), device=self.device, dtype=torch.float32)
+            self._check(self.lib.dsn_decode_ragged(self.ctx, _ptr(x), (C.c_int32 * B)(*fr), _ptr(wav), B, T,
+                                                   self._stream()), "dsn_decode_ragged")
+            return [wav[b, :, :int(target_lens[b])] for b in range(B)]
         x = _dev32(x, self.device)
         out = [None] * x.shape[0]
         for Tb, idx in frame_groups(frames).items():
@@ -713,12 +798,31 @@ class Engine:
         return out
 
     def separate_ragged(self, mixes, *, vae_noise=None, noise=None, seed=0, N=30, corrector_steps=1, snr=0.5,
-                        t_eps=0.03, denoise=True):
-        """Mixtures of different lengths in one batch: list of [1, L_b] -> (list of [n, L_b], nfe).  The codec runs
-        per group of equal frame count, the sampler once on the padded batch (pc_sample with frames).  noise
-        [draws,B,n,D,Tmax]: item b consumes noise[..., :frames[b]]."""
+                        t_eps=0.03, denoise=True, codec="grouped"):
+        """Mixtures of different lengths in one batch: list of [1, L_b] -> (list of [n, L_b], nfe).  The sampler runs
+        once on the padded batch (pc_sample with frames).  noise [draws,B,n,D,Tmax]: item b consumes
+        noise[..., :frames[b]].  codec="grouped" (default): the codec runs per group of equal frame count.
+        codec="padded": encoder, sampler and decoder each run once on the padded batch, in one library call
+        (dsn_separate_ragged); with the device RNG the encoder draws with `seed` and the sampler with seed + 1, as
+        dsn_separate does."""
         # (refused before anything is encoded)
+        check_codec_mode(codec)
         check_ragged(self.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
+        if codec == "padded":
+            mix, vn, frames, lens = self._padded_mixes(mixes, vae_noise)
+            B, Tmax = len(frames), max(frames)
+            nz = None if noise is None else _dev32(noise, self.device)
+            draws = 1 + N * (corrector_steps + 1)
+            if nz is not None and tuple(nz.shape) != (draws, B, self.n_src, self.latent_dim, Tmax):
+                raise ValueError(f"noise must be {(draws, B, self.n_src, self.latent_dim, Tmax)}, got {tuple(nz.shape)}")
+            wav = torch.empty((B, self.n_src, self.hop_length * Tmax), device=self.device, dtype=torch.float32)
+            o = DsnSamplerOpts(PREDICTORS["reverse_diffusion"], CORRECTORS["ald"], int(corrector_steps), float(snr),
+                               float(t_eps), int(denoise), None, None, None)
+            nfe = C.c_int()
+            self._check(self.lib.dsn_separate_ragged(self.ctx, _ptr(mix), (C.c_int32 * B)(*frames), _ptr(vn), _ptr(nz),
+                                                     seed, _ptr(wav), B, Tmax, N, C.byref(o), C.byref(nfe),
+                                                     self._stream()), "dsn_separate_ragged")
+            return [wav[b, :, :lens[b]] for b in range(B)], nfe.value
         y, frames = self.encode_ragged(mixes, vae_noise, seed=seed)
         x, nfe = self.pc_sample(y, noise, N=N, corrector_steps=corrector_steps, snr=snr, t_eps=t_eps, denoise=denoise,
                                 seed=seed, frames=frames)

@@ -154,13 +154,43 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
  * DSN_EINVAL, by name and before any launch: a score network other than the DiT (NCSN++ convolves across time, so
  * padding changes an item's result); a frame count outside [1, T]; DSN_CORR_LANGEVIN (its per-item norms would run
  * over the padding).  The Mix / PriorMix, Schroedinger-bridge and ODE samplers and dsn_score_loss have no ragged form:
- * each reduces over the latent or couples the batch.  The codec has none either (its convolutions see an item's end):
- * encode and decode run per group of equal frame count.  Under dsn_enable_graphs the lengths are data of the captured
- * graph, not part of its key: one graph per (B, T, options) serves every set of lengths. */
+ * each reduces over the latent or couples the batch.  The codec's ragged form is the block below.  Under
+ * dsn_enable_graphs the lengths are data of the captured graph, not part of its key: one graph per (B, T, options)
+ * serves every set of lengths. */
 int dsn_score_ragged(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
                      int B, int T, void* stream);
 int dsn_pc_sample_ragged(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
                          float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream);
+
+/* Ragged batches through the codec (either score network, or none): B items of different lengths in tensors padded to
+ * the longest, T latent frames, coded in ONE pass.  frames [B] (HOST int32) as above.  The codec's convolutions reach
+ * across time, so between two layers the engine writes every item's rows past its own end as zero (one small launch
+ * per layer, call site "vae.ragged_tail_zero"): each convolution then reads past an item's end what it reads for the
+ * item alone, its zero padding, and item b's result over its valid range is what the item gets in a call of its own
+ * with T = frames[b], up to the summation order of a split-K layer.  No convolution kernel knows about lengths; the
+ * padded rows are computed and discarded.
+ *   dsn_decode_ragged    est [B,n_src,D,T] -> wav [B,n_src,hop*T].  The padded region of est may hold anything finite.
+ *                        wav[b, :, hop*frames[b]:] is written as zero; cropping to each item's sample count stays with
+ *                        the caller.
+ *   dsn_encode_ragged    mix [B,1,hop*T] -> y [B,1,D,T].  Item b's samples must be ZERO past its own length (the caller
+ *                        zero-extends every item to hop*T samples) and frames[b] = dsn_latent_frames of that length.
+ *                        vae_noise [B,D,T] or NULL: item b consumes vae_noise[b, :, :frames[b]].  y[b, :, :, frames[b]:]
+ *                        is written as zero.  With the on-device RNG (vae_noise == NULL) an item's draws are indexed by
+ *                        its position in the padded tensor: the result is a valid sample, but NOT the sample the item
+ *                        alone would draw for that seed.
+ *   dsn_separate_ragged  dsn_encode_ragged (seed), dsn_pc_sample_ragged (seed + 1, as dsn_separate), dsn_decode_ragged in
+ *                        one call: mix [B,1,hop*T] -> wav [B,n_src,hop*T].  DiT only, with dsn_pc_sample_ragged's
+ *                        refusals.
+ * DSN_EINVAL / DSN_ESTATE, by name and before any launch or workspace growth: a frame count outside [1, T]; a missing
+ * encoder or decoder; a hop length (decode) or latent width that is not a multiple of 8 (the tail launch stores 16
+ * bytes per lane).  Under dsn_enable_graphs dsn_decode_ragged is captured once per (B, T), as dsn_decode is; the
+ * lengths are data of the graph.  The encoder runs eagerly, as in dsn_encode. */
+int dsn_decode_ragged(dsn_ctx* ctx, const float* est, const int32_t* frames, float* wav, int B, int T, void* stream);
+int dsn_encode_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise, uint64_t seed,
+                      float* y, int B, int T, void* stream);
+int dsn_separate_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise, const float* noise,
+                        uint64_t seed, float* wav, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out,
+                        void* stream);
 
 /* The secondary SDE family of the reference's sampler package on the latent state read as [B, n_src, D*T]:
  * MixSDE (sdes.py:182-352) / PriorMixSDE (:355-593; diffusion scaled by the running RMS of the mixture over `avg_len`
@@ -457,13 +487,13 @@ enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3,
        DSN_TK_PC_PRIOR = 10, DSN_TK_PC_CORRECTOR = 11, DSN_TK_PC_ITEM_NORMS = 12, DSN_TK_PC_PREDICTOR = 13,
        DSN_TK_SIGMA_MIX = 14, DSN_TK_MIX_PRIOR = 15, DSN_TK_MIX_CORRECTOR = 16, DSN_TK_MIX_PREDICTOR = 17,
        DSN_TK_SB_UPDATE = 18, DSN_TK_REPEAT_SOURCES = 19, DSN_TK_VAE_SAMPLE = 20, DSN_TK_RANDN = 21,
-       DSN_TK_RAND_UNIFORM = 22 };
+       DSN_TK_RAND_UNIFORM = 22, DSN_TK_CODEC_TAIL_ZERO = 23 };
 typedef struct DsnTestKernel {
   int kind;                   /* DSN_TK_* */
   /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
    * QKV_ATTENTION: a = LayerNorm output [B*S][D], w = to_qkv [3*D][D], bias [3*D] (optional), rope_cos / rope_sin
    *   [S][32] caller-owned buffers that launch_rope_tables fills here, ipp items per panel; q scale 1/8
-   * both: `lens` (last field; device int32 [B], 1 <= lens[b] <= S, checked here) runs the length-aware variant */
+   * both: `lens` (device int32 [B], 1 <= lens[b] <= S, checked here) runs the length-aware variant */
   int B, S, H, dh, D, ipp;
   /* RESIDUAL_NORM: x [rows][D] (updated in place), slabs nslab x slab_stride, bias / gamma / beta [D] */
   int rows, nslab, do_norm;
@@ -522,6 +552,9 @@ typedef struct DsnTestKernel {
    *   REPEAT_SOURCES y -> x
    *   VAE_SAMPLE     x = encoder output [B][T][2 D] (mean ++ scale), z = noise [B,D,T] -> out_f32 [B,D,T]
    *   RANDN, RAND_UNIFORM  count values of the stream (seed, offset) -> out_f32; RAND_UNIFORM: lo, hi
+   *   CODEC_TAIL_ZERO  launch_codec_tail_zero on B items of L rows of C channels: lens = frames (device int32
+   *                  [ceil(B / rep)], 0 <= frames * mul <= L checked here), rep, mul; destinations out_planes (the engine's
+   *                  plane count, out_ps apart), x (the fp32 stream) and out_f32, each [B][L][C], any of them null
    * Refused by name before any launch: a missing tensor, a non-positive B, n, D, T, L or count, avg_len < 1, and
    * n > 4 for the three MIX_* kernels (they hold the sources of a position in four-element arrays). */
   int n, T, avg_len, em, mean_full, third_is_y;
@@ -534,7 +567,8 @@ typedef struct DsnTestKernel {
   const float* smix;
   const float* norms;
   float* xmean;
-  const int32_t* lens;        /* ATTENTION / QKV_ATTENTION: valid tokens per item (null: dense) */
+  const int32_t* lens;        /* ATTENTION / QKV_ATTENTION: valid tokens per item (null: dense); CODEC_TAIL_ZERO: frames */
+  int rep, mul;               /* CODEC_TAIL_ZERO */
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 

@@ -1,6 +1,9 @@
 """Time the separation of mixtures of different lengths (full-size DiT and Oobleck, fp16, graphs on): `--items` mixtures
 with lengths drawn once (seeded) uniformly between 2 s and 4 s at 16 kHz,
-  ragged   Engine.separate_ragged on the whole batch in the order evaluate.length_batches gives,
+  ragged_grouped / ragged_padded   Engine.separate_ragged on the whole batch in the order evaluate.length_batches
+           gives, with the codec once per group of equal frame count (codec="grouped") or once on the padded batch
+           (codec="padded"); for each also the codec alone (encode_ragged + decode_ragged of a latent of the same shape)
+           and its share of the call,
   single   the same mixtures one Engine.separate call each,
   dense    a dense batch of as many 4 s mixtures (Engine.separate): the upper bound.
 HIP events around whole calls after a warm-up that lets every shape's graph be captured; the median of the repeated
@@ -74,8 +77,17 @@ def main():
     frames = [eng.latent_frames(m.shape[-1]) for m in mixes]
     kw = dict(N=N_STEPS, corrector_steps=CORR, snr=SNR, t_eps=T_EPS, seed=7)
 
-    def ragged():
-        eng.separate_ragged(mixes, **kw)
+    lens = [int(m.shape[-1]) for m in mixes]
+    lat = 0.5 * torch.randn((B, dcfg.n_src, dcfg.latent_dim, max(frames)), device=dev)     # stands in for the sampler's output
+
+    def ragged(mode):
+        return lambda: eng.separate_ragged(mixes, codec=mode, **kw)
+
+    def codec(mode):
+        def fn():
+            _, fr = eng.encode_ragged(mixes, None, seed=7, codec=mode)
+            eng.decode_ragged(lat, fr, lens, codec=mode)
+        return fn
 
     def single():
         for m in mixes:
@@ -87,9 +99,14 @@ def main():
     res = {"items": B, "seconds": [2, 4], "frames_min": min(frames), "frames_max": max(frames),
            "codec_groups": len(set(frames)),
            "padded_token_share": round(1.0 - sum(1 + f for f in frames) / (B * (1 + max(frames))), 4)}
-    for name, fn, iters in (("ragged", ragged, a.iters), ("single", single, max(2, a.iters // 2)), ("dense_4s", dense, a.iters)):
+    runs = [(f"ragged_{m}", ragged(m), a.iters) for m in native.CODEC_MODES]
+    runs += [("single", single, max(2, a.iters // 2)), ("dense_4s", dense, a.iters)]
+    for name, fn, iters in runs:
         ms, times = median_ms(fn, a.warmup, iters)
         res[name] = {"ms": round(ms, 2), "utt_per_s": round(1e3 * B / ms, 1), "runs_ms": [round(t, 2) for t in times]}
+    for m in native.CODEC_MODES:
+        ms, _ = median_ms(codec(m), a.warmup, a.iters)
+        res[f"ragged_{m}"].update(codec_ms=round(ms, 2), codec_share=round(ms / res[f"ragged_{m}"]["ms"], 4))
     eng.close()
     line = json.dumps(res)
     print(line)
