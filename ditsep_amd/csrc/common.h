@@ -59,6 +59,27 @@ __device__ __forceinline__ void dsn_split(float v, op16_t& hi, op16_t& lo, int f
   hi = to_op16(v, f16);
   lo = to_op16(v - from_op16(hi, f16), f16);
 }
+// The operand-plane store of the stand-alone producers: elements dst[i .. i + 3] (8-byte aligned) of plane 0 = hi and,
+// with two planes, of plane 1 (ps elements further) = lo.  pl = DSN_PL(plane count, fp16 flag).
+__device__ __forceinline__ void dsn_store_planes4(op16_t* dst, long ps, int pl, long i, const f32x4& v) {
+  op16x4 hi, lo;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    op16_t h, l;
+    dsn_split(v[r], h, l, PL_F16(pl));
+    hi[r] = h;
+    lo[r] = l;
+  }
+  *reinterpret_cast<op16x4*>(dst + i) = hi;
+  if (PL_COUNT(pl) == 2) *reinterpret_cast<op16x4*>(dst + ps + i) = lo;
+}
+// ... of one element
+__device__ __forceinline__ void dsn_store_planes1(op16_t* dst, long ps, int pl, long i, float v) {
+  op16_t h, l;
+  dsn_split(v, h, l, PL_F16(pl));
+  dst[i] = h;
+  if (PL_COUNT(pl) == 2) dst[ps + i] = l;
+}
 
 // ---- fp8 operands (DSN_PREC_FP8): OCP e4m3 data with one E8M0 scale byte per 32 consecutive K-elements of a row
 // (the MX block format v_mfma_scale_f32_16x16x128_f8f6f4 consumes): value = fp8 * 2^(byte - 127).

@@ -90,6 +90,17 @@ __device__ __forceinline__ float dsn_row_ror(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x120 + ROT, 0xf, 0xf, false));
 }
 
+// equal-count merge of a lane's GroupNorm partial (mean, M2, count) with that of the lane ROT places round its 16-lane
+// row: mean' = (mA + mB)/2, M2' = M2A + M2B + (mB - mA)^2 n/2 (DPP row rotate: registers only, no LDS-unit permute)
+template <int ROT>
+__device__ __forceinline__ void gn_merge_ror(float& mean, float& m2, float& cnt) {
+  const float om = dsn_row_ror<ROT>(mean), o2 = dsn_row_ror<ROT>(m2);
+  const float dm = om - mean;
+  m2 = m2 + o2 + dm * dm * (0.5f * cnt);
+  mean = 0.5f * (mean + om);
+  cnt *= 2.f;
+}
+
 template <int P, int F16, int NT, int MT, int EPI = 0, int LEAN = 0>
 __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)[NT][MT], int mw0, int m_end, int nw0,
                                              int lane, int z, const float* ln_rows = nullptr, int ln_m0 = 0) {
@@ -492,18 +503,11 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
     for (int tn = 0; tn < NT; ++tn) {
       float cnt = (float)(MT * 4);
       float mean = gmean[tn], m2 = gm2[tn];
-      // equal-count merge over the 16 row lanes: mean' = (mA + mB)/2, M2' = M2A + M2B + (mB - mA)^2 n/2, partner =
-      // the lane 8, 4, 2, 1 places round the 16-lane row (DPP row rotate: registers only, no LDS-unit permute)
-#define DSN_GN_MERGE(ROT)                                        \
-      {                                                          \
-        const float om = dsn_row_ror<ROT>(mean), o2 = dsn_row_ror<ROT>(m2); \
-        const float dm = om - mean;                              \
-        m2 = m2 + o2 + dm * dm * (0.5f * cnt);                   \
-        mean = 0.5f * (mean + om);                               \
-        cnt *= 2.f;                                              \
-      }
-      DSN_GN_MERGE(8) DSN_GN_MERGE(4) DSN_GN_MERGE(2) DSN_GN_MERGE(1)
-#undef DSN_GN_MERGE
+      // the 16 row lanes, over a fixed rotation tree
+      gn_merge_ror<8>(mean, m2, cnt);
+      gn_merge_ror<4>(mean, m2, cnt);
+      gn_merge_ror<2>(mean, m2, cnt);
+      gn_merge_ror<1>(mean, m2, cnt);
       const int n = nw0 + tn * 16 + nq;
       if ((lane & 15) == 0 && n < d.N) {
         if (!(LEAN & LEAN_NO_NCSN) && d.gnf_out) {
@@ -519,12 +523,6 @@ __device__ __forceinline__ void epilogue_gen(const GemmDesc& d_arg, f32x4 (&acc)
       }
     }
   }
-}
-
-template <int P, int F16, int LEAN = 0>
-__device__ __forceinline__ void epilogue_tile(const GemmDesc& d, f32x4 (&acc)[4][4], int mw0, int nw0, int lane,
-                                              int z) {
-  epilogue_gen<P, F16, 4, 4, 0, LEAN>(d, acc, mw0, d.M, nw0, lane, z);
 }
 
 // v1: tile 128(m) x 128(n) x 32(k) per 256-thread workgroup (4 waves as 2x2, each 64x64 = 4x4 accumulators).  K loop:
@@ -657,7 +655,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const GemmDesc d) {
     __syncthreads();
   }
 
-  epilogue_tile<P, F16>(d, acc, m0 + wm * 64, n0 + wn * 64, lane, 0);
+  epilogue_gen<P, F16, 4, 4>(d, acc, m0 + wm * 64, d.M, n0 + wn * 64, lane, 0);
 }
 
 }  // namespace

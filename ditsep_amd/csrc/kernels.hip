@@ -13,13 +13,7 @@ inline int grid_for(long n, int per_block = TPB, int cap = 256 * 16) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-// `planes` everywhere in this file is the packed DSN_PL(plane count, fp16 flag)
-__device__ __forceinline__ void store_planes(op16_t* dst, long ps, int planes, long i, float v) {
-  op16_t h, l;
-  dsn_split(v, h, l, PL_F16(planes));
-  dst[i] = h;
-  if (PL_COUNT(planes) == 2) dst[ps + i] = l;
-}
+// `planes` everywhere in this file is the packed DSN_PL(plane count, fp16 flag); plane stores: dsn_store_planes1 / 4
 
 // ------------------------------------------------------------------ transforms
 __global__ void pack_tokens_kernel(const float* __restrict__ s0, int C0, const float* __restrict__ s1, int C1,
@@ -34,7 +28,7 @@ __global__ void pack_tokens_kernel(const float* __restrict__ s0, int C0, const f
     const int b = (int)(bt / T);
     const float v = c < C0 ? s0[((long)b * C0 + c) * T + t] : s1[((long)b * C1 + (c - C0)) * T + t];
     if (df) df[i] = v;
-    if (dp) store_planes(dp, ps, planes, i, v);
+    if (dp) dsn_store_planes1(dp, ps, planes, i, v);
   }
 }
 
@@ -516,8 +510,8 @@ __global__ void timestep_features_kernel(const float* __restrict__ t, const floa
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int b = i / half, k = i - b * half;
     const float f = 2.f * 3.14159265358979323846f * t[b] * w[k];
-    store_planes(out, ps, planes, (long)b * 2 * half + k, cosf(f));
-    store_planes(out, ps, planes, (long)b * 2 * half + half + k, sinf(f));
+    dsn_store_planes1(out, ps, planes, (long)b * 2 * half + k, cosf(f));
+    dsn_store_planes1(out, ps, planes, (long)b * 2 * half + half + k, sinf(f));
   }
 }
 
@@ -689,7 +683,7 @@ __global__ void conv_in1_kernel(const float* __restrict__ wav, const float* __re
       float a = acc;
       if (act == DSN_ACT_ELU) a = dsn_elu(acc);
       else if (act == DSN_ACT_SNAKE) a = dsn_snake(acc, aa[co], ab[co]);
-      store_planes(op, ps, planes, i, a);
+      dsn_store_planes1(op, ps, planes, i, a);
     }
   }
 }
@@ -865,7 +859,7 @@ __global__ void pack_weight_kernel(const float* __restrict__ src, const float* _
       v = src[((long)ci * Cout + co) * kw + (p + tap * stride)];
       if (scale) v *= scale[ci];
     }
-    store_planes(dst, ps, planes, i, v);
+    dsn_store_planes1(dst, ps, planes, i, v);
   }
 }
 

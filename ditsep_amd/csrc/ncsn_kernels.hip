@@ -15,19 +15,6 @@ inline int grid_for(long n, int per_block = TPB, int cap = 256 * 16) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-__device__ __forceinline__ void store_planes4(op16_t* dst, long ps, int planes, long i, const f32x4& v) {
-  op16x4 hi, lo;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    op16_t h, l;
-    dsn_split(v[r], h, l, PL_F16(planes));
-    hi[r] = h;
-    lo[r] = l;
-  }
-  *reinterpret_cast<op16x4*>(dst + i) = hi;
-  if (PL_COUNT(planes) == 2) *reinterpret_cast<op16x4*>(dst + ps + i) = lo;
-}
-
 // xt [B][n][H][T], mix [B][1][H][T]  ->  NHWC [B][H][Wp][Cp], zero in the channel / frame padding
 __global__ void ncsn_pack_kernel(const float* __restrict__ xt, const float* __restrict__ mix, int n, int H, int T,
                                  int Wp, int Cp, float* __restrict__ of, op16_t* __restrict__ op, long ps, int planes,
@@ -45,12 +32,7 @@ __global__ void ncsn_pack_kernel(const float* __restrict__ xt, const float* __re
       else if (c == n) v = mix[(b * H + y) * T + x];
     }
     if (of) of[i] = v;
-    if (op) {
-      op16_t h, l;
-      dsn_split(v, h, l, PL_F16(planes));
-      op[i] = h;
-      if (PL_COUNT(planes) == 2) op[ps + i] = l;
-    }
+    if (op) dsn_store_planes1(op, ps, planes, i, v);
   }
 }
 
@@ -141,7 +123,7 @@ __global__ void gn_apply_kernel(const float* __restrict__ x, long bstride, int r
       }
       const long oi = ((long)b * HW + r[u]) * nq + q[u];
       if (of) reinterpret_cast<f32x4*>(of)[oi] = o;
-      if (op) store_planes4(op, ps, planes, oi * 4, o);
+      if (op) dsn_store_planes4(op, ps, planes, oi * 4, o);
     }
   }
 }
@@ -198,7 +180,7 @@ __global__ void fir2d_kernel(const float* __restrict__ x, long bstride, int rstr
     }
     if (add) acc += reinterpret_cast<const f32x4*>(add)[i];
     if (of) reinterpret_cast<f32x4*>(of)[i] = acc;
-    if (op) store_planes4(op, ps, planes, i * 4, acc);
+    if (op) dsn_store_planes4(op, ps, planes, i * 4, acc);
   }
 }
 
