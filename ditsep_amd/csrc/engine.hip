@@ -432,6 +432,8 @@ struct dsn_ctx {
     Packed p;
     p.N = (int)w.shape[0];
     p.K = (int)(w.numel / w.shape[0]);
+    if (swiglu && p.N % 32 != 0)  // (the row map interleaves groups of 16 + 16 rows: a ragged last group reads past the source)
+      fail(DSN_EINVAL, "%s: a SwiGLU weight needs N %% 32 == 0 (got %d)", wname.c_str(), p.N);
     p.Cin = p.K;
     p.taps = 1;
     p.ps = (long)p.N * p.K;
@@ -459,6 +461,7 @@ struct dsn_ctx {
     p.N = (int)w.shape[0];
     p.K = (int)(w.numel / w.shape[0]);
     if (p.K % 128 != 0) fail(DSN_EINVAL, "%s: fp8 GEMMs need K %% 128 == 0 (got %d)", wname.c_str(), p.K);
+    if (swiglu && p.N % 32 != 0) fail(DSN_EINVAL, "%s: a SwiGLU weight needs N %% 32 == 0 (got %d)", wname.c_str(), p.N);
     p.w = (unsigned char*)dmalloc((size_t)p.N * p.K);
     p.s = (unsigned char*)dmalloc((size_t)p.N * (p.K / 32));
     launch_pack_weight_fp8(w.p, p.w, p.s, p.N, p.K, swiglu ? 1 : 0, st);
@@ -3608,6 +3611,192 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         if (!t->out_f32) fail(DSN_EINVAL, "test_kernel %s: out_f32 missing", nm);
         if (t->kind == DSN_TK_RANDN) launch_randn(t->out_f32, (long)t->count, t->seed, t->offset, st);
         else launch_rand_uniform(t->out_f32, (long)t->count, t->seed, t->offset, t->lo, t->hi, st);
+        break;
+      }
+      // ---- load-time weight preparation, the per-call movers and the feature kernels: tensors passed through
+      case DSN_TK_WN_SCALE: {
+        if (t->rows < 1 || t->count < 1)
+          fail(DSN_EINVAL, "test_kernel wn_scale: rows and count must be positive (rows=%d count=%ld)", t->rows, (long)t->count);
+        if (!t->x || !t->gamma || !t->out_f32) fail(DSN_EINVAL, "test_kernel wn_scale: x (v), gamma (g) or out_f32 missing");
+        launch_wn_scale(t->x, t->gamma, t->out_f32, t->rows, (long)t->count, st);
+        break;
+      }
+      case DSN_TK_PACK_WEIGHT: {
+        static const char* const modes[] = {"linear", "linear_swiglu", "conv", "convt", "conv2d", "nin"};
+        const int m = t->mode, N = t->N, K = t->K;
+        if (m < PACK_LINEAR || m > PACK_NIN) fail(DSN_EINVAL, "test_kernel pack_weight: unknown mode %d", m);
+        if (N < 1 || K < 1) fail(DSN_EINVAL, "test_kernel pack_weight %s: N and K must be positive (N=%d K=%d)", modes[m], N, K);
+        if (!t->x || !oplanes) fail(DSN_EINVAL, "test_kernel pack_weight %s: x (the source) or out_planes missing", modes[m]);
+        if (t->out_ps < (long)N * K) fail(DSN_EINVAL, "test_kernel pack_weight %s: out_ps %ld < N*K", modes[m], (long)t->out_ps);
+        const bool linear = m == PACK_LINEAR || m == PACK_LINEAR_SWIGLU;
+        if (t->colscale && !linear) fail(DSN_EINVAL, "test_kernel pack_weight %s: colscale is read by the linear modes only", modes[m]);
+        if (t->scale && m != PACK_CONV && m != PACK_CONVT)
+          fail(DSN_EINVAL, "test_kernel pack_weight %s: scale is read by conv and convt only", modes[m]);
+        long need = (long)N * K;  // floats of the source the index map reaches
+        if (m == PACK_LINEAR_SWIGLU && N % 32 != 0)
+          fail(DSN_EINVAL, "test_kernel pack_weight linear_swiglu: N %% 32 != 0 (N=%d)", N);
+        if (!linear && m != PACK_NIN) {
+          if (t->Cin < 1 || t->Cout < 1 || t->kw < 1)
+            fail(DSN_EINVAL, "test_kernel pack_weight %s: Cin, Cout, kw must be positive (Cin=%d Cout=%d kw=%d)", modes[m],
+                 t->Cin, t->Cout, t->kw);
+          need = (long)t->Cout * t->Cin * t->kw;
+        }
+        if (m == PACK_CONV && (N != t->Cout || K != t->kw * t->Cin))
+          fail(DSN_EINVAL, "test_kernel pack_weight conv: needs N = Cout, K = kw*Cin (N=%d K=%d)", N, K);
+        if (m == PACK_CONVT) {
+          if (t->stride < 1 || t->kw != 2 * t->stride)
+            fail(DSN_EINVAL, "test_kernel pack_weight convt: kw != 2*stride (kw=%d stride=%d)", t->kw, t->stride);
+          if (N != t->stride * t->Cout || K != 2 * t->Cin)
+            fail(DSN_EINVAL, "test_kernel pack_weight convt: needs N = stride*Cout, K = 2*Cin (N=%d K=%d)", N, K);
+        }
+        if (m == PACK_CONV2D && (t->stride < t->Cin || N < t->Cout || K != t->kw * t->stride))
+          fail(DSN_EINVAL, "test_kernel pack_weight conv2d: needs stride (padded Cin) >= Cin, N >= Cout, K = kw*stride "
+                           "(N=%d K=%d stride=%d)", N, K, t->stride);
+        if (t->count != need)
+          fail(DSN_EINVAL, "test_kernel pack_weight %s: count %ld != the %ld floats the mode reads", modes[m], (long)t->count, need);
+        launch_pack_weight(t->x, t->scale, oplanes, t->out_ps, PL, m, N, K, t->Cin, t->Cout, t->kw, t->stride, st,
+                           t->colscale);
+        break;
+      }
+      case DSN_TK_PACK_BIAS_SWIGLU: {
+        if (t->N < 1 || t->N % 32 != 0) fail(DSN_EINVAL, "test_kernel pack_bias_swiglu: N %% 32 != 0 or N < 1 (N=%d)", t->N);
+        if (!t->x || !t->out_f32) fail(DSN_EINVAL, "test_kernel pack_bias_swiglu: x (the bias) or out_f32 missing");
+        launch_pack_bias_swiglu(t->x, t->out_f32, t->N, st);
+        break;
+      }
+      case DSN_TK_PACK_WEIGHT_FP8: {
+        if (t->N < 1 || t->K < 1) fail(DSN_EINVAL, "test_kernel pack_weight_fp8: N and K must be positive (N=%d K=%d)", t->N, t->K);
+        if (t->K % 32 != 0) fail(DSN_EINVAL, "test_kernel pack_weight_fp8: K %% 32 != 0 (K=%d)", t->K);
+        if (t->mode != PACK_LINEAR && t->mode != PACK_LINEAR_SWIGLU)
+          fail(DSN_EINVAL, "test_kernel pack_weight_fp8: mode %d is neither linear nor linear_swiglu", t->mode);
+        if (t->mode == PACK_LINEAR_SWIGLU && t->N % 32 != 0)
+          fail(DSN_EINVAL, "test_kernel pack_weight_fp8 linear_swiglu: N %% 32 != 0 (N=%d)", t->N);
+        if (!t->x || !t->out_fp8 || !t->out_fp8_scale)
+          fail(DSN_EINVAL, "test_kernel pack_weight_fp8: x (the source), out_fp8 or out_fp8_scale missing");
+        if (((uintptr_t)t->x | (uintptr_t)t->colscale) & 15 || (uintptr_t)t->out_fp8 & 3)
+          fail(DSN_EINVAL, "test_kernel pack_weight_fp8: x / colscale must be 16-byte and out_fp8 4-byte aligned");
+        launch_pack_weight_fp8(t->x, t->out_fp8, t->out_fp8_scale, t->N, t->K, t->mode == PACK_LINEAR_SWIGLU, st, t->colscale);
+        break;
+      }
+      case DSN_TK_PACKED_ROW_SUM: {
+        if (t->N < 1 || t->K < 1) fail(DSN_EINVAL, "test_kernel packed_row_sum: N and K must be positive (N=%d K=%d)", t->N, t->K);
+        if (!t->in_planes || !t->out_f32) fail(DSN_EINVAL, "test_kernel packed_row_sum: in_planes or out_f32 missing");
+        if (t->in_ps < (long)t->N * t->K) fail(DSN_EINVAL, "test_kernel packed_row_sum: in_ps %ld < N*K", (long)t->in_ps);
+        launch_packed_row_sum(reinterpret_cast<const op16_t*>(t->in_planes), t->in_ps, PL, t->N, t->K, t->out_f32, st);
+        break;
+      }
+      case DSN_TK_FP8_ROW_SUM: {
+        if (t->N < 1 || t->K < 1) fail(DSN_EINVAL, "test_kernel fp8_row_sum: N and K must be positive (N=%d K=%d)", t->N, t->K);
+        if (t->K % 32 != 0) fail(DSN_EINVAL, "test_kernel fp8_row_sum: K %% 32 != 0 (K=%d)", t->K);
+        if (!t->in_fp8 || !t->in_fp8_scale || !t->out_f32)
+          fail(DSN_EINVAL, "test_kernel fp8_row_sum: in_fp8, in_fp8_scale or out_f32 missing");
+        if ((uintptr_t)t->in_fp8 & 3) fail(DSN_EINVAL, "test_kernel fp8_row_sum: in_fp8 must be 4-byte aligned");
+        launch_fp8_row_sum(t->in_fp8, t->in_fp8_scale, t->N, t->K, t->out_f32, st);
+        break;
+      }
+      case DSN_TK_BIAS_PLUS_WBETA: {
+        if (t->N < 1 || t->K < 1) fail(DSN_EINVAL, "test_kernel bias_plus_wbeta: N and K must be positive (N=%d K=%d)", t->N, t->K);
+        if (!t->x || !t->beta || !t->out_f32) fail(DSN_EINVAL, "test_kernel bias_plus_wbeta: x (W), beta or out_f32 missing");
+        launch_bias_plus_wbeta(t->x, t->beta, t->bias, t->N, t->K, t->out_f32, st);
+        break;
+      }
+      case DSN_TK_SNAKE_PARAMS: {
+        if (t->C < 1) fail(DSN_EINVAL, "test_kernel snake_params: C must be positive (C=%d)", t->C);
+        if (!t->act_a || !t->act_b || !t->out_f32 || !t->out2_f32)
+          fail(DSN_EINVAL, "test_kernel snake_params: act_a (alpha), act_b (beta), out_f32 or out2_f32 missing");
+        launch_snake_params(t->act_a, t->act_b, t->out_f32, t->out2_f32, t->C, st);
+        break;
+      }
+      case DSN_TK_PACK_TOKENS: {
+        if (t->B < 1 || t->T < 1 || t->C0 < 1 || t->C1 < 0)
+          fail(DSN_EINVAL, "test_kernel pack_tokens: B, T, C0 must be positive and C1 >= 0 (B=%d T=%d C0=%d C1=%d)", t->B,
+               t->T, t->C0, t->C1);
+        if (!t->x || (t->C1 > 0) != !!t->y)
+          fail(DSN_EINVAL, "test_kernel pack_tokens: x (src0) missing, or y (src1) does not go with C1 = %d", t->C1);
+        if (!t->out_f32 && !oplanes) fail(DSN_EINVAL, "test_kernel pack_tokens: out_f32 and out_planes both missing");
+        if (oplanes && t->out_ps < (long)t->B * t->T * (t->C0 + t->C1))
+          fail(DSN_EINVAL, "test_kernel pack_tokens: out_ps %ld < B*T*(C0+C1)", (long)t->out_ps);
+        launch_pack_tokens(t->x, t->C0, t->y, t->C1, t->B, t->T, t->out_f32, oplanes, t->out_ps, PL, st);
+        break;
+      }
+      case DSN_TK_UNPACK_TOKENS: {
+        if (t->B < 1 || t->C < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel unpack_tokens: B, C, T must be positive (B=%d C=%d T=%d)", t->B, t->C, t->T);
+        if (!t->x || !t->out_f32) fail(DSN_EINVAL, "test_kernel unpack_tokens: x or out_f32 missing");
+        launch_unpack_tokens(t->x, t->out_f32, t->B, t->C, t->T, st);
+        break;
+      }
+      case DSN_TK_COPY_ROWS: {
+        if (t->rows < 1 || t->C < 1) fail(DSN_EINVAL, "test_kernel copy_rows: rows and C must be positive (rows=%d C=%d)", t->rows, t->C);
+        if (t->C % 4 != 0 || t->dst_stride % 4 != 0 || t->dst_stride < t->C)
+          fail(DSN_EINVAL, "test_kernel copy_rows: C %% 4 != 0, dst_stride %% 4 != 0 or dst_stride < C (C=%d dst_stride=%ld)",
+               t->C, (long)t->dst_stride);
+        if (!t->x || !t->out_f32) fail(DSN_EINVAL, "test_kernel copy_rows: x or out_f32 missing");
+        if (((uintptr_t)t->x | (uintptr_t)t->out_f32) & 15) fail(DSN_EINVAL, "test_kernel copy_rows: x / out_f32 must be 16-byte aligned");
+        launch_copy_rows(t->x, t->out_f32, t->rows, t->C, (long)t->dst_stride, st);
+        break;
+      }
+      case DSN_TK_TO_PLANES: {
+        if (t->count < 1 || t->count % 4 != 0)
+          fail(DSN_EINVAL, "test_kernel to_planes: count %% 4 != 0 or count < 1 (count=%ld)", (long)t->count);
+        if (!t->x || !oplanes) fail(DSN_EINVAL, "test_kernel to_planes: x or out_planes missing");
+        if (t->out_ps < t->count || t->out_ps % 4 != 0)
+          fail(DSN_EINVAL, "test_kernel to_planes: out_ps %ld < count or out_ps %% 4 != 0", (long)t->out_ps);
+        if ((uintptr_t)t->x & 15 || (uintptr_t)oplanes & 7) fail(DSN_EINVAL, "test_kernel to_planes: x must be 16-byte, out_planes 8-byte aligned");
+        launch_to_planes(t->x, oplanes, t->out_ps, PL, (long)t->count, st);
+        break;
+      }
+      case DSN_TK_ZERO_TAIL: {
+        if (t->B < 1 || t->n < 1 || t->D < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel zero_tail: B, n, D, T must be positive (B=%d n=%d D=%d T=%d)", t->B, t->n, t->D, t->T);
+        if (!t->x || !t->lens) fail(DSN_EINVAL, "test_kernel zero_tail: x or lens missing");
+        launch_zero_tail(t->x, reinterpret_cast<const int*>(t->lens), t->B, t->n, t->D, t->T, st);
+        break;
+      }
+      case DSN_TK_VAE_SAMPLE_RAGGED: {
+        if (t->B < 1 || t->D < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel vae_sample_ragged: B, D, T must be positive (B=%d D=%d T=%d)", t->B, t->D, t->T);
+        if (!t->x || !t->z || !t->lens || !t->out_f32)
+          fail(DSN_EINVAL, "test_kernel vae_sample_ragged: x (encoder output), z, lens (frames) or out_f32 missing");
+        launch_vae_sample_ragged(t->x, t->z, reinterpret_cast<const int*>(t->lens), t->out_f32, t->B, t->D, t->T, st);
+        break;
+      }
+      case DSN_TK_TIMESTEP_FEATURES:
+      case DSN_TK_NCSN_FOURIER: {
+        const char* nm = t->kind == DSN_TK_NCSN_FOURIER ? "ncsn_fourier" : "timestep_features";
+        if (t->B < 1 || t->half < 1) fail(DSN_EINVAL, "test_kernel %s: B and half must be positive (B=%d half=%d)", nm, t->B, t->half);
+        if (!t->x || !t->w || !oplanes) fail(DSN_EINVAL, "test_kernel %s: x (t), w or out_planes missing", nm);
+        if (t->out_ps < 2L * t->B * t->half) fail(DSN_EINVAL, "test_kernel %s: out_ps %ld < 2*B*half", nm, (long)t->out_ps);
+        if (t->kind == DSN_TK_NCSN_FOURIER) launch_ncsn_fourier(t->x, t->w, t->B, t->half, oplanes, t->out_ps, PL, st);
+        else launch_timestep_features(t->x, t->w, t->B, t->half, oplanes, t->out_ps, PL, st);
+        break;
+      }
+      case DSN_TK_ROPE_TABLES: {
+        if (t->S < 1 || t->dh < 2 || (t->dh & 1))
+          fail(DSN_EINVAL, "test_kernel rope_tables: S must be positive and dh (the rotary width) even (S=%d dh=%d)", t->S, t->dh);
+        if (!t->rope_cos || !t->rope_sin) fail(DSN_EINVAL, "test_kernel rope_tables: rope_cos or rope_sin missing");
+        launch_rope_tables(t->rope_cos, t->rope_sin, t->S, t->dh, st);
+        break;
+      }
+      case DSN_TK_NCSN_PACK:
+      case DSN_TK_NCSN_OUTPUT: {
+        const bool pack = t->kind == DSN_TK_NCSN_PACK;
+        const char* nm = pack ? "ncsn_pack" : "ncsn_output";
+        if (t->B < 1 || t->n < 1 || t->H < 1 || t->T < 1)
+          fail(DSN_EINVAL, "test_kernel %s: B, n, H, T must be positive (B=%d n=%d H=%d T=%d)", nm, t->B, t->n, t->H, t->T);
+        if (t->Wp < t->T) fail(DSN_EINVAL, "test_kernel %s: Wp %d < T %d", nm, t->Wp, t->T);
+        if (!t->x || !t->y) fail(DSN_EINVAL, "test_kernel %s: x or y missing", nm);
+        if (pack) {
+          if (t->Cp < t->n + 1) fail(DSN_EINVAL, "test_kernel ncsn_pack: Cp %d < n + 1", t->Cp);
+          if (!t->out_f32 && !oplanes) fail(DSN_EINVAL, "test_kernel ncsn_pack: out_f32 and out_planes both missing");
+          if (oplanes && t->out_ps < (long)t->B * t->H * t->Wp * t->Cp)
+            fail(DSN_EINVAL, "test_kernel ncsn_pack: out_ps %ld < B*H*Wp*Cp", (long)t->out_ps);
+          launch_ncsn_pack(t->x, t->y, t->B, t->n, t->H, t->T, t->Wp, t->Cp, t->out_f32, oplanes, t->out_ps, PL, st);
+        } else {
+          if (t->cin < 1 || t->Cp < t->cin) fail(DSN_EINVAL, "test_kernel ncsn_output: Cp %d < cin %d, or cin < 1", t->Cp, t->cin);
+          if (!t->w || !t->bias || !t->out_f32) fail(DSN_EINVAL, "test_kernel ncsn_output: w, bias or out_f32 missing");
+          launch_ncsn_output(t->x, t->Cp, t->y, t->w, t->bias, t->cin, t->n, t->B, t->H, t->T, t->Wp, t->out_f32, st);
+        }
         break;
       }
       default:

@@ -149,7 +149,14 @@ TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn
                      "conv_out1": 7, "conv_in1": 8, "ru_fused": 9,
                      "pc_prior": 10, "pc_corrector": 11, "pc_item_norms": 12, "pc_predictor": 13, "sigma_mix": 14,
                      "mix_prior": 15, "mix_corrector": 16, "mix_predictor": 17, "sb_update": 18, "repeat_sources": 19,
-                     "vae_sample": 20, "randn": 21, "rand_uniform": 22, "codec_tail_zero": 23}
+                     "vae_sample": 20, "randn": 21, "rand_uniform": 22, "codec_tail_zero": 23,
+                     "wn_scale": 24, "pack_weight": 25, "pack_bias_swiglu": 26, "pack_weight_fp8": 27,
+                     "packed_row_sum": 28, "fp8_row_sum": 29, "bias_plus_wbeta": 30, "snake_params": 31,
+                     "pack_tokens": 32, "unpack_tokens": 33, "copy_rows": 34, "to_planes": 35, "zero_tail": 36,
+                     "vae_sample_ragged": 37, "timestep_features": 38, "rope_tables": 39, "ncsn_pack": 40,
+                     "ncsn_fourier": 41, "ncsn_output": 42}
+# `mode` of the pack_weight kind (DSN_PACK_*); pack_weight_fp8 takes the first two
+PACK_MODES = {"linear": 0, "linear_swiglu": 1, "conv": 2, "convt": 3, "conv2d": 4, "nin": 5}
 
 
 class DsnTestKernel(C.Structure):
@@ -180,6 +187,14 @@ class DsnTestKernel(C.Structure):
         ("xmean", C.c_void_p),
         ("lens", C.c_void_p),
         ("rep", C.c_int), ("mul", C.c_int),
+        # weight preparation, movers and feature kernels
+        ("mode", C.c_int), ("N", C.c_int), ("K", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("kw", C.c_int),
+        ("stride", C.c_int),
+        ("scale", C.c_void_p), ("colscale", C.c_void_p), ("in_planes", C.c_void_p), ("in_ps", C.c_int64),
+        ("in_fp8", C.c_void_p), ("in_fp8_scale", C.c_void_p),
+        ("C0", C.c_int), ("C1", C.c_int), ("dst_stride", C.c_int64),
+        ("Wp", C.c_int), ("Cp", C.c_int), ("cin", C.c_int), ("half", C.c_int),
+        ("out2_f32", C.c_void_p),
     ]
 
 
@@ -1058,12 +1073,13 @@ class Engine:
     def test_kernel(self, kind, **kw):
         """Run one launch wrapper of the non-GEMM kernels (dsn_test_kernel, include/ditsep_hip.h) on caller-owned device
         tensors.  Every keyword is the DsnTestKernel field of the same name; tensors are passed by pointer (fp32, but
-        out_planes int16 [P][out_ps], out_fp8 / out_fp8_scale uint8 and lens int32), `a` / `w` / `w2` also set their
-        _numel field."""
+        out_planes / in_planes int16 [P][out_ps / in_ps], out_fp8 / out_fp8_scale / in_fp8 / in_fp8_scale uint8 and lens
+        int32), `a` / `w` / `w2` also set their _numel field."""
         t = DsnTestKernel()
         t.kind = TEST_KERNEL_KINDS[kind]
         keep = []
-        dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8, "lens": torch.int32}
+        dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8, "lens": torch.int32,
+                  "in_planes": torch.int16, "in_fp8": torch.uint8, "in_fp8_scale": torch.uint8}
         for k, v in kw.items():
             if isinstance(v, torch.Tensor):
                 assert v.is_cuda and v.dtype == dtypes.get(k, torch.float32), k
@@ -1074,6 +1090,8 @@ class Engine:
                     setattr(t, k + "_numel", v.numel())
                 if k == "out_planes" and "out_ps" not in kw:
                     t.out_ps = v.shape[-1] if v.dim() > 1 else v.numel()
+                if k == "in_planes" and "in_ps" not in kw:
+                    t.in_ps = v.shape[-1] if v.dim() > 1 else v.numel()
             elif v is not None:
                 setattr(t, k, v)
         self._check(self.lib.dsn_test_kernel(self.ctx, C.byref(t), self._stream()), f"dsn_test_kernel({kind})")

@@ -487,7 +487,16 @@ enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3,
        DSN_TK_PC_PRIOR = 10, DSN_TK_PC_CORRECTOR = 11, DSN_TK_PC_ITEM_NORMS = 12, DSN_TK_PC_PREDICTOR = 13,
        DSN_TK_SIGMA_MIX = 14, DSN_TK_MIX_PRIOR = 15, DSN_TK_MIX_CORRECTOR = 16, DSN_TK_MIX_PREDICTOR = 17,
        DSN_TK_SB_UPDATE = 18, DSN_TK_REPEAT_SOURCES = 19, DSN_TK_VAE_SAMPLE = 20, DSN_TK_RANDN = 21,
-       DSN_TK_RAND_UNIFORM = 22, DSN_TK_CODEC_TAIL_ZERO = 23 };
+       DSN_TK_RAND_UNIFORM = 22, DSN_TK_CODEC_TAIL_ZERO = 23,
+       DSN_TK_WN_SCALE = 24, DSN_TK_PACK_WEIGHT = 25, DSN_TK_PACK_BIAS_SWIGLU = 26, DSN_TK_PACK_WEIGHT_FP8 = 27,
+       DSN_TK_PACKED_ROW_SUM = 28, DSN_TK_FP8_ROW_SUM = 29, DSN_TK_BIAS_PLUS_WBETA = 30, DSN_TK_SNAKE_PARAMS = 31,
+       DSN_TK_PACK_TOKENS = 32, DSN_TK_UNPACK_TOKENS = 33, DSN_TK_COPY_ROWS = 34, DSN_TK_TO_PLANES = 35,
+       DSN_TK_ZERO_TAIL = 36, DSN_TK_VAE_SAMPLE_RAGGED = 37, DSN_TK_TIMESTEP_FEATURES = 38, DSN_TK_ROPE_TABLES = 39,
+       DSN_TK_NCSN_PACK = 40, DSN_TK_NCSN_FOURIER = 41, DSN_TK_NCSN_OUTPUT = 42 };
+/* `mode` of DSN_TK_PACK_WEIGHT (the PACK_* index maps of ditsep_amd/csrc/kernels.h); DSN_TK_PACK_WEIGHT_FP8 takes the
+ * first two */
+enum { DSN_PACK_LINEAR = 0, DSN_PACK_LINEAR_SWIGLU = 1, DSN_PACK_CONV = 2, DSN_PACK_CONVT = 3, DSN_PACK_CONV2D = 4,
+       DSN_PACK_NIN = 5 };
 typedef struct DsnTestKernel {
   int kind;                   /* DSN_TK_* */
   /* ATTENTION: a = q | k | v [B*S][3*H*dh] -> out_planes [B*S][H*dh] (or out_fp8 + out_fp8_scale)
@@ -569,6 +578,48 @@ typedef struct DsnTestKernel {
   float* xmean;
   const int32_t* lens;        /* ATTENTION / QKV_ATTENTION: valid tokens per item (null: dense); CODEC_TAIL_ZERO: frames */
   int rep, mul;               /* CODEC_TAIL_ZERO */
+  /* Load-time weight preparation and the per-call movers and feature kernels: every tensor is passed through to the
+   * wrapper (nothing is rounded to planes first), fp32 unless said otherwise.
+   *   WN_SCALE         x = v [rows][count], gamma = g [rows] -> out_f32 [rows] = g / |v row|
+   *   PACK_WEIGHT      x = the source weight of `count` floats, which must be what `mode` addresses:
+   *                      LINEAR, LINEAR_SWIGLU  [N][K], colscale [K] optional          (SWIGLU: N % 32 == 0)
+   *                      CONV    [Cout][Cin][kw], scale [Cout] optional; N = Cout, K = kw Cin
+   *                      CONVT   [Cin][Cout][kw], scale [Cin] optional;  kw = 2 stride, N = stride Cout, K = 2 Cin
+   *                      CONV2D  [Cout][Cin][kw];  stride = the padded Cin >= Cin, N >= Cout, K = kw stride
+   *                      NIN     [K][N]
+   *                    -> out_planes [N][K] (out_ps >= N K); a scale / colscale the mode does not read is refused
+   *   PACK_BIAS_SWIGLU x = bias [N] -> out_f32 [N] in PACK_LINEAR_SWIGLU row order (N % 32 == 0)
+   *   PACK_WEIGHT_FP8  x = [N][K], K % 32 == 0, mode LINEAR or LINEAR_SWIGLU (N % 32 == 0), colscale [K] optional
+   *                    -> out_fp8 [N][K] e4m3 bytes, out_fp8_scale [N][K / 32] E8M0 bytes
+   *   PACKED_ROW_SUM   in_planes (the engine's plane count, in_ps >= N K apart) [N][K] -> out_f32 [N]
+   *   FP8_ROW_SUM      in_fp8 [N][K], in_fp8_scale [N][K / 32], K % 32 == 0 -> out_f32 [N]
+   *   BIAS_PLUS_WBETA  x = W [N][K], beta [K], bias [N] optional -> out_f32 [N]
+   *   SNAKE_PARAMS     act_a = alpha, act_b = beta [C] -> out_f32 = exp(alpha), out2_f32 = 1 / (exp(beta) + 1e-9)
+   *   PACK_TOKENS      x = src0 [B][C0][T], y = src1 [B][C1][T] (null exactly when C1 == 0) -> out_f32 and / or
+   *                    out_planes [B T][C0 + C1]
+   *   UNPACK_TOKENS    x = [B T][C] -> out_f32 [B][C][T]
+   *   COPY_ROWS        x = [rows][C] -> out_f32, rows dst_stride floats apart; C, dst_stride multiples of 4, dst_stride >= C
+   *   TO_PLANES        x = [count] -> out_planes; count a multiple of 4, out_ps >= count and a multiple of 4
+   *   ZERO_TAIL        x [B,n,D,T] in place, lens (device int32 [B], counts the timestep token): t >= lens[b] - 1 zeroed
+   *   VAE_SAMPLE_RAGGED  VAE_SAMPLE with lens = frames (device int32 [B]): out_f32[b, :, t] = 0 for t >= frames[b]
+   *   TIMESTEP_FEATURES  x = t [B], w [half] -> out_planes [B][2 half] = cos | sin
+   *   ROPE_TABLES      S positions, dh = the rotary width (even) -> rope_cos, rope_sin [S][dh]
+   *   NCSN_PACK        x = xt [B,n,H,T], y = mix [B,1,H,T] -> out_f32 and / or out_planes [B][H][Wp][Cp];
+   *                    Wp >= T, Cp >= n + 1
+   *   NCSN_FOURIER     x = t [B], w [half] -> out_planes [B][2 half] = sin | cos of 2 pi log(t) w
+   *   NCSN_OUTPUT      x = pyr [B][H][Wp][Cp], y = t [B], w [n][cin], bias [n] -> out_f32 [B T][n H]; Wp >= T, Cp >= cin
+   * Refused by name before any launch: a missing tensor, a non-positive size, and each condition listed above. */
+  int mode, N, K, Cin, Cout, kw, stride;
+  const float* scale;
+  const float* colscale;
+  const int16_t* in_planes;
+  int64_t in_ps;
+  const uint8_t* in_fp8;
+  const uint8_t* in_fp8_scale;
+  int C0, C1;
+  int64_t dst_stride;
+  int Wp, Cp, cin, half;
+  float* out2_f32;
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 
