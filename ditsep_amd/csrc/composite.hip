@@ -14,6 +14,11 @@
 //   finish     per item and measure: the mean of the k smallest per-frame values (LLR, WSS; k from the host) chosen
 //              by rank over LDS tiles, any frame count; the plain mean (segmental SNR)
 // Every reduction has a fixed order (no atomics): two calls on the same input give bit-identical results.
+// Ragged batches (dsn_composite_ragged): rows stay Lmax apart and batch entry b = item / n brings its own sample
+// count lens[b], frame count Fb[b] and trimmed count kb[b], all from the host (null arrays: every item is full
+// length).  Buffers and grids are sized by the longest item; a workgroup wholly past an item's frames leaves at once,
+// a wave past them inside a live workgroup still walks every barrier with zeros.  Nothing past lens[b] is read, and
+// every sum runs in the order the item's own length fixes: an item gets the same bits in a padded batch as alone.
 #include "kernels.h"
 
 namespace {
@@ -38,6 +43,7 @@ __device__ inline double wave_max(double v) {
 __global__ __launch_bounds__(kCondThreads) void composite_condition_kernel(const float* __restrict__ ref,
                                                                             const float* __restrict__ est,
                                                                             const int* __restrict__ ymap, int L,
+                                                                            const int* __restrict__ lens, int n,
                                                                             double* __restrict__ cond) {
   constexpr int kWaves = kCondThreads / 64;
   __shared__ double red[6][kWaves];
@@ -45,8 +51,9 @@ __global__ __launch_bounds__(kCondThreads) void composite_condition_kernel(const
   const int item = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* r = ref + (long)item * L;
   const float* e = est + (long)(ymap ? ymap[item] : item) * L;
+  const int len = lens ? lens[item / n] : L;  // rows are L apart; the item's own samples
   double sr = 0.0, se = 0.0, xr = -INFINITY, xe = -INFINITY, nr = -INFINITY, ne = -INFINITY;  // n*: max of -x
-  for (int t = threadIdx.x; t < L; t += kCondThreads) {
+  for (int t = threadIdx.x; t < len; t += kCondThreads) {
     const double a = r[t], b = e[t];
     sr += a;
     se += b;
@@ -80,7 +87,7 @@ __global__ __launch_bounds__(kCondThreads) void composite_condition_kernel(const
       m4 = fmax(m4, red[4][w]);
       m5 = fmax(m5, red[5][w]);
     }
-    const double mr = s0 / L, me = s1 / L;
+    const double mr = s0 / len, me = s1 / len;
     // max |x - mean| is reached at the largest or the smallest sample (rounding is monotone)
     const double ar = fmax(m2 - mr, m3 + mr), ae = fmax(m4 - me, m5 + me);
     par[0] = mr;
@@ -90,7 +97,7 @@ __global__ __launch_bounds__(kCondThreads) void composite_condition_kernel(const
   __syncthreads();
   const double mr = par[0], me = par[1], sc = par[2];
   double S = 0.0, N = 0.0;
-  for (int t = threadIdx.x; t < L; t += kCondThreads) {
+  for (int t = threadIdx.x; t < len; t += kCondThreads) {
     const double c = (double)r[t] - mr, p = ((double)e[t] - me) * sc, d = c - p;
     S += c * c;
     N += d * d;
@@ -195,6 +202,7 @@ template <int W, int NFFT, int P>
 __global__ __launch_bounds__(256) void composite_frame_kernel(const float* __restrict__ ref,
                                                               const float* __restrict__ est,
                                                               const int* __restrict__ ymap, int L, int F,
+                                                              const int* __restrict__ Fb, int n,
                                                               const double* __restrict__ win, CompositeBands bands,
                                                               const double* __restrict__ bweights,
                                                               const double* __restrict__ cond,
@@ -208,6 +216,8 @@ __global__ __launch_bounds__(256) void composite_frame_kernel(const float* __res
   __shared__ double edb[4][2][kBands];
   const int item = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int Fi = Fb ? Fb[item / n] : F;  // the item's frames; F stays the row stride of llr / wss / ssnr
+  if ((int)blockIdx.x * 4 >= Fi) return;  // uniform over the workgroup
   for (int t = threadIdx.x; t < NFFT / 2; t += 256) {
     double s, c;
     sincospi((double)t / (NFFT / 2), &s, &c);  // exp(-2 pi i t / NFFT)
@@ -215,7 +225,7 @@ __global__ __launch_bounds__(256) void composite_frame_kernel(const float* __res
   }
   for (int t = threadIdx.x; t < W; t += 256) wn[t] = win[t];
   const int f = blockIdx.x * 4 + wave;
-  const bool valid = f < F;
+  const bool valid = f < Fi;
   const double* cd = cond + (long)item * COMPOSITE_COND;
   const double mr = cd[0], me = cd[1], sc = cd[2];
   const float* r = ref + (long)item * L + (long)(valid ? f : 0) * kHop;
@@ -339,11 +349,17 @@ __global__ __launch_bounds__(256) void composite_frame_kernel(const float* __res
 __global__ __launch_bounds__(256) void composite_finish_kernel(const double* __restrict__ llr,
                                                                const double* __restrict__ wss,
                                                                const double* __restrict__ ssnr, int F, int k,
+                                                               const int* __restrict__ Fb,
+                                                               const int* __restrict__ kb, int n,
                                                                double* __restrict__ out) {
   __shared__ double tile[kTile];
   __shared__ double red[4];
   const int item = blockIdx.x, m = blockIdx.y;  // m is uniform over the workgroup
   const double* v = (m == 0 ? llr : m == 1 ? wss : ssnr) + (long)item * F;
+  if (Fb) {  // the item's own frame and trimmed counts; the rows stay F apart
+    F = Fb[item / n];
+    k = kb[item / n];
+  }
   double acc = 0.0;
   if (m == 2) {
     for (int i = threadIdx.x; i < F; i += 256) acc += v[i];
@@ -383,15 +399,18 @@ bool composite_shape(int fs, CompositeShape* s) {
 }
 
 void launch_composite(int fs, const float* ref, const float* est, const int* ymap, int items, int L, int F, int k,
-                      const double* win, const CompositeBands& bands, const double* bweights, double* cond,
+                      const int* lens, const int* Fb, const int* kb, int n, const double* win,
+                      const CompositeBands& bands, const double* bweights, double* cond,
                       double* llr, double* wss, double* ssnr, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(composite_condition_kernel, dim3(items), dim3(kCondThreads), 0, st, ref, est, ymap, L, cond);
+  hipLaunchKernelGGL(composite_condition_kernel, dim3(items), dim3(kCondThreads), 0, st, ref, est, ymap, L, lens, n,
+                     cond);
   const dim3 grid((F + 3) / 4, items);
   if (fs == 16000)
-    hipLaunchKernelGGL((composite_frame_kernel<480, 1024, 16>), grid, dim3(256), 0, st, ref, est, ymap, L, F, win,
-                       bands, bweights, cond, llr, wss, ssnr);
+    hipLaunchKernelGGL((composite_frame_kernel<480, 1024, 16>), grid, dim3(256), 0, st, ref, est, ymap, L, F, Fb, n,
+                       win, bands, bweights, cond, llr, wss, ssnr);
   else
-    hipLaunchKernelGGL((composite_frame_kernel<240, 512, 10>), grid, dim3(256), 0, st, ref, est, ymap, L, F, win,
-                       bands, bweights, cond, llr, wss, ssnr);
-  hipLaunchKernelGGL(composite_finish_kernel, dim3(items, 3), dim3(256), 0, st, llr, wss, ssnr, F, k, out);
+    hipLaunchKernelGGL((composite_frame_kernel<240, 512, 10>), grid, dim3(256), 0, st, ref, est, ymap, L, F, Fb, n,
+                       win, bands, bweights, cond, llr, wss, ssnr);
+  hipLaunchKernelGGL(composite_finish_kernel, dim3(items, 3), dim3(256), 0, st, llr, wss, ssnr, F, k, Fb, kb,
+                     n, out);
 }

@@ -2664,7 +2664,7 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
     if (!ref || !est || B <= 0 || n <= 0 || n > 4 || L <= 0) fail(DSN_EINVAL, "dsn_si_sdr_pit: bad arguments (n <= 4)");
     hipStream_t st = (hipStream_t)stream;
     double* dd = ctx->wsbuf<double>("sisdr", (long)B * n * n * 3);
-    launch_sisdr_dots(ref, est, B, n, L, dd, st);
+    launch_sisdr_dots(ref, est, B, n, L, nullptr, dd, st);
     std::vector<double> h((size_t)B * n * n * 3);
     HIPCHK(hipMemcpyAsync(h.data(), dd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2693,6 +2693,22 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
   });
 }
 
+// The ragged metric calls (dsn_si_bss_eval_ragged, dsn_stoi_ragged, dsn_composite_ragged) read [B, n, Lmax] batches
+// whose item b holds lens[b] samples.  check_item_lens is their refusal, made before anything is allocated or
+// launched; upload_item_ints copies the per-item tables a call derived from lens (asynchronously on `st` from `h`,
+// which the caller keeps alive until it has synchronised) into the workspace buffer `buf`.
+static void check_item_lens(const char* who, const int32_t* lens, int B, int Lmax) {
+  if (!lens) fail(DSN_EINVAL, "%s: lens is null", who);
+  for (int b = 0; b < B; ++b)
+    if (lens[b] < 1 || lens[b] > Lmax)
+      fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, b, (int)lens[b], Lmax);
+}
+static const int* upload_item_ints(dsn_ctx* ctx, const char* buf, const std::vector<int>& h, hipStream_t st) {
+  int* d = ctx->wsbuf<int>(buf, (long)h.size());
+  HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+  return d;
+}
+
 // SI-SDR / SI-SIR / SI-SAR of every estimate against the references (the decomposition of bss_eval with a
 // one-tap, i.e. scale-invariant, distortion filter; evaluate_latent.py:118-136 calls
 // fast_bss_eval.si_bss_eval_sources(ref, est, zero_mean=False, compute_permutation=True, clamp_db=100)):
@@ -2704,16 +2720,26 @@ int dsn_si_sdr_pit(dsn_ctx* ctx, const float* ref, const float* est, int B, int 
 // Device: all inner products (two launches of the dots kernel: ref x est and ref x ref), fp64 accumulation;
 // host: the n <= 4 Gram solves and the permutation (perm_by: 0 = best mean SI-SDR, 1 = best mean SI-SIR --
 // bss_eval's convention, "order according to SIR" evaluate_latent.py:124).  Values clamped to +-clamp_db.
-int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int perm_by, float clamp_db,
-                    float* si_sdr_out, float* si_sir_out, float* si_sar_out, int* perm_out, void* stream) {
+// With lens (ragged) item b's inner products run over its first lens[b] samples of the Lmax-strided rows.
+// dsn_si_bss_eval (lens null, ragged false) and dsn_si_bss_eval_ragged (`who` names the entry point in errors)
+static int si_bss_eval_call(dsn_ctx* ctx, const char* who, const float* ref, const float* est, int B, int n, int L,
+                            const int32_t* lens, bool ragged, int perm_by, float clamp_db, float* si_sdr_out,
+                            float* si_sir_out, float* si_sar_out, int* perm_out, void* stream) {
   return guarded(ctx, [&] {
     if (!ref || !est || B <= 0 || n <= 0 || n > 4 || L <= 0 || perm_by < 0 || perm_by > 1)
-      fail(DSN_EINVAL, "dsn_si_bss_eval: bad arguments (n <= 4, perm_by 0|1)");
+      fail(DSN_EINVAL, "%s: bad arguments (n <= 4, perm_by 0|1)", who);
+    if (ragged) check_item_lens(who, lens, B, L);
     hipStream_t st = (hipStream_t)stream;
     const size_t cnt = (size_t)B * n * n * 3;
     double* dd = ctx->wsbuf<double>("sibss", (long)cnt * 2);
-    launch_sisdr_dots(ref, est, B, n, L, dd, st);
-    launch_sisdr_dots(ref, ref, B, n, L, dd + cnt, st);
+    std::vector<int> hl;
+    const int* dlens = nullptr;
+    if (ragged) {
+      hl.assign(lens, lens + B);
+      dlens = upload_item_ints(ctx, "sibss_lens", hl, st);
+    }
+    launch_sisdr_dots(ref, est, B, n, L, dlens, dd, st);
+    launch_sisdr_dots(ref, ref, B, n, L, dlens, dd + cnt, st);
     std::vector<double> h(cnt * 2);
     HIPCHK(hipMemcpyAsync(h.data(), dd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2732,37 +2758,38 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
           G[i][j] = h[cnt + (((size_t)b * n + i) * n + j) * 3];
         }
       for (int j = 0; j < n; ++j) {
-        // solve G c = X[:, j] by Gaussian elimination with partial pivoting (fp64, n <= 4)
-        double A[4][5];
+        // solve G c = X[:, j] by Gaussian elimination with partial pivoting (fp64, n <= 4).  A column without a pivot
+        // (a reference inside the span of the earlier ones, as with fewer samples than sources) keeps the coefficient
+        // 0: the system is consistent, so the rest still gives the projection on the span.  With full rank the
+        // arithmetic is the plain elimination's.
+        double A[4][5], gmax = 0.0;
         for (int r = 0; r < n; ++r) {
           for (int c = 0; c < n; ++c) A[r][c] = G[r][c];
           A[r][n] = X[r][j];
+          gmax = std::max(gmax, G[r][r]);
         }
-        bool singular = false;
+        const double floor_ = std::max(1e-300, 1e-14 * gmax);
+        int pcol[4], rank = 0;
         for (int c = 0; c < n; ++c) {
-          int piv = c;
-          for (int r = c + 1; r < n; ++r)
+          int piv = rank;
+          for (int r = rank + 1; r < n; ++r)
             if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
-          if (fabs(A[piv][c]) < 1e-300) {
-            singular = true;
-            break;
+          if (fabs(A[piv][c]) < floor_) continue;
+          if (piv != rank)
+            for (int k = 0; k <= n; ++k) std::swap(A[piv][k], A[rank][k]);
+          for (int r = rank + 1; r < n; ++r) {
+            const double f = A[r][c] / A[rank][c];
+            for (int k = c; k <= n; ++k) A[r][k] -= f * A[rank][k];
           }
-          if (piv != c)
-            for (int k = 0; k <= n; ++k) std::swap(A[piv][k], A[c][k]);
-          for (int r = c + 1; r < n; ++r) {
-            const double f = A[r][c] / A[c][c];
-            for (int k = c; k <= n; ++k) A[r][k] -= f * A[c][k];
-          }
+          pcol[rank++] = c;
         }
         double cvec[4] = {0, 0, 0, 0}, pe = 0;
-        if (!singular) {
-          for (int r = n - 1; r >= 0; --r) {
-            double acc = A[r][n];
-            for (int k = r + 1; k < n; ++k) acc -= A[r][k] * cvec[k];
-            cvec[r] = acc / A[r][r];
-          }
-          for (int k = 0; k < n; ++k) pe += cvec[k] * X[k][j];  // |P est_j|^2 = c^T G c = c^T x
+        for (int r = rank - 1; r >= 0; --r) {
+          double acc = A[r][n];
+          for (int q = r + 1; q < rank; ++q) acc -= A[r][pcol[q]] * cvec[pcol[q]];
+          cvec[pcol[r]] = acc / A[r][pcol[r]];
         }
+        for (int k = 0; k < n; ++k) pe += cvec[k] * X[k][j];  // |P est_j|^2 = c^T G c = c^T x
         pe = std::min(std::max(pe, 0.0), ee[j]);
         sar[j] = db(pe, ee[j] - pe);
         for (int i = 0; i < n; ++i) {
@@ -2785,6 +2812,18 @@ int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int
       }
     }
   });
+}
+
+int dsn_si_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int perm_by, float clamp_db,
+                    float* si_sdr_out, float* si_sir_out, float* si_sar_out, int* perm_out, void* stream) {
+  return si_bss_eval_call(ctx, "dsn_si_bss_eval", ref, est, B, n, L, nullptr, false, perm_by, clamp_db, si_sdr_out,
+                          si_sir_out, si_sar_out, perm_out, stream);
+}
+int dsn_si_bss_eval_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                           int perm_by, float clamp_db, float* si_sdr_out, float* si_sir_out, float* si_sar_out,
+                           int* perm_out, void* stream) {
+  return si_bss_eval_call(ctx, "dsn_si_bss_eval_ragged", ref, est, B, n, L, lens, true, perm_by, clamp_db, si_sdr_out,
+                          si_sir_out, si_sar_out, perm_out, stream);
 }
 
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
@@ -2857,36 +2896,58 @@ static const int* upload_item_map(dsn_ctx* ctx, const char* who, const char* buf
 // STOI / ESTOI of every estimate against its reference (pystoi.stoi(ref, est, fs, extended), restated in
 // tests/stoi_restatement.py).  Device: resampling, silent-frame removal, STFT envelopes and segment scores
 // (stoi.hip); host: the filter design, the band table and the permutation map.
-int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, int extended,
-             const int* perm, float* out, int* frames_out, void* stream) {
+// dsn_stoi (lens null, ragged false) and dsn_stoi_ragged (`who` names the entry point in errors): with lens the host
+// also derives every item's 10 kHz frame count, F_b = (ceil(lens[b] up / down) - 256) / 128 + 1 or 0, and uploads
+// lens and F_b together ("stoi_lens": [2][B]); L sizes the buffers and grids.
+static int stoi_call(dsn_ctx* ctx, const char* who, const float* ref, const float* est, int B, int n, int L,
+                     const int32_t* lens, bool ragged, int fs, int extended, const int* perm, float* out,
+                     int* frames_out, void* stream) {
   return guarded(ctx, [&] {
     if (!ref || !est || !out || B <= 0 || n <= 0 || L <= 0)
-      fail(DSN_EINVAL, "dsn_stoi: bad arguments (ref, est, out non-null, B, n, L > 0)");
-    if (n > 4) fail(DSN_EINVAL, "dsn_stoi: n = %d sources (at most 4)", n);
-    if (fs <= 0) fail(DSN_EINVAL, "dsn_stoi: fs = %d (must be positive)", fs);
-    if (extended != 0 && extended != 1) fail(DSN_EINVAL, "dsn_stoi: extended = %d (0 or 1)", extended);
+      fail(DSN_EINVAL, "%s: bad arguments (ref, est, out non-null, B, n, L > 0)", who);
+    if (n > 4) fail(DSN_EINVAL, "%s: n = %d sources (at most 4)", who, n);
+    if (fs <= 0) fail(DSN_EINVAL, "%s: fs = %d (must be positive)", who, fs);
+    if (extended != 0 && extended != 1) fail(DSN_EINVAL, "%s: extended = %d (0 or 1)", who, extended);
+    if (ragged) check_item_lens(who, lens, B, L);
     const int items = B * n;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<int> ymap;
-    const int* dmap = upload_item_map(ctx, "dsn_stoi", "stoi_map", perm, B, n, ymap, st);
+    std::vector<int> ymap, hl;
+    const int* dmap = upload_item_map(ctx, who, "stoi_map", perm, B, n, ymap, st);
+    const int* dlens = nullptr;  // [2][B]: samples, then 10 kHz frames
+    auto frames_of = [](long n10) { return n10 >= 256 ? (int)((n10 - 256) / 128 + 1) : 0; };
     // the 10 kHz signals: the inputs themselves, or their resampled copies [2][items][n10]
     const float* xs = ref;
     const float* ys = est;
     const int* xymap = dmap;
     long n10 = L;
+    int up = 1, down = 1;
+    const dsn_ctx::StoiFilter* f = nullptr;
     if (fs != 10000) {
-      const dsn_ctx::StoiFilter& f = stoi_filter(ctx, fs);
-      n10 = ((long)L * f.up + f.down - 1) / f.down;
-      if (n10 > (1L << 30)) fail(DSN_EINVAL, "dsn_stoi: %ld samples at 10 kHz (L = %d too long)", n10, L);
+      f = &stoi_filter(ctx, fs);
+      up = f->up;
+      down = f->down;
+      n10 = ((long)L * up + down - 1) / down;
+      if (n10 > (1L << 30)) fail(DSN_EINVAL, "%s: %ld samples at 10 kHz (L = %d too long)", who, n10, L);
+    }
+    if (ragged) {
+      hl.resize(2 * (size_t)B);
+      for (int b = 0; b < B; ++b) {
+        hl[b] = lens[b];
+        hl[B + b] = frames_of(((long)lens[b] * up + down - 1) / down);
+      }
+      dlens = upload_item_ints(ctx, "stoi_lens", hl, st);
+    }
+    if (f) {
       float* rs = ctx->wsbuf<float>("stoi_rs", 2 * items * n10);
-      launch_stoi_resample(ref, est, dmap, items, L, f.taps, f.ntaps, f.up, f.down, f.n_pre_pad, f.n_pre_remove,
-                           (int)n10, rs, st);
+      launch_stoi_resample(ref, est, dmap, items, L, dlens, n, f->taps, f->ntaps, up, down, f->n_pre_pad,
+                           f->n_pre_remove, (int)n10, rs, st);
       xs = rs;
       ys = rs + items * n10;
       xymap = nullptr;  // the resampler already placed est source perm[i] at row i
     }
-    const int F = n10 >= 256 ? (int)((n10 - 256) / 128 + 1) : 0;
+    const int F = frames_of(n10);
     if (F == 0) {  // not one frame: no STFT frames at all
+      HIPCHK(hipStreamSynchronize(st));  // the uploads above read ymap and hl
       for (int i = 0; i < items; ++i) {
         out[i] = 1e-5f;
         if (frames_out) frames_out[i] = 0;
@@ -2918,7 +2979,8 @@ int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int
     double* part = ctx->wsbuf<double>("stoi_part", (long)items * Jmax);
     double* score = ctx->wsbuf<double>("stoi_score", items);
     int* frames = ctx->wsbuf<int>("stoi_frames", items);
-    launch_stoi_frames(xs, ys, n10, xymap, items, F, bands, extended, en, idx, Kc, tob, part, score, frames, st);
+    launch_stoi_frames(xs, ys, n10, xymap, items, F, dlens ? dlens + B : nullptr, n, bands, extended, en, idx, Kc, tob,
+                       part, score, frames, st);
     HIPCHK(hipGetLastError());
     std::vector<double> hs(items);
     std::vector<int> hf(items);
@@ -2930,6 +2992,15 @@ int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int
       if (frames_out) frames_out[i] = hf[i];
     }
   });
+}
+
+int dsn_stoi(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, int extended,
+             const int* perm, float* out, int* frames_out, void* stream) {
+  return stoi_call(ctx, "dsn_stoi", ref, est, B, n, L, nullptr, false, fs, extended, perm, out, frames_out, stream);
+}
+int dsn_stoi_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens, int fs,
+                    int extended, const int* perm, float* out, int* frames_out, void* stream) {
+  return stoi_call(ctx, "dsn_stoi_ragged", ref, est, B, n, L, lens, true, fs, extended, perm, out, frames_out, stream);
 }
 
 // The window 0.5 (1 - cos(2 pi k / (win + 1))), k = 1 .. win, and the 25 critical-band filters of the WSS measure
@@ -2979,34 +3050,57 @@ static const dsn_ctx::CompositeTables& composite_tables(dsn_ctx* ctx, int fs, co
 // the composite scores (the reference's src/evaluate/evaluate_covl.py, restated in tests/composite_restatement.py).
 // Device: conditioning, the per-frame measures and their trimmed means (composite.hip); host: the window, the filter
 // table, k = round(0.95 F), the permutation map and the composite arithmetic.
-int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
-                  const float* pesq, const DsnCompositeOut* out, void* stream) {
+// dsn_composite (lens null, ragged false) and dsn_composite_ragged (`who` names the entry point in errors): with lens
+// the host forms F and k for every item by the same two rules and uploads lens, F_b and k_b together ("comp_lens":
+// [3][B]); L sizes the buffers and grids.
+static int composite_call(dsn_ctx* ctx, const char* who, const float* ref, const float* est, int B, int n, int L,
+                          const int32_t* lens, bool ragged, int fs, const int* perm, const float* pesq,
+                          const DsnCompositeOut* out, void* stream) {
   return guarded(ctx, [&] {
     if (!ref || !est || !out || B <= 0 || n <= 0 || L <= 0)
-      fail(DSN_EINVAL, "dsn_composite: bad arguments (ref, est, out non-null, B, n, L > 0)");
-    if (n > 4) fail(DSN_EINVAL, "dsn_composite: n = %d sources (at most 4)", n);
-    if ((long)B * n > 65535) fail(DSN_EINVAL, "dsn_composite: B * n = %ld items (at most 65535)", (long)B * n);
+      fail(DSN_EINVAL, "%s: bad arguments (ref, est, out non-null, B, n, L > 0)", who);
+    if (n > 4) fail(DSN_EINVAL, "%s: n = %d sources (at most 4)", who, n);
+    if ((long)B * n > 65535) fail(DSN_EINVAL, "%s: B * n = %ld items (at most 65535)", who, (long)B * n);
     CompositeShape sh;
-    if (!composite_shape(fs, &sh)) fail(DSN_EINVAL, "dsn_composite: fs = %d (kernels exist for 8000 and 16000)", fs);
-    if ((out->csig || out->cbak || out->covl) && !pesq)
-      fail(DSN_EINVAL, "dsn_composite: csig / cbak / covl need pesq");
+    if (!composite_shape(fs, &sh)) fail(DSN_EINVAL, "%s: fs = %d (kernels exist for 8000 and 16000)", who, fs);
+    if ((out->csig || out->cbak || out->covl) && !pesq) fail(DSN_EINVAL, "%s: csig / cbak / covl need pesq", who);
     // the reference's int(L / hop - win / hop); win = 4 hop at the supported rates
-    const int F = L / sh.hop - sh.win / sh.hop;
+    auto frames_of = [&](int len) { return len / sh.hop - sh.win / sh.hop; };
+    auto trimmed = [](int frames) { return (int)nearbyint(frames * 0.95); };  // Python's round(): half to even
+    const int F = frames_of(L);
     if (F < 1)
-      fail(DSN_EINVAL, "dsn_composite: L = %d is shorter than one frame (%d samples needed at fs = %d)", L,
+      fail(DSN_EINVAL, "%s: L = %d is shorter than one frame (%d samples needed at fs = %d)", who, L,
            sh.win + sh.hop, fs);
-    const int k = (int)nearbyint(F * 0.95);  // Python's round(): half to even
+    if (ragged) {
+      check_item_lens(who, lens, B, L);
+      for (int b = 0; b < B; ++b)
+        if (frames_of(lens[b]) < 1)
+          fail(DSN_EINVAL, "%s: item %d (lens[%d] = %d) is shorter than one frame (%d samples needed at fs = %d)", who,
+               b, b, (int)lens[b], sh.win + sh.hop, fs);
+    }
+    const int k = trimmed(F);
     const int items = B * n;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<int> ymap;
-    const int* dmap = upload_item_map(ctx, "dsn_composite", "comp_map", perm, B, n, ymap, st);
+    std::vector<int> ymap, hl;
+    const int* dmap = upload_item_map(ctx, who, "comp_map", perm, B, n, ymap, st);
+    const int* dlens = nullptr;  // [3][B]: samples, frames, trimmed counts
+    if (ragged) {
+      hl.resize(3 * (size_t)B);
+      for (int b = 0; b < B; ++b) {
+        hl[b] = lens[b];
+        hl[B + b] = frames_of(lens[b]);
+        hl[2 * B + b] = trimmed(hl[B + b]);
+      }
+      dlens = upload_item_ints(ctx, "comp_lens", hl, st);
+    }
     const dsn_ctx::CompositeTables& tab = composite_tables(ctx, fs, sh);
     double* cond = ctx->wsbuf<double>("comp_cond", (long)items * COMPOSITE_COND);
     double* fl = ctx->wsbuf<double>("comp_llr", (long)items * F);
     double* fw = ctx->wsbuf<double>("comp_wss", (long)items * F);
     double* fsn = ctx->wsbuf<double>("comp_ssnr", (long)items * F);
     double* res = ctx->wsbuf<double>("comp_out", (long)items * 3);
-    launch_composite(fs, ref, est, dmap, items, L, F, k, tab.win, tab.bands, tab.bweights, cond, fl, fw, fsn, res, st);
+    launch_composite(fs, ref, est, dmap, items, L, F, k, dlens, dlens ? dlens + B : nullptr,
+                     dlens ? dlens + 2 * B : nullptr, n, tab.win, tab.bands, tab.bweights, cond, fl, fw, fsn, res, st);
     HIPCHK(hipGetLastError());
     std::vector<double> hc((size_t)items * COMPOSITE_COND), hr((size_t)items * 3);
     HIPCHK(hipMemcpyAsync(hc.data(), cond, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st));
@@ -3020,7 +3114,7 @@ int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n
       if (out->wss) out->wss[i] = w;
       if (out->segsnr) out->segsnr[i] = s;
       if (out->snr) out->snr[i] = (float)hc[(size_t)i * COMPOSITE_COND + 3];
-      if (out->frames) out->frames[i] = F;
+      if (out->frames) out->frames[i] = ragged ? hl[B + i / n] : F;
       if (pesq) {
         const double q = pesq[i];
         if (out->csig) out->csig[i] = (float)mos(3.093 - 1.029 * l + 0.603 * q - 0.009 * w);
@@ -3029,6 +3123,15 @@ int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n
       }
     }
   });
+}
+
+int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
+                  const float* pesq, const DsnCompositeOut* out, void* stream) {
+  return composite_call(ctx, "dsn_composite", ref, est, B, n, L, nullptr, false, fs, perm, pesq, out, stream);
+}
+int dsn_composite_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                         int fs, const int* perm, const float* pesq, const DsnCompositeOut* out, void* stream) {
+  return composite_call(ctx, "dsn_composite_ragged", ref, est, B, n, L, lens, true, fs, perm, pesq, out, stream);
 }
 
 // torch.hann_window(win) (periodic: 0.5 - 0.5 cos(2 pi k / win)) centred in fft zeros as torch.stft pads it,

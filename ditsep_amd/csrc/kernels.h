@@ -146,8 +146,10 @@ void launch_ncsn_output(const float* pyr, int Cp, const float* t, const float* w
                         int B, int H, int T, int Wp, float* score, hipStream_t s);
 
 // ---- metrics -----------------------------------------------------------------------------------------
-// out[(b*n + i)*n + j][3] = (<ref_i, est_j>, |ref_i|^2, |est_j|^2) in fp64
-void launch_sisdr_dots(const float* ref, const float* est, int B, int n, int L, double* out, hipStream_t s);
+// out[(b*n + i)*n + j][3] = (<ref_i, est_j>, |ref_i|^2, |est_j|^2) in fp64.  Rows are L apart; lens [B] (device,
+// nullable): item b sums its first lens[b] samples only and reads nothing past them
+void launch_sisdr_dots(const float* ref, const float* est, int B, int n, int L, const int* lens, double* out,
+                       hipStream_t s);
 
 // ---- STOI / ESTOI (stoi.hip) ----------------------------------------------------------------------------
 // one-third-octave band b covers the 512-point FFT bins [lo[b], hi[b])
@@ -155,17 +157,20 @@ struct StoiBands {
   int lo[15], hi[15];
 };
 // polyphase resampling of ref and est [items][n_in] (est row ymap[item], or item when ymap is null) to
-// out [2][items][n_out] with fp64 taps [ntaps] already scaled by `up` (scipy.signal.resample_poly's alignment)
-void launch_stoi_resample(const float* ref, const float* est, const int* ymap, int items, int n_in,
-                          const double* taps, int ntaps, int up, int down, int n_pre_pad, int n_pre_remove, int n_out,
-                          float* out, hipStream_t s);
+// out [2][items][n_out] with fp64 taps [ntaps] already scaled by `up` (scipy.signal.resample_poly's alignment).
+// lens [items / n] (device, nullable): the items of batch entry b hold lens[b] <= n_in samples and get
+// ceil(lens[b] up / down) <= n_out outputs; the rest of their output rows is left as it was
+void launch_stoi_resample(const float* ref, const float* est, const int* ymap, int items, int n_in, const int* lens,
+                          int n, const double* taps, int ntaps, int up, int down, int n_pre_pad, int n_pre_remove,
+                          int n_out, float* out, hipStream_t s);
 // the rest of STOI (extended = 0) or ESTOI (1) on 10 kHz signals x = xs + item*stride, y = ys + ymap[item]*stride
-// (ymap nullable) with F = (len - 256)/128 + 1 frames each.  Work buffers: en [items*F] f64, idx [items*F],
-// Kc [items], tob [items*2*15*max(F-1,1)] f64, part [items*max(F-30,1)] f64.  -> score [items] f64 and the STFT
+// (ymap nullable) with F = (len - 256)/128 + 1 frames each; with Fb [items / n] (device, nullable) the items of batch
+// entry b have Fb[b] <= F frames (0: no frame, score 1e-5) and F sizes the buffers and grids.  Work buffers:
+// en [items*F] f64, idx [items*F], Kc [items], tob [items*2*15*max(F-1,1)] f64, part [items*max(F-30,1)] f64.  -> score [items] f64 and the STFT
 // frame count left after silent-frame removal, frames [items].
 void launch_stoi_frames(const float* xs, const float* ys, long stride, const int* ymap, int items, int F,
-                        StoiBands bands, int extended, double* en, int* idx, int* Kc, double* tob, double* part,
-                        double* score, int* frames, hipStream_t s);
+                        const int* Fb, int n, StoiBands bands, int extended, double* en, int* idx, int* Kc,
+                        double* tob, double* part, double* score, int* frames, hipStream_t s);
 
 // ---- LLR / WSS / segmental SNR of the composite measures (composite.hip) ----------------------------------
 #define COMPOSITE_BANDS 25
@@ -184,10 +189,11 @@ struct CompositeBands {
 // ref, est [items][L] (est row ymap[item], or item when ymap is null), F >= 1 frames per item, win [shape.win] the
 // fp64 window, k = round(0.95 F).  Work buffers: cond [items*COMPOSITE_COND], llr / wss / ssnr [items*F] (the
 // per-frame values).  -> out [items][3] = LLR, WSS (means of the k smallest frames), segmental SNR (mean); the
-// overall SNR is cond[item][3].  All fp64.
+// overall SNR is cond[item][3].  All fp64.  lens, Fb, kb [items / n] (device, all null or none): the items of batch
+// entry b hold lens[b] <= L samples, Fb[b] in [1, F] frames and k = kb[b]; rows stay L and F apart.
 void launch_composite(int fs, const float* ref, const float* est, const int* ymap, int items, int L, int F, int k,
-                      const double* win, const CompositeBands& bands, const double* bweights, double* cond,
-                      double* llr, double* wss, double* ssnr, double* out, hipStream_t s);
+                      const int* lens, const int* Fb, const int* kb, int n, const double* win,
+                      const CompositeBands& bands, const double* bweights, double* cond, double* llr, double* wss, double* ssnr, double* out, hipStream_t s);
 
 // ---- multi-resolution STFT and time-domain reconstruction losses (mrstft.hip) -------------------------------
 #define MRSTFT_MAX_SRC 4

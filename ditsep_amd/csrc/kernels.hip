@@ -1152,17 +1152,20 @@ void launch_snake_params(const float* alpha, const float* beta, float* a, float*
 // ------------------------------------------------------------------ SI-SDR dot products
 // For every (item, ref source i, est source j): <ref_i, est_j>, and the energies |ref_i|^2, |est_j|^2.
 // One workgroup per (item, i, j); wave shuffles + LDS tree; fp32 products accumulated in fp64.
+// Rows are L apart; item b sums its first lens[b] samples (all L when lens is null) and reads nothing past them.
 namespace {
 __global__ __launch_bounds__(256) void sisdr_dots_kernel(const float* __restrict__ ref, const float* __restrict__ est,
-                                                         int n, int L, double* __restrict__ out) {
+                                                         int n, int L, const int* __restrict__ lens,
+                                                         double* __restrict__ out) {
   __shared__ double red[3][4];
   const int b = blockIdx.x / (n * n);
   const int ij = blockIdx.x - b * n * n;
   const int i = ij / n, j = ij - i * n;
   const float* r = ref + ((long)b * n + i) * L;
   const float* e = est + ((long)b * n + j) * L;
+  const int len = lens ? lens[b] : L;
   double sre = 0.0, srr = 0.0, see = 0.0;
-  for (int k = threadIdx.x; k < L; k += blockDim.x) {
+  for (int k = threadIdx.x; k < len; k += blockDim.x) {
     const double rv = r[k], ev = e[k];
     sre += rv * ev;
     srr += rv * rv;
@@ -1190,6 +1193,7 @@ __global__ __launch_bounds__(256) void sisdr_dots_kernel(const float* __restrict
 }
 }  // namespace
 
-void launch_sisdr_dots(const float* ref, const float* est, int B, int n, int L, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(sisdr_dots_kernel, dim3(B * n * n), dim3(256), 0, st, ref, est, n, L, out);
+void launch_sisdr_dots(const float* ref, const float* est, int B, int n, int L, const int* lens, double* out,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(sisdr_dots_kernel, dim3(B * n * n), dim3(256), 0, st, ref, est, n, L, lens, out);
 }

@@ -9,6 +9,11 @@
 //   segment    per 30-frame segment: the STOI band correlations or the ESTOI row/column-normalised inner product
 //   finish     per item: fixed-order fp64 sum over the segments; 1e-5 when fewer than 30 STFT frames remain
 // Every reduction has a fixed order (no atomics): two calls on the same input give bit-identical scores.
+// Ragged batches (dsn_stoi_ragged): rows stay Lmax apart and batch entry b = item / n brings its own sample count
+// lens[b] and frame count Fb[b] (null arrays: every item is full length).  The resampler stops its taps at
+// lens[b] - 1, energy and mask run over Fb[b] frames, and the later stages follow the kept-frame list, so nothing
+// past an item's end is read; buffers and grids are sized by the longest item.  Every sum runs in the order the
+// item's own length fixes: an item scores the same bits in a padded batch as alone.
 #include "kernels.h"
 
 namespace {
@@ -32,29 +37,40 @@ __device__ inline double wave_sum(double v) {
 // out[sig][item][i], sig 0 = ref, 1 = est (est row ymap[item], or item when ymap is null).
 // y[i] = sum_m x[m] h[c - m up], c = (i + n_pre_remove) down - n_pre_pad, 0 <= c - m up < ntaps: scipy's
 // upfirdn on the zero-padded filter, the pre-padding removed.
+// Rows are n_in apart; an item of batch entry b = item / n holds lens[b] samples (n_in when lens is null) and gives
+// ceil(lens[b] up / down) outputs of its n_out-long output row: no tap reaches past lens[b] - 1.
 __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ ref, const float* __restrict__ est,
                                                             const int* __restrict__ ymap, int n_in,
+                                                            const int* __restrict__ lens, int n,
                                                             const double* __restrict__ taps, int ntaps, int up,
                                                             int down, int n_pre_pad, int n_pre_remove, int n_out,
                                                             int items, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_out) return;
   const int item = blockIdx.y, sig = blockIdx.z;
+  const int len = lens ? lens[item / n] : n_in;
+  if (i >= (lens ? (int)(((long)len * up + down - 1) / down) : n_out)) return;
   const float* x = sig == 0 ? ref + (long)item * n_in : est + (long)(ymap ? ymap[item] : item) * n_in;
   const long c = (long)(i + n_pre_remove) * down - n_pre_pad;
-  const long mhi = min(floordiv(c, up), (long)n_in - 1);
+  const long mhi = min(floordiv(c, up), (long)len - 1);
   const long mlo = max(-floordiv(-(c - ntaps + 1), up), 0L);
   double acc = 0.0;
   for (long m = mlo; m <= mhi; ++m) acc += (double)x[m] * taps[c - m * up];
   out[((long)sig * items + item) * n_out + i] = (float)acc;
 }
 
+// Frames of an item: Fb[item / n] when the batch is ragged (Fb non-null), else F.  F stays the row stride of the
+// per-frame buffers.
+__device__ inline int item_frames(const int* __restrict__ Fb, int n, int item, int F) {
+  return Fb ? Fb[item / n] : F;
+}
+
 // en[item][f] = 20 log10(|w * x[128 f : 128 f + 256]| + eps); one wave per frame
 __global__ __launch_bounds__(256) void stoi_energy_kernel(const float* __restrict__ xs, long stride, int F,
+                                                          const int* __restrict__ Fb, int n,
                                                           double* __restrict__ en) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= F) return;
+  if (f >= item_frames(Fb, n, blockIdx.y, F)) return;
   const float* x = xs + (long)blockIdx.y * stride + (long)f * kHop;
   double acc = 0.0;
 #pragma unroll
@@ -68,14 +84,17 @@ __global__ __launch_bounds__(256) void stoi_energy_kernel(const float* __restric
 }
 
 // per item: keep frame f iff max - 40 - en[f] < 0; idx[item][0..K) = kept frame indices in order, Kc[item] = K
-__global__ __launch_bounds__(256) void stoi_mask_kernel(const double* __restrict__ en, int F, int* __restrict__ idx,
+// (K = 0 for an item without a frame)
+__global__ __launch_bounds__(256) void stoi_mask_kernel(const double* __restrict__ en, int F,
+                                                        const int* __restrict__ Fb, int n, int* __restrict__ idx,
                                                         int* __restrict__ Kc) {
   __shared__ double wmax[4];
   __shared__ int wcnt[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double* e = en + (long)blockIdx.x * F;
+  const int Fi = item_frames(Fb, n, blockIdx.x, F);  // uniform over the workgroup
   double mx = -INFINITY;
-  for (int f = threadIdx.x; f < F; f += 256) mx = fmax(mx, e[f]);
+  for (int f = threadIdx.x; f < Fi; f += 256) mx = fmax(mx, e[f]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
   if (lane == 0) wmax[wave] = mx;
@@ -83,9 +102,9 @@ __global__ __launch_bounds__(256) void stoi_mask_kernel(const double* __restrict
   mx = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
   int* out = idx + (long)blockIdx.x * F;
   int base = 0;
-  for (int f0 = 0; f0 < F; f0 += 256) {
+  for (int f0 = 0; f0 < Fi; f0 += 256) {
     const int f = f0 + threadIdx.x;
-    const bool keep = f < F && (mx - kDynRange - e[f]) < 0.0;
+    const bool keep = f < Fi && (mx - kDynRange - e[f]) < 0.0;
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) wcnt[wave] = __popcll(bal);
     __syncthreads();
@@ -287,19 +306,19 @@ __global__ __launch_bounds__(256) void stoi_finish_kernel(const double* __restri
 
 }  // namespace
 
-void launch_stoi_resample(const float* ref, const float* est, const int* ymap, int items, int n_in,
-                          const double* taps, int ntaps, int up, int down, int n_pre_pad, int n_pre_remove, int n_out,
-                          float* out, hipStream_t st) {
+void launch_stoi_resample(const float* ref, const float* est, const int* ymap, int items, int n_in, const int* lens,
+                          int n, const double* taps, int ntaps, int up, int down, int n_pre_pad, int n_pre_remove,
+                          int n_out, float* out, hipStream_t st) {
   hipLaunchKernelGGL(stoi_resample_kernel, dim3((n_out + 255) / 256, items, 2), dim3(256), 0, st, ref, est, ymap,
-                     n_in, taps, ntaps, up, down, n_pre_pad, n_pre_remove, n_out, items, out);
+                     n_in, lens, n, taps, ntaps, up, down, n_pre_pad, n_pre_remove, n_out, items, out);
 }
 
 void launch_stoi_frames(const float* xs, const float* ys, long stride, const int* ymap, int items, int F,
-                        StoiBands bands, int extended, double* en, int* idx, int* Kc, double* tob, double* part,
-                        double* score, int* frames, hipStream_t st) {
+                        const int* Fb, int n, StoiBands bands, int extended, double* en, int* idx, int* Kc,
+                        double* tob, double* part, double* score, int* frames, hipStream_t st) {
   const int Fs = max(F - 1, 1), Jmax = max(F - kSeg, 1);
-  hipLaunchKernelGGL(stoi_energy_kernel, dim3((F + 3) / 4, items), dim3(256), 0, st, xs, stride, F, en);
-  hipLaunchKernelGGL(stoi_mask_kernel, dim3(items), dim3(256), 0, st, en, F, idx, Kc);
+  hipLaunchKernelGGL(stoi_energy_kernel, dim3((F + 3) / 4, items), dim3(256), 0, st, xs, stride, F, Fb, n, en);
+  hipLaunchKernelGGL(stoi_mask_kernel, dim3(items), dim3(256), 0, st, en, F, Fb, n, idx, Kc);
   hipLaunchKernelGGL(stoi_envelope_kernel, dim3((Fs + 3) / 4, items), dim3(256), 0, st, xs, ys, stride, ymap, F, idx,
                      Kc, bands, Fs, tob);
   hipLaunchKernelGGL(stoi_segment_kernel, dim3((Jmax + 63) / 64, items), dim3(64), 0, st, tob, Fs, Kc, extended, Jmax,

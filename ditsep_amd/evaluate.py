@@ -22,7 +22,8 @@ waveform error of each reference source against the estimate the SIR permutation
 
 Utterances of different lengths (the reference evaluates them one at a time, :238): a batch whose `mix` and `target`
 are lists of differently long tensors takes the ragged route -- `length_batches` cuts a data set into such batches
-with little padding -- in which every utterance gets what it gets alone (LatentDiffSep.separate_batch)."""
+with little padding -- in which every utterance gets what it gets alone (LatentDiffSep.separate_batch) and every
+metric above but mrstft and score_loss is one call on the padded batch with the utterances' lengths."""
 from __future__ import annotations
 
 import json
@@ -42,18 +43,21 @@ def length_batches(lengths, batch_size: int) -> list:
     return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
 
 
-def _same_length_groups(lengths) -> dict:
-    groups: dict = {}
-    for i, L in enumerate(lengths):
-        groups.setdefault(int(L), []).append(i)
-    return groups
+def _pad_items(items, Lmax: int, device) -> torch.Tensor:
+    """list of [n, L_b] -> [B, n, Lmax] float32 on `device`, zero past each item's end (the ragged metric calls read
+    nothing there)."""
+    out = torch.zeros((len(items), items[0].shape[0], Lmax), dtype=torch.float32, device=device)
+    for b, t in enumerate(items):
+        out[b, :, :t.shape[-1]] = t.to(device=device, dtype=torch.float32)
+    return out
 
 
 def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended,
-                     codec="grouped") -> dict:
+                     codec="grouped", composite=False, pesq_fn=None) -> dict:
     """One batch of differently long utterances: mixes list of [1, L_b], targets list of [n, L_b].  The timed region is
-    sampler + decode as in the dense route; the metric kernels run per group of equal L.  codec: how the encoder and
-    the decoder take the batch (Engine.encode_ragged)."""
+    sampler + decode as in the dense route; every requested metric then runs once on the padded [B, n, Lmax] pair with
+    the items' lengths (Engine.si_bss_eval / stoi / composite with lens=), each item scored as it is alone.  codec: how
+    the encoder and the decoder take the batch (Engine.encode_ragged)."""
     eng, dev = model.engine, model.engine.device
     B = len(mixes)
     y, frames = eng.encode_ragged(mixes, None, seed=seed + idx, codec=codec)
@@ -66,18 +70,29 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
     est = eng.decode_ragged(x_result, frames, lens, codec=codec)
     torch.cuda.synchronize(dev)
     t_proc = time.perf_counter() - t_s
+    Lmax, n_src = max(lens), targets[0].shape[0]
+    tgt, xr = _pad_items(targets, Lmax, dev), _pad_items(est, Lmax, dev)
+    si_sdr, si_sir, si_sar, perm = eng.si_bss_eval(tgt, xr, perm_by="sir", clamp_db=100.0, lens=lens)
+    st = eng.stoi(tgt, xr, fs, extended=stoi_extended, perm=perm, lens=lens) if stoi else None
+    comp = pq = None
+    if composite:
+        if pesq_fn is not None:
+            pq = torch.tensor([[float(pesq_fn(fs, *condition_for_pesq(targets[b][i].cpu().numpy(),
+                                                                       est[b][int(perm[b, i])].cpu().numpy())))
+                                for i in range(n_src)] for b in range(B)], dtype=torch.float32)
+        comp = eng.composite(tgt, xr, fs, perm=perm, pesq=pq, lens=lens)
     records = {}
-    for L, members in _same_length_groups(lens).items():
-        tgt = torch.stack([targets[i].to(dev) for i in members])
-        xr = torch.stack([est[i] for i in members])
-        si_sdr, si_sir, si_sar, perm = eng.si_bss_eval(tgt, xr, perm_by="sir", clamp_db=100.0)
-        st = eng.stoi(tgt, xr, fs, extended=stoi_extended, perm=perm) if stoi else None
-        for j, i in enumerate(members):
-            records[idx + i] = {"batch_idx": idx + i, "si_sdr": si_sdr[j].tolist(), "si_sir": si_sir[j].tolist(),
-                                "si_sar": si_sar[j].tolist(), "pesq": None,
-                                "stoi": None if st is None else st[j].tolist(), "nfe": nfe, "runtime": t_proc / B,
-                                "len_s": L / fs, "perm": perm[j].tolist()}
-    return {k: records[k] for k in sorted(records)}
+    for b in range(B):
+        rec = {"batch_idx": idx + b, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
+               "si_sar": si_sar[b].tolist(), "pesq": None, "stoi": None if st is None else st[b].tolist(),
+               "nfe": nfe, "runtime": t_proc / B, "len_s": lens[b] / fs, "perm": perm[b].tolist()}
+        if comp is not None:
+            for k in ("llr", "wss", "segsnr") + (("csig", "cbak", "covl") if pq is not None else ()):
+                rec[k] = comp[k][b].tolist()
+            if pq is not None:
+                rec["pesq"] = pq[b].tolist()
+        records[idx + b] = rec
+    return records
 
 
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
@@ -94,10 +109,11 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     A-weighting of `fs`, spectral convergence plus log magnitude).
 
     A batch may also be (list of mix [1,L_b], list of target [n,L_b]) with differing L_b: it takes the ragged route
-    (one sampler call on the padded batch, codec and metric kernels per group of equal length); each record carries
-    its own "len_s", "runtime" stays the batch time divided by B.  score_loss, composite and mrstft have no ragged
-    form (NotImplementedError).  codec="padded" runs the codec of a ragged batch once on the padded batch instead of
-    once per group (Engine.encode_ragged / decode_ragged); dense batches ignore it."""
+    (one sampler call on the padded batch, the codec per group of equal length, every metric once on the padded batch
+    with the items' lengths); each record carries its own "len_s", "runtime" stays the batch time divided by B, and
+    stoi, composite and pesq_fn work as above, pesq_fn on each utterance's own unpadded signals.  score_loss and mrstft
+    have no ragged form (NotImplementedError).  codec="padded" runs the codec of a ragged batch once on the padded batch
+    instead of once per group (Engine.encode_ragged / decode_ragged); dense batches ignore it."""
     from .native import check_codec_mode
     check_codec_mode(codec)
     if pesq_fn is not None and not composite:
@@ -110,10 +126,11 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     dev = model.engine.device
     for mix, target in batches:
         if isinstance(mix, (list, tuple)):
-            if score_loss or composite or mrstft:
-                raise NotImplementedError("score_loss / composite / mrstft are not implemented for ragged batches")
+            if score_loss or mrstft:
+                raise NotImplementedError("score_loss / mrstft are not implemented for ragged batches")
             results.update(_evaluate_ragged(model, list(mix), list(target), fs, idx, seed, N, corrector_steps, snr,
-                                            denoise, stoi, stoi_extended, codec=codec))
+                                            denoise, stoi, stoi_extended, codec=codec, composite=composite,
+                                            pesq_fn=pesq_fn))
             idx += len(mix)
             continue
         mix, target = mix.to(dev), target.to(dev)

@@ -34,6 +34,7 @@ EXPORTS = [
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows",
     "dsn_test_gemm", "dsn_test_kernel", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
+    "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged",
 ]
 
 
@@ -277,6 +278,30 @@ def check_ragged(score_kind: int, frames, B: int, T: int, corrector: str = "ald"
     return fr
 
 
+def composite_min_samples(fs: int) -> Optional[int]:
+    """Samples one frame plus one hop of the composite measures takes at `fs` (window 30 ms, hop a quarter of it), or
+    None for a signal rate the library has no kernel for (it refuses that rate itself)."""
+    return {8000: 300, 16000: 600}.get(int(fs))
+
+
+def check_lens(lens, B: int, Lmax: int, min_len: Optional[int] = None, what: str = "") -> list:
+    """The refusals of the ragged metric calls (include/ditsep_hip.h), raised by name before the library is touched:
+    not one sample count per item, a count outside [1, Lmax], and with min_len (the composite measures) an item shorter
+    than one frame plus one hop.  Returns the counts as a list of ints."""
+    ln = [int(v) for v in lens]
+    if len(ln) != B:
+        raise ValueError(f"lens must hold one sample count per item (B = {B}), got {len(ln)}")
+    for b, v in enumerate(ln):
+        if v < 1 or v > Lmax:
+            raise ValueError(f"sample count lens[{b}] = {v} outside [1, Lmax = {Lmax}]")
+    if min_len is not None:
+        for b, v in enumerate(ln):
+            if v < min_len:
+                raise ValueError(f"item {b} (lens[{b}] = {v}) is shorter than one frame "
+                                 f"({min_len} samples needed{what})")
+    return ln
+
+
 _lib = None
 
 
@@ -341,6 +366,11 @@ def load_library() -> C.CDLL:
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
     lib.dsn_stoi.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
     lib.dsn_composite.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(DsnCompositeOut), vp]
+    i32p = C.POINTER(C.c_int32)
+    lib.dsn_si_bss_eval_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
+    lib.dsn_stoi_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
+    lib.dsn_composite_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, C.POINTER(ci), fp,
+                                         C.POINTER(DsnCompositeOut), vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -889,28 +919,42 @@ class Engine:
         return (torch.tensor(list(sdr), dtype=torch.float32).reshape(B, n),
                 torch.tensor(list(perm), dtype=torch.long).reshape(B, n))
 
-    def si_bss_eval(self, ref, est, perm_by: str = "sir", clamp_db: float = 100.0):
+    def si_bss_eval(self, ref, est, perm_by: str = "sir", clamp_db: float = 100.0, lens=None):
         """ref, est [B,n,L] -> (si_sdr, si_sir, si_sar [B,n] dB, perm [B,n]) with the permutation solved on
-        `perm_by` ("sir" as bss_eval / the reference's evaluate_latent.py:118-124, or "sdr")."""
-        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        `perm_by` ("sir" as bss_eval / the reference's evaluate_latent.py:118-124, or "sdr").  lens (B ints, optional):
+        item b holds lens[b] samples of the L-long rows and gets, bit for bit, what it gets alone; the padding is not
+        read (dsn_si_bss_eval_ragged)."""
         B, n, L = ref.shape
+        if lens is not None:
+            lens = check_lens(lens, B, L)
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
         bufs = [(C.c_float * (B * n))() for _ in range(3)]
         perm = (C.c_int * (B * n))()
-        self._check(self.lib.dsn_si_bss_eval(self.ctx, _ptr(ref), _ptr(est), B, n, L, {"sdr": 0, "sir": 1}[perm_by],
-                                             float(clamp_db), *bufs, perm, self._stream()), "dsn_si_bss_eval")
+        by = {"sdr": 0, "sir": 1}[perm_by]
+        if lens is None:
+            self._check(self.lib.dsn_si_bss_eval(self.ctx, _ptr(ref), _ptr(est), B, n, L, by, float(clamp_db), *bufs,
+                                                 perm, self._stream()), "dsn_si_bss_eval")
+        else:
+            self._check(self.lib.dsn_si_bss_eval_ragged(self.ctx, _ptr(ref), _ptr(est), B, n, L, (C.c_int32 * B)(*lens),
+                                                        by, float(clamp_db), *bufs, perm, self._stream()),
+                        "dsn_si_bss_eval_ragged")
         out = [torch.tensor(list(b), dtype=torch.float32).reshape(B, n) for b in bufs]
         return (*out, torch.tensor(list(perm), dtype=torch.long).reshape(B, n))
 
-    def stoi(self, ref, est, fs: int, extended: bool = True, perm=None, return_frames: bool = False):
+    def stoi(self, ref, est, fs: int, extended: bool = True, perm=None, return_frames: bool = False, lens=None):
         """ref, est [B,n,L] -> [B,n] float32 STOI (extended=False) or extended STOI (True) of est against ref, as
         pystoi.stoi(ref, est, fs, extended) defines it (restated in tests/stoi_restatement.py; parity with the pystoi
         package unpinned).  perm [B,n] (optional): est source perm[b,i] is scored against ref source i.  Items with
         fewer than 30 STFT frames left after silent-frame removal score 1e-5 with a RuntimeWarning, as in pystoi;
-        return_frames=True also returns those frame counts [B,n]."""
-        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        return_frames=True also returns those frame counts [B,n].  lens (B ints, optional): item b holds lens[b]
+        samples of the L-long rows and gets, bit for bit, what it gets alone; the padding is not read; an item shorter
+        than one 10 kHz frame scores 1e-5 with 0 frames (dsn_stoi_ragged)."""
         if ref.dim() != 3 or est.shape != ref.shape:
             raise ValueError(f"ref and est must both be [B,n,L] (got {tuple(ref.shape)} and {tuple(est.shape)})")
         B, n, L = ref.shape
+        if lens is not None:
+            lens = check_lens(lens, B, L)
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
         out = (C.c_float * (B * n))()
         frames = (C.c_int * (B * n))()
         cperm = None
@@ -919,8 +963,13 @@ class Engine:
             if len(p) != B * n:
                 raise ValueError(f"perm must hold B*n = {B * n} entries (got {len(p)})")
             cperm = (C.c_int * (B * n))(*p)
-        self._check(self.lib.dsn_stoi(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), int(bool(extended)), cperm,
-                                      out, frames, self._stream()), "dsn_stoi")
+        if lens is None:
+            self._check(self.lib.dsn_stoi(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), int(bool(extended)), cperm,
+                                          out, frames, self._stream()), "dsn_stoi")
+        else:
+            self._check(self.lib.dsn_stoi_ragged(self.ctx, _ptr(ref), _ptr(est), B, n, L, (C.c_int32 * B)(*lens),
+                                                 int(fs), int(bool(extended)), cperm, out, frames, self._stream()),
+                        "dsn_stoi_ragged")
         score = torch.tensor(list(out), dtype=torch.float32).reshape(B, n)
         nfr = torch.tensor(list(frames), dtype=torch.long).reshape(B, n)
         short = (nfr < 30).nonzero().tolist()
@@ -929,17 +978,22 @@ class Engine:
                           f"removal; their score is 1e-5", RuntimeWarning, stacklevel=2)
         return (score, nfr) if return_frames else score
 
-    def composite(self, ref, est, fs: int, perm=None, pesq=None) -> dict:
+    def composite(self, ref, est, fs: int, perm=None, pesq=None, lens=None) -> dict:
         """ref, est [B,n,L] -> {"llr", "wss", "segsnr", "snr": [B,n] float32, "frames": [B,n] long}: the objective
         measures of the Hu & Loizou composite scores as the reference's evaluate_covl.py computes them (restated in
         tests/composite_restatement.py, pinned by tests/golden/composite.npz).  fs is 8000 or 16000.  perm [B,n]
         (optional): est source perm[b,i] is scored against ref source i.  With pesq [B,n] (PESQ is not computed
         here) the dict also holds "csig", "cbak" and "covl", each clipped to [1, 5].  A constant estimate gives NaN
-        for segsnr, snr and cbak (the reference rescales by max|est - mean| = 0); llr and wss stay defined."""
-        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        for segsnr, snr and cbak (the reference rescales by max|est - mean| = 0); llr and wss stay defined.  lens (B
+        ints, optional): item b holds lens[b] samples of the L-long rows and gets, bit for bit, what it gets alone,
+        "frames" included; the padding is not read; an item shorter than one frame plus one hop is refused by name
+        (dsn_composite_ragged)."""
         if ref.dim() != 3 or est.shape != ref.shape:
             raise ValueError(f"ref and est must both be [B,n,L] (got {tuple(ref.shape)} and {tuple(est.shape)})")
         B, n, L = ref.shape
+        if lens is not None:
+            lens = check_lens(lens, B, L, composite_min_samples(fs), f" at fs = {int(fs)}")
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
         keys = ["llr", "wss", "segsnr", "snr"] + (["csig", "cbak", "covl"] if pesq is not None else [])
         bufs = {k: (C.c_float * (B * n))() for k in keys}
         frames = (C.c_int * (B * n))()
@@ -955,8 +1009,13 @@ class Engine:
 
         cperm = host(None if perm is None else torch.as_tensor(perm, dtype=torch.int32), C.c_int, "perm")
         cpesq = host(None if pesq is None else torch.as_tensor(pesq, dtype=torch.float32), C.c_float, "pesq")
-        self._check(self.lib.dsn_composite(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), cperm, cpesq,
-                                           C.byref(out), self._stream()), "dsn_composite")
+        if lens is None:
+            self._check(self.lib.dsn_composite(self.ctx, _ptr(ref), _ptr(est), B, n, L, int(fs), cperm, cpesq,
+                                               C.byref(out), self._stream()), "dsn_composite")
+        else:
+            self._check(self.lib.dsn_composite_ragged(self.ctx, _ptr(ref), _ptr(est), B, n, L, (C.c_int32 * B)(*lens),
+                                                      int(fs), cperm, cpesq, C.byref(out), self._stream()),
+                        "dsn_composite_ragged")
         res = {k: torch.tensor(list(b), dtype=torch.float32).reshape(B, n) for k, b in bufs.items()}
         res["frames"] = torch.tensor(list(frames), dtype=torch.long).reshape(B, n)
         return res

@@ -364,6 +364,28 @@ typedef struct DsnCompositeOut {
 int dsn_composite(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, int fs, const int* perm,
                   const float* pesq, const DsnCompositeOut* out, void* stream);
 
+/* The three metric calls above on a batch of differently long items, one call (one device-to-host copy, one
+ * synchronise) whatever B is.  ref, est stay [B,n,L] fp32 (device) with L the padded length Lmax; lens [B] (host, like
+ * `frames` of the ragged calls above) holds the sample count of item b, shared by its n sources.  Item b gets exactly
+ * what the dense call gives for ref[b, :, :lens[b]], est[b, :, :lens[b]] alone, bit for bit: every sum runs in the
+ * order the item's own length fixes.  Nothing past lens[b] is read, so the padding may hold anything (NaN included).
+ * All other arguments are those of the dense call.
+ *   dsn_si_bss_eval_ragged  the permutation is solved per item.
+ *   dsn_stoi_ragged         an item shorter than one 10 kHz frame (256 samples at 10 kHz) scores 1e-5 with 0 frames,
+ *                           as the dense call does for a batch that short; fewer than 30 frames -> 1e-5, as there.
+ *   dsn_composite_ragged    out->frames receives every item's own F = lens[b] / hop - win / hop, and its trimmed means
+ *                           take round(0.95 F) of them.
+ * DSN_EINVAL by name, before anything is allocated or launched: lens null; lens[b] outside [1, L]; for
+ * dsn_composite_ragged an item shorter than one frame plus one hop (the message names the item and the samples needed);
+ * and whatever the dense call refuses. */
+int dsn_si_bss_eval_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                           int perm_by, float clamp_db, float* si_sdr_out, float* si_sir_out, float* si_sar_out,
+                           int* perm_out, void* stream);
+int dsn_stoi_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens, int fs,
+                    int extended, const int* perm, float* out, int* frames_out, void* stream);
+int dsn_composite_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                         int fs, const int* perm, const float* pesq, const DsnCompositeOut* out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
