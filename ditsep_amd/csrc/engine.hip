@@ -189,6 +189,13 @@ struct dsn_ctx {
   std::map<int, CompositeTables> composite_tables;
   std::map<long, float*> mrstft_windows;  // dsn_mrstft_loss: (fft << 16 | win_length) -> zero-padded window [fft]
   OdeCtl* ode_host = nullptr;  // dsn_ode_sample: pinned host image of the solver state (upload / per-attempt poll)
+  // dsn_window_stitch: the fade tables last uploaded (fall [O] then rise [O], workspace buffer "stitch_fade"); the host
+  // image stays untouched while an enqueued upload may still read it
+  struct StitchFade {
+    std::vector<float> host;
+    float* dev = nullptr;
+    int O = -1, kind = -1;
+  } stitch_fade;
 
   // DiT
   float* tf_w = nullptr;
@@ -2824,6 +2831,78 @@ int dsn_si_bss_eval_ragged(dsn_ctx* ctx, const float* ref, const float* est, int
                            int* perm_out, void* stream) {
   return si_bss_eval_call(ctx, "dsn_si_bss_eval_ragged", ref, est, B, n, L, lens, true, perm_by, clamp_db, si_sdr_out,
                           si_sir_out, si_sar_out, perm_out, stream);
+}
+
+// dsn_window_stitch's fade tables on the device: fall [O], then rise [O] from the next multiple of 4 floats (both
+// 16-byte aligned).  fp64 on the host, rounded once to fp32 (native.fade_table restates it with the same libm sin).
+// Uploaded only when (O, kind) or the buffer changed; the stream is drained before the host image is rewritten.
+static void stitch_fade_tables(dsn_ctx* ctx, int O, int kind, hipStream_t st, const float** fall, const float** rise) {
+  const long Oq = ((long)O + 3) & ~3L;
+  auto& f = ctx->stitch_fade;
+  float* dev = ctx->wsbuf<float>("stitch_fade", std::max(2 * Oq, 4L));
+  if (f.dev != dev || f.O != O || f.kind != kind) {
+    if (O > 0) {
+      HIPCHK(hipStreamSynchronize(st));
+      f.host.assign((size_t)(2 * Oq), 0.f);
+      for (int k = 0; k < O; ++k) {
+        double r;
+        if (kind == DSN_FADE_LINEAR) {
+          r = ((double)k + 0.5) / (double)O;
+        } else {
+          const double sn = sin(M_PI * ((double)k + 0.5) / (2.0 * (double)O));
+          r = sn * sn;
+        }
+        f.host[k] = (float)(1.0 - r);
+        f.host[Oq + k] = (float)r;
+      }
+      HIPCHK(hipMemcpyAsync(dev, f.host.data(), sizeof(float) * f.host.size(), hipMemcpyHostToDevice, st));
+    }
+    f.dev = dev;
+    f.O = O;
+    f.kind = kind;
+  }
+  *fall = dev;
+  *rise = dev + Oq;
+}
+
+int dsn_window_stitch(dsn_ctx* ctx, const float* chunks, int W, int n, int Lw, int overlap, int L, int fade, int align,
+                      float* out, int32_t* perm_out, double* gram_out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_window_stitch";
+    if (!chunks || !out) fail(DSN_EINVAL, "%s: chunks or out is null", who);
+    if (n < 1 || n > 4) fail(DSN_EINVAL, "%s: n = %d outside [1, 4]", who, n);
+    if (W < 1) fail(DSN_EINVAL, "%s: W = %d < 1", who, W);
+    if (Lw < 1) fail(DSN_EINVAL, "%s: Lw = %d < 1", who, Lw);
+    if (overlap < 0) fail(DSN_EINVAL, "%s: overlap = %d < 0", who, overlap);
+    if (2L * overlap > Lw)
+      fail(DSN_EINVAL, "%s: 2 * overlap = %ld > Lw = %d (a sample may lie in at most two windows)", who, 2L * overlap,
+           Lw);
+    if (fade != DSN_FADE_HANN && fade != DSN_FADE_LINEAR)
+      fail(DSN_EINVAL, "%s: fade = %d is neither 0 (hann) nor 1 (linear)", who, fade);
+    const long hop = Lw - overlap, base = (long)(W - 1) * hop;
+    if (W == 1 && (L < 1 || L > Lw)) fail(DSN_EINVAL, "%s: L = %d outside [1, Lw = %d] for W = 1", who, L, Lw);
+    if (W > 1 && (L <= base + overlap || L > base + Lw))
+      fail(DSN_EINVAL, "%s: L = %d outside (%ld, %ld] for W = %d windows of hop %ld", who, L, base + overlap, base + Lw,
+           W, hop);
+    hipStream_t st = (hipStream_t)stream;
+    const long nb = W - 1, nn = (long)n * n;
+    const int tiles = align ? stitch_tiles(overlap) : 0;
+    double* part = ctx->wsbuf<double>("stitch_part", std::max(nb * tiles * nn, 1L));
+    double* gram = ctx->wsbuf<double>("stitch_gram", std::max(nb * nn, 1L));
+    int* perm = ctx->wsbuf<int>("stitch_perm", (long)W * n);
+    const float *fall, *rise;
+    stitch_fade_tables(ctx, overlap, fade, st, &fall, &rise);
+    if (align) launch_stitch_gram(chunks, W, n, Lw, overlap, part, st);
+    launch_stitch_perm(part, gram, perm, W, n, tiles, align, st);
+    launch_stitch_gather(chunks, perm, fall, rise, out, W, n, Lw, overlap, L, st);
+    HIPCHK(hipGetLastError());
+    if (!perm_out && !gram_out) return;
+    if (perm_out) HIPCHK(hipMemcpyAsync(perm_out, perm, sizeof(int32_t) * (size_t)W * n, hipMemcpyDeviceToHost, st));
+    if (gram_out && align && nb > 0)
+      HIPCHK(hipMemcpyAsync(gram_out, gram, sizeof(double) * (size_t)(nb * nn), hipMemcpyDeviceToHost, st));
+    if (gram_out && !align) std::fill(gram_out, gram_out + nb * nn, 0.0);
+    HIPCHK(hipStreamSynchronize(st));
+  });
 }
 
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)

@@ -300,3 +300,22 @@ void launch_loss_reduce(const LossSde& q, const float* score_tok, const float* z
 // (float)row, else out [1] = (float)(sum row / (B n)).  rows [B n] fp64 is scratch.
 void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, long DT,
                          int mean_reduction, hipStream_t s);
+
+// ---- window stitch (stitch.hip) -----------------------------------------------------------------------------
+// chunks [W][n][Lw]: window w covers samples [w hop, w hop + Lw) of a recording, hop = Lw - O, 2 O <= Lw, n <= 4.
+#define DSN_STITCH_TILE 4096   // overlap positions one workgroup of the Gram launch sums
+inline int stitch_tiles(int O) { return (O + DSN_STITCH_TILE - 1) / DSN_STITCH_TILE; }
+// part[((w tiles + c) n + i) n + j] = fp64 sum over tile c of chunks[w][i][hop + k] * chunks[w + 1][j][k]
+// (w < W - 1; exact fp64 products, per-thread strided accumulation, then a fixed tree: no atomics)
+void launch_stitch_gram(const float* chunks, int W, int n, int Lw, int O, double* part, hipStream_t s);
+// one workgroup.  align != 0: gram[w][i][j] = sum_c part in index order; sigma_w = the permutation with the largest
+// sum_i gram[w][i][sigma(i)], candidates in lexicographic order, replaced only by a strictly greater score (ties go
+// to the identity); perm [W][n]: P_0 = id, P_{w+1}(i) = sigma_w(P_w(i)).  align == 0: every P_w = id, part and gram
+// are not touched.
+void launch_stitch_perm(const double* part, double* gram, int* perm, int W, int n, int tiles, int align,
+                        hipStream_t s);
+// out [n][L]: t in the first O samples of window w >= 1 -> fall[k] chunks[w-1][P_{w-1}(i)][hop + k] +
+// rise[k] chunks[w][P_w(i)][k], k = t - w hop; every other t a plain copy of chunks[w][P_w(i)][k], w = min(t / hop,
+// W - 1).  fall, rise [O] fp32 (device).
+void launch_stitch_gather(const float* chunks, const int* perm, const float* fall, const float* rise, float* out, int W,
+                          int n, int Lw, int O, int L, hipStream_t s);

@@ -340,6 +340,41 @@ class LatentDiffSep:
         dims = [int(m.shape[-1]) for m in mixes] if target_dims is None else list(target_dims)
         return (eng.decode_ragged(est, frames, dims, codec=codec), *others)
 
+    @torch.no_grad()
+    def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
+                      **sampler_kwargs):
+        """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
+        or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
+        recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
+        keywords -> decode(..., window), exactly as `separate` does, so the model's own SDE and sampler are used; an
+        explicit seed is offset by the minibatch index, vae_noise [Wtot, D, Tw] and noise [draws, Wtot, n, D, Tw] are
+        sliced per minibatch.  Each recording is put back together by one Engine.window_stitch call (overlap default
+        window // 4).  The windows are sampled independently: the stitch orders and blends them only."""
+        eng = self.engine
+        if int(batch) < 1:
+            raise ValueError(f"batch = {batch} < 1")
+        single = torch.is_tensor(mixes)
+        pool, plans, overlap = native.cut_windows([mixes] if single else list(mixes), window, overlap, eng.device)
+        kwargs = dict(sampler_kwargs)
+        seed, vae_noise, noise = kwargs.pop("seed", None), kwargs.pop("vae_noise", None), kwargs.pop("noise", None)
+        skw = dict(_get(self.config, "model.sampler", {}) or {})
+        skw.update(kwargs)
+        Wtot = pool.shape[0]
+        sep = torch.empty((Wtot, self.n_src, int(window)), device=eng.device, dtype=torch.float32)
+        nfe = 0
+        for m, lo in enumerate(range(0, Wtot, int(batch))):
+            sl = slice(lo, lo + int(batch))
+            s = self._seed(None) if seed is None else int(seed) + m
+            y, _ = self.encode(pool[sl], None, vae_noise=None if vae_noise is None else vae_noise[sl], seed=s)
+            sampler = self.get_pc_sampler("reverse_diffusion", "ald", y, seed=None if seed is None else s,
+                                          noise=None if noise is None else noise[:, sl], **skw)
+            est, k = sampler()
+            sep[sl] = self.decode(est, int(window))
+            nfe += k
+        outs, info = eng._stitch_plans(sep, plans, overlap, fade, align, return_info)
+        res = (outs[0] if single else outs, nfe)
+        return (*res, info) if return_info else res
+
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod
     def _seed(seed):

@@ -34,7 +34,7 @@ EXPORTS = [
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows",
     "dsn_test_gemm", "dsn_test_kernel", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
-    "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged",
+    "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged", "dsn_window_stitch",
 ]
 
 
@@ -302,6 +302,72 @@ def check_lens(lens, B: int, Lmax: int, min_len: Optional[int] = None, what: str
     return ln
 
 
+FADES = {"hann": 0, "linear": 1}
+
+
+def window_plan(L: int, window: int, overlap: int):
+    """(W, hop) of cutting an L-sample recording into windows of `window` samples that share `overlap` samples with
+    their neighbour: hop = window - overlap, window w covers [w hop, w hop + window), W = 1 for L <= window, else
+    1 + ceil((L - window) / hop); the last window is zero-extended past L.  With this W the last window starts inside
+    the recording and its overlap with the one before holds real samples only ((W-1) hop + overlap < L).  Refused by
+    name: window < 1, overlap < 0, L < 1, and 2 overlap > window -- a sample may lie in at most two windows
+    (dsn_window_stitch's cross-fade is a gather)."""
+    L, window, overlap = int(L), int(window), int(overlap)
+    if window < 1:
+        raise ValueError(f"window = {window} < 1")
+    if overlap < 0:
+        raise ValueError(f"overlap = {overlap} < 0")
+    if L < 1:
+        raise ValueError(f"L = {L} < 1")
+    if 2 * overlap > window:
+        raise ValueError(f"2 * overlap = {2 * overlap} > window = {window}: a sample may lie in at most two windows")
+    hop = window - overlap
+    return (1 if L <= window else 1 + -((window - L) // hop)), hop
+
+
+def fade_table(overlap: int, fade: str = "hann"):
+    """(fall32, rise32), float32 numpy arrays [overlap]: the cross-fade weights of dsn_window_stitch over the overlap
+    position k.  rise[k] = sin^2(pi (k + 1/2) / (2 overlap)) ("hann") or (k + 1/2) / overlap ("linear"),
+    fall[k] = 1 - rise[k]; both in float64 (the C library's sin), rounded once to float32 -- the library builds the same
+    tables, so a restatement that uses these differs from the device by the cross-fade's own rounding only."""
+    rise = fade_rise64(overlap, fade)
+    return (1.0 - rise).astype("float32"), rise.astype("float32")
+
+
+def fade_rise64(overlap: int, fade: str = "hann"):
+    """The rising weight of fade_table before it is rounded: float64 numpy array [overlap]."""
+    import numpy as np
+
+    if fade not in FADES:
+        raise ValueError(f"fade must be one of {sorted(FADES)} (got {fade!r})")
+    O = int(overlap)
+    if O < 0:
+        raise ValueError(f"overlap = {O} < 0")
+    if fade == "linear":
+        return np.asarray([(k + 0.5) / float(O) for k in range(O)], dtype=np.float64)
+    sn = [math.sin(math.pi * (k + 0.5) / (2.0 * float(O))) for k in range(O)]
+    return np.asarray([s * s for s in sn], dtype=np.float64)
+
+
+def cut_windows(mixes, window: int, overlap, device):
+    """list of [1, L_r] recordings -> (pool [Wtot, 1, window] on `device`, plans [(W_r, hop, L_r)], overlap): every
+    recording zero-extended to its plan's (W_r - 1) hop + window samples and unfolded into its W_r windows, the
+    windows of all recordings in order.  overlap None: window // 4."""
+    window = int(window)
+    overlap = window // 4 if overlap is None else int(overlap)
+    rows, plans = [], []
+    for r, m in enumerate(mixes):
+        if m.dim() != 2 or m.shape[0] != 1:
+            raise ValueError(f"recording {r} must be [1, L] (got {tuple(m.shape)})")
+        L = int(m.shape[-1])
+        W, hop = window_plan(L, window, overlap)
+        x = _dev32(m, device).reshape(-1)
+        x = torch.nn.functional.pad(x, (0, (W - 1) * hop + window - L))
+        rows.append(x.unfold(0, window, hop))
+        plans.append((W, hop, L))
+    return torch.cat(rows, dim=0).unsqueeze(1).contiguous(), plans, overlap
+
+
 _lib = None
 
 
@@ -371,6 +437,7 @@ def load_library() -> C.CDLL:
     lib.dsn_stoi_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]
     lib.dsn_composite_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, C.POINTER(ci), fp,
                                          C.POINTER(DsnCompositeOut), vp]
+    lib.dsn_window_stitch.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, i32p, C.POINTER(C.c_double), vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -872,6 +939,77 @@ class Engine:
         x, nfe = self.pc_sample(y, noise, N=N, corrector_steps=corrector_steps, snr=snr, t_eps=t_eps, denoise=denoise,
                                 seed=seed, frames=frames)
         return self.decode_ragged(x, frames, [int(m.shape[-1]) for m in mixes]), nfe
+
+    # ------------------------------------------------------------------ long recordings as batched windows
+    def _stitch(self, chunks, L, overlap, fade, align, host):
+        if fade not in FADES:
+            raise ValueError(f"fade must be one of {sorted(FADES)} (got {fade!r})")
+        chunks = _dev32(chunks, self.device)
+        if chunks.dim() != 3:
+            raise ValueError(f"chunks must be [W, n, Lw] (got {tuple(chunks.shape)})")
+        W, n, Lw = chunks.shape
+        out = torch.empty((n, int(L)), device=self.device, dtype=torch.float32)
+        perms = torch.zeros((W, n), dtype=torch.int32) if host else None
+        gram = torch.zeros((max(W - 1, 0), n, n), dtype=torch.float64) if host else None
+        self._check(self.lib.dsn_window_stitch(
+            self.ctx, _ptr(chunks), W, n, Lw, int(overlap), int(L), FADES[fade], int(bool(align)), _ptr(out),
+            None if perms is None else C.cast(C.c_void_p(perms.data_ptr()), C.POINTER(C.c_int32)),
+            None if gram is None else C.cast(C.c_void_p(gram.data_ptr()), C.POINTER(C.c_double)),
+            self._stream()), "dsn_window_stitch")
+        return out, (None if perms is None else perms.long()), gram
+
+    def window_stitch(self, chunks, L, overlap, fade="hann", align=True):
+        """The separated windows of one recording back into the recording (dsn_window_stitch): chunks [W,n,Lw], window w
+        covering samples [w hop, w hop + Lw) with hop = Lw - overlap (window_plan) -> (out [n,L] on the device, perms
+        [W,n] long, gram [W-1,n,n] float64, both on the host).  Slot i of `out` is slot perms[w,i] of window w: the
+        order of window 0, carried from window to window by the assignment that maximises the overlap inner products
+        gram[w,i,j] = <chunks[w,i,hop:], chunks[w+1,j,:overlap]> (ties go to the identity); overlaps are cross-faded
+        with fade_table(overlap, fade), everything else is copied bit for bit.  align=False: no reordering -- perms is
+        the identity and gram, which is not computed, is returned as zeros.  Needs no score network and no codec."""
+        return self._stitch(chunks, L, overlap, fade, align, True)
+
+    def _stitch_plans(self, sep, plans, overlap, fade, align, return_info):
+        """sep [Wtot,n,window] in plan order, plans [(W, hop, L)] -> list of [n,L] (and the info dict of separate_long)"""
+        outs, info, o = [], {"perms": [], "gram": [], "W": [], "hop": [], "chunks": sep}, 0
+        for W, hop, L in plans:
+            out, perms, gram = self._stitch(sep[o:o + W], L, overlap, fade, align, return_info)
+            outs.append(out)
+            for k, v in (("perms", perms), ("gram", gram), ("W", W), ("hop", hop)):
+                info[k].append(v)
+            o += W
+        return outs, info
+
+    def separate_long(self, mixes, *, window, overlap=None, fade="hann", align=True, batch=64, vae_noise=None,
+                      noise=None, seed=0, N=30, corrector_steps=1, snr=0.5, t_eps=0.03, denoise=True,
+                      return_info=False):
+        """Long recordings as batched windows: `mixes` is one [1, L] tensor or a list of [1, L_r] tensors of any
+        lengths -> (estimates [n, L] -- a list of [n, L_r] for a list --, the summed nfe).  Every recording is cut into
+        windows of `window` samples sharing `overlap` (default window // 4) with their neighbour (window_plan; the last
+        one zero-extended); the windows of all recordings are pooled in order into one [Wtot, 1, window] batch, which
+        `separate` takes `batch` windows at a time (with the device RNG minibatch m draws with seed + m, the convention
+        of LatentDiffSep.get_pc_sampler(minibatch=...)); each recording's windows are then put back together on the
+        device by one window_stitch call.  Explicit vae_noise [Wtot, D, Tw] and noise [draws, Wtot, n, D, Tw] are
+        sliced per minibatch.  return_info=True: also a dict with, per recording, the lists "perms", "gram", "W" and
+        "hop", and "chunks", the separated windows [Wtot, n, window].
+        The windows are sampled independently: the stitch orders and blends them, it does not make the diffusion
+        samples of neighbouring windows agree."""
+        if int(batch) < 1:
+            raise ValueError(f"batch = {batch} < 1")
+        single = torch.is_tensor(mixes)
+        pool, plans, overlap = cut_windows([mixes] if single else list(mixes), window, overlap, self.device)
+        Wtot = pool.shape[0]
+        sep = torch.empty((Wtot, self.n_src, int(window)), device=self.device, dtype=torch.float32)
+        nfe = 0
+        for m, lo in enumerate(range(0, Wtot, int(batch))):
+            sl = slice(lo, lo + int(batch))
+            wav, k = self.separate(pool[sl], vae_noise=None if vae_noise is None else vae_noise[sl],
+                                   noise=None if noise is None else noise[:, sl], seed=seed + m, N=N,
+                                   corrector_steps=corrector_steps, snr=snr, t_eps=t_eps, denoise=denoise)
+            sep[sl] = wav
+            nfe += k
+        outs, info = self._stitch_plans(sep, plans, overlap, fade, align, return_info)
+        res = (outs[0] if single else outs, nfe)
+        return (*res, info) if return_info else res
 
     @property
     def hop_length(self) -> int:

@@ -386,6 +386,32 @@ int dsn_stoi_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int
 int dsn_composite_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
                          int fs, const int* perm, const float* pesq, const DsnCompositeOut* out, void* stream);
 
+/* Put the separated windows of one long recording back together: chunks [W][n][Lw] fp32 (device), window w covering
+ * samples [w hop, w hop + Lw) with hop = Lw - overlap -> out [n][L] fp32 (device), with the speakers in window 0's
+ * order.  Needs no score network and no codec.  Three stages, all on the device:
+ *   Gram         G[w][i][j] = sum_k chunks[w][i][hop + k] chunks[w+1][j][k] over the overlap k in [0, overlap), for
+ *                every boundary w < W - 1: exact fp64 products summed in fp64 in an order the shape alone fixes (no
+ *                atomics: two calls give identical bits).
+ *   permutations sigma_w maximises sum_i G[w][i][sigma(i)] -- the assignment of least squared difference on the
+ *                overlap; a source silent there drops out of the decision.  All n! candidates in lexicographic order
+ *                of (sigma(0) .. sigma(n-1)), a candidate replacing the best only when strictly greater: ties (an
+ *                all-zero overlap, overlap = 0) go to the identity.  P_0 = id, P_{w+1}(i) = sigma_w(P_w(i)).
+ *                align == 0: the Gram stage is skipped and every P_w is the identity.
+ *   cross-fade   for t in [0, L), w = min(t / hop, W - 1), k = t - w hop: with w >= 1 and k < overlap
+ *                out[i][t] = fall[k] chunks[w-1][P_{w-1}(i)][hop + k] + rise[k] chunks[w][P_w(i)][k] (two fp32 products
+ *                and their fp32 sum, not contracted), else out[i][t] = chunks[w][P_w(i)][k], bit for bit.
+ *                rise[k] = sin^2(pi (k + 1/2) / (2 overlap)) (fade = 0, Hann) or (k + 1/2) / overlap (fade = 1,
+ *                linear), fall[k] = 1 - rise[k]: fp64 on the host, rounded once to fp32.
+ * perm_out [W][n] and gram_out [W-1][n][n] are host arrays and may be NULL: with either the call synchronises the
+ * stream and fills them (gram_out with zeros when align == 0); with both NULL it only enqueues.
+ * DSN_EINVAL by name, before anything is allocated or launched: chunks or out null; n outside [1, 4]; W < 1; Lw < 1;
+ * overlap < 0; 2 overlap > Lw (an output sample is covered by at most two windows: the cross-fade is a gather);
+ * a fade other than 0 | 1; L outside ((W-1) hop + overlap, (W-1) hop + Lw] for W > 1 or outside [1, Lw] for W = 1
+ * (the last window starts inside the recording and is zero-extended past its end, and its overlap holds real samples). */
+enum { DSN_FADE_HANN = 0, DSN_FADE_LINEAR = 1 };
+int dsn_window_stitch(dsn_ctx* ctx, const float* chunks, int W, int n, int Lw, int overlap, int L, int fade, int align,
+                      float* out, int32_t* perm_out, double* gram_out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
