@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ditsep_hip.h"
+#include "dit_plan.h"
 #include "igemm.h"
 #include "kernels.h"
 
@@ -112,7 +113,8 @@ struct VaeBlock {
 
 struct Graph {
   hipGraphExec_t exec = nullptr;
-  uint64_t epoch = ~0ull;  // workspace epoch the graph (or its eager warm-up) was built against
+  uint64_t epoch = ~0ull;  // workspace epoch and switches the graph (or its eager warm-up) was built against
+  Switches sw;
   bool warmed = false;
 };
 
@@ -131,11 +133,18 @@ struct ProfRow {
   int64_t launches = 0;
 };
 
+// what dit_plan must stay inside, from the kernel files that own each limit
+DitLimits dit_limits() {
+  return {qkv_attention_max_rows(), qkv_attention_panel_rows(1), PANEL_ROWS_MAX, PANEL_FP8_ROWS_MAX, PANEL_STATS_ROWS_MAX,
+          RESIDUAL_NORM_MAX_SLABS};
+}
+
 }  // namespace
 
 struct dsn_ctx {
   dsn_config cfg;
   std::string err;
+  Switches sw;  // the environment's switches as of this API call (guarded)
   int P = 2;   // operand planes
   int PL = 2;  // DSN_PL(P, fp16 flag) as the kernels take it
   bool fp8 = false;  // DSN_PREC_FP8: DiT layer GEMMs on fp8 (MX) operands, the rest single-plane fp16
@@ -270,7 +279,8 @@ struct dsn_ctx {
 
   // Run `body(stream)` -- a pure sequence of kernel launches over workspace pointers --
   // either eagerly or as a cached hipGraph.  The first call with a given key runs
-  // eagerly (it may grow the workspace), the second captures, later ones replay.
+  // eagerly (it may grow the workspace), the second captures, later ones replay.  A graph built
+  // against another workspace epoch or under other switches is stale: warm again, then recapture.
   template <class F>
   void run_graphed(const std::string& key, hipStream_t st, F&& body) {
     if (!use_graphs || profiling) {
@@ -278,7 +288,8 @@ struct dsn_ctx {
       return;
     }
     Graph& g = graphs[key];
-    if (g.exec && g.epoch == ws_epoch) {
+    const bool fresh = g.epoch == ws_epoch && g.sw == sw;
+    if (g.exec && fresh) {
       HIPCHK(hipGraphLaunch(g.exec, st));
       return;
     }
@@ -286,10 +297,11 @@ struct dsn_ctx {
       (void)hipGraphExecDestroy(g.exec);
       g.exec = nullptr;
     }
-    if (!g.warmed || g.epoch != ws_epoch) {
+    if (!g.warmed || !fresh) {
       body(st);
       g.warmed = true;
       g.epoch = ws_epoch;
+      g.sw = sw;
       return;
     }
     hipGraph_t graph = nullptr;
@@ -596,8 +608,8 @@ struct dsn_ctx {
       ++ws_epoch;
     }
     const int D = cfg.dit_embed_dim;
-    fold_ln = P == 1 && !fp8 && D % 64 == 0 && getenv("DSN_NO_LN_FOLD") == nullptr;
-    fold_ln8 = fp8 && D % 128 == 0 && getenv("DSN_NO_LN_FOLD") == nullptr;
+    fold_ln = dit_fold_ln(cfg, sw);
+    fold_ln8 = dit_fold_ln8(cfg, sw);
     if (cfg.score_kind == DSN_SCORE_DIT) {
       const std::string sp = "score_model.";
       if (D % 64 != 0 || cfg.dit_heads <= 0 || D / cfg.dit_heads != 64 || D % cfg.dit_heads != 0)
@@ -810,14 +822,6 @@ struct dsn_ctx {
     d.act_b = a.ib;
     d.act_mod = a.mod;
   }
-  // split-K factor for a GEMM whose output tile count cannot fill the chip (see dit_forward)
-  int pick_ksplit(const GemmDesc& d) const {
-    const int nkt = d.taps * (d.Cin / 32);
-    const int tiles = cdiv(d.M, 128) * cdiv(d.N, 128);
-    int k = (400 + tiles / 2) / tiles;
-    k = std::min(k, std::min(8, nkt / 8));
-    return std::max(k, 1);
-  }
   // DSN_AUDIT=1 (tests): before a GEMM-family launch, every pointer of its descriptor is checked on the HOST against
   // the device allocation that contains it (hipMemGetAddressRange), over the exact extent the kernels' guards allow --
   // the largest (item, row, column) offsets of A, W, the fp32 / plane / slab outputs, residual, bias vectors, GroupNorm
@@ -900,8 +904,7 @@ struct dsn_ctx {
       fail(DSN_EINVAL, "audit: 2-D conv descriptor with rows_per_b != H*W");
   }
   void run(const GemmDesc& d, hipStream_t st, int panel_bn = 0, bool skinny = false) {
-    static const bool audit = getenv("DSN_AUDIT") != nullptr;
-    if (audit) audit_desc(d);
+    if (sw.audit) audit_desc(d);
     const double flops = 2.0 * (double)d.M * (double)d.N * ((double)d.taps * (double)d.Cin + (d.sc_A ? (double)d.sc_Cin : 0.0));
     // NCSN++ convs of single mixtures: a handful of 128 x 128 tiles each walking a long K alone -> split-K over enough
     // workgroups for a quarter of the chip, then the slab epilogue (B = 1, T = 16: score call 3.07 -> see DESIGN 5)
@@ -990,7 +993,7 @@ struct dsn_ctx {
     // algorithmic HBM bytes: planes in, fp32 residual in, fp32 out (when kept), planes out
     const double bytes = (double)S * (double)L * 128.0 * (2.0 * P + 4.0 + (out_f32 ? 4.0 : 0.0) + 2.0 * P);
     const hipError_t e = profiled({"vae.residual_unit_fused", flops, bytes, true, true}, st,
-                                  [&] { return ru_fused_launch(d, PL, st); });
+                                  [&] { return ru_fused_launch(d, PL, sw.ru_v1, st); });
     if (e != hipSuccess) fail(DSN_EHIP, "fused residual unit launch failed: %s (S=%d L=%ld dil=%d)",
                               hipGetErrorString(e), S, L, r.dil);
   }
@@ -1094,26 +1097,10 @@ struct dsn_ctx {
     unsigned char* H8 = fp8 ? wsbuf<unsigned char>("dit_H8", M * 4 * D) : nullptr;
     unsigned char* SH8 = fp8 ? wsbuf<unsigned char>("dit_SH8", M * 4 * D / 32) : nullptr;
     op16_t* lnout = fp8 ? reinterpret_cast<op16_t*>(A8) : Ap;
-    // single mixtures and pairs (up to 80 token rows = 5 sub-tiles; DSN_SKINNY_MAX moves the limit, at most 128): weight-streaming skinny kernels, split-K 8 for
-    // the two N = D GEMMs so that every CU streams a share of their weights.  Measured (scripts/score_time.py, one
-    // score call): M = 33: 1.52 ms vs 2.27 ms with the panel kernels; M = 17 (config C1): 1.37 vs 2.02 ms; M = 9:
-    // 1.28 vs 2.01 ms; M = 61 (4 sub-tiles): 1.77 vs 2.10 ms; M = 66 (5): 1.72 vs 2.07; M = 99 (7): 2.03 vs 2.08; M = 126 (8): 2.22 vs 2.10.  (The window used to start at 33 rows: below it the launcher picked the 1- / 2-sub-tile
-    // instantiations, which run 2.5x slower than the 3-sub-tile one on the same data -- see igemm_skinny_launch.)
-    const char* skx = getenv("DSN_SKINNY_MAX");  // read per call (tests)
-    const int skinny_max = skx ? std::min(atoi(skx), 128) : 80;
-    const bool skinny = P == 1 && !fp8 && M <= skinny_max && D % 256 == 0;
-    const int skinny_ks = 8;
-    const bool use_panel = D % 64 == 0;  // row-panel kernels
-    // folded ff_norm (single-plane modes, panels of at most 80 rows fill whole rounds): to_out runs WITHOUT split-K in
-    // 128-column tiles, adds the residual itself and writes x' (fp32), its raw operand plane and per-row statistics;
-    // FF-in then applies the LayerNorm algebraically in its epilogue -- the LayerNorm launch between them is gone
-    int fold_rows = 0;
-    if ((fold_ln || fold_ln8) && use_panel && !skinny) {
-      for (int rounds = 1; rounds <= 4 && !fold_rows; ++rounds) {
-        const int np = 256 * rounds / std::max(1, cdiv(D, 128));
-        if (np >= 1 && cdiv(M, np) <= 80) fold_rows = cdiv(M, np);
-      }
-    }
+    // every decision of the call -- kernel families, panel heights, split-K factors -- and why: dit_plan.h
+    const DitPlan plan = dit_plan(cfg, B, T, fold_ln, fold_ln8, sw, dit_limits());
+    const bool skinny = plan.skinny != 0;
+    const int fold_rows = plan.fold_rows, qa_ipp = plan.qa_ipp;
     op16_t* Xp = (fold_rows && !fp8) ? wsbuf<op16_t>("dit_Xp", M * D) : nullptr;
     // (fp8: raw x' as e4m3 + block scales; NOT the to_out input buffer -- other column tiles still read those rows)
     unsigned char* X8 = (fold_rows && fp8) ? wsbuf<unsigned char>("dit_X8", M * D) : nullptr;
@@ -1145,36 +1132,6 @@ struct dsn_ctx {
       }
       launch_copy_rows(te, X, B, D, (long)S * D, st);
     }
-    // Residual-stream GEMMs (out-proj, FF-out) have N = D only: at M ~ 2k rows that is too few
-    // 128x128 tiles to fill 256 CUs, so they run split-K into fp32 slabs and the slab reduction
-    // (+ bias + residual) is fused into the LayerNorm that follows.
-    // Short row panels for the three narrower GEMMs in the single-plane modes, sized so that panels x column tiles
-    // x split-K is one balanced round of 256 workgroups: at M = 2112 out-proj 16 x 8 x split-K 2 and FF-out
-    // 16 x 4 x split-K 4 (132-row panels, 9 sub-tiles) = 256, QKV 21 x 12 (104-row panels, 7 sub-tiles) = 252
-    // (sweep: profiles/r01_gemm_sweep_dit_panel132.log).
-    // (also for small batches: many short panels keep every CU streaming weights -- B = 8: 197 -> 145 ms per step)
-    const bool short_panel = use_panel && P == 1;  // split modes: measured, no gain
-    // panel height for a GEMM with `wg_per_panel` = column tiles x split-K workgroups per row panel: as many
-    // panels as fill whole rounds of 256 CUs
-    auto panel_rows_for = [&](int wg_per_panel, int max_rows = 272) {
-      for (int rounds = 1;; ++rounds) {  // whole rounds of 256 workgroups, panels at most max_rows (<= 272) rows tall
-        const int np = std::max(1, 256 * rounds / std::max(1, wg_per_panel));
-        const int rows = (cdiv(M, np) + 7) / 8 * 8;
-        if (rows <= max_rows) return rows;
-      }
-    };
-    const int qkv_panel = short_panel ? 256 : 0;
-    // Fused to_qkv + attention (single-plane 16-bit modes, 64-wide heads, panels of whole items up to 144 rows -- 240 for
-    // one long item, the 2-stage-ring variant): as many items per panel as keep panels x heads at a full round of the
-    // chip; small batches (fewer than half a round of workgroups) and the skinny window keep the separate kernels.
-    int qa_ipp = 0;
-    if (P == 1 && !skinny && D == H * 64 && S <= qkv_attention_max_rows()) {
-      int ipp = std::min(B, std::max(1, 144 / S));  // several items share a panel only in the 144-row tile
-      while (ipp > 1 && cdiv(B, ipp) * H < 256) --ipp;
-      if (cdiv(B, ipp) * H >= 128) qa_ipp = ipp;
-      const char* force = getenv("DSN_QA_IPP");  // tests: force the fused kernel with this many items per panel
-      if (force && atoi(force) >= 1 && atoi(force) * S <= qkv_attention_max_rows()) qa_ipp = atoi(force);
-    }
     op16_t* AOp = qa_ipp ? wsbuf<op16_t>("dit_AOp", M * D) : nullptr;
     float* slabs = nullptr;
     int pend_n = 0;
@@ -1187,20 +1144,20 @@ struct dsn_ctx {
       return fp8 ? fp8_desc(A8b, SA, w8, (int)M) : base_desc(A16, M * w.Cin, w, 1, (int)M, (int)M);
     };
     // ... and its kernel family: fp8 row panels, the weight-streaming skinny kernel, or the 16-bit kernels (row panels in
-    // bn-column tiles where `panel`)
-    auto layer_gemm = [&](const GemmDesc& d, int bn, bool panel) {
+    // bn-column tiles where the plan gave it a panel height)
+    auto layer_gemm = [&](const GemmDesc& d, int bn) {
       if (fp8) run_fp8(d, st, bn);
       else if (skinny) run(d, st, 0, true);
-      else run(d, st, panel ? bn : 0);
+      else run(d, st, d.panel_rows ? bn : 0);
     };
-    // A residual-stream GEMM (out-proj, FF-out) in bn-column tiles: split-K (skinny: 8, short panels and fp8: ks) into
-    // fp32 slabs, whose reduction + bias + residual the following residual_norm does (pend_n, pend_bias); without
-    // split-K it adds the residual and writes X itself.  (to_out has no bias: pack_linear gives it none to defer.)
-    auto stream_gemm = [&](GemmDesc& d, int bn, int ks, int max_rows) {
-      d.ksplit = skinny ? skinny_ks : ((short_panel || fp8) ? ks : pick_ksplit(d));
-      if (short_panel || fp8) d.panel_rows = panel_rows_for(cdiv(D, bn) * ks, max_rows);
+    // A residual-stream GEMM (out-proj, FF-out) in bn-column tiles: split-K into fp32 slabs, whose reduction + bias +
+    // residual the following residual_norm does (pend_n, pend_bias); without split-K it adds the residual and writes X
+    // itself.  (to_out has no bias: pack_linear gives it none to defer.)
+    auto stream_gemm = [&](GemmDesc& d, int bn, int ksplit, int rows) {
+      d.ksplit = ksplit;
+      d.panel_rows = rows;
       if (d.ksplit > 1) {
-        slabs = wsbuf<float>("dit_slabs", slab_stride * 8);
+        slabs = wsbuf<float>("dit_slabs", slab_stride * RESIDUAL_NORM_MAX_SLABS);
         d.out_f32 = slabs;
         d.slab_stride = slab_stride;
         pend_bias = d.bias;
@@ -1210,7 +1167,7 @@ struct dsn_ctx {
         d.out_f32 = X;
         pend_bias = nullptr;
       }
-      layer_gemm(d, bn, short_panel);
+      layer_gemm(d, bn);
       pend_n = d.ksplit > 1 ? d.ksplit : 0;
     };
     for (int i = 0; i < cfg.dit_depth; ++i) {
@@ -1255,9 +1212,8 @@ struct dsn_ctx {
           d.qkv_D = D;
           d.q_scale = 0.125f;
           d.m_fast = 1;
-          if (qkv_panel) d.panel_rows = panel_rows_for(cdiv(3 * D, qkv_panel));
-          if (fp8) d.panel_rows = panel_rows_for(cdiv(3 * D, 256), 208);
-          layer_gemm(d, 256, short_panel);
+          d.panel_rows = plan.qkv_rows;
+          layer_gemm(d, 256);
         }
         prof_launch("dit.attention", (double)M * D * 2.0 * P * 4.0, st, [&] {
           const hipError_t e = launch_attention_mfma(QKVp, M * 3 * D, lnout, M * D, PL, B, S, H, 64, st, SA8, lens);
@@ -1279,11 +1235,11 @@ struct dsn_ctx {
           d.stat_np = D / 64;
           d.m_fast = 0;  // an XCD's share walks ACROSS the 8 column tiles of a few row panels: the whole
                          // 2 MB weight and 4 panels fit its L2 (m_fast = 1: every XCD re-fetches all of A)
-          layer_gemm(d, 128, true);  // (never skinny: fold_rows excludes it)
+          layer_gemm(d, 128);  // (never skinny: fold_rows excludes it)
           pend_n = 0;
           pend_bias = nullptr;
         } else {
-          stream_gemm(d, 128, 2, 272);
+          stream_gemm(d, 128, plan.attn_out_ksplit, plan.attn_out_rows);
         }
       }
       if (!fold_rows)
@@ -1292,8 +1248,6 @@ struct dsn_ctx {
                                1e-5f, 1, st, SA8);
         });
       {
-        // FF-in through the row-panel kernel: ceil(M/272) equal row panels x 256-column tiles -- for the
-        // benchmark shape (M = 2112 -> 8 panels of 264 rows, N = 8192) exactly 256 workgroups, one round.
         Tag tg(this, "dit.ff_in");
         GemmDesc d = fold_rows ? layer_desc(Xp, X8, SX8, L.ff1f, L.ff1f8) : layer_desc(Ap, A8, SA8, L.ff1, L.ff1_8);
         d.swiglu = 1;
@@ -1314,18 +1268,13 @@ struct dsn_ctx {
         d.out_row_elems = 4 * D;
         d.out_limit = d.out_bstride;
         d.m_fast = 1;
-        if (use_panel) {
-          const int np = cdiv(M, 272);
-          d.panel_rows = short_panel ? panel_rows_for(cdiv(4 * D * 2, 256)) : (cdiv(M, np) + 7) / 8 * 8;
-        }
-        // fp8: 256-column tiles up to 17 row sub-tiles (8 waves x 256 registers, branch-free main loop): one round at C2
-        if (fp8) d.panel_rows = panel_rows_for(cdiv(4 * D * 2, 256));
-        layer_gemm(d, 256, use_panel);
+        d.panel_rows = plan.ff_in_rows;
+        layer_gemm(d, 256);
       }
       {
         Tag tg(this, "dit.ff_out");
         GemmDesc d = layer_desc(FF, H8, SH8, L.ff2, L.ff2_8);
-        stream_gemm(d, 256, 4, fp8 ? 208 : 272);
+        stream_gemm(d, 256, plan.ff_out_ksplit, plan.ff_out_rows);
       }
     }
     // final residual update + planes of X (no norm before project_out)
@@ -1339,14 +1288,8 @@ struct dsn_ctx {
       d.in_pad = -1;
       d.in_bstride = (long)S * D;
       d.out_f32 = SC;
-      // N = n_src * latent_dim is ONE 128-column tile: 128-row tiles leave B*T/128 (17 at C2) workgroups walking the
-      // whole K alone; 64-row panels x 8 waves with a 4-stage ring double the workgroups and the loads in flight
-      if (use_panel && P == 1 && d.N <= 128 && d.M >= 1024) {
-        d.panel_rows = 64;
-        run(d, st, 128);
-      } else {
-        run(d, st);
-      }
+      d.panel_rows = plan.project_out_rows;  // (one 128-column tile)
+      run(d, st, d.panel_rows ? 128 : 0);
     }
     return SC;
   }
@@ -1916,6 +1859,7 @@ int guarded(dsn_ctx* ctx, F&& f) {
   if (!ctx) return DSN_EINVAL;
   try {
     HIPCHK(hipSetDevice(ctx->cfg.device));
+    ctx->sw = Switches::read();
     if (ctx->fin_err_host && *ctx->fin_err_host) {
       *ctx->fin_err_host = 0;
       fail(DSN_EHIP, "a GroupNorm hand-off wait of an earlier call gave up (the workgroups of one conv were not resident "
@@ -1970,9 +1914,9 @@ dsn_ctx* dsn_create(const dsn_config* cfg) {
     HIPCHK(hipSetDevice(cfg->device));
     dsn_ctx* c = new dsn_ctx();
     c->cfg = *cfg;
-    c->P = (cfg->precision == DSN_PREC_BF16X3 || cfg->precision == DSN_PREC_FP16X3) ? 2 : 1;
+    c->P = prec_planes(cfg->precision);
     c->PL = DSN_PL(c->P, cfg->precision >= DSN_PREC_FP16 ? 1 : 0);
-    c->fp8 = cfg->precision == DSN_PREC_FP8;
+    c->fp8 = prec_fp8(cfg->precision);
     if (c->fp8 && cfg->score_kind == DSN_SCORE_DIT && cfg->dit_embed_dim % 128 != 0)
       fail(DSN_EINVAL, "DSN_PREC_FP8: embed_dim must be a multiple of 128 (got %d)", cfg->dit_embed_dim);
     return c;
@@ -3399,6 +3343,14 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
   return (int)ctx->prof_rows.size();
 }
 
+// Test hook: the plan of one DiT score call, as finalize + dit_forward would decide it now (no context, no HIP call).
+int dsn_dit_plan(const dsn_config* cfg, int B, int T, DsnDitPlan* out) {
+  if (!cfg || !out || B <= 0 || T <= 0 || cfg->dit_embed_dim <= 0 || cfg->dit_heads <= 0) return DSN_EINVAL;
+  const Switches sw = Switches::read();
+  *out = dit_plan(*cfg, B, T, dit_fold_ln(*cfg, sw), dit_fold_ln8(*cfg, sw), sw, dit_limits());
+  return DSN_OK;
+}
+
 // Test hook: one chosen kernel of the implicit-GEMM family on a caller-built descriptor (include/ditsep_hip.h).
 int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream) {
   return guarded(ctx, [&] {
@@ -3461,7 +3413,7 @@ int dsn_test_gemm(dsn_ctx* ctx, const DsnTestGemm* t, void* stream) {
       d.sc_row_elems = t->sc_row_elems > 0 ? t->sc_row_elems : t->sc_Cin;
       d.sc_bstride = (long)t->rows_per_b * d.sc_row_elems;
     }
-    static const bool audit = getenv("DSN_AUDIT") != nullptr;
+    const bool audit = ctx->sw.audit;
     auto check = [&](hipError_t e, const char* what) {
       if (e != hipSuccess) fail(DSN_EHIP, "test_gemm: %s refused or failed: %s (M=%d N=%d Cin=%d taps=%d)", what,
                                 hipGetErrorString(e), d.M, d.N, d.Cin, d.taps);
@@ -3686,7 +3638,7 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         d.S = t->B;
         d.L = t->L;
         d.dil = t->dil;
-        const hipError_t e = ru_fused_launch(d, PL, st);
+        const hipError_t e = ru_fused_launch(d, PL, ctx->sw.ru_v1, st);
         if (e != hipSuccess)
           fail(DSN_EHIP, "test_kernel ru_fused: refused or failed: %s (S=%d L=%d dil=%d act %d / %d)", hipGetErrorString(e),
                t->B, t->L, t->dil, t->act, t->act_out);

@@ -337,8 +337,9 @@ void ncs_resblock(const NcsnRes& r, const View& x, const View& out, const float*
     d.bbias_stride = ncs_dense_total;
     h1_stats = gn_in_epilogue(d, r.cout, B, Ho * Wo);   // GroupNorm_1's statistics come out of this epilogue
     // h1 has one consumer, GroupNorm_1 -> SiLU -> Conv_1: where the halo kernel runs this conv in one resident round
-    // its workgroups finish the GroupNorm themselves and write a1 from their accumulators (h1 is never stored)
-    if (h1_stats && P == 1 && (long)cdiv((long)B * Ho * Wo, 128) * cdiv(r.cout, 128) > 32) {
+    // its workgroups finish the GroupNorm themselves and write a1 from their accumulators (h1 is never stored).
+    // DSN_NO_GN_FIN keeps the separate pass.
+    if (!sw.no_gn_fin && h1_stats && P == 1 && (long)cdiv((long)B * Ho * Wo, 128) * cdiv(r.cout, 128) > 32) {
       GemmDesc f = d;
       f.out_f32 = nullptr;
       f.gnf_out = a1.p;

@@ -143,6 +143,7 @@ hipError_t igemm_halo3x3_launch(const GemmDesc& d, int pl, hipStream_t stream);
 // row-tile height the halo kernel runs `d` with: 256 (8 waves) or 128 (4 waves); 0 = not eligible
 int igemm_halo3x3_tile(const GemmDesc& d, int pl);
 // can `d` (with gnf_out set) run as a producer-finished GroupNorm conv: halo-kernel eligible and one resident round?
+// (what the kernels can do; whether the engine wants it is the caller's switch)
 bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl);
 bool igemm2_gnfin_ok(const GemmDesc& d, int pl);   // the same inside igemm2's 128 x 64 tile (128-pixel images, no hand-off)
 // will igemm2_launch run `d` on the halo kernel (the only one that takes sc_A)?
@@ -150,6 +151,10 @@ bool igemm_halo3x3_eligible(const GemmDesc& d, int pl);
 // `pl` = DSN_PL(plane count, fp16 flag)
 // row-panel variant (igemm.hip): d.panel_rows rows x bn (128 | 256) columns per workgroup
 hipError_t igemm_panel_launch(const GemmDesc& d, int pl, int bn, hipStream_t stream);
+// what the row-panel launchers take, for the host code that sizes panels (dit_plan.h)
+constexpr int PANEL_ROWS_MAX = 17 * 16;        // tallest instantiation
+constexpr int PANEL_STATS_ROWS_MAX = 5 * 16;   // with d.stat_out: the 5-sub-tile instantiations alone
+constexpr int PANEL_FP8_ROWS_MAX = 13 * 16;    // fp8, 256-column tiles: tallest that keeps 16 waves (igemm_panel_fp8_launch)
 // skinny variant for M <= 48 rows (single-plane modes, plain row-major GEMM): one wave per 32 columns x split-K,
 // weights streamed straight into MFMA fragments
 hipError_t igemm_skinny_launch(const GemmDesc& d, int pl, hipStream_t stream);
@@ -198,4 +203,5 @@ struct RuDesc {
   const float *mid_a, *mid_b, *out_a, *out_b;  // snake alpha / 1/beta per channel
   int S, L, dil;
 };
-hipError_t ru_fused_launch(const RuDesc& d, int pl, hipStream_t stream);
+// v1 (single-plane modes): the 128-row kernel instead of the 256-row one
+hipError_t ru_fused_launch(const RuDesc& d, int pl, bool v1, hipStream_t stream);

@@ -1857,7 +1857,7 @@ static int halo_resident_blocks() {
 // GroupNorm finished inside igemm2's 128 x 64 tile (128-pixel images: one workgroup holds the image).  The caller
 // forces that tile (cfg_bm/bn/nst/bk = 128, 64, 3, 64).
 bool igemm2_gnfin_ok(const GemmDesc& d, int pl) {
-  if (getenv("DSN_NO_GN_FIN") != nullptr || PL_COUNT(pl) != 1 || !d.gn_stats || d.rows_per_b != 128 || d.M % 128 != 0 ||
+  if (PL_COUNT(pl) != 1 || !d.gn_stats || d.rows_per_b != 128 || d.M % 128 != 0 ||
       d.N % 64 != 0 || d.N > 1024 || d.Cin % 64 != 0 || d.ksplit > 1 || d.resid || d.out_scale != 1.f || d.swiglu ||
       d.rope_cos || d.qkv_D > 0)
     return false;
@@ -1865,9 +1865,8 @@ bool igemm2_gnfin_ok(const GemmDesc& d, int pl) {
 }
 bool igemm_halo3x3_eligible(const GemmDesc& d, int pl) { return igemm_halo3x3_tile(d, pl) != 0; }
 bool igemm_halo3x3_gnfin_ok(const GemmDesc& d, int pl) {
-  const bool off = getenv("DSN_NO_GN_FIN") != nullptr;  // (per call: tests flip it)
   const int v = igemm_halo3x3_tile(d, pl);
-  if (off || !v || !d.gn_stats || d.N % 32 != 0 || d.N > 1024 || d.rows_per_b % v != 0 || d.out_scale != 1.f) return false;
+  if (!v || !d.gn_stats || d.N % 32 != 0 || d.N > 1024 || d.rows_per_b % v != 0 || d.out_scale != 1.f) return false;
   if (!gn_groups_fit(d.N, 128)) return false;
   static int cap[2][2] = {{-1, -1}, {-1, -1}};
   int& c = cap[PL_F16(pl) ? 1 : 0][v == 256 ? 1 : 0];
@@ -2015,7 +2014,7 @@ hipError_t igemm_panel_fp8_launch(const GemmDesc& din, int bn, hipStream_t strea
   // plain row-major GEMM only: one "batch item" of M rows, one tap, K = 2 * Cin fp8 per row, whole 128-wide k-tiles
   if (!d.a_scale || !d.w_scale || d.taps != 1 || d.in_stride != 1 || d.in_pad != 0 || d.rows_per_b != d.M ||
       d.img_w > 0 || d.Cin % 64 != 0 || d.mx_kblocks != d.Cin / 16 || d.M <= 0 || d.N <= 0 || d.panel_rows <= 0 ||
-      d.panel_rows > 17 * 16 || (long)std::max(d.M, d.N) * d.Cin * 2 >= (1L << 32))
+      d.panel_rows > PANEL_ROWS_MAX || (long)std::max(d.M, d.N) * d.Cin * 2 >= (1L << 32))
     return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 64 != 0)) return hipErrorInvalidValue;
   // folded ff_norm: the producer (statistics + raw fp8 x') and the SwiGLU consumer, as in igemm_panel_launch
@@ -2075,7 +2074,7 @@ hipError_t igemm_skinny_launch(const GemmDesc& din, int pl, hipStream_t stream) 
 hipError_t igemm_panel_launch(const GemmDesc& din, int pl, int bn, hipStream_t stream) {
   const int planes = PL_COUNT(pl), f16 = PL_F16(pl);
   GemmDesc d = din;
-  if (d.Cin % 64 != 0 || d.M <= 0 || d.N <= 0 || d.panel_rows <= 0 || d.panel_rows > 17 * 16) return hipErrorInvalidValue;
+  if (d.Cin % 64 != 0 || d.M <= 0 || d.N <= 0 || d.panel_rows <= 0 || d.panel_rows > PANEL_ROWS_MAX) return hipErrorInvalidValue;
   if (d.panel_wm == 2 && d.cfg_bk == 32 && d.Cin % 32 != 0) return hipErrorInvalidValue;
   if (d.swiglu && (d.N % 32 != 0)) return hipErrorInvalidValue;
   if (d.img_w > 0) return hipErrorInvalidValue;

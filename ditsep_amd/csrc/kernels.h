@@ -49,8 +49,9 @@ void launch_zero_tail(float* x, const int* lens, int B, int n, int D, int T, hip
 
 // ---- DiT pieces ---------------------------------------------------------------
 // x += bias + sum(split-K slabs) (written back when nslab > 0), then LayerNorm (do_norm) or a
-// plain copy to operand planes.  D <= 4096, D % 4 == 0.
+// plain copy to operand planes.  D <= 4096, D % 4 == 0, nslab <= RESIDUAL_NORM_MAX_SLABS.
 // out_fp8_scale != null: `out` receives fp8 (e4m3) bytes [rows][D] and out_fp8_scale E8M0 scales [rows][D/32].
+constexpr int RESIDUAL_NORM_MAX_SLABS = 8;
 void launch_residual_norm(float* x, const float* slabs, int nslab, long slab_stride, const float* bias,
                           const float* gamma, const float* beta, op16_t* out, long ps, int planes, int rows, int D,
                           float eps, int do_norm, hipStream_t s, unsigned char* out_fp8_scale = nullptr);

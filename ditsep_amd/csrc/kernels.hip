@@ -1047,7 +1047,7 @@ void launch_residual_norm(float* x, const float* slabs, int nslab, long slab_str
     case 5: RN_LAUNCH(MV, 5, BT_); break;                                                  \
     case 6: RN_LAUNCH(MV, 6, BT_); break;                                                  \
     case 7: RN_LAUNCH(MV, 7, BT_); break;                                                  \
-    default: RN_LAUNCH(MV, 8, BT_); break;  /* pick_ksplit caps the split at 8 */          \
+    default: RN_LAUNCH(MV, 8, BT_); break;  /* RESIDUAL_NORM_MAX_SLABS */                  \
   }
   if (D == 4 * TPB && rows > 256 && nslab <= 4) {  // bandwidth-bound: a row per workgroup, everything in flight
 #define RNR(NS_)                                                                                                     \

@@ -461,7 +461,7 @@ static bool ru_act_ok(int kind, const float* a, const float* b) {
   return kind == DSN_ACT_NONE || kind == DSN_ACT_ELU;
 }
 
-hipError_t ru_fused_launch(const RuDesc& d, int pl, hipStream_t st) {
+hipError_t ru_fused_launch(const RuDesc& d, int pl, bool v1, hipStream_t st) {
   if (d.dil < 1 || d.dil > 9 || d.S <= 0 || d.L <= 0) return hipErrorInvalidValue;
   if (!d.A || !d.X || !d.W7 || !d.W1 || !d.b7 || !d.b1 || (!d.out_f32 && !d.out_planes)) return hipErrorInvalidValue;
   if (!ru_act_ok(d.act_mid, d.mid_a, d.mid_b)) return hipErrorInvalidValue;
@@ -475,7 +475,6 @@ hipError_t ru_fused_launch(const RuDesc& d, int pl, hipStream_t st) {
         if (std::less<const op16_t*>()(a, o + n) && std::less<const op16_t*>()(o, a + n)) return hipErrorInvalidValue;
       }
   }
-  const bool v1 = getenv("DSN_RU_V1") != nullptr;  // read per launch: tests flip it inside one process
   if (P == 1 && !v1) return f16 ? launch2_t<1>(d, st) : launch2_t<0>(d, st);
   if (P == 1) return f16 ? launch_t<1, 1>(d, st) : launch_t<1, 0>(d, st);
   return f16 ? launch_t<2, 1>(d, st) : launch_t<2, 0>(d, st);

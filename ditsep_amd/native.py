@@ -32,7 +32,7 @@ EXPORTS = [
     "dsn_encode", "dsn_decode_chunked", "dsn_encode_chunked",
     "dsn_latent_frames", "dsn_hop_length", "dsn_separate", "dsn_enable_graphs",
     "dsn_workspace_bytes", "dsn_profile_begin", "dsn_profile_end", "dsn_profile_hbm", "dsn_profile_rows",
-    "dsn_test_gemm", "dsn_test_kernel", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
+    "dsn_test_gemm", "dsn_test_kernel", "dsn_dit_plan", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
     "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged", "dsn_window_stitch",
 ]
@@ -115,6 +115,13 @@ class DsnConfig(C.Structure):
         ("vae_has_encoder", C.c_int32), ("vae_has_decoder", C.c_int32),
         ("sde_theta", C.c_float), ("sde_sigma_min", C.c_float), ("sde_sigma_max", C.c_float),
     ]
+
+
+class DsnDitPlan(C.Structure):
+    """dsn_dit_plan (include/ditsep_hip.h): what one DiT score call would run; needs no GPU"""
+    _fields_ = [(k, C.c_int) for k in (
+        "M", "S", "skinny", "fold_rows", "qa_ipp", "qkv_rows", "attn_out_ksplit", "attn_out_rows", "ff_in_rows",
+        "ff_out_ksplit", "ff_out_rows", "project_out_rows")]
 
 
 # dsn_test_gemm (include/ditsep_hip.h): which kernel of the implicit-GEMM family runs the descriptor
@@ -428,6 +435,7 @@ def load_library() -> C.CDLL:
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.dsn_test_gemm.argtypes = [vp, C.POINTER(DsnTestGemm), vp]
     lib.dsn_test_kernel.argtypes = [vp, C.POINTER(DsnTestKernel), vp]
+    lib.dsn_dit_plan.argtypes = [C.POINTER(DsnConfig), ci, ci, C.POINTER(DsnDitPlan)]
     lib.dsn_si_sdr_pit.argtypes = [vp, vp, vp, ci, ci, ci, fp, C.POINTER(ci), vp]
     lib.dsn_si_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, fp, fp, fp, C.POINTER(ci), vp]
     lib.dsn_stoi.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(ci), fp, C.POINTER(ci), vp]

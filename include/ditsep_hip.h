@@ -465,7 +465,7 @@ int dsn_profile_rows(dsn_ctx* ctx, int max_rows, char* names, double* ms, double
                      int64_t* launches);
 
 /* ---- NOT PART OF THE ABI ------------------------------------------------------------------------------------
- * dsn_test_gemm, dsn_test_kernel, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests,
+ * dsn_test_gemm, dsn_test_kernel, dsn_dit_plan, dsn_debug_read and dsn_bench_igemm below are hooks for this repository's own tests,
  * repro scripts and kernel sweeps.  They name internal workspace buffers and kernel variants, change without notice, and a binding of
  * the reference-facing interface must not use them. */
 /* Test hook: run ONE chosen kernel of the implicit-GEMM family (ditsep_amd/csrc/igemm.h) on a descriptor built from
@@ -670,6 +670,22 @@ typedef struct DsnTestKernel {
   float* out2_f32;
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
+
+/* Test hook: what one DiT score call of B mixtures x T frames would run under `cfg` (its precision included) and the
+ * DSN_* switches of the environment -- the plan dit_forward launches from (ditsep_amd/csrc/dit_plan.h).  Needs no
+ * context and no GPU.  A `*_rows` of 0 means that GEMM runs no row-panel kernel. */
+typedef struct DsnDitPlan {
+  int M, S;                   /* token rows B * S, tokens per item S = T + 1 */
+  int skinny;                 /* the layer GEMMs run the weight-streaming skinny kernel */
+  int fold_rows;              /* > 0: ff_norm folded into FF-in; to_out in panels of this many rows, no split-K */
+  int qa_ipp;                 /* > 0: fused to_qkv + attention with this many items per panel */
+  int qkv_rows;
+  int attn_out_ksplit, attn_out_rows;
+  int ff_in_rows;
+  int ff_out_ksplit, ff_out_rows;
+  int project_out_rows;
+} DsnDitPlan;
+int dsn_dit_plan(const dsn_config* cfg, int B, int T, DsnDitPlan* out);
 
 /* Development hook: copy `count` floats of a named workspace buffer to host memory. */
 int dsn_debug_read(dsn_ctx* ctx, const char* name, float* host, int64_t count);

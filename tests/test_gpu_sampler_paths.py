@@ -4,7 +4,8 @@ Every sampler entry point stages its tensors into the same workspace buffers ("p
 the uploaded step-time table's signature, so three things are pinned here on the tiny DiT (bf16x3, B=2, T=8, injected
 noise): a graph-replayed call equals the eager call bit for bit, for the Mix / PriorMix / Schroedinger-bridge samplers
 and the pc_sample variants the other test files leave out; calls of different samplers interleaved on one engine
-do not disturb each other; and a context whose weights are not finalized is refused on the host."""
+do not disturb each other; and a context whose weights are not finalized is refused on the host.  A fourth (fp16, width
+256): a captured graph follows a kernel-choice switch that changes between two calls."""
 import pytest
 import torch
 
@@ -116,3 +117,37 @@ def test_unfinalized_context_is_refused_before_any_launch():
         eng.close()
         if fresh is not None:
             fresh.close()
+
+
+def test_captured_graph_follows_a_switch_changed_between_calls(monkeypatch):
+    """A graph remembers the switches it was built under (engine.hip: run_graphed, Switches).  DiT of width 256 (4 heads,
+    depth 2), fp16, B = 2, T = 8: M = 18 token rows, inside the skinny window by default and on the row-panel kernels
+    under DSN_SKINNY_MAX=0 -- another summation order, so the two eager results differ.  With graphs on, four calls under
+    the default switches (warm-up, capture, two replays), then DSN_SKINNY_MAX=0: the call must give the eager
+    DSN_SKINNY_MAX=0 result, not a replay of the graph captured under the old choice."""
+    monkeypatch.delenv("DSN_SKINNY_MAX", raising=False)
+    cfg = odit.DiTConfig(n_src=2, embed_dim=256, depth=2, num_heads=4)
+    sd = odit.random_dit_weights(cfg, 35, out_gain=0.005)
+    n = 2
+    g = torch.Generator().manual_seed(8)
+    y = torch.randn((B, 1, cfg.latent_dim, T), generator=g)
+    noise = torch.randn((1 + n * 2, B, cfg.n_src, cfg.latent_dim, T), generator=g)
+    eng = make_engine(cfg, sd, precision=native.PREC_FP16)
+
+    def run():
+        out = eng.pc_sample(y, noise, N=n)
+        return (out[0] if isinstance(out, tuple) else out).clone()
+
+    try:
+        eager_skinny = run()
+        monkeypatch.setenv("DSN_SKINNY_MAX", "0")
+        eager_panel = run()
+        assert not torch.equal(eager_skinny, eager_panel)    # else the last assertion below would be vacuous
+        monkeypatch.delenv("DSN_SKINNY_MAX")
+        eng.enable_graphs(True)
+        for _ in range(4):
+            assert torch.equal(run(), eager_skinny)
+        monkeypatch.setenv("DSN_SKINNY_MAX", "0")
+        assert torch.equal(run(), eager_panel)
+    finally:
+        eng.close()
