@@ -23,6 +23,7 @@
 #include "dit_plan.h"
 #include "igemm.h"
 #include "kernels.h"
+#include "score_window.h"
 
 namespace {
 
@@ -1079,8 +1080,16 @@ struct dsn_ctx {
   // lens (device int [B], null = dense): a ragged batch padded to T frames -- tokens per item, 1 + its frame count.
   // The kernel-family choice below is that of (B, T); only the attention launch takes its length-aware variant (every
   // other operation acts per token, so an item's valid rows come out as in a call of its own).
+  // wm (null = none): the items are windows cut from longer tensors -- xt [R,n,Dl,wm->Tsrc], mix [R,1,Dl,wm->Tsrc], item b
+  // the window wm->wtab[b] = (recording, start, length) -- gathered by the pack launch; the score tokens go to wm->sc.
+  // Everything between the pack and the last store is the dense call at (B, T).
+  struct WinMap {
+    const int* wtab;
+    int Tsrc;
+    float* sc;
+  };
   float* dit_forward(const float* xt, const float* t, const float* mix, int B, int T, hipStream_t st,
-                     const int* lens = nullptr) {
+                     const int* lens = nullptr, const WinMap* wm = nullptr) {
     const int n = cfg.n_src, Dl = cfg.latent_dim, D = cfg.dit_embed_dim, H = cfg.dit_heads;
     const int io = n * Dl, din = io + Dl, S = T + 1;
     const long Mt = (long)B * T, M = (long)B * S;
@@ -1089,7 +1098,7 @@ struct dsn_ctx {
     op16_t* Ap = wsbuf<op16_t>("dit_Ap", M * D * P);
     op16_t* QKVp = wsbuf<op16_t>("dit_QKVp", M * 3 * D * P);
     op16_t* FF = wsbuf<op16_t>("dit_FF", M * 4 * D * P);
-    float* SC = wsbuf<float>("sc", Mt * io);
+    float* SC = wm ? wm->sc : wsbuf<float>("sc", Mt * io);
     // DSN_PREC_FP8: the layer GEMMs' A operands as e4m3 bytes + E8M0 block scales (LayerNorm output / attention
     // output share one buffer, the SwiGLU hidden state has its own)
     unsigned char* A8 = fp8 ? wsbuf<unsigned char>("dit_A8", M * D) : nullptr;
@@ -1112,7 +1121,8 @@ struct dsn_ctx {
     float* rs = wsbuf<float>("rope_sin_" + std::to_string(S), (long)S * rot);
     if (new_rope) launch_rope_tables(rc, rs, S, rot, st);
 
-    launch_pack_tokens(xt, io, mix, Dl, B, T, nullptr, Up, Mt * din, PL, st);
+    if (wm) launch_win_pack_tokens(xt, io, mix, Dl, wm->wtab, B, T, wm->Tsrc, nullptr, Up, Mt * din, PL, st);
+    else launch_pack_tokens(xt, io, mix, Dl, B, T, nullptr, Up, Mt * din, PL, st);
     {  // X[b, 1+t] = (U + U Wpre^T) Win^T, one folded matrix (fold_dit_io)
       Tag tg(this, "dit.project_in");
       GemmDesc d = base_desc(Up, Mt * din, pin, B, T, T);
@@ -1308,6 +1318,58 @@ struct dsn_ctx {
     fail(DSN_ESTATE, "no score network configured (score_kind=%d)", cfg.score_kind);
   }
 
+  // The window-blended score (include/ditsep_hip.h, dsn_score_windowed).  upload_window_tables: the plan's tables into
+  // the fixed workspace buffers "win_tab_i" (wtab | ftab | token counts) and "win_tab_f" (fw) the kernels read -- outside
+  // any capture, so they are data of a cached graph, not constants of it.
+  struct WinTables {
+    const ScoreWindowPlan* plan;
+    const int *wtab, *ftab, *wlens;
+    const float* fw;
+    int batch;  // windows per DiT call (<= 0: all)
+  };
+  std::vector<int32_t> win_host_i;
+  std::vector<float> win_host_f;
+  const int* win_dev_i = nullptr;
+  const float* win_dev_f = nullptr;
+  WinTables upload_window_tables(const ScoreWindowPlan& p, int batch, hipStream_t st) {
+    std::vector<int32_t> hi(p.wtab);
+    hi.insert(hi.end(), p.ftab.begin(), p.ftab.end());
+    hi.insert(hi.end(), p.wlens.begin(), p.wlens.end());
+    int* di = wsbuf<int>("win_tab_i", hi.size());
+    float* df = wsbuf<float>("win_tab_f", p.fw.size());
+    if (hi != win_host_i || di != win_dev_i || p.fw != win_host_f || df != win_dev_f) {
+      HIPCHK(hipMemcpyAsync(di, hi.data(), sizeof(int32_t) * hi.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(df, p.fw.data(), sizeof(float) * p.fw.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+      win_host_i = hi;
+      win_host_f = p.fw;
+      win_dev_i = di;
+      win_dev_f = df;
+    }
+    return {&p, di, di + p.wtab.size(), di + p.wtab.size() + p.ftab.size(), df, batch};
+  }
+  // xt [R,n,Dl,T], tw [Wtot] (every window's time: its recording's), mix [R,1,Dl,T] -> blended score token-major
+  // [R*T][n*Dl] in ws "win_blend".  The windows run as dense DiT calls of at most `batch` items whose score tokens land
+  // in one [Wtot][Twin][n*Dl] buffer; one gather launch then blends them.
+  float* score_windowed(const float* xt, const float* tw, const float* mix, const WinTables& w, hipStream_t st) {
+    if (!finalized) fail(DSN_ESTATE, "weights not finalized");
+    if (cfg.score_kind != DSN_SCORE_DIT) fail(DSN_EINVAL, "window-blended scores need the DiT score network");
+    const ScoreWindowPlan& p = *w.plan;
+    const int io = cfg.n_src * cfg.latent_dim;
+    float* WS = wsbuf<float>("win_sc", (long)p.Wtot * p.Twin * io);
+    float* out = wsbuf<float>("win_blend", (long)p.R * p.T * io);
+    const int nb = w.batch > 0 ? std::min(w.batch, p.Wtot) : p.Wtot;
+    for (int lo = 0; lo < p.Wtot; lo += nb) {
+      const WinMap wm{w.wtab + 3L * lo, p.T, WS + (long)lo * p.Twin * io};
+      dit_forward(xt, tw + lo, mix, std::min(nb, p.Wtot - lo), p.Twin, st, p.shorts ? w.wlens + lo : nullptr, &wm);
+    }
+    // algorithmic bytes: every output row written once, one or two window rows read for it
+    prof_launch("score.win_blend", (double)p.R * p.T * io * 4.0 * 2.0, st, [&] {
+      launch_win_blend_tokens(WS, w.ftab, w.fw, out, (long)p.R * p.T, io, p.Twin, st);
+    });
+    return out;
+  }
+
   // ---------------------------------------------------------------- OUVE scalars
   struct Sched {
     std::vector<float> t, std, step, gain, G, g;
@@ -1443,25 +1505,31 @@ struct dsn_ctx {
   };
   // lens (device, null = dense): ragged batch -- every score call takes it, and the result's frames past an item's
   // length are written as zero (the update kernels are elementwise: padding costs them the padded positions only)
+  // win (null = none): the window-blended score of the long state (score_windowed); the step times are then one per
+  // window ("pc_t" [N][Wtot], as is the time-embedding pass), and lens only marks the tail to clear
   float* pc_sample(const float* y, const float* noise, int B, int T, int N, const PcOpts& o, hipStream_t st,
-                   const int* lens = nullptr) {
+                   const int* lens = nullptr, const WinTables* win = nullptr) {
     const int n = cfg.n_src, Dl = cfg.latent_dim;
     const long sz = (long)B * n * Dl * T;
+    const int tB = win ? win->plan->Wtot : B;  // step times per step
     float* x = wsbuf<float>("pc_x", sz);
     float* xm = wsbuf<float>("pc_xm", sz);
-    float* tv = wsbuf<float>("pc_t", (long)B * N);
+    float* tv = wsbuf<float>("pc_t", (long)tB * N);
     float* norms = o.corr == DSN_CORR_LANGEVIN ? wsbuf<float>("pc_norms", 2L * B) : nullptr;
     const Sched s = schedule(N, o.t_eps, o.snr);
     const float dt = (float)(1.0 / N);
     const float* z = noise;
-    TimeEmbedPass te(this, tv, N, B, st);
+    TimeEmbedPass te(this, tv, N, tB, st);
+    auto score = [&](const float* ti) {
+      return win ? score_windowed(x, ti, y, *win, st) : score_tokens(x, ti, y, B, T, st, lens);
+    };
     launch_pc_prior(o.prior_mean ? o.prior_mean : y, o.prior_mean != nullptr, z, x, s.stdT, B, n, Dl, T, st);
     z += sz;
     const bool keep_mean = o.inter != nullptr;  // only `intermediate` reads the corrector's x_mean
     for (int i = 0; i < N; ++i) {
-      const float* ti = tv + (long)i * B;
+      const float* ti = tv + (long)i * tB;
       for (int k = 0; k < o.c; ++k) {
-        float* sc = score_tokens(x, ti, y, B, T, st, lens);
+        float* sc = score(ti);
         if (norms) {
           launch_pc_item_norms(sc, (long)n * Dl * T, B, norms, st);
           launch_pc_item_norms(z, (long)n * Dl * T, B, norms + B, st);
@@ -1478,7 +1546,7 @@ struct dsn_ctx {
         if (o.denoise && i == N - 1) HIPCHK(hipMemcpyAsync(xm, x, sizeof(float) * sz, hipMemcpyDeviceToDevice, st));
         continue;
       }
-      float* sc = score_tokens(x, ti, y, B, T, st, lens);
+      float* sc = score(ti);
       launch_pc_predictor(x, xm, y, sc, z, cfg.sde_theta, dt, s.G[i], s.g[i], o.pred == DSN_PRED_EULER_MARUYAMA, B, n,
                           Dl, T, st);
       z += sz;
@@ -1600,6 +1668,7 @@ struct dsn_ctx {
     int B, T;
     long draws;
     hipStream_t caller;
+    int time_rows = 0;  // step times per step when not B (the windowed sampler: one per window)
   };
   template <class F>
   void run_sampler(const SamplerCall& a, const std::vector<float>& t_per_step, const char* key, const char* result,
@@ -1609,7 +1678,7 @@ struct dsn_ctx {
     float* yb = wsbuf<float>("pc_y", ysz);
     float* nz = a.draws ? wsbuf<float>("pc_noise", sz * a.draws) : nullptr;
     float* pm = a.prior_mean ? wsbuf<float>("pc_prior_mean", sz) : nullptr;
-    upload_step_times(t_per_step, a.B, a.caller);
+    upload_step_times(t_per_step, a.time_rows ? a.time_rows : a.B, a.caller);
     StreamScope sc(this, a.caller);
     HIPCHK(hipMemcpyAsync(yb, a.y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, sc.st));
     if (pm) HIPCHK(hipMemcpyAsync(pm, a.prior_mean, sizeof(float) * sz, hipMemcpyDeviceToDevice, sc.st));
@@ -2016,10 +2085,29 @@ int dsn_score_ragged(dsn_ctx* ctx, const float* xt, const float* t, const float*
   });
 }
 
-// dsn_pc_sample_ex (frames == null) and dsn_pc_sample_ragged
+// The refusals and the plan of the window-blended entry points (include/ditsep_hip.h), before anything is allocated
+struct WindowArgs {
+  int Tw, To, fade, batch;
+};
+static ScoreWindowPlan windowed_plan(dsn_ctx* ctx, const char* who, const int32_t* frames, int R, int T,
+                                     const WindowArgs& wa) {
+  if (ctx->cfg.score_kind != DSN_SCORE_DIT)
+    fail(DSN_EINVAL, "%s: window-blended scores need the DiT score network (their windows are batch items of the "
+         "trained length)", who);
+  char buf[160];
+  if (const char* why = score_window_refusal(frames, R, T, wa.Tw, wa.To, wa.fade, buf, sizeof buf))
+    fail(DSN_EINVAL, "%s: %s", who, why);
+  if (ctx->cfg.n_src * ctx->cfg.latent_dim % 4 != 0)
+    fail(DSN_EINVAL, "%s: the blend launch loads 16 bytes per lane: n_src * latent_dim = %d is not a multiple of 4", who,
+         ctx->cfg.n_src * ctx->cfg.latent_dim);
+  if (!ctx->finalized) fail(DSN_ESTATE, "weights not finalized");
+  return score_window_plan(frames, R, T, wa.Tw, wa.To, wa.fade);
+}
+
+// dsn_pc_sample_ex (frames == null), dsn_pc_sample_ragged and dsn_pc_sample_windowed (wa)
 static int pc_sample_call(dsn_ctx* ctx, const float* y, const int32_t* frames, bool ragged, const float* noise,
                           uint64_t seed, float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out,
-                          void* stream) {
+                          void* stream, const WindowArgs* wa = nullptr) {
   return guarded(ctx, [&] {
     if (!y || !x_out || !opts || B <= 0 || T <= 0 || N <= 0 || opts->corrector_steps < 0)
       fail(DSN_EINVAL, "dsn_pc_sample: bad arguments");
@@ -2034,6 +2122,19 @@ static int pc_sample_call(dsn_ctx* ctx, const float* y, const int32_t* frames, b
              "per-item norms would run over the padding");
       if (!ctx->finalized) fail(DSN_ESTATE, "weights not finalized");
       lens = ctx->upload_lens(frames, B, (hipStream_t)stream);
+    }
+    ScoreWindowPlan wplan;
+    dsn_ctx::WinTables wt{};
+    if (wa) {
+      const char* who = "dsn_pc_sample_windowed";
+      if (opts->prior_mean || opts->intermediates || opts->timesteps)
+        fail(DSN_EINVAL, "%s: prior_mean, intermediates and timesteps are not supported", who);
+      wplan = windowed_plan(ctx, who, frames, B, T, *wa);
+      if (opts->corrector == DSN_CORR_LANGEVIN && wplan.ragged)
+        fail(DSN_EINVAL, "%s: the langevin corrector (DSN_CORR_LANGEVIN) has no form for recordings of different "
+             "lengths: its per-item norms would run over the padding", who);
+      if (wplan.ragged) lens = ctx->upload_lens(frames, B, (hipStream_t)stream);  // (the tail to clear)
+      wt = ctx->upload_window_tables(wplan, wa->batch, (hipStream_t)stream);
     }
     dsn_ctx::PcOpts o;
     o.pred = opts->predictor;
@@ -2055,15 +2156,20 @@ static int pc_sample_call(dsn_ctx* ctx, const float* y, const int32_t* frames, b
         c->t_override.clear();
       }
     } restore{ctx, graphs};
-    char key[192];
+    char key[256];
     // (the last field marks a ragged call: the same graph whatever the lengths, another one than the dense call's)
-    snprintf(key, sizeof key, "pc:%d:%d:%d:%d:%a:%a:%d:%d:%d:%d:%d", B, T, N, o.c, o.snr, o.t_eps, o.denoise, o.pred,
-             o.corr, opts->prior_mean != nullptr, lens != nullptr);
-    ctx->run_sampler({y, noise, opts->prior_mean, seed, x_out, B, T, o.draws(N), (hipStream_t)stream},
+    int kn = snprintf(key, sizeof key, "pc:%d:%d:%d:%d:%a:%a:%d:%d:%d:%d:%d", B, T, N, o.c, o.snr, o.t_eps, o.denoise,
+                      o.pred, o.corr, opts->prior_mean != nullptr, lens != nullptr);
+    // (a windowed call: the shape of its plan -- the tables themselves are data of the graph)
+    if (wa)
+      snprintf(key + kn, sizeof key - kn, ":w%d:%d:%d:%d:%d:%d", wplan.Wtot, wplan.Twin, wa->Tw, wa->To,
+               wa->batch > 0 ? std::min(wa->batch, wplan.Wtot) : wplan.Wtot, (int)wplan.shorts);
+    ctx->run_sampler({y, noise, opts->prior_mean, seed, x_out, B, T, o.draws(N), (hipStream_t)stream,
+                      wa ? wplan.Wtot : 0},
                      ctx->schedule(N, o.t_eps, o.snr).t, key, o.denoise ? "pc_xm" : "pc_x",
                      [&](const float* yb, const float* nz, const float* pm, hipStream_t s2) {
                        o.prior_mean = pm;
-                       return ctx->pc_sample(yb, nz, B, T, N, o, s2, lens);
+                       return ctx->pc_sample(yb, nz, B, T, N, o, s2, lens, wa ? &wt : nullptr);
                      });
     if (nfe_out) *nfe_out = N * (o.c + 1);
   });
@@ -2077,6 +2183,41 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
 int dsn_pc_sample_ragged(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
                          float* x_out, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
   return pc_sample_call(ctx, y, frames, true, noise, seed, x_out, B, T, N, opts, nfe_out, stream);
+}
+
+int dsn_pc_sample_windowed(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
+                           float* x_out, int R, int T, int N, int Tw, int To, int fade, int batch,
+                           const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
+  const WindowArgs wa{Tw, To, fade, batch};
+  return pc_sample_call(ctx, y, frames, false, noise, seed, x_out, R, T, N, opts, nfe_out, stream, &wa);
+}
+
+int dsn_score_window_plan(const int32_t* frames, int R, int T, int Tw, int To, int fade, int32_t* wtab, int32_t* ftab,
+                          float* fw, int* Wtot, int* Twin) {
+  char buf[160];
+  if (score_window_refusal(frames, R, T, Tw, To, fade, buf, sizeof buf)) return DSN_EINVAL;
+  const ScoreWindowPlan p = score_window_plan(frames, R, T, Tw, To, fade);
+  if (wtab) std::copy(p.wtab.begin(), p.wtab.end(), wtab);
+  if (ftab) std::copy(p.ftab.begin(), p.ftab.end(), ftab);
+  if (fw) std::copy(p.fw.begin(), p.fw.end(), fw);
+  if (Wtot) *Wtot = p.Wtot;
+  if (Twin) *Twin = p.Twin;
+  return DSN_OK;
+}
+
+int dsn_score_windowed(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
+                       int R, int T, int Tw, int To, int fade, int batch, void* stream) {
+  return guarded(ctx, [&] {
+    if (!xt || !t || !mix || !out) fail(DSN_EINVAL, "dsn_score_windowed: bad arguments");
+    const ScoreWindowPlan p = windowed_plan(ctx, "dsn_score_windowed", frames, R, T, {Tw, To, fade, batch});
+    hipStream_t st = (hipStream_t)stream;
+    const dsn_ctx::WinTables wt = ctx->upload_window_tables(p, batch, st);
+    float* tw = ctx->wsbuf<float>("win_t", p.Wtot);
+    launch_win_times(t, wt.wtab, p.Wtot, tw, st);  // every window's time: its recording's
+    float* sc = ctx->score_windowed(xt, tw, mix, wt, st);
+    launch_unpack_tokens(sc, out, R, ctx->cfg.n_src * ctx->cfg.latent_dim, T, st);
+    HIPCHK(hipGetLastError());
+  });
 }
 
 int dsn_pc_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t seed, float* x_out, int B, int T, int N,
@@ -2603,6 +2744,31 @@ int dsn_separate_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, c
   if ((rc = dsn_encode_ragged(ctx, mix, frames, vae_noise, seed, y, B, T, stream))) return rc;
   if ((rc = dsn_pc_sample_ragged(ctx, y, frames, noise, seed + 1, x, B, T, N, opts, nfe_out, stream))) return rc;
   return dsn_decode_ragged(ctx, x, frames, wav, B, T, stream);
+}
+
+int dsn_separate_windowed(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise,
+                          const float* noise, uint64_t seed, float* wav, int R, int T, int N, int Tw, int To, int fade,
+                          int batch, const dsn_sampler_opts* opts, int* nfe_out, void* stream) {
+  float* y = nullptr;
+  float* x = nullptr;
+  int rc = guarded(ctx, [&] {
+    if (!mix || !wav || !opts || R <= 0 || T <= 0 || N <= 0) fail(DSN_EINVAL, "dsn_separate_windowed: bad arguments");
+    ctx->check_frames("dsn_separate_windowed", frames, R, T,
+                      dsn_ctx::RAGGED_DIT | dsn_ctx::RAGGED_ENC | dsn_ctx::RAGGED_DEC);
+    const ScoreWindowPlan p = windowed_plan(ctx, "dsn_separate_windowed", frames, R, T, {Tw, To, fade, batch});
+    if (opts->corrector == DSN_CORR_LANGEVIN && p.ragged)
+      fail(DSN_EINVAL, "dsn_separate_windowed: the langevin corrector (DSN_CORR_LANGEVIN) has no form for recordings of "
+           "different lengths: its per-item norms would run over the padding");
+    const long ysz = (long)R * ctx->cfg.latent_dim * T;
+    y = ctx->wsbuf<float>("sep_y", ysz);
+    x = ctx->wsbuf<float>("sep_x", ysz * ctx->cfg.n_src);
+  });
+  if (rc) return rc;
+  if ((rc = dsn_encode_ragged(ctx, mix, frames, vae_noise, seed, y, R, T, stream))) return rc;
+  if ((rc = dsn_pc_sample_windowed(ctx, y, frames, noise, seed + 1, x, R, T, N, Tw, To, fade, batch, opts, nfe_out,
+                                   stream)))
+    return rc;
+  return dsn_decode_ragged(ctx, x, frames, wav, R, T, stream);
 }
 
 // Scale-invariant SDR with permutation-invariant assignment (the step right after the path in
@@ -3851,6 +4017,50 @@ int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream) {
         if (oplanes && t->out_ps < (long)t->B * t->T * (t->C0 + t->C1))
           fail(DSN_EINVAL, "test_kernel pack_tokens: out_ps %ld < B*T*(C0+C1)", (long)t->out_ps);
         launch_pack_tokens(t->x, t->C0, t->y, t->C1, t->B, t->T, t->out_f32, oplanes, t->out_ps, PL, st);
+        break;
+      }
+      case DSN_TK_WIN_PACK_TOKENS: {
+        if (t->B < 1 || t->T < 1 || t->C0 < 1 || t->C1 < 0 || t->R < 1 || t->Tsrc < 1)
+          fail(DSN_EINVAL, "test_kernel win_pack_tokens: B, T, C0, R, Tsrc must be positive and C1 >= 0 (B=%d T=%d C0=%d "
+               "C1=%d R=%d Tsrc=%d)", t->B, t->T, t->C0, t->C1, t->R, t->Tsrc);
+        if (!t->x || (t->C1 > 0) != !!t->y || !t->wtab)
+          fail(DSN_EINVAL, "test_kernel win_pack_tokens: x (src0) or wtab missing, or y (src1) does not go with C1 = %d",
+               t->C1);
+        if (!t->out_f32 && !oplanes) fail(DSN_EINVAL, "test_kernel win_pack_tokens: out_f32 and out_planes both missing");
+        if (oplanes && t->out_ps < (long)t->B * t->T * (t->C0 + t->C1))
+          fail(DSN_EINVAL, "test_kernel win_pack_tokens: out_ps %ld < B*T*(C0+C1)", (long)t->out_ps);
+        std::vector<int32_t> h((size_t)t->B * 3);
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(h.data(), t->wtab, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+        for (int b = 0; b < t->B; ++b) {
+          const int r = h[3 * b], s = h[3 * b + 1], l = h[3 * b + 2];
+          if (r < 0 || r >= t->R || s < 0 || l < 0 || l > t->T || (long)s + l > t->Tsrc)
+            fail(DSN_EINVAL, "test_kernel win_pack_tokens: wtab[%d] = (%d, %d, %d) outside R = %d, Tsrc = %d, T = %d", b, r,
+                 s, l, t->R, t->Tsrc, t->T);
+        }
+        launch_win_pack_tokens(t->x, t->C0, t->y, t->C1, reinterpret_cast<const int*>(t->wtab), t->B, t->T, t->Tsrc,
+                               t->out_f32, oplanes, t->out_ps, PL, st);
+        break;
+      }
+      case DSN_TK_WIN_BLEND_TOKENS: {
+        if (t->B < 1 || t->T < 1 || t->C < 4 || t->C % 4 != 0 || t->rows < 1)
+          fail(DSN_EINVAL, "test_kernel win_blend_tokens: B, T, rows must be positive and C a positive multiple of 4 "
+               "(B=%d T=%d rows=%d C=%d)", t->B, t->T, t->rows, t->C);
+        if (!t->x || !t->ftab || !t->fw || !t->out_f32)
+          fail(DSN_EINVAL, "test_kernel win_blend_tokens: x (window tokens), ftab, fw or out_f32 missing");
+        if (((uintptr_t)t->x | (uintptr_t)t->out_f32) & 15)
+          fail(DSN_EINVAL, "test_kernel win_blend_tokens: x / out_f32 must be 16-byte aligned");
+        std::vector<int32_t> h((size_t)t->rows * 4);
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(h.data(), t->ftab, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < t->rows; ++f)
+          for (int k = 0; k < 4; k += 2) {
+            const int w = h[4 * f + k], o = h[4 * f + k + 1];
+            if (w >= t->B || (w >= 0 && (o < 0 || o >= t->T)))
+              fail(DSN_EINVAL, "test_kernel win_blend_tokens: ftab[%d] names window %d offset %d outside B = %d, T = %d",
+                   f, w, o, t->B, t->T);
+          }
+        launch_win_blend_tokens(t->x, reinterpret_cast<const int*>(t->ftab), t->fw, t->out_f32, t->rows, t->C, t->T, st);
         break;
       }
       case DSN_TK_UNPACK_TOKENS: {

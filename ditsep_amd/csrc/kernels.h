@@ -7,6 +7,16 @@
 // dst[(b*T + t)*(C0+C1) + c] as fp32 (optional) and as operand planes (optional).
 void launch_pack_tokens(const float* src0, int C0, const float* src1, int C1, int B, int T,
                         float* dst_f32, op16_t* dst_planes, long ps, int planes, hipStream_t s);
+// the same with a window gather (the window-blended score call): item w of dst is window w of wtab [W][3] = (recording,
+// start, length; device) of sources [R][C][Tsrc], Tw rows per window, rows past a window's length written as zero
+void launch_win_pack_tokens(const float* src0, int C0, const float* src1, int C1, const int* wtab, int W, int Tw,
+                            int Tsrc, float* dst_f32, op16_t* dst_planes, long ps, int planes, hipStream_t s);
+// tw[w] = t[wtab[3 w]]: the recordings' times replicated to their windows
+void launch_win_times(const float* t, const int* wtab, int W, float* tw, hipStream_t s);
+// window tokens [W][Tw][C] -> out [rows][C] by the frame table ftab [rows][4] = (window0, offset0, window1, offset1),
+// fw [rows][2] = (fall, rise): zero (window0 < 0), a copy (window1 < 0) or fmaf(rise, s1, fall s0).  C % 4 == 0.
+void launch_win_blend_tokens(const float* src, const int* ftab, const float* fw, float* out, long rows, int C, int Tw,
+                             hipStream_t s);
 // rows of `width` floats (multiple of 4) into rows `dst_stride` floats apart
 void launch_copy_rows(const float* src, float* dst, int rows, int width, long dst_stride, hipStream_t s);
 // token-major fp32 [B*T][C] -> channel-major [B][C][T]

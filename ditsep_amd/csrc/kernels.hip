@@ -16,9 +16,12 @@ inline int grid_for(long n, int per_block = TPB, int cap = 256 * 16) {
 // `planes` everywhere in this file is the packed DSN_PL(plane count, fp16 flag); plane stores: dsn_store_planes1 / 4
 
 // ------------------------------------------------------------------ transforms
+// WIN (the window-blended score call): item b of the output is window b of `wtab` [B][3] = (recording, start, length),
+// cut from sources of Tsrc frames per recording; its rows t >= length are written as zero.  One store path for both.
+template <bool WIN>
 __global__ void pack_tokens_kernel(const float* __restrict__ s0, int C0, const float* __restrict__ s1, int C1,
                                    int B, int T, float* __restrict__ df, op16_t* __restrict__ dp, long ps,
-                                   int planes) {
+                                   int planes, const int* __restrict__ wtab, int Tsrc) {
   const int C = C0 + C1;
   const long n = (long)B * T * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -26,9 +29,48 @@ __global__ void pack_tokens_kernel(const float* __restrict__ s0, int C0, const f
     const long bt = i / C;
     const int t = (int)(bt % T);
     const int b = (int)(bt / T);
-    const float v = c < C0 ? s0[((long)b * C0 + c) * T + t] : s1[((long)b * C1 + (c - C0)) * T + t];
+    float v;
+    if (WIN) {
+      const int r = wtab[3 * b], ts = wtab[3 * b + 1] + t;
+      v = t >= wtab[3 * b + 2] ? 0.f
+          : c < C0             ? s0[((long)r * C0 + c) * Tsrc + ts]
+                               : s1[((long)r * C1 + (c - C0)) * Tsrc + ts];
+    } else {
+      v = c < C0 ? s0[((long)b * C0 + c) * T + t] : s1[((long)b * C1 + (c - C0)) * T + t];
+    }
     if (df) df[i] = v;
     if (dp) dsn_store_planes1(dp, ps, planes, i, v);
+  }
+}
+
+// tw[w] = t[recording of window w]: a score call's times, one per window
+__global__ void win_times_kernel(const float* __restrict__ t, const int* __restrict__ wtab, int W,
+                                 float* __restrict__ tw) {
+  for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += gridDim.x * blockDim.x) tw[w] = t[wtab[3 * w]];
+}
+
+// The window scores [W][Tw][C] back into one score per frame, out [rows][C] (rows = R Tmax), as a gather over the frame
+// table: ftab [rows][4] = (window0, offset0, window1, offset1), fw [rows][2] = (fall, rise).  window0 < 0: past the
+// recording's end, zero; window1 < 0: a copy, bit for bit; else fmaf(rise, s1, fall s0) in fp32.  16 bytes per lane
+// along the channels (C4 = C / 4).
+__global__ void win_blend_tokens_kernel(const float* __restrict__ src, const int* __restrict__ ftab,
+                                        const float* __restrict__ fw, float* __restrict__ out, long rows, int C4,
+                                        int Tw) {
+  const long n = rows * C4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long f = i / C4;
+    const int c = (int)(i - f * C4);
+    const int w0 = ftab[4 * f], w1 = ftab[4 * f + 2];
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (w0 >= 0) {
+      v = reinterpret_cast<const f32x4*>(src + ((long)w0 * Tw + ftab[4 * f + 1]) * (C4 * 4L))[c];
+      if (w1 >= 0) {
+        const f32x4 u = reinterpret_cast<const f32x4*>(src + ((long)w1 * Tw + ftab[4 * f + 3]) * (C4 * 4L))[c];
+        const float fall = fw[2 * f], rise = fw[2 * f + 1];
+        for (int j = 0; j < 4; ++j) v[j] = __fmaf_rn(rise, u[j], __fmul_rn(fall, v[j]));
+      }
+    }
+    reinterpret_cast<f32x4*>(out)[i] = v;
   }
 }
 
@@ -962,8 +1004,22 @@ __global__ void snake_params_kernel(const float* __restrict__ alpha, const float
 void launch_pack_tokens(const float* s0, int C0, const float* s1, int C1, int B, int T, float* df, op16_t* dp,
                         long ps, int planes, hipStream_t st) {
   const long n = (long)B * T * (C0 + C1);
-  hipLaunchKernelGGL(pack_tokens_kernel, dim3(grid_for(n)), dim3(TPB), 0, st, s0, C0, s1, C1, B, T, df, dp, ps,
-                     planes);
+  hipLaunchKernelGGL(pack_tokens_kernel<false>, dim3(grid_for(n)), dim3(TPB), 0, st, s0, C0, s1, C1, B, T, df, dp, ps,
+                     planes, (const int*)nullptr, 0);
+}
+void launch_win_pack_tokens(const float* s0, int C0, const float* s1, int C1, const int* wtab, int W, int Tw, int Tsrc,
+                            float* df, op16_t* dp, long ps, int planes, hipStream_t st) {
+  const long n = (long)W * Tw * (C0 + C1);
+  hipLaunchKernelGGL(pack_tokens_kernel<true>, dim3(grid_for(n)), dim3(TPB), 0, st, s0, C0, s1, C1, W, Tw, df, dp, ps,
+                     planes, wtab, Tsrc);
+}
+void launch_win_times(const float* t, const int* wtab, int W, float* tw, hipStream_t st) {
+  hipLaunchKernelGGL(win_times_kernel, dim3(grid_for(W)), dim3(TPB), 0, st, t, wtab, W, tw);
+}
+void launch_win_blend_tokens(const float* src, const int* ftab, const float* fw, float* out, long rows, int C, int Tw,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(win_blend_tokens_kernel, dim3(grid_for(rows * (C / 4))), dim3(TPB), 0, st, src, ftab, fw, out,
+                     rows, C / 4, Tw);
 }
 void launch_copy_rows(const float* src, float* dst, int rows, int width, long dst_stride, hipStream_t st) {
   hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for((long)rows * (width / 4))), dim3(TPB), 0, st, src, dst, rows,

@@ -342,17 +342,36 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      **sampler_kwargs):
+                      mode="stitch", **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
         keywords -> decode(..., window), exactly as `separate` does, so the model's own SDE and sampler are used; an
         explicit seed is offset by the minibatch index, vae_noise [Wtot, D, Tw] and noise [draws, Wtot, n, D, Tw] are
         sliced per minibatch.  Each recording is put back together by one Engine.window_stitch call (overlap default
-        window // 4).  The windows are sampled independently: the stitch orders and blends them only."""
+        window // 4).  The windows are sampled independently: the stitch orders and blends them only.
+        mode="score": Engine.separate_long(mode="score") with the model's SDE steps, t_eps and the configured sampler
+        keywords (N, snr, corrector_steps, denoise, eps) -- every recording one latent and one diffusion sample, the
+        score window-blended; vae_noise is then a list of [D, T_r] and noise [draws, R, n, D, Tmax]."""
         eng = self.engine
+        if mode not in native.LONG_MODES:
+            raise ValueError(f"mode must be one of {native.LONG_MODES} (got {mode!r})")
         if int(batch) < 1:
             raise ValueError(f"batch = {batch} < 1")
+        if mode == "score":
+            kwargs = dict(_get(self.config, "model.sampler", {}) or {})
+            kwargs.update(sampler_kwargs)
+            seed = kwargs.pop("seed", None)
+            call = dict(vae_noise=kwargs.pop("vae_noise", None), noise=kwargs.pop("noise", None), seed=self._seed(seed),
+                        N=int(kwargs.pop("N", None) or self.sde.N), snr=float(kwargs.pop("snr", 0.1)),
+                        corrector_steps=int(kwargs.pop("corrector_steps", 1)), denoise=bool(kwargs.pop("denoise", True)),
+                        t_eps=float(kwargs.pop("eps", self.t_eps)))
+            kwargs.pop("n_spkrs", None)
+            if kwargs:
+                raise NotImplementedError(f"mode='score' runs the OUVE predictor-corrector sampler (reverse_diffusion + "
+                                          f"ald); unsupported sampler keywords: {sorted(kwargs)}")
+            return eng.separate_long(mixes, window=window, overlap=overlap, fade=fade, batch=batch,
+                                     return_info=return_info, mode="score", **call)
         single = torch.is_tensor(mixes)
         pool, plans, overlap = native.cut_windows([mixes] if single else list(mixes), window, overlap, eng.device)
         kwargs = dict(sampler_kwargs)

@@ -35,6 +35,7 @@ EXPORTS = [
     "dsn_test_gemm", "dsn_test_kernel", "dsn_dit_plan", "dsn_bench_igemm", "dsn_debug_read", "dsn_si_sdr_pit", "dsn_si_bss_eval",
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
     "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged", "dsn_window_stitch",
+    "dsn_score_window_plan", "dsn_score_windowed", "dsn_pc_sample_windowed", "dsn_separate_windowed",
 ]
 
 
@@ -162,7 +163,7 @@ TEST_KERNEL_KINDS = {"attention": 1, "qkv_attention": 2, "residual_norm": 3, "gn
                      "packed_row_sum": 28, "fp8_row_sum": 29, "bias_plus_wbeta": 30, "snake_params": 31,
                      "pack_tokens": 32, "unpack_tokens": 33, "copy_rows": 34, "to_planes": 35, "zero_tail": 36,
                      "vae_sample_ragged": 37, "timestep_features": 38, "rope_tables": 39, "ncsn_pack": 40,
-                     "ncsn_fourier": 41, "ncsn_output": 42}
+                     "ncsn_fourier": 41, "ncsn_output": 42, "win_pack_tokens": 43, "win_blend_tokens": 44}
 # `mode` of the pack_weight kind (DSN_PACK_*); pack_weight_fp8 takes the first two
 PACK_MODES = {"linear": 0, "linear_swiglu": 1, "conv": 2, "convt": 3, "conv2d": 4, "nin": 5}
 
@@ -203,6 +204,7 @@ class DsnTestKernel(C.Structure):
         ("C0", C.c_int), ("C1", C.c_int), ("dst_stride", C.c_int64),
         ("Wp", C.c_int), ("Cp", C.c_int), ("cin", C.c_int), ("half", C.c_int),
         ("out2_f32", C.c_void_p),
+        ("wtab", C.c_void_p), ("ftab", C.c_void_p), ("fw", C.c_void_p), ("Tsrc", C.c_int), ("R", C.c_int),
     ]
 
 
@@ -356,6 +358,82 @@ def fade_rise64(overlap: int, fade: str = "hann"):
     return np.asarray([s * s for s in sn], dtype=np.float64)
 
 
+def score_window_plan(frames, Tw: int, To: int, fade: str = "hann", T: Optional[int] = None) -> dict:
+    """The plan of a window-blended score call (dsn_score_windowed; mirrored by csrc/score_window.h): `frames` holds one
+    latent frame count per recording, `Tw` is the window and `To` the overlap in frames, `T` (default max(frames)) the
+    padded length of the tensors.  A recording of F <= Tw frames is one window [0, F).  Otherwise hop = Tw - To and
+    W = 1 + ceil((F - Tw) / hop) (window_plan's W) full windows, window w starting at min(w hop, F - Tw): the last one is
+    shifted back into the recording, not zero-extended.  Seam j is the To frames [(j+1) hop, (j+1) hop + To), the last
+    To frames of window j; left of it a frame takes window j, right of it window j+1, inside it
+    fall[k] s_j + rise[k] s_{j+1} with fade_table(To, fade).  -> dict of
+      "W"       windows per recording;  "Wtot" their sum;  "Twin" the DiT call's length: Tw, or max(frames) when no
+                recording is longer than a window;  "T";  "short": some window is shorter than Twin
+      "windows" int32 [Wtot, 3] = (recording, start, length), the windows of all recordings in order
+      "table"   int32 [R T, 4] = (window0, offset0, window1, offset1): window1 = -1 outside seams, window0 = -1 past the
+                recording's end (the score there is written as zero)
+      "weights" float32 [R T, 2] = (fall, rise); (1, 0) outside seams
+    Refused in window_plan's words: Tw < 1, To < 0, 2 To > Tw, a frame count outside [1, T]."""
+    import numpy as np
+
+    fr = [int(f) for f in frames]
+    Tw, To = int(Tw), int(To)
+    T = max(fr) if T is None else int(T)
+    for r, F in enumerate(fr):
+        if F < 1 or F > T:
+            raise ValueError(f"frame count frames[{r}] = {F} outside [1, T = {T}]")
+        window_plan(F, Tw, To)                                             # (the refusals, by name)
+    fall, rise = fade_table(To, fade)
+    hop, R = Tw - To, len(fr)
+    windows, counts = [], []
+    table = np.zeros((R * T, 4), dtype=np.int32)
+    table[:, 0] = table[:, 2] = -1
+    weights = np.zeros((R * T, 2), dtype=np.float32)
+    weights[:, 0] = 1.0
+    for r, F in enumerate(fr):
+        base = len(windows)
+        W = window_plan(F, Tw, To)[0]
+        start = [0] if W == 1 else [min(w * hop, F - Tw) for w in range(W)]
+        windows += [(r, s, min(F, Tw)) for s in start]
+        counts.append(W)
+        for f in range(F):
+            w = 0 if W == 1 else min(f // hop, W - 1)
+            k = f - w * hop
+            if w >= 1 and k < To:
+                table[r * T + f] = (base + w - 1, f - start[w - 1], base + w, f - start[w])
+                weights[r * T + f] = (fall[k], rise[k])
+            else:
+                table[r * T + f, :2] = (base + w, f - start[w])
+    windows = np.asarray(windows, dtype=np.int32).reshape(-1, 3)
+    Twin = int(windows[:, 2].max())
+    return {"W": counts, "Wtot": len(windows), "Twin": Twin, "T": T, "short": bool((windows[:, 2] != Twin).any()),
+            "windows": windows, "table": table, "weights": weights}
+
+
+def check_windowed(score_kind: int, frames, R: int, T: int, window, corrector: str = "ald") -> tuple:
+    """The refusals of the window-blended entry points, raised by name before the library is touched: a score network
+    other than the DiT, score_window_plan's, and the langevin corrector when the lengths differ.  -> (frames, Tw, To)"""
+    if score_kind != SCORE_DIT:
+        raise ValueError("window-blended scores need the DiT score network: its windows are batch items of the trained "
+                         "length")
+    if frames is None:
+        raise ValueError("window= needs frames=, one latent frame count per recording")
+    fr = [int(f) for f in frames]
+    if len(fr) != R:
+        raise ValueError(f"frames must hold one frame count per recording (R = {R}), got {len(fr)}")
+    Tw, To = (int(v) for v in window)
+    for r, F in enumerate(fr):
+        if F < 1 or F > T:
+            raise ValueError(f"frame count frames[{r}] = {F} outside [1, T = {T}]")
+        window_plan(F, Tw, To)
+    if corrector == "langevin" and len(set(fr)) > 1:
+        raise ValueError("the langevin corrector has no form for recordings of different lengths: its per-item norms "
+                         "would run over the padding")
+    return fr, Tw, To
+
+
+LONG_MODES = ("stitch", "score")
+
+
 def cut_windows(mixes, window: int, overlap, device):
     """list of [1, L_r] recordings -> (pool [Wtot, 1, window] on `device`, plans [(W_r, hop, L_r)], overlap): every
     recording zero-extended to its plan's (W_r - 1) hop + window samples and unfolded into its W_r windows, the
@@ -446,6 +524,12 @@ def load_library() -> C.CDLL:
     lib.dsn_composite_ragged.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, C.POINTER(ci), fp,
                                          C.POINTER(DsnCompositeOut), vp]
     lib.dsn_window_stitch.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, i32p, C.POINTER(C.c_double), vp]
+    lib.dsn_score_window_plan.argtypes = [i32p, ci, ci, ci, ci, ci, i32p, i32p, fp, C.POINTER(ci), C.POINTER(ci)]
+    lib.dsn_score_windowed.argtypes = [vp, vp, vp, vp, i32p, vp, ci, ci, ci, ci, ci, ci, vp]
+    lib.dsn_pc_sample_windowed.argtypes = [vp, vp, i32p, vp, C.c_uint64, vp, ci, ci, ci, ci, ci, ci, ci,
+                                           C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
+    lib.dsn_separate_windowed.argtypes = [vp, vp, i32p, vp, vp, C.c_uint64, vp, ci, ci, ci, ci, ci, ci, ci,
+                                          C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -612,9 +696,24 @@ class Engine:
         self._check(self.lib.dsn_finalize_weights_ex(self.ctx, int(strict)), "dsn_finalize_weights")
 
     # ------------------------------------------------------------------ path
-    def score(self, xt, t, mix, frames=None):
+    def score(self, xt, t, mix, frames=None, window=None, batch=0, fade="hann"):
         """frames (sequence of B ints, optional): a ragged batch padded to T frames -- item b's score over its first
-        frames[b] frames is what it gets alone; the padded region of the output is unspecified (dsn_score_ragged)."""
+        frames[b] frames is what it gets alone; the padded region of the output is unspecified (dsn_score_ragged).
+        window = (Tw, To) in latent frames, with frames: the window-blended score of long latents (score_window_plan,
+        dsn_score_windowed) -- the DiT runs on overlapping windows of Tw frames, at most `batch` per call (0: all), and
+        the window scores are cross-faded (`fade`) back into one score per recording, zero past its end.  A definition,
+        not the score of any trained model."""
+        if window is not None:
+            fr, Tw, To = check_windowed(self.cfg.score_kind, frames, xt.shape[0], xt.shape[-1], window)
+            if fade not in FADES:
+                raise ValueError(f"fade must be one of {sorted(FADES)} (got {fade!r})")
+            xt, t, mix = (_dev32(a, self.device) for a in (xt, t, mix))
+            R, n, D, T = xt.shape
+            out = torch.empty_like(xt)
+            self._check(self.lib.dsn_score_windowed(self.ctx, _ptr(xt), _ptr(t), _ptr(mix), (C.c_int32 * R)(*fr),
+                                                    _ptr(out), R, T, Tw, To, FADES[fade], int(batch), self._stream()),
+                        "dsn_score_windowed")
+            return out
         if frames is not None:
             frames = check_ragged(self.cfg.score_kind, frames, xt.shape[0], xt.shape[-1])
         xt, t, mix = (_dev32(a, self.device) for a in (xt, t, mix))
@@ -639,14 +738,38 @@ class Engine:
 
     def pc_sample(self, y, noise=None, *, N=30, corrector_steps=1, snr=0.5, t_eps=0.03, denoise=True, seed=0,
                   timesteps=None, predictor="reverse_diffusion", corrector="ald", prior_mean=None,
-                  intermediate=False, frames=None):
+                  intermediate=False, frames=None, window=None, batch=0, fade="hann"):
         """timesteps: optional explicit schedule (>= N floats, host) -> the scheduled sampler.
         predictor / corrector: the reference's registered names (the ones with a native kernel).
         prior_mean: `true_mean` [B,n,D,T].  intermediate: also return the per-step (x, x_mean) list.
         frames (sequence of B ints, optional): a ragged batch -- y and noise keep their padded shapes, item b consumes
-        noise[..., :frames[b]] and gets what it gets alone; x[b, :, :, frames[b]:] is zero (dsn_pc_sample_ragged)."""
+        noise[..., :frames[b]] and gets what it gets alone; x[b, :, :, frames[b]:] is zero (dsn_pc_sample_ragged).
+        window = (Tw, To) in latent frames, with frames: the state is the whole latent of every recording and every
+        score evaluation is the window-blended one of `score` (dsn_pc_sample_windowed); nfe = N (corrector_steps + 1),
+        shared by all windows.  Not with timesteps, prior_mean or intermediate."""
         if predictor not in PREDICTORS or corrector not in CORRECTORS:
             raise NotImplementedError(f"no native kernel for predictor {predictor!r} / corrector {corrector!r}")
+        if window is not None:
+            if timesteps is not None or prior_mean is not None or intermediate:
+                raise NotImplementedError("window= does not take timesteps, prior_mean or intermediate")
+            if fade not in FADES:
+                raise ValueError(f"fade must be one of {sorted(FADES)} (got {fade!r})")
+            fr, Tw, To = check_windowed(self.cfg.score_kind, frames, y.shape[0], y.shape[-1], window, corrector)
+            y = _dev32(y, self.device)
+            R, _, D, T = y.shape
+            draws = 1 + N * (corrector_steps + (0 if predictor == "none" else 1))
+            if noise is not None:
+                noise = _dev32(noise, self.device)
+                if tuple(noise.shape) != (draws, R, self.n_src, D, T):
+                    raise ValueError(f"noise must be {(draws, R, self.n_src, D, T)}, got {tuple(noise.shape)}")
+            x = torch.empty((R, self.n_src, D, T), device=self.device, dtype=torch.float32)
+            nfe = C.c_int()
+            o = DsnSamplerOpts(PREDICTORS[predictor], CORRECTORS[corrector], int(corrector_steps), float(snr),
+                               float(t_eps), int(denoise), None, None, None)
+            self._check(self.lib.dsn_pc_sample_windowed(self.ctx, _ptr(y), (C.c_int32 * R)(*fr), _ptr(noise), seed,
+                                                        _ptr(x), R, T, N, Tw, To, FADES[fade], int(batch), C.byref(o),
+                                                        C.byref(nfe), self._stream()), "dsn_pc_sample_windowed")
+            return x, nfe.value
         if frames is not None:
             frames = check_ragged(self.cfg.score_kind, frames, y.shape[0], y.shape[-1], corrector)
         y = _dev32(y, self.device)
@@ -989,7 +1112,7 @@ class Engine:
 
     def separate_long(self, mixes, *, window, overlap=None, fade="hann", align=True, batch=64, vae_noise=None,
                       noise=None, seed=0, N=30, corrector_steps=1, snr=0.5, t_eps=0.03, denoise=True,
-                      return_info=False):
+                      return_info=False, mode="stitch"):
         """Long recordings as batched windows: `mixes` is one [1, L] tensor or a list of [1, L_r] tensors of any
         lengths -> (estimates [n, L] -- a list of [n, L_r] for a list --, the summed nfe).  Every recording is cut into
         windows of `window` samples sharing `overlap` (default window // 4) with their neighbour (window_plan; the last
@@ -1000,9 +1123,22 @@ class Engine:
         sliced per minibatch.  return_info=True: also a dict with, per recording, the lists "perms", "gram", "W" and
         "hop", and "chunks", the separated windows [Wtot, n, window].
         The windows are sampled independently: the stitch orders and blends them, it does not make the diffusion
-        samples of neighbouring windows agree."""
+        samples of neighbouring windows agree.
+        mode="score": every recording is ONE latent and one diffusion sample; only the score call is windowed
+        (dsn_separate_windowed: one padded encoder pass, the sampler with the window-blended score of `score`, one padded
+        decoder pass).  `window` and `overlap` are still in samples and must be multiples of the hop length; `batch`
+        caps the windows per DiT call; `align` does not apply (there is no permutation to repair).  vae_noise: list of
+        [D, T_r] (encode_ragged's), noise [draws, R, n, D, Tmax]; with the device RNG the encoder draws with `seed`, the
+        sampler with seed + 1.  nfe = N (corrector_steps + 1), shared by all windows.  return_info: {"W", "windows",
+        "frames", "Tw", "To"} of score_window_plan.  The blended score is a definition, not the score of any trained
+        model; its separation quality against the other routes is unmeasured."""
+        if mode not in LONG_MODES:
+            raise ValueError(f"mode must be one of {LONG_MODES} (got {mode!r})")
         if int(batch) < 1:
             raise ValueError(f"batch = {batch} < 1")
+        if mode == "score":
+            return self._separate_long_score(mixes, window, overlap, fade, batch, vae_noise, noise, seed, N,
+                                             corrector_steps, snr, t_eps, denoise, return_info)
         single = torch.is_tensor(mixes)
         pool, plans, overlap = cut_windows([mixes] if single else list(mixes), window, overlap, self.device)
         Wtot = pool.shape[0]
@@ -1018,6 +1154,46 @@ class Engine:
         outs, info = self._stitch_plans(sep, plans, overlap, fade, align, return_info)
         res = (outs[0] if single else outs, nfe)
         return (*res, info) if return_info else res
+
+    def _separate_long_score(self, mixes, window, overlap, fade, batch, vae_noise, noise, seed, N, corrector_steps, snr,
+                             t_eps, denoise, return_info):
+        hop = self.hop_length
+        window = int(window)
+        overlap = window // 4 if overlap is None else int(overlap)
+        if window % hop or overlap % hop:
+            raise ValueError(f"mode='score' windows the latent: window = {window} and overlap = {overlap} must be "
+                             f"multiples of the hop length {hop}")
+        if fade not in FADES:
+            raise ValueError(f"fade must be one of {sorted(FADES)} (got {fade!r})")
+        single = torch.is_tensor(mixes)
+        mixes = [mixes] if single else list(mixes)
+        for r, m in enumerate(mixes):
+            if m.dim() != 2 or m.shape[0] != 1:
+                raise ValueError(f"recording {r} must be [1, L] (got {tuple(m.shape)})")
+        R = len(mixes)
+        frames = [latent_frames_of(int(m.shape[-1]), hop) for m in mixes]
+        Tmax = max(frames)
+        fr, Tw, To = check_windowed(self.cfg.score_kind, frames, R, Tmax, (window // hop, overlap // hop))
+        if vae_noise is not None and torch.is_tensor(vae_noise):
+            vae_noise = [vae_noise[r, :, :frames[r]] for r in range(R)]
+        mix, vn, _, lens = self._padded_mixes(mixes, vae_noise)
+        nz = None if noise is None else _dev32(noise, self.device)
+        draws = 1 + N * (corrector_steps + 1)
+        if nz is not None and tuple(nz.shape) != (draws, R, self.n_src, self.latent_dim, Tmax):
+            raise ValueError(f"noise must be {(draws, R, self.n_src, self.latent_dim, Tmax)}, got {tuple(nz.shape)}")
+        wav = torch.empty((R, self.n_src, hop * Tmax), device=self.device, dtype=torch.float32)
+        o = DsnSamplerOpts(PREDICTORS["reverse_diffusion"], CORRECTORS["ald"], int(corrector_steps), float(snr),
+                           float(t_eps), int(denoise), None, None, None)
+        nfe = C.c_int()
+        self._check(self.lib.dsn_separate_windowed(self.ctx, _ptr(mix), (C.c_int32 * R)(*fr), _ptr(vn), _ptr(nz), seed,
+                                                   _ptr(wav), R, Tmax, N, Tw, To, FADES[fade], int(batch), C.byref(o),
+                                                   C.byref(nfe), self._stream()), "dsn_separate_windowed")
+        outs = [wav[r, :, :lens[r]] for r in range(R)]
+        res = (outs[0] if single else outs, nfe.value)
+        if not return_info:
+            return res
+        plan = score_window_plan(fr, Tw, To, fade)
+        return (*res, {"W": plan["W"], "windows": plan["windows"], "frames": fr, "Tw": Tw, "To": To})
 
     @property
     def hop_length(self) -> int:
@@ -1278,13 +1454,14 @@ class Engine:
     def test_kernel(self, kind, **kw):
         """Run one launch wrapper of the non-GEMM kernels (dsn_test_kernel, include/ditsep_hip.h) on caller-owned device
         tensors.  Every keyword is the DsnTestKernel field of the same name; tensors are passed by pointer (fp32, but
-        out_planes / in_planes int16 [P][out_ps / in_ps], out_fp8 / out_fp8_scale / in_fp8 / in_fp8_scale uint8 and lens
-        int32), `a` / `w` / `w2` also set their _numel field."""
+        out_planes / in_planes int16 [P][out_ps / in_ps], out_fp8 / out_fp8_scale / in_fp8 / in_fp8_scale uint8 and lens,
+        wtab and ftab int32), `a` / `w` / `w2` also set their _numel field."""
         t = DsnTestKernel()
         t.kind = TEST_KERNEL_KINDS[kind]
         keep = []
         dtypes = {"out_planes": torch.int16, "out_fp8": torch.uint8, "out_fp8_scale": torch.uint8, "lens": torch.int32,
-                  "in_planes": torch.int16, "in_fp8": torch.uint8, "in_fp8_scale": torch.uint8}
+                  "in_planes": torch.int16, "in_fp8": torch.uint8, "in_fp8_scale": torch.uint8, "wtab": torch.int32,
+                  "ftab": torch.int32}
         for k, v in kw.items():
             if isinstance(v, torch.Tensor):
                 assert v.is_cuda and v.dtype == dtypes.get(k, torch.float32), k

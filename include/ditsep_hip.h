@@ -192,6 +192,48 @@ int dsn_separate_ragged(dsn_ctx* ctx, const float* mix, const int32_t* frames, c
                         uint64_t seed, float* wav, int B, int T, int N, const dsn_sampler_opts* opts, int* nfe_out,
                         void* stream);
 
+/* Long recordings as ONE latent each, with a window-blended DiT score (the MultiDiffusion / DiffCollage construction
+ * applied to the score).  R recordings of frames[r] latent frames (HOST int32, 1 <= frames[r] <= T) in tensors padded
+ * to T frames.  The sampler state is the whole [R,n_src,D,T] latent -- one trajectory, one prior draw, one noise
+ * stream; only the score call is windowed:
+ *   plan    a recording of F <= Tw frames is one window [0, F).  Otherwise hop = Tw - To, W = 1 + ceil((F - Tw) / hop)
+ *           windows of Tw frames, window w starting at min(w hop, F - Tw): the last one is shifted back into the
+ *           recording, never zero-extended.  Seam j is the To frames [(j+1) hop, (j+1) hop + To), the last To frames of
+ *           window j; left of it a frame takes window j, right of it window j+1, inside it
+ *           fall[k] s_j + rise[k] s_{j+1} with the fade tables of dsn_window_stitch.  The plan is two tables, which
+ *           the device follows (the kernels know nothing about hops): wtab [Wtot][3] = (recording, start, length), the
+ *           windows of all recordings in order, and ftab [R T][4] = (window0, offset0, window1, offset1) with
+ *           fw [R T][2] = (fall, rise); window1 = -1 outside seams, window0 = -1 past a recording's end.
+ *   score   every evaluation gathers the windows from the long state straight into the DiT's operand planes
+ *           (call site of launch_win_pack_tokens), runs exactly the dense DiT call at (B = windows, T = Tw') at most
+ *           `batch` windows at a time (batch <= 0: all at once) -- Tw' = Tw, or the longest recording when none is
+ *           longer than a window; windows shorter than Tw' run the length-aware attention kernels, as a ragged batch
+ *           does -- and blends the window scores back into [R T][n_src D] in one gather launch
+ *           ("score.win_blend"): a copy outside seams, fmaf(rise, s1, fall * s0) inside, zero past a recording's end.
+ *           The blended score is a DEFINITION: it is not the score of any trained model.
+ *   dsn_score_windowed      xt [R,n_src,D,T], t [R], mix [R,1,D,T] -> out [R,n_src,D,T]
+ *   dsn_pc_sample_windowed  dsn_pc_sample_ex on the long state with that score: nfe = N (corrector_steps + 1), every
+ *                           evaluation shared by the whole pool.  x_out[r, :, :, frames[r]:] is zero.
+ *   dsn_separate_windowed   dsn_encode_ragged (seed) -> dsn_pc_sample_windowed (seed + 1) -> dsn_decode_ragged in one
+ *                           call: mix [R,1,hop*T] -> wav [R,n_src,hop*T], with their conventions.
+ * The tables are uploaded per call into fixed workspace buffers, outside any capture: under dsn_enable_graphs the
+ * sampler's graph key carries R, T, Wtot, Tw, To, batch and the short-window flag, not the table contents.
+ * DSN_EINVAL by name, before any launch: a score network other than the DiT; Tw < 1, To < 0, 2 To > Tw (a frame may lie
+ * in at most two windows); a frame count outside [1, T]; an unknown fade; n_src D not a multiple of 4; the langevin
+ * corrector when the frame counts differ; opts->prior_mean / intermediates / timesteps are not supported.
+ * dsn_score_window_plan is the plan alone (needs no context and no GPU): Wtot and Tw' always, the tables into any
+ * non-null HOST array ([Wtot][3], [R T][4], [R T][2]). */
+int dsn_score_window_plan(const int32_t* frames, int R, int T, int Tw, int To, int fade, int32_t* wtab, int32_t* ftab,
+                          float* fw, int* Wtot, int* Twin);
+int dsn_score_windowed(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
+                       int R, int T, int Tw, int To, int fade, int batch, void* stream);
+int dsn_pc_sample_windowed(dsn_ctx* ctx, const float* y, const int32_t* frames, const float* noise, uint64_t seed,
+                           float* x_out, int R, int T, int N, int Tw, int To, int fade, int batch,
+                           const dsn_sampler_opts* opts, int* nfe_out, void* stream);
+int dsn_separate_windowed(dsn_ctx* ctx, const float* mix, const int32_t* frames, const float* vae_noise,
+                          const float* noise, uint64_t seed, float* wav, int R, int T, int N, int Tw, int To, int fade,
+                          int batch, const dsn_sampler_opts* opts, int* nfe_out, void* stream);
+
 /* The secondary SDE family of the reference's sampler package on the latent state read as [B, n_src, D*T]:
  * MixSDE (sdes.py:182-352) / PriorMixSDE (:355-593; diffusion scaled by the running RMS of the mixture over `avg_len`
  * flattened latent samples) through the same predictor-corrector loop, predictors as above, corrector
@@ -540,7 +582,8 @@ enum { DSN_TK_ATTENTION = 1, DSN_TK_QKV_ATTENTION = 2, DSN_TK_RESIDUAL_NORM = 3,
        DSN_TK_PACKED_ROW_SUM = 28, DSN_TK_FP8_ROW_SUM = 29, DSN_TK_BIAS_PLUS_WBETA = 30, DSN_TK_SNAKE_PARAMS = 31,
        DSN_TK_PACK_TOKENS = 32, DSN_TK_UNPACK_TOKENS = 33, DSN_TK_COPY_ROWS = 34, DSN_TK_TO_PLANES = 35,
        DSN_TK_ZERO_TAIL = 36, DSN_TK_VAE_SAMPLE_RAGGED = 37, DSN_TK_TIMESTEP_FEATURES = 38, DSN_TK_ROPE_TABLES = 39,
-       DSN_TK_NCSN_PACK = 40, DSN_TK_NCSN_FOURIER = 41, DSN_TK_NCSN_OUTPUT = 42 };
+       DSN_TK_NCSN_PACK = 40, DSN_TK_NCSN_FOURIER = 41, DSN_TK_NCSN_OUTPUT = 42, DSN_TK_WIN_PACK_TOKENS = 43,
+       DSN_TK_WIN_BLEND_TOKENS = 44 };
 /* `mode` of DSN_TK_PACK_WEIGHT (the PACK_* index maps of ditsep_amd/csrc/kernels.h); DSN_TK_PACK_WEIGHT_FP8 takes the
  * first two */
 enum { DSN_PACK_LINEAR = 0, DSN_PACK_LINEAR_SWIGLU = 1, DSN_PACK_CONV = 2, DSN_PACK_CONVT = 3, DSN_PACK_CONV2D = 4,
@@ -656,6 +699,12 @@ typedef struct DsnTestKernel {
    *                    Wp >= T, Cp >= n + 1
    *   NCSN_FOURIER     x = t [B], w [half] -> out_planes [B][2 half] = sin | cos of 2 pi log(t) w
    *   NCSN_OUTPUT      x = pyr [B][H][Wp][Cp], y = t [B], w [n][cin], bias [n] -> out_f32 [B T][n H]; Wp >= T, Cp >= cin
+   *   WIN_PACK_TOKENS  PACK_TOKENS with the window gather: x = src0 [R][C0][Tsrc], y = src1 [R][C1][Tsrc], wtab (device
+   *                    int32 [B][3] = recording, start, length; checked here against R, Tsrc and T) -> out_f32
+   *                    and / or out_planes [B T][C0 + C1]; rows t >= length of a window are written as zero
+   *   WIN_BLEND_TOKENS x = window tokens [B][T][C], ftab (device int32 [rows][4] = window0, offset0, window1, offset1;
+   *                    checked here against B and T), fw (device fp32 [rows][2] = fall, rise) -> out_f32 [rows][C];
+   *                    C a multiple of 4
    * Refused by name before any launch: a missing tensor, a non-positive size, and each condition listed above. */
   int mode, N, K, Cin, Cout, kw, stride;
   const float* scale;
@@ -668,6 +717,10 @@ typedef struct DsnTestKernel {
   int64_t dst_stride;
   int Wp, Cp, cin, half;
   float* out2_f32;
+  const int32_t* wtab;        /* WIN_PACK_TOKENS */
+  const int32_t* ftab;        /* WIN_BLEND_TOKENS */
+  const float* fw;
+  int Tsrc, R;                /* WIN_PACK_TOKENS: the sources' frames per recording, and the recordings */
 } DsnTestKernel;
 int dsn_test_kernel(dsn_ctx* ctx, const DsnTestKernel* t, void* stream);
 
