@@ -23,6 +23,7 @@
 #include "dit_plan.h"
 #include "igemm.h"
 #include "kernels.h"
+#include "resample_plan.h"
 #include "score_window.h"
 
 namespace {
@@ -206,6 +207,17 @@ struct dsn_ctx {
     float* dev = nullptr;
     int O = -1, kind = -1;
   } stitch_fade;
+  // dsn_resample: the compact polyphase tables per (orig, new), uploaded once (taps [new][stride], stride = the
+  // support made odd; k0 [new]) and kept until the context goes; the item lengths last uploaded ("resample_lens")
+  struct ResampleTables {
+    ResamplePlan plan;
+    float* taps = nullptr;
+    int* k0 = nullptr;
+    int stride = 1, kmin = 0, kspan = 1;
+  };
+  std::map<std::pair<int, int>, ResampleTables> resample_tables;
+  std::vector<int> resample_lens_host;
+  const int* resample_lens_dev = nullptr;
 
   // DiT
   float* tf_w = nullptr;
@@ -3012,6 +3024,103 @@ int dsn_window_stitch(dsn_ctx* ctx, const float* chunks, int W, int n, int Lw, i
       HIPCHK(hipMemcpyAsync(gram_out, gram, sizeof(double) * (size_t)(nb * nn), hipMemcpyDeviceToHost, st));
     if (gram_out && !align) std::fill(gram_out, gram_out + nb * nn, 0.0);
     HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
+// ---- sinc resampling (resample_plan.h, resample.hip)
+int dsn_resample_plan(int fs_in, int fs_out, int* orig, int* new_, int* width, int* support, int32_t* k0, float* taps) {
+  char buf[128];
+  if (resample_refusal(fs_in, fs_out, buf, sizeof buf)) return DSN_EINVAL;
+  const ResamplePlan p = resample_plan(fs_in, fs_out);
+  if (orig) *orig = p.o;
+  if (new_) *new_ = p.n;
+  if (width) *width = p.width;
+  if (support) *support = p.S;
+  if (k0) std::copy(p.k0.begin(), p.k0.end(), k0);
+  if (taps) std::copy(p.c.begin(), p.c.end(), taps);
+  return DSN_OK;
+}
+
+int dsn_resample_length(int fs_in, int fs_out, int L) {
+  if (fs_in < 1 || fs_out < 1 || L < 0) return -1;
+  const int g = std::gcd(fs_in, fs_out);
+  return (int)resample_length(fs_in / g, fs_out / g, L);
+}
+
+// The tables of (orig, new) on the device.  Equal rates are the one-tap filter h = 1: a copy that honours lens and
+// downmix.  Refuses a plan that does not fit the kernel's LDS before anything is allocated.
+static const dsn_ctx::ResampleTables& resample_tables(dsn_ctx* ctx, const char* who, int fs_in, int fs_out) {
+  const int g = std::gcd(fs_in, fs_out);
+  const int o = fs_in / g, n = fs_out / g;
+  auto it = ctx->resample_tables.find({o, n});
+  if (it != ctx->resample_tables.end()) return it->second;
+  char buf[256];
+  // (a phase has at least 12 taps inside the window: a table that cannot fit is refused before it is computed)
+  if (const char* why = resample_lds_refusal(o, n, o == n ? 1 : 13, o == n ? 1 : 12, buf, sizeof buf))
+    fail(DSN_EINVAL, "%s: %s", who, why);
+  dsn_ctx::ResampleTables t;
+  if (o == n) {
+    t.plan.k0.assign(1, 0);
+    t.plan.c.assign(1, 1.f);
+    t.plan.S = 1;
+  } else {
+    t.plan = resample_plan(fs_in, fs_out);
+  }
+  const ResamplePlan& p = t.plan;
+  t.stride = p.S | 1;
+  t.kmin = *std::min_element(p.k0.begin(), p.k0.end());
+  t.kspan = *std::max_element(p.k0.begin(), p.k0.end()) + p.S - t.kmin;
+  if (const char* why = resample_lds_refusal(p.o, p.n, t.stride, t.kspan, buf, sizeof buf))
+    fail(DSN_EINVAL, "%s: %s", who, why);
+  std::vector<float> padded((size_t)p.n * t.stride, 0.f);
+  for (int ph = 0; ph < p.n; ++ph)
+    std::copy(p.c.begin() + (size_t)ph * p.S, p.c.begin() + (size_t)(ph + 1) * p.S, padded.begin() + (size_t)ph * t.stride);
+  t.taps = (float*)ctx->dmalloc(sizeof(float) * padded.size());
+  t.k0 = (int*)ctx->dmalloc(sizeof(int) * p.k0.size());
+  HIPCHK(hipMemcpy(t.taps, padded.data(), sizeof(float) * padded.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t.k0, p.k0.data(), sizeof(int) * p.k0.size(), hipMemcpyHostToDevice));
+  return ctx->resample_tables.emplace(std::make_pair(o, n), std::move(t)).first->second;
+}
+
+int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_t* lens, int fs_in, int fs_out,
+                 int downmix, float* out, int Lout, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_resample";
+    char buf[128];
+    if (!x || !out) fail(DSN_EINVAL, "%s: x or out is null", who);
+    if (const char* why = resample_refusal(fs_in, fs_out, buf, sizeof buf)) fail(DSN_EINVAL, "%s: %s", who, why);
+    if (B < 1) fail(DSN_EINVAL, "%s: B = %d < 1", who, B);
+    if (C < 1) fail(DSN_EINVAL, "%s: C = %d < 1", who, C);
+    if (L < 1) fail(DSN_EINVAL, "%s: L = %d < 1", who, L);
+    if ((long)B * C > 65535) fail(DSN_EINVAL, "%s: B * C = %ld > 65535 rows in one call", who, (long)B * C);
+    for (int b = 0; lens && b < B; ++b)
+      if (lens[b] < 1 || lens[b] > L)
+        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, L = %d]", who, b, (int)lens[b], L);
+    const int g = std::gcd(fs_in, fs_out);
+    const long need = resample_length(fs_in / g, fs_out / g, L);
+    if (need > INT32_MAX) fail(DSN_EINVAL, "%s: ceil(new * L / orig) = %ld does not fit 32 bits", who, need);
+    if (Lout < need) fail(DSN_EINVAL, "%s: Lout = %d < ceil(new * L / orig) = %ld", who, Lout, need);
+    const dsn_ctx::ResampleTables& t = resample_tables(ctx, who, fs_in, fs_out);
+    hipStream_t st = (hipStream_t)stream;
+    const int* dlens = nullptr;
+    if (lens) {
+      std::vector<int> h(lens, lens + B);
+      int* d = ctx->wsbuf<int>("resample_lens", B);
+      if (h != ctx->resample_lens_host || d != ctx->resample_lens_dev) {
+        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
+        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->resample_lens_host = h;
+        ctx->resample_lens_dev = d;
+      }
+      dlens = d;
+    }
+    const ResamplePlan& p = t.plan;
+    ctx->prof_launch("resample", 4.0 * ((double)B * C * L + (double)B * (downmix ? 1 : C) * Lout), st, [&] {
+      launch_resample(x, dlens, t.taps, t.k0, out, B, C, L, Lout, p.o, p.n, p.width, p.S, t.stride, t.kmin, t.kspan,
+                      downmix, st);
+    });
+    HIPCHK(hipGetLastError());
   });
 }
 

@@ -312,6 +312,18 @@ void launch_loss_reduce(const LossSde& q, const float* score_tok, const float* z
 void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, long DT,
                          int mean_reduction, hipStream_t s);
 
+// ---- sinc resampling (resample.hip) -------------------------------------------------------------------------
+// x [B][C][L] -> out [B][C or 1][Lout] by the compact polyphase table of resample_plan.h: taps [n][stride] (row p holds
+// c[p][0 .. S), stride >= S), k0 [n], both on the device; kmin = min k0, kspan = max k0 + S - kmin.  lens [B] (device,
+// or null: every item has L samples): item b's first ceil(n lens[b] / o) outputs are formed, the rest of its row is
+// written as zero, and nothing at or past lens[b] is read.  downmix: the C channels are averaged while the input is
+// staged and out has one channel.  resample_lds_refusal: nullptr, or why the plan does not fit the kernel's LDS.
+long resample_lds_words(int o, int n, int stride, int kspan);
+const char* resample_lds_refusal(int o, int n, int stride, int kspan, char* buf, size_t bufsz);
+void launch_resample(const float* x, const int* lens, const float* taps, const int* k0, float* out, int B, int C,
+                     int L, int Lout, int o, int n, int width, int S, int stride, int kmin, int kspan, int downmix,
+                     hipStream_t s);
+
 // ---- window stitch (stitch.hip) -----------------------------------------------------------------------------
 // chunks [W][n][Lw]: window w covers samples [w hop, w hop + Lw) of a recording, hop = Lw - O, 2 O <= Lw, n <= 4.
 #define DSN_STITCH_TILE 4096   // overlap positions one workgroup of the Gram launch sums

@@ -125,6 +125,8 @@ class LatentDiffSep:
         self.t_eps = float(_get(config, "model.t_eps", 0.03))
         self.t_max = self.sde.T
         self.n_src = n_src
+        fs = _get(config, "model.fs")                   # the key the reference's CLI reads (src/inference/separate.py:141)
+        self.fs = None if fs is None else int(fs)
         self.engine = native.Engine(**args)
         # the object `config.model.score_model._target_` names (reference diffsep_latent.py:39), bound to the engine
         from . import score_models
@@ -301,8 +303,61 @@ class LatentDiffSep:
 
         return batched_sampling_fn
 
+    # ------------------------------------------------------------------ audio at any sample rate
+    def _model_rate(self, what: str) -> int:
+        if self.fs is None:
+            raise ValueError(f"{what} needs the model's sample rate: config.model.fs is missing")
+        return self.fs
+
     @torch.no_grad()
-    def separate(self, mix, target_dim=None, latent=False, **kwargs):
+    def preprocess_audio_for_encoder(self, audio, in_sr):
+        """AudioAutoencoder.preprocess_audio_for_encoder (autoencoders.py:543-551): one clip -> [1, 1, Lpad]."""
+        return self.preprocess_audio_list_for_encoder([audio], [in_sr])
+
+    @torch.no_grad()
+    def preprocess_audio_list_for_encoder(self, audio_list, in_sr_list):
+        """AudioAutoencoder.preprocess_audio_list_for_encoder (autoencoders.py:553-594) for this mono model: a list of
+        clips of different lengths, channel counts ([L], [C, L] or [1, C, L]) and sample rates (`in_sr_list`: an int
+        or one rate per clip) -> [B, 1, Lpad] at `config.model.fs`, ready for `encode`.  Every clip is resampled on the
+        device (Engine.resample: torchaudio.transforms.Resample's default filter; one call per distinct input rate and
+        channel count, a mono clip already at the model's rate is copied), mixed down to mono, and zero-padded to
+        Lpad = max_len + (hop - max_len % hop) % hop -- that function's rule, not utils.pad's.  The reference
+        resamples every channel and then takes their mean; the mean is taken first here, which is the same sum."""
+        fs = self._model_rate("preprocess_audio_list_for_encoder")
+        if isinstance(in_sr_list, int):
+            in_sr_list = [in_sr_list] * len(audio_list)
+        if len(in_sr_list) != len(audio_list):
+            raise ValueError("list of sample rates must be the same length of audio_list")      # reference :566
+        rows = self.engine.to_model_rate(list(audio_list), list(in_sr_list), fs)
+        hop = self.hop_length
+        max_len = max(int(r.shape[-1]) for r in rows)
+        out = torch.zeros((len(rows), 1, max_len + (hop - max_len % hop) % hop), device=self.engine.device,
+                          dtype=torch.float32)
+        for b, r in enumerate(rows):
+            out[b, :, :r.shape[-1]] = r
+        return out
+
+    @torch.no_grad()
+    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs):
+        """`separate` of mix [B, C, L] (or [B, L]) at `sample_rate`: to the model's rate (mixed down), the existing
+        call, every estimate back to `sample_rate` and cropped to L."""
+        fs, eng = self._model_rate("sample_rate="), self.engine
+        mix = mix[:, None] if mix.dim() == 2 else mix
+        L = int(mix.shape[-1])
+        m = eng.resample(mix, sample_rate, fs, downmix=True)
+        est, *others = self.separate(m, target_dim, **kwargs)
+        return (eng.resample(est, fs, sample_rate)[..., :L], *others)
+
+    @torch.no_grad()
+    def separate(self, mix, target_dim=None, latent=False, sample_rate=None, **kwargs):
+        """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
+        call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
+        down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
+        `sample_rate`, cropped to L."""
+        if sample_rate is not None:
+            if latent:
+                raise ValueError("sample_rate= applies to waveforms: a latent has no sample rate to convert")
+            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs)
         if not latent:
             # the reference draws fresh VAE posterior noise on every call (bottleneck.py:57-83): without an explicit
             # seed, so does this (an explicit seed makes the whole call reproducible)
@@ -317,15 +372,26 @@ class LatentDiffSep:
         return (est, *others)
 
     @torch.no_grad()
-    def separate_batch(self, mixes, target_dims=None, codec="grouped", **sampler_kwargs):
+    def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
         batch padded to the longest item with the score network masking each item's keys at its own length.
         Keywords as `separate` (seed, vae_noise: list of [D, T_b], noise [draws,B,n,D,Tmax], N, snr, ...).
         codec="padded": encoder and decoder run once on the padded batch as well (Engine.encode_ragged /
-        decode_ragged); per item the same result up to summation order, other device-RNG VAE draws."""
+        decode_ragged); per item the same result up to summation order, other device-RNG VAE draws.
+        sample_rates (default None: every mixture is mono at the model's rate, the call is what it was): an int or one
+        rate per item; the mixtures may then be [L], [C, L] or [1, C, L].  They are resampled to config.model.fs on the
+        device (Engine.to_model_rate: mixed down, one call per distinct rate), separated as above -- target_dims,
+        vae_noise and noise keep their meaning at the model's rate -- and every estimate comes back at its item's own
+        rate, cropped to the item's sample count (Engine.from_model_rate)."""
         eng = self.engine
+        if sample_rates is not None:
+            fs = self._model_rate("sample_rates=")
+            rates = [int(sample_rates)] * len(mixes) if isinstance(sample_rates, int) else [int(r) for r in sample_rates]
+            at_fs = eng.to_model_rate(list(mixes), rates, fs)
+            est, *others = self.separate_batch(at_fs, target_dims, codec, **sampler_kwargs)
+            return (eng.from_model_rate(est, rates, fs, [int(m.shape[-1]) for m in mixes]), *others)
         native.check_codec_mode(codec)
         native.check_ragged(eng.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
         kwargs = dict(sampler_kwargs)
@@ -342,7 +408,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      mode="stitch", **sampler_kwargs):
+                      mode="stitch", sample_rates=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -352,8 +418,23 @@ class LatentDiffSep:
         window // 4).  The windows are sampled independently: the stitch orders and blends them only.
         mode="score": Engine.separate_long(mode="score") with the model's SDE steps, t_eps and the configured sampler
         keywords (N, snr, corrector_steps, denoise, eps) -- every recording one latent and one diffusion sample, the
-        score window-blended; vae_noise is then a list of [D, T_r] and noise [draws, R, n, D, Tmax]."""
+        score window-blended; vae_noise is then a list of [D, T_r] and noise [draws, R, n, D, Tmax].
+        sample_rates (default None: the recordings are mono at the model's rate, the call is what it was): an int or
+        one rate per recording, as in separate_batch -- the recordings are resampled to config.model.fs and mixed down,
+        `window` and `overlap` stay in samples at the model's rate, and every estimate comes back at its recording's
+        own rate and sample count."""
         eng = self.engine
+        if sample_rates is not None:
+            fs = self._model_rate("sample_rates=")
+            single = torch.is_tensor(mixes)
+            clips = [mixes] if single else list(mixes)
+            rates = [int(sample_rates)] * len(clips) if isinstance(sample_rates, int) else [int(r) for r in sample_rates]
+            at_fs = eng.to_model_rate(clips, rates, fs)
+            est, *others = self.separate_long(at_fs[0] if single else at_fs, window, overlap=overlap, fade=fade,
+                                              align=align, batch=batch, return_info=return_info, mode=mode,
+                                              **sampler_kwargs)
+            back = eng.from_model_rate([est] if single else est, rates, fs, [int(m.shape[-1]) for m in clips])
+            return (back[0] if single else back, *others)
         if mode not in native.LONG_MODES:
             raise ValueError(f"mode must be one of {native.LONG_MODES} (got {mode!r})")
         if int(batch) < 1:

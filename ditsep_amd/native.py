@@ -36,6 +36,7 @@ EXPORTS = [
     "dsn_stoi", "dsn_ode_sample", "dsn_score_loss", "dsn_composite", "dsn_mrstft_loss",
     "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged", "dsn_window_stitch",
     "dsn_score_window_plan", "dsn_score_windowed", "dsn_pc_sample_windowed", "dsn_separate_windowed",
+    "dsn_resample_plan", "dsn_resample_length", "dsn_resample",
 ]
 
 
@@ -453,6 +454,64 @@ def cut_windows(mixes, window: int, overlap, device):
     return torch.cat(rows, dim=0).unsqueeze(1).contiguous(), plans, overlap
 
 
+def check_rates(fs_in, fs_out) -> tuple:
+    """The sample rates of a resampling call as ints; refused by name: a rate that is not a positive integer."""
+    for name, fs in (("fs_in", fs_in), ("fs_out", fs_out)):
+        if int(fs) != fs or int(fs) < 1:
+            raise ValueError(f"sample rates must be positive integers ({name} = {fs!r})")
+    return int(fs_in), int(fs_out)
+
+
+def resample_length(fs_in: int, fs_out: int, L: int) -> int:
+    """Samples an L-sample row has after resampling (dsn_resample_length): ceil(new L / orig) with
+    orig = fs_in / gcd, new = fs_out / gcd, in integer arithmetic."""
+    fs_in, fs_out = check_rates(fs_in, fs_out)
+    if int(L) < 0:
+        raise ValueError(f"L = {L} < 0")
+    return int(load_library().dsn_resample_length(fs_in, fs_out, int(L)))
+
+
+def resample_plan(fs_in: int, fs_out: int) -> dict:
+    """The plan of a resampling call (dsn_resample_plan, csrc/resample_plan.h; needs no GPU): the default filter of
+    torchaudio.transforms.Resample(fs_in, fs_out) -- sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99 -- as a
+    polyphase table cut down to the taps that are not exactly 0.0 in float32.  -> dict of
+      "orig", "new"  the rates over their gcd;  "width" = ceil(6 orig / (0.99 min(orig, new)));  "K" = 2 width + orig, the
+                     taps per phase of the dense table
+      "support"      S: the longest run, over the phases, from the first to the last non-zero tap
+      "k0"           int32 [new]: the first non-zero tap of each phase
+      "taps"         float32 [new, S]: taps[p, j] = h[p, k0[p] + j], zero-filled on the right
+    out[m new + p] = sum_j taps[p, j] x[m orig + k0[p] + j - width] with x read as zero outside its samples."""
+    import numpy as np
+
+    fs_in, fs_out = check_rates(fs_in, fs_out)
+    lib = load_library()
+    o, n, w, S = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = lib.dsn_resample_plan(fs_in, fs_out, C.byref(o), C.byref(n), C.byref(w), C.byref(S), None, None)
+    if rc != 0:
+        raise ValueError(f"dsn_resample_plan({fs_in}, {fs_out}) refused ({rc})")
+    k0 = np.zeros(n.value, dtype=np.int32)
+    taps = np.zeros((n.value, S.value), dtype=np.float32)
+    lib.dsn_resample_plan(fs_in, fs_out, None, None, None, None, k0.ctypes.data_as(C.POINTER(C.c_int32)),
+                          taps.ctypes.data_as(C.POINTER(C.c_float)))
+    return {"orig": o.value, "new": n.value, "width": w.value, "K": 2 * w.value + o.value, "support": S.value,
+            "k0": k0, "taps": taps}
+
+
+def check_resample(fs_in, fs_out, shape, lens=None) -> tuple:
+    """The refusals of Engine.resample (dsn_resample's), raised by name before the library is touched: a non-positive
+    rate; x that is not [L], [C, L] or [B, C, L]; C < 1 or L < 1; lens that is not one count in [1, L] per item.
+    -> (fs_in, fs_out, (B, C, L), lens as a list or None)"""
+    fs_in, fs_out = check_rates(fs_in, fs_out)
+    if len(shape) not in (1, 2, 3):
+        raise ValueError(f"x must be [L], [C, L] or [B, C, L] (got {tuple(shape)})")
+    B, Cn, L = (1,) * (3 - len(shape)) + tuple(int(v) for v in shape)
+    if B < 1 or Cn < 1:
+        raise ValueError(f"x must hold at least one item and one channel (got {tuple(shape)}: C = {Cn} < 1 or B = {B} < 1)")
+    if L < 1:
+        raise ValueError(f"x must hold at least one sample (L = {L} < 1)")
+    return fs_in, fs_out, (B, Cn, L), (None if lens is None else check_lens(lens, B, L))
+
+
 _lib = None
 
 
@@ -530,6 +589,9 @@ def load_library() -> C.CDLL:
                                            C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
     lib.dsn_separate_windowed.argtypes = [vp, vp, i32p, vp, vp, C.c_uint64, vp, ci, ci, ci, ci, ci, ci, ci,
                                           C.POINTER(DsnSamplerOpts), C.POINTER(ci), vp]
+    lib.dsn_resample_plan.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), i32p, fp]
+    lib.dsn_resample_length.argtypes = [ci, ci, ci]
+    lib.dsn_resample.argtypes = [vp, vp, ci, ci, ci, i32p, ci, ci, ci, vp, ci, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -1194,6 +1256,85 @@ class Engine:
             return res
         plan = score_window_plan(fr, Tw, To, fade)
         return (*res, {"W": plan["W"], "windows": plan["windows"], "frames": fr, "Tw": Tw, "To": To})
+
+    # ------------------------------------------------------------------ any sample rate
+    def resample(self, x, fs_in: int, fs_out: int, lens=None, downmix: bool = False):
+        """Sinc resampling on the device (dsn_resample; the filter of resample_plan, torchaudio.transforms.Resample's
+        default): x [L], [C, L] or [B, C, L] at fs_in -> the same layout at fs_out with resample_length(L) samples.
+        downmix: the channels are averaged first (in fp32, before the filter) and one channel comes back.
+        lens (one sample count per item, shared by its channels): a ragged batch padded to L -- item b gets
+        resample_length(lens[b]) samples, the rest of its rows is zero, and x at or past lens[b] is never read (it may
+        hold NaN); the result is then (out, out_lens).  fs_in == fs_out is a copy.  Needs no score network and no
+        codec; two calls give identical bits."""
+        fs_in, fs_out, (B, Cn, L), ln = check_resample(fs_in, fs_out, tuple(x.shape), lens)
+        nd = x.dim()
+        x = _dev32(x, self.device).reshape(B, Cn, L)
+        Lout = resample_length(fs_in, fs_out, L)
+        Co = 1 if downmix else Cn
+        out = torch.empty((B, Co, Lout), device=self.device, dtype=torch.float32)
+        self._check(self.lib.dsn_resample(self.ctx, _ptr(x), B, Cn, L, None if ln is None else (C.c_int32 * B)(*ln),
+                                          fs_in, fs_out, int(bool(downmix)), _ptr(out), Lout, self._stream()),
+                    "dsn_resample")
+        out = out.reshape((Lout,) if nd == 1 else (Co, Lout) if nd == 2 else (B, Co, Lout))
+        return out if ln is None else (out, [resample_length(fs_in, fs_out, v) for v in ln])
+
+    def to_model_rate(self, clips, rates, fs: int):
+        """Clips of any rate, channel count and length at the model's rate `fs`, mixed down to mono: `clips` is a list
+        of [L], [C, L] or [1, C, L] tensors, `rates` an int or one rate per clip -> list of [1, L'_b] on the device.
+        Clips are grouped by input rate: one resample call per distinct (rate, channel count), its clips padded to the
+        group's longest; a mono clip already at `fs` is copied."""
+        rates = [int(rates)] * len(clips) if isinstance(rates, int) else [int(r) for r in rates]
+        if len(rates) != len(clips):
+            raise ValueError(f"one sample rate per clip is needed ({len(clips)} clips, {len(rates)} rates)")
+        norm = []
+        for i, a in enumerate(clips):
+            if a.dim() == 3 and a.shape[0] == 1:
+                a = a[0]
+            elif a.dim() == 1:
+                a = a[None]
+            if a.dim() != 2:
+                raise ValueError(f"clip {i} must be [L], [C, L] or [1, C, L] (got {tuple(a.shape)})")
+            check_resample(rates[i], fs, tuple(a.shape))
+            norm.append(a)
+        groups, out = {}, [None] * len(clips)
+        for i, a in enumerate(norm):
+            groups.setdefault((rates[i], int(a.shape[0])), []).append(i)
+        for (rate, Cn), idx in groups.items():
+            if rate == fs and Cn == 1:
+                for i in idx:
+                    out[i] = _dev32(norm[i], self.device).clone()
+                continue
+            ln = [int(norm[i].shape[-1]) for i in idx]
+            x = torch.zeros((len(idx), Cn, max(ln)), device=self.device, dtype=torch.float32)
+            for j, i in enumerate(idx):
+                x[j, :, :ln[j]] = _dev32(norm[i], self.device)
+            y, yl = self.resample(x, rate, fs, lens=ln, downmix=True)
+            for j, i in enumerate(idx):
+                out[i] = y[j, :, :yl[j]]
+        return out
+
+    def from_model_rate(self, ests, rates, fs: int, lengths):
+        """The way back: `ests` is a list of [n, L'_b] estimates at the model's rate `fs` -> list of [n, lengths[b]] at
+        rates[b], one resample call per distinct rate, each estimate cropped to its clip's original sample count (the
+        round trip never comes back shorter: ceil(orig ceil(new L / orig) / new) >= L).  An estimate whose rate is `fs`
+        is handed back as it is."""
+        groups, out = {}, [None] * len(ests)
+        for i, r in enumerate(rates):
+            groups.setdefault(int(r), []).append(i)
+        for rate, idx in groups.items():
+            if rate == fs:
+                for i in idx:
+                    out[i] = ests[i][:, :int(lengths[i])]
+                continue
+            ln = [int(ests[i].shape[-1]) for i in idx]
+            n = int(ests[idx[0]].shape[0])
+            x = torch.zeros((len(idx), n, max(ln)), device=self.device, dtype=torch.float32)
+            for j, i in enumerate(idx):
+                x[j, :, :ln[j]] = ests[i]
+            y, _ = self.resample(x, fs, rate, lens=ln)
+            for j, i in enumerate(idx):
+                out[i] = y[j, :, :int(lengths[i])]
+        return out
 
     @property
     def hop_length(self) -> int:

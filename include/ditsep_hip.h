@@ -454,6 +454,39 @@ enum { DSN_FADE_HANN = 0, DSN_FADE_LINEAR = 1 };
 int dsn_window_stitch(dsn_ctx* ctx, const float* chunks, int W, int n, int Lw, int overlap, int L, int fade, int align,
                       float* out, int32_t* perm_out, double* gram_out, void* stream);
 
+/* Sinc resampling on the device: audio at any sample rate to the model's rate and back.  The filter is the default of
+ * torchaudio.transforms.Resample (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), which the reference applies
+ * in AudioAutoencoder.preprocess_audio_list_for_encoder (autoencoders.py:553-594); restated in float64 in
+ * tests/resample_restatement.py.  With g = gcd(fs_in, fs_out), orig = fs_in / g, new = fs_out / g,
+ * base = min(orig, new) 0.99, width = ceil(6 orig / base), K = 2 width + orig, for phase p < new and tap k < K
+ *   t = clamp((-p / new + (k - width) / orig) base, -6, 6),  h[p][k] = float32(sinc(pi t) cos^2(pi t / 12) base / orig)
+ * (float64, rounded once), and a row of L samples gives ceil(new L / orig) samples
+ *   out[m new + p] = sum_k h[p][k] xz[m orig + k - width]        (xz: x extended by zeros on both sides).
+ * Content above 0.495 of the lower rate is removed.  In float32 all taps of a phase but one short run are exactly 0:
+ * the plan keeps, per phase, the first tap k0[p] that is not and `support` taps from there (the longest such run over
+ * the phases, zero-filled on the right).  A tap is dropped only when it equals 0.0f, so the compact sum is the dense sum.
+ *   dsn_resample_plan    the plan alone (no context, no GPU): orig, new, width, support always; k0 [new] and taps
+ *                        [new][support] into any non-null HOST array.  DSN_EINVAL for a non-positive rate.
+ *   dsn_resample_length  ceil(new L / orig); -1 for a non-positive rate or L < 0.
+ *   dsn_resample         x [B][C][L] fp32 (device) -> out [B][C or 1][Lout] fp32 (device) in one launch.  lens (HOST,
+ *                        [B], or NULL: every item has L samples) are the valid samples per item, shared by its channels:
+ *                        item b gets ceil(new lens[b] / orig) samples, the rest of its rows is written as zero, and
+ *                        nothing at or past lens[b] is read (the padding may hold NaN).  downmix != 0: the channels are
+ *                        averaged in fp32 before the filter, (x_0 + .. + x_{C-1}) / C in that order, and out has one
+ *                        channel.  Each output is one fp32 product and support - 1 fused multiply-adds in tap order; no
+ *                        atomics: two calls give identical bits.  fs_in == fs_out is a copy (with lens, zero past each
+ *                        item).  Needs no score network and no codec.  The tables are uploaded once per (orig, new) and
+ *                        kept by the context; the call synchronises the stream when it uploads tables or new lens, so
+ *                        it must not be captured into a graph.
+ * DSN_EINVAL by name, before anything is allocated or launched: x or out null; a non-positive rate; C < 1, L < 1, B < 1,
+ * B C > 65535; lens[b] outside [1, L]; Lout < ceil(new L / orig); a plan whose table, first taps and tile span do not fit
+ * the LDS budget the kernel declares (csrc/resample.hip).  All pairs between {8000, 16000} and {8000, 11025, 16000,
+ * 22050, 24000, 32000, 44100, 48000} fit (support <= 73, tables <= 32.5 KB). */
+int dsn_resample_plan(int fs_in, int fs_out, int* orig, int* new_, int* width, int* support, int32_t* k0, float* taps);
+int dsn_resample_length(int fs_in, int fs_out, int L);
+int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_t* lens, int fs_in, int fs_out,
+                 int downmix, float* out, int Lout, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
