@@ -18,7 +18,7 @@ def __getattr__(name):
         from .native import Engine
         return Engine
     if name in ("sdes", "synthetic", "distributed", "native", "latent", "score_models", "checkpoint", "evaluate",
-                "aweight"):
+                "aweight", "wavio", "files"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -3124,6 +3124,130 @@ int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_
   });
 }
 
+// ---- WAV payloads and the output gain (pcm.hip)
+// A host table on the device (workspace buffer `name`).  The stream is drained before the buffer is rewritten (an
+// earlier call may still read it) and after the copy (the host image is the caller's local).
+static const void* upload_table(dsn_ctx* ctx, const char* name, const void* h, size_t bytes, hipStream_t st) {
+  char* d = ctx->wsbuf<char>(name, bytes);
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return d;
+}
+
+int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const int64_t* offset, const int32_t* frames,
+                   const int32_t* channels, const int32_t* encoding, int downmix, float* out, int Cout, int Lmax,
+                   void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_pcm_decode";
+    if (!bytes || !out) fail(DSN_EINVAL, "%s: bytes or out is null", who);
+    if (!offset || !frames || !channels || !encoding)
+      fail(DSN_EINVAL, "%s: offset, frames, channels or encoding is null", who);
+    if (nbytes < 1) fail(DSN_EINVAL, "%s: nbytes = %ld < 1", who, (long)nbytes);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (Lmax < 1) fail(DSN_EINVAL, "%s: Lmax = %d < 1", who, Lmax);
+    if (Cout < 1) fail(DSN_EINVAL, "%s: Cout = %d < 1", who, Cout);
+    if (downmix && Cout != 1) fail(DSN_EINVAL, "%s: downmix gives one channel, Cout = %d", who, Cout);
+    std::vector<PcmItem> items((size_t)B);
+    int widest = 1;
+    for (int b = 0; b < B; ++b) {
+      const int w = pcm_sample_bytes(encoding[b]);
+      if (!w) fail(DSN_EINVAL, "%s: encoding[%d] = %d is none of DSN_PCM_U8 .. DSN_PCM_F64", who, b, (int)encoding[b]);
+      if (channels[b] < 1) fail(DSN_EINVAL, "%s: channels[%d] = %d < 1", who, b, (int)channels[b]);
+      if (!downmix && channels[b] > Cout)
+        fail(DSN_EINVAL, "%s: channels[%d] = %d > Cout = %d without downmix", who, b, (int)channels[b], Cout);
+      if ((long)channels[b] * w > DSN_PCM_MAX_FRAME_BYTES)
+        fail(DSN_EINVAL, "%s: item %d has frames of %ld bytes, more than DSN_PCM_MAX_FRAME_BYTES = %d", who, b,
+             (long)channels[b] * w, DSN_PCM_MAX_FRAME_BYTES);
+      if (frames[b] < 1 || frames[b] > Lmax)
+        fail(DSN_EINVAL, "%s: frames[%d] = %d outside [1, Lmax = %d]", who, b, (int)frames[b], Lmax);
+      const long fb = (long)channels[b] * w, need = fb * frames[b];
+      if (offset[b] < 0 || offset[b] > nbytes - need)
+        fail(DSN_EINVAL, "%s: item %d takes bytes [%ld, %ld), outside [0, nbytes = %ld)", who, b, (long)offset[b],
+             (long)offset[b] + need, (long)nbytes);
+      items[b] = PcmItem{(long)offset[b], frames[b], channels[b], encoding[b], 0};
+      widest = std::max(widest, (int)fb);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const PcmItem* d = (const PcmItem*)upload_table(ctx, "pcm_items", items.data(), sizeof(PcmItem) * items.size(), st);
+    ctx->prof_launch("pcm_decode", (double)nbytes + 4.0 * B * Cout * Lmax, st, [&] {
+      launch_pcm_decode((const unsigned char*)bytes, (long)nbytes, d, B, downmix, out, Cout, Lmax, widest, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dsn_pcm_encode(dsn_ctx* ctx, const float* x, int R, int Lmax, const int32_t* lens, int encoding, void* bytes,
+                   int64_t nbytes, const int64_t* offset, int64_t* clipped, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_pcm_encode";
+    if (!x || !bytes) fail(DSN_EINVAL, "%s: x or bytes is null", who);
+    if (!lens || !offset) fail(DSN_EINVAL, "%s: lens or offset is null", who);
+    if (R < 1 || R > 65535) fail(DSN_EINVAL, "%s: R = %d outside [1, 65535]", who, R);
+    if (Lmax < 1) fail(DSN_EINVAL, "%s: Lmax = %d < 1", who, Lmax);
+    if (encoding != DSN_PCM_S16 && encoding != DSN_PCM_S24 && encoding != DSN_PCM_F32)
+      fail(DSN_EINVAL, "%s: encoding = %d is none of DSN_PCM_S16, DSN_PCM_S24, DSN_PCM_F32", who, encoding);
+    const int w = pcm_sample_bytes(encoding);
+    std::vector<PcmItem> items((size_t)R);
+    std::vector<std::pair<long, int>> order((size_t)R);
+    for (int r = 0; r < R; ++r) {
+      if (lens[r] < 1 || lens[r] > Lmax)
+        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, r, (int)lens[r], Lmax);
+      const long need = (long)lens[r] * w;
+      if (offset[r] < 0 || nbytes < need || offset[r] > nbytes - need)
+        fail(DSN_EINVAL, "%s: row %d takes bytes [%ld, %ld), outside [0, nbytes = %ld)", who, r, (long)offset[r],
+             (long)offset[r] + need, (long)nbytes);
+      items[r] = PcmItem{(long)offset[r], lens[r], 1, encoding, 0};
+      order[r] = {(long)offset[r], r};
+    }
+    std::sort(order.begin(), order.end());
+    for (int k = 1; k < R; ++k) {
+      const int p = order[k - 1].second, q = order[k].second;
+      if (order[k - 1].first + (long)lens[p] * w > order[k].first)
+        fail(DSN_EINVAL, "%s: the payloads of rows %d and %d overlap", who, p, q);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const PcmItem* d = (const PcmItem*)upload_table(ctx, "pcm_rows", items.data(), sizeof(PcmItem) * items.size(), st);
+    unsigned long long* cnt = ctx->wsbuf<unsigned long long>("pcm_clipped", R);
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)R, st));
+    ctx->prof_launch("pcm_encode", 4.0 * R * Lmax + (double)w * R * Lmax, st, [&] {
+      launch_pcm_encode(x, d, R, Lmax, encoding, (unsigned char*)bytes, cnt, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!clipped) return;
+    HIPCHK(hipMemcpyAsync(clipped, cnt, sizeof(int64_t) * (size_t)R, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
+int dsn_scale_output(dsn_ctx* ctx, const float* mix, const float* sep, int B, int n, int Lmax, const int32_t* lens,
+                     float* out, float* alpha_out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_scale_output";
+    if (!mix || !sep || !out) fail(DSN_EINVAL, "%s: mix, sep or out is null", who);
+    if (B < 1) fail(DSN_EINVAL, "%s: B = %d < 1", who, B);
+    if (n < 1) fail(DSN_EINVAL, "%s: n = %d < 1", who, n);
+    if ((long)B * n > 65535) fail(DSN_EINVAL, "%s: B * n = %ld > 65535 rows in one call", who, (long)B * n);
+    if (Lmax < 1) fail(DSN_EINVAL, "%s: Lmax = %d < 1", who, Lmax);
+    for (int b = 0; lens && b < B; ++b)
+      if (lens[b] < 1 || lens[b] > Lmax)
+        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, b, (int)lens[b], Lmax);
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)B * n;
+    double* part = ctx->wsbuf<double>("scale_part", (size_t)(rows * scale_output_tiles(Lmax) * 2));
+    float* alpha = ctx->wsbuf<float>("scale_alpha", (size_t)rows);
+    const int* dlens = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "scale_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    ctx->prof_launch("scale_output", 4.0 * (3.0 * rows + B) * Lmax, st, [&] {
+      launch_scale_output(mix, sep, dlens, B, n, Lmax, part, alpha, out, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!alpha_out) return;
+    HIPCHK(hipMemcpyAsync(alpha_out, alpha, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
 static double bessel_i0(double x) {
   double s = 1.0, t = 1.0;

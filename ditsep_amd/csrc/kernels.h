@@ -324,6 +324,31 @@ void launch_resample(const float* x, const int* lens, const float* taps, const i
                      int L, int Lout, int o, int n, int width, int S, int stride, int kmin, int kspan, int downmix,
                      hipStream_t s);
 
+// ---- WAV payloads and the output gain (pcm.hip) -------------------------------------------------------------
+struct PcmItem {      // one item of a decode call, or one row of an encode call
+  long offset;        // its first byte in the byte buffer
+  int frames;         // frames (decode) or samples (encode)
+  int channels, enc;  // (decode only) DSN_PCM_*
+  int pad;
+};
+// bytes per sample of DSN_PCM_U8 .. DSN_PCM_F64; 0 for anything else
+__host__ __device__ inline int pcm_sample_bytes(int enc) {
+  return enc == 0 ? 1 : enc == 1 ? 2 : enc == 2 ? 3 : enc == 3 || enc == 4 ? 4 : enc == 5 ? 8 : 0;   // (by code 0 .. 5)
+}
+long scale_output_tiles(int L);   // tiles the gain's sum launch cuts a row of L samples into
+// bytes [nbytes] -> out [B][Cout][Lmax] by items [B] (device); max_frame_bytes: the widest frame among them (LDS)
+void launch_pcm_decode(const unsigned char* bytes, long nbytes, const PcmItem* items, int B, int downmix, float* out,
+                       int Cout, int Lmax, int max_frame_bytes, hipStream_t s);
+// x [R][Lmax] -> row r's items[r].frames samples as `enc` from bytes + items[r].offset; clipped [R] (device, zeroed
+// by the caller) is added to with integer atomics
+void launch_pcm_encode(const float* x, const PcmItem* items, int R, int Lmax, int enc, unsigned char* bytes,
+                       unsigned long long* clipped, hipStream_t s);
+// part [B n][tiles][2] = the fp64 sums over tile c of mix sep and sep^2 + 1e-10 (t < lens[b]; tiles past it untouched);
+// alpha [B n] = float(sum_c part[.][c][0] / sum_c part[.][c][1]) over the row's own ceil(lens[b] / tile) tiles;
+// out = alpha sep for t < lens[b], zero past it.  lens [B] (device, or null: Lmax each)
+void launch_scale_output(const float* mix, const float* sep, const int* lens, int B, int n, int Lmax, double* part,
+                         float* alpha, float* out, hipStream_t s);
+
 // ---- window stitch (stitch.hip) -----------------------------------------------------------------------------
 // chunks [W][n][Lw]: window w covers samples [w hop, w hop + Lw) of a recording, hop = Lw - O, 2 O <= Lw, n <= 4.
 #define DSN_STITCH_TILE 4096   // overlap positions one workgroup of the Gram launch sums

@@ -1,0 +1,140 @@
+"""WAV files in, one WAV per speaker out: the file layer over LatentDiffSep.separate_batch / separate_long.
+
+The host parses headers and moves raw bytes (wavio); every sample conversion runs on the device (Engine.pcm_decode /
+pcm_encode), so a batch costs one host-to-device copy of the payloads as the files hold them and one device-to-host
+copy of the payloads as they are written."""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+from . import native, wavio
+
+
+def plan_files(headers, fs: int, hop: int, batch: int = 64, long_after: Optional[float] = None) -> dict:
+    """How a set of files goes through the engine (pure: no GPU, no file is opened).  `headers` is one
+    wavio.WavHeader per file, `fs` the model's rate, `hop` its hop length ->
+      "lengths"  every file's sample count at the model's rate (native.resample_length of its frame count)
+      "frames"   .. and its latent frames
+      "batches"  index lists of at most `batch` files of similar length (evaluate.length_batches on "lengths":
+                 sorted by length, ties by index), over the files that are not set aside
+      "long"     the files longer than `long_after` seconds (default None: none), in input order
+    Every file appears exactly once, in one batch or in "long"."""
+    from .evaluate import length_batches
+
+    if int(batch) < 1:
+        raise ValueError(f"batch = {batch} < 1")
+    if long_after is not None and not float(long_after) > 0:
+        raise ValueError(f"long_after = {long_after!r} must be a positive number of seconds")
+    lengths = [native.resample_length(h.rate, fs, h.frames) for h in headers]
+    long = [i for i, h in enumerate(headers) if long_after is not None and h.frames > float(long_after) * h.rate]
+    short = [i for i in range(len(headers)) if i not in set(long)]
+    batches = [[short[j] for j in b] for b in length_batches([lengths[i] for i in short], int(batch))]
+    return {"lengths": lengths, "frames": [native.latent_frames_of(v, hop) for v in lengths], "batches": batches,
+            "long": long}
+
+
+def parse_inputs(paths) -> list:
+    """Every header, before any device work: a file wavio refuses raises its ValueError, and so do two inputs with the
+    same stem (they would be written to the same output files)."""
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("no input files")
+    stems = {}
+    for p in paths:
+        stem = os.path.splitext(os.path.basename(p))[0]
+        if stem in stems:
+            raise ValueError(f"{p} and {stems[stem]} have the same stem {stem!r}: their outputs would collide")
+        stems[stem] = p
+    return [wavio.read_header(p) for p in paths]
+
+
+def load_batch(engine, paths, headers):
+    """The payloads of `paths` back to back in one pinned buffer, one host-to-device copy, one decode launch ->
+    (list of mono [1, frames_b] clips at each file's own rate, on the device)"""
+    import torch
+
+    offsets, total = [], 0
+    for h in headers:
+        offsets.append(total)
+        total += h.data_bytes
+    raw = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    view = raw.numpy()
+    for p, h, o in zip(paths, headers, offsets):
+        wavio.read_payload(p, h, out=view[o:o + h.data_bytes])
+    items = [(o, h.frames, h.channels, h.encoding) for o, h in zip(offsets, headers)]
+    x, frames = engine.pcm_decode(raw, items, downmix=True)
+    return [x[b, :, :frames[b]] for b in range(len(headers))]
+
+
+def _padded(rows, device):
+    import torch
+
+    lens = [int(r.shape[-1]) for r in rows]
+    out = torch.zeros((len(rows), int(rows[0].shape[0]), max(lens)), device=device, dtype=torch.float32)
+    for b, r in enumerate(rows):
+        out[b, :, :lens[b]] = r
+    return out, lens
+
+
+def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
+                   window=None, overlap=None, long_mode="stitch", seed=None, **sampler_kwargs) -> list:
+    """LatentDiffSep.separate_files (see there)."""
+    eng = model.engine
+    fs = model._model_rate("separate_files")
+    if encoding not in native.PCM_OUT_ENCODINGS:
+        raise ValueError(f"encoding must be one of {native.PCM_OUT_ENCODINGS} (got {encoding!r})")
+    native.check_codec_mode(codec)
+    if long_mode not in native.LONG_MODES:
+        raise ValueError(f"long_mode must be one of {native.LONG_MODES} (got {long_mode!r})")
+    paths = [os.fspath(p) for p in paths]
+    headers = parse_inputs(paths)
+    hop = model.hop_length
+    plan = plan_files(headers, fs, hop, batch, long_after)
+    if plan["long"] and window is None:
+        window = max(4 * hop, int(float(long_after) * fs) // (4 * hop) * (4 * hop))
+    out_dir = os.fspath(out_dir)
+    n = model.n_src
+    records = [None] * len(paths)
+
+    def finish(idx, at_fs, est, label):
+        """estimates at the model's rate -> files; `at_fs` the mono mixtures there"""
+        alpha = None
+        if rescale:
+            sep, lens = _padded(est, eng.device)
+            mix, _ = _padded(at_fs, eng.device)
+            scaled, alpha = eng.scale_output(mix, sep, lens)
+            est = [scaled[j, :, :lens[j]] for j in range(len(idx))]
+        hs = [headers[i] for i in idx]
+        back = eng.from_model_rate(est, [h.rate for h in hs], fs, [h.frames for h in hs])
+        rows, lens = _padded(back, eng.device)
+        payloads, clipped = eng.pcm_encode(rows.reshape(len(idx) * n, -1), [v for v in lens for _ in range(n)],
+                                           encoding)
+        for j, i in enumerate(idx):
+            stem = os.path.splitext(os.path.basename(paths[i]))[0]
+            outs = []
+            for s in range(n):
+                d = os.path.join(out_dir, f"s{s}")
+                os.makedirs(d, exist_ok=True)
+                outs.append(os.path.join(d, stem + ".wav"))
+                wavio.write_wav(outs[-1], payloads[j * n + s], hs[j].rate, 1, encoding)
+            rec = {"path": paths[i], "rate": hs[j].rate, "channels": hs[j].channels, "frames": hs[j].frames,
+                   "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label}
+            if alpha is not None:
+                rec["alpha"] = [float(a) for a in alpha[j]]
+            records[i] = rec
+
+    for k, idx in enumerate(plan["batches"]):
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx])
+        at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
+        kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed) + k)
+        est, *_ = model.separate_batch(at_fs, codec=codec, **kw)
+        finish(idx, at_fs, est, k)
+    if plan["long"]:
+        idx = plan["long"]
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx])
+        at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
+        kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed))
+        est, *_ = model.separate_long(at_fs, window, overlap=overlap, mode=long_mode, batch=batch, **kw)
+        finish(idx, at_fs, est, "long")
+    return records

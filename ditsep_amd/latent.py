@@ -475,6 +475,31 @@ class LatentDiffSep:
         res = (outs[0] if single else outs, nfe)
         return (*res, info) if return_info else res
 
+    @torch.no_grad()
+    def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
+                       long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, **sampler_kwargs):
+        """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
+        count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
+        resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
+        inputs with the same stem, raises ValueError before any device work.  The files are cut into batches of
+        similar length at the model's rate (files.plan_files); per batch the payloads are read into one pinned buffer
+        and copied once, decoded and mixed down on the device (Engine.pcm_decode), taken to config.model.fs
+        (Engine.to_model_rate), separated by `separate_batch(codec=codec)` -- batch k with seed + k when a seed is
+        given --, optionally scaled by the reference's output gain against the mono mixture at the model's rate
+        (rescale: Engine.scale_output), taken back to each file's rate and frame count (Engine.from_model_rate),
+        quantised on the device (Engine.pcm_encode: "s16", "s24" or "f32"; no dither), copied back once and written.
+        long_after (seconds; default None: nothing is set aside): longer files go together through
+        `separate_long(window, overlap=overlap, mode=long_mode, batch=batch, seed=seed)` -- window and overlap in
+        samples at the model's rate, window defaulting to long_after seconds rounded down to a multiple of 4 hops --
+        and the same way out.  -> one dict per input, in input order: "path", "rate", "channels", "frames", "outputs"
+        (the files written), "clipped" (per speaker, the samples that were clamped), "alpha" (per speaker, with
+        rescale), "batch" (the batch index, or "long").  DiT score network only (separate_batch's restriction)."""
+        from . import files
+
+        return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
+                                    long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
+                                    seed=seed, **sampler_kwargs)
+
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod
     def _seed(seed):

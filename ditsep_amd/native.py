@@ -37,6 +37,7 @@ EXPORTS = [
     "dsn_si_bss_eval_ragged", "dsn_stoi_ragged", "dsn_composite_ragged", "dsn_window_stitch",
     "dsn_score_window_plan", "dsn_score_windowed", "dsn_pc_sample_windowed", "dsn_separate_windowed",
     "dsn_resample_plan", "dsn_resample_length", "dsn_resample",
+    "dsn_pcm_decode", "dsn_pcm_encode", "dsn_scale_output",
 ]
 
 
@@ -512,6 +513,37 @@ def check_resample(fs_in, fs_out, shape, lens=None) -> tuple:
     return fs_in, fs_out, (B, Cn, L), (None if lens is None else check_lens(lens, B, L))
 
 
+PCM_ENCODINGS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5}        # DSN_PCM_*
+PCM_SAMPLE_BYTES = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8}
+PCM_OUT_ENCODINGS = ("s16", "s24", "f32")                                          # what dsn_pcm_encode writes
+PCM_MAX_FRAME_BYTES = 48                                                           # DSN_PCM_MAX_FRAME_BYTES
+
+
+def check_pcm_items(items, nbytes: int, downmix: bool = True) -> tuple:
+    """The refusals of Engine.pcm_decode (dsn_pcm_decode's), raised by name before the library is touched.  `items` is
+    one (offset, frames, channels, encoding) per payload, encoding a key of PCM_ENCODINGS: an unknown encoding;
+    frames < 1 or channels < 1; a frame wider than PCM_MAX_FRAME_BYTES; a payload that leaves [0, nbytes).
+    -> (offsets, frames, channels, codes, Cout, Lmax)"""
+    items = [tuple(it) for it in items]
+    if not items:
+        raise ValueError("pcm_decode needs at least one item")
+    offs, frames, chans, codes = [], [], [], []
+    for b, (off, fr, ch, enc) in enumerate(items):
+        if enc not in PCM_ENCODINGS:
+            raise ValueError(f"item {b}: encoding must be one of {sorted(PCM_ENCODINGS)} (got {enc!r})")
+        off, fr, ch = int(off), int(fr), int(ch)
+        if fr < 1 or ch < 1:
+            raise ValueError(f"item {b}: frames = {fr} and channels = {ch} must be at least 1")
+        fb = ch * PCM_SAMPLE_BYTES[enc]
+        if fb > PCM_MAX_FRAME_BYTES:
+            raise ValueError(f"item {b}: frames of {fb} bytes ({ch} x {enc}) exceed PCM_MAX_FRAME_BYTES = "
+                             f"{PCM_MAX_FRAME_BYTES}")
+        if off < 0 or off + fb * fr > int(nbytes):
+            raise ValueError(f"item {b} takes bytes [{off}, {off + fb * fr}), outside [0, {int(nbytes)})")
+        offs.append(off), frames.append(fr), chans.append(ch), codes.append(PCM_ENCODINGS[enc])
+    return offs, frames, chans, codes, (1 if downmix else max(chans)), max(frames)
+
+
 _lib = None
 
 
@@ -592,6 +624,10 @@ def load_library() -> C.CDLL:
     lib.dsn_resample_plan.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), i32p, fp]
     lib.dsn_resample_length.argtypes = [ci, ci, ci]
     lib.dsn_resample.argtypes = [vp, vp, ci, ci, ci, i32p, ci, ci, ci, vp, ci, vp]
+    i64p = C.POINTER(C.c_int64)
+    lib.dsn_pcm_decode.argtypes = [vp, vp, C.c_int64, ci, i64p, i32p, i32p, i32p, ci, vp, ci, ci, vp]
+    lib.dsn_pcm_encode.argtypes = [vp, vp, ci, ci, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
+    lib.dsn_scale_output.argtypes = [vp, vp, vp, ci, ci, ci, i32p, vp, fp, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -1335,6 +1371,93 @@ class Engine:
             for j, i in enumerate(idx):
                 out[i] = y[j, :, :int(lengths[i])]
         return out
+
+    # ------------------------------------------------------------------ WAV payloads and the output gain
+    def pcm_decode(self, raw, items, downmix: bool = True):
+        """The `data` payloads of WAV files to float32 on the device (dsn_pcm_decode, one launch for the whole mixed
+        batch): `raw` is the payloads back to back -- a uint8 tensor (host, pinned or not, or device) or a bytes-like
+        object; it goes to the device in one copy --, `items` one (offset, frames, channels, encoding) per payload with
+        encoding one of PCM_ENCODINGS.  -> (x [B, Cout, Lmax] float32, zero past each item's end, and the frame counts).
+        The conversions are torchaudio.load(normalize=True)'s, defined to the bit (include/ditsep_hip.h).  downmix:
+        Cout = 1 and a frame is (x_0 + .. + x_{C-1}) / C in that order; else Cout is the largest channel count and an
+        item's unused channels are zero.  Needs no score network and no codec."""
+        if not torch.is_tensor(raw):
+            raw = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+        if raw.dtype != torch.uint8 or raw.dim() != 1:
+            raise ValueError(f"raw must be a 1-D uint8 tensor or bytes (got {raw.dtype}, {tuple(raw.shape)})")
+        offs, frames, chans, codes, Cout, Lmax = check_pcm_items(items, raw.numel(), downmix)
+        raw = raw.to(self.device, non_blocking=True).contiguous()
+        B = len(offs)
+        out = torch.empty((B, Cout, Lmax), device=self.device, dtype=torch.float32)
+        i32 = C.c_int32 * B
+        self._check(self.lib.dsn_pcm_decode(self.ctx, _ptr(raw), raw.numel(), B, (C.c_int64 * B)(*offs), i32(*frames),
+                                            i32(*chans), i32(*codes), int(bool(downmix)), _ptr(out), Cout, Lmax,
+                                            self._stream()), "dsn_pcm_decode")
+        return out, frames
+
+    def pcm_encode(self, x, lens=None, encoding: str = "s16", offsets=None, out=None):
+        """Float32 rows to mono WAV payloads on the device (dsn_pcm_encode): x [R, Lmax] (or [Lmax]), one row per
+        (file, speaker) with lens[r] samples (default: Lmax each), encoding one of PCM_OUT_ENCODINGS -> (one `bytes` per
+        row, the clipped counts).  s16 / s24: rint(x 2^(b-1)) with ties to even, clamped, NaN -> 0; a row's count is
+        the samples that were clamped or not finite.  f32 copies the bits and counts nothing.  The rows are packed back
+        to back into one device byte buffer that comes to the host in one copy; `offsets` (one byte offset per row) and
+        `out` (a uint8 device tensor) place them in a buffer of the caller's instead, of which only each row's own
+        bytes are written.  Needs no score network and no codec; two calls give identical bytes."""
+        if encoding not in PCM_OUT_ENCODINGS:
+            raise ValueError(f"encoding must be one of {PCM_OUT_ENCODINGS} (got {encoding!r})")
+        x = _dev32(x, self.device)
+        x = x[None] if x.dim() == 1 else x
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x must be [R, Lmax] with at least one row and one sample (got {tuple(x.shape)})")
+        R, Lmax = (int(v) for v in x.shape)
+        ln = [Lmax] * R if lens is None else check_lens(lens, R, Lmax)
+        w = PCM_SAMPLE_BYTES[encoding]
+        if offsets is None:
+            offsets, o = [], 0
+            for v in ln:
+                offsets.append(o)
+                o += v * w
+        offsets = [int(v) for v in offsets]
+        if len(offsets) != R:
+            raise ValueError(f"one byte offset per row is needed ({R} rows, {len(offsets)} offsets)")
+        if out is None:
+            out = torch.zeros(max(o + v * w for o, v in zip(offsets, ln)), device=self.device, dtype=torch.uint8)
+        if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous 1-D uint8 tensor on the device")
+        clipped = (C.c_int64 * R)()
+        self._check(self.lib.dsn_pcm_encode(self.ctx, _ptr(x), R, Lmax, (C.c_int32 * R)(*ln), PCM_ENCODINGS[encoding],
+                                            _ptr(out), out.numel(), (C.c_int64 * R)(*offsets), clipped, self._stream()),
+                    "dsn_pcm_encode")
+        host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out)
+        view = memoryview(host.numpy())
+        return [bytes(view[o:o + v * w]) for o, v in zip(offsets, ln)], [int(c) for c in clipped]
+
+    def scale_output(self, mix, sep, lens=None):
+        """The reference's output gain (src/inference/separate.py:73-78) for a ragged batch (dsn_scale_output): mix
+        [B, Lmax] or [B, 1, Lmax], sep [B, n, Lmax], lens one sample count per item (default: Lmax each) ->
+        (alpha sep [B, n, Lmax] on the device, zero past each item's end; alpha [B, n] float32 on the host) with
+        alpha[b, i] = sum_t mix sep / sum_t (sep^2 + 1e-10) over t < lens[b], summed in float64 in a fixed order and
+        rounded once.  Nothing at or past lens[b] is read; an all-zero estimate gives zeros.  Needs no score network
+        and no codec; a row gives the bits it gives alone."""
+        mix, sep = _dev32(mix, self.device), _dev32(sep, self.device)
+        if mix.dim() == 3 and mix.shape[1] == 1:
+            mix = mix[:, 0]
+        if sep.dim() != 3 or mix.dim() != 2 or mix.shape[0] != sep.shape[0] or mix.shape[-1] != sep.shape[-1]:
+            raise ValueError(f"mix must be [B, Lmax] or [B, 1, Lmax] and sep [B, n, Lmax] (got {tuple(mix.shape)}, "
+                             f"{tuple(sep.shape)})")
+        B, n, Lmax = (int(v) for v in sep.shape)
+        if B < 1 or n < 1 or Lmax < 1:
+            raise ValueError(f"sep must hold at least one item, source and sample (got {tuple(sep.shape)})")
+        ln = None if lens is None else check_lens(lens, B, Lmax)
+        mix = mix.contiguous()
+        out = torch.empty_like(sep)
+        alpha = torch.zeros((B, n), dtype=torch.float32)
+        self._check(self.lib.dsn_scale_output(self.ctx, _ptr(mix), _ptr(sep), B, n, Lmax,
+                                              None if ln is None else (C.c_int32 * B)(*ln), _ptr(out),
+                                              C.cast(C.c_void_p(alpha.data_ptr()), C.POINTER(C.c_float)),
+                                              self._stream()), "dsn_scale_output")
+        return out, alpha
 
     @property
     def hop_length(self) -> int:

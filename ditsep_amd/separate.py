@@ -1,0 +1,126 @@
+"""python -m ditsep_amd.separate input_dir output_dir --config CONFIG --checkpoint CKPT
+
+Separate every .wav file of a folder (the reference's src/inference/separate.py, with its sampler arguments): the files
+go through LatentDiffSep.separate_files in batches of similar length, and `output_dir/s{i}/{stem}.wav` is written at
+each input's own sample rate and frame count.  A file at another rate than the model's is resampled on the device (the
+reference prints "Skipping" for it and separates it at the wrong rate anyway)."""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+
+def str_or_int(x):
+    try:
+        return int(x)
+    except ValueError:
+        return x
+
+
+def _bool(x):
+    if str(x).lower() in ("1", "true", "yes", "on"):
+        return True
+    if str(x).lower() in ("0", "false", "no", "off"):
+        return False
+    raise argparse.ArgumentTypeError(f"expected a boolean, got {x!r}")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The command line (importing and calling this needs neither the HIP library nor a GPU)."""
+    p = argparse.ArgumentParser(prog="python -m ditsep_amd.separate",
+                                description="Separate all the wav files in a specified folder")
+    p.add_argument("input_dir", type=Path, help="Path to the input folder")
+    p.add_argument("output_dir", type=Path, help="Path to the output folder")
+    # the reference's arguments
+    p.add_argument("-d", "--device", type=str_or_int, default="cuda:0", help="Device to use (default: cuda:0)")
+    p.add_argument("-N", type=int, default=None, help="Number of steps (default: config.model.sampler.N)")
+    p.add_argument("--snr", type=float, default=None, help="Step size of corrector")
+    p.add_argument("--corrector-steps", type=int, default=None, help="Number of corrector steps")
+    p.add_argument("--denoise", type=_bool, default=True, help="Use denoising in solver")
+    p.add_argument("-s", "--schedule", type=str, default=None, help="Pick a different schedule for the inference")
+    # the model
+    p.add_argument("--config", type=Path, required=True,
+                   help="The model's configuration tree: JSON, or YAML when the yaml package is installed")
+    p.add_argument("--checkpoint", type=Path, default=None, help="Checkpoint written by the reference's training loop")
+    p.add_argument("--ema", action="store_true", help="Use the checkpoint's EMA weights")
+    p.add_argument("--precision", default="fp16", choices=["bf16", "bf16x3", "fp16", "fp16x3", "fp8"])
+    # the file layer
+    p.add_argument("--batch", type=int, default=64, help="Files per batch (and windows per batch of long files)")
+    p.add_argument("--encoding", default="s16", choices=["s16", "s24", "f32"], help="Sample format of the outputs")
+    p.add_argument("--rescale", action="store_true",
+                   help="Scale every output by the reference's gain (the mixture projected onto it)")
+    p.add_argument("--long-after", type=float, default=None,
+                   help="Seconds; longer files are separated as windows (default: none are)")
+    p.add_argument("--window", type=int, default=None, help="Window of long files, samples at the model's rate")
+    p.add_argument("--overlap", type=int, default=None, help="Overlap of neighbouring windows (default window / 4)")
+    p.add_argument("--long-mode", default="stitch", choices=["stitch", "score"])
+    p.add_argument("--seed", type=int, default=None, help="Makes the run reproducible")
+    return p
+
+
+def load_config(path: Path):
+    text = Path(path).read_text()
+    if Path(path).suffix.lower() in (".yaml", ".yml"):
+        try:
+            import yaml
+        except ImportError as e:
+            raise ValueError(f"{path}: a YAML configuration needs the yaml package; convert it to JSON") from e
+        return yaml.safe_load(text)
+    return json.loads(text)
+
+
+def device_index(device) -> int:
+    if isinstance(device, int):
+        return device
+    if device == "cuda":
+        return 0
+    if str(device).startswith("cuda:"):
+        return int(str(device)[5:])
+    raise ValueError(f"the engine runs on a GPU: --device must be cuda:<index> or an index (got {device!r})")
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    try:
+        if not args.input_dir.is_dir():
+            raise ValueError(f"{args.input_dir} is not a folder")
+        if args.output_dir.is_file():
+            raise ValueError("Output directory is a file")
+        paths = sorted(args.input_dir.glob("*.wav"))
+        if not paths:
+            raise ValueError(f"no .wav files in {args.input_dir}")
+        config = load_config(args.config)
+        dev = device_index(args.device)
+    except ValueError as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+
+    from .latent import LatentDiffSep
+
+    model = LatentDiffSep(config, device=dev, precision=args.precision)
+    try:
+        if args.checkpoint is not None:
+            model.load_checkpoint(args.checkpoint, use_ema=args.ema)
+        kw = {k: v for k, v in (("N", args.N), ("snr", args.snr), ("corrector_steps", args.corrector_steps),
+                                ("schedule", args.schedule)) if v is not None}
+        try:
+            records = model.separate_files(paths, args.output_dir, batch=args.batch, encoding=args.encoding,
+                                           rescale=args.rescale, long_after=args.long_after, window=args.window,
+                                           overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
+                                           denoise=args.denoise, **kw)
+        except ValueError as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
+        for r in records:
+            clipped = sum(r["clipped"])
+            print(f"{r['path']}: {r['frames']} frames at {r['rate']} Hz, {r['channels']} ch -> {len(r['outputs'])} files"
+                  + (f", {clipped} samples clipped" if clipped else ""))
+        return 0
+    finally:
+        model.close()
+
+
+if __name__ == "__main__":
+    sys.exit(main())

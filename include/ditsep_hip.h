@@ -487,6 +487,53 @@ int dsn_resample_length(int fs_in, int fs_out, int L);
 int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_t* lens, int fs_in, int fs_out,
                  int downmix, float* out, int Lout, void* stream);
 
+/* The first and the last step of separating audio files, on the device: the `data` payloads of WAV files to fp32 and
+ * fp32 back to payloads, and the reference's output gain (src/inference/separate.py:73-78).  Restated in numpy in
+ * tests/pcm_restatement.py.  All three need no score network and no codec.  Every per-item table (offset, frames,
+ * channels, encoding, lens) is a HOST array, like `lens` of the resampling call: the call uploads it and synchronises
+ * the stream, so it must not be captured into a graph.  Samples are little-endian; a payload interleaves its channels.
+ *   decode   bytes [nbytes] (device, any alignment) holds the payloads of B files back to back: item b is frames[b]
+ *            frames of channels[b] samples of encoding[b] from byte offset[b] (any alignment).  -> out [B][Cout][Lmax]
+ *            fp32 (device) in one launch, whatever mix of encodings and channel counts the batch holds.  The
+ *            conversions are those of torchaudio.load(normalize=True):
+ *              U8  (v - 128) / 128        S16  v / 2^15        S24  v / 2^23 (three bytes, sign-extended)
+ *              S32 float32(v) 2^-31, v rounded once to nearest even        F32  the bits, NaN payloads included
+ *              F64 rounded once to fp32 (nearest even, overflow to +-inf, every NaN to the quiet NaN 0x7fc00000)
+ *            -- all exact but S32 and F64, all defined to the bit.  downmix != 0: Cout must be 1 and a frame becomes
+ *            (x_0 + .. + x_{C-1}) / C in fp32 in that order, the expression of the resampling call (a one-channel item
+ *            is not divided: its bits pass).  downmix == 0: channel c < channels[b] goes to out[b][c], the channels
+ *            past an item's own count are written as zero.  Samples at or past frames[b] are written as zero.  No byte
+ *            outside [0, nbytes) is loaded, and none outside an item's own range takes part in its result.
+ *   encode   x [R][Lmax] fp32 (device), one row per (file, speaker), lens[r] samples each -> R mono payloads in bytes
+ *            [nbytes] (device), row r at byte offset[r].  encoding is S16, S24 or F32.  An integer encoding of b bits:
+ *            q = rint(x 2^(b-1)) (ties to even; the product is exact), clamped to [-2^(b-1), 2^(b-1) - 1], NaN -> 0.
+ *            clipped [R] (HOST, may be NULL) counts, per row, the samples whose rounded value lay outside that range
+ *            or was not finite (integer atomics: the count does not depend on their order); F32 copies the bits and
+ *            counts nothing.  Only the lens[r] bytes-per-sample bytes of a row are written: whatever lies between and
+ *            after the rows stays as it was.  Two calls give identical bytes.
+ *   scale    mix [B][Lmax], sep [B][n][Lmax] fp32 (device) -> out [B][n][Lmax]:
+ *              alpha[b][i] = sum_t mix[b][t] sep[b][i][t] / sum_t (sep[b][i][t]^2 + 1e-10)  over t < lens[b],
+ *            both sums in fp64 over exact fp64 products, in an order a row's own length fixes (per thread in stride
+ *            order, a fixed tree, the tile sums in index order; no floating-point atomics: a row gives the bits it
+ *            gives alone, and so does a second call); alpha is rounded once to fp32 and out = alpha sep is one fp32
+ *            product.  An all-zero estimate gives alpha = 0 and a zero row.  lens (HOST, or NULL: Lmax each); nothing
+ *            at or past lens[b] is read, and out is written as zero there.  alpha_out [B][n] (HOST, may be NULL: the
+ *            call then only enqueues once lens is on the device).
+ * DSN_EINVAL by name, before anything is allocated or launched: a null pointer; B, R, n or Lmax < 1; B or R > 65535;
+ * an encoding outside the list (decode) or other than S16, S24, F32 (encode); frames[b] outside [1, Lmax];
+ * channels[b] < 1; a frame of more than DSN_PCM_MAX_FRAME_BYTES bytes; downmix with Cout != 1; without downmix
+ * channels[b] > Cout; an item whose bytes leave [0, nbytes); lens[r] outside [1, Lmax]; rows of the encoder whose
+ * payloads overlap or leave the buffer. */
+enum { DSN_PCM_U8 = 0, DSN_PCM_S16 = 1, DSN_PCM_S24 = 2, DSN_PCM_S32 = 3, DSN_PCM_F32 = 4, DSN_PCM_F64 = 5 };
+#define DSN_PCM_MAX_FRAME_BYTES 48
+int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const int64_t* offset, const int32_t* frames,
+                   const int32_t* channels, const int32_t* encoding, int downmix, float* out, int Cout, int Lmax,
+                   void* stream);
+int dsn_pcm_encode(dsn_ctx* ctx, const float* x, int R, int Lmax, const int32_t* lens, int encoding, void* bytes,
+                   int64_t nbytes, const int64_t* offset, int64_t* clipped, void* stream);
+int dsn_scale_output(dsn_ctx* ctx, const float* mix, const float* sep, int B, int n, int Lmax, const int32_t* lens,
+                     float* out, float* alpha_out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
