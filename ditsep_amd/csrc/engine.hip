@@ -3556,6 +3556,87 @@ int dsn_composite_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B
   return composite_call(ctx, "dsn_composite_ragged", ref, est, B, n, L, lens, true, fs, perm, pesq, out, stream);
 }
 
+// bss_eval SDR / SIR / SAR with F-tap distortion filters (include/ditsep_hip.h states the definition; restated in
+// tests/bss_eval_restatement.py).  Device: everything from the correlations to the permutation (bss_eval.hip); host:
+// the refusals, the chunking under the workspace budget (bss_eval_plan: the same chunk sizes dsn_bss_eval_plan
+// reports, whatever sir_sar is) and one copy back.  Per-batch buffers (lens, perm, ee, Q, status, results) are small;
+// the chunk's partials, lag tables and systems are reused from chunk to chunk on the one stream.
+int dsn_bss_eval_plan(int B, int n, int L, int F, int64_t budget, int* tiles, int* M, int* items_per_chunk,
+                      int64_t* workspace_bytes) {
+  BssPlan p;
+  if (!bss_eval_plan(B, n, L, F, budget, &p)) return DSN_EINVAL;
+  if (tiles) *tiles = p.tiles;
+  if (M) *M = p.M;
+  if (items_per_chunk) *items_per_chunk = p.items_per_chunk;
+  if (workspace_bytes) *workspace_bytes = p.per_item * p.items_per_chunk;
+  return DSN_OK;
+}
+
+int dsn_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                 const int* perm, const DsnBssEvalOpts* opts, const DsnBssEvalOut* out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_bss_eval";
+    if (!ref || !est) fail(DSN_EINVAL, "%s: ref or est is null", who);
+    if (!opts || !out || B <= 0 || L <= 0) fail(DSN_EINVAL, "%s: bad arguments (opts, out non-null, B, L > 0)", who);
+    if (n < 1 || n > BSS_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, BSS_MAX_SRC);
+    const int F = opts->filter_length;
+    if (F < 1 || F > BSS_MAX_TAPS) fail(DSN_EINVAL, "%s: filter_length = %d outside [1, %d]", who, F, BSS_MAX_TAPS);
+    if (!(opts->load_diag >= 0)) fail(DSN_EINVAL, "%s: load_diag = %g < 0", who, opts->load_diag);
+    if (opts->perm_by < 0 || opts->perm_by > 1) fail(DSN_EINVAL, "%s: perm_by = %d (0 = SDR, 1 = SIR)", who, opts->perm_by);
+    if (lens) check_item_lens(who, lens, B, L);
+    if (perm)
+      for (int k = 0; k < B * n; ++k)
+        if (perm[k] < 0 || perm[k] >= n) fail(DSN_EINVAL, "%s: perm[%d] = %d outside [0, %d)", who, k, perm[k], n);
+    if (opts->workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)opts->workspace_budget);
+    BssPlan plan;
+    if (!bss_eval_plan(B, n, L, F, opts->workspace_budget, &plan)) {
+      bss_eval_plan(1, n, L, F, 0, &plan);
+      fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at n = %d, L = %d, "
+           "filter_length = %d)", who, (long)opts->workspace_budget, (long)plan.per_item, n, L, F);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int full = opts->sir_sar != 0, ipc = plan.items_per_chunk;
+    const long bn = (long)B * n;
+    std::vector<int> hl, hp;
+    const int *dlens = nullptr, *dperm = nullptr;
+    if (lens) {
+      hl.assign(lens, lens + B);
+      dlens = upload_item_ints(ctx, "bss_lens", hl, st);
+    }
+    if (perm) {
+      hp.assign(perm, perm + bn);
+      dperm = upload_item_ints(ctx, "bss_perm", hp, st);
+    }
+    double* part = ctx->wsbuf<double>("bss_part", (size_t)ipc * plan.part);
+    double* tab = ctx->wsbuf<double>("bss_tab", (size_t)ipc * plan.tab);
+    double* mats = ctx->wsbuf<double>("bss_gram", (size_t)ipc * plan.mats);
+    double* Q = ctx->wsbuf<double>("bss_q", (size_t)B * 32);
+    double* ee = ctx->wsbuf<double>("bss_ee", (size_t)bn);
+    // results: sdr, sir, sar [B n], then the two pair tables [B n n]
+    double* res = ctx->wsbuf<double>("bss_out", (size_t)bn * (3 + 2 * n));
+    int* ints = ctx->wsbuf<int>("bss_ints", (size_t)B + bn);  // status [B], perm_out [B n]
+    HIPCHK(hipMemsetAsync(ints, 0, sizeof(int) * B, st));
+    HIPCHK(hipMemsetAsync(Q, 0, sizeof(double) * B * 32, st));
+    for (int item0 = 0; item0 < B; item0 += ipc) {
+      const int items = std::min(ipc, B - item0);
+      launch_bss_corr(ref, est, n, L, dlens, F, item0, items, plan, part, tab, ee, st);
+      launch_bss_solve(tab, n, F, full, opts->load_diag, item0, items, plan, mats, Q, ints, st);
+    }
+    double *d_sdr = res, *d_sir = res + bn, *d_sar = res + 2 * bn, *d_sdrp = res + 3 * bn, *d_sirp = d_sdrp + bn * n;
+    launch_bss_finish(Q, ee, ints, dperm, B, n, full, opts->perm_by, opts->clamp_db, d_sdr, d_sir, d_sar, d_sdrp, d_sirp,
+                      ints + B, st);
+    HIPCHK(hipGetLastError());
+    const struct { void* host; const void* dev; size_t bytes; } copies[7] = {
+        {out->sdr, d_sdr, sizeof(double) * bn},          {out->sir, d_sir, sizeof(double) * bn},
+        {out->sar, d_sar, sizeof(double) * bn},          {out->sdr_pairs, d_sdrp, sizeof(double) * bn * n},
+        {out->sir_pairs, d_sirp, sizeof(double) * bn * n}, {out->perm_out, ints + B, sizeof(int) * bn},
+        {out->status, ints, sizeof(int) * B}};
+    for (const auto& c : copies)
+      if (c.host) HIPCHK(hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
 // torch.hann_window(win) (periodic: 0.5 - 0.5 cos(2 pi k / win)) centred in fft zeros as torch.stft pads it,
 // (fft - win) / 2 on the left.  The reference's window is a float32 tensor, so it is formed in float32 the way torch
 // forms it (k times the rounded step, cos, times -0.5, plus 0.5): the leakage floor of a spectrum follows the window's

@@ -206,6 +206,54 @@ void launch_composite(int fs, const float* ref, const float* est, const int* yma
                       const int* lens, const int* Fb, const int* kb, int n, const double* win,
                       const CompositeBands& bands, const double* bweights, double* cond, double* llr, double* wss, double* ssnr, double* out, hipStream_t s);
 
+// ---- bss_eval SDR / SIR / SAR with F-tap distortion filters (bss_eval.hip) ----------------------------------
+#define BSS_MAX_SRC 4
+#define BSS_MAX_TAPS 512
+#define BSS_TILE 4096                        // samples of an item one workgroup of the correlation launch takes
+#define BSS_DEFAULT_BUDGET (512LL << 20)     // bytes of per-chunk workspace when the caller gives 0
+// What a call on (B, n, L, F) under a workspace budget does: time tiles of the longest item, M = n F unknowns,
+// correlation jobs per item (2 n^2 + n), items per chunk, and the doubles one item takes of the tile partials
+// [jobs][tiles][F], the lag tables [jobs][F] and the systems (one of M and n - 1 of F unknowns: the lower triangle of
+// the factor, m (m + 1) / 2 entries, then the n right-hand sides of m each); per_item = the bytes of all three.
+struct BssPlan {
+  int tiles, M, jobs, items_per_chunk;
+  long part, tab, mat_full, mat_block, mats;
+  int64_t per_item;
+};
+// false where dsn_bss_eval_plan refuses: B, L < 1, n outside [1, 4], F outside [1, 512], budget < 0 or below one item
+inline bool bss_eval_plan(int B, int n, int L, int F, int64_t budget, BssPlan* p) {
+  if (B < 1 || L < 1 || n < 1 || n > BSS_MAX_SRC || F < 1 || F > BSS_MAX_TAPS || budget < 0) return false;
+  p->tiles = (int)(((long)L + BSS_TILE - 1) / BSS_TILE);
+  p->M = n * F;
+  p->jobs = 2 * n * n + n;
+  p->part = (long)p->jobs * p->tiles * F;
+  p->tab = (long)p->jobs * F;
+  p->mat_full = (long)p->M * (p->M + 1) / 2 + (long)n * p->M;
+  p->mat_block = (long)F * (F + 1) / 2 + (long)n * F;
+  p->mats = p->mat_full + (long)(n - 1) * p->mat_block;
+  p->per_item = (int64_t)sizeof(double) * (p->part + p->tab + p->mats);
+  const int64_t fit = (budget ? budget : BSS_DEFAULT_BUDGET) / p->per_item;
+  if (fit < 1) return false;
+  p->items_per_chunk = (int)(fit < B ? fit : B);
+  if (p->items_per_chunk > 65535) p->items_per_chunk = 65535;   // (a grid dimension)
+  return true;
+}
+// items [item0, item0 + items) of ref, est [B][n][L] (lens [B] device, nullable: item b holds lens[b] <= L samples and
+// nothing past them is read) -> part, tab (chunk-local, sized by the plan) and ee [B][n] = sum est_j^2
+void launch_bss_corr(const float* ref, const float* est, int n, int L, const int* lens, int F, int item0, int items,
+                     const BssPlan& plan, double* part, double* tab, double* ee, hipStream_t s);
+// the chunk's lag tables -> Q [B][2][4][4] (Q[0][j][i]: the share of reference i's rows in pall_j; Q[1][i][j] = pt_ij)
+// and status [B] (zeroed by the caller; 1 where a pivot was <= 0 or not finite).  full == 0: only the pt_ij.
+// mats: the chunk's systems, plan.mats doubles per item
+void launch_bss_solve(const double* tab, int n, int F, int full, double load_diag, int item0, int items,
+                      const BssPlan& plan, double* mats, double* Q, int* status, hipStream_t s);
+// -> sdr, sir, sar [B][n] on the chosen pairs, the pair tables [B][n][n] ([i][j]: est_j against ref_i) and perm_out
+// [B][n]; perm [B][n] (device, nullable: searched, key = sum of SIR when perm_by && full, else of SDR).  Items with
+// status != 0 are NaN throughout (their permutation is the caller's, or the identity)
+void launch_bss_finish(const double* Q, const double* ee, const int* status, const int* perm, int B, int n, int full,
+                       int perm_by, double clamp_db, double* sdr, double* sir, double* sar, double* sdr_pairs,
+                       double* sir_pairs, int* perm_out, hipStream_t s);
+
 // ---- multi-resolution STFT and time-domain reconstruction losses (mrstft.hip) -------------------------------
 #define MRSTFT_MAX_SRC 4
 #define MRSTFT_MAX_RES 16

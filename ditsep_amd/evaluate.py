@@ -23,7 +23,12 @@ waveform error of each reference source against the estimate the SIR permutation
 Utterances of different lengths (the reference evaluates them one at a time, :238): a batch whose `mix` and `target`
 are lists of differently long tensors takes the ragged route -- `length_batches` cuts a data set into such batches
 with little padding -- in which every utterance gets what it gets alone (LatentDiffSep.separate_batch) and every
-metric above but mrstft and score_loss is one call on the padded batch with the utterances' lengths."""
+metric above but mrstft and score_loss is one call on the padded batch with the utterances' lengths.
+
+bss_eval=True adds "sdr", "sir" and "sar" per source from the device (dsn_bss_eval): classic bss_eval (Vincent et al.
+2006) with distortion filters of bss_filter_length taps (512, the bss_eval default, behind the SDRi column of a
+WSJ0-2mix table), scored on the record's SI-SIR permutation as stoi and composite are; dense and ragged batches alike.
+Parity with fast_bss_eval / mir_eval is unpinned (tests/bss_eval_restatement.py is the contract)."""
 from __future__ import annotations
 
 import json
@@ -53,7 +58,7 @@ def _pad_items(items, Lmax: int, device) -> torch.Tensor:
 
 
 def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended,
-                     codec="grouped", composite=False, pesq_fn=None) -> dict:
+                     codec="grouped", composite=False, pesq_fn=None, bss_eval=False, bss_filter_length=512) -> dict:
     """One batch of differently long utterances: mixes list of [1, L_b], targets list of [n, L_b].  The timed region is
     sampler + decode as in the dense route; every requested metric then runs once on the padded [B, n, Lmax] pair with
     the items' lengths (Engine.si_bss_eval / stoi / composite with lens=), each item scored as it is alone.  codec: how
@@ -81,6 +86,7 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
                                                                        est[b][int(perm[b, i])].cpu().numpy())))
                                 for i in range(n_src)] for b in range(B)], dtype=torch.float32)
         comp = eng.composite(tgt, xr, fs, perm=perm, pesq=pq, lens=lens)
+    bss = eng.bss_eval(tgt, xr, filter_length=bss_filter_length, perm=perm, lens=lens)[:3] if bss_eval else None
     records = {}
     for b in range(B):
         rec = {"batch_idx": idx + b, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
@@ -91,6 +97,9 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
                 rec[k] = comp[k][b].tolist()
             if pq is not None:
                 rec["pesq"] = pq[b].tolist()
+        if bss is not None:
+            for k, v in zip(("sdr", "sir", "sar"), bss):
+                rec[k] = v[b].tolist()
         records[idx + b] = rec
     return records
 
@@ -98,7 +107,8 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
 def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = None, corrector_steps: Optional[int] = None,
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
                      stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False,
-                     composite: bool = False, pesq_fn=None, mrstft: bool = False, codec: str = "grouped") -> dict:
+                     composite: bool = False, pesq_fn=None, mrstft: bool = False, codec: str = "grouped",
+                     bss_eval: bool = False, bss_filter_length: int = 512) -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
     with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
     adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
@@ -106,7 +116,8 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     adds "llr", "wss" and "segsnr" (n floats each); with pesq_fn(fs, ref_1d, est_1d) -> float as well, "pesq" is filled
     and "csig", "cbak" and "covl" are added.  mrstft=True adds "mrstft" and "l1" (n floats each, unweighted): the
     diagonal, under the SIR permutation, of the pair tables of Engine.mrstft_loss at its defaults (seven resolutions,
-    A-weighting of `fs`, spectral convergence plus log magnitude).
+    A-weighting of `fs`, spectral convergence plus log magnitude).  bss_eval=True adds "sdr", "sir" and "sar" (n floats
+    each, last in the record): Engine.bss_eval with bss_filter_length taps on the record's "perm".
 
     A batch may also be (list of mix [1,L_b], list of target [n,L_b]) with differing L_b: it takes the ragged route
     (one sampler call on the padded batch, the codec per group of equal length, every metric once on the padded batch
@@ -130,7 +141,8 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                 raise NotImplementedError("score_loss / mrstft are not implemented for ragged batches")
             results.update(_evaluate_ragged(model, list(mix), list(target), fs, idx, seed, N, corrector_steps, snr,
                                             denoise, stoi, stoi_extended, codec=codec, composite=composite,
-                                            pesq_fn=pesq_fn))
+                                            pesq_fn=pesq_fn, bss_eval=bss_eval,
+                                            bss_filter_length=bss_filter_length))
             idx += len(mix)
             continue
         mix, target = mix.to(dev), target.to(dev)
@@ -168,6 +180,8 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
             spec = (tabs["sc"] + tabs["log_mag"]).mean(0)                        # [B,n,n]: mean over the resolutions
             mr = {"mrstft": torch.stack([spec[b, rows, perm[b]] for b in range(B)]),
                   "l1": torch.stack([tabs["l1"][b, rows, perm[b]] for b in range(B)])}
+        bss = (model.engine.bss_eval(target, x_result, filter_length=bss_filter_length, perm=perm)[:3]
+               if bss_eval else None)
         for b in range(B):
             results[idx] = {"batch_idx": idx, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
                             "si_sar": si_sar[b].tolist(),
@@ -183,6 +197,9 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
             if mr is not None:
                 for k in ("mrstft", "l1"):
                     results[idx][k] = mr[k][b].tolist()
+            if bss is not None:
+                for k, v in zip(("sdr", "sir", "sar"), bss):
+                    results[idx][k] = v[b].tolist()
             idx += 1
     return results
 
@@ -235,6 +252,11 @@ def write_results(path: str, results: dict):
     if any("mrstft" in rec for rec in results.values()):
         summary["mrstft_impl"] = ("native (dsn_mrstft_loss): pinned to the reference's auraloss.MultiResolutionSTFTLoss "
                                   "(A-weighted, 7 resolutions) and L1; per source under the SIR permutation")
+    if any("sdr" in rec for rec in results.values()):
+        summary["bss_eval_impl"] = ("native (dsn_bss_eval): bss_eval SDR / SIR / SAR with a 512-tap distortion filter "
+                                    "unless bss_filter_length says otherwise, pinned to the float64 restatement in "
+                                    "tests/bss_eval_restatement.py; parity unpinned vs fast_bss_eval / mir_eval "
+                                    "(neither is installed)")
     summary["nfe_note"] = "nfe = N * (corrector_steps + 1), the reference's bookkeeping (not a count of score calls)"
     with open(path.replace(".json", "_summary.json"), "w") as fh:
         json.dump(summary, fh, indent=2)

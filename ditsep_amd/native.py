@@ -38,6 +38,7 @@ EXPORTS = [
     "dsn_score_window_plan", "dsn_score_windowed", "dsn_pc_sample_windowed", "dsn_separate_windowed",
     "dsn_resample_plan", "dsn_resample_length", "dsn_resample",
     "dsn_pcm_decode", "dsn_pcm_encode", "dsn_scale_output",
+    "dsn_bss_eval", "dsn_bss_eval_plan",
 ]
 
 
@@ -82,6 +83,16 @@ class DsnLossOpts(C.Structure):
 class DsnCompositeOut(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_float)) for k in ("llr", "wss", "segsnr", "snr", "csig", "cbak", "covl")] + [
         ("frames", C.POINTER(C.c_int))]
+
+
+class DsnBssEvalOpts(C.Structure):
+    _fields_ = [("filter_length", C.c_int), ("perm_by", C.c_int), ("clamp_db", C.c_double), ("load_diag", C.c_double),
+                ("sir_sar", C.c_int), ("workspace_budget", C.c_int64)]
+
+
+class DsnBssEvalOut(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("sdr", "sir", "sar", "sdr_pairs", "sir_pairs")] + [
+        ("perm_out", C.POINTER(C.c_int)), ("status", C.POINTER(C.c_int))]
 
 
 class DsnMrstftConfig(C.Structure):
@@ -311,6 +322,60 @@ def check_lens(lens, B: int, Lmax: int, min_len: Optional[int] = None, what: str
                 raise ValueError(f"item {b} (lens[{b}] = {v}) is shorter than one frame "
                                  f"({min_len} samples needed{what})")
     return ln
+
+
+BSS_MAX_SRC, BSS_MAX_TAPS, BSS_TILE, BSS_DEFAULT_BUDGET = 4, 512, 4096, 512 << 20
+BSS_PERM_BY = {"sdr": 0, "sir": 1}
+
+
+def bss_eval_plan(B: int, n: int, L: int, F: int = 512, budget: int = 0) -> dict:
+    """What Engine.bss_eval does with a [B, n, L] batch and F filter taps under a workspace budget in bytes (0: 512 MiB),
+    restated from dsn_bss_eval_plan: "tiles" time tiles of 4096 samples for the longest item, "M" = n F unknowns,
+    "items_per_chunk", "per_item_bytes" -- the float64 tile partials [2 n^2 + n][tiles][F], lag tables [2 n^2 + n][F]
+    and systems (one of M and n - 1 of F unknowns: a packed lower triangle plus n right-hand sides) of one item -- and "workspace_bytes" of one chunk.  ValueError
+    where the library returns DSN_EINVAL."""
+    B, n, L, F, budget = int(B), int(n), int(L), int(F), int(budget)
+    if B < 1 or L < 1:
+        raise ValueError(f"bss_eval: B = {B}, L = {L} (both at least 1)")
+    if n < 1 or n > BSS_MAX_SRC:
+        raise ValueError(f"bss_eval: n = {n} outside [1, {BSS_MAX_SRC}]")
+    if F < 1 or F > BSS_MAX_TAPS:
+        raise ValueError(f"bss_eval: filter_length = {F} outside [1, {BSS_MAX_TAPS}]")
+    if budget < 0:
+        raise ValueError(f"bss_eval: workspace_budget = {budget} < 0")
+    tiles, M, jobs = (L + BSS_TILE - 1) // BSS_TILE, n * F, 2 * n * n + n
+    per_item = 8 * (jobs * tiles * F + jobs * F + M * (M + 1) // 2 + n * M + (n - 1) * (F * (F + 1) // 2 + n * F))
+    fit = (budget or BSS_DEFAULT_BUDGET) // per_item
+    if fit < 1:
+        raise ValueError(f"bss_eval: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
+                         f"n = {n}, L = {L}, filter_length = {F})")
+    ipc = min(fit, B, 65535)
+    return {"tiles": tiles, "M": M, "items_per_chunk": ipc, "per_item_bytes": per_item,
+            "workspace_bytes": per_item * ipc}
+
+
+def check_bss_eval(shape, est_shape, *, filter_length=512, perm_by="sir", load_diag=0.0, perm=None, lens=None,
+                   workspace_budget=0) -> tuple:
+    """The refusals of dsn_bss_eval (include/ditsep_hip.h), raised by name before the library is touched.  Returns
+    (plan, perm_by code, lens as a list or None, perm as a flat list or None)."""
+    if len(shape) != 3 or tuple(est_shape) != tuple(shape):
+        raise ValueError(f"ref and est must both be [B,n,L] (got {tuple(shape)} and {tuple(est_shape)})")
+    B, n, L = (int(v) for v in shape)
+    if perm_by not in BSS_PERM_BY:
+        raise ValueError(f"bss_eval: perm_by = {perm_by!r} (one of {sorted(BSS_PERM_BY)})")
+    if not float(load_diag) >= 0.0:
+        raise ValueError(f"bss_eval: load_diag = {load_diag} < 0")
+    plan = bss_eval_plan(B, n, L, filter_length, workspace_budget)
+    if lens is not None:
+        lens = check_lens(lens, B, L)
+    if perm is not None:
+        perm = torch.as_tensor(perm, dtype=torch.int32).reshape(-1).tolist()
+        if len(perm) != B * n:
+            raise ValueError(f"perm must hold B*n = {B * n} entries (got {len(perm)})")
+        for k, v in enumerate(perm):
+            if v < 0 or v >= n:
+                raise ValueError(f"bss_eval: perm[{k}] = {v} outside [0, {n})")
+    return plan, BSS_PERM_BY[perm_by], lens, perm
 
 
 FADES = {"hann": 0, "linear": 1}
@@ -628,6 +693,9 @@ def load_library() -> C.CDLL:
     lib.dsn_pcm_decode.argtypes = [vp, vp, C.c_int64, ci, i64p, i32p, i32p, i32p, ci, vp, ci, ci, vp]
     lib.dsn_pcm_encode.argtypes = [vp, vp, ci, ci, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
     lib.dsn_scale_output.argtypes = [vp, vp, vp, ci, ci, ci, i32p, vp, fp, vp]
+    lib.dsn_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, i32p, C.POINTER(ci), C.POINTER(DsnBssEvalOpts),
+                                 C.POINTER(DsnBssEvalOut), vp]
+    lib.dsn_bss_eval_plan.argtypes = [ci, ci, ci, ci, C.c_int64, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), i64p]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -1604,6 +1672,49 @@ class Engine:
                         "dsn_composite_ragged")
         res = {k: torch.tensor(list(b), dtype=torch.float32).reshape(B, n) for k, b in bufs.items()}
         res["frames"] = torch.tensor(list(frames), dtype=torch.long).reshape(B, n)
+        return res
+
+    def bss_eval(self, ref, est, *, filter_length: int = 512, perm_by: str = "sir", clamp_db: float = 0.0,
+                 load_diag: float = 0.0, perm=None, lens=None, sir_sar: bool = True, return_pairs: bool = False,
+                 workspace_budget: int = 0):
+        """ref, est [B,n,L] -> (sdr, sir, sar [B,n] float64 dB, perm [B,n]): classic bss_eval (Vincent et al. 2006)
+        with distortion filters of `filter_length` taps (1 .. 512), what fast_bss_eval.bss_eval_sources reports and,
+        with sir_sar=False (sir and sar NaN, permutation on SDR), fast_bss_eval.sdr; restated in
+        tests/bss_eval_restatement.py, parity with the fast_bss_eval / mir_eval packages unpinned.  filter_length=1 is
+        si_bss_eval's decomposition.  There is no zero_mean option: subtract the means first.  The permutation is
+        solved on `perm_by` ("sir", bss_eval's convention, or "sdr") unless perm [B,n] is given (est source perm[b,i]
+        against ref source i).  clamp_db > 0 clamps the dB values to +-clamp_db.  lens (B ints): item b holds lens[b]
+        samples and gets, bit for bit, what it gets alone; the padding is not read.  return_pairs=True appends the
+        tables (sdr_pairs, sir_pairs [B,n,n]; [b,i,j]: est j against ref i).  workspace_budget (bytes, 0 = 512 MiB)
+        bounds the workspace of one chunk of items (native.bss_eval_plan); it changes no bit of the result.
+        An item whose Cholesky factorisation breaks down (an all-zero reference, or references so band-limited that
+        the F-shift Gram matrix is numerically singular) is NaN throughout, with a RuntimeWarning that names it:
+        load_diag > 0 (added to the diagonal of the unit-norm Gram matrix) regularises such items."""
+        plan, by, lens, perm = check_bss_eval(ref.shape, est.shape, filter_length=filter_length, perm_by=perm_by,
+                                              load_diag=load_diag, perm=perm, lens=lens,
+                                              workspace_budget=workspace_budget)
+        B, n, L = ref.shape
+        ref, est = _dev32(ref, self.device), _dev32(est, self.device)
+        vals = {k: (C.c_double * (B * n))() for k in ("sdr", "sir", "sar")}
+        pairs = {k: (C.c_double * (B * n * n))() for k in ("sdr_pairs", "sir_pairs")} if return_pairs else {}
+        perm_out, status = (C.c_int * (B * n))(), (C.c_int * B)()
+        opts = DsnBssEvalOpts(int(filter_length), by, float(clamp_db), float(load_diag), int(bool(sir_sar)),
+                              int(workspace_budget))
+        out = DsnBssEvalOut(perm_out=perm_out, status=status, **vals, **pairs)
+        self._check(self.lib.dsn_bss_eval(self.ctx, _ptr(ref), _ptr(est), B, n, L,
+                                          None if lens is None else (C.c_int32 * B)(*lens),
+                                          None if perm is None else (C.c_int * (B * n))(*perm), C.byref(opts),
+                                          C.byref(out), self._stream()), "dsn_bss_eval")
+        broken = [b for b in range(B) if status[b]]
+        if broken:
+            warnings.warn(f"bss_eval: the Cholesky factorisation broke down for {len(broken)} item(s) {broken[:8]} "
+                          f"(a pivot <= 0 or not finite: an all-zero or band-limited reference); their values are NaN. "
+                          f"load_diag > 0 regularises the Gram matrix", RuntimeWarning, stacklevel=2)
+        res = tuple(torch.tensor(list(vals[k]), dtype=torch.float64).reshape(B, n) for k in ("sdr", "sir", "sar"))
+        res += (torch.tensor(list(perm_out), dtype=torch.long).reshape(B, n),)
+        if return_pairs:
+            res += tuple(torch.tensor(list(pairs[k]), dtype=torch.float64).reshape(B, n, n)
+                         for k in ("sdr_pairs", "sir_pairs"))
         return res
 
     def mrstft_loss(self, reals, decoded, fs: int, *, fft_sizes=MRSTFT_FFT_SIZES, hop_sizes=MRSTFT_HOP_SIZES,

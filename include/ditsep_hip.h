@@ -428,6 +428,56 @@ int dsn_stoi_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int
 int dsn_composite_ragged(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
                          int fs, const int* perm, const float* pesq, const DsnCompositeOut* out, void* stream);
 
+/* Classic bss_eval SDR, SIR and SAR (Vincent et al. 2006): the decomposition dsn_si_bss_eval makes with one tap, made
+ * with a distortion filter of filter_length = F taps (1 <= F <= 512) -- what fast_bss_eval.bss_eval_sources
+ * reports, and with sir_sar = 0 fast_bss_eval.sdr (restated in float64 in tests/bss_eval_restatement.py; parity with
+ * the fast_bss_eval and mir_eval packages unpinned).  ref, est [B,n,L] fp32 (device), all signals zero-extended,
+ * reference i scaled by s_i = 1 / |ref_i| (0 for an all-zero reference; the norm in fp64 over exact products):
+ *   c_ij[k] = s_i s_j sum_t ref_i[t] ref_j[t+k], |k| < F;   G[(i,p),(j,q)] = c_ij[p-q] + load_diag [i = j and p = q]
+ *   d_ij[p] = s_i sum_t ref_i[t-p] est_j[t], 0 <= p < F;    ee_j = sum_t est_j[t]^2
+ *   pt_ij = d_ij^T G_ii^-1 d_ij (G_ii: the F x F Toeplitz block of reference i),  pall_j = d_j^T G^-1 d_j (M = n F)
+ *   SDR_ij = 10 log10(pt_ij / (ee_j - pt_ij)),  SIR_ij = 10 log10(pt_ij / (pall_j - pt_ij)),
+ *   SAR_j = 10 log10(pall_j / (ee_j - pall_j))
+ * numerators and denominators clamped below at 1e-300, the dB value then to +-clamp_db when clamp_db > 0.  With F = 1
+ * this is the SI-BSS decomposition.  Device: fp64 correlations (exact products, fixed order), an fp64 Cholesky of G
+ * and of every G_ii with the right-hand sides carried as extra rows (only the quadratic forms are formed, never the
+ * filters), the ratios and the permutation.  The permutation: `perm` [B*n] (host, may be NULL) is used as is (est
+ * source perm[b*n+i] against ref source i); otherwise all n! candidates in lexicographic order, the key the sum of
+ * SIR (perm_by = 1, bss_eval's convention) or of SDR (perm_by = 0), replaced only by a strictly greater key.
+ * Outputs (host, float64, any may be NULL): sdr, sir, sar [B*n] on the chosen pairs (sar of the assigned estimate),
+ * sdr_pairs, sir_pairs [B*n*n] ([b][i][j]: est_j against ref_i), perm_out [B*n], status [B].
+ * sir_sar = 0: the M x M system is skipped, sir, sar and sir_pairs are NaN and perm_by = 0 is forced; sdr is bit for
+ * bit that of the full call.
+ * lens [B] (host, may be NULL: every item has L samples): item b holds lens[b] samples and gets bit for bit what the
+ * dense call gives for ref[b, :, :lens[b]], est[b, :, :lens[b]] alone; nothing past its end is read.  Two calls give
+ * the same bits (no atomics; every sum's order is fixed by the item's own length, n and F).
+ * Breakdown: a pivot that is <= 0 or not finite (an all-zero reference without load_diag; references so band-limited
+ * that G is numerically singular) sets status[b] = 1 and every value of item b to NaN (its perm_out: `perm`, or the
+ * identity); the call still returns DSN_OK.  load_diag > 0 regularises.
+ * Workspace: the items are taken in chunks whose correlation partials, lag tables and systems stay within
+ * workspace_budget bytes (0 = 512 MiB); the chunking changes no bit of any item.  dsn_bss_eval_plan (no context, no
+ * GPU) returns the time tiles of the longest item, M, the items per chunk and the bytes of one chunk.
+ * There is no zero_mean option (the caller subtracts the means) and no conjugate-gradient solver.
+ * DSN_EINVAL by name, before anything is allocated or launched: ref or est null; n outside [1, 4]; filter_length outside
+ * [1, 512]; load_diag < 0 (or NaN); lens[b] outside [1, L]; a perm entry outside [0, n); perm_by outside {0, 1}; a
+ * budget smaller than one item. */
+typedef struct DsnBssEvalOpts {
+  int filter_length, perm_by;
+  double clamp_db, load_diag;
+  int sir_sar;
+  int64_t workspace_budget;
+} DsnBssEvalOpts;
+typedef struct DsnBssEvalOut {
+  double *sdr, *sir, *sar;        /* [B*n] host */
+  double *sdr_pairs, *sir_pairs;  /* [B*n*n] host */
+  int* perm_out;                  /* [B*n] */
+  int* status;                    /* [B] */
+} DsnBssEvalOut;
+int dsn_bss_eval(dsn_ctx* ctx, const float* ref, const float* est, int B, int n, int L, const int32_t* lens,
+                 const int* perm, const DsnBssEvalOpts* opts, const DsnBssEvalOut* out, void* stream);
+int dsn_bss_eval_plan(int B, int n, int L, int F, int64_t budget, int* tiles, int* M, int* items_per_chunk,
+                      int64_t* workspace_bytes);
+
 /* Put the separated windows of one long recording back together: chunks [W][n][Lw] fp32 (device), window w covering
  * samples [w hop, w hop + Lw) with hop = Lw - overlap -> out [n][L] fp32 (device), with the speakers in window 0's
  * order.  Needs no score network and no codec.  Three stages, all on the device:
