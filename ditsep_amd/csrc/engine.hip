@@ -218,6 +218,9 @@ struct dsn_ctx {
   std::map<std::pair<int, int>, ResampleTables> resample_tables;
   std::vector<int> resample_lens_host;
   const int* resample_lens_dev = nullptr;
+  // dsn_mask_refine: the item lengths last uploaded ("refine_lens") and where they went
+  std::vector<int> refine_lens_host;
+  const int* refine_lens_dev = nullptr;
 
   // DiT
   float* tf_w = nullptr;
@@ -3119,6 +3122,53 @@ int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_
     ctx->prof_launch("resample", 4.0 * ((double)B * C * L + (double)B * (downmix ? 1 : C) * Lout), st, [&] {
       launch_resample(x, dlens, t.taps, t.k0, out, B, C, L, Lout, p.o, p.n, p.width, p.S, t.stride, t.kmin, t.kspan,
                       downmix, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// ---- mixture-consistent STFT masks (maskrefine.hip; include/ditsep_hip.h states the definition)
+int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int n, int Lmax, const int32_t* lens,
+                    int n_fft, int hop, int power, float eps, float* out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_mask_refine";
+    if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
+    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
+      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
+    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
+    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
+    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
+    const int need = n_fft / 2 + 1;
+    for (int b = 0; b < B; ++b) {
+      const int len = lens ? lens[b] : Lmax;
+      if (len < need || len > Lmax)
+        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
+             "reflection must reach the item)", who, b, len, need, Lmax, need);
+      if (!lens) break;
+    }
+    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    const size_t row = sizeof(float) * (size_t)B * Lmax;
+    if ((o0 < m0 + row && m0 < o0 + row * n) || (o0 < e0 + row * n && e0 < o0 + row * n))
+      fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int* dlens = nullptr;
+    if (lens) {
+      std::vector<int> h(lens, lens + B);
+      int* d = ctx->wsbuf<int>("refine_lens", B);
+      if (h != ctx->refine_lens_host || d != ctx->refine_lens_dev) {
+        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
+        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->refine_lens_host = h;
+        ctx->refine_lens_dev = d;
+      }
+      dlens = d;
+    }
+    ctx->prof_launch("mask_refine", 4.0 * (double)B * Lmax * (2 * n + 1), st, [&] {
+      launch_mask_refine(mix, est, dlens, out, B, n, Lmax, n_fft, hop, power, eps, st);
     });
     HIPCHK(hipGetLastError());
   });

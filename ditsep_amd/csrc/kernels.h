@@ -415,3 +415,11 @@ void launch_stitch_perm(const double* part, double* gram, int* perm, int W, int 
 // W - 1).  fall, rise [O] fp32 (device).
 void launch_stitch_gather(const float* chunks, const int* perm, const float* fall, const float* rise, float* out, int W,
                           int n, int Lw, int O, int L, hipStream_t s);
+
+// ---- mixture-consistent STFT masks (maskrefine.hip) -----------------------------------------------------------
+// mix [B][Lmax], est / out [B][n][Lmax] fp32, lens [B] (device) or null, n <= MASK_REFINE_MAX_SRC, nfft a power of two
+// mask_refine_fft_ok accepts, nfft / hop in {2, 4, 8}: one launch, a workgroup per (span of output samples, item).
+#define MASK_REFINE_MAX_SRC 4
+bool mask_refine_fft_ok(int nfft);
+void launch_mask_refine(const float* mix, const float* est, const int* lens, float* out, int B, int n, int Lmax,
+                        int nfft, int hop, int power, float eps, hipStream_t s);

@@ -78,13 +78,14 @@ def _padded(rows, device):
 
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
-                   window=None, overlap=None, long_mode="stitch", seed=None, **sampler_kwargs) -> list:
+                   window=None, overlap=None, long_mode="stitch", seed=None, refine=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     eng = model.engine
     fs = model._model_rate("separate_files")
     if encoding not in native.PCM_OUT_ENCODINGS:
         raise ValueError(f"encoding must be one of {native.PCM_OUT_ENCODINGS} (got {encoding!r})")
     native.check_codec_mode(codec)
+    refine = native.refine_options(refine)
     if long_mode not in native.LONG_MODES:
         raise ValueError(f"long_mode must be one of {native.LONG_MODES} (got {long_mode!r})")
     paths = [os.fspath(p) for p in paths]
@@ -95,11 +96,20 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         window = max(4 * hop, int(float(long_after) * fs) // (4 * hop) * (4 * hop))
     out_dir = os.fspath(out_dir)
     n = model.n_src
+    if refine is not None:
+        # its refusals before any device work (checked on a stand-in item long enough for every n_fft), a file too
+        # short for one reflection included
+        need = native.check_mask_refine((1, 2049), (1, n, 2049), None, **refine)[2] // 2 + 1
+        for p, v in zip(paths, plan["lengths"]):
+            if v < need:
+                raise ValueError(f"{p}: {v} samples at the model's rate; refine= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
 
     def finish(idx, at_fs, est, label):
         """estimates at the model's rate -> files; `at_fs` the mono mixtures there"""
         alpha = None
+        if refine is not None:
+            est = eng.mask_refine(at_fs, est, **refine)
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)

@@ -338,26 +338,43 @@ class LatentDiffSep:
         return out
 
     @torch.no_grad()
-    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs):
+    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs, refine=None):
         """`separate` of mix [B, C, L] (or [B, L]) at `sample_rate`: to the model's rate (mixed down), the existing
-        call, every estimate back to `sample_rate` and cropped to L."""
+        call (with `refine`, there), every estimate back to `sample_rate` and cropped to L."""
         fs, eng = self._model_rate("sample_rate="), self.engine
         mix = mix[:, None] if mix.dim() == 2 else mix
         L = int(mix.shape[-1])
         m = eng.resample(mix, sample_rate, fs, downmix=True)
-        est, *others = self.separate(m, target_dim, **kwargs)
+        est, *others = self.separate(m, target_dim, refine=refine, **kwargs)
         return (eng.resample(est, fs, sample_rate)[..., :L], *others)
 
     @torch.no_grad()
-    def separate(self, mix, target_dim=None, latent=False, sample_rate=None, **kwargs):
+    def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
-        `sample_rate`, cropped to L."""
+        `sample_rate`, cropped to L.
+        refine (default None: the decoder's output is returned as it is): None, True or "mask" (Engine.mask_refine
+        with native.MASK_REFINE_DEFAULTS) or a dict of n_fft / hop / power / eps -- the estimates are refined against
+        the mono mixture at the model's rate after the decoder and before any resampling back.  Where the estimates
+        are longer than the mixture (without target_dim the codec hands back whole hops) the mixture is zero-extended
+        to their length, which is what the encoder saw; shorter estimates are refused.  Refused with latent=True:
+        there is no waveform mixture."""
+        opts = native.refine_options(refine)
+        if opts is not None and latent:
+            raise ValueError("refine= applies to waveforms: with latent=True there is no waveform mixture to refine "
+                             "against")
         if sample_rate is not None:
             if latent:
                 raise ValueError("sample_rate= applies to waveforms: a latent has no sample rate to convert")
-            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs)
+            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs, refine=refine)
+        if opts is not None:
+            est, *others = self.separate(mix, target_dim, **kwargs)
+            short = int(est.shape[-1]) - int(mix.shape[-1])
+            if short < 0:
+                raise ValueError(f"refine=: the estimates ({est.shape[-1]} samples) are shorter than the mixture "
+                                 f"({mix.shape[-1]}); target_dim must not cut the mixture")
+            return (self.engine.mask_refine(torch.nn.functional.pad(mix, (0, short)), est, **opts), *others)
         if not latent:
             # the reference draws fresh VAE posterior noise on every call (bottleneck.py:57-83): without an explicit
             # seed, so does this (an explicit seed makes the whole call reproducible)
@@ -372,7 +389,8 @@ class LatentDiffSep:
         return (est, *others)
 
     @torch.no_grad()
-    def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, **sampler_kwargs):
+    def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None,
+                       **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -384,14 +402,20 @@ class LatentDiffSep:
         rate per item; the mixtures may then be [L], [C, L] or [1, C, L].  They are resampled to config.model.fs on the
         device (Engine.to_model_rate: mixed down, one call per distinct rate), separated as above -- target_dims,
         vae_noise and noise keep their meaning at the model's rate -- and every estimate comes back at its item's own
-        rate, cropped to the item's sample count (Engine.from_model_rate)."""
+        rate, cropped to the item's sample count (Engine.from_model_rate).
+        refine (default None: off), as in `separate`: one Engine.mask_refine call on the padded batch with the items'
+        lengths, at the model's rate, before any resampling back; each item gets the bits it gets alone."""
         eng = self.engine
+        opts = native.refine_options(refine)
         if sample_rates is not None:
             fs = self._model_rate("sample_rates=")
             rates = [int(sample_rates)] * len(mixes) if isinstance(sample_rates, int) else [int(r) for r in sample_rates]
             at_fs = eng.to_model_rate(list(mixes), rates, fs)
-            est, *others = self.separate_batch(at_fs, target_dims, codec, **sampler_kwargs)
+            est, *others = self.separate_batch(at_fs, target_dims, codec, refine=refine, **sampler_kwargs)
             return (eng.from_model_rate(est, rates, fs, [int(m.shape[-1]) for m in mixes]), *others)
+        if opts is not None:
+            est, *others = self.separate_batch(mixes, target_dims, codec, **sampler_kwargs)
+            return (eng.mask_refine(list(mixes), est, **opts), *others)
         native.check_codec_mode(codec)
         native.check_ragged(eng.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
         kwargs = dict(sampler_kwargs)
@@ -408,7 +432,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      mode="stitch", sample_rates=None, **sampler_kwargs):
+                      mode="stitch", sample_rates=None, refine=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -422,8 +446,11 @@ class LatentDiffSep:
         sample_rates (default None: the recordings are mono at the model's rate, the call is what it was): an int or
         one rate per recording, as in separate_batch -- the recordings are resampled to config.model.fs and mixed down,
         `window` and `overlap` stay in samples at the model's rate, and every estimate comes back at its recording's
-        own rate and sample count."""
+        own rate and sample count.
+        refine (default None: off), as in `separate`: every recording is refined whole against its mono mixture at
+        the model's rate, after the stitch (or the single decode of mode="score") and before any resampling back."""
         eng = self.engine
+        opts = native.refine_options(refine)
         if sample_rates is not None:
             fs = self._model_rate("sample_rates=")
             single = torch.is_tensor(mixes)
@@ -432,9 +459,15 @@ class LatentDiffSep:
             at_fs = eng.to_model_rate(clips, rates, fs)
             est, *others = self.separate_long(at_fs[0] if single else at_fs, window, overlap=overlap, fade=fade,
                                               align=align, batch=batch, return_info=return_info, mode=mode,
-                                              **sampler_kwargs)
+                                              refine=refine, **sampler_kwargs)
             back = eng.from_model_rate([est] if single else est, rates, fs, [int(m.shape[-1]) for m in clips])
             return (back[0] if single else back, *others)
+        if opts is not None:
+            single = torch.is_tensor(mixes)
+            est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
+                                              return_info=return_info, mode=mode, **sampler_kwargs)
+            ref = eng.mask_refine([mixes] if single else list(mixes), [est] if single else est, **opts)
+            return (ref[0] if single else ref, *others)
         if mode not in native.LONG_MODES:
             raise ValueError(f"mode must be one of {native.LONG_MODES} (got {mode!r})")
         if int(batch) < 1:
@@ -477,7 +510,8 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
-                       long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, **sampler_kwargs):
+                       long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
+                       **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -493,12 +527,14 @@ class LatentDiffSep:
         samples at the model's rate, window defaulting to long_after seconds rounded down to a multiple of 4 hops --
         and the same way out.  -> one dict per input, in input order: "path", "rate", "channels", "frames", "outputs"
         (the files written), "clipped" (per speaker, the samples that were clamped), "alpha" (per speaker, with
-        rescale), "batch" (the batch index, or "long").  DiT score network only (separate_batch's restriction)."""
+        rescale), "batch" (the batch index, or "long").  DiT score network only (separate_batch's restriction).
+        refine (default None: off), as in `separate`: per batch the order is separate -> refine (Engine.mask_refine
+        against the mono mixtures at the model's rate) -> rescale -> back to each file's rate -> quantise."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
-                                    seed=seed, **sampler_kwargs)
+                                    seed=seed, refine=refine, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -39,6 +39,7 @@ EXPORTS = [
     "dsn_resample_plan", "dsn_resample_length", "dsn_resample",
     "dsn_pcm_decode", "dsn_pcm_encode", "dsn_scale_output",
     "dsn_bss_eval", "dsn_bss_eval_plan",
+    "dsn_mask_refine",
 ]
 
 
@@ -578,6 +579,64 @@ def check_resample(fs_in, fs_out, shape, lens=None) -> tuple:
     return fs_in, fs_out, (B, Cn, L), (None if lens is None else check_lens(lens, B, L))
 
 
+MASK_REFINE_DEFAULTS = dict(n_fft=512, hop=128, power=2, eps=1e-10)
+MASK_REFINE_MAX_SRC = 4
+
+
+def refine_options(refine) -> Optional[dict]:
+    """The `refine` keyword of the separation entry points as Engine.mask_refine's keywords: None (off, the default)
+    -> None; True or "mask" -> MASK_REFINE_DEFAULTS; a dict of n_fft / hop / power / eps -> the defaults with those
+    replaced.  Anything else, False included, is refused by name."""
+    if refine is None:
+        return None
+    if refine is True or refine == "mask":
+        return dict(MASK_REFINE_DEFAULTS)
+    if isinstance(refine, Mapping):
+        extra = sorted(set(refine) - set(MASK_REFINE_DEFAULTS))
+        if extra:
+            raise ValueError(f"refine: unknown keys {extra} (a dict of {sorted(MASK_REFINE_DEFAULTS)})")
+        return dict(MASK_REFINE_DEFAULTS, **refine)
+    raise ValueError(f"refine must be None, True, 'mask' or a dict of {sorted(MASK_REFINE_DEFAULTS)} (got {refine!r})")
+
+
+def check_mask_refine(mix_shape, est_shape, lens=None, n_fft=512, hop=128, power=2, eps=1e-10) -> tuple:
+    """The refusals of dsn_mask_refine (include/ditsep_hip.h), raised by name before the library is touched: mix that
+    is not [B, L] or [B, 1, L] and est that is not [B, n, L] of the same B and L; n outside [1, 4]; n_fft not a power
+    of two in [64, 2048]; n_fft / hop not in {2, 4, 8}; power not 1 or 2; eps not finite or <= 0; an item shorter than
+    n_fft / 2 + 1 samples (one reflection must reach it) or lens[b] > L.
+    -> ((B, n, L), lens as a list or None, n_fft, hop, power, eps)"""
+    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
+    if len(mix_shape) == 3 and mix_shape[1] == 1:
+        mix_shape = (mix_shape[0], mix_shape[2])
+    if len(mix_shape) != 2 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != mix_shape:
+        raise ValueError(f"mask_refine: mix must be [B, L] or [B, 1, L] and est [B, n, L] of the same B and L (got "
+                         f"{mix_shape} and {est_shape})")
+    B, n, L = est_shape
+    if B < 1:
+        raise ValueError(f"mask_refine: B = {B} < 1")
+    if n < 1 or n > MASK_REFINE_MAX_SRC:
+        raise ValueError(f"mask_refine: n = {n} outside [1, {MASK_REFINE_MAX_SRC}]")
+    if int(n_fft) != n_fft or int(n_fft) < 64 or int(n_fft) > 2048 or int(n_fft) & (int(n_fft) - 1):
+        raise ValueError(f"mask_refine: n_fft = {n_fft!r} is not a power of two in [64, 2048]")
+    n_fft = int(n_fft)
+    if int(hop) != hop or int(hop) < 1 or n_fft % int(hop) or n_fft // int(hop) not in (2, 4, 8):
+        raise ValueError(f"mask_refine: n_fft / hop = {n_fft} / {hop!r} is not one of 2, 4, 8")
+    if power not in (1, 2):
+        raise ValueError(f"mask_refine: power = {power!r} is not 1 or 2")
+    eps = float(eps)
+    if not math.isfinite(eps) or not eps > 0.0:
+        raise ValueError(f"mask_refine: eps = {eps} is not a finite positive number")
+    need = n_fft // 2 + 1
+    ln = [L] if lens is None else [int(v) for v in lens]
+    if lens is not None and len(ln) != B:
+        raise ValueError(f"lens must hold one sample count per item (B = {B}), got {len(ln)}")
+    for b, v in enumerate(ln):
+        if v < need or v > L:
+            raise ValueError(f"mask_refine: item {b} has {v} samples, outside [n_fft / 2 + 1 = {need}, L = {L}] "
+                             f"({need} samples needed: one reflection must reach the item)")
+    return (B, n, L), (None if lens is None else ln), n_fft, int(hop), int(power), eps
+
+
 PCM_ENCODINGS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5}        # DSN_PCM_*
 PCM_SAMPLE_BYTES = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8}
 PCM_OUT_ENCODINGS = ("s16", "s24", "f32")                                          # what dsn_pcm_encode writes
@@ -696,6 +755,7 @@ def load_library() -> C.CDLL:
     lib.dsn_bss_eval.argtypes = [vp, vp, vp, ci, ci, ci, i32p, C.POINTER(ci), C.POINTER(DsnBssEvalOpts),
                                  C.POINTER(DsnBssEvalOut), vp]
     lib.dsn_bss_eval_plan.argtypes = [ci, ci, ci, ci, C.c_int64, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), i64p]
+    lib.dsn_mask_refine.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, ci, ci, C.c_float, vp, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -1381,6 +1441,43 @@ class Engine:
                     "dsn_resample")
         out = out.reshape((Lout,) if nd == 1 else (Co, Lout) if nd == 2 else (B, Co, Lout))
         return out if ln is None else (out, [resample_length(fs_in, fs_out, v) for v in ln])
+
+    # ------------------------------------------------------------------ mixture-consistent masks
+    def mask_refine(self, mix, est, lens=None, n_fft=512, hop=128, power=2, eps=1e-10):
+        """Mixture-consistent STFT masks on the device (dsn_mask_refine, csrc/maskrefine.hip; the definition is in
+        include/ditsep_hip.h and tests/mask_refine_restatement.py): soft masks M_i = (|S_i|^power + eps) /
+        (sum_j |S_j|^power + n eps) from the estimates' STFTs (periodic Hann of n_fft samples every hop), applied to
+        the mixture's STFT and transformed back.  mix [B, L] or [B, 1, L], est [B, n, L] -> [B, n, L]: every output
+        has the mixture's phase and the outputs sum to the mixture up to float32 rounding.  lens (one sample count per
+        item): a ragged batch padded to L -- nothing at or past lens[b] is read (it may hold NaN), the result is zero
+        there and each item gets the bits it gets alone.  Lists (mix: [1, L_b] or [L_b] each, est: [n, L_b] each) are
+        padded once and a list of [n, L_b] comes back.  Not a trained step: what it does to separation quality is
+        unmeasured.  Needs no score network and no codec; two calls give identical bits."""
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
+                raise ValueError("mask_refine: a list of mixtures goes with a list of as many estimates and no lens")
+            ln = [int(e.shape[-1]) for e in est]
+            for b, (m, e) in enumerate(zip(mix, est)):
+                if e.dim() != 2 or m.numel() != ln[b] or m.dim() not in (1, 2):
+                    raise ValueError(f"mask_refine: item {b} must be mix [1, L] and est [n, L] (got {tuple(m.shape)} "
+                                     f"and {tuple(e.shape)})")
+            Lmax = max(ln)
+            mp = torch.zeros((len(mix), Lmax), device=self.device, dtype=torch.float32)
+            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
+            for b, (m, e) in enumerate(zip(mix, est)):
+                mp[b, :ln[b]] = _dev32(m, self.device).reshape(-1)
+                ep[b, :, :ln[b]] = _dev32(e, self.device)
+            out = self.mask_refine(mp, ep, lens=ln, n_fft=n_fft, hop=hop, power=power, eps=eps)
+            return [out[b, :, :ln[b]] for b in range(len(mix))]
+        (B, n, L), ln, n_fft, hop, power, eps = check_mask_refine(tuple(mix.shape), tuple(est.shape), lens, n_fft, hop,
+                                                                  power, eps)
+        mix = _dev32(mix, self.device).reshape(B, L)
+        est = _dev32(est, self.device)
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        self._check(self.lib.dsn_mask_refine(self.ctx, _ptr(mix), _ptr(est), B, n, L,
+                                             None if ln is None else (C.c_int32 * B)(*ln), n_fft, hop, power, eps,
+                                             _ptr(out), self._stream()), "dsn_mask_refine")
+        return out
 
     def to_model_rate(self, clips, rates, fs: int):
         """Clips of any rate, channel count and length at the model's rate `fs`, mixed down to mono: `clips` is a list

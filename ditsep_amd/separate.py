@@ -57,6 +57,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--overlap", type=int, default=None, help="Overlap of neighbouring windows (default window / 4)")
     p.add_argument("--long-mode", default="stitch", choices=["stitch", "score"])
     p.add_argument("--seed", type=int, default=None, help="Makes the run reproducible")
+    p.add_argument("--refine", action="store_true",
+                   help="Refine the estimates with mixture-consistent STFT masks before they are written (not a "
+                        "trained step; off by default)")
+    p.add_argument("--refine-nfft", type=int, default=512, help="Window of the masks, samples at the model's rate")
+    p.add_argument("--refine-hop", type=int, default=128, help="Hop of the masks (window / 2, / 4 or / 8)")
+    p.add_argument("--refine-power", type=int, default=2, choices=[1, 2], help="Exponent of the mask magnitudes")
     return p
 
 
@@ -79,6 +85,13 @@ def device_index(device) -> int:
     if str(device).startswith("cuda:"):
         return int(str(device)[5:])
     raise ValueError(f"the engine runs on a GPU: --device must be cuda:<index> or an index (got {device!r})")
+
+
+def refine_of(args):
+    """The `refine` keyword of separate_files from the parsed flags: None unless --refine is given."""
+    if not args.refine:
+        return None
+    return dict(n_fft=args.refine_nfft, hop=args.refine_hop, power=args.refine_power)
 
 
 def main(argv=None) -> int:
@@ -109,7 +122,7 @@ def main(argv=None) -> int:
             records = model.separate_files(paths, args.output_dir, batch=args.batch, encoding=args.encoding,
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
-                                           denoise=args.denoise, **kw)
+                                           refine=refine_of(args), denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2

@@ -537,6 +537,33 @@ int dsn_resample_length(int fs_in, int fs_out, int L);
 int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_t* lens, int fs_in, int fs_out,
                  int downmix, float* out, int Lout, void* stream);
 
+/* Mixture-consistent STFT masks: a refinement of separated estimates against the mixture they came from (Wiener-style
+ * post-filtering; csrc/maskrefine.hip, restated in float64 in tests/mask_refine_restatement.py).  It is a definition, not
+ * a trained step, and nothing calls it unless asked to.  Per item, with mixture m [L], estimates s_i [L] (i < n):
+ *   padding    Lp = hop ceil(L / hop); every signal is zero-extended to Lp
+ *   analysis   torch.stft(center = True, pad_mode = "reflect") with the periodic Hann window of n_fft samples, computed
+ *              in fp64 and rounded once to fp32: F = 1 + Lp / hop frames, bins 0 .. n_fft / 2
+ *   masks      a_i = |S_i|^power,  M_i = (a_i + eps) / (sum_j a_j + n eps): they sum to 1, also where every estimate is
+ *              silent (there M_i = 1 / n)
+ *   synthesis  Y_i = M_i X (X: the mixture's STFT), y_i = the overlap-add of the windowed inverse frames divided, per
+ *              sample, by the sum of w^2 over the frames that cover it; cropped to L
+ * Every output carries the mixture's phase and sum_i y_i = m up to rounding.  mix [B][Lmax], est and out [B][n][Lmax]
+ * fp32 (device), one launch, no workspace.  lens (HOST, [B], or NULL: every item is Lmax long): item b has its own
+ * L_b = lens[b], Lp_b and F_b and is reflected at its own end; nothing at or past lens[b] is read from mix or est (the
+ * padding may hold NaN) and out is written as zero there.  All arithmetic is fp32 in a fixed order with no atomics: an
+ * item's result does not depend on its position in the batch, on the other items or on how the samples are divided among
+ * workgroups, and two calls give identical bits.  With n = 1 the mask is exactly 1; silent estimates with n = 2 or 4
+ * give the n = 1 result scaled by 1 / n to the bit.  Needs no score network and no codec.  The window and the twiddles
+ * are formed on the device; the call uploads `lens` when it is given and differs from the last upload, and then
+ * synchronises the stream, so with lens it must not be captured into a graph.
+ * DSN_EINVAL by name, before anything is allocated or launched: mix, est or out null; B < 1 or B > 65535; n outside
+ * [1, 4]; n_fft not a power of two in [64, 2048]; n_fft / hop not in {2, 4, 8}; power not 1 or 2; eps not finite or <= 0;
+ * Lmax > 2^30; lens[b] (or Lmax without lens) outside [n_fft / 2 + 1, Lmax] -- one reflection must reach the item, the
+ * message names the item and the samples needed; out overlapping mix or est (neighbouring workgroups read the samples
+ * around a span). */
+int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int n, int Lmax, const int32_t* lens,
+                    int n_fft, int hop, int power, float eps, float* out, void* stream);
+
 /* The first and the last step of separating audio files, on the device: the `data` payloads of WAV files to fp32 and
  * fp32 back to payloads, and the reference's output gain (src/inference/separate.py:73-78).  Restated in numpy in
  * tests/pcm_restatement.py.  All three need no score network and no codec.  Every per-item table (offset, frames,
