@@ -221,6 +221,9 @@ struct dsn_ctx {
   // dsn_mask_refine: the item lengths last uploaded ("refine_lens") and where they went
   std::vector<int> refine_lens_host;
   const int* refine_lens_dev = nullptr;
+  // dsn_ensemble_combine: likewise ("ensemble_lens")
+  std::vector<int> ensemble_lens_host;
+  const int* ensemble_lens_dev = nullptr;
 
   // DiT
   float* tf_w = nullptr;
@@ -3171,6 +3174,74 @@ int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int
       launch_mask_refine(mix, est, dlens, out, B, n, Lmax, n_fft, hop, power, eps, st);
     });
     HIPCHK(hipGetLastError());
+  });
+}
+
+// ---- ensemble combine (ensemble.hip; include/ditsep_hip.h states the definition)
+int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int B, int K, int n, int Lmax,
+                         const int32_t* lens, int mode, float* out, int32_t* perm_out, int32_t* anchor_out,
+                         int32_t* best_out, double* resid_db_out, double* agree_db_out, double* gram_out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_ensemble_combine";
+    if (!cands || !out) fail(DSN_EINVAL, "%s: cands or out is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (K < 1 || K > ENSEMBLE_MAX_K) fail(DSN_EINVAL, "%s: K = %d outside [1, %d]", who, K, ENSEMBLE_MAX_K);
+    if (n < 1 || n > ENSEMBLE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, ENSEMBLE_MAX_SRC);
+    if (Lmax < 1 || Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d outside [1, 2^30]", who, Lmax);
+    if (mode < DSN_ENSEMBLE_MEAN || mode > DSN_ENSEMBLE_MEDOID)
+      fail(DSN_EINVAL, "%s: mode = %d is not one of 0 (mean), 1 (median), 2 (best), 3 (medoid)", who, mode);
+    if (mode == DSN_ENSEMBLE_BEST && !mix)
+      fail(DSN_EINVAL, "%s: mode best ranks the candidates by their residual against the mixture: mix is null", who);
+    for (int b = 0; lens && b < B; ++b)
+      if (lens[b] < 1 || lens[b] > Lmax)
+        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, b, lens[b], Lmax);
+    const char *c0 = (const char*)cands, *o0 = (const char*)out;
+    const size_t row = sizeof(float) * (size_t)B * n * Lmax;
+    if (o0 < c0 + row * K && c0 < o0 + row) fail(DSN_EINVAL, "%s: out overlaps cands", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int* dlens = nullptr;
+    if (lens) {
+      std::vector<int> h(lens, lens + B);
+      int* d = ctx->wsbuf<int>("ensemble_lens", B);
+      if (h != ctx->ensemble_lens_host || d != ctx->ensemble_lens_dev) {
+        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
+        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->ensemble_lens_host = h;
+        ctx->ensemble_lens_dev = d;
+      }
+      dlens = d;
+    }
+    const long R = (long)K * n + (mix ? 1 : 0), tiles = ensemble_tiles(Lmax);
+    int RB, NB, S, SUBQ;
+    ensemble_gram_plan((int)R, &RB, &NB, &S, &SUBQ);
+    double* part = ctx->wsbuf<double>("ensemble_part", (size_t)B * tiles * NB * 16);
+    // gram [B][R][R], resid_db [B][K], agree_db [B][K][n]; perm [B][K][n], anchor [B], best [B]
+    double* gram = ctx->wsbuf<double>("ensemble_info", (size_t)B * (R * R + K + (long)K * n));
+    double *resid = gram + (size_t)B * R * R, *agree = resid + (size_t)B * K;
+    int* perm = ctx->wsbuf<int>("ensemble_perm", (size_t)B * ((long)K * n + 2));
+    int *anchor = perm + (size_t)B * K * n, *best = anchor + B;
+    const double bytes = 4.0 * (double)B * Lmax * ((double)K * n + (mix ? 1 : 0));
+    ctx->prof_launch("ensemble_gram", bytes, st, [&] { launch_ensemble_gram(cands, mix, dlens, part, B, K, n, Lmax, st); });
+    ctx->prof_launch("ensemble_solve", 8.0 * (double)B * tiles * NB * 16, st, [&] {
+      launch_ensemble_solve(dlens, part, gram, perm, anchor, best, resid, agree, B, K, n, Lmax, mix ? 1 : 0, st);
+    });
+    const double rows = mode == DSN_ENSEMBLE_MEAN || mode == DSN_ENSEMBLE_MEDIAN ? K : 1;
+    ctx->prof_launch("ensemble_gather", 4.0 * (double)B * n * Lmax * (rows + 1), st, [&] {
+      launch_ensemble_gather(cands, dlens, perm, anchor, best, out, B, K, n, Lmax, mode, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!perm_out && !anchor_out && !best_out && !resid_db_out && !agree_db_out && !gram_out) return;
+    auto back = [&](void* dst, const void* src, size_t nbytes) {
+      if (dst) HIPCHK(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, st));
+    };
+    back(perm_out, perm, sizeof(int32_t) * (size_t)B * K * n);
+    back(anchor_out, anchor, sizeof(int32_t) * (size_t)B);
+    back(best_out, best, sizeof(int32_t) * (size_t)B);
+    back(resid_db_out, resid, sizeof(double) * (size_t)B * K);
+    back(agree_db_out, agree, sizeof(double) * (size_t)B * K * n);
+    back(gram_out, gram, sizeof(double) * (size_t)B * R * R);
+    HIPCHK(hipStreamSynchronize(st));
   });
 }
 

@@ -423,3 +423,21 @@ void launch_stitch_gather(const float* chunks, const int* perm, const float* fal
 bool mask_refine_fft_ok(int nfft);
 void launch_mask_refine(const float* mix, const float* est, const int* lens, float* out, int B, int n, int Lmax,
                         int nfft, int hop, int power, float eps, hipStream_t s);
+
+// ---- ensemble combine (ensemble.hip) -----------------------------------------------------------------------------
+// cands [B][K][n][Lmax], mix [B][Lmax] or null, out [B][n][Lmax] fp32, lens [B] (device) or null, K <= ENSEMBLE_MAX_K,
+// n <= ENSEMBLE_MAX_SRC.  Three launches: Gram partials part [B][tiles][NB][16] (4 x 4 blocks of row pairs on and above
+// the diagonal of the R = K n (+ 1) rows; ensemble_gram_plan gives NB), one workgroup per item for gram [B][R][R],
+// perm [B][K][n], anchor / best [B], resid_db [B][K], agree_db [B][K][n], and the gather.
+#define ENSEMBLE_MAX_K 16
+#define ENSEMBLE_MAX_SRC 4
+#define ENS_TILE 2048   // samples one workgroup of the Gram launch sums, counted from the item's own start
+inline int ensemble_tiles(int Lmax) { return (Lmax + ENS_TILE - 1) / ENS_TILE; }
+void ensemble_gram_plan(int R, int* RB, int* NB, int* S, int* SUBQ);
+void launch_ensemble_gram(const float* cands, const float* mix, const int* lens, double* part, int B, int K, int n,
+                          int Lmax, hipStream_t s);
+void launch_ensemble_solve(const int* lens, const double* part, double* gram, int* perm, int* anchor, int* best,
+                           double* resid_db, double* agree_db, int B, int K, int n, int Lmax, int has_mix,
+                           hipStream_t s);
+void launch_ensemble_gather(const float* cands, const int* lens, const int* perm, const int* anchor, const int* best,
+                            float* out, int B, int K, int n, int Lmax, int mode, hipStream_t s);

@@ -34,6 +34,16 @@ def plan_files(headers, fs: int, hop: int, batch: int = 64, long_after: Optional
             "long": long}
 
 
+def files_per_batch(batch: int, samples: Optional[int] = None) -> int:
+    """Files of one separate_batch call of `batch` rows when every file is drawn `samples` times: batch // samples
+    (default None: one draw, `batch` files).  A batch too small for one file is refused."""
+    if samples is None:
+        return int(batch)
+    if int(batch) < int(samples):
+        raise ValueError(f"batch = {batch} < samples = {samples}: a batch holds batch // samples files")
+    return int(batch) // int(samples)
+
+
 def parse_inputs(paths) -> list:
     """Every header, before any device work: a file wavio refuses raises its ValueError, and so do two inputs with the
     same stem (they would be written to the same output files)."""
@@ -78,7 +88,8 @@ def _padded(rows, device):
 
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
-                   window=None, overlap=None, long_mode="stitch", seed=None, refine=None, **sampler_kwargs) -> list:
+                   window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
+                   **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     eng = model.engine
     fs = model._model_rate("separate_files")
@@ -91,7 +102,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     paths = [os.fspath(p) for p in paths]
     headers = parse_inputs(paths)
     hop = model.hop_length
-    plan = plan_files(headers, fs, hop, batch, long_after)
+    ens = {} if samples is None else dict(samples=native.check_samples(samples, combine), combine=combine)
+    plan = plan_files(headers, fs, hop, files_per_batch(batch, samples), long_after)
+    if ens and plan["long"]:
+        raise ValueError(f"{paths[plan['long'][0]]} is longer than long_after = {long_after} s and would be separated as "
+                         f"windows: samples= has no separate_long form")
     if plan["long"] and window is None:
         window = max(4 * hop, int(float(long_after) * fs) // (4 * hop) * (4 * hop))
     out_dir = os.fspath(out_dir)
@@ -138,7 +153,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx])
         at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed) + k)
-        est, *_ = model.separate_batch(at_fs, codec=codec, **kw)
+        est, *_ = model.separate_batch(at_fs, codec=codec, **ens, **kw)
         finish(idx, at_fs, est, k)
     if plan["long"]:
         idx = plan["long"]

@@ -338,18 +338,20 @@ class LatentDiffSep:
         return out
 
     @torch.no_grad()
-    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs, refine=None):
+    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs, refine=None, **ens):
         """`separate` of mix [B, C, L] (or [B, L]) at `sample_rate`: to the model's rate (mixed down), the existing
-        call (with `refine`, there), every estimate back to `sample_rate` and cropped to L."""
+        call (with `refine` and the `samples` keywords `ens`, there), every estimate back to `sample_rate` and cropped
+        to L."""
         fs, eng = self._model_rate("sample_rate="), self.engine
         mix = mix[:, None] if mix.dim() == 2 else mix
         L = int(mix.shape[-1])
         m = eng.resample(mix, sample_rate, fs, downmix=True)
-        est, *others = self.separate(m, target_dim, refine=refine, **kwargs)
+        est, *others = self.separate(m, target_dim, refine=refine, **ens, **kwargs)
         return (eng.resample(est, fs, sample_rate)[..., :L], *others)
 
     @torch.no_grad()
-    def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, **kwargs):
+    def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
+                 return_info=False, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -359,7 +361,24 @@ class LatentDiffSep:
         the mono mixture at the model's rate after the decoder and before any resampling back.  Where the estimates
         are longer than the mixture (without target_dim the codec hands back whole hops) the mixture is zero-extended
         to their length, which is what the encoder saw; shorter estimates are refused.  Refused with latent=True:
-        there is no waveform mixture."""
+        there is no waveform mixture.
+        samples (default None: one draw, the call is what it was): K in [1, 16] -- every mixture is repeated K times
+        item-major (row b K + k) and goes through this call once under the one seed (the device generator gives every
+        batch row its own draws; explicit vae_noise / noise then have B K rows), and the K candidates of each mixture
+        are aligned and combined on the device (Engine.ensemble_combine, combine = "mean", "median", "best" or
+        "medoid") against the mono mixture at the model's rate, zero-extended or cut to the estimates' length --
+        after the decoder and before refine and any resampling back.  return_info=True appends the info dict of
+        Engine.ensemble_combine to what is returned.  Refused with latent=True and with intermediate."""
+        ens = {}
+        if samples is not None:
+            ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
+            if latent:
+                raise ValueError("samples= combines waveforms: with latent=True there is nothing to decode (combine "
+                                 "flattened latents with Engine.ensemble_combine)")
+            if kwargs.get("intermediate"):
+                raise ValueError("samples= does not go with intermediate: the per-step states are not combined")
+        elif return_info:
+            raise ValueError("return_info=True hands back the info of the combine: it needs samples=")
         opts = native.refine_options(refine)
         if opts is not None and latent:
             raise ValueError("refine= applies to waveforms: with latent=True there is no waveform mixture to refine "
@@ -367,14 +386,22 @@ class LatentDiffSep:
         if sample_rate is not None:
             if latent:
                 raise ValueError("sample_rate= applies to waveforms: a latent has no sample rate to convert")
-            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs, refine=refine)
+            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs, refine=refine, **ens)
         if opts is not None:
-            est, *others = self.separate(mix, target_dim, **kwargs)
+            est, *others = self.separate(mix, target_dim, **ens, **kwargs)
             short = int(est.shape[-1]) - int(mix.shape[-1])
             if short < 0:
                 raise ValueError(f"refine=: the estimates ({est.shape[-1]} samples) are shorter than the mixture "
                                  f"({mix.shape[-1]}); target_dim must not cut the mixture")
             return (self.engine.mask_refine(torch.nn.functional.pad(mix, (0, short)), est, **opts), *others)
+        if ens:
+            B, K = int(mix.shape[0]), ens["samples"]
+            est, *others = self.separate(mix.repeat_interleave(K, 0), target_dim, **kwargs)
+            Le = int(est.shape[-1])
+            m = mix.reshape(B, -1)[:, :Le].to(device=est.device, dtype=torch.float32)
+            m = torch.nn.functional.pad(m, (0, Le - int(m.shape[-1])))
+            res = self.engine.ensemble_combine(est.reshape(B, K, -1, Le), m, mode=combine, return_info=return_info)
+            return (res[0], *others, res[1]) if return_info else (res, *others)
         if not latent:
             # the reference draws fresh VAE posterior noise on every call (bottleneck.py:57-83): without an explicit
             # seed, so does this (an explicit seed makes the whole call reproducible)
@@ -389,8 +416,8 @@ class LatentDiffSep:
         return (est, *others)
 
     @torch.no_grad()
-    def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None,
-                       **sampler_kwargs):
+    def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
+                       combine="mean", return_info=False, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -404,18 +431,44 @@ class LatentDiffSep:
         vae_noise and noise keep their meaning at the model's rate -- and every estimate comes back at its item's own
         rate, cropped to the item's sample count (Engine.from_model_rate).
         refine (default None: off), as in `separate`: one Engine.mask_refine call on the padded batch with the items'
-        lengths, at the model's rate, before any resampling back; each item gets the bits it gets alone."""
+        lengths, at the model's rate, before any resampling back; each item gets the bits it gets alone.
+        samples (default None: one draw), combine, return_info as in `separate`: every mixture is repeated K times
+        item-major, the B K rows go through this call once, and one Engine.ensemble_combine call on the padded
+        candidates with the items' lengths combines them against the mixtures, before refine and resampling back."""
         eng = self.engine
+        ens = {}
+        if samples is not None:
+            ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
+            if sampler_kwargs.get("intermediate"):
+                raise ValueError("samples= does not go with intermediate: the per-step states are not combined")
+        elif return_info:
+            raise ValueError("return_info=True hands back the info of the combine: it needs samples=")
         opts = native.refine_options(refine)
         if sample_rates is not None:
             fs = self._model_rate("sample_rates=")
             rates = [int(sample_rates)] * len(mixes) if isinstance(sample_rates, int) else [int(r) for r in sample_rates]
             at_fs = eng.to_model_rate(list(mixes), rates, fs)
-            est, *others = self.separate_batch(at_fs, target_dims, codec, refine=refine, **sampler_kwargs)
+            est, *others = self.separate_batch(at_fs, target_dims, codec, refine=refine, **ens, **sampler_kwargs)
             return (eng.from_model_rate(est, rates, fs, [int(m.shape[-1]) for m in mixes]), *others)
         if opts is not None:
-            est, *others = self.separate_batch(mixes, target_dims, codec, **sampler_kwargs)
+            est, *others = self.separate_batch(mixes, target_dims, codec, **ens, **sampler_kwargs)
             return (eng.mask_refine(list(mixes), est, **opts), *others)
+        if ens:
+            B, K = len(mixes), ens["samples"]
+            dims = None if target_dims is None else [d for d in target_dims for _ in range(K)]
+            est, *others = self.separate_batch([m for m in mixes for _ in range(K)], dims, codec, **sampler_kwargs)
+            ln = [int(est[b * K].shape[-1]) for b in range(B)]
+            cands = torch.zeros((B, K, int(est[0].shape[0]), max(ln)), device=eng.device, dtype=torch.float32)
+            mp = torch.zeros((B, max(ln)), device=eng.device, dtype=torch.float32)
+            for b, m in enumerate(mixes):
+                v = min(ln[b], int(m.shape[-1]))
+                mp[b, :v] = m.reshape(-1)[:v]
+                for k in range(K):
+                    cands[b, k, :, :ln[b]] = est[b * K + k]
+            res = eng.ensemble_combine(cands, mp, lens=ln, mode=combine, return_info=return_info)
+            out = res[0] if return_info else res
+            outs = [out[b, :, :ln[b]] for b in range(B)]
+            return (outs, *others, res[1]) if return_info else (outs, *others)
         native.check_codec_mode(codec)
         native.check_ragged(eng.cfg.score_kind, [1] * len(mixes), len(mixes), 1)
         kwargs = dict(sampler_kwargs)
@@ -511,7 +564,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
-                       **sampler_kwargs):
+                       samples=None, combine="mean", **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -529,12 +582,15 @@ class LatentDiffSep:
         (the files written), "clipped" (per speaker, the samples that were clamped), "alpha" (per speaker, with
         rescale), "batch" (the batch index, or "long").  DiT score network only (separate_batch's restriction).
         refine (default None: off), as in `separate`: per batch the order is separate -> refine (Engine.mask_refine
-        against the mono mixtures at the model's rate) -> rescale -> back to each file's rate -> quantise."""
+        against the mono mixtures at the model's rate) -> rescale -> back to each file's rate -> quantise.
+        samples (default None: one draw), combine as in `separate_batch`, which gets them: a batch then holds
+        batch // samples files, and a file that would go through separate_long (long_after) is refused before any
+        device work -- candidate windows are a different problem."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
-                                    seed=seed, refine=refine, **sampler_kwargs)
+                                    seed=seed, refine=refine, samples=samples, combine=combine, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -40,6 +40,7 @@ EXPORTS = [
     "dsn_pcm_decode", "dsn_pcm_encode", "dsn_scale_output",
     "dsn_bss_eval", "dsn_bss_eval_plan",
     "dsn_mask_refine",
+    "dsn_ensemble_combine",
 ]
 
 
@@ -637,6 +638,47 @@ def check_mask_refine(mix_shape, est_shape, lens=None, n_fft=512, hop=128, power
     return (B, n, L), (None if lens is None else ln), n_fft, int(hop), int(power), eps
 
 
+ENSEMBLE_MODES = {"mean": 0, "median": 1, "best": 2, "medoid": 3}                  # DSN_ENSEMBLE_*
+ENSEMBLE_MAX_K, ENSEMBLE_MAX_SRC = 16, 4
+
+
+def check_samples(samples, combine="mean") -> int:
+    """The `samples` / `combine` keywords of the separation entry points: samples an int in [1, 16], combine one of
+    ENSEMBLE_MODES, both refused by name otherwise.  -> samples as an int"""
+    if isinstance(samples, bool) or int(samples) != samples or not 1 <= int(samples) <= ENSEMBLE_MAX_K:
+        raise ValueError(f"samples = {samples!r} is not an int in [1, {ENSEMBLE_MAX_K}]")
+    if combine not in ENSEMBLE_MODES:
+        raise ValueError(f"combine must be one of {sorted(ENSEMBLE_MODES)} (got {combine!r})")
+    return int(samples)
+
+
+def ensemble_checks(cands, mix=None, lens=None, mode="mean") -> tuple:
+    """The refusals of dsn_ensemble_combine (include/ditsep_hip.h), raised by name before the library is touched: an
+    unknown mode; cands that is not a float32 [B, K, n, L]; K outside [1, 16] or n outside [1, 4]; mix that is not a
+    float32 [B, L] or [B, 1, L] of the same B and L; mode "best" without mix; not one lens entry per item, or an entry
+    below 1 or above L.  -> ((B, K, n, L), lens as a list or None, the DSN_ENSEMBLE_* mode)"""
+    if mode not in ENSEMBLE_MODES:
+        raise ValueError(f"ensemble_combine: mode must be one of {sorted(ENSEMBLE_MODES)} (got {mode!r})")
+    shape = tuple(int(v) for v in cands.shape)
+    if len(shape) != 4 or cands.dtype != torch.float32 or min(shape[0], shape[3]) < 1:
+        raise ValueError(f"ensemble_combine: cands must be float32 [B, K, n, L] (got {cands.dtype} {shape})")
+    B, K, n, L = shape
+    if K < 1 or K > ENSEMBLE_MAX_K:
+        raise ValueError(f"ensemble_combine: K = {K} outside [1, {ENSEMBLE_MAX_K}]")
+    if n < 1 or n > ENSEMBLE_MAX_SRC:
+        raise ValueError(f"ensemble_combine: n = {n} outside [1, {ENSEMBLE_MAX_SRC}]")
+    if mix is not None:
+        ms = tuple(int(v) for v in mix.shape)
+        if ms not in ((B, L), (B, 1, L)):
+            raise ValueError(f"ensemble_combine: mix must be [B, L] or [B, 1, L] with B = {B}, L = {L} (got {ms})")
+        if mix.dtype != torch.float32:
+            raise ValueError(f"ensemble_combine: mix must be float32 (got {mix.dtype})")
+    elif mode == "best":
+        raise ValueError("ensemble_combine: mode 'best' ranks the candidates by their residual against the mixture: "
+                         "mix is None")
+    return shape, (None if lens is None else check_lens(lens, B, L)), ENSEMBLE_MODES[mode]
+
+
 PCM_ENCODINGS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5}        # DSN_PCM_*
 PCM_SAMPLE_BYTES = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8}
 PCM_OUT_ENCODINGS = ("s16", "s24", "f32")                                          # what dsn_pcm_encode writes
@@ -756,6 +798,9 @@ def load_library() -> C.CDLL:
                                  C.POINTER(DsnBssEvalOut), vp]
     lib.dsn_bss_eval_plan.argtypes = [ci, ci, ci, ci, C.c_int64, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), i64p]
     lib.dsn_mask_refine.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, ci, ci, C.c_float, vp, vp]
+    f64p = C.POINTER(C.c_double)
+    lib.dsn_ensemble_combine.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, ci, vp, i32p, i32p, i32p, f64p, f64p, f64p,
+                                         vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -1478,6 +1523,41 @@ class Engine:
                                              None if ln is None else (C.c_int32 * B)(*ln), n_fft, hop, power, eps,
                                              _ptr(out), self._stream()), "dsn_mask_refine")
         return out
+
+    # ------------------------------------------------------------------ K candidates -> one separation
+    def ensemble_combine(self, cands, mix=None, lens=None, mode="mean", return_info=False):
+        """K candidate separations of the same mixtures -> one (dsn_ensemble_combine, csrc/ensemble.hip; the definition
+        is in include/ditsep_hip.h and tests/ensemble_restatement.py).  cands [B, K, n, L] float32 -- K draws of the
+        sampler, or any rows: flattened latents [B, K, n, D T] go with mix=None --, mix [B, L] or [B, 1, L] or None ->
+        out [B, n, L].  The candidates come in arbitrary source order: they are aligned to an anchor candidate (the
+        one the others agree with most) by the permutations that maximise the inner products, then combined per
+        sample: mode "mean" (float32 sum in candidate order, its rounding errors given back, / K), "median", "best" (the candidate with the
+        smallest mixture residual |mix - sum_i cand_i|^2; needs mix) or "medoid" (the anchor).  lens: a ragged batch
+        padded to L -- nothing at or past lens[b] is read, out is zero there, each item gets the bits it gets alone.
+        return_info=True: (out, info) with, on the host, "perm" [B, K, n] (slot i of candidate k is its source
+        perm[b, k, i]), "anchor" [B], "best" [B] (-1 without mix), "resid_db" [B, K] (the relative residual energy;
+        below about L 2^-53 it is rounding), "agree_db" [B, K, n] (the SI-SDR of each aligned row against the anchor's:
+        +inf for the anchor itself) and "gram" [B, R, R] float64, R = K n (+ 1, the mixture's row last).  Not a
+        trained step: what it does to separation quality is unmeasured.  Needs no score network and no codec; two
+        calls give identical bits."""
+        (B, K, n, L), ln, code = ensemble_checks(cands, mix, lens, mode)
+        cands = _dev32(cands, self.device)
+        mix = None if mix is None else _dev32(mix, self.device).reshape(B, L)
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        info, R = None, K * n + (mix is not None)
+        if return_info:
+            info = {"perm": torch.zeros((B, K, n), dtype=torch.int32), "anchor": torch.zeros(B, dtype=torch.int32),
+                    "best": torch.zeros(B, dtype=torch.int32), "resid_db": torch.zeros((B, K), dtype=torch.float64),
+                    "agree_db": torch.zeros((B, K, n), dtype=torch.float64),
+                    "gram": torch.zeros((B, R, R), dtype=torch.float64)}
+        host = lambda k, t: None if info is None else C.cast(C.c_void_p(info[k].data_ptr()), C.POINTER(t))
+        self._check(self.lib.dsn_ensemble_combine(
+            self.ctx, _ptr(cands), _ptr(mix), B, K, n, L, None if ln is None else (C.c_int32 * B)(*ln), code, _ptr(out),
+            host("perm", C.c_int32), host("anchor", C.c_int32), host("best", C.c_int32), host("resid_db", C.c_double),
+            host("agree_db", C.c_double), host("gram", C.c_double), self._stream()), "dsn_ensemble_combine")
+        if info is None:
+            return out
+        return out, {k: (v.long() if v.dtype == torch.int32 else v) for k, v in info.items()}
 
     def to_model_rate(self, clips, rates, fs: int):
         """Clips of any rate, channel count and length at the model's rate `fs`, mixed down to mono: `clips` is a list

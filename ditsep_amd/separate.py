@@ -63,6 +63,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--refine-nfft", type=int, default=512, help="Window of the masks, samples at the model's rate")
     p.add_argument("--refine-hop", type=int, default=128, help="Hop of the masks (window / 2, / 4 or / 8)")
     p.add_argument("--refine-power", type=int, default=2, choices=[1, 2], help="Exponent of the mask magnitudes")
+    p.add_argument("--samples", type=int, default=None,
+                   help="Draw this many candidate separations per file (1 to 16) and combine them on the device "
+                        "(default: one draw)")
+    p.add_argument("--combine", default="mean", choices=["mean", "median", "best", "medoid"],
+                   help="How the candidates of --samples are combined")
     return p
 
 
@@ -122,7 +127,8 @@ def main(argv=None) -> int:
             records = model.separate_files(paths, args.output_dir, batch=args.batch, encoding=args.encoding,
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
-                                           refine=refine_of(args), denoise=args.denoise, **kw)
+                                           refine=refine_of(args), samples=args.samples, combine=args.combine,
+                                           denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2

@@ -564,6 +564,53 @@ int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_
 int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int n, int Lmax, const int32_t* lens,
                     int n_fft, int hop, int power, float eps, float* out, void* stream);
 
+/* Ensemble combine: K candidate separations of the same mixtures (K draws of the diffusion sampler) -> one separation
+ * (csrc/ensemble.hip, restated in float64 in tests/ensemble_restatement.py).  A definition, not a trained step; nothing
+ * calls it unless asked to.  cands [B][K][n][Lmax], mix [B][Lmax] or NULL, out [B][n][Lmax] fp32 (device),
+ * 1 <= K <= 16, 1 <= n <= 4.  lens (HOST, [B], or NULL: every item is Lmax long): item b has L_b = lens[b] samples;
+ * nothing at or past lens[b] is read (the padding may hold NaN) and out is written as zero there.  Per item:
+ *   Gram       the K n candidate rows, row (k, i) = k n + i, plus the mixture's row m = K n when mix is given (R rows):
+ *              G[p][q] = sum_{t < L_b} x_p[t] x_q[t].  fp32 x fp32 products are exact in fp64 and are summed in fp64 in a
+ *              fixed order over tiles of 2048 samples counted from the item's own start: per thread in stride order, a
+ *              fixed tree, the tile partials in index order; plain stores, no atomics.  An item has the same bits alone,
+ *              at any batch position and under any padding.  |G - exact| <= L_b 2^-53 sum_t |x_p[t]| |x_q[t]|.
+ *   alignment  S[a][k] = max over the n! permutations pi of sum_i G[(a, i)][(k, pi(i))] (raw inner products, the window
+ *              stitch's rule; ties go to the lexicographically first permutation).  S is symmetric: it is formed for
+ *              a < k and used for (k, a) as well, so with K = 2 the two totals are one number.  The anchor a* = argmax_a
+ *              sum_{k != a} S[a][k] (k ascending; ties to the lowest index; 0 for K = 1, 2).  perm[k] is the maximiser for
+ *              (a*, k) and perm[a*] the identity: slot i of candidate k is its source perm[k][i].
+ *   info       E_k = (G[m][m] - 2 sum_i G[m][(k, i)]) + sum_i sum_j G[(k, i)][(k, j)] (m the mixture's row; i, then j,
+ *              ascending) is |mix - sum_i cand_k,i|^2 and resid_db[k] = 10 log10(max(E_k, 0) / G[m][m]); best = argmin_k
+ *              E_k, ties to the lowest index.  E_k is a difference of sums of size |mix|^2: a relative residual energy
+ *              below about L_b 2^-53 (-111 dB at 64000 samples) is rounding, not signal -- a candidate that sums exactly to
+ *              the mixture reports -inf or a figure below that floor.  A silent mixture gives NaN.  Without mix best is
+ *              -1 and resid_db NaN.  agree_db[k][i] is the SI-SDR of row c = (k, perm[k][i]) against the anchor's row
+ *              a = (a*, i): 10 log10(g^2 / max(G[a][a] G[c][c] - g^2, 0)) with g = G[a][c]; NaN when either energy is 0,
+ *              otherwise +inf for k = a*.
+ *   combine    one gather launch over the aligned rows c_k,i = cands[k][perm[k][i]], fp32, contraction off:
+ *              DSN_ENSEMBLE_MEAN    s = ((c_0,i + c_1,i) + ...) + c_K-1,i in candidate order, every addition's rounding
+ *                                   error (Knuth's two-sum, six fp32 operations, exact) added into e in the same
+ *                                   order; then (s + e) / float(K), s / float(K) where e is 0 (K = 1: a copy).  The bare sequential sum does
+ *                                   not return x from 8 or 16 copies of x (5 x, 6 x, 7 x each round); this one
+ *                                   does for K = 2, 4, 8, 16: e is exact there and s + e = K x.  A sum that
+ *                                   overflows gives NaN, not inf.
+ *              DSN_ENSEMBLE_MEDIAN  the middle of the K values per sample (stable order); even K: (lo + hi) * 0.5f of
+ *                                   the two middle values
+ *              DSN_ENSEMBLE_BEST    c_best,i (refused without mix)
+ *              DSN_ENSEMBLE_MEDOID  c_a*,i
+ * 16-byte loads and stores where Lmax is a multiple of 4 and the bases are aligned, scalar ones otherwise, with the
+ * same bits.  Every *_out is a HOST array or NULL: perm_out [B][K][n], anchor_out / best_out [B], resid_db_out [B][K],
+ * agree_db_out [B][K][n], gram_out [B][R][R]; with any of them the stream is synchronised.  The call uploads `lens` when
+ * it is given and differs from the last upload, and then synchronises the stream.  Needs no score network and no codec;
+ * two calls give identical bits.
+ * DSN_EINVAL by name, before anything is allocated or launched: cands or out null; B outside [1, 65535]; K outside
+ * [1, 16]; n outside [1, 4]; Lmax outside [1, 2^30]; an unknown mode; DSN_ENSEMBLE_BEST without mix; lens[b] outside
+ * [1, Lmax]; out overlapping cands. */
+enum { DSN_ENSEMBLE_MEAN = 0, DSN_ENSEMBLE_MEDIAN = 1, DSN_ENSEMBLE_BEST = 2, DSN_ENSEMBLE_MEDOID = 3 };
+int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int B, int K, int n, int Lmax,
+                         const int32_t* lens, int mode, float* out, int32_t* perm_out, int32_t* anchor_out,
+                         int32_t* best_out, double* resid_db_out, double* agree_db_out, double* gram_out, void* stream);
+
 /* The first and the last step of separating audio files, on the device: the `data` payloads of WAV files to fp32 and
  * fp32 back to payloads, and the reference's output gain (src/inference/separate.py:73-78).  Restated in numpy in
  * tests/pcm_restatement.py.  All three need no score network and no codec.  Every per-item table (offset, frames,
