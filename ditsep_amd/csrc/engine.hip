@@ -3298,46 +3298,71 @@ int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const
   });
 }
 
+// dsn_pcm_encode (C = 1, channels null) and dsn_pcm_encode_frames: x [R][C][Lmax] -> interleaved payloads
+static void pcm_encode_rows(dsn_ctx* ctx, const char* who, const float* x, int R, int C, int Lmax, const int32_t* lens,
+                            const int32_t* channels, int encoding, void* bytes, int64_t nbytes, const int64_t* offset,
+                            int64_t* clipped, void* stream) {
+  if (!x || !bytes) fail(DSN_EINVAL, "%s: x or bytes is null", who);
+  if (!offset) fail(DSN_EINVAL, "%s: offset is null", who);
+  if (R < 1 || R > 65535) fail(DSN_EINVAL, "%s: R = %d outside [1, 65535]", who, R);
+  if (C < 1) fail(DSN_EINVAL, "%s: C = %d < 1", who, C);
+  if (Lmax < 1) fail(DSN_EINVAL, "%s: Lmax = %d < 1", who, Lmax);
+  if (encoding != DSN_PCM_S16 && encoding != DSN_PCM_S24 && encoding != DSN_PCM_F32)
+    fail(DSN_EINVAL, "%s: encoding = %d is none of DSN_PCM_S16, DSN_PCM_S24, DSN_PCM_F32", who, encoding);
+  const int w = pcm_sample_bytes(encoding);
+  std::vector<PcmItem> items((size_t)R);
+  std::vector<std::pair<long, int>> order((size_t)R);
+  std::vector<long> need((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    const int len = lens ? lens[r] : Lmax, ch = channels ? channels[r] : C;
+    if (len < 1 || len > Lmax)
+      fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, r, len, Lmax);
+    if (ch < 1 || ch > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, r, ch, C);
+    if ((long)ch * w > DSN_PCM_MAX_FRAME_BYTES)
+      fail(DSN_EINVAL, "%s: row %d has frames of %ld bytes, more than DSN_PCM_MAX_FRAME_BYTES = %d", who, r,
+           (long)ch * w, DSN_PCM_MAX_FRAME_BYTES);
+    need[r] = (long)len * ch * w;
+    if (offset[r] < 0 || nbytes < need[r] || offset[r] > nbytes - need[r])
+      fail(DSN_EINVAL, "%s: row %d takes bytes [%ld, %ld), outside [0, nbytes = %ld)", who, r, (long)offset[r],
+           (long)offset[r] + need[r], (long)nbytes);
+    items[r] = PcmItem{(long)offset[r], len, ch, encoding, 0};
+    order[r] = {(long)offset[r], r};
+  }
+  std::sort(order.begin(), order.end());
+  for (int k = 1; k < R; ++k) {
+    const int p = order[k - 1].second, q = order[k].second;
+    if (order[k - 1].first + need[p] > order[k].first)
+      fail(DSN_EINVAL, "%s: the payloads of rows %d and %d overlap", who, p, q);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const PcmItem* d = (const PcmItem*)upload_table(ctx, "pcm_rows", items.data(), sizeof(PcmItem) * items.size(), st);
+  unsigned long long* cnt = ctx->wsbuf<unsigned long long>("pcm_clipped", R);
+  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)R, st));
+  ctx->prof_launch(C == 1 && !channels ? "pcm_encode" : "pcm_encode_frames", (4.0 + w) * R * C * Lmax, st, [&] {
+    launch_pcm_encode(x, d, R, C, Lmax, encoding, (unsigned char*)bytes, cnt, st);
+  });
+  HIPCHK(hipGetLastError());
+  if (!clipped) return;
+  HIPCHK(hipMemcpyAsync(clipped, cnt, sizeof(int64_t) * (size_t)R, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+}
+
 int dsn_pcm_encode(dsn_ctx* ctx, const float* x, int R, int Lmax, const int32_t* lens, int encoding, void* bytes,
                    int64_t nbytes, const int64_t* offset, int64_t* clipped, void* stream) {
   return guarded(ctx, [&] {
     const char* who = "dsn_pcm_encode";
     if (!x || !bytes) fail(DSN_EINVAL, "%s: x or bytes is null", who);
     if (!lens || !offset) fail(DSN_EINVAL, "%s: lens or offset is null", who);
-    if (R < 1 || R > 65535) fail(DSN_EINVAL, "%s: R = %d outside [1, 65535]", who, R);
-    if (Lmax < 1) fail(DSN_EINVAL, "%s: Lmax = %d < 1", who, Lmax);
-    if (encoding != DSN_PCM_S16 && encoding != DSN_PCM_S24 && encoding != DSN_PCM_F32)
-      fail(DSN_EINVAL, "%s: encoding = %d is none of DSN_PCM_S16, DSN_PCM_S24, DSN_PCM_F32", who, encoding);
-    const int w = pcm_sample_bytes(encoding);
-    std::vector<PcmItem> items((size_t)R);
-    std::vector<std::pair<long, int>> order((size_t)R);
-    for (int r = 0; r < R; ++r) {
-      if (lens[r] < 1 || lens[r] > Lmax)
-        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, r, (int)lens[r], Lmax);
-      const long need = (long)lens[r] * w;
-      if (offset[r] < 0 || nbytes < need || offset[r] > nbytes - need)
-        fail(DSN_EINVAL, "%s: row %d takes bytes [%ld, %ld), outside [0, nbytes = %ld)", who, r, (long)offset[r],
-             (long)offset[r] + need, (long)nbytes);
-      items[r] = PcmItem{(long)offset[r], lens[r], 1, encoding, 0};
-      order[r] = {(long)offset[r], r};
-    }
-    std::sort(order.begin(), order.end());
-    for (int k = 1; k < R; ++k) {
-      const int p = order[k - 1].second, q = order[k].second;
-      if (order[k - 1].first + (long)lens[p] * w > order[k].first)
-        fail(DSN_EINVAL, "%s: the payloads of rows %d and %d overlap", who, p, q);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PcmItem* d = (const PcmItem*)upload_table(ctx, "pcm_rows", items.data(), sizeof(PcmItem) * items.size(), st);
-    unsigned long long* cnt = ctx->wsbuf<unsigned long long>("pcm_clipped", R);
-    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)R, st));
-    ctx->prof_launch("pcm_encode", 4.0 * R * Lmax + (double)w * R * Lmax, st, [&] {
-      launch_pcm_encode(x, d, R, Lmax, encoding, (unsigned char*)bytes, cnt, st);
-    });
-    HIPCHK(hipGetLastError());
-    if (!clipped) return;
-    HIPCHK(hipMemcpyAsync(clipped, cnt, sizeof(int64_t) * (size_t)R, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    pcm_encode_rows(ctx, who, x, R, 1, Lmax, lens, nullptr, encoding, bytes, nbytes, offset, clipped, stream);
+  });
+}
+
+int dsn_pcm_encode_frames(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens,
+                          const int32_t* channels, int encoding, void* bytes, int64_t nbytes, const int64_t* offset,
+                          int64_t* clipped, void* stream) {
+  return guarded(ctx, [&] {
+    pcm_encode_rows(ctx, "dsn_pcm_encode_frames", x, R, C, Lmax, lens, channels, encoding, bytes, nbytes, offset,
+                    clipped, stream);
   });
 }
 
@@ -3365,6 +3390,69 @@ int dsn_scale_output(dsn_ctx* ctx, const float* mix, const float* sep, int B, in
     HIPCHK(hipGetLastError());
     if (!alpha_out) return;
     HIPCHK(hipMemcpyAsync(alpha_out, alpha, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
+// ---- multichannel stems from mono estimates (maskrefine.hip; include/ditsep_hip.h states the definition)
+int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
+              const int32_t* channels, int mode, int n_fft, int hop, int power, float eps, float reg, float* out,
+              double* info_R, double* info_den, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_stems";
+    if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
+    if (mode != DSN_STEMS_MASK && mode != DSN_STEMS_WIENER)
+      fail(DSN_EINVAL, "%s: mode = %d is not one of 0 (DSN_STEMS_MASK), 1 (DSN_STEMS_WIENER)", who, mode);
+    const int wiener = mode == DSN_STEMS_WIENER, Cmax = wiener ? STEMS_WIENER_MAX_CH : STEMS_MASK_MAX_CH;
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (C < 1 || C > Cmax)
+      fail(DSN_EINVAL, "%s: C = %d outside [1, %d] (%s)", who, C, Cmax,
+           wiener ? "DSN_STEMS_WIENER solves 1 x 1 and 2 x 2 systems" : "DSN_STEMS_MASK");
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
+    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
+      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
+    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
+    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
+    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
+    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
+    const int need = n_fft / 2 + 1;
+    for (int b = 0; b < B; ++b) {
+      const int len = lens ? lens[b] : Lmax;
+      if (len < need || len > Lmax)
+        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
+             "reflection must reach the item)", who, b, len, need, Lmax, need);
+      if (channels && (channels[b] < 1 || channels[b] > C))
+        fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, (int)channels[b], C);
+    }
+    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    const size_t row = sizeof(float) * (size_t)B * Lmax;
+    if ((o0 < m0 + row * C && m0 < o0 + row * n * C) || (o0 < e0 + row * n && e0 < o0 + row * n * C))
+      fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int *dlens = nullptr, *dch = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "stems_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    if (channels) dch = (const int*)upload_table(ctx, "stems_channels", channels, sizeof(int32_t) * (size_t)B, st);
+    const size_t bins = (size_t)n_fft / 2 + 1, nR = (size_t)B * n * bins * C * C * 2, nd = (size_t)B * n * bins;
+    double *part = nullptr, *R = nullptr, *den = nullptr;
+    if (wiener) {
+      part = ctx->wsbuf<double>("stems_part", (size_t)B * stems_stat_spans(n_fft, hop, Lmax) * n * 5 * bins);
+      R = ctx->wsbuf<double>("stems_R", nR + nd);
+      den = R + nR;
+    }
+    ctx->prof_launch(wiener ? "stems_wiener" : "stems_mask", 4.0 * (double)B * Lmax * (C + n + (double)n * C), st, [&] {
+      launch_stems(mix, est, dlens, dch, out, part, R, den, B, C, n, Lmax, wiener, n_fft, hop, power, eps, reg, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!info_R && !info_den) return;
+    if (info_R) {
+      if (wiener) HIPCHK(hipMemcpyAsync(info_R, R, sizeof(double) * nR, hipMemcpyDeviceToHost, st));
+      else std::fill(info_R, info_R + nR, 0.0);
+    }
+    if (info_den) {
+      if (wiener) HIPCHK(hipMemcpyAsync(info_den, den, sizeof(double) * nd, hipMemcpyDeviceToHost, st));
+      else std::fill(info_den, info_den + nd, 0.0);
+    }
     HIPCHK(hipStreamSynchronize(st));
   });
 }

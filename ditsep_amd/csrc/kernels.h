@@ -375,8 +375,8 @@ void launch_resample(const float* x, const int* lens, const float* taps, const i
 // ---- WAV payloads and the output gain (pcm.hip) -------------------------------------------------------------
 struct PcmItem {      // one item of a decode call, or one row of an encode call
   long offset;        // its first byte in the byte buffer
-  int frames;         // frames (decode) or samples (encode)
-  int channels, enc;  // (decode only) DSN_PCM_*
+  int frames;         // frames
+  int channels, enc;  // enc: (decode only) DSN_PCM_*
   int pad;
 };
 // bytes per sample of DSN_PCM_U8 .. DSN_PCM_F64; 0 for anything else
@@ -387,9 +387,9 @@ long scale_output_tiles(int L);   // tiles the gain's sum launch cuts a row of L
 // bytes [nbytes] -> out [B][Cout][Lmax] by items [B] (device); max_frame_bytes: the widest frame among them (LDS)
 void launch_pcm_decode(const unsigned char* bytes, long nbytes, const PcmItem* items, int B, int downmix, float* out,
                        int Cout, int Lmax, int max_frame_bytes, hipStream_t s);
-// x [R][Lmax] -> row r's items[r].frames samples as `enc` from bytes + items[r].offset; clipped [R] (device, zeroed
-// by the caller) is added to with integer atomics
-void launch_pcm_encode(const float* x, const PcmItem* items, int R, int Lmax, int enc, unsigned char* bytes,
+// x [R][C][Lmax] -> row r's items[r].frames frames of its first items[r].channels channels, interleaved, as `enc` from
+// bytes + items[r].offset; clipped [R] (device, zeroed by the caller) is added to with integer atomics
+void launch_pcm_encode(const float* x, const PcmItem* items, int R, int C, int Lmax, int enc, unsigned char* bytes,
                        unsigned long long* clipped, hipStream_t s);
 // part [B n][tiles][2] = the fp64 sums over tile c of mix sep and sep^2 + 1e-10 (t < lens[b]; tiles past it untouched);
 // alpha [B n] = float(sum_c part[.][c][0] / sum_c part[.][c][1]) over the row's own ceil(lens[b] / tile) tiles;
@@ -423,6 +423,17 @@ void launch_stitch_gather(const float* chunks, const int* perm, const float* fal
 bool mask_refine_fft_ok(int nfft);
 void launch_mask_refine(const float* mix, const float* est, const int* lens, float* out, int B, int n, int Lmax,
                         int nfft, int hop, int power, float eps, hipStream_t s);
+// Multichannel stems (dsn_stems): mix [B][C][Lmax], est [B][n][Lmax], out [B][n][C][Lmax], lens / chans [B] (device) or
+// null.  wiener == 0: the launch above with a grid dimension over the channel, C <= STEMS_MASK_MAX_CH; part, R and den
+// are not touched.  wiener != 0 (C <= STEMS_WIENER_MAX_CH), three launches: fp64 partials part [B][stems_stat_spans]
+// [n][5][bins] over the frames each workgroup owns, R [B][n][bins][C][C] complex and den [B][n][bins] from them in
+// workgroup order, and the per-bin solve inside the filter launch.  bins = nfft / 2 + 1.
+#define STEMS_MASK_MAX_CH 8
+#define STEMS_WIENER_MAX_CH 2
+int stems_stat_spans(int nfft, int hop, int Lmax);
+void launch_stems(const float* mix, const float* est, const int* lens, const int* chans, float* out, double* part,
+                  double* R, double* den, int B, int C, int n, int Lmax, int wiener, int nfft, int hop, int power,
+                  float eps, float reg, hipStream_t s);
 
 // ---- ensemble combine (ensemble.hip) -----------------------------------------------------------------------------
 // cands [B][K][n][Lmax], mix [B][Lmax] or null, out [B][n][Lmax] fp32, lens [B] (device) or null, K <= ENSEMBLE_MAX_K,

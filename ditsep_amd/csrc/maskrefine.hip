@@ -27,6 +27,20 @@
 // point contraction off and the fused multiply-adds written out, whichever workgroup and frame slot computes it --,
 // every sample adds its frames in increasing frame order starting from +0, and there are no atomics.  So the result
 // does not depend on SPAN, on the batch position or on the other items, and two calls give identical bits.
+//
+// dsn_stems (multichannel stems from mono estimates) runs the same kernel in three modes:
+//   MR_MASK    the launch above with a grid dimension over the mixture's channels: workgroup (c, b, ch) filters channel
+//              ch of item b with the masks of the mono estimates and writes out[b][i][ch].  The mono call is C = 1.
+//   MR_STATS   workgroup (c, b) owns the frames [c SPAN / hop, (c + 1) SPAN / hop) of item b -- every frame has exactly
+//              one owner --, transforms its C channels and n estimates and sums, per bin, M_i^2 X X^H and v_i in fp64
+//              over its frames in increasing order: the thread that owns a bin adds one group of frames in registers
+//              and then adds that to the workgroup's own partial in global memory (plain loads and stores).
+//   (reduce)   one thread per (item, source, bin) adds the partials in workgroup order and writes R = N / d and d.
+//   MR_WIENER  as MR_MASK, but all C channels are transformed and, in place of Y = M X, the per-bin solve of the
+//              multichannel Wiener filter runs in fp64 with R read from global memory; only channel ch of the n
+//              outputs is formed, rounded once to fp32, and transformed back.
+// In every mode a frame goes through the same loads, transform and split, so X, S and M have the same bits wherever
+// they are formed.
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -37,6 +51,9 @@ constexpr int MRT = 256;                          // threads
 constexpr int MR_MAX_SRC = MASK_REFINE_MAX_SRC;
 constexpr int MR_POINTS = 1024;                   // complex points per signal in LDS: 2048 / NFFT frames at a time
 constexpr int MR_BF = (MR_MAX_SRC + 1) * (MR_POINTS / 2) / MRT;   // butterflies per thread and stage at n = 4
+constexpr int MR_BF_STEMS = (STEMS_WIENER_MAX_CH + MR_MAX_SRC) * (MR_POINTS / 2) / MRT;   // .. with C = 2 channels
+enum { MR_MASK = 0, MR_STATS = 1, MR_WIENER = 2 };
+constexpr int MR_STAT = 5;   // fp64 sums per (source, bin): N00, N11, Re N01, Im N01, d
 
 template <int NFFT>
 constexpr int mr_span() { return NFFT >= 2048 ? 4096 : 2048; }
@@ -45,19 +62,21 @@ struct MaskRefineShape {
   int n, Lmax, hop, power;
   float eps;
   int vec;   // out is 16-byte aligned and Lmax % 4 == 0: whole quads are stored at once
+  int C;     // channels of mix (and of every out[b][i]); the mono call has 1
+  float reg;
 };
 
 // `nbf` butterflies per stage = transforms * H / 2; natural order in and out.  A stage reads x[j], x[j + H / 2] of
 // every transform into registers and, after a barrier, writes the butterfly to ((j - k) << 1) + k and that + Ns,
 // k = j mod Ns.  tw[k] = exp(-2 pi i k / (2 H)).  Ends with a barrier.
-template <int H, bool INV>
+template <int H, bool INV, int BF>
 __device__ __forceinline__ void mr_fft(float2* __restrict__ base, const float2* __restrict__ tw, int nbf, int tid) {
   constexpr int LOGH = __builtin_ctz(H);
   for (int ls = 0; ls < LOGH; ++ls) {
     const int Ns = 1 << ls;
-    float2 u[MR_BF], v[MR_BF];
+    float2 u[BF], v[BF];
 #pragma unroll
-    for (int q = 0; q < MR_BF; ++q) {
+    for (int q = 0; q < BF; ++q) {
       const int bf = tid + q * MRT;
       if (bf < nbf) {
         const float2* a = base + (bf >> (LOGH - 1)) * H;
@@ -71,7 +90,7 @@ __device__ __forceinline__ void mr_fft(float2* __restrict__ base, const float2* 
     }
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < MR_BF; ++q) {
+    for (int q = 0; q < BF; ++q) {
       const int bf = tid + q * MRT;
       if (bf < nbf) {
         float2* a = base + (bf >> (LOGH - 1)) * H;
@@ -119,33 +138,122 @@ __device__ __forceinline__ void mr_store(const MaskRefineShape& q, float* __rest
   }
 }
 
-// mix [B][Lmax], est / out [B][n][Lmax], lens [B] or null.  Grid (ceil(Lmax / SPAN), B).
-// Dynamic LDS: float2 tw[H] | float2 buf[n + 1][G][H] | float win[NFFT] | float ola[n][SPAN]
-template <int NFFT>
+// The masks of bins k and km = H - k of one frame: e -> the frame's slot in the first estimate's transforms, the
+// next estimate's MR_POINTS further; t = exp(-2 pi i k / NFFT).
+__device__ __forceinline__ void mr_masks(const MaskRefineShape& q, const float2* __restrict__ e, int k, int km, float2 t,
+                                         float* mk, float* mm) {
+  const int n = q.n;
+  float ak[MR_MAX_SRC], am[MR_MAX_SRC];
+  float dk = 0.f, dm = 0.f;
+#pragma unroll
+  for (int i = 0; i < MR_MAX_SRC; ++i)
+    if (i < n) {
+      const float2* a = e + i * MR_POINTS;
+      float2 sk, sm;
+      mr_split(a[k], a[km], t, sk, sm);
+      ak[i] = mr_mag(sk, q.power);
+      am[i] = mr_mag(sm, q.power);
+      dk = i == 0 ? ak[i] : dk + ak[i];
+      dm = i == 0 ? am[i] : dm + am[i];
+    }
+  const float ne = (float)n * q.eps;
+  dk = dk + ne;
+  dm = dm + ne;
+#pragma unroll
+  for (int i = 0; i < MR_MAX_SRC; ++i)
+    if (i < n) {
+      mk[i] = (ak[i] + q.eps) / dk;
+      mm[i] = (am[i] + q.eps) / dm;
+    }
+}
+
+// One bin of the multichannel Wiener filter in fp64 (include/ditsep_hip.h, dsn_stems): X [Cb] the mixture's channels,
+// M [n] the masks, R -> R_0 of this bin ([C][C] complex as double pairs, source stride rs doubles); Y [n] = channel
+// `co` of the n outputs, rounded once.  Cb is 1 or 2; Cb = 1 reads R[0] only.
+__device__ __forceinline__ void mr_wiener_bin(const MaskRefineShape& q, int Cb, int co, const float2* X, const float* M,
+                                              const double* __restrict__ R, long rs, float2* Y) {
+  const int n = q.n, C = q.C;
+  const double x0r = X[0].x, x0i = X[0].y, x1r = Cb > 1 ? (double)X[1].x : 0.0, x1i = Cb > 1 ? (double)X[1].y : 0.0;
+  const double p = ((x0r * x0r + x0i * x0i) + (x1r * x1r + x1i * x1i)) / (double)Cb;
+  double v[MR_MAX_SRC], s00 = 0.0, s11 = 0.0, s01r = 0.0, s01i = 0.0;
+#pragma unroll
+  for (int i = 0; i < MR_MAX_SRC; ++i)
+    if (i < n) {
+      const double* Ri = R + i * rs;
+      v[i] = ((double)M[i] * (double)M[i]) * p;
+      s00 += v[i] * Ri[0];
+      if (Cb > 1) {
+        s11 += v[i] * Ri[2 * (C + 1)];
+        s01r += v[i] * Ri[2];
+        s01i += v[i] * Ri[3];
+      }
+    }
+  const double lam = (double)q.reg * ((s00 + s11) / (double)Cb) + (double)q.eps;
+  const double a00 = s00 + lam, a11 = s11 + lam;
+  double z0r, z0i, z1r = 0.0, z1i = 0.0;
+  if (Cb > 1) {   // z = adj(A) X / det A, A = [[a00, s01], [conj s01, a11]]
+    const double det = a00 * a11 - (s01r * s01r + s01i * s01i);
+    z0r = (a11 * x0r - (s01r * x1r - s01i * x1i)) / det;
+    z0i = (a11 * x0i - (s01r * x1i + s01i * x1r)) / det;
+    z1r = (a00 * x1r - (s01r * x0r + s01i * x0i)) / det;
+    z1i = (a00 * x1i - (s01r * x0i - s01i * x0r)) / det;
+  } else {
+    z0r = x0r / a00;
+    z0i = x0i / a00;
+  }
+  const double share = lam / (double)n, zr = co == 0 ? z0r : z1r, zi = co == 0 ? z0i : z1i;
+#pragma unroll
+  for (int i = 0; i < MR_MAX_SRC; ++i)
+    if (i < n) {
+      const double* Rc = R + i * rs + 2 * co * C;   // row `co` of R_i
+      double yr = Rc[0] * z0r - Rc[1] * z0i, yi = Rc[0] * z0i + Rc[1] * z0r;
+      if (Cb > 1) {
+        yr += Rc[2] * z1r - Rc[3] * z1i;
+        yi += Rc[2] * z1i + Rc[3] * z1r;
+      }
+      Y[i] = make_float2((float)(v[i] * yr + share * zr), (float)(v[i] * yi + share * zi));
+    }
+}
+
+// mix [B][C][Lmax], est [B][n][Lmax], out [B][n][C][Lmax], lens / chans [B] or null (Lmax / C each).
+// MR_MASK, MR_WIENER: grid (ceil(Lmax / SPAN), B, C); MR_STATS: grid (frame spans, B), part [B][spans][n][MR_STAT][H + 1].
+// Rg [B][n][H + 1][C][C][2] (MR_WIENER).
+// Dynamic LDS: float2 tw[H] | float2 buf[NX + n][G][H] | float win[NFFT] | float ola[n][SPAN] (not MR_STATS), NX = 1
+// (MR_MASK) or C mixture channels
+template <int NFFT, int MODE>
 __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape q, const float* __restrict__ mix,
                                                           const float* __restrict__ est,
-                                                          const int* __restrict__ lens, float* __restrict__ out) {
+                                                          const int* __restrict__ lens, const int* __restrict__ chans,
+                                                          float* __restrict__ out, const double* __restrict__ Rg,
+                                                          double* __restrict__ part) {
   static_assert(NFFT >= 64 && NFFT <= 2 * MR_POINTS && (NFFT & (NFFT - 1)) == 0, "FFT size");
   constexpr int H = NFFT / 2, LOGH = __builtin_ctz(H), G = MR_POINTS / H, NP = H / 2 + 1, SPAN = mr_span<NFFT>();
+  constexpr int BF = MODE == MR_MASK ? MR_BF : MR_BF_STEMS;
   extern __shared__ __attribute__((aligned(16))) float2 mr_lds[];
   const int n = q.n, hop = q.hop, r = NFFT / hop, tid = threadIdx.x;
+  const int b = blockIdx.y, co = blockIdx.z, s0 = blockIdx.x * SPAN;
+  const int Cb = chans ? chans[b] : q.C;
+  const int nx = MODE == MR_MASK ? 1 : Cb;          // mixture channels in LDS: slots 0 .. nx - 1, then the estimates
+  const int cx = MODE == MR_MASK ? co : 0;          // .. the first of them
   float2* tw = mr_lds;
   float2* buf = tw + H;
-  float* win = reinterpret_cast<float*>(buf + (n + 1) * MR_POINTS);
+  float* win = reinterpret_cast<float*>(buf + ((MODE == MR_MASK ? 1 : q.C) + n) * MR_POINTS);
   float* ola = win + NFFT;
-  const int b = blockIdx.y, s0 = blockIdx.x * SPAN;
   const int L = lens ? lens[b] : q.Lmax;
   const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
-  const float* mixb = mix + (long)b * q.Lmax;
+  const float* mixb = mix + ((long)b * q.C + cx) * q.Lmax;
   const float* estb = est + (long)b * n * q.Lmax;
-  float* outb = out + (long)b * n * q.Lmax;
+  float* outb = out + ((long)b * n * q.C + co) * q.Lmax;   // source i: + i C Lmax
+  const long orow = (long)q.C * q.Lmax;
 
-  if (s0 >= L) {   // (uniform) the whole span lies past the item's end
+  if (MODE != MR_STATS && (s0 >= L || co >= Cb)) {   // (uniform) past the item's end, or a channel it does not have
     for (int i = 0; i < n; ++i)
       for (int v = tid; v < SPAN / 4; v += MRT)
-        if (s0 + 4 * v < q.Lmax) mr_store(q, outb + (long)i * q.Lmax, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (s0 + 4 * v < q.Lmax) mr_store(q, outb + i * orow, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
     return;
   }
+  const int fps = SPAN / hop;   // MR_STATS: the frames one workgroup owns
+  if (MODE == MR_STATS && (int)blockIdx.x * fps >= F) return;   // (uniform)
 
   for (int t = tid; t < H; t += MRT) {
     double s, c;
@@ -153,12 +261,16 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
     tw[t] = make_float2((float)c, (float)-s);
   }
   for (int t = tid; t < NFFT; t += MRT) win[t] = (float)(0.5 - 0.5 * cospi((double)t / H));   // periodic Hann
-  for (int e = tid; e < n * SPAN; e += MRT) ola[e] = 0.f;
+  if (MODE != MR_STATS)
+    for (int e = tid; e < n * SPAN; e += MRT) ola[e] = 0.f;
 
   // sample p is covered by the r frames (p + H) / hop - r + 1 .. (p + H) / hop, where they exist
   const int pend = min(s0 + SPAN, L);
-  const int f_first = max(0, (s0 + H) / hop - r + 1), f_last = min(F - 1, (pend - 1 + H) / hop);
+  const int f_first = MODE == MR_STATS ? (int)blockIdx.x * fps : max(0, (s0 + H) / hop - r + 1);
+  const int f_last = MODE == MR_STATS ? min(F, f_first + fps) - 1 : min(F - 1, (pend - 1 + H) / hop);
   const float inv_n = 1.f / (float)NFFT;   // mr_merge hands back twice the packed transform: 1 / (2 H)
+  const long rs = 2L * (H + 1) * q.C * q.C;   // doubles between R_i and R_{i+1} of an item
+  double* partw = MODE == MR_STATS ? part + ((long)b * gridDim.x + blockIdx.x) * n * MR_STAT * (H + 1) : nullptr;
 
   for (int f0 = f_first; f0 <= f_last; f0 += G) {
     __syncthreads();   // the tables are in; the previous group's frames have been added
@@ -172,57 +284,104 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
       i0 = i0 >= Lp ? 2 * (Lp - 1) - i0 : i0;   // Lp > H: one reflection reaches [0, Lp)
       i1 = i1 >= Lp ? 2 * (Lp - 1) - i1 : i1;
       const float w0 = win[2 * tp], w1 = win[2 * tp + 1];
-      for (int s = 0; s <= n; ++s) {
-        const float* row = s == 0 ? mixb : estb + (long)(s - 1) * q.Lmax;
+      for (int s = 0; s < nx + n; ++s) {
+        const float* row = s < nx ? mixb + (long)s * q.Lmax : estb + (long)(s - nx) * q.Lmax;
         const float v0 = valid && i0 < L ? row[i0] : 0.f;
         const float v1 = valid && i1 < L ? row[i1] : 0.f;
         buf[(s * G + fg) * H + tp] = make_float2(v0 * w0, v1 * w1);
       }
     }
     __syncthreads();
-    mr_fft<H, false>(buf, tw, (n + 1) * (MR_POINTS / 2), tid);
+    mr_fft<H, false, BF>(buf, tw, (nx + n) * (MR_POINTS / 2), tid);
+    if (MODE == MR_STATS) {
+      // ---- statistics: a thread owns bin j for the whole launch and adds this group's frames in frame order
+      for (int j = tid; j <= H; j += MRT) {
+        const bool lower = 2 * j <= H;
+        const int k = lower ? j : H - j, km = (H - k) & (H - 1);
+        const float2 t = tw[k];
+        double acc[MR_MAX_SRC][MR_STAT];
+#pragma unroll
+        for (int i = 0; i < MR_MAX_SRC; ++i)
+#pragma unroll
+          for (int u = 0; u < MR_STAT; ++u) acc[i][u] = 0.0;
+        for (int fg = 0; fg < G && f0 + fg <= f_last; ++fg) {
+          float2 xk, xm;
+          float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
+          const float2* a = buf + fg * H;
+          mr_split(a[k], a[km], t, xk, xm);
+          const float2 x0 = lower ? xk : xm;
+          float2 x1 = make_float2(0.f, 0.f);
+          if (nx > 1) {
+            mr_split(a[MR_POINTS + k], a[MR_POINTS + km], t, xk, xm);
+            x1 = lower ? xk : xm;
+          }
+          mr_masks(q, buf + nx * MR_POINTS + fg * H, k, km, t, mk, mm);
+          const double x0r = x0.x, x0i = x0.y, x1r = x1.x, x1i = x1.y;
+          const double p00 = x0r * x0r + x0i * x0i, p11 = x1r * x1r + x1i * x1i;
+          const double p01r = x0r * x1r + x0i * x1i, p01i = x0i * x1r - x0r * x1i;   // X_0 conj X_1
+          const double pm = (p00 + p11) / (double)nx;
+#pragma unroll
+          for (int i = 0; i < MR_MAX_SRC; ++i)
+            if (i < n) {
+              const double m = lower ? mk[i] : mm[i], m2 = m * m;
+              acc[i][0] += m2 * p00;
+              acc[i][1] += m2 * p11;
+              acc[i][2] += m2 * p01r;
+              acc[i][3] += m2 * p01i;
+              acc[i][4] += m2 * pm;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < MR_MAX_SRC; ++i)
+          if (i < n) {
+#pragma unroll
+            for (int u = 0; u < MR_STAT; ++u) {
+              double* d = partw + ((long)i * MR_STAT + u) * (H + 1) + j;
+              *d = f0 == f_first ? acc[i][u] : *d + acc[i][u];
+            }
+          }
+      }
+      continue;
+    }
     // ---- masks: one thread per (frame, pair of bins k and H - k); the estimates' slots become Y_i, packed again
     for (int e = tid; e < G * NP; e += MRT) {
       const int fg = e / NP, k = e - fg * NP, km = (H - k) & (H - 1);
       if (f0 + fg > f_last) continue;
       const float2 t = tw[k];
-      float2 xk, xm, sk[MR_MAX_SRC], sm[MR_MAX_SRC];
-      float ak[MR_MAX_SRC], am[MR_MAX_SRC];
-      {
-        const float2* a = buf + fg * H;
-        mr_split(a[k], a[km], t, xk, xm);
+      float2 xk[STEMS_WIENER_MAX_CH], xm[STEMS_WIENER_MAX_CH], yk[MR_MAX_SRC], ym[MR_MAX_SRC];
+      float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
+      const float2* a = buf + fg * H;
+      mr_split(a[k], a[km], t, xk[0], xm[0]);
+      if (MODE == MR_WIENER && nx > 1) mr_split(a[MR_POINTS + k], a[MR_POINTS + km], t, xk[1], xm[1]);
+      mr_masks(q, buf + nx * MR_POINTS + fg * H, k, km, t, mk, mm);
+      if (MODE == MR_WIENER) {
+        const double* Rb = Rg + (long)b * n * rs;
+        mr_wiener_bin(q, Cb, co, xk, mk, Rb + 2L * k * q.C * q.C, rs, yk);
+        mr_wiener_bin(q, Cb, co, xm, mm, Rb + 2L * (H - k) * q.C * q.C, rs, ym);
+      } else {
+#pragma unroll
+        for (int i = 0; i < MR_MAX_SRC; ++i)
+          if (i < n) {
+            yk[i] = make_float2(mk[i] * xk[0].x, mk[i] * xk[0].y);
+            ym[i] = make_float2(mm[i] * xm[0].x, mm[i] * xm[0].y);
+          }
       }
-      float dk = 0.f, dm = 0.f;
 #pragma unroll
       for (int i = 0; i < MR_MAX_SRC; ++i)
         if (i < n) {
-          const float2* a = buf + ((i + 1) * G + fg) * H;
-          mr_split(a[k], a[km], t, sk[i], sm[i]);
-          ak[i] = mr_mag(sk[i], q.power);
-          am[i] = mr_mag(sm[i], q.power);
-          dk = i == 0 ? ak[i] : dk + ak[i];
-          dm = i == 0 ? am[i] : dm + am[i];
-        }
-      const float ne = (float)n * q.eps;
-      dk = dk + ne;
-      dm = dm + ne;
-#pragma unroll
-      for (int i = 0; i < MR_MAX_SRC; ++i)
-        if (i < n) {
-          const float mk = (ak[i] + q.eps) / dk, mm = (am[i] + q.eps) / dm;
           float2 zk, zm;
-          mr_merge(make_float2(mk * xk.x, mk * xk.y), make_float2(mm * xm.x, mm * xm.y), t, zk, zm);
-          float2* a = buf + ((i + 1) * G + fg) * H;
-          a[k] = zk;
-          if (km != k) a[km] = zm;
+          mr_merge(yk[i], ym[i], t, zk, zm);
+          float2* o = buf + ((nx + i) * G + fg) * H;
+          o[k] = zk;
+          if (km != k) o[km] = zm;
         }
     }
     __syncthreads();
-    mr_fft<H, true>(buf + MR_POINTS, tw, n * (MR_POINTS / 2), tid);
+    mr_fft<H, true, BF>(buf + nx * MR_POINTS, tw, n * (MR_POINTS / 2), tid);
     // ---- add: a thread owns quads of samples for the whole launch, so every sample's sum runs in frame order
     const int g_last = min(f0 + G - 1, f_last);
     for (int i = 0; i < n; ++i) {
-      const float* y = reinterpret_cast<const float*>(buf + (i + 1) * MR_POINTS);
+      const float* y = reinterpret_cast<const float*>(buf + (nx + i) * MR_POINTS);
       for (int v = tid; v < SPAN / 4; v += MRT) {
         const int p = s0 + 4 * v;
         if (p >= pend) continue;
@@ -242,6 +401,7 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
       }
     }
   }
+  if (MODE == MR_STATS) return;
 
   // ---- the envelope of the frames that exist, the division and the store (the quads this thread summed itself)
   for (int v = tid; v < SPAN / 4; v += MRT) {
@@ -268,23 +428,89 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
         o.z = p + 2 < L ? acc.z / env[2] : 0.f;
         o.w = p + 3 < L ? acc.w / env[3] : 0.f;
       }
-      mr_store(q, outb + (long)i * q.Lmax, p, o);
+      mr_store(q, outb + i * orow, p, o);
     }
   }
 }
 
-template <int NFFT>
-size_t mr_lds_bytes(int n) {
-  return sizeof(float2) * ((size_t)NFFT / 2 + (size_t)(n + 1) * MR_POINTS) +
-         sizeof(float) * ((size_t)NFFT + (size_t)n * mr_span<NFFT>());
+// R [B][n][H + 1][C][C] complex and den [B][n][H + 1] from part [B][spans][n][MR_STAT][H + 1]: one thread per (item,
+// source, bin) adds the item's own ceil(F / fps) partials in workgroup order; R = N / d, the identity where d = 0,
+// zero outside the item's own channels.
+__global__ __launch_bounds__(MRT) void stems_reduce_kernel(const double* __restrict__ part, const int* __restrict__ lens,
+                                                           const int* __restrict__ chans, int B, int n, int C, int Lmax,
+                                                           int bins, int hop, int fps, int spans,
+                                                           double* __restrict__ R, double* __restrict__ den) {
+  const long e = (long)blockIdx.x * MRT + threadIdx.x;
+  if (e >= (long)B * n * bins) return;
+  const int j = (int)(e % bins), i = (int)(e / bins % n), b = (int)(e / bins / n);
+  const int L = lens ? lens[b] : Lmax, Cb = chans ? chans[b] : C;
+  const int F = 1 + (L + hop - 1) / hop, ns = (F + fps - 1) / fps;
+  double s[MR_STAT] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int c = 0; c < ns; ++c)
+#pragma unroll
+    for (int u = 0; u < MR_STAT; ++u)
+      s[u] += part[((((long)b * spans + c) * n + i) * MR_STAT + u) * bins + j];
+  const double d = s[4];
+  double* Re = R + 2 * e * C * C;
+  for (int u = 0; u < 2 * C * C; ++u) Re[u] = 0.0;
+  Re[0] = d == 0.0 ? 1.0 : s[0] / d;
+  if (Cb > 1) {
+    Re[2 * (C + 1)] = d == 0.0 ? 1.0 : s[1] / d;
+    if (d != 0.0) {
+      Re[2] = s[2] / d, Re[3] = s[3] / d;
+      Re[2 * C] = s[2] / d, Re[2 * C + 1] = -(s[3] / d);
+    }
+  }
+  den[e] = d;
 }
 
 template <int NFFT>
-void mr_launch(const MaskRefineShape& q, const float* mix, const float* est, const int* lens, float* out, int B,
-               hipStream_t st) {
-  dsn_allow_lds<mask_refine_kernel<NFFT>>((int)mr_lds_bytes<NFFT>(MR_MAX_SRC));
-  const dim3 grid((unsigned)((q.Lmax + mr_span<NFFT>() - 1) / mr_span<NFFT>()), (unsigned)B);
-  hipLaunchKernelGGL((mask_refine_kernel<NFFT>), grid, dim3(MRT), mr_lds_bytes<NFFT>(q.n), st, q, mix, est, lens, out);
+size_t mr_lds_bytes(int nx, int n, bool ola) {
+  return sizeof(float2) * ((size_t)NFFT / 2 + (size_t)(nx + n) * MR_POINTS) +
+         sizeof(float) * ((size_t)NFFT + (ola ? (size_t)n * mr_span<NFFT>() : 0));
+}
+
+struct MrArgs {
+  const float *mix, *est;
+  const int *lens, *chans;
+  float* out;
+  double *R, *den, *part;
+  int B;
+};
+
+template <int NFFT, int MODE>
+void mr_launch(const MaskRefineShape& q, const MrArgs& a, dim3 grid, hipStream_t st) {
+  const int nxmax = MODE == MR_MASK ? 1 : STEMS_WIENER_MAX_CH, nx = MODE == MR_MASK ? 1 : q.C;
+  dsn_allow_lds<mask_refine_kernel<NFFT, MODE>>((int)mr_lds_bytes<NFFT>(nxmax, MR_MAX_SRC, MODE != MR_STATS));
+  hipLaunchKernelGGL((mask_refine_kernel<NFFT, MODE>), grid, dim3(MRT), mr_lds_bytes<NFFT>(nx, q.n, MODE != MR_STATS),
+                     st, q, a.mix, a.est, a.lens, a.chans, a.out, a.R, a.part);
+}
+
+template <int NFFT>
+void mr_run(int wiener, const MaskRefineShape& q, const MrArgs& a, hipStream_t st) {
+  constexpr int SPAN = mr_span<NFFT>();
+  const dim3 grid((unsigned)((q.Lmax + SPAN - 1) / SPAN), (unsigned)a.B, (unsigned)q.C);
+  if (!wiener) {
+    mr_launch<NFFT, MR_MASK>(q, a, grid, st);
+    return;
+  }
+  const int spans = stems_stat_spans(NFFT, q.hop, q.Lmax), bins = NFFT / 2 + 1;
+  mr_launch<NFFT, MR_STATS>(q, a, dim3((unsigned)spans, (unsigned)a.B), st);
+  const long rows = (long)a.B * q.n * bins;
+  hipLaunchKernelGGL(stems_reduce_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, a.part, a.lens,
+                     a.chans, a.B, q.n, q.C, q.Lmax, bins, q.hop, SPAN / q.hop, spans, a.R, a.den);
+  mr_launch<NFFT, MR_WIENER>(q, a, grid, st);
+}
+
+void mr_dispatch(int nfft, int wiener, const MaskRefineShape& q, const MrArgs& a, hipStream_t st) {
+  switch (nfft) {
+    case 64: mr_run<64>(wiener, q, a, st); break;
+    case 128: mr_run<128>(wiener, q, a, st); break;
+    case 256: mr_run<256>(wiener, q, a, st); break;
+    case 512: mr_run<512>(wiener, q, a, st); break;
+    case 1024: mr_run<1024>(wiener, q, a, st); break;
+    default: mr_run<2048>(wiener, q, a, st); break;
+  }
 }
 
 }  // namespace
@@ -293,13 +519,18 @@ bool mask_refine_fft_ok(int nfft) { return nfft >= 64 && nfft <= 2 * MR_POINTS &
 
 void launch_mask_refine(const float* mix, const float* est, const int* lens, float* out, int B, int n, int Lmax,
                         int nfft, int hop, int power, float eps, hipStream_t st) {
-  const MaskRefineShape q{n, Lmax, hop, power, eps, ((uintptr_t)out & 15) == 0 && Lmax % 4 == 0 ? 1 : 0};
-  switch (nfft) {
-    case 64: mr_launch<64>(q, mix, est, lens, out, B, st); break;
-    case 128: mr_launch<128>(q, mix, est, lens, out, B, st); break;
-    case 256: mr_launch<256>(q, mix, est, lens, out, B, st); break;
-    case 512: mr_launch<512>(q, mix, est, lens, out, B, st); break;
-    case 1024: mr_launch<1024>(q, mix, est, lens, out, B, st); break;
-    default: mr_launch<2048>(q, mix, est, lens, out, B, st); break;
-  }
+  const MaskRefineShape q{n, Lmax, hop, power, eps, ((uintptr_t)out & 15) == 0 && Lmax % 4 == 0 ? 1 : 0, 1, 0.f};
+  mr_dispatch(nfft, 0, q, MrArgs{mix, est, lens, nullptr, out, nullptr, nullptr, nullptr, B}, st);
+}
+
+int stems_stat_spans(int nfft, int hop, int Lmax) {
+  const int F = 1 + (Lmax + hop - 1) / hop, fps = (nfft >= 2048 ? mr_span<2048>() : mr_span<64>()) / hop;
+  return (F + fps - 1) / fps;
+}
+
+void launch_stems(const float* mix, const float* est, const int* lens, const int* chans, float* out, double* part,
+                  double* R, double* den, int B, int C, int n, int Lmax, int wiener, int nfft, int hop, int power,
+                  float eps, float reg, hipStream_t st) {
+  const MaskRefineShape q{n, Lmax, hop, power, eps, ((uintptr_t)out & 15) == 0 && Lmax % 4 == 0 ? 1 : 0, C, reg};
+  mr_dispatch(nfft, wiener, q, MrArgs{mix, est, lens, chans, out, R, den, part, B}, st);
 }

@@ -1,4 +1,5 @@
-// WAV payloads to fp32 and back, and the reference's output gain (dsn_pcm_decode, dsn_pcm_encode, dsn_scale_output).
+// WAV payloads to fp32 and back, and the reference's output gain (dsn_pcm_decode, dsn_pcm_encode,
+// dsn_pcm_encode_frames, dsn_scale_output).
 // Restated in numpy in tests/pcm_restatement.py.
 //
 //   pcm_decode_kernel   one launch for a mixed batch.  A workgroup owns one tile of PCM_TILE frames of one item, whatever
@@ -10,7 +11,8 @@
 //                       per sample: a sample may straddle dwords) and stores them as one 16-byte store per output row
 //                       where the row's alignment allows.  Frames at or past the item's end, and the channels past its
 //                       own, are written as zero without touching LDS.
-//   pcm_encode_kernel   a workgroup owns one tile of PCM_TILE samples of one row: coalesced loads, quantisation, the
+//   pcm_encode_kernel   a workgroup owns one tile of PCM_TILE payload samples of one row (a row's channels interleaved;
+//                       the mono call has one): loads coalesced per channel, quantisation, the
 //                       tile's byte image in LDS at the 16-byte phase of its place in the buffer; then the bytes up to
 //                       the first 16-byte boundary one by one, whole aligned 16-byte stores, and the rest one by one.
 //                       Nothing outside the tile's own bytes is written: neighbouring rows share dwords.
@@ -120,25 +122,29 @@ __global__ void __launch_bounds__(PCPB) pcm_decode_kernel(const unsigned char* _
   }
 }
 
-// grid (x: tiles of Lmax, y: row)
+// grid (x: tiles of C Lmax interleaved samples, y: row); x [R][C][Lmax], row r holds items[r].frames frames of
+// items[r].channels channels: payload sample j is channel j % channels of frame j / channels
 __global__ void __launch_bounds__(PCPB) pcm_encode_kernel(const float* __restrict__ x,
-                                                          const PcmItem* __restrict__ items, int Lmax, int enc,
+                                                          const PcmItem* __restrict__ items, int C, int Lmax, int enc,
                                                           unsigned char* __restrict__ bytes,
                                                           unsigned long long* __restrict__ clipped) {
   __shared__ __attribute__((aligned(16))) unsigned char img[PCM_TILE * 4 + 32];
   const int r = blockIdx.y, tid = threadIdx.x;
   const PcmItem it = items[r];
-  const long j0 = (long)blockIdx.x * PCM_TILE;
-  if (j0 >= it.frames) return;   // (uniform)
-  const int nj = it.frames - j0 < PCM_TILE ? (int)(it.frames - j0) : PCM_TILE;
+  const long j0 = (long)blockIdx.x * PCM_TILE, total_j = (long)it.frames * it.channels;
+  if (j0 >= total_j) return;   // (uniform)
+  const int nj = total_j - j0 < PCM_TILE ? (int)(total_j - j0) : PCM_TILE;
   const int w = pcm_sample_bytes(enc);
   unsigned char* dst = bytes + it.offset + j0 * w;
   const int lead = (int)((uintptr_t)dst & 15);
-  const float* row = x + (long)r * Lmax + j0;
+  const float* row = x + (long)r * C * Lmax;
   const float scale = enc == DSN_PCM_S16 ? 32768.f : 8388608.f;
   int clip = 0;
+  const long fr0 = j0 / it.channels;                  // (uniform) the tile's first frame ..
+  const int c0 = (int)(j0 - fr0 * it.channels);       // .. and the channel it starts in
   for (int j = tid; j < nj; j += PCPB) {
-    const float v = row[j];
+    const int s = c0 + j, df = it.channels == 1 ? s : s / it.channels;
+    const float v = row[(long)(s - df * it.channels) * Lmax + fr0 + df];
     unsigned q;
     if (enc == DSN_PCM_F32) {
       q = __float_as_uint(v);
@@ -267,10 +273,10 @@ void launch_pcm_decode(const unsigned char* bytes, long nbytes, const PcmItem* i
                      downmix ? 1 : 0, out, Cout, Lmax, vec_in, vec_out);
 }
 
-void launch_pcm_encode(const float* x, const PcmItem* items, int R, int Lmax, int enc, unsigned char* bytes,
+void launch_pcm_encode(const float* x, const PcmItem* items, int R, int C, int Lmax, int enc, unsigned char* bytes,
                        unsigned long long* clipped, hipStream_t s) {
-  const dim3 grid((unsigned)(((long)Lmax + PCM_TILE - 1) / PCM_TILE), (unsigned)R);
-  hipLaunchKernelGGL(pcm_encode_kernel, grid, dim3(PCPB), 0, s, x, items, Lmax, enc, bytes, clipped);
+  const dim3 grid((unsigned)(((long)C * Lmax + PCM_TILE - 1) / PCM_TILE), (unsigned)R);
+  hipLaunchKernelGGL(pcm_encode_kernel, grid, dim3(PCPB), 0, s, x, items, C, Lmax, enc, bytes, clipped);
 }
 
 void launch_scale_output(const float* mix, const float* sep, const int* lens, int B, int n, int Lmax, double* part,

@@ -59,9 +59,10 @@ def parse_inputs(paths) -> list:
     return [wavio.read_header(p) for p in paths]
 
 
-def load_batch(engine, paths, headers):
+def load_batch(engine, paths, headers, downmix: bool = True):
     """The payloads of `paths` back to back in one pinned buffer, one host-to-device copy, one decode launch ->
-    (list of mono [1, frames_b] clips at each file's own rate, on the device)"""
+    (list of mono [1, frames_b] clips at each file's own rate, on the device; downmix=False: [channels_b, frames_b],
+    every file with its own channels)"""
     import torch
 
     offsets, total = [], 0
@@ -73,8 +74,8 @@ def load_batch(engine, paths, headers):
     for p, h, o in zip(paths, headers, offsets):
         wavio.read_payload(p, h, out=view[o:o + h.data_bytes])
     items = [(o, h.frames, h.channels, h.encoding) for o, h in zip(offsets, headers)]
-    x, frames = engine.pcm_decode(raw, items, downmix=True)
-    return [x[b, :, :frames[b]] for b in range(len(headers))]
+    x, frames = engine.pcm_decode(raw, items, downmix=downmix)
+    return [x[b, :1 if downmix else h.channels, :frames[b]] for b, h in enumerate(headers)]
 
 
 def _padded(rows, device):
@@ -89,14 +90,20 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   **sampler_kwargs) -> list:
+                   stems=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
+    import torch
+
     eng = model.engine
     fs = model._model_rate("separate_files")
     if encoding not in native.PCM_OUT_ENCODINGS:
         raise ValueError(f"encoding must be one of {native.PCM_OUT_ENCODINGS} (got {encoding!r})")
     native.check_codec_mode(codec)
     refine = native.refine_options(refine)
+    stems = native.stems_options(stems)
+    if stems is not None and rescale:
+        raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
+                         "mixture")
     if long_mode not in native.LONG_MODES:
         raise ValueError(f"long_mode must be one of {native.LONG_MODES} (got {long_mode!r})")
     paths = [os.fspath(p) for p in paths]
@@ -118,13 +125,49 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         for p, v in zip(paths, plan["lengths"]):
             if v < need:
                 raise ValueError(f"{p}: {v} samples at the model's rate; refine= needs at least n_fft / 2 + 1 = {need}")
+    if stems is not None:
+        # .. and those of the stems: the parameters on a stand-in item, every file's channel count and length
+        need = native.check_stems((1, 1, 2049), (1, n, 2049), None, None, **stems)[4] // 2 + 1
+        for p, h, v in zip(paths, headers, plan["lengths"]):
+            if h.channels > native.STEMS_MAX_CHANNELS[stems["mode"]]:
+                raise ValueError(f"{p}: {h.channels} channels; stems mode {stems['mode']!r} takes at most "
+                                 f"{native.STEMS_MAX_CHANNELS[stems['mode']]}")
+            if v < need:
+                raise ValueError(f"{p}: {v} samples at the model's rate; stems= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
 
-    def finish(idx, at_fs, est, label):
+    def finish_stems(idx, clips, est, label):
+        """mono estimates at the model's rate -> multichannel files; `clips` the files' own channels at their own rates"""
+        hs = [headers[i] for i in idx]
+        at_fs = eng.to_model_rate(clips, [h.rate for h in hs], fs, downmix=False)
+        back = eng.stems_from_model_rate(eng.stems(at_fs, est, **stems), [h.rate for h in hs], fs,
+                                         [h.frames for h in hs])
+        rows = torch.zeros((len(idx), n, max(h.channels for h in hs), max(h.frames for h in hs)), device=eng.device,
+                           dtype=torch.float32)
+        for j, y in enumerate(back):
+            rows[j, :, :hs[j].channels, :hs[j].frames] = y
+        payloads, clipped = eng.pcm_encode_frames(rows.reshape(len(idx) * n, *rows.shape[2:]),
+                                                  [h.frames for h in hs for _ in range(n)],
+                                                  [h.channels for h in hs for _ in range(n)], encoding)
+        for j, i in enumerate(idx):
+            stem = os.path.splitext(os.path.basename(paths[i]))[0]
+            outs = []
+            for s in range(n):
+                d = os.path.join(out_dir, f"s{s}")
+                os.makedirs(d, exist_ok=True)
+                outs.append(os.path.join(d, stem + ".wav"))
+                wavio.write_wav(outs[-1], payloads[j * n + s], hs[j].rate, hs[j].channels, encoding)
+            records[i] = {"path": paths[i], "rate": hs[j].rate, "channels": hs[j].channels, "frames": hs[j].frames,
+                          "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label,
+                          "stems": stems["mode"]}
+
+    def finish(idx, at_fs, est, label, clips=None):
         """estimates at the model's rate -> files; `at_fs` the mono mixtures there"""
         alpha = None
         if refine is not None:
             est = eng.mask_refine(at_fs, est, **refine)
+        if stems is not None:
+            return finish_stems(idx, clips, est, label)
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)
@@ -150,16 +193,16 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             records[i] = rec
 
     for k, idx in enumerate(plan["batches"]):
-        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx])
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=stems is None)
         at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed) + k)
         est, *_ = model.separate_batch(at_fs, codec=codec, **ens, **kw)
-        finish(idx, at_fs, est, k)
+        finish(idx, at_fs, est, k, clips)
     if plan["long"]:
         idx = plan["long"]
-        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx])
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=stems is None)
         at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed))
         est, *_ = model.separate_long(at_fs, window, overlap=overlap, mode=long_mode, batch=batch, **kw)
-        finish(idx, at_fs, est, "long")
+        finish(idx, at_fs, est, "long", clips)
     return records

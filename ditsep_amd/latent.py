@@ -349,9 +349,71 @@ class LatentDiffSep:
         est, *others = self.separate(m, target_dim, refine=refine, **ens, **kwargs)
         return (eng.resample(est, fs, sample_rate)[..., :L], *others)
 
+    # ------------------------------------------------------------------ multichannel stems (the `stems` keyword)
+    @staticmethod
+    def _fit(x, L):
+        """x [..., L0] zero-extended or cut to L samples"""
+        return torch.nn.functional.pad(x, (0, L - int(x.shape[-1]))) if int(x.shape[-1]) < L else x[..., :L]
+
+    def _stems_refusals(self, sopts, channels, latent=False, intermediate=None):
+        """What the `stems` keyword refuses, before any device work"""
+        if latent:
+            raise ValueError("stems= filters waveforms: with latent=True there is no mixture to filter")
+        if intermediate:
+            raise ValueError("stems= does not go with intermediate: the per-step states are not filtered")
+        most = native.STEMS_MAX_CHANNELS[sopts["mode"]]
+        for b, c in enumerate(channels):
+            if c < 1 or c > most:
+                raise ValueError(f"stems: item {b} has {c} channels, outside [1, {most}] for mode {sopts['mode']!r}")
+
+    @torch.no_grad()
+    def _separate_stems(self, mix, target_dim, sample_rate, sopts, mono_kw, kwargs):
+        """`separate` with stems=: mix [B, C, L] -> the mono call on the downmix, Engine.stems against the channels at
+        the model's rate (zero-extended or cut to the estimates' length), back to `sample_rate`"""
+        eng = self.engine
+        if not torch.is_tensor(mix) or mix.dim() != 3:
+            raise ValueError(f"stems= takes mix [B, C, L] (got {tuple(getattr(mix, 'shape', ()))})")
+        B, Cn, L = (int(v) for v in mix.shape)
+        self._stems_refusals(sopts, [Cn], intermediate=kwargs.get("intermediate"))
+        if sample_rate is None:
+            mc = native._dev32(mix, eng.device)
+            mono = native.downmix(mc)
+        else:
+            fs = self._model_rate("sample_rate=")
+            mc, mono = eng.resample(mix, sample_rate, fs), eng.resample(mix, sample_rate, fs, downmix=True)
+        est, *others = self.separate(mono, target_dim, **mono_kw, **kwargs)
+        out = eng.stems(self._fit(mc, int(est.shape[-1])), est, **sopts)
+        if sample_rate is not None:
+            n, Le = int(out.shape[1]), int(out.shape[-1])
+            out = eng.resample(out.reshape(B, n * Cn, Le), fs, sample_rate)[..., :L].reshape(B, n, Cn, L)
+        return (out, *others)
+
+    @torch.no_grad()
+    def _stems_of_lists(self, clips, rates, sopts, run):
+        """The list entry points with stems=: `clips` [C_b, L_b] each (or [L_b], [1, C_b, L_b]) at `rates` (None: the
+        model's rate); run(list of mono [1, L'_b]) -> (list of [n, Le_b] estimates at the model's rate, *others).
+        -> (list of [n, C_b, L_b] at each clip's own rate, *others)"""
+        eng = self.engine
+        clips = [c[None] if c.dim() == 1 else c[0] if c.dim() == 3 and c.shape[0] == 1 else c for c in clips]
+        for b, c in enumerate(clips):
+            if c.dim() != 2:
+                raise ValueError(f"stems=: clip {b} must be [L], [C, L] or [1, C, L] (got {tuple(c.shape)})")
+        self._stems_refusals(sopts, [int(c.shape[0]) for c in clips])
+        if rates is None:
+            mc = [native._dev32(c, eng.device) for c in clips]
+            mono = [native.downmix(c[None])[0] for c in mc]
+        else:
+            fs = self._model_rate("sample_rates=")
+            mc, mono = eng.to_model_rate(clips, rates, fs, downmix=False), eng.to_model_rate(clips, rates, fs)
+        est, *others = run(mono)
+        out = eng.stems([self._fit(m, int(e.shape[-1])) for m, e in zip(mc, est)], list(est), **sopts)
+        if rates is not None:
+            out = eng.stems_from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
+        return (out, *others)
+
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
-                 return_info=False, **kwargs):
+                 return_info=False, stems=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -368,7 +430,18 @@ class LatentDiffSep:
         are aligned and combined on the device (Engine.ensemble_combine, combine = "mean", "median", "best" or
         "medoid") against the mono mixture at the model's rate, zero-extended or cut to the estimates' length --
         after the decoder and before refine and any resampling back.  return_info=True appends the info dict of
-        Engine.ensemble_combine to what is returned.  Refused with latent=True and with intermediate."""
+        Engine.ensemble_combine to what is returned.  Refused with latent=True and with intermediate.
+        stems (default None: the call is what it was): "mask", "wiener" or a dict of mode / n_fft / hop / power / eps /
+        reg (native.stems_options) -- mix is then [B, C, L] and [B, n, C, L] comes back: the call above runs on the
+        downmix ((x_0 + .. + x_{C-1}) / C), and Engine.stems filters the mixture's channels at the model's rate (the
+        channels resampled without downmix, zero-extended or cut to the estimates' length) with the mono estimates,
+        after combine and refine and before the resampling back.  The stems of a channel sum to that channel; nothing
+        above the model's Nyquist frequency comes back.  Refused with latent=True and with intermediate."""
+        sopts = native.stems_options(stems)
+        if sopts is not None:
+            self._stems_refusals(sopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
+            mono_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info)
+            return self._separate_stems(mix, target_dim, sample_rate, sopts, mono_kw, kwargs)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -417,7 +490,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
-                       combine="mean", return_info=False, **sampler_kwargs):
+                       combine="mean", return_info=False, stems=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -434,8 +507,20 @@ class LatentDiffSep:
         lengths, at the model's rate, before any resampling back; each item gets the bits it gets alone.
         samples (default None: one draw), combine, return_info as in `separate`: every mixture is repeated K times
         item-major, the B K rows go through this call once, and one Engine.ensemble_combine call on the padded
-        candidates with the items' lengths combines them against the mixtures, before refine and resampling back."""
+        candidates with the items' lengths combines them against the mixtures, before refine and resampling back.
+        stems (default None: off), as in `separate`: the mixtures are [C_b, L_b] (mixed channel counts are fine), the
+        call runs on their downmixes, one Engine.stems call on the padded batch filters every item's own channels at
+        the model's rate, and a list of [n, C_b, L_b] comes back, each item with the bits it gets alone."""
         eng = self.engine
+        sopts = native.stems_options(stems)
+        if sopts is not None:
+            self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
+            return self._stems_of_lists(list(mixes), rates, sopts, lambda mono: self.separate_batch(
+                mono, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
+                **sampler_kwargs))
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -485,7 +570,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      mode="stitch", sample_rates=None, refine=None, **sampler_kwargs):
+                      mode="stitch", sample_rates=None, refine=None, stems=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -501,8 +586,23 @@ class LatentDiffSep:
         `window` and `overlap` stay in samples at the model's rate, and every estimate comes back at its recording's
         own rate and sample count.
         refine (default None: off), as in `separate`: every recording is refined whole against its mono mixture at
-        the model's rate, after the stitch (or the single decode of mode="score") and before any resampling back."""
+        the model's rate, after the stitch (or the single decode of mode="score") and before any resampling back.
+        stems (default None: off), as in `separate_batch`: the recordings are [C, L_r], the call runs on their
+        downmixes, and every recording's channels are filtered whole (Engine.stems) at the model's rate after the
+        stitch and refine: [n, C, L] or a list of [n, C_r, L_r] comes back."""
         eng = self.engine
+        sopts = native.stems_options(stems)
+        if sopts is not None:
+            self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
+            single = torch.is_tensor(mixes)
+            clips = [mixes] if single else list(mixes)
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(clips) if isinstance(rates, int) else [int(r) for r in rates]
+            out, *others = self._stems_of_lists(clips, rates, sopts, lambda mono: self.separate_long(
+                mono, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
+                refine=refine, **sampler_kwargs))
+            return (out[0] if single else out, *others)
         opts = native.refine_options(refine)
         if sample_rates is not None:
             fs = self._model_rate("sample_rates=")
@@ -564,7 +664,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
-                       samples=None, combine="mean", **sampler_kwargs):
+                       samples=None, combine="mean", stems=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -585,12 +685,19 @@ class LatentDiffSep:
         against the mono mixtures at the model's rate) -> rescale -> back to each file's rate -> quantise.
         samples (default None: one draw), combine as in `separate_batch`, which gets them: a batch then holds
         batch // samples files, and a file that would go through separate_long (long_after) is refused before any
-        device work -- candidate windows are a different problem."""
+        device work -- candidate windows are a different problem.
+        stems (default None: off), as in `separate`: the files are decoded with their channels, the separation runs
+        on the downmix as above, and after refine every file's own channels are filtered at the model's rate
+        (Engine.stems), taken back to the file's rate and frame count, interleaved and quantised on the device
+        (Engine.pcm_encode_frames) and written with the input's channel count: a stereo file gives stereo stems that
+        sum to it, a mono file in the same batch comes out mono.  Each dict gains "stems" (the mode).  Refused with
+        rescale (the stems already sum to the mixture) before any device work."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
-                                    seed=seed, refine=refine, samples=samples, combine=combine, **sampler_kwargs)
+                                    seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
+                                    **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

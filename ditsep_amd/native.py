@@ -41,6 +41,7 @@ EXPORTS = [
     "dsn_bss_eval", "dsn_bss_eval_plan",
     "dsn_mask_refine",
     "dsn_ensemble_combine",
+    "dsn_stems", "dsn_pcm_encode_frames",
 ]
 
 
@@ -638,6 +639,65 @@ def check_mask_refine(mix_shape, est_shape, lens=None, n_fft=512, hop=128, power
     return (B, n, L), (None if lens is None else ln), n_fft, int(hop), int(power), eps
 
 
+STEMS_MODES = {"mask": 0, "wiener": 1}                                              # DSN_STEMS_*
+STEMS_MAX_CHANNELS = {"mask": 8, "wiener": 2}
+STEMS_DEFAULTS = dict(mode="wiener", n_fft=512, hop=128, power=2, eps=1e-10, reg=1e-3)
+
+
+def stems_options(stems) -> Optional[dict]:
+    """The `stems` keyword of the separation entry points as Engine.stems' keywords: None (off, the default) -> None;
+    "mask" or "wiener" -> STEMS_DEFAULTS with that mode; a dict of mode / n_fft / hop / power / eps / reg -> the
+    defaults with those replaced.  Anything else, an unknown key or mode included, is refused by name."""
+    if stems is None:
+        return None
+    if isinstance(stems, str) and stems in STEMS_MODES:
+        return dict(STEMS_DEFAULTS, mode=stems)
+    if isinstance(stems, Mapping):
+        extra = sorted(set(stems) - set(STEMS_DEFAULTS))
+        if extra:
+            raise ValueError(f"stems: unknown keys {extra} (a dict of {sorted(STEMS_DEFAULTS)})")
+        opts = dict(STEMS_DEFAULTS, **stems)
+        if opts["mode"] not in STEMS_MODES:
+            raise ValueError(f"stems: mode must be one of {sorted(STEMS_MODES)} (got {opts['mode']!r})")
+        return opts
+    raise ValueError(f"stems must be None, 'mask', 'wiener' or a dict of {sorted(STEMS_DEFAULTS)} (got {stems!r})")
+
+
+def check_stems(mix_shape, est_shape, lens=None, channels=None, mode="wiener", n_fft=512, hop=128, power=2, eps=1e-10,
+                reg=1e-3) -> tuple:
+    """The refusals of dsn_stems (include/ditsep_hip.h), raised by name before the library is touched: an unknown
+    mode; mix that is not [B, C, L] and est that is not [B, n, L] of the same B and L; C outside [1, 8] (mask) or
+    [1, 2] (wiener); what check_mask_refine refuses (n, n_fft, hop, power, eps, an item too short for one reflection);
+    reg not finite or < 0; not one channel count per item, or one outside [1, C].
+    -> ((B, C, n, L), lens or None, channels or None, the DSN_STEMS_* mode, n_fft, hop, power, eps, reg)"""
+    if mode not in STEMS_MODES:
+        raise ValueError(f"stems: mode must be one of {sorted(STEMS_MODES)} (got {mode!r})")
+    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
+    if len(mix_shape) != 3 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != (mix_shape[0], mix_shape[2]):
+        raise ValueError(f"stems: mix must be [B, C, L] and est [B, n, L] of the same B and L (got {mix_shape} and "
+                         f"{est_shape})")
+    B, Cn, L = mix_shape
+    if Cn < 1 or Cn > STEMS_MAX_CHANNELS[mode]:
+        raise ValueError(f"stems: C = {Cn} outside [1, {STEMS_MAX_CHANNELS[mode]}] for mode {mode!r}"
+                         + (" (the Wiener filter solves 1 x 1 and 2 x 2 systems)" if mode == "wiener" else ""))
+    try:
+        (_, n, _), ln, n_fft, hop, power, eps = check_mask_refine((B, L), est_shape, lens, n_fft, hop, power, eps)
+    except ValueError as e:
+        raise ValueError(str(e).replace("mask_refine:", "stems:")) from None
+    reg = float(reg)
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError(f"stems: reg = {reg} is not a finite number >= 0")
+    ch = None
+    if channels is not None:
+        ch = [int(v) for v in channels]
+        if len(ch) != B:
+            raise ValueError(f"stems: channels must hold one channel count per item (B = {B}), got {len(ch)}")
+        for b, v in enumerate(ch):
+            if v < 1 or v > Cn:
+                raise ValueError(f"stems: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    return (B, Cn, n, L), ln, ch, STEMS_MODES[mode], n_fft, hop, power, eps, reg
+
+
 ENSEMBLE_MODES = {"mean": 0, "median": 1, "best": 2, "medoid": 3}                  # DSN_ENSEMBLE_*
 ENSEMBLE_MAX_K, ENSEMBLE_MAX_SRC = 16, 4
 
@@ -801,6 +861,9 @@ def load_library() -> C.CDLL:
     f64p = C.POINTER(C.c_double)
     lib.dsn_ensemble_combine.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, ci, vp, i32p, i32p, i32p, f64p, f64p, f64p,
                                          vp]
+    lib.dsn_stems.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, vp, f64p,
+                              f64p, vp]
+    lib.dsn_pcm_encode_frames.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
@@ -892,6 +955,15 @@ def mrstft_combine(tables: Mapping, *, w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, m
 
 def _dev32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def downmix(x: torch.Tensor) -> torch.Tensor:
+    """x [B, C, L] -> [B, 1, L]: (x_0 + .. + x_{C-1}) / C in float32 in that order, the expression of the device's
+    downmix (dsn_resample, dsn_pcm_decode); one channel passes as it is"""
+    s = x[:, 0]
+    for c in range(1, int(x.shape[1])):
+        s = s + x[:, c]
+    return (s / float(x.shape[1]) if x.shape[1] > 1 else s)[:, None]
 
 
 class Engine:
@@ -1524,6 +1596,57 @@ class Engine:
                                              _ptr(out), self._stream()), "dsn_mask_refine")
         return out
 
+    # ------------------------------------------------------------------ multichannel stems from mono estimates
+    def stems(self, mix, est, lens=None, channels=None, mode="wiener", n_fft=512, hop=128, power=2, eps=1e-10,
+              reg=1e-3, return_info=False):
+        """The mixture's channels filtered with the mono estimates (dsn_stems, csrc/maskrefine.hip; the definition is
+        in include/ditsep_hip.h and tests/stems_restatement.py): mix [B, C, L], est [B, n, L] -> [B, n, C, L], every
+        source with the mixture's channels.  mode "mask": the masks of `mask_refine` on every channel (C <= 8; bit for
+        bit mask_refine of that channel).  mode "wiener": one expectation-maximisation pass of the multichannel Wiener
+        filter (C <= 2) -- a spatial covariance per source and bin from the mixture, the per-bin solve in float64,
+        lambda = reg tr(Sigma) / C + eps on the diagonal and its remainder handed out equally, so the stems of a
+        channel sum to that channel up to float32 rounding.  lens / channels (one per item): a ragged batch padded to
+        L and C -- nothing past an item's end or in a channel it does not have is read (it may hold NaN), the result
+        is zero there and each item gets the bits it gets alone.  Lists (mix: [C_b, L_b] each, est: [n, L_b] each) are
+        padded once and a list of [n, C_b, L_b] comes back.  return_info=True: (out, {"R": complex128 [B, n, bins, C,
+        C], "den": float64 [B, n, bins]}) on the host, the spatial covariances and their denominators (zeros in mask
+        mode).  Not a trained step: what it does to separation quality is unmeasured.  Needs no score network and no
+        codec; two calls give identical bits."""
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
+                raise ValueError("stems: a list of mixtures goes with a list of as many estimates and no lens or "
+                                 "channels")
+            ln = [int(e.shape[-1]) for e in est]
+            for b, (m, e) in enumerate(zip(mix, est)):
+                if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
+                    raise ValueError(f"stems: item {b} must be mix [C, L] and est [n, L] (got {tuple(m.shape)} and "
+                                     f"{tuple(e.shape)})")
+            ch = [int(m.shape[0]) for m in mix]
+            Lmax = max(ln)
+            mp = torch.zeros((len(mix), max(ch), Lmax), device=self.device, dtype=torch.float32)
+            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
+            for b, (m, e) in enumerate(zip(mix, est)):
+                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
+                ep[b, :, :ln[b]] = _dev32(e, self.device)
+            res = self.stems(mp, ep, lens=ln, channels=ch, mode=mode, n_fft=n_fft, hop=hop, power=power, eps=eps,
+                             reg=reg, return_info=return_info)
+            out = res[0] if return_info else res
+            outs = [out[b, :, :ch[b], :ln[b]] for b in range(len(mix))]
+            return (outs, res[1]) if return_info else outs
+        (B, Cn, n, L), ln, ch, code, n_fft, hop, power, eps, reg = check_stems(
+            tuple(mix.shape), tuple(est.shape), lens, channels, mode, n_fft, hop, power, eps, reg)
+        mix, est = _dev32(mix, self.device), _dev32(est, self.device)
+        out = torch.empty((B, n, Cn, L), device=self.device, dtype=torch.float32)
+        bins = n_fft // 2 + 1
+        R = torch.zeros((B, n, bins, Cn, Cn), dtype=torch.complex128) if return_info else None
+        den = torch.zeros((B, n, bins), dtype=torch.float64) if return_info else None
+        host = lambda t: None if t is None else C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double))
+        i32 = C.c_int32 * B
+        self._check(self.lib.dsn_stems(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, None if ln is None else i32(*ln),
+                                       None if ch is None else i32(*ch), code, n_fft, hop, power, eps, reg, _ptr(out),
+                                       host(R), host(den), self._stream()), "dsn_stems")
+        return (out, {"R": R, "den": den}) if return_info else out
+
     # ------------------------------------------------------------------ K candidates -> one separation
     def ensemble_combine(self, cands, mix=None, lens=None, mode="mean", return_info=False):
         """K candidate separations of the same mixtures -> one (dsn_ensemble_combine, csrc/ensemble.hip; the definition
@@ -1559,11 +1682,12 @@ class Engine:
             return out
         return out, {k: (v.long() if v.dtype == torch.int32 else v) for k, v in info.items()}
 
-    def to_model_rate(self, clips, rates, fs: int):
+    def to_model_rate(self, clips, rates, fs: int, downmix: bool = True):
         """Clips of any rate, channel count and length at the model's rate `fs`, mixed down to mono: `clips` is a list
         of [L], [C, L] or [1, C, L] tensors, `rates` an int or one rate per clip -> list of [1, L'_b] on the device.
         Clips are grouped by input rate: one resample call per distinct (rate, channel count), its clips padded to the
-        group's longest; a mono clip already at `fs` is copied."""
+        group's longest; a mono clip already at `fs` is copied.  downmix=False keeps the channels: a list of
+        [C_b, L'_b], every channel resampled alone (a clip already at `fs` is copied whatever its channel count)."""
         rates = [int(rates)] * len(clips) if isinstance(rates, int) else [int(r) for r in rates]
         if len(rates) != len(clips):
             raise ValueError(f"one sample rate per clip is needed ({len(clips)} clips, {len(rates)} rates)")
@@ -1581,7 +1705,7 @@ class Engine:
         for i, a in enumerate(norm):
             groups.setdefault((rates[i], int(a.shape[0])), []).append(i)
         for (rate, Cn), idx in groups.items():
-            if rate == fs and Cn == 1:
+            if rate == fs and (Cn == 1 or not downmix):
                 for i in idx:
                     out[i] = _dev32(norm[i], self.device).clone()
                 continue
@@ -1589,7 +1713,7 @@ class Engine:
             x = torch.zeros((len(idx), Cn, max(ln)), device=self.device, dtype=torch.float32)
             for j, i in enumerate(idx):
                 x[j, :, :ln[j]] = _dev32(norm[i], self.device)
-            y, yl = self.resample(x, rate, fs, lens=ln, downmix=True)
+            y, yl = self.resample(x, rate, fs, lens=ln, downmix=bool(downmix))
             for j, i in enumerate(idx):
                 out[i] = y[j, :, :yl[j]]
         return out
@@ -1615,6 +1739,18 @@ class Engine:
             y, _ = self.resample(x, fs, rate, lens=ln)
             for j, i in enumerate(idx):
                 out[i] = y[j, :, :int(lengths[i])]
+        return out
+
+    def stems_from_model_rate(self, stems, rates, fs: int, lengths):
+        """`from_model_rate` for multichannel stems: a list of [n, C_b, L'_b] at `fs` -> list of [n, C_b, lengths[b]] at
+        rates[b]; one resample call per distinct (rate, channel count)."""
+        out = [None] * len(stems)
+        for cn in sorted({int(s.shape[1]) for s in stems}):
+            idx = [i for i, s in enumerate(stems) if int(s.shape[1]) == cn]
+            back = self.from_model_rate([stems[i].reshape(-1, stems[i].shape[-1]) for i in idx],
+                                        [rates[i] for i in idx], fs, [lengths[i] for i in idx])
+            for i, y in zip(idx, back):
+                out[i] = y.reshape(int(stems[i].shape[0]), cn, -1)
         return out
 
     # ------------------------------------------------------------------ WAV payloads and the output gain
@@ -1677,6 +1813,53 @@ class Engine:
         host.copy_(out)
         view = memoryview(host.numpy())
         return [bytes(view[o:o + v * w]) for o, v in zip(offsets, ln)], [int(c) for c in clipped]
+
+    def pcm_encode_frames(self, x, lens=None, channels=None, encoding: str = "s16", offsets=None, out=None):
+        """Float32 rows to interleaved multichannel WAV payloads on the device (dsn_pcm_encode_frames): x [R, C, Lmax],
+        row r is lens[r] frames (default Lmax) of its first channels[r] channels (default C) -> (one `bytes` per row,
+        channels[r] samples per frame, and the clipped counts, summed over a row's channels).  Quantisation, clamping,
+        NaN handling, `offsets` and `out` as in `pcm_encode`, whose bytes these are with C = 1.  A frame wider than
+        PCM_MAX_FRAME_BYTES is refused.  Needs no score network and no codec; two calls give identical bytes."""
+        if encoding not in PCM_OUT_ENCODINGS:
+            raise ValueError(f"encoding must be one of {PCM_OUT_ENCODINGS} (got {encoding!r})")
+        x = _dev32(x, self.device)
+        if x.dim() != 3 or min(x.shape) < 1:
+            raise ValueError(f"x must be [R, C, Lmax] with at least one row, channel and sample (got {tuple(x.shape)})")
+        R, Cn, Lmax = (int(v) for v in x.shape)
+        ln = [Lmax] * R if lens is None else check_lens(lens, R, Lmax)
+        ch = [Cn] * R if channels is None else [int(v) for v in channels]
+        w = PCM_SAMPLE_BYTES[encoding]
+        if len(ch) != R:
+            raise ValueError(f"one channel count per row is needed ({R} rows, {len(ch)} counts)")
+        for r, v in enumerate(ch):
+            if v < 1 or v > Cn:
+                raise ValueError(f"row {r}: channels = {v} outside [1, C = {Cn}]")
+            if v * w > PCM_MAX_FRAME_BYTES:
+                raise ValueError(f"row {r}: a frame of {v * w} bytes is wider than PCM_MAX_FRAME_BYTES = "
+                                 f"{PCM_MAX_FRAME_BYTES}")
+        size = [v * c * w for v, c in zip(ln, ch)]
+        if offsets is None:
+            offsets, o = [], 0
+            for v in size:
+                offsets.append(o)
+                o += v
+        offsets = [int(v) for v in offsets]
+        if len(offsets) != R:
+            raise ValueError(f"one byte offset per row is needed ({R} rows, {len(offsets)} offsets)")
+        if out is None:
+            out = torch.zeros(max(o + v for o, v in zip(offsets, size)), device=self.device, dtype=torch.uint8)
+        if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous 1-D uint8 tensor on the device")
+        clipped = (C.c_int64 * R)()
+        i32 = C.c_int32 * R
+        self._check(self.lib.dsn_pcm_encode_frames(self.ctx, _ptr(x), R, Cn, Lmax, i32(*ln), i32(*ch),
+                                                   PCM_ENCODINGS[encoding], _ptr(out), out.numel(),
+                                                   (C.c_int64 * R)(*offsets), clipped, self._stream()),
+                    "dsn_pcm_encode_frames")
+        host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out)
+        view = memoryview(host.numpy())
+        return [bytes(view[o:o + v]) for o, v in zip(offsets, size)], [int(c) for c in clipped]
 
     def scale_output(self, mix, sep, lens=None):
         """The reference's output gain (src/inference/separate.py:73-78) for a ragged batch (dsn_scale_output): mix

@@ -68,6 +68,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "(default: one draw)")
     p.add_argument("--combine", default="mean", choices=["mean", "median", "best", "medoid"],
                    help="How the candidates of --samples are combined")
+    p.add_argument("--stems", default=None, choices=["mask", "wiener"],
+                   help="Write every speaker with the input's own channels: the mixture's channels filtered with the "
+                        "mono estimates (mask: the masks on every channel; wiener: multichannel Wiener filter, up to "
+                        "two channels; not a trained step; off by default)")
+    p.add_argument("--stems-nfft", type=int, default=512, help="Window of the stems filter, samples at the model's rate")
+    p.add_argument("--stems-hop", type=int, default=128, help="Hop of the stems filter (window / 2, / 4 or / 8)")
+    p.add_argument("--stems-power", type=int, default=2, choices=[1, 2], help="Exponent of the mask magnitudes")
+    p.add_argument("--stems-reg", type=float, default=1e-3,
+                   help="Diagonal loading of the Wiener solve, relative to the mean channel variance")
     return p
 
 
@@ -99,6 +108,14 @@ def refine_of(args):
     return dict(n_fft=args.refine_nfft, hop=args.refine_hop, power=args.refine_power)
 
 
+def stems_of(args):
+    """The `stems` keyword of separate_files from the parsed flags: None unless --stems is given."""
+    if args.stems is None:
+        return None
+    return dict(mode=args.stems, n_fft=args.stems_nfft, hop=args.stems_hop, power=args.stems_power,
+                reg=args.stems_reg)
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     try:
@@ -128,7 +145,7 @@ def main(argv=None) -> int:
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
-                                           denoise=args.denoise, **kw)
+                                           stems=stems_of(args), denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2

@@ -564,6 +564,45 @@ int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_
 int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int n, int Lmax, const int32_t* lens,
                     int n_fft, int hop, int power, float eps, float* out, void* stream);
 
+/* Multichannel stems from mono estimates: the mixture's C channels filtered with what the mono estimates say about the
+ * sources, so every source comes back with the mixture's channels and spatial image (the last step of Open-Unmix /
+ * norbert; Duong, Vincent, Gribonval 2010; csrc/maskrefine.hip, restated in float64 in tests/stems_restatement.py).  A
+ * definition, not a trained step; nothing calls it unless asked to.  mix [B][C][Lmax], est [B][n][Lmax] (mono), out
+ * [B][n][C][Lmax] fp32 (device).  lens and channels (HOST, [B], or NULL: Lmax and C for every item): item b has
+ * lens[b] samples and uses its first channels[b] channels; its other output channels and everything at or past lens[b]
+ * are written as zero, and nothing there is read from mix or est (it may hold NaN).  Padding, analysis, window,
+ * reflection, masks M_i and synthesis are dsn_mask_refine's (above), X_c the STFT of channel c, S_i of estimate i.
+ *   DSN_STEMS_MASK    Y_i,c = M_i X_c: one launch, no workspace, C <= 8.  out[b][i][c] has, bit for bit, what
+ *                     dsn_mask_refine returns for mix = channel c.
+ *   DSN_STEMS_WIENER  one expectation-maximisation pass of the multichannel Wiener filter, C = channels[b] <= 2.  With
+ *                     the fp32 spectra and masks widened to fp64 (bin f, frame t):
+ *                       v_i(f,t) = M_i^2 (1/C) sum_c |X_c|^2
+ *                       N_i(f) = sum_t M_i^2 X X^H (C x C, Hermitian),  d_i(f) = sum_t v_i
+ *                       R_i(f) = N_i / d_i, the identity where d_i = 0
+ *                       Sigma(f,t) = sum_j v_j R_j,  lambda(f,t) = reg tr(Sigma) / C + eps
+ *                       z = (Sigma + lambda I)^-1 X  (the closed-form 2 x 2 adjugate),
+ *                       Y_i = v_i R_i z + (lambda / n) z
+ *                     so sum_i Y_i = X in exact arithmetic: the regularisation's remainder is handed out equally and
+ *                     every channel of the stems adds up to that channel of the mixture.  N, d, R and the per-bin
+ *                     solve are fp64 (two identical channels make Sigma singular: only lambda inverts it); Y is
+ *                     rounded once to fp32 before the inverse transform.  Three launches: every frame is owned by
+ *                     exactly one workgroup of the statistics launch (frames [c S / hop, (c + 1) S / hop), S = 2048,
+ *                     4096 for n_fft = 2048), which adds its frames in increasing order; a reduce launch adds the
+ *                     partials in workgroup order; the filter launch reads R from global memory.  No floating-point
+ *                     atomics: the order depends on the item's length and the parameters alone.
+ * An item has the same bits alone, at any batch position and under any padding, and two calls give identical bits.
+ * Silent estimates give n outputs that are equal to the bit.  info_R ([B][n][n_fft / 2 + 1][C][C] complex as double
+ * pairs; zero outside an item's own channels) and info_den ([B][n][n_fft / 2 + 1]) are HOST arrays or NULL: R_i and
+ * d_i of the Wiener mode (zeros in mask mode); with either the stream is synchronised.  The partials and R live in a
+ * workspace the context keeps and grows.  The call uploads lens and channels when given and then synchronises the
+ * stream, so with them it must not be captured into a graph.  Needs no score network and no codec.
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_mask_refine refuses; an unknown mode; C outside
+ * [1, 8] (mask) or [1, 2] (wiener); channels[b] outside [1, C]; reg not finite or < 0; out overlapping mix or est. */
+enum { DSN_STEMS_MASK = 0, DSN_STEMS_WIENER = 1 };
+int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
+              const int32_t* channels, int mode, int n_fft, int hop, int power, float eps, float reg, float* out,
+              double* info_R, double* info_den, void* stream);
+
 /* Ensemble combine: K candidate separations of the same mixtures (K draws of the diffusion sampler) -> one separation
  * (csrc/ensemble.hip, restated in float64 in tests/ensemble_restatement.py).  A definition, not a trained step; nothing
  * calls it unless asked to.  cands [B][K][n][Lmax], mix [B][Lmax] or NULL, out [B][n][Lmax] fp32 (device),
@@ -635,6 +674,10 @@ int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int
  *            or was not finite (integer atomics: the count does not depend on their order); F32 copies the bits and
  *            counts nothing.  Only the lens[r] bytes-per-sample bytes of a row are written: whatever lies between and
  *            after the rows stays as it was.  Two calls give identical bytes.
+ *   encode_frames  the same for multichannel payloads: x [R][C][Lmax], row r is lens[r] frames of its first channels[r]
+ *            channels (lens, channels: HOST, or NULL: Lmax and C each), interleaved sample by sample at byte
+ *            offset[r].  Quantisation, clamping and NaN handling are encode's; clipped[r] is summed over the row's
+ *            channels.  With C = 1 the bytes are encode's.  Only a row's own bytes are written.
  *   scale    mix [B][Lmax], sep [B][n][Lmax] fp32 (device) -> out [B][n][Lmax]:
  *              alpha[b][i] = sum_t mix[b][t] sep[b][i][t] / sum_t (sep[b][i][t]^2 + 1e-10)  over t < lens[b],
  *            both sums in fp64 over exact fp64 products, in an order a row's own length fixes (per thread in stride
@@ -647,7 +690,7 @@ int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int
  * an encoding outside the list (decode) or other than S16, S24, F32 (encode); frames[b] outside [1, Lmax];
  * channels[b] < 1; a frame of more than DSN_PCM_MAX_FRAME_BYTES bytes; downmix with Cout != 1; without downmix
  * channels[b] > Cout; an item whose bytes leave [0, nbytes); lens[r] outside [1, Lmax]; rows of the encoder whose
- * payloads overlap or leave the buffer. */
+ * payloads overlap or leave the buffer; (encode_frames) C < 1 or channels[r] outside [1, C]. */
 enum { DSN_PCM_U8 = 0, DSN_PCM_S16 = 1, DSN_PCM_S24 = 2, DSN_PCM_S32 = 3, DSN_PCM_F32 = 4, DSN_PCM_F64 = 5 };
 #define DSN_PCM_MAX_FRAME_BYTES 48
 int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const int64_t* offset, const int32_t* frames,
@@ -655,6 +698,9 @@ int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const
                    void* stream);
 int dsn_pcm_encode(dsn_ctx* ctx, const float* x, int R, int Lmax, const int32_t* lens, int encoding, void* bytes,
                    int64_t nbytes, const int64_t* offset, int64_t* clipped, void* stream);
+int dsn_pcm_encode_frames(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens,
+                          const int32_t* channels, int encoding, void* bytes, int64_t nbytes, const int64_t* offset,
+                          int64_t* clipped, void* stream);
 int dsn_scale_output(dsn_ctx* ctx, const float* mix, const float* sep, int B, int n, int Lmax, const int32_t* lens,
                      float* out, float* alpha_out, void* stream);
 
