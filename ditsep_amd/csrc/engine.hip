@@ -2493,11 +2493,14 @@ int dsn_ode_sample(dsn_ctx* ctx, const float* y, const float* noise, uint64_t se
   });
 }
 
-int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t, const float* noise,
-                   const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out, float* t_out, float* sigma_out,
-                   float* z_out, int B, int T, const DsnLossOpts* o, void* stream) {
+// dsn_score_loss (ragged == false) and dsn_score_loss_ragged (frames: HOST [B])
+static int score_loss_call(dsn_ctx* ctx, const float* y, const float* x0, const int32_t* frames, bool ragged,
+                           const float* t, const float* noise, const int32_t* perm, uint64_t seed, float* loss_out,
+                           float* xt_out, float* t_out, float* sigma_out, float* z_out, int B, int T,
+                           const DsnLossOpts* o, void* stream) {
   return guarded(ctx, [&] {
     if (!y || !x0 || !o || B <= 0 || T <= 0 || B > 65535) fail(DSN_EINVAL, "dsn_score_loss: bad arguments");
+    if (ragged) ctx->check_frames("dsn_score_loss_ragged", frames, B, T);
     if (o->mode != DSN_LOSS_DSM && o->mode != DSN_LOSS_INIT_PIT)
       fail(DSN_EINVAL, "dsn_score_loss: mode %d is neither DSN_LOSS_DSM nor DSN_LOSS_INIT_PIT", o->mode);
     if (o->reduction != DSN_LOSS_REDUCE_NONE && o->reduction != DSN_LOSS_REDUCE_MEAN)
@@ -2552,6 +2555,9 @@ int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t
     double* part = ctx->wsbuf<double>("loss_part", (long)B * n * n * chunks);
     double* rows = ctx->wsbuf<double>("loss_rows", (long)B * n);
     float* lo = ctx->wsbuf<float>("loss_out", (long)B * n);
+    // the token counts 1 + frames[b] of the length-aware attention, which the loss kernels read as well: uploaded
+    // outside the capture, so the lengths are data of the cached graph
+    const int* tok = ragged ? ctx->upload_lens(frames, B, caller) : nullptr;
     dsn_ctx::StreamScope sc(ctx, caller);
     hipStream_t st = sc.st;
     HIPCHK(hipMemcpyAsync(yb, y, sizeof(float) * ysz, hipMemcpyDeviceToDevice, st));
@@ -2561,15 +2567,15 @@ int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t
     else if (!pit) launch_rand_uniform(tin, B, seed ^ 0x9E3779B97F4A7C15ULL, 0, o->t_eps, 1.f, st);
     if (perm) HIPCHK(hipMemcpyAsync(pb, perm, sizeof(int) * B * n, hipMemcpyDeviceToDevice, st));
     char key[160];
-    snprintf(key, sizeof key, "loss:%d:%d:%d:%d:%d:%d", B, T, o->mode, o->reduction, perm != nullptr,
-             loss_out != nullptr);
+    snprintf(key, sizeof key, "loss:%d:%d:%d:%d:%d:%d:%d", B, T, o->mode, o->reduction, perm != nullptr,
+             loss_out != nullptr, ragged);
     ctx->run_graphed(key, st, [&](hipStream_t s2) {
       launch_loss_perturb(q, yb, xb, nz, pit ? nullptr : tin, 1.f, perm ? pb : nullptr, pit, xt, tv, sg, B, n, Dl, T,
-                          s2);
+                          s2, tok);
       if (!loss_out) return;
-      const float* sc = ctx->score_tokens(xt, tv, yb, B, T, s2);
-      launch_loss_reduce(q, sc, nz, yb, xb, tv, sg, pit, part, B, n, Dl, T, s2);
-      launch_loss_combine(part, rows, lo, B, n, nj, chunks, DT, o->reduction == DSN_LOSS_REDUCE_MEAN, s2);
+      const float* sc = ctx->score_tokens(xt, tv, yb, B, T, s2, tok);
+      launch_loss_reduce(q, sc, nz, yb, xb, tv, sg, pit, part, B, n, Dl, T, s2, tok);
+      launch_loss_combine(part, rows, lo, B, n, nj, chunks, Dl, T, o->reduction == DSN_LOSS_REDUCE_MEAN, s2, tok);
     });
     if (loss_out) {
       const long cnt = o->reduction == DSN_LOSS_REDUCE_MEAN ? 1 : (long)B * n;
@@ -2582,6 +2588,21 @@ int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t
     sc.leave();
     HIPCHK(hipGetLastError());
   });
+}
+
+int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t, const float* noise,
+                   const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out, float* t_out, float* sigma_out,
+                   float* z_out, int B, int T, const DsnLossOpts* o, void* stream) {
+  return score_loss_call(ctx, y, x0, nullptr, false, t, noise, perm, seed, loss_out, xt_out, t_out, sigma_out, z_out, B,
+                         T, o, stream);
+}
+
+int dsn_score_loss_ragged(dsn_ctx* ctx, const float* y, const float* x0, const int32_t* frames, const float* t,
+                          const float* noise, const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out,
+                          float* t_out, float* sigma_out, float* z_out, int B, int T, const DsnLossOpts* o,
+                          void* stream) {
+  return score_loss_call(ctx, y, x0, frames, true, t, noise, perm, seed, loss_out, xt_out, t_out, sigma_out, z_out, B, T,
+                         o, stream);
 }
 
 int dsn_hop_length(const dsn_ctx* ctx) { return ctx ? ctx->hop() : DSN_EINVAL; }
@@ -3867,8 +3888,9 @@ static const float* mrstft_window(dsn_ctx* ctx, int fft, int win) {
 // auraloss.py::MultiResolutionSTFTLoss and losses.py::L1Loss / MSELoss under PITLoss, restated in
 // tests/mrstft_restatement.py).  Device: prefilter, spectra and every sum (mrstft.hip); host: the windows, the launch
 // plan and the zeroing of the terms whose weight is zero.
-int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int B, int n, int L,
-                    const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream) {
+// dsn_mrstft_loss (lens == null) and dsn_mrstft_loss_ragged (lens: HOST [B])
+static int mrstft_call(dsn_ctx* ctx, const float* reals, const float* decoded, const int32_t* lens, bool ragged, int B,
+                       int n, int L, const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream) {
   return guarded(ctx, [&] {
     if (!reals || !decoded || !cfg || !out || B <= 0 || n <= 0 || L <= 0)
       fail(DSN_EINVAL, "dsn_mrstft_loss: bad arguments (reals, decoded, cfg, out non-null, B, n, L > 0)");
@@ -3888,6 +3910,13 @@ int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int 
     }
     if (L <= max_fft / 2)
       fail(DSN_EINVAL, "dsn_mrstft_loss: L = %d needs reflect padding of %d samples (L must exceed it)", L, max_fft / 2);
+    if (ragged) {
+      check_item_lens("dsn_mrstft_loss_ragged", lens, B, L);
+      for (int b = 0; b < B; ++b)
+        if (lens[b] <= max_fft / 2)
+          fail(DSN_EINVAL, "dsn_mrstft_loss_ragged: lens[%d] = %d needs reflect padding of %d samples (it must exceed "
+               "it)", b, lens[b], max_fft / 2);
+    }
     const bool filter = R > 0 && cfg->taps != nullptr;
     if (filter && (cfg->n_taps < 1 || cfg->n_taps % 2 == 0 || cfg->n_taps > MRSTFT_MAX_TAPS))
       fail(DSN_EINVAL, "dsn_mrstft_loss: %d prefilter taps (odd, at most %d)", cfg->n_taps, MRSTFT_MAX_TAPS);
@@ -3895,7 +3924,9 @@ int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int 
     const long per = (long)B * n * n, sig = (long)B * n * L;
     MrstftPlan plan;
     plan.R = R;
-    for (int r = 0; r < R; ++r) mrstft_plan_resolution(&plan, r, cfg->fft[r], cfg->hop[r], B, L);
+    const std::vector<int> hl(lens, lens + (ragged ? B : 0));
+    for (int r = 0; r < R; ++r)
+      mrstft_plan_resolution(&plan, r, cfg->fft[r], cfg->hop[r], B, L, ragged ? hl.data() : nullptr);
     const long nparts = R ? plan.off[R - 1] + (long)B * plan.wgs[R - 1] * MRSTFT_SACC : 1;
     std::vector<const float*> wins(R);
     for (int r = 0; r < R; ++r) wins[r] = mrstft_window(ctx, cfg->fft[r], cfg->win[r]);
@@ -3912,9 +3943,11 @@ int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int 
       yf = xf + sig;
       HIPCHK(hipMemcpyAsync(dtaps, cfg->taps, sizeof(float) * cfg->n_taps, hipMemcpyHostToDevice, st));
     }
-    launch_mrstft_time(reals, decoded, B, n, L, dtaps, filter ? cfg->n_taps : 0, xf, yf, tpart, st);
-    for (int r = 0; r < R; ++r) launch_mrstft_spec(plan, r, reals, decoded, xf, yf, wins[r], B, n, L, part, st);
-    launch_mrstft_finish(plan, part, tpart, B, n, L, d_sc, d_lg, d_lin, d_l1, d_l2, st);
+    // the lengths on the device (hl outlives the copy: the call ends with a synchronisation)
+    const int* dl = ragged ? upload_item_ints(ctx, "mrstft_lens", hl, st) : nullptr;
+    launch_mrstft_time(reals, decoded, B, n, L, dtaps, filter ? cfg->n_taps : 0, xf, yf, tpart, st, dl);
+    for (int r = 0; r < R; ++r) launch_mrstft_spec(plan, r, reals, decoded, xf, yf, wins[r], B, n, L, part, st, dl);
+    launch_mrstft_finish(plan, part, tpart, B, n, L, d_sc, d_lg, d_lin, d_l1, d_l2, st, dl);
     HIPCHK(hipGetLastError());
     // a term whose weight is zero is the reference's constant 0.0 (STFTLoss.forward skips it)
     const struct { double* host; const double* dev; long count; bool on; } copies[5] = {
@@ -3930,6 +3963,16 @@ int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int 
     }
     HIPCHK(hipStreamSynchronize(st));
   });
+}
+
+int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int B, int n, int L,
+                    const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream) {
+  return mrstft_call(ctx, reals, decoded, nullptr, false, B, n, L, cfg, out, stream);
+}
+
+int dsn_mrstft_loss_ragged(dsn_ctx* ctx, const float* reals, const float* decoded, const int32_t* lens, int B, int n,
+                           int L, const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream) {
+  return mrstft_call(ctx, reals, decoded, lens, true, B, n, L, cfg, out, stream);
 }
 
 // Development hook: copy `count` floats of the named workspace buffer to host memory.

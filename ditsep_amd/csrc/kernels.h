@@ -269,21 +269,41 @@ struct MrstftPlan {
   long off[MRSTFT_MAX_RES];
 };
 bool mrstft_fft_ok(int fft);   // a power of two in [32, 2048]
-int mrstft_time_chunks(int L);
-// fills entry r (entries 0 .. r-1 must be filled: off accumulates)
-void mrstft_plan_resolution(MrstftPlan* plan, int r, int fft, int hop, int B, int L);
+__host__ __device__ inline int mrstft_time_chunks(int L) { return (L + MRSTFT_TCHUNK - 1) / MRSTFT_TCHUNK; }
+// The spectral stage's partition of one item's F = 1 + L / hop frames: groups of 2048 / fft consecutive frames, gpw
+// groups per workgroup, wgs workgroups -- about 1024 workgroups per launch over the B items that share the plan.
+// The dense call plans once with its B and L; a ragged call plans every item as a batch of one with its own length
+// (on the host for the grid, in the kernels for the item), so an item's partition never depends on its neighbours.
+struct MrstftSplit {
+  int F, gpw, wgs;
+};
+__host__ __device__ inline MrstftSplit mrstft_split(int fft, int hop, int B, int L) {
+  const int F = 1 + L / hop, fpg = 2048 / fft, groups = (F + fpg - 1) / fpg;
+  const int cap = (1024 + B - 1) / B, lim = groups < cap ? groups : cap, want = lim > 1 ? lim : 1;
+  const int gpw = (groups + want - 1) / want;
+  return {F, gpw, (groups + gpw - 1) / gpw};
+}
+// fills entry r (entries 0 .. r-1 must be filled: off accumulates).  lens (host [B], nullable): the ragged plan --
+// wgs[r] is the largest count any item needs (the launch grid and the stride of the partials); frames / gpw are unused
+void mrstft_plan_resolution(MrstftPlan* plan, int r, int fft, int hop, int B, int L, const int* lens = nullptr);
+// The three launches below take lens [B] (device, nullable): item b holds lens[b] <= L samples in its rows of stride
+// L.  Its frames reflect at its own end, the prefilter reads zero past it, nothing at or past lens[b] is read or
+// written, and its partials are those of mrstft_split(fft, hop, 1, lens[b]) and of the time chunks below lens[b];
+// the workgroups past them leave at once and finish does not read their slots.
 // x = reals, y = decoded [B][n][L] -> tpart [B][chunks][MRSTFT_TACC] (sum |r_i - d_j|, sum (r_i - d_j)^2) and, with
 // taps [ntaps] (device, fp32, ntaps odd <= MRSTFT_MAX_TAPS), xf / yf [B][n][L] = conv1d(., taps, padding = ntaps / 2)
 // in fp64
 void launch_mrstft_time(const float* x, const float* y, int B, int n, int L, const float* taps, int ntaps, double* xf,
-                        double* yf, double* tpart, hipStream_t s);
+                        double* yf, double* tpart, hipStream_t s, const int* lens = nullptr);
 // resolution r: the signals [B][n][L] are xr64 / xd64 (the prefiltered ones) or, when those are null, xr / xd;
 // win [fft] the window zero-padded to the FFT length -> part + plan.off[r]
 void launch_mrstft_spec(const MrstftPlan& plan, int r, const float* xr, const float* xd, const double* xr64,
-                        const double* xd64, const float* win, int B, int n, int L, double* part, hipStream_t s);
+                        const double* xd64, const float* win, int B, int n, int L, double* part, hipStream_t s,
+                        const int* lens = nullptr);
 // partials -> sc / lg / lin [R][B][n][n], l1 / l2 [B][n][n] (fp64, device)
 void launch_mrstft_finish(const MrstftPlan& plan, const double* part, const double* tpart, int B, int n, int L,
-                          double* sc, double* lg, double* lin, double* l1, double* l2, hipStream_t s);
+                          double* sc, double* lg, double* lin, double* l1, double* l2, hipStream_t s,
+                          const int* lens = nullptr);
 
 // ---- probability-flow ODE sampler (ode.hip) ---------------------------------------------------------------
 // Explicit embedded Runge-Kutta pair with scipy 1.15's solve_ivp step control on the fp64 state y [B,n,D,T].
@@ -343,22 +363,27 @@ struct LossSde {
   double theta, sigma_min, logsig;
 };
 #define DSN_LOSS_CHUNK 2048   // elements of one (item, source) row a workgroup sums
-inline int loss_chunks(int D, int T) { return (int)(((long)D * T + DSN_LOSS_CHUNK - 1) / DSN_LOSS_CHUNK); }
+__host__ __device__ inline int loss_chunks(int D, int T) { return (int)(((long)D * T + DSN_LOSS_CHUNK - 1) / DSN_LOSS_CHUNK); }
 // perturb, one launch over [B,n,D,T]:  pit = 0: x_t = (e x0[b, perm[b,s]] + (1 - e) y) + sigma(t_b) z  (perm nullable:
 // identity);  pit = 1: x_t = y + sigma(t_b) z.  Also writes tv [B] = t (the score call's time vector) and sigma [B].
 // t_in nullable: every item at t_const (pit mode: T = 1).
+// The three launches take tok [B] (device, nullable): the ragged form, tok[b] = 1 + frames[b], the token counts the
+// length-aware attention kernels read.  perturb then writes x_t[b, :, :, frames[b]:] as zero and reads neither x0, z
+// nor y there; reduce and combine walk the D frames[b] valid elements of a row in (channel, frame) order, cut into
+// chunks of DSN_LOSS_CHUNK from the row's start, so an item's sums depend on its own length alone.
 void launch_loss_perturb(const LossSde& q, const float* y, const float* x0, const float* z, const float* t_in,
                          float t_const, const int* perm, int pit, float* xt, float* tv, float* sigma, int B, int n,
-                         int D, int T, hipStream_t s);
+                         int D, int T, hipStream_t s, const int* tok = nullptr);
 // reduce: part[((b n + s) nj + j) chunks + c] = fp64 sum over chunk c of row (b, s) of (sigma s_theta + z_j)^2 with
 // score token-major [B*T][n*D].  pit = 0: nj = 1, z_0 = z.  pit = 1: nj = n, z_j = z + (y - mean(x0[b, j])) / sigma.
 void launch_loss_reduce(const LossSde& q, const float* score_tok, const float* z, const float* y, const float* x0,
                         const float* tv, const float* sigma, int pit, double* part, int B, int n, int D, int T,
-                        hipStream_t s);
+                        hipStream_t s, const int* tok = nullptr);
 // combine (one workgroup, fixed order): row[b n + s] = min_j (sum_c part) / (D T); mean_reduction = 0: out [B n] =
-// (float)row, else out [1] = (float)(sum row / (B n)).  rows [B n] fp64 is scratch.
-void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, long DT,
-                         int mean_reduction, hipStream_t s);
+// (float)row, else out [1] = (float)(sum row / (B n)).  rows [B n] fp64 is scratch.  chunks is the stride of part
+// (loss_chunks(D, T)); with tok a row sums its own loss_chunks(D, frames[b]) chunks and divides by D frames[b].
+void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, int D, int T,
+                         int mean_reduction, hipStream_t s, const int* tok = nullptr);
 
 // ---- sinc resampling (resample.hip) -------------------------------------------------------------------------
 // x [B][C][L] -> out [B][C or 1][Lout] by the compact polyphase table of resample_plan.h: taps [n][stride] (row p holds

@@ -13,6 +13,12 @@
 // so the n x n table  L[s][j] = mean_{D,T} (sigma score[s] + z0[s] + (y - mean(x0[j])) / sigma)^2  holds every
 // permutation's loss, and the reference's stack(dim=1).min(dim=1) -- a minimum per (item, slot) -- is min_j L[s][j]
 // (every source occupies every slot in some permutation).  One score call instead of n!.
+//
+// Ragged batches (tok non-null: tok[b] = 1 + frames[b], the token counts the length-aware attention reads): item b's
+// valid elements are [.., :frames[b]] of its rows of stride T.  perturb forms exactly the dense value there, writes
+// x_t as zero past the end and reads nothing else there; reduce and combine walk the D frames[b] valid elements of a
+// row in (channel, frame) order, chunked from the row's start, and divide by D frames[b]: the same fp64 terms in an
+// order that depends on the item's own length only, whatever the padding and the batch around it.
 #include "../../include/ditsep_hip.h"
 #include "kernels.h"
 
@@ -46,7 +52,8 @@ __device__ double loss_block_sum(double v, double* red) {
 __global__ void loss_perturb_kernel(const LossSde q, const float* __restrict__ y, const float* __restrict__ x0,
                                     const float* __restrict__ z, const float* __restrict__ t_in, float t_const,
                                     const int* __restrict__ perm, int pit, float* __restrict__ xt,
-                                    float* __restrict__ tv, float* __restrict__ sigma, int n, long DT) {
+                                    float* __restrict__ tv, float* __restrict__ sigma, int n, long DT, int T,
+                                    const int* __restrict__ tok) {
   const int b = blockIdx.y;
   const float tf = t_in ? t_in[b] : t_const;
   const float e = (float)loss_decay(q, (double)tf);
@@ -57,11 +64,16 @@ __global__ void loss_perturb_kernel(const LossSde q, const float* __restrict__ y
   }
   const long per_item = (long)n * DT;
   const float ome = 1.f - e;
+  const int fb = tok ? tok[b] - 1 : T;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < per_item; i += (long)gridDim.x * blockDim.x) {
     const int s = (int)(i / DT);
     const long r = i - (long)s * DT;
-    const float ym = y[b * DT + r];
     const long xi = (long)b * per_item + i;
+    if (tok && (int)(r % T) >= fb) {  // past the item's end: zero, and nothing is read
+      xt[xi] = 0.f;
+      continue;
+    }
+    const float ym = y[b * DT + r];
     float v;
     if (pit) {
       v = ym + sg * z[xi];
@@ -78,20 +90,24 @@ __global__ void loss_perturb_kernel(const LossSde q, const float* __restrict__ y
 __global__ void loss_reduce_kernel(const LossSde q, const float* __restrict__ sc, const float* __restrict__ z,
                                    const float* __restrict__ y, const float* __restrict__ x0,
                                    const float* __restrict__ tv, const float* __restrict__ sigma, int pit,
-                                   double* __restrict__ part, int n, int D, int T) {
+                                   double* __restrict__ part, int n, int D, int T, const int* __restrict__ tok) {
   __shared__ double red[LTPB / 64];
   const int c = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
   const int chunks = gridDim.x;
   const long DT = (long)D * T;
+  const int fb = tok ? tok[b] - 1 : T;  // the row's valid frames
+  const long DF = (long)D * fb;
+  if ((long)c * DSN_LOSS_CHUNK >= DF) return;  // uniform: a chunk past the item's end
   const double sg = (double)sigma[b];
   const double e = (double)(float)loss_decay(q, (double)tv[b]);
   const double ome = (double)(1.f - (float)e);
   const long r0 = (long)c * DSN_LOSS_CHUNK;
-  const long r1 = r0 + DSN_LOSS_CHUNK < DT ? r0 + DSN_LOSS_CHUNK : DT;
+  const long r1 = r0 + DSN_LOSS_CHUNK < DF ? r0 + DSN_LOSS_CHUNK : DF;
   const int nj = pit ? n : 1;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
-    const int ch = (int)(r / T), t = (int)(r - (long)ch * T);
+  for (long k = r0 + threadIdx.x; k < r1; k += blockDim.x) {
+    const int ch = (int)(k / fb), t = (int)(k - (long)ch * fb);
+    const long r = (long)ch * T + t;  // (k itself when fb == T)
     const double sv = (double)sc[((long)b * T + t) * ((long)n * D) + (long)s * D + ch];
     const double base = sg * sv + (double)z[((long)b * n + s) * DT + r];
     if (!pit) {
@@ -118,15 +134,17 @@ __global__ void loss_reduce_kernel(const LossSde q, const float* __restrict__ sc
 }
 
 __global__ void loss_combine_kernel(const double* __restrict__ part, double* __restrict__ rows,
-                                    float* __restrict__ out, int rows_n, int nj, int chunks, double len,
-                                    int mean_reduction) {
+                                    float* __restrict__ out, int rows_n, int nj, int chunks, int n, int D, int T,
+                                    int mean_reduction, const int* __restrict__ tok) {
   __shared__ double red[LTPB / 64];
   double acc = 0.0;
   for (int i = threadIdx.x; i < rows_n; i += blockDim.x) {
     double best = 0.0;
+    const int fb = tok ? tok[i / n] - 1 : T, own = tok ? loss_chunks(D, fb) : chunks;  // chunks stays the stride
+    const double len = (double)((long)D * fb);
     for (int j = 0; j < nj; ++j) {
       double v = 0.0;
-      for (int c = 0; c < chunks; ++c) v += part[((long)i * nj + j) * chunks + c];
+      for (int c = 0; c < own; ++c) v += part[((long)i * nj + j) * chunks + c];
       v /= len;
       if (j == 0 || v < best) best = v;
     }
@@ -144,23 +162,23 @@ __global__ void loss_combine_kernel(const double* __restrict__ part, double* __r
 
 void launch_loss_perturb(const LossSde& q, const float* y, const float* x0, const float* z, const float* t_in,
                          float t_const, const int* perm, int pit, float* xt, float* tv, float* sigma, int B, int n,
-                         int D, int T, hipStream_t s) {
+                         int D, int T, hipStream_t s, const int* tok) {
   const long DT = (long)D * T, per_item = DT * n;
   long gx = (per_item + 4L * LTPB - 1) / (4L * LTPB);
   if (gx > 256) gx = 256;
   hipLaunchKernelGGL(loss_perturb_kernel, dim3((unsigned)gx, (unsigned)B), dim3(LTPB), 0, s, q, y, x0, z, t_in,
-                     t_const, perm, pit, xt, tv, sigma, n, DT);
+                     t_const, perm, pit, xt, tv, sigma, n, DT, T, tok);
 }
 
 void launch_loss_reduce(const LossSde& q, const float* score_tok, const float* z, const float* y, const float* x0,
                         const float* tv, const float* sigma, int pit, double* part, int B, int n, int D, int T,
-                        hipStream_t s) {
+                        hipStream_t s, const int* tok) {
   hipLaunchKernelGGL(loss_reduce_kernel, dim3((unsigned)loss_chunks(D, T), (unsigned)n, (unsigned)B), dim3(LTPB), 0, s,
-                     q, score_tok, z, y, x0, tv, sigma, pit, part, n, D, T);
+                     q, score_tok, z, y, x0, tv, sigma, pit, part, n, D, T, tok);
 }
 
-void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, long DT,
-                         int mean_reduction, hipStream_t s) {
-  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(LTPB), 0, s, part, rows, out, B * n, nj, chunks,
-                     (double)DT, mean_reduction);
+void launch_loss_combine(const double* part, double* rows, float* out, int B, int n, int nj, int chunks, int D, int T,
+                         int mean_reduction, hipStream_t s, const int* tok) {
+  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(LTPB), 0, s, part, rows, out, B * n, nj, chunks, n,
+                     D, T, mean_reduction, tok);
 }

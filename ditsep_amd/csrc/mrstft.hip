@@ -14,6 +14,12 @@
 //            log mag_d|, sum |mag_r - mag_d| and, per estimate, sum mag_d^2 in fp64.  No magnitude goes to memory.
 //   finish   the workgroup partials summed in index order in fp64 -> the pair tables
 // Every reduction has a fixed order (no atomics): two calls on the same input give bit-identical results.
+// Ragged batches (lens non-null in all three kernels): item b holds lens[b] samples in rows of stride L.  Its frames,
+// its reflection, the zero past the end that the prefilter reads and the divisors are those of its own length, and
+// its partition into workgroup partials is the one the item gets as a batch of one (mrstft_split(fft, hop, 1,
+// lens[b]); time chunks from the item's start), so its tables have the same bits alone, at any batch position and
+// under any padding.  Workgroups an item does not need leave before their first barrier and write nothing; finish
+// sums the item's own partials only.
 // The filtered signals, the windowed frames and the transforms are fp64: the A-weighted spectra span more than 80 dB,
 // the log-magnitude term weighs every bin alike, and on a single resolution with few frames the float32 rounding of
 // the filtered signal alone moves that term by up to 1.2e-6 (the fp32 FFT by 1.6e-6, measured), past the 1e-6 the
@@ -54,13 +60,16 @@ template <bool FILTER>
 __global__ __launch_bounds__(kThreads) void mrstft_time_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                int n, int L, const float* __restrict__ taps, int ntaps,
                                                                double* __restrict__ xf, double* __restrict__ yf,
-                                                               double* __restrict__ tpart) {
+                                                               double* __restrict__ tpart,
+                                                               const int* __restrict__ lens) {
   constexpr int kHalo = MRSTFT_MAX_TAPS - 1;
   __shared__ float sig[FILTER ? 2 * kMaxSrc : 1][FILTER ? MRSTFT_TCHUNK + kHalo : 1];
   __shared__ double tp[FILTER ? MRSTFT_MAX_TAPS : 1];
   __shared__ double red[4];
   const int b = blockIdx.y, c = blockIdx.x, chunks = gridDim.x;
-  const int t0 = c * MRSTFT_TCHUNK, tn = min(MRSTFT_TCHUNK, L - t0);
+  const int Lb = lens ? lens[b] : L;  // the item's samples; the rows keep the stride L
+  const int t0 = c * MRSTFT_TCHUNK, tn = min(MRSTFT_TCHUNK, Lb - t0);
+  if (tn <= 0) return;  // uniform: a chunk past the item's end
   const float* xb = x + (long)b * n * L;
   const float* yb = y + (long)b * n * L;
   double a1[kMaxSrc][kMaxSrc], a2[kMaxSrc][kMaxSrc];
@@ -104,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void mrstft_time_kernel(const float* __re
       const float* src = (s < n ? xb : yb) + (long)(s < n ? s : s - n) * L;
       for (int q = threadIdx.x; q < span; q += kThreads) {
         const int t = t0 - half + q;
-        sig[s][q] = (t >= 0 && t < L) ? src[t] : 0.f;
+        sig[s][q] = (t >= 0 && t < Lb) ? src[t] : 0.f;
       }
     }
     __syncthreads();
@@ -133,7 +142,8 @@ __global__ __launch_bounds__(kSpecThreads) void mrstft_spec_kernel(const float* 
                                                                    const double* __restrict__ xd64,
                                                                    const float* __restrict__ win, int n, int L,
                                                                    int hop, int F, int gpw,
-                                                                   double* __restrict__ part) {
+                                                                   double* __restrict__ part,
+                                                                   const int* __restrict__ lens) {
   constexpr int kThreads = kSpecThreads;
   static_assert(NFFT >= 32 && NFFT <= kPoints && (NFFT & (NFFT - 1)) == 0, "FFT size");
   constexpr int FPG = kPoints / NFFT, LOG = __builtin_ctz(NFFT), NB = NFFT / 2 + 1, HALF = NFFT / 2;
@@ -143,12 +153,20 @@ __global__ __launch_bounds__(kSpecThreads) void mrstft_spec_kernel(const float* 
   double2* tw = smem;
   double2* buf = smem + HALF;
   const int b = blockIdx.y, w = blockIdx.x, tid = threadIdx.x;
+  const int rowL = L;  // stride of a signal's row
+  if (lens) {          // the item's own length and its own partition (uniform)
+    L = lens[b];
+    const MrstftSplit sp = mrstft_split(NFFT, hop, 1, L);
+    F = sp.F;
+    gpw = sp.gpw;
+    if (w >= sp.wgs) return;
+  }
   for (int t = tid; t < HALF; t += kThreads) {
     double s, c;
     sincospi((double)t / HALF, &s, &c);  // exp(-2 pi i t / NFFT)
     tw[t] = make_double2(c, -s);
   }
-  const long boff = (long)b * n * L;
+  const long boff = (long)b * n * rowL;
   const bool wide = xr64 != nullptr;  // uniform
   const int groups = (F + FPG - 1) / FPG;
   const int g1 = min(groups, (w + 1) * gpw);
@@ -177,7 +195,7 @@ __global__ __launch_bounds__(kSpecThreads) void mrstft_spec_kernel(const float* 
 #pragma unroll
       for (int i = 0; i < kMaxSrc; ++i)
         if (i < n) {
-          const long at = boff + (long)i * L + idx;
+          const long at = boff + (long)i * rowL + idx;
           double r = 0.0, d = 0.0;
           if (valid) {
             r = wide ? xr64[at] : (double)xr[at];
@@ -276,34 +294,38 @@ __global__ __launch_bounds__(kThreads) void mrstft_finish_kernel(MrstftPlan plan
                                                                  const double* __restrict__ tpart, int B, int n, int L,
                                                                  int tchunks, double* __restrict__ sc,
                                                                  double* __restrict__ lg, double* __restrict__ lin,
-                                                                 double* __restrict__ l1, double* __restrict__ l2) {
+                                                                 double* __restrict__ l1, double* __restrict__ l2,
+                                                                 const int* __restrict__ lens) {
   const long per = (long)B * n * n, e = (long)blockIdx.x * kThreads + threadIdx.x;
   if (e >= per * (plan.R + 1)) return;
   const int r = (int)(e / per);
   const long o = e - (long)r * per;
   const int j = (int)(o % n), i = (int)((o / n) % n), b = (int)(o / ((long)n * n));
+  const int Lb = lens ? lens[b] : L;
   if (r == plan.R) {
     double s1 = 0.0, s2 = 0.0;
-    for (int c = 0; c < tchunks; ++c) {
+    const int own = lens ? mrstft_time_chunks(Lb) : tchunks;  // tchunks stays the stride
+    for (int c = 0; c < own; ++c) {
       const double* p = tpart + ((long)b * tchunks + c) * MRSTFT_TACC + (i * kMaxSrc + j) * 2;
       s1 += p[0];
       s2 += p[1];
     }
-    l1[o] = s1 / L;
-    l2[o] = s2 / L;
+    l1[o] = s1 / Lb;
+    l2[o] = s2 / Lb;
     return;
   }
-  const int W = plan.wgs[r];
+  const int W = plan.wgs[r];  // the stride; a ragged item sums its own workgroups
+  const MrstftSplit sp = lens ? mrstft_split(plan.fft[r], plan.hop[r], 1, Lb) : MrstftSplit{plan.frames[r], 0, W};
   const double* base = part + plan.off[r] + (long)b * W * MRSTFT_SACC;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, sd = 0.0;
-  for (int w = 0; w < W; ++w) {
+  for (int w = 0; w < sp.wgs; ++w) {
     const double* p = base + (long)w * MRSTFT_SACC;
     s0 += p[(i * kMaxSrc + j) * 3];
     s1 += p[(i * kMaxSrc + j) * 3 + 1];
     s2 += p[(i * kMaxSrc + j) * 3 + 2];
     sd += p[kMaxSrc * kMaxSrc * 3 + j];
   }
-  const double cnt = (double)(plan.fft[r] / 2 + 1) * plan.frames[r];
+  const double cnt = (double)(plan.fft[r] / 2 + 1) * sp.F;
   sc[(long)r * per + o] = sqrt(s0) / sqrt(sd);
   lg[(long)r * per + o] = s1 / cnt;
   lin[(long)r * per + o] = s2 / cnt;
@@ -311,59 +333,60 @@ __global__ __launch_bounds__(kThreads) void mrstft_finish_kernel(MrstftPlan plan
 
 template <int NFFT>
 void launch_spec(const float* xr, const float* xd, const double* xr64, const double* xd64, const float* win, int B,
-                 int n, int L, int hop, int F, int wgs, int gpw, double* part, hipStream_t st) {
+                 int n, int L, int hop, int F, int wgs, int gpw, double* part, hipStream_t st, const int* lens) {
   const size_t smem = ((size_t)NFFT / 2 + (size_t)n * kPoints) * sizeof(double2);
   dsn_allow_lds<mrstft_spec_kernel<NFFT>>((int)((NFFT / 2 + kMaxSrc * kPoints) * sizeof(double2)));
   hipLaunchKernelGGL((mrstft_spec_kernel<NFFT>), dim3(wgs, B), dim3(kSpecThreads), smem, st, xr, xd, xr64, xd64, win, n,
-                     L, hop, F, gpw, part);
+                     L, hop, F, gpw, part, lens);
 }
 
 }  // namespace
 
 bool mrstft_fft_ok(int fft) { return fft >= 32 && fft <= kPoints && (fft & (fft - 1)) == 0; }
 
-int mrstft_time_chunks(int L) { return (L + MRSTFT_TCHUNK - 1) / MRSTFT_TCHUNK; }
-
-void mrstft_plan_resolution(MrstftPlan* plan, int r, int fft, int hop, int B, int L) {
-  const int F = 1 + L / hop, fpg = kPoints / fft, groups = (F + fpg - 1) / fpg;
-  // about 1024 workgroups per launch, whatever the batch
-  const int want = std::max(1, std::min(groups, (1024 + B - 1) / B));
-  const int gpw = (groups + want - 1) / want;
+void mrstft_plan_resolution(MrstftPlan* plan, int r, int fft, int hop, int B, int L, const int* lens) {
+  static_assert(kPoints == 2048, "mrstft_split groups 2048 / fft frames");
+  MrstftSplit sp = mrstft_split(fft, hop, B, L);
+  if (lens) {
+    sp = {0, 0, 0};
+    for (int b = 0; b < B; ++b) sp.wgs = std::max(sp.wgs, mrstft_split(fft, hop, 1, lens[b]).wgs);
+  }
   plan->fft[r] = fft;
   plan->hop[r] = hop;
-  plan->frames[r] = F;
-  plan->gpw[r] = gpw;
-  plan->wgs[r] = (groups + gpw - 1) / gpw;
+  plan->frames[r] = sp.F;
+  plan->gpw[r] = sp.gpw;
+  plan->wgs[r] = sp.wgs;
   plan->off[r] = r == 0 ? 0 : plan->off[r - 1] + (long)B * plan->wgs[r - 1] * MRSTFT_SACC;
 }
 
 void launch_mrstft_time(const float* x, const float* y, int B, int n, int L, const float* taps, int ntaps, double* xf,
-                        double* yf, double* tpart, hipStream_t st) {
+                        double* yf, double* tpart, hipStream_t st, const int* lens) {
   const dim3 grid(mrstft_time_chunks(L), B);
   if (taps)
-    hipLaunchKernelGGL(mrstft_time_kernel<true>, grid, dim3(kThreads), 0, st, x, y, n, L, taps, ntaps, xf, yf, tpart);
+    hipLaunchKernelGGL(mrstft_time_kernel<true>, grid, dim3(kThreads), 0, st, x, y, n, L, taps, ntaps, xf, yf, tpart, lens);
   else
-    hipLaunchKernelGGL(mrstft_time_kernel<false>, grid, dim3(kThreads), 0, st, x, y, n, L, taps, ntaps, xf, yf, tpart);
+    hipLaunchKernelGGL(mrstft_time_kernel<false>, grid, dim3(kThreads), 0, st, x, y, n, L, taps, ntaps, xf, yf, tpart, lens);
 }
 
 void launch_mrstft_spec(const MrstftPlan& plan, int r, const float* xr, const float* xd, const double* xr64,
-                        const double* xd64, const float* win, int B, int n, int L, double* part, hipStream_t st) {
+                        const double* xd64, const float* win, int B, int n, int L, double* part, hipStream_t st,
+                        const int* lens) {
   double* p = part + plan.off[r];
   const int hop = plan.hop[r], F = plan.frames[r], wgs = plan.wgs[r], gpw = plan.gpw[r];
   switch (plan.fft[r]) {
-    case 32: launch_spec<32>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    case 64: launch_spec<64>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    case 128: launch_spec<128>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    case 256: launch_spec<256>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    case 512: launch_spec<512>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    case 1024: launch_spec<1024>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
-    default: launch_spec<2048>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st); break;
+    case 32: launch_spec<32>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    case 64: launch_spec<64>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    case 128: launch_spec<128>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    case 256: launch_spec<256>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    case 512: launch_spec<512>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    case 1024: launch_spec<1024>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
+    default: launch_spec<2048>(xr, xd, xr64, xd64, win, B, n, L, hop, F, wgs, gpw, p, st, lens); break;
   }
 }
 
 void launch_mrstft_finish(const MrstftPlan& plan, const double* part, const double* tpart, int B, int n, int L,
-                          double* sc, double* lg, double* lin, double* l1, double* l2, hipStream_t st) {
+                          double* sc, double* lg, double* lin, double* l1, double* l2, hipStream_t st, const int* lens) {
   const long total = (long)B * n * n * (plan.R + 1);
   hipLaunchKernelGGL(mrstft_finish_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                     plan, part, tpart, B, n, L, mrstft_time_chunks(L), sc, lg, lin, l1, l2);
+                     plan, part, tpart, B, n, L, mrstft_time_chunks(L), sc, lg, lin, l1, l2, lens);
 }

@@ -23,7 +23,9 @@ waveform error of each reference source against the estimate the SIR permutation
 Utterances of different lengths (the reference evaluates them one at a time, :238): a batch whose `mix` and `target`
 are lists of differently long tensors takes the ragged route -- `length_batches` cuts a data set into such batches
 with little padding -- in which every utterance gets what it gets alone (LatentDiffSep.separate_batch) and every
-metric above but mrstft and score_loss is one call on the padded batch with the utterances' lengths.
+metric above is one call on the padded batch with the utterances' lengths.  mrstft and score_loss are refused there
+(NotImplementedError) unless the caller passes ragged_losses=True: they then run as one call each too, under this
+project's definitions for mixed lengths (Engine.score_loss with frames=, Engine.mrstft_loss with lens=).
 
 bss_eval=True adds "sdr", "sir" and "sar" per source from the device (dsn_bss_eval): classic bss_eval (Vincent et al.
 2006) with distortion filters of bss_filter_length taps (512, the bss_eval default, behind the SDRi column of a
@@ -58,17 +60,27 @@ def _pad_items(items, Lmax: int, device) -> torch.Tensor:
 
 
 def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, snr, denoise, stoi, stoi_extended,
-                     codec="grouped", composite=False, pesq_fn=None, bss_eval=False, bss_filter_length=512) -> dict:
+                     codec="grouped", composite=False, pesq_fn=None, bss_eval=False, bss_filter_length=512,
+                     score_loss=False, mrstft=False) -> dict:
     """One batch of differently long utterances: mixes list of [1, L_b], targets list of [n, L_b].  The timed region is
     sampler + decode as in the dense route; every requested metric then runs once on the padded [B, n, Lmax] pair with
-    the items' lengths (Engine.si_bss_eval / stoi / composite with lens=), each item scored as it is alone.  codec: how
-    the encoder and the decoder take the batch (Engine.encode_ragged)."""
+    the items' lengths (Engine.si_bss_eval / stoi / composite / mrstft_loss with lens=), each item scored as it is alone.
+    score_loss: the targets are encoded as B * n rows (seed + idx + 1) and scored by one Engine.score_loss call with the
+    items' frame counts (seed + idx), as the dense route seeds them.  codec: how the encoder and the decoder take the
+    batch (Engine.encode_ragged)."""
     eng, dev = model.engine, model.engine.device
     B = len(mixes)
     y, frames = eng.encode_ragged(mixes, None, seed=seed + idx, codec=codec)
     sampler = model.get_pc_sampler("reverse_diffusion", "ald", y, N=N, denoise=denoise, corrector_steps=corrector_steps,
                                    snr=snr, seed=seed + idx, frames=frames)
     lens = [int(t.shape[-1]) for t in targets]
+    sl = None
+    if score_loss:
+        n0 = targets[0].shape[0]
+        tgt_lat, _ = eng.encode_ragged([t[i:i + 1] for t in targets for i in range(n0)], None, seed=seed + idx + 1,
+                                       codec=codec)
+        sl = eng.score_loss(y, tgt_lat.reshape(B, n0, *tgt_lat.shape[2:]), reduction="none", t_eps=model.t_eps,
+                            seed=seed + idx, frames=frames).cpu()
     torch.cuda.synchronize(dev)
     t_s = time.perf_counter()
     x_result, nfe = sampler()
@@ -86,17 +98,29 @@ def _evaluate_ragged(model, mixes, targets, fs, idx, seed, N, corrector_steps, s
                                                                        est[b][int(perm[b, i])].cpu().numpy())))
                                 for i in range(n_src)] for b in range(B)], dtype=torch.float32)
         comp = eng.composite(tgt, xr, fs, perm=perm, pesq=pq, lens=lens)
+    mr = None
+    if mrstft:
+        tabs = eng.mrstft_loss(tgt, xr, fs, pit=None, lens=lens)
+        rows = torch.arange(n_src)
+        spec = (tabs["sc"] + tabs["log_mag"]).mean(0)                        # [B,n,n]: mean over the resolutions
+        mr = {"mrstft": torch.stack([spec[b, rows, perm[b]] for b in range(B)]),
+              "l1": torch.stack([tabs["l1"][b, rows, perm[b]] for b in range(B)])}
     bss = eng.bss_eval(tgt, xr, filter_length=bss_filter_length, perm=perm, lens=lens)[:3] if bss_eval else None
     records = {}
     for b in range(B):
         rec = {"batch_idx": idx + b, "si_sdr": si_sdr[b].tolist(), "si_sir": si_sir[b].tolist(),
                "si_sar": si_sar[b].tolist(), "pesq": None, "stoi": None if st is None else st[b].tolist(),
                "nfe": nfe, "runtime": t_proc / B, "len_s": lens[b] / fs, "perm": perm[b].tolist()}
+        if sl is not None:
+            rec["score_loss"] = sl[b].tolist()
         if comp is not None:
             for k in ("llr", "wss", "segsnr") + (("csig", "cbak", "covl") if pq is not None else ()):
                 rec[k] = comp[k][b].tolist()
             if pq is not None:
                 rec["pesq"] = pq[b].tolist()
+        if mr is not None:
+            for k in ("mrstft", "l1"):
+                rec[k] = mr[k][b].tolist()
         if bss is not None:
             for k, v in zip(("sdr", "sir", "sar"), bss):
                 rec[k] = v[b].tolist()
@@ -108,7 +132,7 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
                      snr: Optional[float] = None, denoise: bool = True, start_idx: int = 0, seed: int = 0,
                      stoi: bool = False, stoi_extended: bool = True, score_loss: bool = False,
                      composite: bool = False, pesq_fn=None, mrstft: bool = False, codec: str = "grouped",
-                     bss_eval: bool = False, bss_filter_length: int = 512) -> dict:
+                     bss_eval: bool = False, bss_filter_length: int = 512, ragged_losses: bool = False) -> dict:
     """`batches` yields (mix [B,1,L], target [B,n,L]); returns {utterance index: record}.  stoi=True fills "stoi"
     with n floats per record (ESTOI, or STOI with stoi_extended=False); it stays null otherwise.  score_loss=True
     adds "score_loss": the denoising score-matching loss of the utterance per source slot (n floats; one score
@@ -123,7 +147,11 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     (one sampler call on the padded batch, the codec per group of equal length, every metric once on the padded batch
     with the items' lengths); each record carries its own "len_s", "runtime" stays the batch time divided by B, and
     stoi, composite and pesq_fn work as above, pesq_fn on each utterance's own unpadded signals.  score_loss and mrstft
-    have no ragged form (NotImplementedError).  codec="padded" runs the codec of a ragged batch once on the padded batch
+    on a list batch need ragged_losses=True (NotImplementedError without it, as before they had a ragged form): the
+    keyword is the caller's consent to what the mixed-length forms are -- score_loss on each utterance's own latent
+    frames with device draws indexed by position in the padded batch (Engine.score_loss with frames=: a valid draw,
+    not the one the utterance alone makes for that seed), mrstft on its own samples (Engine.mrstft_loss with lens=) --
+    with the record keys and seeds of the dense branch; dense batches ignore it.  codec="padded" runs the codec of a ragged batch once on the padded batch
     instead of once per group (Engine.encode_ragged / decode_ragged); dense batches ignore it."""
     from .native import check_codec_mode
     check_codec_mode(codec)
@@ -137,12 +165,14 @@ def evaluate_batches(model, batches: Iterable, fs: int, *, N: Optional[int] = No
     dev = model.engine.device
     for mix, target in batches:
         if isinstance(mix, (list, tuple)):
-            if score_loss or mrstft:
-                raise NotImplementedError("score_loss / mrstft are not implemented for ragged batches")
+            if (score_loss or mrstft) and not ragged_losses:
+                raise NotImplementedError("score_loss / mrstft are not implemented for ragged batches unless "
+                                          "ragged_losses=True asks for their mixed-length forms")
             results.update(_evaluate_ragged(model, list(mix), list(target), fs, idx, seed, N, corrector_steps, snr,
                                             denoise, stoi, stoi_extended, codec=codec, composite=composite,
                                             pesq_fn=pesq_fn, bss_eval=bss_eval,
-                                            bss_filter_length=bss_filter_length))
+                                            bss_filter_length=bss_filter_length, score_loss=score_loss,
+                                            mrstft=mrstft))
             idx += len(mix)
             continue
         mix, target = mix.to(dev), target.to(dev)

@@ -708,9 +708,36 @@ class LatentDiffSep:
         mb = B if minibatch is None else int(minibatch)
         return [slice(i, min(i + mb, B)) for i in range(0, B, mb)]
 
-    def _score_loss(self, mode, reduction, y, x, time, noise, perm, seed, minibatch):
-        """One engine call per minibatch; an explicit seed is offset by the minibatch index (as get_pc_sampler)."""
+    def encode_lists(self, mixes, targets, seed=None, codec="grouped"):
+        """A mixed-length batch as lists -- mixtures [1, L_b] and targets [n, L_b] -> (y [B,1,D,Tmax], x [B,n,D,Tmax],
+        frames): Engine.encode_ragged under `codec` on the mixtures (seed) and on the B * n target rows (seed + 1, as
+        `encode` does), zero past each item's frames."""
+        mixes, targets = list(mixes), list(targets)
+        if len(mixes) != len(targets) or not mixes:
+            raise ValueError(f"a list batch needs as many mixtures as targets, at least one (got {len(mixes)} and "
+                             f"{len(targets)})")
+        n = int(targets[0].shape[0])
+        for b, (m, t) in enumerate(zip(mixes, targets)):
+            if m.dim() != 2 or t.dim() != 2 or m.shape[0] != 1 or t.shape[0] != n or m.shape[-1] != t.shape[-1]:
+                raise ValueError(f"item {b}: the mixture must be [1, L_b] and the target [{n}, L_b] (got "
+                                 f"{tuple(m.shape)} and {tuple(t.shape)})")
+        native.check_codec_mode(codec)
         seed = self._seed(seed)
+        y, frames = self.engine.encode_ragged(mixes, None, seed=seed, codec=codec)
+        x, _ = self.engine.encode_ragged([t[i:i + 1] for t in targets for i in range(n)], None, seed=seed + 1,
+                                         codec=codec)
+        self.max_len_lat = max(self.max_len_lat, y.shape[-1])
+        return y, x.reshape(len(mixes), n, *x.shape[2:]), frames
+
+    def _score_loss(self, mode, reduction, y, x, time, noise, perm, seed, minibatch, frames=None):
+        """One engine call per minibatch; an explicit seed is offset by the minibatch index (as get_pc_sampler).
+        frames: a ragged batch, which is one call (Engine.score_loss with frames=)."""
+        seed = self._seed(seed)
+        if frames is not None:
+            if minibatch is not None:
+                raise ValueError("a mixed-length batch is one score_loss call: minibatch= does not go with lists")
+            return self.engine.score_loss(y, x, mode=mode, reduction=reduction, t_eps=self.t_eps, seed=seed, time=time,
+                                          noise=noise, perm=perm, frames=frames)
         outs, sizes = [], []
         for i, sl in enumerate(self._loss_chunks(y.shape[0], minibatch)):
             outs.append(self.engine.score_loss(
@@ -742,35 +769,56 @@ class LatentDiffSep:
         return aux["x_t"], aux["t"], aux["sigma"].reshape(-1, 1, 1, 1), aux["z"]
 
     @torch.no_grad()
-    def compute_score_loss(self, y, x, time=None, noise=None, seed=None, perm=None, minibatch=None):
+    def compute_score_loss(self, y, x, time=None, noise=None, seed=None, perm=None, minibatch=None, codec="grouped"):
         """reference :154-160 with ONE native call (dsn_score_loss): `loss(score(x_t, t, y) sigma, -z)` followed by
         the reference's mean over the trailing axes -- a scalar for MSELoss(), **[B, n]** for
-        MSELoss(reduction="none") (the mean runs over (D, T) only; kept as the reference has it)."""
-        return self._score_loss("dsm", self.loss_reduction, y, x, time, noise, perm, seed, minibatch)
+        MSELoss(reduction="none") (the mean runs over (D, T) only; kept as the reference has it).
+        Lists (an addition of this project): y a list of mixture waveforms [1, L_b] and x a list of target waveforms
+        [n, L_b] of different lengths.  They are encoded by `encode_lists` under `codec` (seed, seed + 1) and scored by
+        one Engine.score_loss call with the items' frame counts: each row is the mean over the item's own frames, and
+        MSELoss() becomes the mean of the B * n row means.  noise, when given, is [B,n,D,Tmax]."""
+        y, x, frames = self._maybe_lists(y, x, seed, codec)
+        return self._score_loss("dsm", self.loss_reduction, y, x, time, noise, perm, seed, minibatch, frames)
+
+    def _maybe_lists(self, y, x, seed, codec):
+        if isinstance(y, (list, tuple)) != isinstance(x, (list, tuple)):
+            raise ValueError("mixtures and targets must both be tensors (latents) or both be lists (waveforms)")
+        if not isinstance(y, (list, tuple)):
+            return y, x, None
+        return self.encode_lists(y, x, seed=seed, codec=codec)
 
     @torch.no_grad()
-    def compute_score_loss_init_hack_pit(self, mix, target, noise=None, seed=None, minibatch=None):
+    def compute_score_loss_init_hack_pit(self, mix, target, noise=None, seed=None, minibatch=None, codec="grouped"):
         """reference :162-187 -> [B, n]: t = T, x_t = mix + sigma z0 and the minimum over all source permutations
         **per (item, source slot)** (the reference's stack(dim=1).min(dim=1) on [B,n] losses).  The reference calls
         the network n! times on identical inputs; this makes one call.  With MSELoss() the reference's stack of
-        scalars raises IndexError, and so does this."""
+        scalars raises IndexError, and so does this.  Lists of waveforms as in compute_score_loss."""
         if self.loss_reduction != "none":
             raise IndexError("Dimension out of range: compute_score_loss_init_hack_pit needs "
                              "MSELoss(reduction='none'), as in the reference")
-        return self._score_loss("init_pit", "none", mix, target, None, noise, None, seed, minibatch)
+        mix, target, frames = self._maybe_lists(mix, target, seed, codec)
+        return self._score_loss("init_pit", "none", mix, target, None, noise, None, seed, minibatch, frames)
 
     @torch.no_grad()
     def train_step_init_5(self, mix, target, pit_mask=None, perm=None, time=None, noise=None, seed=None,
-                          minibatch=None):
+                          minibatch=None, codec="grouped", frames=None):
         """reference :189-208 (forward value only): items with pit_mask go through the PIT variant, the rest through
         shuffle_sources + compute_score_loss; torch.cat(losses).mean().  pit_mask [B] bool (default: a
         Bernoulli(init_hack_p) draw), perm [B - n_pit, n] (default: argsort of a uniform draw per item) -- both host
         draws from torch's generator, seeded by `seed` when given; time [B - n_pit] / noise [B,n,D,T] (z0 of the PIT
-        items, z of the rest) are injected into the engine calls."""
+        items, z of the rest) are injected into the engine calls.
+        Lists of waveforms as in compute_score_loss (encoded once, then split by pit_mask), or padded latents with
+        frames= (B ints): each of the two groups is then one ragged Engine.score_loss call."""
         if self.loss_reduction != "none":
             raise ValueError("Reduction should 'none' for loss with init_hack == 5")
-        B, n = target.shape[:2]
         seed = self._seed(seed)
+        if isinstance(mix, (list, tuple)) or isinstance(target, (list, tuple)):
+            if frames is not None:
+                raise ValueError("frames= goes with padded latents; lists of waveforms carry their own lengths")
+            mix, target, frames = self._maybe_lists(mix, target, seed, codec)
+        B, n = target.shape[:2]
+        if frames is not None:
+            frames = native.check_ragged(self.engine.cfg.score_kind, frames, B, target.shape[-1])
         g = torch.Generator().manual_seed(seed)
         if pit_mask is None:
             pit_mask = torch.rand(B, generator=g) < self.init_hack_p
@@ -780,31 +828,39 @@ class LatentDiffSep:
         def take(a, mask):
             return None if a is None else a[mask.to(a.device)]
 
+        def take_frames(mask):
+            return None if frames is None else [f for f, m in zip(frames, mask.tolist()) if m]
+
         losses = []
         if n_pit > 0:
             losses.append(self._score_loss("init_pit", "none", take(mix, pit), take(target, pit), None,
-                                           take(noise, pit), None, seed, minibatch))
+                                           take(noise, pit), None, seed, minibatch, take_frames(pit)))
         if n_pit != B:
             if perm is None:
                 perm = torch.argsort(torch.rand((B - n_pit, n), generator=g), dim=1)
             losses.append(self._score_loss("dsm", "none", take(mix, ~pit), take(target, ~pit), time,
-                                           take(noise, ~pit), perm, seed + 7919, minibatch))
+                                           take(noise, ~pit), perm, seed + 7919, minibatch, take_frames(~pit)))
         return torch.cat(losses).mean()
 
     def on_validation_epoch_start(self):
         self.n_batches_est_done = 0
 
     @torch.no_grad()
-    def validation_step(self, batch, batch_idx=0, dataset_i=0, seed=None, **loss_kwargs):
+    def validation_step(self, batch, batch_idx=0, dataset_i=0, seed=None, codec="grouped", **loss_kwargs):
         """reference :251-273 as a dict instead of Lightning log calls: encode mix and targets, then
         "val/score_loss" (train_step_init_5 when init_hack == 5, else compute_score_loss; loss_kwargs are passed
         on) and, for the first `valid_max_sep_batches` calls since on_validation_epoch_start, "val/si_sdr": the
         reference's SISDRLoss(zero_mean=false, clamp_db=30, sign_flip=true, reduction=mean) of separate()'s estimate,
         from the device SI-SDR (dsn_si_sdr_pit).  That number is unpinned, like the other SI-SDR figures of this
         build: the reference computes it with fast_bss_eval.si_sdr_pit_loss, which is not available to compare with.
-        "val/pesq" is not computed."""
+        "val/pesq" is not computed.
+        A batch of lists (mixtures [1, L_b], targets [n, L_b] of different lengths): encode_lists under `codec`, one
+        ragged score-loss call (or train_step_init_5's two), separate_batch for the estimates and the SI-SDR of every
+        item over its own samples under its best SI-SDR permutation (Engine.si_bss_eval with lens=)."""
         mix, target = batch
         seed = self._seed(seed)
+        if isinstance(mix, (list, tuple)):
+            return self._validation_step_lists(list(mix), list(target), seed, codec, loss_kwargs)
         y, x = self.encode(mix, target, seed=seed)
         if self.init_hack == 5:
             loss = self.train_step_init_5(y, x, seed=seed, **loss_kwargs)
@@ -815,6 +871,25 @@ class LatentDiffSep:
             self.n_batches_est_done += 1
             est, *_ = self.separate(y, latent=True, target_dim=target.shape[-1], seed=seed)
             si_sdr, _ = self.engine.si_sdr_pit(target, est)
+            out["val/si_sdr"] = si_sdr.clamp(-30.0, 30.0).mean()
+        return out
+
+    def _validation_step_lists(self, mixes, targets, seed, codec, loss_kwargs):
+        y, x, frames = self.encode_lists(mixes, targets, seed=seed, codec=codec)
+        if self.init_hack == 5:
+            loss = self.train_step_init_5(y, x, seed=seed, frames=frames, **loss_kwargs)
+        else:
+            loss = self._score_loss("dsm", self.loss_reduction, y, x, loss_kwargs.get("time"), loss_kwargs.get("noise"),
+                                    loss_kwargs.get("perm"), seed, loss_kwargs.get("minibatch"), frames)
+        out = {"val/score_loss": loss}
+        if self.n_batches_est_done < self.valid_max_sep_batches:
+            self.n_batches_est_done += 1
+            est, *_ = self.separate_batch(mixes, codec=codec, seed=seed)
+            lens = [int(t.shape[-1]) for t in targets]
+            dev = self.engine.device
+            pad = lambda items: torch.stack([torch.nn.functional.pad(t.to(dev, torch.float32), (0, max(lens) - t.shape[-1]))
+                                             for t in items])
+            si_sdr = self.engine.si_bss_eval(pad(targets), pad(est), perm_by="sdr", clamp_db=30.0, lens=lens)[0]
             out["val/si_sdr"] = si_sdr.clamp(-30.0, 30.0).mean()
         return out
 
@@ -861,6 +936,29 @@ def reconstruction_loss_config(config) -> dict:
     return kw
 
 
+def padded_pair(decoded, reals, lens, device):
+    """losses_gen's arguments -> (decoded, reals, lens): tensors pass as they are; two lists of [n, L_b] whose items
+    agree in shape are zero-padded once to [B, n, Lmax] and lens becomes their lengths."""
+    dl, rl = isinstance(decoded, (list, tuple)), isinstance(reals, (list, tuple))
+    if dl != rl:
+        raise ValueError("decoded and reals must both be tensors or both be lists of [n, L_b]")
+    if not dl:
+        return decoded, reals, lens
+    if lens is not None:
+        raise ValueError("lens= goes with padded tensors; lists carry their own lengths")
+    if len(decoded) != len(reals) or not reals:
+        raise ValueError(f"decoded and reals must hold the same number of items, at least one (got {len(decoded)} and "
+                         f"{len(reals)})")
+    for b, (d, r) in enumerate(zip(decoded, reals)):
+        if d.dim() != 2 or tuple(d.shape) != tuple(r.shape) or d.shape[0] != reals[0].shape[0]:
+            raise ValueError(f"item {b}: decoded and reals must both be [n, L_b] (got {tuple(d.shape)} and "
+                             f"{tuple(r.shape)})")
+    lens = [int(r.shape[-1]) for r in reals]
+    pad = lambda items: torch.stack([torch.nn.functional.pad(t.to(device=device, dtype=torch.float32),
+                                                             (0, max(lens) - t.shape[-1])) for t in items])
+    return pad(decoded), pad(reals), lens
+
+
 class LDM(LatentDiffSep):
     """The reference's second latent module (src/ldm.py), which fine-tunes the decoder through the frozen sampler:
     the inference surface is LatentDiffSep's (`LDM.separate` is the same code), and `losses_gen` is the forward value
@@ -874,12 +972,16 @@ class LDM(LatentDiffSep):
         super().__init__(config, device=device, precision=precision)
 
     @torch.no_grad()
-    def losses_gen(self, decoded, reals):
+    def losses_gen(self, decoded, reals, lens=None):
         """reference ldm.py:154 `self.losses_gen({"reals": reals, "decoded": decoded})` -> (loss, losses) with the
         MultiLoss keys "pit_mrstft_loss", "pit_l1_loss", "pit_l2_loss" (the latter two with a positive weight only).
-        `self.last_loss_tables` keeps the whole Engine.mrstft_loss result (pair tables, chosen permutations)."""
+        `self.last_loss_tables` keeps the whole Engine.mrstft_loss result (pair tables, chosen permutations).
+        Mixed lengths (an addition of this project): decoded and reals as lists of [n, L_b] -- padded once and scored
+        by one call with the items' lengths -- or as padded tensors with lens=; every item's tables are those it gets
+        alone, combined as a dense batch's are (native.mrstft_combine)."""
+        decoded, reals, lens = padded_pair(decoded, reals, lens, self.engine.device)
         res = self.engine.mrstft_loss(reals, decoded, self.loss_fs if self.loss_fs is not None else 0,
-                                      pit=self.pit, **self.loss_kwargs)
+                                      pit=self.pit, lens=lens, **self.loss_kwargs)
         self.last_loss_tables = res
         losses = {k: res[k] for k in ("pit_mrstft_loss", "pit_l1_loss", "pit_l2_loss") if k in res}
         return res["loss"], losses

@@ -42,6 +42,7 @@ EXPORTS = [
     "dsn_mask_refine",
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
+    "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
 ]
 
 
@@ -812,6 +813,8 @@ def load_library() -> C.CDLL:
                                    vp]
     lib.dsn_score_loss.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, ci, ci,
                                    C.POINTER(DsnLossOpts), vp]
+    lib.dsn_score_loss_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp,
+                                          ci, ci, C.POINTER(DsnLossOpts), vp]
     lib.dsn_decode.argtypes = [vp, vp, vp, ci, ci, ci, vp]
     lib.dsn_encode.argtypes = [vp, vp, vp, C.c_uint64, vp, ci, ci, vp]
     lib.dsn_decode_chunked.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
@@ -865,6 +868,8 @@ def load_library() -> C.CDLL:
                               f64p, vp]
     lib.dsn_pcm_encode_frames.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
+    lib.dsn_mrstft_loss_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, C.POINTER(DsnMrstftConfig),
+                                           C.POINTER(DsnMrstftOut), vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -909,7 +914,12 @@ def mrstft_combine(tables: Mapping, *, w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, m
       chosen independently per term (pit="batch"); a single source takes no permutation.  pit="item" (the
       smallest loss per item) and pit=None (the identity) are additions of this project, not reference behaviour.
     * ldm.py:132-152: the L1 / L2 terms exist only with a positive weight; "loss" is the sum of the terms present.
-    Ties go to the first permutation in itertools.permutations order."""
+    Ties go to the first permutation in itertools.permutations order.
+
+    Mixed lengths (Engine.mrstft_loss with lens=): the per-item tables of a ragged batch are treated exactly as those
+    of a dense batch -- every item weighs the same in a batch mean, however long it is, and pit="batch" still picks
+    one permutation for the whole batch by that mean.  This is this project's DEFINITION: the reference has no
+    mixed-length form (its tensors hold equally long items, for which the two readings coincide)."""
     from itertools import permutations
 
     if pit not in ("batch", "item", None):
@@ -1221,13 +1231,20 @@ class Engine:
         return x, st.nfev
 
     def score_loss(self, y, x0, *, mode="dsm", reduction="none", t_eps=0.03, time=None, noise=None, perm=None, seed=0,
-                   loss=True, return_aux=False):
+                   loss=True, return_aux=False, frames=None):
         """Denoising score-matching loss with one score call (dsn_score_loss; reference sample_prior +
         compute_score_loss, or compute_score_loss_init_hack_pit for mode="init_pit").  y [B,1,D,T], x0 [B,n,D,T] ->
         loss [B,n] (reduction="none") or a scalar tensor ("mean"), float32 on the device.  time [B] in (0, 1], noise
         [B,n,D,T] and perm [B,n] (slot s of item b holds source perm[b,s]) are injected when given; otherwise t and z
         come from the device RNG for `seed`.  loss=False: the perturbation only, no score call (loss is None).
-        return_aux=True: (loss, {"x_t", "t", "sigma" [B], "z"})."""
+        return_aux=True: (loss, {"x_t", "t", "sigma" [B], "z"}).
+        frames (B ints, optional; DiT only): a ragged batch padded to T frames, item b valid over [..., :frames[b]]
+        (dsn_score_loss_ragged).  x_t there is bit for bit the dense value and zero past the item's end; x0 and noise
+        are not read in the padding (y's padding goes to the score call and must be finite); loss[b, s] is the mean
+        over the item's own D * frames[b] elements, and reduction="mean" the mean of the B * n row means -- a
+        definition, equal to MSELoss() for equal lengths.  With the device RNG the normals are indexed by position in
+        the padded tensor: a valid draw, not the one the item alone would make for that seed.  The aux tensors keep
+        the padded shape."""
         if mode not in LOSS_MODES or reduction not in LOSS_REDUCTIONS:
             raise ValueError(f"mode must be one of {sorted(LOSS_MODES)} and reduction one of {sorted(LOSS_REDUCTIONS)}")
         y, x0 = _dev32(y, self.device), _dev32(x0, self.device)
@@ -1236,6 +1253,8 @@ class Engine:
         B, _, D, T = y.shape
         if tuple(x0.shape) != (B, self.n_src, D, T) or D != self.latent_dim:
             raise ValueError(f"x0 must be [{B},{self.n_src},{self.latent_dim},{T}], got {tuple(x0.shape)}")
+        if frames is not None:
+            frames = check_ragged(self.cfg.score_kind, frames, B, T)
         if time is not None:
             time = _dev32(torch.as_tensor(time), self.device).reshape(-1)
             if time.numel() != B:
@@ -1256,10 +1275,13 @@ class Engine:
             aux = {"x_t": torch.empty_like(x0), "t": torch.empty(B, device=self.device, dtype=torch.float32),
                    "sigma": torch.empty(B, device=self.device, dtype=torch.float32), "z": torch.empty_like(x0)}
         o = DsnLossOpts(LOSS_MODES[mode], LOSS_REDUCTIONS[reduction], float(t_eps))
-        self._check(self.lib.dsn_score_loss(self.ctx, _ptr(y), _ptr(x0), _ptr(time), _ptr(noise), _ptr(perm),
-                                            int(seed), _ptr(out), _ptr(aux.get("x_t")), _ptr(aux.get("t")),
-                                            _ptr(aux.get("sigma")), _ptr(aux.get("z")), B, T, C.byref(o),
-                                            self._stream()), "dsn_score_loss")
+        tail = (_ptr(time), _ptr(noise), _ptr(perm), int(seed), _ptr(out), _ptr(aux.get("x_t")), _ptr(aux.get("t")),
+                _ptr(aux.get("sigma")), _ptr(aux.get("z")), B, T, C.byref(o), self._stream())
+        if frames is None:
+            self._check(self.lib.dsn_score_loss(self.ctx, _ptr(y), _ptr(x0), *tail), "dsn_score_loss")
+        else:
+            self._check(self.lib.dsn_score_loss_ragged(self.ctx, _ptr(y), _ptr(x0), (C.c_int32 * B)(*frames), *tail),
+                        "dsn_score_loss_ragged")
         if out is not None and reduction == "mean":
             out = out.reshape(())
         return (out, aux) if return_aux else out
@@ -2080,7 +2102,7 @@ class Engine:
     def mrstft_loss(self, reals, decoded, fs: int, *, fft_sizes=MRSTFT_FFT_SIZES, hop_sizes=MRSTFT_HOP_SIZES,
                     win_lengths=None, perceptual_weighting: bool = True, w_sc: float = 1.0, w_log_mag: float = 1.0,
                     w_lin_mag: float = 0.0, l1_weight: float = 0.0, l2_weight: float = 0.0,
-                    mrstft_weight: float = 1.0, pit="batch", **options) -> dict:
+                    mrstft_weight: float = 1.0, pit="batch", lens=None, **options) -> dict:
         """reals, decoded [B,n,L] -> the forward value of the reference's LDM generator objective (src/ldm.py:100-154:
         PITLoss(AuralossLoss(MultiResolutionSTFTLoss)) plus PITLoss(L1Loss) / PITLoss(MSELoss) under MultiLoss), from
         one native call (dsn_mrstft_loss) that forms every spectrum once and returns (reference source, estimate
@@ -2092,7 +2114,12 @@ class Engine:
         source i); "perms" and "mrstft_values", the weighted MR-STFT loss of every permutation tried ([P], or [B,P]
         with pit="item").  perceptual_weighting filters both signals with the 101-tap A-weighting FIR of `fs`
         (ditsep_amd/aweight.py).  `options` takes the reference's remaining keywords (window, w_phs, scale, n_bins,
-        scale_invariance, decay, sample_rate): anything but their defaults raises NotImplementedError."""
+        scale_invariance, decay, sample_rate): anything but their defaults raises NotImplementedError.
+        lens (B ints, optional): a ragged batch padded to L samples, item b holding lens[b] of them
+        (dsn_mrstft_loss_ragged).  Item b's rows of every table are, bit for bit, those of this call on the item alone
+        -- its own frame count, reflection at its own end, its own divisors -- whatever the padding (which is not
+        read) and the batch around it; every lens[b] must exceed max(fft_sizes) / 2.  The combine treats the per-item
+        tables as it treats those of a dense batch (mrstft_combine: the definition for mixed lengths)."""
         options.pop("sample_rate", None)
         if options.get("n_bins") is None:
             options.pop("n_bins", None)
@@ -2109,6 +2136,9 @@ class Engine:
             raise ValueError(f"pit must be 'batch', 'item' or None (got {pit!r})")
         B, n, L = reals.shape
         R = len(fft_sizes)
+        if lens is not None:
+            lens = check_lens(lens, B, L, (max(fft_sizes) // 2 + 1) if R else None,
+                              " for the reflect padding of the largest FFT")
         cfg = DsnMrstftConfig(n_res=R, fft=(C.c_int * R)(*fft_sizes), hop=(C.c_int * R)(*hop_sizes),
                               win=(C.c_int * R)(*win_lengths), w_sc=float(w_sc), w_log_mag=float(w_log_mag),
                               w_lin_mag=float(w_lin_mag), taps=None, n_taps=0)
@@ -2120,8 +2150,13 @@ class Engine:
         tabs = {k: torch.zeros((R, B, n, n) if k in ("sc", "log_mag", "lin_mag") else (B, n, n), dtype=torch.float64)
                 for k in ("sc", "log_mag", "lin_mag", "l1", "l2")}
         out = DsnMrstftOut(**{k: C.cast(C.c_void_p(v.data_ptr()), C.POINTER(C.c_double)) for k, v in tabs.items()})
-        self._check(self.lib.dsn_mrstft_loss(self.ctx, _ptr(reals), _ptr(decoded), B, n, L, C.byref(cfg),
-                                             C.byref(out), self._stream()), "dsn_mrstft_loss")
+        if lens is None:
+            self._check(self.lib.dsn_mrstft_loss(self.ctx, _ptr(reals), _ptr(decoded), B, n, L, C.byref(cfg),
+                                                 C.byref(out), self._stream()), "dsn_mrstft_loss")
+        else:
+            self._check(self.lib.dsn_mrstft_loss_ragged(self.ctx, _ptr(reals), _ptr(decoded), (C.c_int32 * B)(*lens), B,
+                                                        n, L, C.byref(cfg), C.byref(out), self._stream()),
+                        "dsn_mrstft_loss_ragged")
         res = dict(tabs)
         res.update(mrstft_combine(tabs, w_sc=w_sc, w_log_mag=w_log_mag, w_lin_mag=w_lin_mag,
                                   mrstft_weight=mrstft_weight, l1_weight=l1_weight, l2_weight=l2_weight, pit=pit))

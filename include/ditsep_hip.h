@@ -153,8 +153,9 @@ int dsn_pc_sample_ex(dsn_ctx* ctx, const float* y, const float* noise, uint64_t 
  *                         for that seed.
  * DSN_EINVAL, by name and before any launch: a score network other than the DiT (NCSN++ convolves across time, so
  * padding changes an item's result); a frame count outside [1, T]; DSN_CORR_LANGEVIN (its per-item norms would run
- * over the padding).  The Mix / PriorMix, Schroedinger-bridge and ODE samplers and dsn_score_loss have no ragged form:
- * each reduces over the latent or couples the batch.  The codec's ragged form is the block below.  Under
+ * over the padding).  The Mix / PriorMix, Schroedinger-bridge and ODE samplers have no ragged form: each reduces over
+ * the latent or couples the batch.  The score-matching loss has one, dsn_score_loss_ragged (declared with
+ * dsn_score_loss), whose reductions run over each item's own frames.  The codec's ragged form is the block below.  Under
  * dsn_enable_graphs the lengths are data of the captured graph, not part of its key: one graph per (B, T, options)
  * serves every set of lengths. */
 int dsn_score_ragged(dsn_ctx* ctx, const float* xt, const float* t, const float* mix, const int32_t* frames, float* out,
@@ -327,6 +328,24 @@ typedef struct DsnLossOpts {
 int dsn_score_loss(dsn_ctx* ctx, const float* y, const float* x0, const float* t, const float* noise,
                    const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out, float* t_out, float* sigma_out,
                    float* z_out, int B, int T, const DsnLossOpts* opts, void* stream);
+/* The same loss on a ragged batch (DiT only; NCSN++ is refused by name as in dsn_score_ragged): y, x0, noise and the
+ * outputs keep their padded shapes, frames [B] (HOST int32, 1 <= frames[b] <= T) as in the ragged block above.
+ *   perturb  x_t[b, :, :, :frames[b]] is exactly dsn_score_loss's value (same fp32 order, sigma and e rounded once from
+ *            fp64); x_t is written as zero past the item's end, and x0 and noise are not read there (they may hold
+ *            anything, NaN included).  y's padding is only handed on to the score call and must be finite.
+ *   score    one dsn_score_ragged-path call on (x_t, t, y, frames), also for DSN_LOSS_INIT_PIT.
+ *   reduce   loss[b, s] = mean over the D * frames[b] valid elements of (sigma score + z)^2 (INIT_PIT: the per-slot
+ *            minimum over j of the table entry), fp64 terms summed in a fixed order that depends on the item's own
+ *            length only.  DSN_LOSS_REDUCE_MEAN is the mean of the B * n_src row means.  This is a DEFINITION: the
+ *            reference has no mixed-length form; for equal lengths it equals MSELoss().
+ * RNG: t_b comes from counter b as in the dense call.  With noise == NULL the normals are indexed by position in the
+ * padded tensor: a valid draw, but NOT the draw the item alone would make for that seed (dsn_pc_sample_ragged's
+ * caveat).  Injected noise: item b uses noise[b, ..., :frames[b]].  z_out hands the padded z back as it was used.
+ * Under dsn_enable_graphs the lengths are data of the captured graph: one graph per (B, T, mode, reduction). */
+int dsn_score_loss_ragged(dsn_ctx* ctx, const float* y, const float* x0, const int32_t* frames, const float* t,
+                          const float* noise, const int32_t* perm, uint64_t seed, float* loss_out, float* xt_out,
+                          float* t_out, float* sigma_out, float* z_out, int B, int T, const DsnLossOpts* opts,
+                          void* stream);
 
 /* LatentDiffSep.decode: est [B,n_src,D,T] -> wav [B,n_src,target_len] (crop of hop*T;
  * target_len <= 0 means hop*T). */
@@ -735,6 +754,16 @@ typedef struct DsnMrstftOut {
 } DsnMrstftOut;
 int dsn_mrstft_loss(dsn_ctx* ctx, const float* reals, const float* decoded, int B, int n, int L,
                     const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream);
+/* The same tables for a ragged batch: reals, decoded [B,n,L] padded to the longest item, lens [B] (HOST int32): item b
+ * holds lens[b] samples.  Item b's rows of every table are those of dsn_mrstft_loss on the item alone with L = lens[b]:
+ * 1 + lens[b] / hop frames per resolution, centred and reflected at the item's own end; the prefilter reads zero past
+ * that end; l1 / l2 divide by lens[b], log_mag / lin_mag by bins * frames_b.  Nothing at or past lens[b] is read (the
+ * padding may hold NaN).  An item's sums are cut into workgroup partials by its own length and the resolution alone
+ * (the dense call's partition at B = 1), so its tables have the same bits alone, at any batch position, under any
+ * amount of padding and in a second call.  DSN_EINVAL, before any launch, beside the dense call's refusals: lens[b]
+ * outside [1, L]; lens[b] <= max(fft) / 2. */
+int dsn_mrstft_loss_ragged(dsn_ctx* ctx, const float* reals, const float* decoded, const int32_t* lens, int B, int n,
+                           int L, const DsnMrstftConfig* cfg, const DsnMrstftOut* out, void* stream);
 
 /* introspection for benchmarks / tests */
 int dsn_enable_graphs(dsn_ctx* ctx, int enable);          /* hipGraph replay of sample/decode */
