@@ -3478,6 +3478,94 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
   });
 }
 
+// ---- loudness, true peak and the gain (loudness.hip; include/ditsep_hip.h states the definition)
+int dsn_kweight_coeffs(int fs, double* out) {
+  if (!out || fs < LOUD_MIN_RATE || fs > LOUD_MAX_RATE) return DSN_EINVAL;
+  kweight_coeffs(fs, out);
+  return DSN_OK;
+}
+
+// the refusals dsn_loudness and dsn_apply_gain share, and the rows as the kernels take them (h and rate left 0)
+static std::vector<LoudItem> loudness_rows(const char* who, int B, int C, int Lmax, const int32_t* lens,
+                                           const int32_t* channels) {
+  if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: %d rows, outside [1, 65535]", who, B);
+  if (C < 1 || C > LOUD_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, LOUD_MAX_CH);
+  if (Lmax < 1 || Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d outside [1, 2^30]", who, Lmax);
+  std::vector<LoudItem> rows((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int len = lens ? lens[b] : Lmax, ch = channels ? channels[b] : C;
+    if (len < 1 || len > Lmax)
+      fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, b, len, Lmax);
+    if (ch < 1 || ch > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, ch, C);
+    rows[b] = LoudItem{len, ch, 0, 0};
+  }
+  return rows;
+}
+
+int dsn_loudness(dsn_ctx* ctx, const float* x, int B, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                 const int32_t* rates, int want_true_peak, double* stats_host, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_loudness";
+    if (!x || !rates || !stats_host) fail(DSN_EINVAL, "%s: x, rates or stats_host is null", who);
+    std::vector<LoudItem> items = loudness_rows(who, B, C, Lmax, lens, channels);
+    std::vector<int> distinct;
+    for (int b = 0; b < B; ++b) {
+      if (rates[b] < LOUD_MIN_RATE || rates[b] > LOUD_MAX_RATE)
+        fail(DSN_EINVAL, "%s: rates[%d] = %d Hz outside [%d, %d]", who, b, (int)rates[b], LOUD_MIN_RATE, LOUD_MAX_RATE);
+      auto it = std::find(distinct.begin(), distinct.end(), (int)rates[b]);
+      items[b].rate = (int)(it - distinct.begin());
+      items[b].h = (rates[b] + 5) / 10;
+      if (it == distinct.end()) distinct.push_back(rates[b]);
+    }
+    std::vector<LoudRate> table(distinct.size());
+    for (size_t r = 0; r < distinct.size(); ++r) {
+      kweight_coeffs(distinct[r], table[r].c);
+      kweight_chunk_transition(table[r].c, table[r].P);
+    }
+    const dsn_ctx::ResampleTables& t = resample_tables(ctx, who, 1, 4);   // the true-peak interpolator
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)B * C, chunks = loudness_chunks(Lmax), segs = loudness_segments(Lmax);
+    double* state = ctx->wsbuf<double>("loud_state", (size_t)(rows * chunks * 4));
+    double* part = ctx->wsbuf<double>("loud_part", (size_t)(rows * chunks * 2));
+    double* seg = ctx->wsbuf<double>("loud_seg", (size_t)(rows * segs + (long)B * 2 * segs));
+    double* z = seg + rows * segs;
+    double* stats = ctx->wsbuf<double>("loud_stats", (size_t)B * 6);
+    unsigned long long* bad = ctx->wsbuf<unsigned long long>("loud_count", (size_t)B * 2);
+    unsigned* peaks = (unsigned*)(bad + B);
+    const LoudItem* ditems = (const LoudItem*)upload_table(ctx, "loud_items", items.data(), sizeof(LoudItem) * items.size(), st);
+    const LoudRate* drates = (const LoudRate*)upload_table(ctx, "loud_rates", table.data(), sizeof(LoudRate) * table.size(), st);
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(unsigned long long) * (size_t)B * 2, st));
+    const ResamplePlan& p = t.plan;
+    ctx->prof_launch("loudness", 4.0 * (double)rows * Lmax * (want_true_peak ? 3 : 2), st, [&] {
+      launch_loudness(x, ditems, drates, B, C, Lmax, state, part, seg, z, peaks, bad, stats, t.taps, t.k0, p.S, t.stride,
+                      t.kmin, t.kspan, p.width, want_true_peak, st);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(stats_host, stats, sizeof(double) * (size_t)B * 6, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
+int dsn_apply_gain(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                   const float* gain, float* out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_apply_gain";
+    if (!x || !gain || !out) fail(DSN_EINVAL, "%s: x, gain or out is null", who);
+    const std::vector<LoudItem> rows = loudness_rows(who, R, C, Lmax, lens, channels);
+    const char *x0 = (const char*)x, *o0 = (const char*)out;
+    const size_t bytes = sizeof(float) * (size_t)R * C * Lmax;
+    if (o0 != x0 && o0 < x0 + bytes && x0 < o0 + bytes)
+      fail(DSN_EINVAL, "%s: out overlaps x without being x (in place is fine, a shifted copy is not)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const LoudItem* drows = (const LoudItem*)upload_table(ctx, "gain_rows", rows.data(), sizeof(LoudItem) * rows.size(), st);
+    const float* dgain = (const float*)upload_table(ctx, "gain_values", gain, sizeof(float) * (size_t)R, st);
+    ctx->prof_launch("apply_gain", 8.0 * (double)R * C * Lmax, st, [&] {
+      launch_apply_gain(x, drows, dgain, out, R, C, Lmax, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
 static double bessel_i0(double x) {
   double s = 1.0, t = 1.0;

@@ -477,3 +477,37 @@ void launch_ensemble_solve(const int* lens, const double* part, double* gram, in
                            hipStream_t s);
 void launch_ensemble_gather(const float* cands, const int* lens, const int* perm, const int* anchor, const int* best,
                             float* out, int B, int K, int n, int Lmax, int mode, hipStream_t s);
+
+// ---- loudness, true peak and the gain (loudness.hip) -----------------------------------------------------------
+// x [B][C][Lmax] fp32, C <= LOUD_MAX_CH.  items [B] and rates [distinct rates] are device tables: an item's samples,
+// channels, segment length h = (fs + 5) / 10 and the row of `rates` with its K-weighting coefficients (kweight_coeffs'
+// ten) and the zero-input transition of the cascade's four state variables over LOUD_CHUNK samples (row-major).
+// Four launches: the chunks' final states from zero state into state [B][C][chunks][4]; one thread per (item, channel)
+// turning them into the chunks' initial states in place; the chunks again from those, their y^2 sums into part
+// [B][C][chunks][2] (the segment the chunk starts in, and the next); one workgroup per item for seg [B][C][segs],
+// z [B][segs] and stats [B][6].  want_tp and the sample peak: one launch that stages tiles of LOUD_PEAK_TILE samples and
+// their halo, peaks [B][2] (true, sample; the bits of non-negative floats under an integer maximum) and bad [B] zeroed
+// by the caller.  taps [4][stride], k0 [4]: the (1, 4) resampling tables on the device.
+#define LOUD_MAX_CH 2
+#define LOUD_CHUNK 256
+#define LOUD_MIN_RATE 8000
+#define LOUD_MAX_RATE 192000
+#define LOUD_PEAK_TILE 2048
+struct LoudRate {
+  double c[10];
+  double P[16];
+};
+struct LoudItem {
+  int len, ch, h, rate;
+};
+void kweight_coeffs(int fs, double out[10]);
+void kweight_chunk_transition(const double c[10], double P[16]);
+inline long loudness_chunks(int Lmax) { return ((long)Lmax + LOUD_CHUNK - 1) / LOUD_CHUNK; }
+inline long loudness_segments(int Lmax) { return (long)Lmax / ((LOUD_MIN_RATE + 5) / 10) + 1; }
+void launch_loudness(const float* x, const LoudItem* items, const LoudRate* rates, int B, int C, int Lmax, double* state,
+                     double* part, double* seg, double* z, unsigned* peaks, unsigned long long* bad, double* stats,
+                     const float* taps, const int* k0, int S, int stride, int kmin, int kspan, int width, int want_tp,
+                     hipStream_t s);
+// out = gain[r] x over a row's own samples and channels (rows [R]: len, ch), zero elsewhere; out may be x
+void launch_apply_gain(const float* x, const LoudItem* rows, const float* gain, float* out, int R, int C, int Lmax,
+                       hipStream_t s);

@@ -90,7 +90,7 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, **sampler_kwargs) -> list:
+                   stems=None, loudness=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -104,10 +104,21 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     if stems is not None and rescale:
         raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
                          "mixture")
+    loud = native.loudness_options(loudness)
     if long_mode not in native.LONG_MODES:
         raise ValueError(f"long_mode must be one of {native.LONG_MODES} (got {long_mode!r})")
     paths = [os.fspath(p) for p in paths]
     headers = parse_inputs(paths)
+    if loud is not None:
+        for p, h in zip(paths, headers):
+            if not native.LOUDNESS_RATES[0] <= h.rate <= native.LOUDNESS_RATES[1]:
+                raise ValueError(f"{p}: {h.rate} Hz; loudness= measures rates in [{native.LOUDNESS_RATES[0]}, "
+                                 f"{native.LOUDNESS_RATES[1]}] Hz")
+            if loud["link"] == "mixture" and h.channels > native.LOUDNESS_MAX_CHANNELS:
+                raise ValueError(f"{p}: {h.channels} channels; loudness= with link 'mixture' measures at most "
+                                 f"{native.LOUDNESS_MAX_CHANNELS} (no surround weights; link 'stem' measures the outputs)")
+    # the files' own channels are needed by the stems filter and as the gain source of a mixture-linked loudness
+    keep_channels = stems is not None or (loud is not None and loud["link"] == "mixture")
     hop = model.hop_length
     ens = {} if samples is None else dict(samples=native.check_samples(samples, combine), combine=combine)
     plan = plan_files(headers, fs, hop, files_per_batch(batch, samples), long_after)
@@ -136,12 +147,21 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 raise ValueError(f"{p}: {v} samples at the model's rate; stems= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
 
+    def level(idx, clips, back):
+        """the `loudness` step: rows at the files' own rates -> (the rows with their gains applied, the record entries)"""
+        if loud is None:
+            return back, [{} for _ in idx]
+        back, info = eng.loudness_normalize(clips, back, [headers[i].rate for i in idx], **loud)
+        return back, [{k: info[k][j] for k in ("loudness_in", "loudness_out", "gain_db", "true_peak_db")}
+                      for j in range(len(idx))]
+
     def finish_stems(idx, clips, est, label):
         """mono estimates at the model's rate -> multichannel files; `clips` the files' own channels at their own rates"""
         hs = [headers[i] for i in idx]
         at_fs = eng.to_model_rate(clips, [h.rate for h in hs], fs, downmix=False)
         back = eng.stems_from_model_rate(eng.stems(at_fs, est, **stems), [h.rate for h in hs], fs,
                                          [h.frames for h in hs])
+        back, levels = level(idx, clips, back)
         rows = torch.zeros((len(idx), n, max(h.channels for h in hs), max(h.frames for h in hs)), device=eng.device,
                            dtype=torch.float32)
         for j, y in enumerate(back):
@@ -159,7 +179,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 wavio.write_wav(outs[-1], payloads[j * n + s], hs[j].rate, hs[j].channels, encoding)
             records[i] = {"path": paths[i], "rate": hs[j].rate, "channels": hs[j].channels, "frames": hs[j].frames,
                           "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label,
-                          "stems": stems["mode"]}
+                          "stems": stems["mode"], **levels[j]}
 
     def finish(idx, at_fs, est, label, clips=None):
         """estimates at the model's rate -> files; `at_fs` the mono mixtures there"""
@@ -175,6 +195,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             est = [scaled[j, :, :lens[j]] for j in range(len(idx))]
         hs = [headers[i] for i in idx]
         back = eng.from_model_rate(est, [h.rate for h in hs], fs, [h.frames for h in hs])
+        back, levels = level(idx, clips, back)
         rows, lens = _padded(back, eng.device)
         payloads, clipped = eng.pcm_encode(rows.reshape(len(idx) * n, -1), [v for v in lens for _ in range(n)],
                                            encoding)
@@ -190,17 +211,17 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                    "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label}
             if alpha is not None:
                 rec["alpha"] = [float(a) for a in alpha[j]]
-            records[i] = rec
+            records[i] = dict(rec, **levels[j])
 
     for k, idx in enumerate(plan["batches"]):
-        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=stems is None)
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=not keep_channels)
         at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed) + k)
         est, *_ = model.separate_batch(at_fs, codec=codec, **ens, **kw)
         finish(idx, at_fs, est, k, clips)
     if plan["long"]:
         idx = plan["long"]
-        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=stems is None)
+        clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=not keep_channels)
         at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed))
         est, *_ = model.separate_long(at_fs, window, overlap=overlap, mode=long_mode, batch=batch, **kw)

@@ -411,9 +411,41 @@ class LatentDiffSep:
             out = eng.stems_from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
 
+    # ------------------------------------------------------------------ loudness (the `loudness` keyword)
+    def _loudness_refusals(self, lopts, channels, latent=False, intermediate=None):
+        """What the `loudness` keyword refuses, before any device work"""
+        if latent:
+            raise ValueError("loudness= measures waveforms: with latent=True there is nothing to measure")
+        if intermediate:
+            raise ValueError("loudness= does not go with intermediate: the per-step states are not normalised")
+        most = native.LOUDNESS_MAX_CHANNELS
+        for b, c in enumerate(channels):
+            if lopts["link"] == "mixture" and (c < 1 or c > most):
+                raise ValueError(f"loudness: mixture {b} has {c} channels, outside [1, {most}] (every channel has "
+                                 f"weight 1: no surround weights; link='stem' measures the stems instead)")
+
+    @staticmethod
+    def _clip_channels(c):
+        """channel count of a clip given as [L], [C, L] or [1, C, L]"""
+        return 1 if c.dim() == 1 else int(c.shape[-2])
+
+    def _normalise(self, lopts, sources, ests, rates, others, return_info, inner_info):
+        """The last step of the entry points with loudness=: Engine.loudness_normalize on the lists, and the info dict
+        merged into the combine's (inner_info) or appended (return_info alone)"""
+        src = None
+        if lopts["link"] == "mixture":
+            src = [m[None] if m.dim() == 1 else m.reshape(-1, m.shape[-1]) for m in sources]
+        outs, info = self.engine.loudness_normalize(src, list(ests), rates, **lopts)
+        others = list(others)
+        if inner_info:
+            others[-1] = dict(others[-1], **info)
+        elif return_info:
+            others.append(info)
+        return outs, others
+
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
-                 return_info=False, stems=None, **kwargs):
+                 return_info=False, stems=None, loudness=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -436,7 +468,32 @@ class LatentDiffSep:
         downmix ((x_0 + .. + x_{C-1}) / C), and Engine.stems filters the mixture's channels at the model's rate (the
         channels resampled without downmix, zero-extended or cut to the estimates' length) with the mono estimates,
         after combine and refine and before the resampling back.  The stems of a channel sum to that channel; nothing
-        above the model's Nyquist frequency comes back.  Refused with latent=True and with intermediate."""
+        above the model's Nyquist frequency comes back.  Refused with latent=True and with intermediate.
+        loudness (default None: the call returns the bits it returned before): True, a target in LUFS or a dict of
+        target / peak / link (native.loudness_options; -23 LUFS, a true-peak ceiling of -1 dBTP, link "mixture") --
+        the last step, after combine, refine, stems and the resampling back, at the rate the estimates come back at:
+        the programme loudness (ITU-R BS.1770-4 / EBU R 128) and the true peak are measured on the device
+        (Engine.loudness) and every estimate is multiplied by one gain (Engine.apply_gain; a gain, not a limiter).
+        link "mixture": the gain source is the mixture as it was given, all its channels (at most two) at its own
+        rate, and all stems of an item share the gain g that brings the mixture to the target -- held back so that no
+        stem's true peak passes the ceiling --, so stems that summed to the mixture sum to g mixture.  link "stem":
+        every stem is brought to the target by itself.  A source that passes no gating block stays at 0 dB.
+        return_info=True (allowed without samples= then) appends, or merges into the combine's info, "loudness_in",
+        "loudness_out", "gain_db", "true_peak_db" (one list of n per item), "limited", "silent", "nonfinite".  Refused
+        with latent=True and with intermediate."""
+        lopts = native.loudness_options(loudness)
+        if lopts is not None:
+            chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else [1]
+            self._loudness_refusals(lopts, chans, latent=latent, intermediate=kwargs.get("intermediate"))
+            rate = self._model_rate("loudness=") if sample_rate is None else int(sample_rate)
+            inner = bool(return_info) and samples is not None
+            est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
+                                         combine=combine, return_info=inner, stems=stems, **kwargs)
+            B = int(est.shape[0])
+            m3 = mix[:, None] if mix.dim() == 2 else mix
+            outs, others = self._normalise(lopts, [m3[b] for b in range(B)], [est[b] for b in range(B)], rate, others,
+                                           return_info, inner)
+            return (torch.stack(outs), *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
@@ -490,7 +547,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
-                       combine="mean", return_info=False, stems=None, **sampler_kwargs):
+                       combine="mean", return_info=False, stems=None, loudness=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -510,8 +567,23 @@ class LatentDiffSep:
         candidates with the items' lengths combines them against the mixtures, before refine and resampling back.
         stems (default None: off), as in `separate`: the mixtures are [C_b, L_b] (mixed channel counts are fine), the
         call runs on their downmixes, one Engine.stems call on the padded batch filters every item's own channels at
-        the model's rate, and a list of [n, C_b, L_b] comes back, each item with the bits it gets alone."""
+        the model's rate, and a list of [n, C_b, L_b] comes back, each item with the bits it gets alone.
+        loudness (default None: off), as in `separate`: the last step, one Engine.loudness call on the padded mixtures
+        as they were given (each at its own rate, with its own channels), one on the padded estimates, one
+        Engine.apply_gain call; each item gets the gain it gets alone."""
         eng = self.engine
+        lopts = native.loudness_options(loudness)
+        if lopts is not None:
+            mixes = list(mixes)
+            self._loudness_refusals(lopts, [self._clip_channels(m) for m in mixes],
+                                    intermediate=sampler_kwargs.get("intermediate"))
+            rates = self._model_rate("loudness=") if sample_rates is None else sample_rates
+            inner = bool(return_info) and samples is not None
+            est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
+                                               samples=samples, combine=combine, return_info=inner, stems=stems,
+                                               **sampler_kwargs)
+            outs, others = self._normalise(lopts, mixes, est, rates, others, return_info, inner)
+            return (outs, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -570,7 +642,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      mode="stitch", sample_rates=None, refine=None, stems=None, **sampler_kwargs):
+                      mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -589,8 +661,23 @@ class LatentDiffSep:
         the model's rate, after the stitch (or the single decode of mode="score") and before any resampling back.
         stems (default None: off), as in `separate_batch`: the recordings are [C, L_r], the call runs on their
         downmixes, and every recording's channels are filtered whole (Engine.stems) at the model's rate after the
-        stitch and refine: [n, C, L] or a list of [n, C_r, L_r] comes back."""
+        stitch and refine: [n, C, L] or a list of [n, C_r, L_r] comes back.
+        loudness (default None: off), as in `separate_batch`: every recording is measured whole and gets one gain,
+        the last step; with return_info=True its entries join the stitch's info dict."""
         eng = self.engine
+        lopts = native.loudness_options(loudness)
+        if lopts is not None:
+            single = torch.is_tensor(mixes)
+            clips = [mixes] if single else list(mixes)
+            self._loudness_refusals(lopts, [self._clip_channels(m) for m in clips],
+                                    intermediate=sampler_kwargs.get("intermediate"))
+            rates = self._model_rate("loudness=") if sample_rates is None else sample_rates
+            est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
+                                              return_info=return_info, mode=mode, sample_rates=sample_rates,
+                                              refine=refine, stems=stems, **sampler_kwargs)
+            outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
+                                           bool(return_info))
+            return (outs[0] if single else outs, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -664,7 +751,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
-                       samples=None, combine="mean", stems=None, **sampler_kwargs):
+                       samples=None, combine="mean", stems=None, loudness=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -691,13 +778,19 @@ class LatentDiffSep:
         (Engine.stems), taken back to the file's rate and frame count, interleaved and quantised on the device
         (Engine.pcm_encode_frames) and written with the input's channel count: a stereo file gives stereo stems that
         sum to it, a mono file in the same batch comes out mono.  Each dict gains "stems" (the mode).  Refused with
-        rescale (the stems already sum to the mixture) before any device work."""
+        rescale (the stems already sum to the mixture) before any device work.
+        loudness (default None: off, the files are the bytes they were), as in `separate`: the last step before the
+        quantiser, at each file's own rate -- after refine, stems, rescale and the resampling back.  link "mixture"
+        measures the file as it was decoded, with its channels (at most two; refused before any device work
+        otherwise), and all its speakers share one gain; link "stem" brings every speaker's file to the target.  Each
+        dict gains "loudness_in", "loudness_out", "gain_db" and "true_peak_db", one entry per speaker.  A single
+        gain, not a limiter, and no dither."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
-                                    **sampler_kwargs)
+                                    loudness=loudness, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

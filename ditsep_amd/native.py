@@ -43,6 +43,7 @@ EXPORTS = [
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
+    "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
 ]
 
 
@@ -771,6 +772,137 @@ def check_pcm_items(items, nbytes: int, downmix: bool = True) -> tuple:
     return offs, frames, chans, codes, (1 if downmix else max(chans)), max(frames)
 
 
+LOUDNESS_DEFAULTS = dict(target=-23.0, peak=-1.0, link="mixture")
+LOUDNESS_LINKS = ("mixture", "stem")
+LOUDNESS_RATES = (8000, 192000)                                                    # LOUD_MIN_RATE, LOUD_MAX_RATE
+LOUDNESS_MAX_CHANNELS = 2                                                          # LOUD_MAX_CH
+
+
+def loudness_options(spec) -> Optional[dict]:
+    """The `loudness` keyword of the separation entry points: None (off, the default) -> None; True ->
+    LOUDNESS_DEFAULTS (-23 LUFS, a true-peak ceiling of -1 dBTP, one gain per item from the mixture); a number -> the
+    defaults with that target; a dict of target / peak / link -> the defaults with those replaced (peak=None: no
+    ceiling).  Anything else -- False, an unknown key or link, a target or ceiling that is not a finite number -- is
+    refused by name."""
+    if spec is None:
+        return None
+    if spec is True:
+        opts = dict(LOUDNESS_DEFAULTS)
+    elif isinstance(spec, (int, float)) and not isinstance(spec, bool):
+        opts = dict(LOUDNESS_DEFAULTS, target=spec)
+    elif isinstance(spec, Mapping):
+        extra = sorted(set(spec) - set(LOUDNESS_DEFAULTS))
+        if extra:
+            raise ValueError(f"loudness: unknown keys {extra} (a dict of {sorted(LOUDNESS_DEFAULTS)})")
+        opts = dict(LOUDNESS_DEFAULTS, **spec)
+    else:
+        raise ValueError(f"loudness must be None, True, a target in LUFS or a dict of {sorted(LOUDNESS_DEFAULTS)} "
+                         f"(got {spec!r})")
+    for key in ("target", "peak"):
+        v = opts[key]
+        if key == "peak" and v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"loudness: {key} = {v!r} is not a finite number"
+                             + (" (or None: no ceiling)" if key == "peak" else ""))
+        opts[key] = float(v)
+    if opts["link"] not in LOUDNESS_LINKS:
+        raise ValueError(f"loudness: link must be one of {LOUDNESS_LINKS} (got {opts['link']!r})")
+    return opts
+
+
+def check_loudness(shape, rates, lens=None, channels=None) -> tuple:
+    """The refusals of dsn_loudness (include/ditsep_hip.h), raised by name before the library is touched: x that is
+    not [L], [C, L] or [B, C, L]; B outside [1, 65535]; C outside [1, 2]; L outside [1, 2^30]; rates that is not an
+    integer or one integer per item in [8000, 192000]; lens[b] outside [1, L]; channels[b] outside [1, C].
+    -> ((B, C, L), rates, lens or None, channels or None) as lists"""
+    if len(shape) not in (1, 2, 3):
+        raise ValueError(f"loudness: x must be [L], [C, L] or [B, C, L] (got {tuple(shape)})")
+    B, Cn, L = (1,) * (3 - len(shape)) + tuple(int(v) for v in shape)
+    if B < 1 or B > 65535:
+        raise ValueError(f"loudness: B = {B} outside [1, 65535]")
+    if Cn < 1 or Cn > LOUDNESS_MAX_CHANNELS:
+        raise ValueError(f"loudness: C = {Cn} outside [1, {LOUDNESS_MAX_CHANNELS}] (every channel has weight 1: no "
+                         f"surround weights)")
+    if L < 1 or L > 2 ** 30:
+        raise ValueError(f"loudness: L = {L} outside [1, 2^30]")
+    rates = [rates] * B if isinstance(rates, int) else list(rates)
+    if len(rates) != B:
+        raise ValueError(f"loudness: one sample rate per item is needed (B = {B}), got {len(rates)}")
+    for b, r in enumerate(rates):
+        if isinstance(r, bool) or int(r) != r or not LOUDNESS_RATES[0] <= int(r) <= LOUDNESS_RATES[1]:
+            raise ValueError(f"loudness: rates[{b}] = {r!r} is not an integer in [{LOUDNESS_RATES[0]}, "
+                             f"{LOUDNESS_RATES[1]}] Hz")
+    ch = None
+    if channels is not None:
+        ch = [int(v) for v in channels]
+        if len(ch) != B:
+            raise ValueError(f"loudness: channels must hold one channel count per item (B = {B}), got {len(ch)}")
+        for b, v in enumerate(ch):
+            if v < 1 or v > Cn:
+                raise ValueError(f"loudness: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    return (B, Cn, L), [int(r) for r in rates], (None if lens is None else check_lens(lens, B, L)), ch
+
+
+def kweight_coeffs(fs: int):
+    """The K-weighting cascade at `fs` Hz (dsn_kweight_coeffs; needs no GPU): float64 [10] = the shelf's b0 b1 b2 a1
+    a2, then the high-pass's."""
+    import numpy as np
+
+    out = np.zeros(10, dtype=np.float64)
+    if isinstance(fs, bool) or int(fs) != fs or load_library().dsn_kweight_coeffs(
+            int(fs), out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise ValueError(f"kweight_coeffs: fs = {fs!r} is not an integer in [{LOUDNESS_RATES[0]}, {LOUDNESS_RATES[1]}] Hz")
+    return out
+
+
+def loudness_gain(stats_src, stats_rows, groups, target, peak) -> dict:
+    """The gain rule of the `loudness` keyword (pure host arithmetic in float64).  Row r of the output has a gain
+    source of integrated loudness stats_src[r] (LUFS) and its own true peak stats_rows[r] (linear); rows with the same
+    groups[r] share one gain (groups=None: every row alone) and must share the source.
+      g_dB = target - I_src;   with a ceiling (peak is not None): g_dB = min(g_dB, peak - 20 log10(TP)), TP the largest
+      true peak of the group (a group of silent rows has no ceiling);   I_src = -inf (nothing passed the gates) or a
+      statistic that is NaN (non-finite samples) gives 0 dB, and the row is named.
+    -> {"gain_db": [R] float64, "gain": [R] 10^(g_dB / 20) rounded once to float32 (as Python floats), "limited": [R]
+    bool (the ceiling set the gain), "silent": the rows whose source was -inf, "nonfinite": the rows with a NaN}"""
+    import numpy as np
+
+    src = [float(v) for v in stats_src]
+    tp = [float(v) for v in stats_rows]
+    R = len(src)
+    if len(tp) != R:
+        raise ValueError(f"loudness_gain: {R} sources but {len(tp)} rows")
+    groups = list(range(R)) if groups is None else list(groups)
+    if len(groups) != R:
+        raise ValueError(f"loudness_gain: {R} rows but {len(groups)} group labels")
+    target = float(target)
+    members = {}
+    for r, k in enumerate(groups):
+        members.setdefault(k, []).append(r)
+    gain_db, limited, silent, nonfinite = [0.0] * R, [False] * R, [], []
+    for k, rows in members.items():
+        I = src[rows[0]]
+        if any(src[r] != I and not (math.isnan(src[r]) and math.isnan(I)) for r in rows):
+            raise ValueError(f"loudness_gain: the rows of group {k!r} do not share one gain source")
+        top = max(tp[r] for r in rows) if not any(math.isnan(tp[r]) for r in rows) else math.nan
+        if math.isnan(I) or math.isnan(top) or I == math.inf:
+            nonfinite.extend(rows)
+            continue
+        if I == -math.inf:
+            silent.extend(rows)
+            continue
+        g, lim = target - I, False
+        if peak is not None and top > 0.0:
+            ceil_db = float(peak) - 20.0 * math.log10(top)
+            if ceil_db < g:
+                g, lim = ceil_db, True
+        for r in rows:
+            gain_db[r], limited[r] = g, lim
+    gain = [float(np.float32(10.0 ** (g / 20.0))) for g in gain_db]
+    return {"gain_db": gain_db, "gain": gain, "limited": limited, "silent": sorted(silent),
+            "nonfinite": sorted(nonfinite)}
+
+
 _lib = None
 
 
@@ -870,6 +1002,9 @@ def load_library() -> C.CDLL:
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_mrstft_loss_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, C.POINTER(DsnMrstftConfig),
                                            C.POINTER(DsnMrstftOut), vp]
+    lib.dsn_kweight_coeffs.argtypes = [ci, f64p]
+    lib.dsn_loudness.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, ci, f64p, vp]
+    lib.dsn_apply_gain.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, fp, vp, vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -1908,6 +2043,102 @@ class Engine:
                                               C.cast(C.c_void_p(alpha.data_ptr()), C.POINTER(C.c_float)),
                                               self._stream()), "dsn_scale_output")
         return out, alpha
+
+    # ------------------------------------------------------------------ loudness, true peak and one gain
+    def loudness(self, x, rates, lens=None, channels=None, true_peak=True) -> dict:
+        """Programme loudness by ITU-R BS.1770-4 / EBU R 128 and the peaks of a ragged batch on the device
+        (dsn_loudness, csrc/loudness.hip; the definition is in include/ditsep_hip.h and tests/loudness_restatement.py):
+        x [L], [C, L] or [B, C, L] with C <= 2, rates an int or one rate per item in [8000, 192000] Hz, lens /
+        channels one count per item (default: L and C) -> a dict of host tensors, one entry per item:
+          "loudness"     float64, integrated loudness in LUFS (K-weighting, 400 ms blocks every 100 ms, the absolute
+                         gate at -70 and the relative gate 10 LU under the gated mean); -inf when no block passes
+          "true_peak"    float64, linear: max |.| of the item at four times its rate (the project's resampler at 1 -> 4);
+                         NaN with true_peak=False
+          "sample_peak"  float64, linear: max |x|
+          "blocks", "gated_blocks"  int64: complete blocks, and those that pass both gates
+          "nonfinite"    int64: samples that are NaN or infinite (both peaks are then NaN)
+        Nothing at or past lens[b] or in a channel an item does not have is read (it may hold NaN); an item has the
+        bits it has alone, whatever the batch.  Needs no score network and no codec."""
+        (B, Cn, L), rt, ln, ch = check_loudness(tuple(x.shape), rates, lens, channels)
+        x = _dev32(x, self.device).reshape(B, Cn, L)
+        stats = torch.zeros((B, 6), dtype=torch.float64)
+        i32 = C.c_int32 * B
+        self._check(self.lib.dsn_loudness(self.ctx, _ptr(x), B, Cn, L, None if ln is None else i32(*ln),
+                                          None if ch is None else i32(*ch), i32(*rt), int(bool(true_peak)),
+                                          C.cast(C.c_void_p(stats.data_ptr()), C.POINTER(C.c_double)),
+                                          self._stream()), "dsn_loudness")
+        return {"loudness": stats[:, 0].clone(), "true_peak": stats[:, 1].clone(), "sample_peak": stats[:, 2].clone(),
+                "blocks": stats[:, 3].long(), "gated_blocks": stats[:, 4].long(), "nonfinite": stats[:, 5].long()}
+
+    def apply_gain(self, x, gain, lens=None, channels=None, out=None):
+        """out = gain[r] x, one float32 product per sample (dsn_apply_gain): x [R, C, L] (or [C, L], [L]) with C <= 2,
+        gain one number per row (rounded to float32), lens / channels one count per row (default: L and C) -- zero
+        at or past lens[r] and in the channels a row does not have, where nothing is read.  out=x works in place."""
+        shape = tuple(x.shape)
+        (R, Cn, L), _, ln, ch = check_loudness(shape, LOUDNESS_RATES[0], lens, channels)
+        gain = [float(g) for g in (gain.tolist() if torch.is_tensor(gain) else gain)]
+        if len(gain) != R:
+            raise ValueError(f"apply_gain: one gain per row is needed (R = {R}), got {len(gain)}")
+        x = _dev32(x, self.device)
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+            raise ValueError("apply_gain: out must be a contiguous float32 tensor of x's shape on the device")
+        i32 = C.c_int32 * R
+        self._check(self.lib.dsn_apply_gain(self.ctx, _ptr(x), R, Cn, L, None if ln is None else i32(*ln),
+                                            None if ch is None else i32(*ch), (C.c_float * R)(*gain), _ptr(out),
+                                            self._stream()), "dsn_apply_gain")
+        return out
+
+    def loudness_normalize(self, sources, stems, rates, target=-23.0, peak=-1.0, link="mixture"):
+        """The `loudness` keyword's last step for a list of items: `stems` is one [n, L_b] or [n, C_b, L_b] tensor per
+        item at rates[b], `sources` the items' mixtures [C'_b, L'_b] (or [L'_b]) at the same rates.  link "mixture":
+        every item's gain source is its mixture and its n stems share one gain; link "stem": every stem is its own
+        source (sources may be None).  One Engine.loudness call on the padded mixtures, one on the padded stems, the
+        gains by native.loudness_gain, one Engine.apply_gain call.  -> (list of tensors shaped like `stems`, info) with
+        info = {"loudness_in", "loudness_out", "gain_db", "true_peak_db": one list of n floats per item (the source's
+        loudness, that plus the gain, the gain, the stem's true peak after the gain in dBTP), "limited": likewise,
+        booleans, "silent" / "nonfinite": the (item, stem) pairs left at 0 dB because their source passed no block /
+        held non-finite samples}."""
+        if link not in LOUDNESS_LINKS:
+            raise ValueError(f"loudness: link must be one of {LOUDNESS_LINKS} (got {link!r})")
+        B = len(stems)
+        rates = [int(rates)] * B if isinstance(rates, int) else [int(r) for r in rates]
+        rows3 = [s[:, None] if s.dim() == 2 else s for s in stems]
+        for b, s in enumerate(rows3):
+            if s.dim() != 3:
+                raise ValueError(f"loudness: item {b} must be [n, L] or [n, C, L] (got {tuple(stems[b].shape)})")
+        n = int(rows3[0].shape[0])
+        ch = [int(s.shape[1]) for s in rows3]
+        ln = [int(s.shape[2]) for s in rows3]
+        x = torch.zeros((B * n, max(ch), max(ln)), device=self.device, dtype=torch.float32)
+        for b, s in enumerate(rows3):
+            x[b * n:(b + 1) * n, :ch[b], :ln[b]] = _dev32(s, self.device)
+        rep = lambda v: [a for a in v for _ in range(n)]
+        rows = self.loudness(x, rep(rates), rep(ln), rep(ch))
+        if link == "mixture":
+            if sources is None or len(sources) != B:
+                raise ValueError("loudness: link 'mixture' needs one mixture per item")
+            src = [m.reshape(-1, m.shape[-1]) for m in sources]
+            sc, sl = [int(m.shape[0]) for m in src], [int(m.shape[1]) for m in src]
+            mx = torch.zeros((B, max(sc), max(sl)), device=self.device, dtype=torch.float32)
+            for b, m in enumerate(src):
+                mx[b, :sc[b], :sl[b]] = _dev32(m, self.device)
+            I_src = rep(self.loudness(mx, rates, sl, sc, true_peak=False)["loudness"].tolist())
+            groups = rep(list(range(B)))
+        else:
+            I_src, groups = rows["loudness"].tolist(), None
+        g = loudness_gain(I_src, rows["true_peak"].tolist(), groups, target, peak)
+        self.apply_gain(x, g["gain"], rep(ln), rep(ch), out=x)
+        outs = [x[b * n:(b + 1) * n, :ch[b], :ln[b]].reshape(stems[b].shape) for b in range(B)]
+        tp = rows["true_peak"].tolist()
+        tp_db = [20.0 * math.log10(v) + d if v > 0.0 else (-math.inf if v == 0.0 else math.nan)
+                 for v, d in zip(tp, g["gain_db"])]
+        per = lambda v: [list(v[b * n:(b + 1) * n]) for b in range(B)]
+        info = {"loudness_in": per(I_src), "loudness_out": per([a + d for a, d in zip(I_src, g["gain_db"])]),
+                "gain_db": per(g["gain_db"]), "true_peak_db": per(tp_db), "limited": per(g["limited"]),
+                "silent": [divmod(r, n) for r in g["silent"]], "nonfinite": [divmod(r, n) for r in g["nonfinite"]]}
+        return outs, info
 
     @property
     def hop_length(self) -> int:

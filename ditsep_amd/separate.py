@@ -27,6 +27,15 @@ def _bool(x):
     raise argparse.ArgumentTypeError(f"expected a boolean, got {x!r}")
 
 
+def _dbtp(x):
+    if str(x).lower() == "none":
+        return None
+    try:
+        return float(x)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a level in dBTP or 'none', got {x!r}") from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The command line (importing and calling this needs neither the HIP library nor a GPU)."""
     p = argparse.ArgumentParser(prog="python -m ditsep_amd.separate",
@@ -77,6 +86,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stems-power", type=int, default=2, choices=[1, 2], help="Exponent of the mask magnitudes")
     p.add_argument("--stems-reg", type=float, default=1e-3,
                    help="Diagonal loading of the Wiener solve, relative to the mean channel variance")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="Bring every file's stems to this programme loudness (ITU-R BS.1770 / EBU R 128, measured on "
+                        "the device) with one gain, e.g. -23; a gain, not a limiter (off by default)")
+    p.add_argument("--true-peak", type=_dbtp, default=-1.0, metavar="DBTP",
+                   help="With --loudness: the gain is held back so that no stem's true peak exceeds this (default -1; "
+                        "'none': no ceiling)")
+    p.add_argument("--loudness-link", default="mixture", choices=["mixture", "stem"],
+                   help="With --loudness: measure the input file and give all its stems one gain (mixture), or bring "
+                        "every stem to the target by itself (stem)")
     return p
 
 
@@ -116,6 +134,13 @@ def stems_of(args):
                 reg=args.stems_reg)
 
 
+def loudness_of(args):
+    """The `loudness` keyword of separate_files from the parsed flags: None unless --loudness is given."""
+    if args.loudness is None:
+        return None
+    return dict(target=args.loudness, peak=args.true_peak, link=args.loudness_link)
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     try:
@@ -145,14 +170,16 @@ def main(argv=None) -> int:
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
-                                           stems=stems_of(args), denoise=args.denoise, **kw)
+                                           stems=stems_of(args), loudness=loudness_of(args), denoise=args.denoise,
+                                           **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
         for r in records:
             clipped = sum(r["clipped"])
             print(f"{r['path']}: {r['frames']} frames at {r['rate']} Hz, {r['channels']} ch -> {len(r['outputs'])} files"
-                  + (f", {clipped} samples clipped" if clipped else ""))
+                  + (f", {clipped} samples clipped" if clipped else "")
+                  + (f", gain {', '.join(f'{g:+.2f}' for g in r['gain_db'])} dB" if "gain_db" in r else ""))
         return 0
     finally:
         model.close()

@@ -723,6 +723,63 @@ int dsn_pcm_encode_frames(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, 
 int dsn_scale_output(dsn_ctx* ctx, const float* mix, const float* sep, int B, int n, int Lmax, const int32_t* lens,
                      float* out, float* alpha_out, void* stream);
 
+/* Programme loudness, true peak and one gain on the device: the level step in front of dsn_pcm_encode* (ITU-R BS.1770-4 /
+ * EBU R 128 integrated loudness; csrc/loudness.hip, restated in float64 in tests/loudness_restatement.py).  A
+ * measurement and a single gain, not a limiter; nothing calls it unless asked to.  x [B][C][Lmax] fp32 (device), C <= 2.
+ * Item b has channels[b] <= C channels, lens[b] samples and its own rate rates[b] in Hz, any integer in [8000, 192000];
+ * every channel has weight 1.
+ *   K-weighting  two biquads in cascade, formed on the host in fp64 from the rate fs (the libebur128 / pyloudnorm
+ *                formulation).  Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                K = tan(pi f0 / fs), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0, a = [1, 2 (K^2 - 1) / a0,
+ *                (1 - K / Q + K^2) / a0].  High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K, a0 and a by
+ *                the same expressions, b = [1, -2, 1] (not divided by a0).  At 48 kHz these are the standard's table.
+ *                dsn_kweight_coeffs(fs, out): out = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (no context, no
+ *                GPU); DSN_EINVAL for a rate outside [8000, 192000] or a null out.
+ *   blocks       h = (fs + 5) / 10 by integer division (11025 Hz gives 1103).  Block j covers samples [j h, j h + 4 h)
+ *                of the filtered signal y, which starts from zero state at sample 0; only complete blocks count:
+ *                J = (L - 4 h) / h + 1 when L >= 4 h, else 0.  z_j = sum_c mean(y_c^2) over the block,
+ *                l_j = -0.691 + 10 log10(z_j).
+ *   gates        absolute: l_j > -70.  Gamma = -0.691 + 10 log10(mean of z_j over the absolute-gated blocks) - 10.
+ *                I = -0.691 + 10 log10(mean of z_j over the blocks with l_j > -70 and l_j > Gamma); -inf when no
+ *                block passes.
+ *   true peak    the maximum of |.| over all channels of the item interpolated to four times its rate by this
+ *                library's resampler at the ratio 1 -> 4 (dsn_resample_plan(1, 4): 4 phases of 13 taps, zero beyond an
+ *                item's own ends), each value one fp32 product and support - 1 fused multiply-adds in tap order.  The
+ *                sample peak is max |x|.  Both are exact maxima: they do not depend on the order of reduction.  A
+ *                non-finite sample makes both peaks NaN and is counted.  Without want_true_peak the true peak is NaN.
+ * The recursion runs in fp64 over chunks of 256 samples counted from the item's own start: a first launch filters
+ * every chunk from zero state and keeps its final state (four doubles), one thread per (item, channel) carries the
+ * true state across the chunks with the 4 x 4 zero-input transition matrix raised to the chunk length (formed on the
+ * host in fp64 per distinct rate), a second launch filters every chunk again from its true state and adds y^2 in fp64
+ * in sample order into the two h-sample segments the chunk touches; a block is four consecutive segments, a segment
+ * the sum of its chunks' parts in chunk order, and one pass per item forms z_j, the gates and I in fp64 in index
+ * order.  The peaks are one more launch that stages a tile and its halo in LDS (16-byte loads where a quad is aligned
+ * and whole) and writes no interpolated signal.  No floating-point atomics (the maxima and the count are integer
+ * atomics, which no order changes): an item has the same bits alone, at any batch position, under any padding, from a
+ * base pointer of any 4-byte alignment and in a second call -- they depend on its own samples, length, rate and
+ * channel count alone.  Nothing at or past lens[b], or in a channel an item does not have, is read (it may hold NaN).
+ *   dsn_loudness    stats_host [B][6] doubles (HOST): I (LUFS), true peak (linear), sample peak (linear), J, the number
+ *                   of blocks passing both gates, the count of non-finite samples.  lens, channels and rates are HOST
+ *                   arrays; lens and channels may be NULL (Lmax and C for every item).  The call uploads its tables and
+ *                   synchronises the stream: it must not be captured into a graph.  The workspace lives in the context
+ *                   and grows.  Needs no score network and no codec.
+ *   dsn_apply_gain  x [R][C][Lmax] -> out [R][C][Lmax]: out = gain[r] x as one fp32 product per sample; zero at or past
+ *                   lens[r] and in the channels past channels[r], where nothing is read.  gain [R] is a HOST fp32 array.
+ *                   16-byte loads and stores where the rows are aligned, scalar ones otherwise, with the same bits.
+ *                   out may be x itself (any other overlap is refused).
+ * The gain that reaches a target is the caller's to form from the statistics (ditsep_amd.native.loudness_gain:
+ * g_dB = target - I_src, at most ceiling - 20 log10(TP) with a true-peak ceiling, 0 dB for I_src = -inf; 10^(g_dB / 20)
+ * rounded once to fp32).
+ * DSN_EINVAL by name, before anything is allocated or launched: a null pointer (x, rates, stats_host; x, gain, out);
+ * B or R < 1 or > 65535; C outside [1, 2]; channels[b] outside [1, C]; lens[b] outside [1, Lmax]; a rate outside
+ * [8000, 192000]; Lmax < 1 or > 2^30. */
+int dsn_kweight_coeffs(int fs, double* out);
+int dsn_loudness(dsn_ctx* ctx, const float* x, int B, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                 const int32_t* rates, int want_true_peak, double* stats_host, void* stream);
+int dsn_apply_gain(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                   const float* gain, float* out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
