@@ -3566,6 +3566,130 @@ int dsn_apply_gain(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const i
   });
 }
 
+// ---- the true-peak look-ahead limiter (limiter.hip; include/ditsep_hip.h states the definition)
+// W = max(1, floor(lookahead_ms fs / 1000 + 1/2)), or -1 when that is not in [1, LIM_MAX_W]
+static int limiter_half_window(double lookahead_ms, int fs) {
+  const double w = floor(lookahead_ms * (double)fs / 1000.0 + 0.5);
+  if (!(lookahead_ms >= 0.0) || !(w <= (double)LIM_MAX_W)) return -1;
+  return w < 1.0 ? 1 : (int)w;
+}
+
+static std::vector<LimRow> limiter_rows(const char* who, int R, int C, int Lmax, const int32_t* lens,
+                                        const int32_t* channels, const int32_t* group, int G) {
+  if (R < 1 || R > 65535) fail(DSN_EINVAL, "%s: %d rows, outside [1, 65535]", who, R);
+  if (C < 1 || C > LOUD_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, LOUD_MAX_CH);
+  if (Lmax < 1 || Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d outside [1, 2^30]", who, Lmax);
+  if (G < 1 || G > 65535) fail(DSN_EINVAL, "%s: %d groups, outside [1, 65535]", who, G);
+  std::vector<LimRow> rows((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    const int len = lens ? lens[r] : Lmax, ch = channels ? channels[r] : C;
+    if (len < 1 || len > Lmax)
+      fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, r, len, Lmax);
+    if (ch < 1 || ch > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, r, ch, C);
+    if (group[r] < 0 || group[r] >= G) fail(DSN_EINVAL, "%s: group[%d] = %d outside [0, G = %d)", who, r, (int)group[r], G);
+    rows[r] = LimRow{len, ch, (int)group[r], 0};
+  }
+  return rows;
+}
+
+int dsn_limiter_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                      const int32_t* rates, const int32_t* group, int G, const float* pregain, float ceiling,
+                      double lookahead_ms, float* curve, float* envelope, double* stats_host, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_limiter_curve";
+    if (!x || !rates || !group || !pregain || !curve || !stats_host)
+      fail(DSN_EINVAL, "%s: x, rates, group, pregain, curve or stats_host is null", who);
+    if (R >= 1 && G > R) fail(DSN_EINVAL, "%s: %d groups of %d rows: every group needs a row", who, G, R);
+    const std::vector<LimRow> rows = limiter_rows(who, R, C, Lmax, lens, channels, group, G);
+    if (!std::isfinite(ceiling) || !(ceiling > 0.f))
+      fail(DSN_EINVAL, "%s: the ceiling %g is not finite and positive", who, (double)ceiling);
+    if (!std::isfinite(lookahead_ms)) fail(DSN_EINVAL, "%s: lookahead_ms = %g is not finite", who, lookahead_ms);
+    std::vector<LimGroup> groups((size_t)G);
+    std::vector<int> distinct;   // half-windows
+    for (int r = 0; r < R; ++r) {
+      if (rates[r] < LOUD_MIN_RATE || rates[r] > LOUD_MAX_RATE)
+        fail(DSN_EINVAL, "%s: rates[%d] = %d Hz outside [%d, %d]", who, r, (int)rates[r], LOUD_MIN_RATE, LOUD_MAX_RATE);
+      const int g = rows[r].group;
+      if (r == 0 ? g != 0 : (g != rows[r - 1].group && g != rows[r - 1].group + 1))
+        fail(DSN_EINVAL, "%s: group[%d] = %d: the groups must be 0 .. G - 1 in non-decreasing order", who, r, g);
+      if (r > 0 && g == rows[r - 1].group) {
+        if (rows[r].len != rows[r - 1].len || rates[r] != rates[r - 1])
+          fail(DSN_EINVAL, "%s: rows %d and %d of group %d disagree on length or rate (%d at %d Hz, %d at %d Hz)", who,
+               r - 1, r, g, rows[r - 1].len, (int)rates[r - 1], rows[r].len, (int)rates[r]);
+        groups[g].row1 = r + 1;
+        continue;
+      }
+      const int W = limiter_half_window(lookahead_ms, rates[r]);
+      if (W < 0)
+        fail(DSN_EINVAL, "%s: a look-ahead of %g ms at %d Hz is a half-window W outside [1, %d]", who, lookahead_ms,
+             (int)rates[r], LIM_MAX_W);
+      if (!std::isfinite(pregain[g])) fail(DSN_EINVAL, "%s: pregain[%d] = %g is not finite", who, g, (double)pregain[g]);
+      auto it = std::find(distinct.begin(), distinct.end(), W);
+      groups[g] = LimGroup{r, r + 1, rows[r].len, W, (int)(it - distinct.begin()), pregain[g]};
+      if (it == distinct.end()) distinct.push_back(W);
+    }
+    if (rows[R - 1].group != G - 1) fail(DSN_EINVAL, "%s: the last row is of group %d, not G - 1 = %d", who, rows[R - 1].group, G - 1);
+    // w[k] = (1/2 + 1/2 cos(pi k / (W + 1))) / (W + 1), k = -W .. W, in fp64 and rounded once
+    const int wrow = 2 * LIM_MAX_W + 1;
+    std::vector<float> window(distinct.size() * (size_t)wrow, 0.f);
+    for (size_t i = 0; i < distinct.size(); ++i) {
+      const int W = distinct[i];
+      for (int k = -W; k <= W; ++k)
+        window[i * wrow + (size_t)(k + W)] = (float)((0.5 + 0.5 * cos(M_PI * (double)k / (double)(W + 1))) / (double)(W + 1));
+    }
+    const int Wmax = *std::max_element(distinct.begin(), distinct.end());
+    const dsn_ctx::ResampleTables& t = resample_tables(ctx, who, 1, 4);
+    hipStream_t st = (hipStream_t)stream;
+    float* req = ctx->wsbuf<float>("lim_req", (size_t)G * Lmax);
+    unsigned long long* counts = ctx->wsbuf<unsigned long long>("lim_count", (size_t)G * 3);
+    unsigned long long *bad = counts, *reduced = counts + G;
+    unsigned* deepest = (unsigned*)(counts + 2 * (size_t)G);
+    const LimRow* drows = (const LimRow*)upload_table(ctx, "lim_rows", rows.data(), sizeof(LimRow) * rows.size(), st);
+    const LimGroup* dgroups = (const LimGroup*)upload_table(ctx, "lim_groups", groups.data(), sizeof(LimGroup) * groups.size(), st);
+    const float* dwin = (const float*)upload_table(ctx, "lim_window", window.data(), sizeof(float) * window.size(), st);
+    HIPCHK(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (size_t)G * 3, st));
+    const ResamplePlan& p = t.plan;
+    ctx->prof_launch("limiter_curve", 4.0 * ((double)R * C + 3.0 * G) * Lmax, st, [&] {
+      launch_limiter_curve(x, drows, dgroups, G, C, Lmax, Wmax, ceiling, dwin, t.taps, t.k0, p.S, t.stride, t.kmin,
+                           t.kspan, p.width, req, envelope, curve, bad, reduced, deepest, st);
+    });
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned long long> host((size_t)G * 3);
+    HIPCHK(hipMemcpyAsync(host.data(), counts, sizeof(unsigned long long) * host.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned* deep = (const unsigned*)(host.data() + 2 * (size_t)G);
+    for (int g = 0; g < G; ++g) {
+      const uint32_t bits = 0x3f800000u - deep[g];
+      float low;
+      memcpy(&low, &bits, sizeof low);
+      stats_host[3 * g] = host[g] ? (double)NAN : (double)low;
+      stats_host[3 * g + 1] = (double)host[(size_t)G + g];
+      stats_host[3 * g + 2] = (double)host[g];
+    }
+  });
+}
+
+int dsn_apply_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                    const int32_t* group, int G, const float* pregain, const float* curve, float* out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_apply_curve";
+    if (!x || !group || !pregain || !curve || !out) fail(DSN_EINVAL, "%s: x, group, pregain, curve or out is null", who);
+    // (the groups of these rows are the curve's: any order, and a group may have no row here)
+    const std::vector<LimRow> rows = limiter_rows(who, R, C, Lmax, lens, channels, group, G);
+    const char *x0 = (const char*)x, *o0 = (const char*)out;
+    const size_t bytes = sizeof(float) * (size_t)R * C * Lmax;
+    if (o0 != x0 && o0 < x0 + bytes && x0 < o0 + bytes)
+      fail(DSN_EINVAL, "%s: out overlaps x without being x (in place is fine, a shifted copy is not)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const LimRow* drows = (const LimRow*)upload_table(ctx, "curve_rows", rows.data(), sizeof(LimRow) * rows.size(), st);
+    const float* dgain = (const float*)upload_table(ctx, "curve_pregain", pregain, sizeof(float) * (size_t)G, st);
+    ctx->prof_launch("apply_curve", 4.0 * (2.0 * R * C + G) * Lmax, st, [&] {
+      launch_apply_curve(x, drows, dgain, curve, out, R, C, Lmax, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
 static double bessel_i0(double x) {
   double s = 1.0, t = 1.0;

@@ -511,3 +511,29 @@ void launch_loudness(const float* x, const LoudItem* items, const LoudRate* rate
 // out = gain[r] x over a row's own samples and channels (rows [R]: len, ch), zero elsewhere; out may be x
 void launch_apply_gain(const float* x, const LoudItem* rows, const float* gain, float* out, int R, int C, int Lmax,
                        hipStream_t s);
+
+// ---- true-peak look-ahead limiter (limiter.hip) ------------------------------------------------------------------
+// x [R][C][Lmax] fp32.  rows [R] and groups [G] are device tables: a row's samples, channels and group; a group's rows
+// [row0, row1), their common length, the half-window W, the row of `window` ([distinct W][2 LIM_MAX_W + 1], w[-W .. W]
+// from column 0) and the pre-gain.  Two launches over tiles of LIM_TILE samples: the required gain r into req
+// [G][Lmax] (and the envelope p into env [G][Lmax] unless null) with bad [G] counting non-finite samples, then the
+// curve [G][Lmax] with reduced [G] (samples with g < 1) and deepest [G] (0x3f800000 minus the bits of the smallest g,
+// under an integer maximum); bad, reduced and deepest zeroed by the caller.  taps [4][stride], k0 [4]: the (1, 4)
+// resampling tables on the device.
+#define LIM_TILE 2048
+#define LIM_MAX_W 1024
+struct LimRow {
+  int len, ch, group, pad;
+};
+struct LimGroup {
+  int row0, row1, len, W, wofs;
+  float pregain;
+};
+size_t limiter_curve_lds(int Wmax);
+void launch_limiter_curve(const float* x, const LimRow* rows, const LimGroup* groups, int G, int C, int Lmax, int Wmax,
+                          float ceiling, const float* window, const float* taps, const int* k0, int S, int stride,
+                          int kmin, int kspan, int width, float* req, float* env, float* curve, unsigned long long* bad,
+                          unsigned long long* reduced, unsigned* deepest, hipStream_t s);
+// out = (pregain[group] x) curve[group][t] over a row's own samples and channels, zero elsewhere; out may be x
+void launch_apply_curve(const float* x, const LimRow* rows, const float* pregain, const float* curve, float* out, int R,
+                        int C, int Lmax, hipStream_t s);

@@ -90,7 +90,7 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, loudness=None, **sampler_kwargs) -> list:
+                   stems=None, loudness=None, limit=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -104,7 +104,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     if stems is not None and rescale:
         raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
                          "mixture")
-    loud = native.loudness_options(loudness)
+    loud = native.level_options(loudness, limit)
+    linked = loud is not None and loud["link"] == "mixture" and loud["target"] is not None   # the file is the source
     if long_mode not in native.LONG_MODES:
         raise ValueError(f"long_mode must be one of {native.LONG_MODES} (got {long_mode!r})")
     paths = [os.fspath(p) for p in paths]
@@ -114,11 +115,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             if not native.LOUDNESS_RATES[0] <= h.rate <= native.LOUDNESS_RATES[1]:
                 raise ValueError(f"{p}: {h.rate} Hz; loudness= measures rates in [{native.LOUDNESS_RATES[0]}, "
                                  f"{native.LOUDNESS_RATES[1]}] Hz")
-            if loud["link"] == "mixture" and h.channels > native.LOUDNESS_MAX_CHANNELS:
+            if linked and h.channels > native.LOUDNESS_MAX_CHANNELS:
                 raise ValueError(f"{p}: {h.channels} channels; loudness= with link 'mixture' measures at most "
                                  f"{native.LOUDNESS_MAX_CHANNELS} (no surround weights; link 'stem' measures the outputs)")
     # the files' own channels are needed by the stems filter and as the gain source of a mixture-linked loudness
-    keep_channels = stems is not None or (loud is not None and loud["link"] == "mixture")
+    keep_channels = stems is not None or linked
     hop = model.hop_length
     ens = {} if samples is None else dict(samples=native.check_samples(samples, combine), combine=combine)
     plan = plan_files(headers, fs, hop, files_per_batch(batch, samples), long_after)
@@ -151,9 +152,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         """the `loudness` step: rows at the files' own rates -> (the rows with their gains applied, the record entries)"""
         if loud is None:
             return back, [{} for _ in idx]
-        back, info = eng.loudness_normalize(clips, back, [headers[i].rate for i in idx], **loud)
-        return back, [{k: info[k][j] for k in ("loudness_in", "loudness_out", "gain_db", "true_peak_db")}
-                      for j in range(len(idx))]
+        back, info = eng.loudness_normalize(clips if linked else None, back, [headers[i].rate for i in idx], **loud)
+        keys = ("loudness_in", "loudness_out", "gain_db", "true_peak_db")
+        if loud.get("limit") is not None:
+            keys += ("reached", "evaluations", "reduction_db", "limited_samples")
+        return back, [{k: info[k][j] for k in keys} for j in range(len(idx))]
 
     def finish_stems(idx, clips, est, label):
         """mono estimates at the model's rate -> multichannel files; `clips` the files' own channels at their own rates"""

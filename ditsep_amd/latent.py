@@ -420,7 +420,7 @@ class LatentDiffSep:
             raise ValueError("loudness= does not go with intermediate: the per-step states are not normalised")
         most = native.LOUDNESS_MAX_CHANNELS
         for b, c in enumerate(channels):
-            if lopts["link"] == "mixture" and (c < 1 or c > most):
+            if lopts["link"] == "mixture" and lopts["target"] is not None and (c < 1 or c > most):
                 raise ValueError(f"loudness: mixture {b} has {c} channels, outside [1, {most}] (every channel has "
                                  f"weight 1: no surround weights; link='stem' measures the stems instead)")
 
@@ -433,7 +433,7 @@ class LatentDiffSep:
         """The last step of the entry points with loudness=: Engine.loudness_normalize on the lists, and the info dict
         merged into the combine's (inner_info) or appended (return_info alone)"""
         src = None
-        if lopts["link"] == "mixture":
+        if lopts["link"] == "mixture" and lopts["target"] is not None:
             src = [m[None] if m.dim() == 1 else m.reshape(-1, m.shape[-1]) for m in sources]
         outs, info = self.engine.loudness_normalize(src, list(ests), rates, **lopts)
         others = list(others)
@@ -445,7 +445,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
-                 return_info=False, stems=None, loudness=None, **kwargs):
+                 return_info=False, stems=None, loudness=None, limit=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -480,8 +480,17 @@ class LatentDiffSep:
         every stem is brought to the target by itself.  A source that passes no gating block stays at 0 dB.
         return_info=True (allowed without samples= then) appends, or merges into the combine's info, "loudness_in",
         "loudness_out", "gain_db", "true_peak_db" (one list of n per item), "limited", "silent", "nonfinite".  Refused
-        with latent=True and with intermediate."""
-        lopts = native.loudness_options(loudness)
+        with latent=True and with intermediate.
+        limit (default None: the call returns the bits it returned before): True or a dict of ceiling / lookahead_ms /
+        drive_db / iterations / tol (native.limit_options) -- the true-peak look-ahead limiter (Engine.limiter_curve /
+        apply_curve) as part of that last step: an item whose target the ceiling forbids to a single gain is driven
+        harder and only the neighbourhood of its peaks is lowered, until the limited programme measures the target
+        within tol (Engine.loudness_normalize states the loop); an item the single gain brings to the target keeps
+        its bits.  With link "mixture" the stems share the curve g[t], so stems that summed to the mixture sum to
+        g[t] G mixture[t].  Without loudness= every item goes once
+        through the limiter at 0 dB against the ceiling (default -1 dBTP).  The info gains "reached", "evaluations",
+        "reduction_db" and "limited_samples".  Refused where loudness= is."""
+        lopts = native.level_options(loudness, limit)
         if lopts is not None:
             chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else [1]
             self._loudness_refusals(lopts, chans, latent=latent, intermediate=kwargs.get("intermediate"))
@@ -547,7 +556,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
-                       combine="mean", return_info=False, stems=None, loudness=None, **sampler_kwargs):
+                       combine="mean", return_info=False, stems=None, loudness=None, limit=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -570,9 +579,11 @@ class LatentDiffSep:
         the model's rate, and a list of [n, C_b, L_b] comes back, each item with the bits it gets alone.
         loudness (default None: off), as in `separate`: the last step, one Engine.loudness call on the padded mixtures
         as they were given (each at its own rate, with its own channels), one on the padded estimates, one
-        Engine.apply_gain call; each item gets the gain it gets alone."""
+        Engine.apply_gain call; each item gets the gain it gets alone.
+        limit (default None: off), as in `separate`: the items the ceiling holds back go through the limiter's loop
+        together, each with the pre-gains and the curve it gets alone."""
         eng = self.engine
-        lopts = native.loudness_options(loudness)
+        lopts = native.level_options(loudness, limit)
         if lopts is not None:
             mixes = list(mixes)
             self._loudness_refusals(lopts, [self._clip_channels(m) for m in mixes],
@@ -642,7 +653,8 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
-                      mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, **sampler_kwargs):
+                      mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
+                      **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -663,9 +675,10 @@ class LatentDiffSep:
         downmixes, and every recording's channels are filtered whole (Engine.stems) at the model's rate after the
         stitch and refine: [n, C, L] or a list of [n, C_r, L_r] comes back.
         loudness (default None: off), as in `separate_batch`: every recording is measured whole and gets one gain,
-        the last step; with return_info=True its entries join the stitch's info dict."""
+        the last step; with return_info=True its entries join the stitch's info dict.
+        limit (default None: off), as in `separate_batch`: every recording is limited whole."""
         eng = self.engine
-        lopts = native.loudness_options(loudness)
+        lopts = native.level_options(loudness, limit)
         if lopts is not None:
             single = torch.is_tensor(mixes)
             clips = [mixes] if single else list(mixes)
@@ -751,7 +764,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
-                       samples=None, combine="mean", stems=None, loudness=None, **sampler_kwargs):
+                       samples=None, combine="mean", stems=None, loudness=None, limit=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -784,13 +797,17 @@ class LatentDiffSep:
         measures the file as it was decoded, with its channels (at most two; refused before any device work
         otherwise), and all its speakers share one gain; link "stem" brings every speaker's file to the target.  Each
         dict gains "loudness_in", "loudness_out", "gain_db" and "true_peak_db", one entry per speaker.  A single
-        gain, not a limiter, and no dither."""
+        gain, not a limiter, and no dither.
+        limit (default None: off, the files are the bytes they were), as in `separate`: the true-peak look-ahead limiter
+        in that last step, immediately before the quantiser; a file the single gain brings to the target keeps its
+        bytes.  Each dict gains "reached", "evaluations", "reduction_db" and "limited_samples", one entry per speaker
+        (and, without loudness=, the four entries above)."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
-                                    loudness=loudness, **sampler_kwargs)
+                                    loudness=loudness, limit=limit, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -44,6 +44,7 @@ EXPORTS = [
     "dsn_stems", "dsn_pcm_encode_frames",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
+    "dsn_limiter_curve", "dsn_apply_curve",
 ]
 
 
@@ -903,6 +904,158 @@ def loudness_gain(stats_src, stats_rows, groups, target, peak) -> dict:
             "nonfinite": sorted(nonfinite)}
 
 
+LIMIT_DEFAULTS = dict(ceiling=None, lookahead_ms=5.0, drive_db=6.0, iterations=4, tol=0.1)
+LIMIT_MAX_HALF_WINDOW = 1024                                                       # LIM_MAX_W
+LIMIT_DEFAULT_CEILING = -1.0                                                       # dBTP, when loudness= sets none
+
+
+def limit_options(spec) -> Optional[dict]:
+    """The `limit` keyword of the separation entry points: None (off, the default) -> None; True -> LIMIT_DEFAULTS; a
+    dict of ceiling / lookahead_ms / drive_db / iterations / tol -> the defaults with those replaced.  ceiling (dBTP;
+    None: the `loudness` keyword's peak, or -1 dBTP without one) is a finite number; lookahead_ms a finite number
+    > 0; drive_db a finite number >= 0 (how far above the single-gain rule's gain the pre-gain may go); iterations an
+    integer in [1, 16]; tol a finite number > 0 (LU).  Anything else -- False, an unknown key -- is refused by name."""
+    if spec is None:
+        return None
+    if spec is True:
+        opts = dict(LIMIT_DEFAULTS)
+    elif isinstance(spec, Mapping):
+        extra = sorted(set(spec) - set(LIMIT_DEFAULTS))
+        if extra:
+            raise ValueError(f"limit: unknown keys {extra} (a dict of {sorted(LIMIT_DEFAULTS)})")
+        opts = dict(LIMIT_DEFAULTS, **spec)
+    else:
+        raise ValueError(f"limit must be None, True or a dict of {sorted(LIMIT_DEFAULTS)} (got {spec!r})")
+    for key in ("ceiling", "lookahead_ms", "drive_db", "tol"):
+        v = opts[key]
+        if key == "ceiling" and v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"limit: {key} = {v!r} is not a finite number"
+                             + (" (or None: the loudness keyword's peak)" if key == "ceiling" else ""))
+        opts[key] = float(v)
+    if opts["lookahead_ms"] <= 0.0:
+        raise ValueError(f"limit: lookahead_ms = {opts['lookahead_ms']!r} is not positive")
+    if opts["drive_db"] < 0.0:
+        raise ValueError(f"limit: drive_db = {opts['drive_db']!r} is negative")
+    if opts["tol"] <= 0.0:
+        raise ValueError(f"limit: tol = {opts['tol']!r} is not positive")
+    k = opts["iterations"]
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 16:
+        raise ValueError(f"limit: iterations = {k!r} is not an integer in [1, 16]")
+    return opts
+
+
+def level_options(loudness, limit) -> Optional[dict]:
+    """The `loudness` and `limit` keywords of the entry points as the keywords of Engine.loudness_normalize: None when
+    both are off; loudness alone is loudness_options' three keys; with a limit its options ride along as "limit", and
+    limit alone is no loudness rule (target None): every item one curve against the limiter's ceiling."""
+    lopts, lim = loudness_options(loudness), limit_options(limit)
+    if lim is None:
+        return lopts
+    if lopts is None:
+        lopts = dict(target=None, peak=None, link="mixture")
+    return dict(lopts, limit=lim)
+
+
+def limiter_half_window(lookahead_ms, fs: int) -> int:
+    """W = max(1, floor(lookahead_ms fs / 1000 + 1/2)) (include/ditsep_hip.h); not yet checked against [1, 1024]"""
+    return max(1, int(math.floor(float(lookahead_ms) * int(fs) / 1000.0 + 0.5)))
+
+
+def limiter_window(W: int):
+    """The smoothing window of the limiter: w[k] = (1/2 + 1/2 cos(pi k / (W + 1))) / (W + 1), k = -W .. W, formed in
+    float64 and rounded once -> float32 [2 W + 1].  The exact sum is 1."""
+    import numpy as np
+
+    W = int(W)
+    if not 1 <= W <= LIMIT_MAX_HALF_WINDOW:
+        raise ValueError(f"limiter: the half-window W = {W} is outside [1, {LIMIT_MAX_HALF_WINDOW}]")
+    k = np.arange(-W, W + 1, dtype=np.float64)
+    return ((0.5 + 0.5 * np.cos(np.pi * k / (W + 1))) / (W + 1)).astype(np.float32)
+
+
+def check_limiter(shape, rates, group, pregain, ceiling=None, lookahead_ms=None, lens=None, channels=None) -> tuple:
+    """The refusals of dsn_limiter_curve and dsn_apply_curve (include/ditsep_hip.h), raised by name before the library
+    is touched: what check_loudness refuses of x [R, C, L], rates, lens and channels; group that is not one integer
+    per row; pregain that is not one finite number per group.  With a ceiling (the curve call; linear): group labels
+    that are not 0 .. G - 1 in non-decreasing order; rows of a group that disagree on length or rate; a ceiling that
+    is not finite and positive; a look-ahead that gives a half-window outside [1, 1024].  Without (apply_curve): a
+    label outside [0, G).  -> ((R, C, L), rates, lens or None, channels or None, group, pregain)"""
+    (R, Cn, L), rt, ln, ch = check_loudness(shape, rates, lens, channels)
+    try:
+        bad = any(isinstance(v, bool) or int(v) != v for v in group)
+        group = [int(v) for v in group]
+    except (TypeError, ValueError):
+        bad = True
+    if bad or len(group) != R:
+        raise ValueError(f"limiter: group must hold one integer label per row (R = {R})")
+    pregain = [float(v) for v in pregain]
+    G = len(pregain)
+    if G < 1:
+        raise ValueError("limiter: pregain must hold one number per group, at least one")
+    for q, v in enumerate(pregain):
+        if not math.isfinite(v):
+            raise ValueError(f"limiter: pregain[{q}] = {v!r} is not finite")
+    if ceiling is None:
+        for r, q in enumerate(group):
+            if not 0 <= q < G:
+                raise ValueError(f"limiter: group[{r}] = {q} outside [0, G = {G})")
+        return (R, Cn, L), rt, ln, ch, group, pregain
+    if isinstance(ceiling, bool) or not isinstance(ceiling, (int, float)) or not math.isfinite(ceiling) or ceiling <= 0:
+        raise ValueError(f"limiter: the ceiling {ceiling!r} is not a finite positive number (linear)")
+    if (isinstance(lookahead_ms, bool) or not isinstance(lookahead_ms, (int, float)) or not math.isfinite(lookahead_ms)
+            or lookahead_ms < 0):
+        raise ValueError(f"limiter: lookahead_ms = {lookahead_ms!r} is not a finite number >= 0")
+    if group[0] != 0 or group[-1] != G - 1 or any(b - a not in (0, 1) for a, b in zip(group, group[1:])):
+        raise ValueError(f"limiter: the group labels must be 0 .. G - 1 = {G - 1} in non-decreasing order")
+    for r in range(R):
+        W = limiter_half_window(lookahead_ms, rt[r])
+        if W > LIMIT_MAX_HALF_WINDOW:
+            raise ValueError(f"limiter: a look-ahead of {lookahead_ms} ms at {rt[r]} Hz is a half-window W = {W} outside "
+                             f"[1, {LIMIT_MAX_HALF_WINDOW}]")
+        if r and group[r] == group[r - 1]:
+            a, b = (L if ln is None else ln[r - 1]), (L if ln is None else ln[r])
+            if a != b or rt[r] != rt[r - 1]:
+                raise ValueError(f"limiter: rows {r - 1} and {r} of group {group[r]} disagree on length or rate "
+                                 f"({a} at {rt[r - 1]} Hz, {b} at {rt[r]} Hz)")
+    return (R, Cn, L), rt, ln, ch, group, pregain
+
+
+def limiter_drive(g_lo, i_src, target, history, drive_db=6.0, iterations=4, tol=0.1):
+    """The pre-gain rule of the `limit` keyword for one group (pure host arithmetic in float64).  g_lo is the gain
+    (dB) the single-gain rule native.loudness_gain gave when the ceiling set it, i_src the source's loudness, history
+    the evaluations so far as (G dB, measured loudness of the limited programme) pairs.  -> the next pre-gain in dB, or
+    None when the loop stops.  Every G is clamped to [g_lo, g_lo + drive_db].
+      G_0 = target - i_src;   G_1 = G_0 + (target - I_0);   then the secant step G_k + (target - I_k) / s with the
+      slope s = (I_k - I_{k-1}) / (G_k - G_{k-1}) clamped to [1/4, 1];
+      stop when |target - I_k| <= tol, after `iterations` evaluations, when I_k is not finite, or when the clamped G
+      is one that was evaluated already."""
+    lo, hi = float(g_lo), float(g_lo) + float(drive_db)
+    clamp = lambda v: min(max(v, lo), hi)
+    target = float(target)
+    if not history:
+        return clamp(target - float(i_src))
+    g_k, i_k = (float(v) for v in history[-1])
+    if not math.isfinite(i_k) or abs(target - i_k) <= tol or len(history) >= iterations:
+        return None
+    if len(history) == 1:
+        nxt = g_k + (target - i_k)
+    else:
+        g_p, i_p = (float(v) for v in history[-2])
+        slope = (i_k - i_p) / (g_k - g_p) if g_k != g_p and math.isfinite(i_p) else 1.0
+        nxt = g_k + (target - i_k) / min(max(slope, 0.25), 1.0)
+    nxt = clamp(nxt)
+    return None if any(nxt == float(g) for g, _ in history) else nxt
+
+
+def limiter_best(history, target) -> int:
+    """The evaluation of a limiter_drive history that is kept: the one closest to the target (the first of equals);
+    evaluations that are not finite lose to any that is."""
+    dist = [abs(float(target) - float(i)) if math.isfinite(float(i)) else math.inf for _, i in history]
+    return dist.index(min(dist))
+
+
 _lib = None
 
 
@@ -1005,6 +1158,9 @@ def load_library() -> C.CDLL:
     lib.dsn_kweight_coeffs.argtypes = [ci, f64p]
     lib.dsn_loudness.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, ci, f64p, vp]
     lib.dsn_apply_gain.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, fp, vp, vp]
+    lib.dsn_limiter_curve.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, i32p, ci, fp, cf, C.c_double, vp, vp, f64p,
+                                      vp]
+    lib.dsn_apply_curve.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, ci, fp, vp, vp, vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -2090,7 +2246,116 @@ class Engine:
                                             self._stream()), "dsn_apply_gain")
         return out
 
-    def loudness_normalize(self, sources, stems, rates, target=-23.0, peak=-1.0, link="mixture"):
+    def limiter_curve(self, x, rates, group, pregain, ceiling, lookahead_ms=5.0, lens=None, channels=None,
+                      envelope=False):
+        """The gain curve of the true-peak look-ahead limiter (dsn_limiter_curve, csrc/limiter.hip; the definition is
+        in include/ditsep_hip.h and tests/limiter_restatement.py): x [R, C, L] (or [C, L], [L]) with C <= 2, rates an
+        int or one rate per row, group one label per row (0 .. G - 1, non-decreasing; the rows of a group share one
+        curve, one length and one rate), pregain one linear gain per group (rounded to float32), ceiling linear,
+        lens / channels one count per row -> (curve [G, L] float32 on the device -- 1 at and past a group's length --,
+        {"min_gain": float64 [G] the smallest g (NaN with non-finite samples), "limited_samples": int64 [G] the
+        samples with g < 1, "nonfinite": int64 [G]}), and with envelope=True the envelope p [G, L] as a third entry
+        (zero where it is not written)."""
+        (R, Cn, L), rt, ln, ch, grp, pg = check_limiter(tuple(x.shape), rates, group, pregain, ceiling, lookahead_ms,
+                                                        lens, channels)
+        x = _dev32(x, self.device).reshape(R, Cn, L)
+        G = len(pg)
+        curve = torch.empty((G, L), device=x.device, dtype=torch.float32)
+        env = torch.zeros((G, L), device=x.device, dtype=torch.float32) if envelope else None
+        stats = torch.zeros((G, 3), dtype=torch.float64)
+        i32 = C.c_int32 * R
+        self._check(self.lib.dsn_limiter_curve(self.ctx, _ptr(x), R, Cn, L, None if ln is None else i32(*ln),
+                                               None if ch is None else i32(*ch), i32(*rt), i32(*grp), G,
+                                               (C.c_float * G)(*pg), float(ceiling), float(lookahead_ms), _ptr(curve),
+                                               _ptr(env),
+                                               C.cast(C.c_void_p(stats.data_ptr()), C.POINTER(C.c_double)),
+                                               self._stream()), "dsn_limiter_curve")
+        info = {"min_gain": stats[:, 0].clone(), "limited_samples": stats[:, 1].long(), "nonfinite": stats[:, 2].long()}
+        return (curve, info, env) if envelope else (curve, info)
+
+    def apply_curve(self, x, group, pregain, curve, lens=None, channels=None, out=None):
+        """out = (pregain[group[r]] x) curve[group[r]], two float32 products per sample (dsn_apply_curve): x [R, C, L]
+        (or [C, L], [L]) with C <= 2, group one label in [0, G) per row in any order, pregain [G], curve [G, L] float32
+        on the device (Engine.limiter_curve's) -- zero at or past lens[r] and in the channels a row does not have, where
+        nothing is read.  The rows need not be the ones the curve was formed from.  out=x works in place."""
+        (R, Cn, L), _, ln, ch, grp, pg = check_limiter(tuple(x.shape), LOUDNESS_RATES[0], group, pregain, None, None,
+                                                       lens, channels)
+        G = len(pg)
+        x = _dev32(x, self.device)
+        if (not torch.is_tensor(curve) or tuple(curve.shape) != (G, L) or curve.dtype != torch.float32
+                or curve.device != x.device or not curve.is_contiguous()):
+            raise ValueError(f"apply_curve: curve must be a contiguous float32 tensor [G = {G}, L = {L}] on the device")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+            raise ValueError("apply_curve: out must be a contiguous float32 tensor of x's shape on the device")
+        i32 = C.c_int32 * R
+        self._check(self.lib.dsn_apply_curve(self.ctx, _ptr(x), R, Cn, L, None if ln is None else i32(*ln),
+                                             None if ch is None else i32(*ch), i32(*grp), G, (C.c_float * G)(*pg),
+                                             _ptr(curve), _ptr(out), self._stream()), "dsn_apply_curve")
+        return out
+
+    def _limit_groups(self, xs, rt, ln, ch, grp, prog, g_lo, i_src, target, ceiling, lim):
+        """The `limit` keyword's loop for the groups the ceiling held back: xs [R, C, L] the rows before any gain, grp
+        their labels 0 .. Q - 1, prog None (a group is one row and its own programme) or (mx [Q, C', L], channels):
+        one mixture per group, measured in place of the rows.  g_lo, i_src per group; target None: one evaluation at
+        0 dB and no measurement.  -> (the limited rows, per group: gain_db, loudness, evaluations, min_gain,
+        limited_samples, trim (linear); per row: the true peak after the trim)"""
+        import numpy as np
+
+        Q = len(g_lo)
+        lin = lambda d: float(np.float32(10.0 ** (d / 20.0)))
+        first = [b for b in range(len(grp)) if b == 0 or grp[b] != grp[b - 1]]   # a row of every group
+        q_rt, q_ln = [rt[r] for r in first], [ln[r] for r in first]
+        hist = [[] for _ in range(Q)]
+        kw = dict(drive_db=lim["drive_db"], iterations=lim["iterations"], tol=lim["tol"])
+        cur = [0.0 if target is None else limiter_drive(g_lo[q], i_src[q], target, [], **kw) for q in range(Q)]
+        active = [] if target is None else list(range(Q))
+        while active:
+            pg = [lin(v) for v in cur]
+            curve, _ = self.limiter_curve(xs, rt, grp, pg, ceiling, lim["lookahead_ms"], ln, ch)
+            if prog is None:
+                I = self.loudness(self.apply_curve(xs, grp, pg, curve, ln, ch), rt, ln, ch, true_peak=False)
+            else:
+                I = self.loudness(self.apply_curve(prog[0], list(range(Q)), pg, curve, q_ln, prog[1]), q_rt, q_ln,
+                                  prog[1], true_peak=False)
+            I = I["loudness"].tolist()
+            still = []
+            for q in active:
+                hist[q].append((cur[q], I[q]))
+                nxt = limiter_drive(g_lo[q], i_src[q], target, hist[q], **kw)
+                if nxt is not None:
+                    cur[q] = nxt
+                    still.append(q)
+            active = still
+        loud = [math.nan] * Q
+        for q in range(Q):
+            if hist[q]:
+                cur[q], loud[q] = hist[q][limiter_best(hist[q], target)]
+        pg = [lin(v) for v in cur]
+        curve, st = self.limiter_curve(xs, rt, grp, pg, ceiling, lim["lookahead_ms"], ln, ch)
+        y = self.apply_curve(xs, grp, pg, curve, ln, ch)
+        m = self.loudness(y, rt, ln, ch)
+        if target is None:
+            loud = [m["loudness"][r].item() for r in first]   # (a group's first row; with link "stem" its only one)
+        # the trim: interpolating g y is not g times the interpolation, so the ceiling is measured, not assumed
+        trim, out, tp = [1.0] * Q, y, m["true_peak"].tolist()
+        for _ in range(3):
+            top = [max(tp[r] for r in range(len(grp)) if grp[r] == q) for q in range(Q)]
+            over = [q for q in range(Q) if top[q] > ceiling]
+            if not over:
+                break
+            for q in over:
+                trim[q] = float(np.float32(trim[q] * (ceiling / top[q])))
+            out = self.apply_gain(y, [trim[q] for q in grp], ln, ch)
+            tp = self.loudness(out, rt, ln, ch)["true_peak"].tolist()
+        res = {"gain_db": [cur[q] + 20.0 * math.log10(trim[q]) for q in range(Q)],
+               "loudness": [loud[q] + 20.0 * math.log10(trim[q]) for q in range(Q)],
+               "evaluations": [max(len(h), 1) for h in hist], "min_gain": st["min_gain"].tolist(),
+               "limited_samples": st["limited_samples"].tolist(), "trim": trim, "true_peak": tp}
+        return out, res
+
+    def loudness_normalize(self, sources, stems, rates, target=-23.0, peak=-1.0, link="mixture", limit=None):
         """The `loudness` keyword's last step for a list of items: `stems` is one [n, L_b] or [n, C_b, L_b] tensor per
         item at rates[b], `sources` the items' mixtures [C'_b, L'_b] (or [L'_b]) at the same rates.  link "mixture":
         every item's gain source is its mixture and its n stems share one gain; link "stem": every stem is its own
@@ -2099,9 +2364,23 @@ class Engine:
         info = {"loudness_in", "loudness_out", "gain_db", "true_peak_db": one list of n floats per item (the source's
         loudness, that plus the gain, the gain, the stem's true peak after the gain in dBTP), "limited": likewise,
         booleans, "silent" / "nonfinite": the (item, stem) pairs left at 0 dB because their source passed no block /
-        held non-finite samples}."""
+        held non-finite samples}.
+        limit (default None: the calls and bits above): True or a dict (native.limit_options) -- the groups whose gain
+        the ceiling set ("limited") go through the true-peak look-ahead limiter instead (Engine.limiter_curve /
+        apply_curve): the pre-gain starts at target - I_src, clamped to [g, g + drive_db] with g the single gain, each
+        evaluation is curve -> apply -> Engine.loudness of the limited programme (the limited mixture with link
+        "mixture", zero-extended or cut to the stems' length; the limited stem with link "stem"), native.limiter_drive gives the
+        next pre-gain, the evaluation closest to the target is kept, and the group is trimmed by ceiling / TP where the
+        measured true peak of a limited stem still exceeds the ceiling.  Other groups are untouched.  target=None
+        with a limit: no loudness rule, every group one evaluation at 0 dB against the ceiling.  info gains, one list of
+        n per item: "reached" (|target - loudness_out| <= tol; true where the single gain sufficed), "evaluations",
+        "reduction_db" (20 log10 of the smallest g) and "limited_samples"; "loudness_out" and "true_peak_db" of a
+        limited group are measured figures."""
         if link not in LOUDNESS_LINKS:
             raise ValueError(f"loudness: link must be one of {LOUDNESS_LINKS} (got {link!r})")
+        lim = limit_options(limit)
+        if target is None and lim is None:
+            raise ValueError("loudness: target=None (no loudness rule) needs limit=")
         B = len(stems)
         rates = [int(rates)] * B if isinstance(rates, int) else [int(r) for r in rates]
         rows3 = [s[:, None] if s.dim() == 2 else s for s in stems]
@@ -2116,28 +2395,84 @@ class Engine:
             x[b * n:(b + 1) * n, :ch[b], :ln[b]] = _dev32(s, self.device)
         rep = lambda v: [a for a in v for _ in range(n)]
         rows = self.loudness(x, rep(rates), rep(ln), rep(ch))
-        if link == "mixture":
+        src = sc = sl = None
+        if link == "mixture" and (target is not None or sources is not None):
             if sources is None or len(sources) != B:
                 raise ValueError("loudness: link 'mixture' needs one mixture per item")
             src = [m.reshape(-1, m.shape[-1]) for m in sources]
             sc, sl = [int(m.shape[0]) for m in src], [int(m.shape[1]) for m in src]
-            mx = torch.zeros((B, max(sc), max(sl)), device=self.device, dtype=torch.float32)
-            for b, m in enumerate(src):
-                mx[b, :sc[b], :sl[b]] = _dev32(m, self.device)
-            I_src = rep(self.loudness(mx, rates, sl, sc, true_peak=False)["loudness"].tolist())
-            groups = rep(list(range(B)))
+        if target is None:
+            tp = rows["true_peak"].tolist()
+            groups = rep(list(range(B))) if link == "mixture" else list(range(B * n))
+            nonf = sorted(r for r in range(B * n) if any(math.isnan(tp[k]) for k in range(B * n) if groups[k] == groups[r]))
+            I_src = rows["loudness"].tolist()
+            g = {"gain_db": [0.0] * (B * n), "gain": [1.0] * (B * n), "limited": [r not in nonf for r in range(B * n)],
+                 "silent": [], "nonfinite": nonf}
         else:
-            I_src, groups = rows["loudness"].tolist(), None
-        g = loudness_gain(I_src, rows["true_peak"].tolist(), groups, target, peak)
-        self.apply_gain(x, g["gain"], rep(ln), rep(ch), out=x)
-        outs = [x[b * n:(b + 1) * n, :ch[b], :ln[b]].reshape(stems[b].shape) for b in range(B)]
+            if link == "mixture":
+                mx = torch.zeros((B, max(sc), max(sl)), device=self.device, dtype=torch.float32)
+                for b, m in enumerate(src):
+                    mx[b, :sc[b], :sl[b]] = _dev32(m, self.device)
+                I_src = rep(self.loudness(mx, rates, sl, sc, true_peak=False)["loudness"].tolist())
+                groups = rep(list(range(B)))
+            else:
+                I_src, groups = rows["loudness"].tolist(), None
+            g = loudness_gain(I_src, rows["true_peak"].tolist(), groups, target, peak)
+        sel = [r for r in range(B * n) if g["limited"][r]] if lim is not None else []
+        held = x[sel].clone() if sel else None   # the rows of the limited groups before any gain
+        if target is not None:
+            self.apply_gain(x, g["gain"], rep(ln), rep(ch), out=x)
         tp = rows["true_peak"].tolist()
         tp_db = [20.0 * math.log10(v) + d if v > 0.0 else (-math.inf if v == 0.0 else math.nan)
                  for v, d in zip(tp, g["gain_db"])]
+        gain_db = list(g["gain_db"])
+        loud_out = [a + d for a, d in zip(I_src, gain_db)]
+        extra = {}
+        if lim is not None:
+            R = B * n
+            ok = [r not in g["silent"] and r not in g["nonfinite"] for r in range(R)]
+            extra = {"reached": ok, "evaluations": [0] * R, "reduction_db": [0.0] * R, "limited_samples": [0] * R}
+        if sel:
+            c_db = lim["ceiling"] if lim["ceiling"] is not None else (peak if peak is not None else LIMIT_DEFAULT_CEILING)
+            import numpy as np
+
+            ceiling = float(np.float32(10.0 ** (float(c_db) / 20.0)))
+            labels = groups if groups is not None else list(range(B * n))
+            order = []
+            for r in sel:
+                if labels[r] not in order:
+                    order.append(labels[r])
+            grp = [order.index(labels[r]) for r in sel]
+            first = [sel[grp.index(q)] for q in range(len(order))]
+            prog = None
+            if link == "mixture" and target is not None:
+                items = [r // n for r in first]
+                pm = torch.zeros((len(items), max(sc[b] for b in items), int(x.shape[-1])), device=self.device,
+                                 dtype=torch.float32)
+                for q, b in enumerate(items):   # (zero-extended or cut to the stems' length: one curve for both)
+                    v = min(sl[b], ln[b])
+                    pm[q, :sc[b], :v] = _dev32(src[b], self.device)[:, :v]
+                prog = (pm, [sc[b] for b in items])
+            out, res = self._limit_groups(held, [rep(rates)[r] for r in sel], [rep(ln)[r] for r in sel],
+                                          [rep(ch)[r] for r in sel], grp, prog, [g["gain_db"][r] for r in first],
+                                          [I_src[r] for r in first], target, ceiling, lim)
+            x[sel] = out
+            for k, r in enumerate(sel):
+                q = grp[k]
+                gain_db[r], loud_out[r] = res["gain_db"][q], res["loudness"][q]
+                v = res["true_peak"][k]
+                tp_db[r] = 20.0 * math.log10(v) if v > 0.0 else (-math.inf if v == 0.0 else math.nan)
+                low = res["min_gain"][q]
+                extra["reached"][r] = True if target is None else bool(abs(target - loud_out[r]) <= lim["tol"])
+                extra["evaluations"][r] = res["evaluations"][q]
+                extra["reduction_db"][r] = 20.0 * math.log10(low) if low > 0.0 else (-math.inf if low == 0.0 else math.nan)
+                extra["limited_samples"][r] = int(res["limited_samples"][q])
+        outs = [x[b * n:(b + 1) * n, :ch[b], :ln[b]].reshape(stems[b].shape) for b in range(B)]
         per = lambda v: [list(v[b * n:(b + 1) * n]) for b in range(B)]
-        info = {"loudness_in": per(I_src), "loudness_out": per([a + d for a, d in zip(I_src, g["gain_db"])]),
-                "gain_db": per(g["gain_db"]), "true_peak_db": per(tp_db), "limited": per(g["limited"]),
+        info = {"loudness_in": per(I_src), "loudness_out": per(loud_out),
+                "gain_db": per(gain_db), "true_peak_db": per(tp_db), "limited": per(g["limited"]),
                 "silent": [divmod(r, n) for r in g["silent"]], "nonfinite": [divmod(r, n) for r in g["nonfinite"]]}
+        info.update({k: per(v) for k, v in extra.items()})
         return outs, info
 
     @property

@@ -95,6 +95,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loudness-link", default="mixture", choices=["mixture", "stem"],
                    help="With --loudness: measure the input file and give all its stems one gain (mixture), or bring "
                         "every stem to the target by itself (stem)")
+    p.add_argument("--limit", action="store_true",
+                   help="True-peak look-ahead limiter as the last step: where the ceiling forbids the --loudness target "
+                        "to a single gain, only the neighbourhood of the peaks is lowered so that the rest can reach it; "
+                        "without --loudness, every file once against a ceiling of -1 dBTP (off by default)")
+    p.add_argument("--limit-lookahead", type=float, default=5.0, metavar="MS",
+                   help="With --limit: the look-ahead (and hold) time in milliseconds")
+    p.add_argument("--limit-drive", type=float, default=6.0, metavar="DB",
+                   help="With --limit: how far above the single gain the pre-gain may go")
+    p.add_argument("--limit-iterations", type=int, default=4, metavar="K",
+                   help="With --limit: at most this many evaluations of the limited programme's loudness")
     return p
 
 
@@ -141,6 +151,13 @@ def loudness_of(args):
     return dict(target=args.loudness, peak=args.true_peak, link=args.loudness_link)
 
 
+def limit_of(args):
+    """The `limit` keyword of separate_files from the parsed flags: None unless --limit is given."""
+    if not args.limit:
+        return None
+    return dict(lookahead_ms=args.limit_lookahead, drive_db=args.limit_drive, iterations=args.limit_iterations)
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     try:
@@ -170,8 +187,8 @@ def main(argv=None) -> int:
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
-                                           stems=stems_of(args), loudness=loudness_of(args), denoise=args.denoise,
-                                           **kw)
+                                           stems=stems_of(args), loudness=loudness_of(args), limit=limit_of(args),
+                                           denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
@@ -179,7 +196,9 @@ def main(argv=None) -> int:
             clipped = sum(r["clipped"])
             print(f"{r['path']}: {r['frames']} frames at {r['rate']} Hz, {r['channels']} ch -> {len(r['outputs'])} files"
                   + (f", {clipped} samples clipped" if clipped else "")
-                  + (f", gain {', '.join(f'{g:+.2f}' for g in r['gain_db'])} dB" if "gain_db" in r else ""))
+                  + (f", gain {', '.join(f'{g:+.2f}' for g in r['gain_db'])} dB" if "gain_db" in r else "")
+                  + (f", limiter down to {min(r['reduction_db']):+.2f} dB"
+                     + ("" if all(r["reached"]) else ", target not reached") if "reduction_db" in r else ""))
         return 0
     finally:
         model.close()

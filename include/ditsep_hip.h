@@ -780,6 +780,56 @@ int dsn_loudness(dsn_ctx* ctx, const float* x, int B, int C, int Lmax, const int
 int dsn_apply_gain(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
                    const float* gain, float* out, void* stream);
 
+/* True-peak look-ahead limiter: a time-varying gain that lowers only the neighbourhood of the peaks, so that the rest of
+ * a programme can rise to a loudness target its true-peak ceiling would otherwise forbid (csrc/limiter.hip, restated in
+ * float64 in tests/limiter_restatement.py).  Nothing calls it unless asked to.  x [R][C][Lmax] fp32 (device), C <= 2;
+ * row r has channels[r] <= C channels, lens[r] samples and the rate rates[r] in [8000, 192000] Hz.  A group is the set
+ * of rows that share one gain curve: group [R] holds 0 .. G - 1 in non-decreasing order, and the rows of a group share
+ * one length and one rate.  All arithmetic is fp32 without contraction, except where an fma is written.  For group q
+ * with the pre-gain G_q = pregain[q], the ceiling c (linear) and the half-window
+ * W = max(1, floor(lookahead_ms fs / 1000 + 1/2)), 1 <= W <= 1024:
+ *   1 pre-gain   y = G_q x, one product per sample (the bits of dsn_apply_gain).
+ *   2 envelope   p[t] = max over the group's rows and channels of max(|y[t]|, |u[4 t]|, .., |u[4 t + 3]|), u the row
+ *                interpolated 1 -> 4 as dsn_loudness forms its true peak (dsn_resample_plan(1, 4): one product and
+ *                support - 1 fmas in tap order, zero beyond the item's own ends).  A non-finite y is counted and makes
+ *                the group's whole curve NaN.
+ *   3 required   r[t] = min(1, c / p[t]) by a correctly rounded division, 1 where p = 0; and where the fp32 product
+ *                r[t] p[t] rounds above c (the quotient was rounded up), r[t] is the next float below.  With that step
+ *                fl(g[t] p[t]) <= c holds for every sample whatever the rounding does, since g <= r below.
+ *   4 hold       m[t] = min over |s - t| <= W of r[s], with r = 1 outside [0, len).
+ *   5 smoothing  g[t] = max(0, min(r[t], 1 - a[t])), a[t] = sum_{k = -W .. W} w[k] (1 - m[t + k]) accumulated from 0 by
+ *                fma in increasing k, w[k] = (1/2 + 1/2 cos(pi k / (W + 1))) / (W + 1) formed on the host in fp64 and
+ *                rounded once (the exact sum is 1).  It is written on the deficit 1 - m: where no sample within 2 W needs
+ *                reducing every term is +0, g is exactly 1.0f and out is y bit for bit -- and a tile or a sample that
+ *                skips the sum there has the bits of the sum.
+ *   6 output     out = y g[t] = (G_q x) g[t], two products, for every row of the group.
+ * Two launches over tiles of 2048 samples counted from the group's own start: the envelope (every row of the group
+ * through LDS with the interpolator's halo, 16-byte loads where a quad is aligned and whole) writes r to a workspace in
+ * the context; the second stages r over the tile and 2 W on either side, forms the hold by doubling minima (a minimum
+ * does not depend on its order), then a and g.  No floating-point atomics: a group's curve has the same bits alone, at
+ * any batch position, under any padding, from a base pointer of any 4-byte alignment and in a second call.  Symmetric
+ * (zero-phase, release = attack), offline; no soft knee, no clipper.  The true peak of out as dsn_loudness measures it
+ * is NOT bounded by c by theorem (interpolating g y is not g times the interpolation): a caller that promises a ceiling
+ * measures again and trims (ditsep_amd.native.Engine.loudness_normalize does).
+ *   dsn_limiter_curve  curve [G][Lmax] fp32 (device): g over [0, len), 1.0f at and past len.  envelope: NULL, or
+ *                      [G][Lmax] fp32 (device) that receives p over [0, len) (not written elsewhere).  stats_host
+ *                      [G][3] doubles (HOST): the smallest g (NaN with non-finite samples), the number of samples with
+ *                      g < 1, the count of non-finite samples.  lens, channels, rates, group and pregain are HOST arrays;
+ *                      lens and channels may be NULL.  Uploads its tables and synchronises the stream: not for capture.
+ *   dsn_apply_curve    x [R][C][Lmax] -> out [R][C][Lmax]: out = (pregain[group[r]] x) curve[group[r]][t]; zero at or
+ *                      past lens[r] and in the channels past channels[r], where nothing is read.  Any rows: group[r] in
+ *                      [0, G) in any order, so the curve of the stems can be applied to their mixture.  curve is
+ *                      [G][Lmax] with this call's Lmax.  out may be x itself (any other overlap is refused).
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_loudness refuses; a null group, pregain or
+ * curve; G < 1 or (curve) > R; a group label outside [0, G) or (curve) out of order; rows of a group that disagree on
+ * length or rate; W outside [1, 1024] or a look-ahead that is negative or not finite; a ceiling that is not finite and
+ * positive; a pre-gain that is not finite. */
+int dsn_limiter_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                      const int32_t* rates, const int32_t* group, int G, const float* pregain, float ceiling,
+                      double lookahead_ms, float* curve, float* envelope, double* stats_host, void* stream);
+int dsn_apply_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                    const int32_t* group, int G, const float* pregain, const float* curve, float* out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
