@@ -1,0 +1,555 @@
+// Mask-based MVDR beamforming (dsn_beamform; the definition is in include/ditsep_hip.h, restated in float64 in
+// tests/beamform_restatement.py): the masks of the mono estimates give one spatial covariance per source and bin from
+// the mixture's own channels, and a minimum-variance distortionless-response filter (Souden, Benesty, Affes 2010)
+// returns one mono signal per source.  Frames, spectra and masks are formed by the code of maskrefine.hip
+// (maskrefine_dev.h), so they have the bits they have there.  Three launches per chunk of items, then one for the batch:
+//   stats    workgroup (o, b, i) owns the frames [o fpo, (o + 1) fpo) of item b for source i -- every frame has exactly
+//            one owner per source; fpo is a whole number of spans, more than one where the item has more than
+//            BEAMFORM_MAX_OWNERS spans --, transforms the item's C_b channels and n estimates in groups of
+//            2048 / n_fft frames and, per bin, sums M_i X X^H (upper triangle, fp64 products) in frame order: the
+//            thread that owns a bin below 256 keeps the sums of all the owner's frames in registers and stores them
+//            once; bins 256 and up are summed over a group in registers and then added to the owner's partial in
+//            global memory with plain loads and stores.
+//   reduce   one thread per (item, source, entry, bin) adds the item's partials in owner order.
+//   weights  eight lanes per (item, source, bin): every lane forms A = Q_i + lambda I and its Cholesky factor itself
+//            (channels the item does not have are an identity block, which leaves the other entries' arithmetic as it
+//            is) and solves column `lane` of Z = A^-1 N_i; the diagonal of Z goes through LDS, tau is added in channel
+//            order by the lane of the reference channel, which writes w = Z[:, ref] / tau.
+//   apply    workgroup (span, item, source), the mask kernel's layout: transforms the C_b channels (and the n
+//            estimates only where the post-filter needs the masks), contracts the channels with w in fp64 in channel
+//            order, rounds once, writes Y_i over channel 0's slot, inverse-transforms that slot and overlap-adds.
+// No atomics; nothing depends on the batch position, the padding or the chunking, so an item has the same bits alone.
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+#include "maskrefine_dev.h"
+
+constexpr int BF_MAX_CH = BEAMFORM_MAX_CH;
+constexpr int BF_TRI = BF_MAX_CH * (BF_MAX_CH + 1) / 2;                          // Hermitian entries held in registers
+constexpr int BF_BF = (BF_MAX_CH + MR_MAX_SRC) * (MR_POINTS / 2) / MRT;          // butterflies per thread and stage
+// output samples a workgroup of the apply launch owns, and the frames of one owner's span: maskrefine.hip's spans
+template <int NFFT>
+constexpr int bf_span() { return NFFT >= 2048 ? 4096 : 2048; }
+constexpr int BF_LANES = 8, BF_GROUPS = MRT / BF_LANES;                          // weights launch: lanes per system
+
+__host__ __device__ inline int bf_tri(int C) { return C * (C + 1) / 2; }
+// entry (c1 <= c2) of the upper triangle of a C x C matrix, row after row
+__host__ __device__ inline int bf_idx(int C, int c1, int c2) { return c1 * C - c1 * (c1 - 1) / 2 + (c2 - c1); }
+
+// frames one owner takes of an item of F frames: whole spans of `base` frames, as few as keep the owners within the cap
+__host__ __device__ inline int bf_owner_frames(int F, int base) {
+  const int spans = (F + base - 1) / base;
+  return base * ((spans + BEAMFORM_MAX_OWNERS - 1) / BEAMFORM_MAX_OWNERS);
+}
+
+// The load of maskrefine.hip: slot fg of signal s holds frame f0 + fg, even samples in .x and odd in .y, windowed;
+// signals 0 .. nx - 1 are the mixture's channels, then ne estimates.
+template <int H>
+__device__ __forceinline__ void bf_load(float2* buf, const float* win, const float* mixb, const float* estb, int Lmax,
+                                        int L, int Lp, int hop, int nx, int ne, int f0, int f_last, int tid) {
+  constexpr int LOGH = __builtin_ctz(H), G = MR_POINTS / H;
+  for (int e = tid; e < G * H; e += MRT) {
+    const int fg = e >> LOGH, tp = e & (H - 1), f = f0 + fg;
+    const bool valid = f <= f_last;
+    int i0 = f * hop - H + 2 * tp, i1 = i0 + 1;   // (f hop <= Lp: no overflow)
+    i0 = i0 < 0 ? -i0 : i0;
+    i1 = i1 < 0 ? -i1 : i1;
+    i0 = i0 >= Lp ? 2 * (Lp - 1) - i0 : i0;   // Lp > H: one reflection reaches [0, Lp)
+    i1 = i1 >= Lp ? 2 * (Lp - 1) - i1 : i1;
+    const float w0 = win[2 * tp], w1 = win[2 * tp + 1];
+    for (int s = 0; s < nx + ne; ++s) {
+      const float* row = s < nx ? mixb + (long)s * Lmax : estb + (long)(s - nx) * Lmax;
+      const float v0 = valid && i0 < L ? row[i0] : 0.f;
+      const float v1 = valid && i1 < L ? row[i1] : 0.f;
+      buf[(s * G + fg) * H + tp] = make_float2(v0 * w0, v1 * w1);
+    }
+  }
+}
+
+template <int H>
+__device__ __forceinline__ void bf_tables(float2* tw, float* win, int tid) {
+  for (int t = tid; t < H; t += MRT) {
+    double s, c;
+    sincospi((double)t / H, &s, &c);   // exp(-2 pi i t / NFFT)
+    tw[t] = make_float2((float)c, (float)-s);
+  }
+  for (int t = tid; t < 2 * H; t += MRT) win[t] = (float)(0.5 - 0.5 * cospi((double)t / H));   // periodic Hann
+}
+
+// Source `src`, bin j: rows [R0, R1) of M_src X X^H (upper triangle, X_c1 conj X_c2) of the `frames` frames in LDS,
+// added to acc in frame order.  Products and sums in fp64 on the widened fp32 spectra and masks.
+template <int H, int R0, int R1>
+__device__ __forceinline__ void bf_accumulate(const MaskRefineShape& q, const float2* buf, const float2* tw, int Cb,
+                                              int src, int j, int frames, double (&acc)[BF_TRI][2]) {
+  const bool lower = 2 * j <= H;
+  const int k = lower ? j : H - j, km = (H - k) & (H - 1);
+  const float2 t = tw[k];
+  for (int fg = 0; fg < frames; ++fg) {
+    double xr[BF_MAX_CH], xi[BF_MAX_CH];
+#pragma unroll
+    for (int c = 0; c < BF_MAX_CH; ++c) {
+      xr[c] = xi[c] = 0.0;
+      if (c < Cb) {
+        const float2* a = buf + c * MR_POINTS + fg * H;
+        float2 xk, xm;
+        mr_split(a[k], a[km], t, xk, xm);
+        xr[c] = lower ? xk.x : xm.x;
+        xi[c] = lower ? xk.y : xm.y;
+      }
+    }
+    float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
+    mr_masks(q, buf + Cb * MR_POINTS + fg * H, k, km, t, mk, mm);
+    float mi = 0.f;
+#pragma unroll
+    for (int s = 0; s < MR_MAX_SRC; ++s)
+      if (s == src) mi = lower ? mk[s] : mm[s];
+    const double m = mi;
+#pragma unroll
+    for (int c1 = R0; c1 < R1; ++c1)
+#pragma unroll
+      for (int c2 = c1; c2 < BF_MAX_CH; ++c2)
+        if (c2 < Cb) {
+          const int u = c1 * BF_MAX_CH - c1 * (c1 - 1) / 2 + (c2 - c1);
+          acc[u][0] += m * (xr[c1] * xr[c2] + xi[c1] * xi[c2]);
+          acc[u][1] += m * (xi[c1] * xr[c2] - xr[c1] * xi[c2]);
+        }
+  }
+}
+
+// Bin j >= 256 of one frame group: rows [R0, R1) summed over the group in registers, then added to the owner's partial.
+template <int H, int R0, int R1>
+__device__ __forceinline__ void bf_high_bin(const MaskRefineShape& q, const float2* buf, const float2* tw, int Cb,
+                                            int src, int j, int frames, bool first, double* __restrict__ partw) {
+  double acc[BF_TRI][2];
+#pragma unroll
+  for (int u = 0; u < BF_TRI; ++u) acc[u][0] = acc[u][1] = 0.0;
+  bf_accumulate<H, R0, R1>(q, buf, tw, Cb, src, j, frames, acc);
+#pragma unroll
+  for (int c1 = R0; c1 < R1; ++c1)
+#pragma unroll
+    for (int c2 = c1; c2 < BF_MAX_CH; ++c2)
+      if (c2 < Cb) {
+        const int u = c1 * BF_MAX_CH - c1 * (c1 - 1) / 2 + (c2 - c1);
+        double* d = partw + 2L * bf_idx(q.C, c1, c2) * (H + 1) + j;
+        d[0] = first ? acc[u][0] : d[0] + acc[u][0];
+        d[H + 1] = first ? acc[u][1] : d[H + 1] + acc[u][1];
+      }
+}
+
+// grid (owners, items, n).  part [items][gridDim.x][n][2 tri(C)][H + 1].
+// Dynamic LDS: float2 tw[H] | float2 buf[C + n][G][H] | float win[NFFT]
+// A thread owns bin `tid` for the whole launch and keeps that bin's sums of its one source in registers over all the
+// owner's frames (36 complex doubles at C = 8: one source is what the registers hold, so the source is in the grid and
+// the transforms are formed once per source); they are stored once at the end.  Bins 256 and up (n_fft >= 512) are
+// added a frame group at a time into the partial in global memory, by the same thread every group.
+template <int NFFT>
+__global__ __launch_bounds__(MRT) void beamform_stats_kernel(const MaskRefineShape q, const float* __restrict__ mix,
+                                                             const float* __restrict__ est,
+                                                             const int* __restrict__ lens, const int* __restrict__ chans,
+                                                             double* __restrict__ part) {
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = bf_span<NFFT>();
+  extern __shared__ __attribute__((aligned(16))) float2 bf_lds[];
+  const int n = q.n, hop = q.hop, tid = threadIdx.x, b = blockIdx.y, src = blockIdx.z;
+  const int Cb = chans ? chans[b] : q.C;
+  const int L = lens ? lens[b] : q.Lmax;
+  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const int fpo = bf_owner_frames(F, SPAN / hop);
+  if ((long)blockIdx.x * fpo >= F) return;   // (uniform)
+  float2* tw = bf_lds;
+  float2* buf = tw + H;
+  float* win = reinterpret_cast<float*>(buf + (q.C + n) * MR_POINTS);
+  const float* mixb = mix + (long)b * q.C * q.Lmax;
+  const float* estb = est + (long)b * n * q.Lmax;
+  bf_tables<H>(tw, win, tid);
+  const int f_first = blockIdx.x * fpo, f_last = min(F, f_first + fpo) - 1;
+  const int T2 = 2 * bf_tri(q.C);
+  double* partw = part + (((long)b * gridDim.x + blockIdx.x) * n + src) * T2 * (H + 1);
+  double own[BF_TRI][2];
+#pragma unroll
+  for (int u = 0; u < BF_TRI; ++u) own[u][0] = own[u][1] = 0.0;
+
+  for (int f0 = f_first; f0 <= f_last; f0 += G) {
+    __syncthreads();   // the tables are in; the previous group's spectra have been read
+    bf_load<H>(buf, win, mixb, estb, q.Lmax, L, Lp, hop, Cb, n, f0, f_last, tid);
+    __syncthreads();
+    mr_fft<H, false, BF_BF>(buf, tw, (Cb + n) * (MR_POINTS / 2), tid);
+    const int frames = min(G, f_last - f0 + 1);
+    if (tid <= H) bf_accumulate<H, 0, BF_MAX_CH>(q, buf, tw, Cb, src, tid, frames, own);
+    if (H + 1 > MRT)
+      for (int j = tid + MRT; j <= H; j += MRT) {   // (in two halves of the triangle: `own` stays in registers)
+        bf_high_bin<H, 0, 3>(q, buf, tw, Cb, src, j, frames, f0 == f_first, partw);
+        bf_high_bin<H, 3, BF_MAX_CH>(q, buf, tw, Cb, src, j, frames, f0 == f_first, partw);
+      }
+  }
+  if (tid <= H) {
+    int u = 0;
+#pragma unroll
+    for (int c1 = 0; c1 < BF_MAX_CH; ++c1)
+#pragma unroll
+      for (int c2 = c1; c2 < BF_MAX_CH; ++c2, ++u)
+        if (c2 < Cb) {
+          double* d = partw + 2L * bf_idx(q.C, c1, c2) * (H + 1) + tid;
+          d[0] = own[u][0];
+          d[H + 1] = own[u][1];
+        }
+  }
+}
+
+// N [items][n][2 tri(C)][bins] from part [items][OW][n][2 tri(C)][bins]: the item's own owners, in owner order.  Entries
+// of channels the item does not have are written as zero.
+__global__ __launch_bounds__(MRT) void beamform_reduce_kernel(const double* __restrict__ part,
+                                                              const int* __restrict__ lens,
+                                                              const int* __restrict__ chans, int items, int n, int C,
+                                                              int Lmax, int bins, int hop, int base, int OW,
+                                                              double* __restrict__ N) {
+  const int T2 = 2 * bf_tri(C);
+  const long e = (long)blockIdx.x * MRT + threadIdx.x;
+  if (e >= (long)items * n * T2 * bins) return;
+  const int j = (int)(e % bins), u = (int)(e / bins % T2), i = (int)(e / bins / T2 % n);
+  const int b = (int)(e / bins / T2 / n);
+  const int L = lens ? lens[b] : Lmax, Cb = chans ? chans[b] : C;
+  const int F = 1 + (L + hop - 1) / hop, fpo = bf_owner_frames(F, base), owners = (F + fpo - 1) / fpo;
+  // entry u / 2 is (c1, c2): it exists for the item where c2 < Cb
+  int c1 = 0, rest = u / 2;
+  while (rest >= C - c1) rest -= C - c1, ++c1;
+  const int c2 = c1 + rest;
+  double s = 0.0;
+  if (c2 < Cb)
+    for (int o = 0; o < owners; ++o) s += part[((((long)b * OW + o) * n + i) * T2 + u) * bins + j];
+  N[e] = s;
+}
+
+// N [items][n][2 tri(C)][bins] -> w [items][n][bins][C] complex doubles.  Thread (g, lane) of a workgroup: system
+// blockIdx.x BF_GROUPS + g = (item, source, bin), right-hand side `lane`.
+__global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __restrict__ N,
+                                                               const int* __restrict__ chans, int ref, int items,
+                                                               int n, int C, int bins, double reg, double eps,
+                                                               double* __restrict__ w) {
+  __shared__ double zd[BF_GROUPS][BF_LANES];
+  const int lane = threadIdx.x % BF_LANES, g = threadIdx.x / BF_LANES;
+  const long sys = (long)blockIdx.x * BF_GROUPS + g, total = (long)items * n * bins;
+  const bool live = sys < total;
+  const long e = live ? sys : total - 1;
+  const int j = (int)(e % bins), i = (int)(e / bins % n), b = (int)(e / bins / n);
+  const int Cb = chans ? chans[b] : C;
+  const int T2 = 2 * bf_tri(C);
+  const double* Nb = N + (long)b * n * T2 * bins + j;   // entry u of source s: Nb[(s T2 + u) bins]
+
+  // A = Q_i + lambda I: the lower triangle, row after row; a[r (r + 1) / 2 + c] = A[r][c] = conj(Q[c][r]), c <= r
+  double ar[BF_TRI], ai[BF_TRI];
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r)
+#pragma unroll
+    for (int c = 0; c <= r; ++c) {
+      const int p = r * (r + 1) / 2 + c;
+      ar[p] = ai[p] = 0.0;
+      if (r < Cb) {
+        const long at = 2L * bf_idx(C, c, r) * bins;
+        for (int s = 0; s < n; ++s)
+          if (s != i) {
+            ar[p] += Nb[(long)s * T2 * bins + at];
+            ai[p] -= Nb[(long)s * T2 * bins + at + bins];
+          }
+      }
+    }
+  double tr = 0.0;
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c)
+    if (c < Cb) tr += ar[c * (c + 1) / 2 + c];
+  const double lam = reg * (tr / (double)Cb) + eps;
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c) {
+    const int p = c * (c + 1) / 2 + c;
+    ar[p] = c < Cb ? ar[p] + lam : 1.0;
+    ai[p] = 0.0;
+  }
+  // Cholesky A = L L^H in place, column after column; the diagonal holds L[c][c], real
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c) {
+    const int pc = c * (c + 1) / 2;
+    double d = ar[pc + c];
+#pragma unroll
+    for (int k = 0; k < c; ++k) d -= ar[pc + k] * ar[pc + k] + ai[pc + k] * ai[pc + k];
+    const double l = sqrt(d);
+    ar[pc + c] = l;
+#pragma unroll
+    for (int r = c + 1; r < BF_MAX_CH; ++r) {
+      const int pr = r * (r + 1) / 2;
+      double sr = ar[pr + c], si = ai[pr + c];
+#pragma unroll
+      for (int k = 0; k < c; ++k) {   // L[r][k] conj L[c][k]
+        sr -= ar[pr + k] * ar[pc + k] + ai[pr + k] * ai[pc + k];
+        si -= ai[pr + k] * ar[pc + k] - ar[pr + k] * ai[pc + k];
+      }
+      ar[pr + c] = sr / l;
+      ai[pr + c] = si / l;
+    }
+  }
+  // column `lane` of N_i: N[r][lane] = upper(r, lane) for r <= lane, conj upper(lane, r) below
+  double zr[BF_MAX_CH], zi[BF_MAX_CH];
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r) {
+    zr[r] = zi[r] = 0.0;
+    if (r < Cb && lane < Cb) {
+      const int lo = min(r, lane), hi = max(r, lane);
+      const long at = ((long)i * T2 + 2L * bf_idx(C, lo, hi)) * bins;
+      zr[r] = Nb[at];
+      zi[r] = r <= lane ? Nb[at + bins] : -Nb[at + bins];
+    }
+  }
+  // L y = b, then L^H z = y
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r) {
+    const int pr = r * (r + 1) / 2;
+#pragma unroll
+    for (int k = 0; k < r; ++k) {
+      zr[r] -= ar[pr + k] * zr[k] - ai[pr + k] * zi[k];
+      zi[r] -= ar[pr + k] * zi[k] + ai[pr + k] * zr[k];
+    }
+    zr[r] = zr[r] / ar[pr + r];
+    zi[r] = zi[r] / ar[pr + r];
+  }
+#pragma unroll
+  for (int r = BF_MAX_CH - 1; r >= 0; --r) {
+#pragma unroll
+    for (int k = r + 1; k < BF_MAX_CH; ++k) {   // conj(L[k][r]) z[k]
+      const int pk = k * (k + 1) / 2;
+      zr[r] -= ar[pk + r] * zr[k] + ai[pk + r] * zi[k];
+      zi[r] -= ar[pk + r] * zi[k] - ai[pk + r] * zr[k];
+    }
+    zr[r] = zr[r] / ar[r * (r + 1) / 2 + r];
+    zi[r] = zi[r] / ar[r * (r + 1) / 2 + r];
+  }
+  double own = 0.0;
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r)
+    if (r == lane) own = zr[r];
+  zd[g][lane] = own;
+  __syncthreads();
+  if (!live || lane != ref) return;
+  double tau = 0.0;
+  for (int c = 0; c < Cb; ++c) tau = c == 0 ? zd[g][0] : tau + zd[g][c];
+  const bool ok = tau > 0.0 && tau <= 1.7976931348623157e308;   // finite and positive (false for NaN)
+  double* wo = w + 2L * e * C;
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c)
+    if (c < C) {
+      double vr = 0.0, vi = 0.0;
+      if (c < Cb) {
+        vr = ok ? zr[c] / tau : (c == ref ? 1.0 : 0.0);
+        vi = ok ? zi[c] / tau : 0.0;
+      }
+      wo[2 * c] = vr;
+      wo[2 * c + 1] = vi;
+    }
+}
+
+// grid (ceil(Lmax / SPAN), items, n).  w [items][n][H + 1][C] complex doubles, out [items][n][Lmax].
+// Dynamic LDS: float2 tw[H] | float2 buf[C + (post ? n : 0)][G][H] | float win[NFFT] | float ola[SPAN]
+template <int NFFT>
+__global__ __launch_bounds__(MRT) void beamform_apply_kernel(const MaskRefineShape q, int post,
+                                                             const float* __restrict__ mix,
+                                                             const float* __restrict__ est,
+                                                             const int* __restrict__ lens, const int* __restrict__ chans,
+                                                             const double* __restrict__ w, float* __restrict__ out) {
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = bf_span<NFFT>();
+  extern __shared__ __attribute__((aligned(16))) float2 bf_lds[];
+  const int n = q.n, hop = q.hop, r = NFFT / hop, tid = threadIdx.x;
+  const int b = blockIdx.y, src = blockIdx.z, s0 = blockIdx.x * SPAN;
+  const int Cb = chans ? chans[b] : q.C;
+  const int ne = post ? n : 0;
+  float2* tw = bf_lds;
+  float2* buf = tw + H;
+  float* win = reinterpret_cast<float*>(buf + (q.C + ne) * MR_POINTS);
+  float* ola = win + NFFT;
+  const int L = lens ? lens[b] : q.Lmax;
+  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const float* mixb = mix + (long)b * q.C * q.Lmax;
+  const float* estb = est + (long)b * n * q.Lmax;
+  float* outb = out + ((long)b * n + src) * q.Lmax;
+
+  if (s0 >= L) {   // (uniform) past the item's end
+    for (int v = tid; v < SPAN / 4; v += MRT)
+      if (s0 + 4 * v < q.Lmax) mr_store(q, outb, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  bf_tables<H>(tw, win, tid);
+  for (int e = tid; e < SPAN; e += MRT) ola[e] = 0.f;
+
+  // sample p is covered by the r frames (p + H) / hop - r + 1 .. (p + H) / hop, where they exist
+  const int pend = min(s0 + SPAN, L);
+  const int f_first = max(0, (s0 + H) / hop - r + 1), f_last = min(F - 1, (pend - 1 + H) / hop);
+  const float inv_n = 1.f / (float)NFFT;   // mr_merge hands back twice the packed transform: 1 / (2 H)
+  const double* wb = w + 2L * ((long)b * n + src) * (H + 1) * q.C;   // bin j, channel c: wb[2 (j C + c)]
+
+  for (int f0 = f_first; f0 <= f_last; f0 += G) {
+    __syncthreads();   // the tables are in; the previous group's frames have been added
+    bf_load<H>(buf, win, mixb, estb, q.Lmax, L, Lp, hop, Cb, ne, f0, f_last, tid);
+    __syncthreads();
+    mr_fft<H, false, BF_BF>(buf, tw, (Cb + ne) * (MR_POINTS / 2), tid);
+    // ---- contract: one thread per (frame, pair of bins k and H - k); channel 0's slot becomes Y, packed again
+    for (int e = tid; e < G * NP; e += MRT) {
+      const int fg = e / NP, k = e - fg * NP, km = (H - k) & (H - 1);
+      if (f0 + fg > f_last) continue;
+      const float2 t = tw[k];
+      const double* wk = wb + 2L * k * q.C;
+      const double* wm = wb + 2L * (H - k) * q.C;
+      double ykr = 0.0, yki = 0.0, ymr = 0.0, ymi = 0.0;
+      for (int c = 0; c < Cb; ++c) {   // conj(w_c) X_c
+        const float2* a = buf + c * MR_POINTS + fg * H;
+        float2 xk, xm;
+        mr_split(a[k], a[km], t, xk, xm);
+        const double kr = wk[2 * c], ki = wk[2 * c + 1], mr = wm[2 * c], mi = wm[2 * c + 1];
+        const double pkr = kr * (double)xk.x + ki * (double)xk.y, pki = kr * (double)xk.y - ki * (double)xk.x;
+        const double pmr = mr * (double)xm.x + mi * (double)xm.y, pmi = mr * (double)xm.y - mi * (double)xm.x;
+        ykr = c == 0 ? pkr : ykr + pkr;
+        yki = c == 0 ? pki : yki + pki;
+        ymr = c == 0 ? pmr : ymr + pmr;
+        ymi = c == 0 ? pmi : ymi + pmi;
+      }
+      float2 yk = make_float2((float)ykr, (float)yki), ym = make_float2((float)ymr, (float)ymi);
+      if (post) {
+        float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
+        mr_masks(q, buf + Cb * MR_POINTS + fg * H, k, km, t, mk, mm);
+        float sk = 0.f, sm = 0.f;
+#pragma unroll
+        for (int s = 0; s < MR_MAX_SRC; ++s)
+          if (s == src) sk = mk[s], sm = mm[s];
+        yk = make_float2(sk * yk.x, sk * yk.y);
+        ym = make_float2(sm * ym.x, sm * ym.y);
+      }
+      float2 zk, zm;
+      mr_merge(yk, ym, t, zk, zm);
+      float2* o = buf + fg * H;
+      o[k] = zk;
+      if (km != k) o[km] = zm;
+    }
+    __syncthreads();
+    mr_fft<H, true, BF_BF>(buf, tw, MR_POINTS / 2, tid);
+    // ---- add: a thread owns quads of samples for the whole launch, so every sample's sum runs in frame order
+    const int g_last = min(f0 + G - 1, f_last);
+    const float* y = reinterpret_cast<const float*>(buf);
+    for (int v = tid; v < SPAN / 4; v += MRT) {
+      const int p = s0 + 4 * v;
+      if (p >= pend) continue;
+      const int fhi = (p + H) / hop;   // (hop % 4 == 0: the same frames cover the whole quad)
+      const int fa = max(fhi - r + 1, f0), fb = min(fhi, g_last);
+      float4 acc = *reinterpret_cast<float4*>(ola + 4 * v);
+      for (int f = fa; f <= fb; ++f) {
+        const int t = p + H - f * hop;
+        const float4 yv = *reinterpret_cast<const float4*>(y + (f - f0) * NFFT + t);
+        const float4 wv = *reinterpret_cast<const float4*>(win + t);
+        acc.x = acc.x + (yv.x * inv_n) * wv.x;
+        acc.y = acc.y + (yv.y * inv_n) * wv.y;
+        acc.z = acc.z + (yv.z * inv_n) * wv.z;
+        acc.w = acc.w + (yv.w * inv_n) * wv.w;
+      }
+      *reinterpret_cast<float4*>(ola + 4 * v) = acc;
+    }
+  }
+
+  // ---- the envelope of the frames that exist, the division and the store (the quads this thread summed itself)
+  for (int v = tid; v < SPAN / 4; v += MRT) {
+    const int p = s0 + 4 * v;
+    if (p >= q.Lmax) continue;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (p < pend) {
+      float env[4] = {0.f, 0.f, 0.f, 0.f};
+      const int fhi = (p + H) / hop;
+      const int fa = max(fhi - r + 1, 0), fb = min(fhi, F - 1);
+      for (int f = fa; f <= fb; ++f) {
+        const float4 wv = *reinterpret_cast<const float4*>(win + (p + H - f * hop));
+        env[0] = env[0] + wv.x * wv.x;
+        env[1] = env[1] + wv.y * wv.y;
+        env[2] = env[2] + wv.z * wv.z;
+        env[3] = env[3] + wv.w * wv.w;
+      }
+      const float4 acc = *reinterpret_cast<const float4*>(ola + 4 * v);
+      o.x = acc.x / env[0];
+      o.y = p + 1 < L ? acc.y / env[1] : 0.f;
+      o.z = p + 2 < L ? acc.z / env[2] : 0.f;
+      o.w = p + 3 < L ? acc.w / env[3] : 0.f;
+    }
+    mr_store(q, outb, p, o);
+  }
+}
+
+template <int NFFT>
+size_t bf_lds_bytes(int slots, bool ola) {
+  return sizeof(float2) * ((size_t)NFFT / 2 + (size_t)slots * MR_POINTS) +
+         sizeof(float) * ((size_t)NFFT + (ola ? (size_t)bf_span<NFFT>() : 0));
+}
+
+struct BfArgs {
+  const float *mix, *est;
+  const int *lens, *chans;
+  int ref;
+  double *part, *N, *w;
+  float* out;
+  int items, post;
+  double reg, eps;
+};
+
+template <int NFFT>
+void bf_run(int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st) {
+  constexpr int SPAN = bf_span<NFFT>();
+  const int bins = NFFT / 2 + 1, T2 = 2 * bf_tri(q.C), OW = beamform_owners(NFFT, q.hop, q.Lmax);
+  if (stage == 0) {
+    dsn_allow_lds<beamform_stats_kernel<NFFT>>((int)bf_lds_bytes<NFFT>(BF_MAX_CH + MR_MAX_SRC, false));
+    hipLaunchKernelGGL((beamform_stats_kernel<NFFT>), dim3((unsigned)OW, (unsigned)a.items, (unsigned)q.n), dim3(MRT),
+                       bf_lds_bytes<NFFT>(q.C + q.n, false), st, q, a.mix, a.est, a.lens, a.chans, a.part);
+    const long rows = (long)a.items * q.n * T2 * bins;
+    hipLaunchKernelGGL(beamform_reduce_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, a.part,
+                       a.lens, a.chans, a.items, q.n, q.C, q.Lmax, bins, q.hop, SPAN / q.hop, OW, a.N);
+    const long systems = (long)a.items * q.n * bins;
+    hipLaunchKernelGGL(beamform_weights_kernel, dim3((unsigned)((systems + BF_GROUPS - 1) / BF_GROUPS)), dim3(MRT), 0,
+                       st, a.N, a.chans, a.ref, a.items, q.n, q.C, bins, a.reg, a.eps, a.w);
+    return;
+  }
+  const int slots = q.C + (a.post ? q.n : 0);
+  dsn_allow_lds<beamform_apply_kernel<NFFT>>((int)bf_lds_bytes<NFFT>(BF_MAX_CH + MR_MAX_SRC, true));
+  hipLaunchKernelGGL((beamform_apply_kernel<NFFT>),
+                     dim3((unsigned)((q.Lmax + SPAN - 1) / SPAN), (unsigned)a.items, (unsigned)q.n), dim3(MRT),
+                     bf_lds_bytes<NFFT>(slots, true), st, q, a.post, a.mix, a.est, a.lens, a.chans, a.w, a.out);
+}
+
+void bf_dispatch(int nfft, int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st) {
+  switch (nfft) {
+    case 64: bf_run<64>(stage, q, a, st); break;
+    case 128: bf_run<128>(stage, q, a, st); break;
+    case 256: bf_run<256>(stage, q, a, st); break;
+    case 512: bf_run<512>(stage, q, a, st); break;
+    case 1024: bf_run<1024>(stage, q, a, st); break;
+    default: bf_run<2048>(stage, q, a, st); break;
+  }
+}
+
+}  // namespace
+
+int beamform_owners(int nfft, int hop, int Lmax) {
+  const int F = 1 + (Lmax + hop - 1) / hop, base = (nfft >= 2048 ? bf_span<2048>() : bf_span<64>()) / hop;
+  return std::min(BEAMFORM_MAX_OWNERS, (F + base - 1) / base);   // (an item of L <= Lmax samples has no more owners)
+}
+
+size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n) {
+  return ((size_t)beamform_owners(nfft, hop, Lmax) + 1) * n * 2 * bf_tri(C) * ((size_t)nfft / 2 + 1);
+}
+
+void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,
+                             double* part, double* N, double* w, int items, int C, int n, int Lmax, int nfft, int hop,
+                             int power, float eps, float reg, hipStream_t st) {
+  const MaskRefineShape q{n, Lmax, hop, power, eps, 0, C, reg};
+  bf_dispatch(nfft, 0, q, BfArgs{mix, est, lens, chans, ref, part, N, w, nullptr, items, 0, (double)reg, (double)eps},
+              st);
+}
+
+void launch_beamform_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
+                           float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
+                           int post, hipStream_t st) {
+  const MaskRefineShape q{n, Lmax, hop, power, eps, ((uintptr_t)out & 15) == 0 && Lmax % 4 == 0 ? 1 : 0, C, 0.f};
+  bf_dispatch(nfft, 1, q, BfArgs{mix, est, lens, chans, 0, nullptr, nullptr, const_cast<double*>(w), out, items,
+                                 post, 0.0, (double)eps}, st);
+}

@@ -3478,6 +3478,74 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
   });
 }
 
+// ---- mask-based MVDR beamforming (beamform.hip; include/ditsep_hip.h states the definition)
+int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
+                 const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
+                 int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_beamform";
+    if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
+    if (postfilter != DSN_BEAMFORM_POST_NONE && postfilter != DSN_BEAMFORM_POST_MASK)
+      fail(DSN_EINVAL, "%s: postfilter = %d is not one of 0 (DSN_BEAMFORM_POST_NONE), 1 (DSN_BEAMFORM_POST_MASK)", who,
+           postfilter);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
+    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
+      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
+    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
+    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
+    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
+    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
+    const int need = n_fft / 2 + 1;
+    for (int b = 0; b < B; ++b) {
+      const int len = lens ? lens[b] : Lmax;
+      if (len < need || len > Lmax)
+        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
+             "reflection must reach the item)", who, b, len, need, Lmax, need);
+      const int cb = channels ? (int)channels[b] : C;
+      if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
+      if (ref < 0 || ref >= cb)
+        fail(DSN_EINVAL, "%s: ref = %d outside [0, %d): item %d has %d channels", who, ref, cb, b, cb);
+    }
+    if (workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)workspace_budget);
+    const size_t per_item = sizeof(double) * beamform_item_doubles(n_fft, hop, Lmax, C, n);
+    const size_t fit = (size_t)(workspace_budget ? workspace_budget : BEAMFORM_DEFAULT_BUDGET) / per_item;
+    if (fit < 1)
+      fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at C = %d, n = %d, "
+           "n_fft = %d, hop = %d, Lmax = %d)", who, (long)workspace_budget, (long)per_item, C, n, n_fft, hop, Lmax);
+    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    const size_t row = sizeof(float) * (size_t)B * Lmax;
+    if ((o0 < m0 + row * C && m0 < o0 + row * n) || (o0 < e0 + row * n && e0 < o0 + row * n))
+      fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int *dlens = nullptr, *dch = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "beamform_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    if (channels) dch = (const int*)upload_table(ctx, "beamform_channels", channels, sizeof(int32_t) * (size_t)B, st);
+    const int ipc = (int)std::min<size_t>(fit, (size_t)B);
+    const size_t bins = (size_t)n_fft / 2 + 1, T2 = (size_t)C * (C + 1), nw = (size_t)B * n * bins * C * 2;
+    const size_t npart = (size_t)ipc * beamform_owners(n_fft, hop, Lmax) * n * T2 * bins;
+    double* part = ctx->wsbuf<double>("beamform_part", npart + (size_t)ipc * n * T2 * bins);
+    double* N = part + npart;
+    double* w = ctx->wsbuf<double>("beamform_w", nw);
+    ctx->prof_launch("beamform", 4.0 * (double)B * Lmax * ((double)C * (n + 1) + (postfilter ? 2.0 : 1.0) * n + n), st, [&] {
+      for (int b0 = 0; b0 < B; b0 += ipc) {   // the chunk's partials are reused from chunk to chunk on the one stream
+        const int items = std::min(ipc, B - b0);
+        launch_beamform_weights(mix + (size_t)b0 * C * Lmax, est + (size_t)b0 * n * Lmax, dlens ? dlens + b0 : nullptr,
+                                dch ? dch + b0 : nullptr, ref, part, N, w + (size_t)b0 * n * bins * C * 2, items, C, n,
+                                Lmax, n_fft, hop, power, eps, reg, st);
+      }
+      launch_beamform_apply(mix, est, dlens, dch, w, out, B, C, n, Lmax, n_fft, hop, power, eps,
+                            postfilter == DSN_BEAMFORM_POST_MASK, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!info_w) return;
+    HIPCHK(hipMemcpyAsync(info_w, w, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
 // ---- loudness, true peak and the gain (loudness.hip; include/ditsep_hip.h states the definition)
 int dsn_kweight_coeffs(int fs, double* out) {
   if (!out || fs < LOUD_MIN_RATE || fs > LOUD_MAX_RATE) return DSN_EINVAL;

@@ -460,6 +460,25 @@ void launch_stems(const float* mix, const float* est, const int* lens, const int
                   double* R, double* den, int B, int C, int n, int Lmax, int wiener, int nfft, int hop, int power,
                   float eps, float reg, hipStream_t s);
 
+// ---- mask-based MVDR beamforming (beamform.hip) --------------------------------------------------------------------
+// mix [items][C][Lmax], est / out [items][n][Lmax] fp32, lens / chans [items] (device) or null, C <= BEAMFORM_MAX_CH.
+// launch_beamform_weights, three launches: fp64 partials part [items][beamform_owners][n][C (C + 1)][bins] over the
+// frames each owner takes (grid (owners, items, n): every frame has one owner per source; an item has at most
+// BEAMFORM_MAX_OWNERS of them, each taking whole spans, more than one on long items), N [items][n][C (C + 1)][bins] from them in owner order, and the per-bin
+// Cholesky solve that writes w [items][n][bins][C] complex doubles.  launch_beamform_apply: one launch, a workgroup
+// per (span, item, source), w read from global memory.  bins = nfft / 2 + 1.
+#define BEAMFORM_MAX_CH 8
+#define BEAMFORM_MAX_OWNERS 16
+#define BEAMFORM_DEFAULT_BUDGET (512L << 20)
+int beamform_owners(int nfft, int hop, int Lmax);
+size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n);   // part and N of one item
+void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,
+                             double* part, double* N, double* w, int items, int C, int n, int Lmax, int nfft, int hop,
+                             int power, float eps, float reg, hipStream_t s);
+void launch_beamform_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
+                           float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
+                           int post, hipStream_t s);
+
 // ---- ensemble combine (ensemble.hip) -----------------------------------------------------------------------------
 // cands [B][K][n][Lmax], mix [B][Lmax] or null, out [B][n][Lmax] fp32, lens [B] (device) or null, K <= ENSEMBLE_MAX_K,
 // n <= ENSEMBLE_MAX_SRC.  Three launches: Gram partials part [B][tiles][NB][16] (4 x 4 blocks of row pairs on and above

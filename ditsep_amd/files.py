@@ -90,7 +90,7 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, loudness=None, limit=None, **sampler_kwargs) -> list:
+                   stems=None, loudness=None, limit=None, beamform=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -104,6 +104,10 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     if stems is not None and rescale:
         raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
                          "mixture")
+    beam = native.beamform_options(beamform)
+    if beam is not None and stems is not None:
+        raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, stems= "
+                         "the mixture's channels")
     loud = native.level_options(loudness, limit)
     linked = loud is not None and loud["link"] == "mixture" and loud["target"] is not None   # the file is the source
     if long_mode not in native.LONG_MODES:
@@ -115,11 +119,12 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             if not native.LOUDNESS_RATES[0] <= h.rate <= native.LOUDNESS_RATES[1]:
                 raise ValueError(f"{p}: {h.rate} Hz; loudness= measures rates in [{native.LOUDNESS_RATES[0]}, "
                                  f"{native.LOUDNESS_RATES[1]}] Hz")
-            if linked and h.channels > native.LOUDNESS_MAX_CHANNELS:
+            if linked and beam is None and h.channels > native.LOUDNESS_MAX_CHANNELS:
                 raise ValueError(f"{p}: {h.channels} channels; loudness= with link 'mixture' measures at most "
                                  f"{native.LOUDNESS_MAX_CHANNELS} (no surround weights; link 'stem' measures the outputs)")
-    # the files' own channels are needed by the stems filter and as the gain source of a mixture-linked loudness
-    keep_channels = stems is not None or linked
+    # the files' own channels are needed by the stems filter, by the beamformer and as the gain source of a
+    # mixture-linked loudness
+    keep_channels = stems is not None or beam is not None or linked
     hop = model.hop_length
     ens = {} if samples is None else dict(samples=native.check_samples(samples, combine), combine=combine)
     plan = plan_files(headers, fs, hop, files_per_batch(batch, samples), long_after)
@@ -146,13 +151,29 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                                  f"{native.STEMS_MAX_CHANNELS[stems['mode']]}")
             if v < need:
                 raise ValueError(f"{p}: {v} samples at the model's rate; stems= needs at least n_fft / 2 + 1 = {need}")
+    if beam is not None:
+        # .. and those of the beamformer: the parameters on a stand-in item, every file's channel count and length
+        need = native.check_beamform((1, 8, 2049), (1, n, 2049), None, None, **dict(beam, ref=0))[4] // 2 + 1
+        ref = beam["ref"]
+        for p, h, v in zip(paths, headers, plan["lengths"]):
+            if h.channels > native.BEAMFORM_MAX_CHANNELS:
+                raise ValueError(f"{p}: {h.channels} channels; beamform= takes at most {native.BEAMFORM_MAX_CHANNELS}")
+            if isinstance(ref, bool) or int(ref) != ref or not 0 <= ref < h.channels:
+                raise ValueError(f"{p}: {h.channels} channels; beamform= has ref = {ref!r} outside [0, {h.channels})")
+            if v < need:
+                raise ValueError(f"{p}: {v} samples at the model's rate; beamform= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
+
+    def reference(clips):
+        """channel `ref` of every clip [C, L] as [1, L]: what the model separates and loudness measures with beamform="""
+        return [c[beam["ref"]:beam["ref"] + 1].contiguous() for c in clips]
 
     def level(idx, clips, back):
         """the `loudness` step: rows at the files' own rates -> (the rows with their gains applied, the record entries)"""
         if loud is None:
             return back, [{} for _ in idx]
-        back, info = eng.loudness_normalize(clips if linked else None, back, [headers[i].rate for i in idx], **loud)
+        sources = None if not linked else clips if beam is None else reference(clips)
+        back, info = eng.loudness_normalize(sources, back, [headers[i].rate for i in idx], **loud)
         keys = ("loudness_in", "loudness_out", "gain_db", "true_peak_db")
         if loud.get("limit") is not None:
             keys += ("reached", "evaluations", "reduction_db", "limited_samples")
@@ -184,13 +205,16 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                           "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label,
                           "stems": stems["mode"], **levels[j]}
 
-    def finish(idx, at_fs, est, label, clips=None):
-        """estimates at the model's rate -> files; `at_fs` the mono mixtures there"""
+    def finish(idx, at_fs, est, label, clips=None, channels_fs=None):
+        """estimates at the model's rate -> files; `at_fs` the mono mixtures there (with beamform=: channel `ref`, and
+        `channels_fs` all channels)"""
         alpha = None
         if refine is not None:
             est = eng.mask_refine(at_fs, est, **refine)
         if stems is not None:
             return finish_stems(idx, clips, est, label)
+        if beam is not None:
+            est = eng.beamform([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est), **beam)
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)
@@ -214,19 +238,30 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                    "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label}
             if alpha is not None:
                 rec["alpha"] = [float(a) for a in alpha[j]]
+            if beam is not None:
+                rec["beamform"] = beam["ref"]
             records[i] = dict(rec, **levels[j])
+
+    def mono_at_model_rate(idx, clips):
+        """what the model separates, at its rate: the downmix -- or, with beamform=, channel `ref` of all channels taken
+        there with the channels kept, which come back as well"""
+        rates = [headers[i].rate for i in idx]
+        if beam is None:
+            return eng.to_model_rate(clips, rates, fs), None
+        channels_fs = eng.to_model_rate(clips, rates, fs, downmix=False)
+        return reference(channels_fs), channels_fs
 
     for k, idx in enumerate(plan["batches"]):
         clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=not keep_channels)
-        at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
+        at_fs, channels_fs = mono_at_model_rate(idx, clips)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed) + k)
         est, *_ = model.separate_batch(at_fs, codec=codec, **ens, **kw)
-        finish(idx, at_fs, est, k, clips)
+        finish(idx, at_fs, est, k, clips, channels_fs)
     if plan["long"]:
         idx = plan["long"]
         clips = load_batch(eng, [paths[i] for i in idx], [headers[i] for i in idx], downmix=not keep_channels)
-        at_fs = eng.to_model_rate(clips, [headers[i].rate for i in idx], fs)
+        at_fs, channels_fs = mono_at_model_rate(idx, clips)
         kw = dict(sampler_kwargs) if seed is None else dict(sampler_kwargs, seed=int(seed))
         est, *_ = model.separate_long(at_fs, window, overlap=overlap, mode=long_mode, batch=batch, **kw)
-        finish(idx, at_fs, est, "long", clips)
+        finish(idx, at_fs, est, "long", clips, channels_fs)
     return records

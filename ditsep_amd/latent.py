@@ -411,6 +411,76 @@ class LatentDiffSep:
             out = eng.stems_from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
 
+    # ------------------------------------------------------------------ beamforming (the `beamform` keyword)
+    def _beamform_refusals(self, bopts, channels, stems=None, latent=False, intermediate=None):
+        """What the `beamform` keyword refuses, before any device work"""
+        if stems is not None:
+            raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, "
+                             "stems= the mixture's channels")
+        if latent:
+            raise ValueError("beamform= filters waveforms: with latent=True there is no mixture to filter")
+        if intermediate:
+            raise ValueError("beamform= does not go with intermediate: the per-step states are not filtered")
+        ref, most = bopts["ref"], native.BEAMFORM_MAX_CHANNELS
+        for b, c in enumerate(channels):
+            if c < 1 or c > most:
+                raise ValueError(f"beamform: item {b} has {c} channels, outside [1, {most}]")
+            if isinstance(ref, bool) or int(ref) != ref or not 0 <= ref < c:
+                raise ValueError(f"beamform: ref = {ref!r} outside [0, {c}): item {b} has {c} channels")
+
+    @staticmethod
+    def _reference_channel(clips, ref):
+        """clips [C_b, L_b] each -> channel `ref` of each as [1, L_b]"""
+        return [c[ref:ref + 1].contiguous() for c in clips]
+
+    @torch.no_grad()
+    def _separate_beamform(self, mix, target_dim, sample_rate, bopts, mono_kw, kwargs):
+        """`separate` with beamform=: mix [B, C, L] -> the mono call on channel `ref`, Engine.beamform against all
+        channels at the model's rate (zero-extended or cut to the estimates' length), back to `sample_rate`"""
+        eng = self.engine
+        if not torch.is_tensor(mix) or mix.dim() != 3:
+            raise ValueError(f"beamform= takes mix [B, C, L] (got {tuple(getattr(mix, 'shape', ()))})")
+        B, Cn, L = (int(v) for v in mix.shape)
+        self._beamform_refusals(bopts, [Cn], intermediate=kwargs.get("intermediate"))
+        if sample_rate is None:
+            mc = native._dev32(mix, eng.device)
+        else:
+            fs = self._model_rate("sample_rate=")
+            mc = eng.resample(mix, sample_rate, fs)
+        one = mc[:, bopts["ref"]:bopts["ref"] + 1].contiguous()
+        est, *others = self.separate(one, target_dim, **mono_kw, **kwargs)
+        out = eng.beamform(self._fit(mc, int(est.shape[-1])), est, **bopts)
+        if sample_rate is not None:
+            out = eng.resample(out, fs, sample_rate)[..., :L]
+        return (out, *others)
+
+    @staticmethod
+    def _as_channel_clips(clips, what):
+        clips = [c[None] if c.dim() == 1 else c[0] if c.dim() == 3 and c.shape[0] == 1 else c for c in clips]
+        for b, c in enumerate(clips):
+            if c.dim() != 2:
+                raise ValueError(f"{what}=: clip {b} must be [L], [C, L] or [1, C, L] (got {tuple(c.shape)})")
+        return clips
+
+    @torch.no_grad()
+    def _beamform_of_lists(self, clips, rates, bopts, run):
+        """The list entry points with beamform=: `clips` [C_b, L_b] each (or [L_b], [1, C_b, L_b]) at `rates` (None:
+        the model's rate); run(list of [1, L'_b], channel `ref` of each) -> (list of [n, Le_b] estimates at the model's
+        rate, *others).  -> (list of [n, L_b] at each clip's own rate, *others)"""
+        eng = self.engine
+        clips = self._as_channel_clips(clips, "beamform")
+        self._beamform_refusals(bopts, [int(c.shape[0]) for c in clips])
+        if rates is None:
+            mc = [native._dev32(c, eng.device) for c in clips]
+        else:
+            fs = self._model_rate("sample_rates=")
+            mc = eng.to_model_rate(clips, rates, fs, downmix=False)
+        est, *others = run(self._reference_channel(mc, bopts["ref"]))
+        out = eng.beamform([self._fit(m, int(e.shape[-1])) for m, e in zip(mc, est)], list(est), **bopts)
+        if rates is not None:
+            out = eng.from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
+        return (out, *others)
+
     # ------------------------------------------------------------------ loudness (the `loudness` keyword)
     def _loudness_refusals(self, lopts, channels, latent=False, intermediate=None):
         """What the `loudness` keyword refuses, before any device work"""
@@ -445,7 +515,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
-                 return_info=False, stems=None, loudness=None, limit=None, **kwargs):
+                 return_info=False, stems=None, loudness=None, limit=None, beamform=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -489,17 +559,31 @@ class LatentDiffSep:
         its bits.  With link "mixture" the stems share the curve g[t], so stems that summed to the mixture sum to
         g[t] G mixture[t].  Without loudness= every item goes once
         through the limiter at 0 dB against the ceiling (default -1 dBTP).  The info gains "reached", "evaluations",
-        "reduction_db" and "limited_samples".  Refused where loudness= is."""
+        "reduction_db" and "limited_samples".  Refused where loudness= is.
+        beamform (default None: the call returns the bits it returned before): True, an int (the reference channel) or
+        a dict of ref / n_fft / hop / power / eps / reg / postfilter (native.beamform_options) -- mix is then a
+        microphone-array recording [B, C, L] (C <= 8) and [B, n, L] comes back: the call above runs on channel `ref`
+        (not on the downmix), and Engine.beamform filters all channels at the model's rate (resampled with the
+        channels kept, zero-extended or cut to the estimates' length) towards every source with a mask-based MVDR
+        beamformer, after combine and refine and before the resampling back, loudness and limit, which see mono
+        estimates as they do without the keyword; loudness with link "mixture" measures channel `ref`.  One filter
+        per recording; not a trained step.  Refused together with stems=, with latent=True and with intermediate."""
+        bopts = native.beamform_options(beamform)
+        if bopts is not None:
+            chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else []
+            self._beamform_refusals(bopts, chans, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
-            chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else [1]
+            chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 and bopts is None else [1]
             self._loudness_refusals(lopts, chans, latent=latent, intermediate=kwargs.get("intermediate"))
             rate = self._model_rate("loudness=") if sample_rate is None else int(sample_rate)
             inner = bool(return_info) and samples is not None
             est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
-                                         combine=combine, return_info=inner, stems=stems, **kwargs)
+                                         combine=combine, return_info=inner, stems=stems, beamform=beamform, **kwargs)
             B = int(est.shape[0])
             m3 = mix[:, None] if mix.dim() == 2 else mix
+            if bopts is not None:
+                m3 = m3[:, bopts["ref"]:bopts["ref"] + 1]
             outs, others = self._normalise(lopts, [m3[b] for b in range(B)], [est[b] for b in range(B)], rate, others,
                                            return_info, inner)
             return (torch.stack(outs), *others)
@@ -508,6 +592,9 @@ class LatentDiffSep:
             self._stems_refusals(sopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
             mono_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info)
             return self._separate_stems(mix, target_dim, sample_rate, sopts, mono_kw, kwargs)
+        if bopts is not None:
+            mono_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info)
+            return self._separate_beamform(mix, target_dim, sample_rate, bopts, mono_kw, kwargs)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -556,7 +643,8 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
-                       combine="mean", return_info=False, stems=None, loudness=None, limit=None, **sampler_kwargs):
+                       combine="mean", return_info=False, stems=None, loudness=None, limit=None, beamform=None,
+                       **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -581,19 +669,29 @@ class LatentDiffSep:
         as they were given (each at its own rate, with its own channels), one on the padded estimates, one
         Engine.apply_gain call; each item gets the gain it gets alone.
         limit (default None: off), as in `separate`: the items the ceiling holds back go through the limiter's loop
-        together, each with the pre-gains and the curve it gets alone."""
+        together, each with the pre-gains and the curve it gets alone.
+        beamform (default None: off), as in `separate`: the mixtures are array recordings [C_b, L_b] (mixed channel
+        counts are fine), the call runs on channel `ref` of each, one Engine.beamform call on the padded batch filters
+        every item's own channels at the model's rate, and a list of [n, L_b] comes back, each item with the bits it
+        gets alone."""
         eng = self.engine
+        bopts = native.beamform_options(beamform)
+        if bopts is not None:
+            mixes = self._as_channel_clips(list(mixes), "beamform")
+            self._beamform_refusals(bopts, [int(m.shape[0]) for m in mixes], stems=stems,
+                                    intermediate=sampler_kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
             mixes = list(mixes)
-            self._loudness_refusals(lopts, [self._clip_channels(m) for m in mixes],
+            sources = mixes if bopts is None else self._reference_channel(mixes, bopts["ref"])
+            self._loudness_refusals(lopts, [self._clip_channels(m) for m in sources],
                                     intermediate=sampler_kwargs.get("intermediate"))
             rates = self._model_rate("loudness=") if sample_rates is None else sample_rates
             inner = bool(return_info) and samples is not None
             est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
                                                samples=samples, combine=combine, return_info=inner, stems=stems,
-                                               **sampler_kwargs)
-            outs, others = self._normalise(lopts, mixes, est, rates, others, return_info, inner)
+                                               beamform=beamform, **sampler_kwargs)
+            outs, others = self._normalise(lopts, sources, est, rates, others, return_info, inner)
             return (outs, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -603,6 +701,13 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
             return self._stems_of_lists(list(mixes), rates, sopts, lambda mono: self.separate_batch(
                 mono, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
+                **sampler_kwargs))
+        if bopts is not None:
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
+            return self._beamform_of_lists(mixes, rates, bopts, lambda one: self.separate_batch(
+                one, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
                 **sampler_kwargs))
         ens = {}
         if samples is not None:
@@ -654,7 +759,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
                       mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
-                      **sampler_kwargs):
+                      beamform=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -676,18 +781,28 @@ class LatentDiffSep:
         stitch and refine: [n, C, L] or a list of [n, C_r, L_r] comes back.
         loudness (default None: off), as in `separate_batch`: every recording is measured whole and gets one gain,
         the last step; with return_info=True its entries join the stitch's info dict.
-        limit (default None: off), as in `separate_batch`: every recording is limited whole."""
+        limit (default None: off), as in `separate_batch`: every recording is limited whole.
+        beamform (default None: off), as in `separate_batch`, in both modes: the recordings are [C, L_r], the call runs
+        on channel `ref` of each, and every recording's channels are beamformed whole (Engine.beamform: one filter per
+        recording) at the model's rate after the stitch and refine: [n, L] or a list of [n, L_r] comes back."""
         eng = self.engine
+        bopts = native.beamform_options(beamform)
+        if bopts is not None:
+            bclips = self._as_channel_clips([mixes] if torch.is_tensor(mixes) else list(mixes), "beamform")
+            self._beamform_refusals(bopts, [int(m.shape[0]) for m in bclips], stems=stems,
+                                    intermediate=sampler_kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
             single = torch.is_tensor(mixes)
             clips = [mixes] if single else list(mixes)
+            if bopts is not None:
+                clips = self._reference_channel(bclips, bopts["ref"])
             self._loudness_refusals(lopts, [self._clip_channels(m) for m in clips],
                                     intermediate=sampler_kwargs.get("intermediate"))
             rates = self._model_rate("loudness=") if sample_rates is None else sample_rates
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
                                               return_info=return_info, mode=mode, sample_rates=sample_rates,
-                                              refine=refine, stems=stems, **sampler_kwargs)
+                                              refine=refine, stems=stems, beamform=beamform, **sampler_kwargs)
             outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
                                            bool(return_info))
             return (outs[0] if single else outs, *others)
@@ -701,6 +816,15 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(clips) if isinstance(rates, int) else [int(r) for r in rates]
             out, *others = self._stems_of_lists(clips, rates, sopts, lambda mono: self.separate_long(
                 mono, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
+                refine=refine, **sampler_kwargs))
+            return (out[0] if single else out, *others)
+        if bopts is not None:
+            single = torch.is_tensor(mixes)
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(bclips) if isinstance(rates, int) else [int(r) for r in rates]
+            out, *others = self._beamform_of_lists(bclips, rates, bopts, lambda one: self.separate_long(
+                one, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
                 refine=refine, **sampler_kwargs))
             return (out[0] if single else out, *others)
         opts = native.refine_options(refine)
@@ -764,7 +888,8 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
-                       samples=None, combine="mean", stems=None, loudness=None, limit=None, **sampler_kwargs):
+                       samples=None, combine="mean", stems=None, loudness=None, limit=None, beamform=None,
+                       **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -801,13 +926,20 @@ class LatentDiffSep:
         limit (default None: off, the files are the bytes they were), as in `separate`: the true-peak look-ahead limiter
         in that last step, immediately before the quantiser; a file the single gain brings to the target keeps its
         bytes.  Each dict gains "reached", "evaluations", "reduction_db" and "limited_samples", one entry per speaker
-        (and, without loudness=, the four entries above)."""
+        (and, without loudness=, the four entries above).
+        beamform (default None: off, the files are the bytes they were), as in `separate`: array recordings of up to 8
+        channels are decoded with their channels (Engine.pcm_decode, downmix=False), the separation runs on channel
+        `ref` at the model's rate, and after refine every file's own channels are beamformed (Engine.beamform); then
+        rescale (against channel `ref`), the resampling back, loudness (link "mixture" measures channel `ref` of the
+        file) and limit as without the keyword.  The outputs stay mono `out_dir/s{i}/{stem}.wav`.  Each dict gains
+        "beamform" (the reference channel).  A file with too few channels for `ref`, more than 8, or too short for one
+        reflection is refused before any device work; so is stems= together with it."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
-                                    loudness=loudness, limit=limit, **sampler_kwargs)
+                                    loudness=loudness, limit=limit, beamform=beamform, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

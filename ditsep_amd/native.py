@@ -42,6 +42,7 @@ EXPORTS = [
     "dsn_mask_refine",
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
+    "dsn_beamform",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
@@ -701,6 +702,95 @@ def check_stems(mix_shape, est_shape, lens=None, channels=None, mode="wiener", n
     return (B, Cn, n, L), ln, ch, STEMS_MODES[mode], n_fft, hop, power, eps, reg
 
 
+BEAMFORM_POSTFILTERS = {None: 0, "none": 0, "mask": 1}                               # DSN_BEAMFORM_POST_*
+BEAMFORM_MAX_CHANNELS, BEAMFORM_MAX_OWNERS, BEAMFORM_DEFAULT_BUDGET = 8, 16, 512 << 20
+# n_fft, hop, power, eps and reg are STEMS_DEFAULTS' values: they are not tuned for beamforming.
+BEAMFORM_DEFAULTS = dict(ref=0, n_fft=STEMS_DEFAULTS["n_fft"], hop=STEMS_DEFAULTS["hop"], power=STEMS_DEFAULTS["power"],
+                         eps=STEMS_DEFAULTS["eps"], reg=STEMS_DEFAULTS["reg"], postfilter=None)
+
+
+def beamform_options(beamform) -> Optional[dict]:
+    """The `beamform` keyword of the separation entry points as Engine.beamform's keywords: None (off, the default)
+    -> None; True -> BEAMFORM_DEFAULTS; an int -> the defaults with that reference channel; a dict of ref / n_fft /
+    hop / power / eps / reg / postfilter -> the defaults with those replaced.  Anything else, False and an unknown key
+    or post-filter included, is refused by name."""
+    if beamform is None:
+        return None
+    if beamform is True:
+        return dict(BEAMFORM_DEFAULTS)
+    if isinstance(beamform, int) and not isinstance(beamform, bool):
+        if beamform < 0:
+            raise ValueError(f"beamform: the reference channel {beamform} is negative")
+        return dict(BEAMFORM_DEFAULTS, ref=int(beamform))
+    if isinstance(beamform, Mapping):
+        extra = sorted(set(beamform) - set(BEAMFORM_DEFAULTS))
+        if extra:
+            raise ValueError(f"beamform: unknown keys {extra} (a dict of {sorted(BEAMFORM_DEFAULTS)})")
+        opts = dict(BEAMFORM_DEFAULTS, **beamform)
+        if opts["postfilter"] not in BEAMFORM_POSTFILTERS:
+            raise ValueError(f"beamform: postfilter must be None, 'none' or 'mask' (got {opts['postfilter']!r})")
+        return opts
+    raise ValueError(f"beamform must be None, True, a reference channel or a dict of {sorted(BEAMFORM_DEFAULTS)} "
+                     f"(got {beamform!r})")
+
+
+def beamform_item_bytes(n_fft: int, hop: int, L: int, Cn: int, n: int) -> int:
+    """The workspace one item of a [B, C, L] batch needs in dsn_beamform: the float64 partials of its owners and their
+    sum, (owners + 1) n C (C + 1) (n_fft / 2 + 1) doubles, owners = min(16, spans of L)."""
+    F, base = 1 + (L + hop - 1) // hop, (4096 if n_fft >= 2048 else 2048) // hop
+    owners = min(BEAMFORM_MAX_OWNERS, (F + base - 1) // base)
+    return 8 * (owners + 1) * n * Cn * (Cn + 1) * (n_fft // 2 + 1)
+
+
+def check_beamform(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
+                   reg=1e-3, postfilter=None, workspace_budget=0) -> tuple:
+    """The refusals of dsn_beamform (include/ditsep_hip.h), raised by name before the library is touched: mix that is
+    not [B, C, L] and est that is not [B, n, L] of the same B and L; C outside [1, 8]; what check_mask_refine refuses
+    (n, n_fft, hop, power, eps, an item too short for one reflection); reg not finite or < 0; an unknown post-filter;
+    not one channel count per item, or one outside [1, C]; ref outside [0, channels[b]) for any item; a negative
+    workspace budget or one smaller than one item.
+    -> ((B, C, n, L), lens or None, channels or None, ref, n_fft, hop, power, eps, reg, the DSN_BEAMFORM_POST_* code,
+    workspace_budget)"""
+    if postfilter not in BEAMFORM_POSTFILTERS:
+        raise ValueError(f"beamform: postfilter must be None, 'none' or 'mask' (got {postfilter!r})")
+    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
+    if len(mix_shape) != 3 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != (mix_shape[0], mix_shape[2]):
+        raise ValueError(f"beamform: mix must be [B, C, L] and est [B, n, L] of the same B and L (got {mix_shape} and "
+                         f"{est_shape})")
+    B, Cn, L = mix_shape
+    if Cn < 1 or Cn > BEAMFORM_MAX_CHANNELS:
+        raise ValueError(f"beamform: C = {Cn} outside [1, {BEAMFORM_MAX_CHANNELS}]")
+    try:
+        (_, n, _), ln, n_fft, hop, power, eps = check_mask_refine((B, L), est_shape, lens, n_fft, hop, power, eps)
+    except ValueError as e:
+        raise ValueError(str(e).replace("mask_refine:", "beamform:")) from None
+    reg = float(reg)
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError(f"beamform: reg = {reg} is not a finite number >= 0")
+    ch = None
+    if channels is not None:
+        ch = [int(v) for v in channels]
+        if len(ch) != B:
+            raise ValueError(f"beamform: channels must hold one channel count per item (B = {B}), got {len(ch)}")
+        for b, v in enumerate(ch):
+            if v < 1 or v > Cn:
+                raise ValueError(f"beamform: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    if isinstance(ref, bool) or int(ref) != ref:
+        raise ValueError(f"beamform: ref = {ref!r} is not a channel index")
+    ref = int(ref)
+    for b, v in enumerate(ch if ch is not None else [Cn]):
+        if ref < 0 or ref >= v:
+            raise ValueError(f"beamform: ref = {ref} outside [0, {v}): item {b} has {v} channels")
+    budget = int(workspace_budget)
+    if budget < 0:
+        raise ValueError(f"beamform: workspace_budget = {budget} < 0")
+    per_item = beamform_item_bytes(n_fft, hop, L, Cn, n)
+    if (budget or BEAMFORM_DEFAULT_BUDGET) < per_item:
+        raise ValueError(f"beamform: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
+                         f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L})")
+    return (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, BEAMFORM_POSTFILTERS[postfilter], budget
+
+
 ENSEMBLE_MODES = {"mean": 0, "median": 1, "best": 2, "medoid": 3}                  # DSN_ENSEMBLE_*
 ENSEMBLE_MAX_K, ENSEMBLE_MAX_SRC = 16, 4
 
@@ -1152,6 +1242,8 @@ def load_library() -> C.CDLL:
     lib.dsn_stems.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, vp, f64p,
                               f64p, vp]
     lib.dsn_pcm_encode_frames.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
+    lib.dsn_beamform.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
+                                 C.c_int64, vp, f64p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_mrstft_loss_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, C.POINTER(DsnMrstftConfig),
                                            C.POINTER(DsnMrstftOut), vp]
@@ -1959,6 +2051,59 @@ class Engine:
                                        None if ch is None else i32(*ch), code, n_fft, hop, power, eps, reg, _ptr(out),
                                        host(R), host(den), self._stream()), "dsn_stems")
         return (out, {"R": R, "den": den}) if return_info else out
+
+    # ------------------------------------------------------------------ mask-based MVDR beamforming
+    def beamform(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10, reg=1e-3,
+                 postfilter=None, workspace_budget=0, return_info=False):
+        """A microphone-array recording beamformed towards every source the mono estimates describe (dsn_beamform,
+        csrc/beamform.hip; the definition is in include/ditsep_hip.h and tests/beamform_restatement.py): mix
+        [B, C, L] (C <= 8), est [B, n, L] -> [B, n, L], every source a linear time-invariant filter of the channels.
+        The masks of `mask_refine` weight the mixture's own frames into one spatial covariance per source and bin; the
+        MVDR filter (Souden et al.) w = Z[:, ref] / tr Z, Z = (Q + lambda I)^-1 N_i with Q the other sources'
+        covariances and lambda = reg tr(Q) / C + eps, solved per bin in float64 by Cholesky, passes source i as it is
+        at channel `ref` and suppresses the others.  postfilter "mask" multiplies the beamformed spectrum with the
+        source's mask.  lens / channels (one per item): a ragged batch padded to L and C -- nothing past an item's
+        end or in a channel it does not have is read (it may hold NaN), the result is zero past the end and each item
+        gets the bits it gets alone, under any workspace_budget (bytes, 0 = 512 MiB: the items are processed in
+        chunks).  Lists (mix: [C_b, L_b] each, est: [n, L_b] each) are padded once and a list of [n, L_b] comes back.
+        return_info=True: (out, {"w": complex128 [B, n, bins, C]}) on the host.  One filter per recording (no tracking
+        of moving sources); not a trained step: what it does to separation quality is unmeasured.  Needs no score
+        network and no codec; two calls give identical bits."""
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
+                raise ValueError("beamform: a list of mixtures goes with a list of as many estimates and no lens or "
+                                 "channels")
+            ln = [int(e.shape[-1]) for e in est]
+            for b, (m, e) in enumerate(zip(mix, est)):
+                if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
+                    raise ValueError(f"beamform: item {b} must be mix [C, L] and est [n, L] (got {tuple(m.shape)} and "
+                                     f"{tuple(e.shape)})")
+            ch = [int(m.shape[0]) for m in mix]
+            Lmax = max(ln)
+            mp = torch.zeros((len(mix), max(ch), Lmax), device=self.device, dtype=torch.float32)
+            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
+            for b, (m, e) in enumerate(zip(mix, est)):
+                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
+                ep[b, :, :ln[b]] = _dev32(e, self.device)
+            res = self.beamform(mp, ep, lens=ln, channels=ch, ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps,
+                                reg=reg, postfilter=postfilter, workspace_budget=workspace_budget,
+                                return_info=return_info)
+            out = res[0] if return_info else res
+            outs = [out[b, :, :ln[b]] for b in range(len(mix))]
+            return (outs, res[1]) if return_info else outs
+        (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, post, budget = check_beamform(
+            tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg, postfilter,
+            workspace_budget)
+        mix, est = _dev32(mix, self.device), _dev32(est, self.device)
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        w = torch.zeros((B, n, n_fft // 2 + 1, Cn), dtype=torch.complex128) if return_info else None
+        i32 = C.c_int32 * B
+        self._check(self.lib.dsn_beamform(
+            self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, None if ln is None else i32(*ln),
+            None if ch is None else i32(*ch), ref, n_fft, hop, power, eps, reg, post, budget, _ptr(out),
+            None if w is None else C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_double)), self._stream()),
+            "dsn_beamform")
+        return (out, {"w": w}) if return_info else out
 
     # ------------------------------------------------------------------ K candidates -> one separation
     def ensemble_combine(self, cands, mix=None, lens=None, mode="mean", return_info=False):

@@ -86,6 +86,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stems-power", type=int, default=2, choices=[1, 2], help="Exponent of the mask magnitudes")
     p.add_argument("--stems-reg", type=float, default=1e-3,
                    help="Diagonal loading of the Wiener solve, relative to the mean channel variance")
+    p.add_argument("--beamform", action="store_true",
+                   help="Microphone-array input (up to 8 channels): separate the reference channel and beamform all "
+                        "channels towards every speaker with a mask-based MVDR filter; the outputs stay mono (not a "
+                        "trained step; off by default)")
+    p.add_argument("--beamform-ref", type=int, default=0, help="Reference channel of the beamformer")
+    p.add_argument("--beamform-nfft", type=int, default=512, help="Window of the beamformer, samples at the model's rate")
+    p.add_argument("--beamform-hop", type=int, default=128, help="Hop of the beamformer (window / 2, / 4 or / 8)")
+    p.add_argument("--beamform-reg", type=float, default=1e-3,
+                   help="Diagonal loading of the beamformer's solve, relative to the mean interference power")
+    p.add_argument("--beamform-post", default="none", choices=["none", "mask"],
+                   help="Post-filter of the beamformed spectrum: the speaker's own mask, or none")
     p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                    help="Bring every file's stems to this programme loudness (ITU-R BS.1770 / EBU R 128, measured on "
                         "the device) with one gain, e.g. -23; a gain, not a limiter (off by default)")
@@ -144,6 +155,14 @@ def stems_of(args):
                 reg=args.stems_reg)
 
 
+def beamform_of(args):
+    """The `beamform` keyword of separate_files from the parsed flags: None unless --beamform is given."""
+    if not args.beamform:
+        return None
+    return dict(ref=args.beamform_ref, n_fft=args.beamform_nfft, hop=args.beamform_hop, reg=args.beamform_reg,
+                postfilter=None if args.beamform_post == "none" else args.beamform_post)
+
+
 def loudness_of(args):
     """The `loudness` keyword of separate_files from the parsed flags: None unless --loudness is given."""
     if args.loudness is None:
@@ -187,7 +206,8 @@ def main(argv=None) -> int:
                                            rescale=args.rescale, long_after=args.long_after, window=args.window,
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
-                                           stems=stems_of(args), loudness=loudness_of(args), limit=limit_of(args),
+                                           stems=stems_of(args), beamform=beamform_of(args),
+                                           loudness=loudness_of(args), limit=limit_of(args),
                                            denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)

@@ -622,6 +622,51 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
               const int32_t* channels, int mode, int n_fft, int hop, int power, float eps, float reg, float* out,
               double* info_R, double* info_den, void* stream);
 
+/* Mask-based MVDR beamforming: a microphone-array recording and the mono estimates of its sources -> one mono signal per
+ * source, a linear time-invariant filter of the microphones that passes the source undistorted at the reference
+ * microphone and places spatial nulls on the other sources (Souden, Benesty, Affes 2010; Heymann et al. / Erdogan et
+ * al. 2016; csrc/beamform.hip, restated in float64 in tests/beamform_restatement.py).  A definition, not a trained
+ * step; nothing calls it unless asked to.  mix [B][C][Lmax], est and out [B][n][Lmax] fp32 (device), C <= 8, n <= 4.
+ * lens and channels (HOST, [B], or NULL: Lmax and C for every item): item b has lens[b] samples and C_b = channels[b]
+ * channels; nothing at or past lens[b] and no channel >= channels[b] is read (they may hold NaN), and out is zero at or
+ * past lens[b].  `ref` < C_b is the reference channel.  Padding, window, reflection, frame count F, the spectra
+ * X_c(f,t), S_i(f,t) and the fp32 masks M_i(f,t) are dsn_mask_refine's (above), with the bits they have there; spectra
+ * and masks are widened to fp64.  Per item, source i and bin f:
+ *   statistics    N_i(f) = sum_t M_i X X^H, C_b x C_b Hermitian, the upper triangle stored; products in fp64.  Every
+ *                 frame has, per source, exactly one owning workgroup, which adds its frames in increasing order
+ *                 (bins below 256 over all its frames in registers; bins 256 and up a group of 2048 / n_fft frames in
+ *                 registers, then into its partial); the owners' partials are added in owner order.  An owner takes whole spans of S / hop frames (S = 2048, 4096 for n_fft = 2048): one span, or
+ *                 ceil(spans / 16) where the item has more than 16 spans -- a function of the item's length and the
+ *                 parameters alone.
+ *   interference  Q_i(f) = sum_{j != i} N_j, added in increasing j; the zero matrix for n = 1
+ *   loading       lambda_i(f) = reg tr(Q_i) / C_b + eps,  A = Q_i + lambda I
+ *   solve         A = L L^H by fp64 Cholesky,  Z = A^-1 N_i (all C_b columns),  tau = sum_c Re Z_cc in channel order
+ *   weights       w_i(f) = Z[:, ref] / tau where tau is finite and > 0, otherwise the unit vector e_ref (tau = 0 only
+ *                 where the mixture is zero in that bin on every frame)
+ *   apply         Y_i(f,t) = sum_c conj(w_i,c) X_c in fp64 and in channel order, rounded once to fp32; with
+ *                 DSN_BEAMFORM_POST_MASK then Y_i <- (M_i Re Y_i, M_i Im Y_i), the two fp32 products of the mask mode
+ *   synthesis     dsn_mask_refine's inverse transform, overlap-add and envelope division; cropped to L
+ * The scale of N_i cancels in w, so nothing is normalised by sum_t M.  With C_b = 1, w = Z / Z = 1.0 exactly: the output
+ * of every source equals dsn_mask_refine with n = 1, and with DSN_BEAMFORM_POST_MASK dsn_mask_refine itself.  Silent
+ * estimates give n outputs that are equal to the bit.  No floating-point atomics: an item has the same bits alone, at
+ * any batch position, under any padding, from a base pointer of any 4-byte alignment, under any workspace budget and
+ * in a second call.  The partials and N ((owners + 1) n C (C + 1) (n_fft / 2 + 1) doubles per item, owners =
+ * min(16, spans of Lmax)) live in a workspace the context keeps; the batch is processed in chunks of as many items as
+ * fit `workspace_budget` bytes (0: 512 MiB); the weights (B n (n_fft / 2 + 1) C complex doubles) are kept for the whole
+ * batch outside that budget.  info_w (HOST, [B][n][n_fft / 2 + 1][C] complex as double pairs, or NULL): the weights,
+ * zero in channels an item does not have; with it the stream is synchronised.  The call uploads lens and channels
+ * when given and then synchronises the stream, so with them it must not be captured into a graph.  Needs no score
+ * network and no codec.  It computes one filter per recording (no tracking of moving sources); dual-mono input has no
+ * spatial information and gives the channel average; its effect on separation quality is unmeasured.
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_mask_refine refuses; C outside [1, 8];
+ * channels[b] outside [1, C]; ref outside [0, channels[b]) for any item (the message names the item); reg not finite or
+ * < 0; an unknown post-filter; a negative budget or one too small for one item (the message names the bytes needed);
+ * out overlapping mix or est. */
+enum { DSN_BEAMFORM_POST_NONE = 0, DSN_BEAMFORM_POST_MASK = 1 };
+int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
+                 const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
+                 int64_t workspace_budget, float* out, double* info_w, void* stream);
+
 /* Ensemble combine: K candidate separations of the same mixtures (K draws of the diffusion sampler) -> one separation
  * (csrc/ensemble.hip, restated in float64 in tests/ensemble_restatement.py).  A definition, not a trained step; nothing
  * calls it unless asked to.  cands [B][K][n][Lmax], mix [B][Lmax] or NULL, out [B][n][Lmax] fp32 (device),
