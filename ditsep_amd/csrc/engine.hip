@@ -3546,6 +3546,85 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
   });
 }
 
+// ---- WPE dereverberation (dereverb.hip; include/ditsep_hip.h states the definition)
+int dsn_dereverb(dsn_ctx* ctx, const float* mix, int B, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                 int n_fft, int hop, int taps, int delay, int iterations, float reg, float eps, int64_t workspace_budget,
+                 float* out, double* info_G, int32_t* info_fail, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_dereverb";
+    if (!mix || !out) fail(DSN_EINVAL, "%s: mix or out is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (C < 1 || C > DEREVERB_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, DEREVERB_MAX_CH);
+    if (taps < 1 || taps > DEREVERB_MAX_TAPS)
+      fail(DSN_EINVAL, "%s: taps = %d outside [1, %d]", who, taps, DEREVERB_MAX_TAPS);
+    if (delay < 1 || delay > DEREVERB_MAX_DELAY)
+      fail(DSN_EINVAL, "%s: delay = %d outside [1, %d]", who, delay, DEREVERB_MAX_DELAY);
+    if (C * taps > DEREVERB_MAX_UNKNOWNS)
+      fail(DSN_EINVAL, "%s: C taps = %d x %d = %d unknowns per bin, more than %d", who, C, taps, C * taps,
+           DEREVERB_MAX_UNKNOWNS);
+    if (iterations < 1 || iterations > DEREVERB_MAX_ITER)
+      fail(DSN_EINVAL, "%s: iterations = %d outside [1, %d]", who, iterations, DEREVERB_MAX_ITER);
+    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
+    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
+      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
+    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
+    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
+    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
+    const int need = n_fft / 2 + 1;
+    for (int b = 0; b < B; ++b) {
+      const int len = lens ? lens[b] : Lmax;
+      if (len < need || len > Lmax)
+        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
+             "reflection must reach the item)", who, b, len, need, Lmax, need);
+      const int cb = channels ? (int)channels[b] : C;
+      if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
+    }
+    if (workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)workspace_budget);
+    const size_t per_item = dereverb_item_bytes(n_fft, hop, Lmax, C, taps);
+    const size_t fit = (size_t)(workspace_budget ? workspace_budget : DEREVERB_DEFAULT_BUDGET) / per_item;
+    if (fit < 1)
+      fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at C = %d, taps = %d, "
+           "n_fft = %d, hop = %d, Lmax = %d)", who, (long)workspace_budget, (long)per_item, C, taps, n_fft, hop, Lmax);
+    const char *m0 = (const char*)mix, *o0 = (const char*)out;
+    const size_t all = sizeof(float) * (size_t)B * C * Lmax;
+    if (o0 < m0 + all && m0 < o0 + all)
+      fail(DSN_EINVAL, "%s: out overlaps mix (the analysis of one chunk of items runs after the synthesis of another)",
+           who);
+    hipStream_t st = (hipStream_t)stream;
+    const int *dlens = nullptr, *dch = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "dereverb_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    if (channels) dch = (const int*)upload_table(ctx, "dereverb_channels", channels, sizeof(int32_t) * (size_t)B, st);
+    const int ipc = (int)std::min<size_t>(fit, (size_t)B);
+    const size_t bins = (size_t)n_fft / 2 + 1, gsz = bins * C * taps * C * 2;   // doubles of G per item
+    char* ws = ctx->wsbuf<char>("dereverb_ws", per_item * ipc);
+    std::vector<int32_t> flags;
+    if (info_fail) flags.resize((size_t)ipc * bins);
+    for (int b0 = 0; b0 < B; b0 += ipc) {   // the chunk's workspace is reused from chunk to chunk on the one stream
+      const int items = std::min(ipc, B - b0);
+      ctx->prof_launch("dereverb", 8.0 * (double)items * C * Lmax, st, [&] {
+        launch_dereverb(mix + (size_t)b0 * C * Lmax, dlens ? dlens + b0 : nullptr, dch ? dch + b0 : nullptr, ws,
+                        out + (size_t)b0 * C * Lmax, items, C, Lmax, n_fft, hop, taps, delay, iterations, (double)reg,
+                        (double)eps, st);
+      });
+      HIPCHK(hipGetLastError());
+      if (info_G)   // (G is the first array of the workspace)
+        HIPCHK(hipMemcpyAsync(info_G + (size_t)b0 * gsz, ws, sizeof(double) * gsz * items, hipMemcpyDeviceToHost, st));
+      if (info_fail) {
+        const size_t Fs = (size_t)dereverb_frames(hop, Lmax), sys = (size_t)items * bins;
+        const char* failed = ws + 8 * gsz * items + sys * (8 * Fs + 16 * C * Fs);
+        HIPCHK(hipMemcpyAsync(flags.data(), failed, sizeof(int32_t) * sys, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int b = 0; b < items; ++b) {
+          int32_t count = 0;
+          for (size_t j = 0; j < bins; ++j) count += flags[(size_t)b * bins + j];
+          info_fail[b0 + b] = count;
+        }
+      }
+    }
+    if (info_G || info_fail) HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
 // ---- loudness, true peak and the gain (loudness.hip; include/ditsep_hip.h states the definition)
 int dsn_kweight_coeffs(int fs, double* out) {
   if (!out || fs < LOUD_MIN_RATE || fs > LOUD_MAX_RATE) return DSN_EINVAL;

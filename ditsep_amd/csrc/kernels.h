@@ -479,6 +479,24 @@ void launch_beamform_apply(const float* mix, const float* est, const int* lens, 
                            float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
                            int post, hipStream_t s);
 
+// ---- weighted prediction error dereverberation (dereverb.hip) ------------------------------------------------------
+// mix / out [items][C][Lmax] fp32, lens / chans [items] (device) or null.  Three launches: the frames' transforms
+// bin-major into the workspace, one workgroup per (bin, item) that runs all iterations of the K-tap, D-delay filter
+// estimate in fp64 on-die (dynamic LDS dereverb_lds_bytes of the call's own C K), and the synthesis.  `workspace` holds
+// dereverb_item_bytes per item: G [bins][C K][C] complex doubles | lambda [bins][Fs] doubles | Y, X [bins][C][Fs]
+// complex floats | failed [bins] int32, each array for all items in turn; Fs = dereverb_frames, bins = nfft / 2 + 1.
+#define DEREVERB_MAX_CH 8
+#define DEREVERB_MAX_TAPS 16
+#define DEREVERB_MAX_DELAY 8
+#define DEREVERB_MAX_UNKNOWNS 80
+#define DEREVERB_MAX_ITER 8
+#define DEREVERB_DEFAULT_BUDGET (512L << 20)
+int dereverb_frames(int hop, int Lmax);
+size_t dereverb_lds_bytes(int C, int K, int D);
+size_t dereverb_item_bytes(int nfft, int hop, int Lmax, int C, int K);
+void launch_dereverb(const float* mix, const int* lens, const int* chans, void* workspace, float* out, int items, int C,
+                     int Lmax, int nfft, int hop, int K, int D, int I, double reg, double eps, hipStream_t s);
+
 // ---- ensemble combine (ensemble.hip) -----------------------------------------------------------------------------
 // cands [B][K][n][Lmax], mix [B][Lmax] or null, out [B][n][Lmax] fp32, lens [B] (device) or null, K <= ENSEMBLE_MAX_K,
 // n <= ENSEMBLE_MAX_SRC.  Three launches: Gram partials part [B][tiles][NB][16] (4 x 4 blocks of row pairs on and above

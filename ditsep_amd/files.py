@@ -90,7 +90,7 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, loudness=None, limit=None, beamform=None, **sampler_kwargs) -> list:
+                   stems=None, loudness=None, limit=None, beamform=None, dereverb=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -108,6 +108,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     if beam is not None and stems is not None:
         raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, stems= "
                          "the mixture's channels")
+    dere = native.dereverb_options(dereverb)
     loud = native.level_options(loudness, limit)
     linked = loud is not None and loud["link"] == "mixture" and loud["target"] is not None   # the file is the source
     if long_mode not in native.LONG_MODES:
@@ -122,9 +123,9 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             if linked and beam is None and h.channels > native.LOUDNESS_MAX_CHANNELS:
                 raise ValueError(f"{p}: {h.channels} channels; loudness= with link 'mixture' measures at most "
                                  f"{native.LOUDNESS_MAX_CHANNELS} (no surround weights; link 'stem' measures the outputs)")
-    # the files' own channels are needed by the stems filter, by the beamformer and as the gain source of a
-    # mixture-linked loudness
-    keep_channels = stems is not None or beam is not None or linked
+    # the files' own channels are needed by the stems filter, by the beamformer, by the dereverberation and as the gain
+    # source of a mixture-linked loudness
+    keep_channels = stems is not None or beam is not None or dere is not None or linked
     hop = model.hop_length
     ens = {} if samples is None else dict(samples=native.check_samples(samples, combine), combine=combine)
     plan = plan_files(headers, fs, hop, files_per_batch(batch, samples), long_after)
@@ -162,6 +163,15 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 raise ValueError(f"{p}: {h.channels} channels; beamform= has ref = {ref!r} outside [0, {h.channels})")
             if v < need:
                 raise ValueError(f"{p}: {v} samples at the model's rate; beamform= needs at least n_fft / 2 + 1 = {need}")
+    if dere is not None:
+        # .. and those of the dereverberation: the parameters on a stand-in item, every file's channel count and length
+        need = native.check_dereverb((1, 1, 2049), None, None, **dere)[6] // 2 + 1
+        for p, h, v in zip(paths, headers, plan["lengths"]):
+            if h.channels > native.DEREVERB_MAX_CHANNELS:
+                raise ValueError(f"{p}: {h.channels} channels; dereverb= takes at most {native.DEREVERB_MAX_CHANNELS}")
+            native.check_dereverb((1, h.channels, 2049), None, None, **dere)
+            if v < need:
+                raise ValueError(f"{p}: {v} samples at the model's rate; dereverb= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
 
     def reference(clips):
@@ -179,10 +189,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             keys += ("reached", "evaluations", "reduction_db", "limited_samples")
         return back, [{k: info[k][j] for k in keys} for j in range(len(idx))]
 
-    def finish_stems(idx, clips, est, label):
-        """mono estimates at the model's rate -> multichannel files; `clips` the files' own channels at their own rates"""
+    def finish_stems(idx, clips, est, label, channels_fs=None):
+        """mono estimates at the model's rate -> multichannel files; `clips` the files' own channels at their own rates
+        (with dereverb=: `channels_fs` the dereverberated channels at the model's rate, which the filter then sees)"""
         hs = [headers[i] for i in idx]
-        at_fs = eng.to_model_rate(clips, [h.rate for h in hs], fs, downmix=False)
+        at_fs = channels_fs if dere is not None else eng.to_model_rate(clips, [h.rate for h in hs], fs, downmix=False)
         back = eng.stems_from_model_rate(eng.stems(at_fs, est, **stems), [h.rate for h in hs], fs,
                                          [h.frames for h in hs])
         back, levels = level(idx, clips, back)
@@ -204,6 +215,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             records[i] = {"path": paths[i], "rate": hs[j].rate, "channels": hs[j].channels, "frames": hs[j].frames,
                           "outputs": outs, "clipped": clipped[j * n:(j + 1) * n], "batch": label,
                           "stems": stems["mode"], **levels[j]}
+            if dere is not None:
+                records[i]["dereverb"] = dict(dere)
 
     def finish(idx, at_fs, est, label, clips=None, channels_fs=None):
         """estimates at the model's rate -> files; `at_fs` the mono mixtures there (with beamform=: channel `ref`, and
@@ -212,7 +225,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         if refine is not None:
             est = eng.mask_refine(at_fs, est, **refine)
         if stems is not None:
-            return finish_stems(idx, clips, est, label)
+            return finish_stems(idx, clips, est, label, channels_fs)
         if beam is not None:
             est = eng.beamform([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est), **beam)
         if rescale:
@@ -240,15 +253,23 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 rec["alpha"] = [float(a) for a in alpha[j]]
             if beam is not None:
                 rec["beamform"] = beam["ref"]
+            if dere is not None:
+                rec["dereverb"] = dict(dere)
             records[i] = dict(rec, **levels[j])
 
     def mono_at_model_rate(idx, clips):
         """what the model separates, at its rate: the downmix -- or, with beamform=, channel `ref` of all channels taken
         there with the channels kept, which come back as well"""
         rates = [headers[i].rate for i in idx]
-        if beam is None:
+        if beam is None and dere is None:
             return eng.to_model_rate(clips, rates, fs), None
         channels_fs = eng.to_model_rate(clips, rates, fs, downmix=False)
+        if dere is not None:
+            # the first waveform step: every file dereverberated whole with its channels kept; the model separates
+            # native.downmix of the result (or, with beamform=, its channel `ref`)
+            channels_fs = eng.dereverb(list(channels_fs), **dere)
+            if beam is None:
+                return [native.downmix(c[None])[0] for c in channels_fs], channels_fs
         return reference(channels_fs), channels_fs
 
     for k, idx in enumerate(plan["batches"]):

@@ -481,6 +481,71 @@ class LatentDiffSep:
             out = eng.from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
 
+    # ------------------------------------------------------------------ dereverberation (the `dereverb` keyword)
+    def _dereverb_refusals(self, dopts, shapes, rates=None, latent=False, intermediate=None):
+        """What the `dereverb` keyword refuses, before any device work: `shapes` is one (channels, samples) per item,
+        `rates` None (the model's rate) or one rate per item"""
+        if latent:
+            raise ValueError("dereverb= filters waveforms: with latent=True there is no mixture to filter")
+        if intermediate:
+            raise ValueError("dereverb= does not go with intermediate: the per-step states are not filtered")
+        most, need = native.DEREVERB_MAX_CHANNELS, int(dopts["n_fft"]) // 2 + 1
+        fs = None if rates is None else self._model_rate("dereverb=")
+        for b, (c, v) in enumerate(shapes):
+            if c < 1 or c > most:
+                raise ValueError(f"dereverb: item {b} has {c} channels, outside [1, {most}]")
+            at = v if rates is None else native.resample_length(int(rates[b]), fs, v)
+            if at < need:
+                raise ValueError(f"dereverb: item {b} has {at} samples at the model's rate; dereverb= needs at least "
+                                 f"n_fft / 2 + 1 = {need}")
+
+    @torch.no_grad()
+    def _separate_dereverb(self, mix, target_dim, sample_rate, dopts, inner_kw, kwargs):
+        """`separate` with dereverb=: mix [B, C, L] (or mono [B, L]) to the model's rate with its channels kept,
+        Engine.dereverb, the existing call there -- on native.downmix of the result, or on its channels with stems= or
+        beamform= --, the outputs back to `sample_rate`"""
+        eng = self.engine
+        if not torch.is_tensor(mix) or mix.dim() not in (2, 3):
+            raise ValueError(f"dereverb= takes mix [B, C, L] or [B, L] (got {tuple(getattr(mix, 'shape', ()))})")
+        m3 = mix[:, None] if mix.dim() == 2 else mix
+        B, Cn, L = (int(v) for v in m3.shape)
+        self._dereverb_refusals(dopts, [(Cn, L)], None if sample_rate is None else [sample_rate],
+                                intermediate=kwargs.get("intermediate"))
+        if sample_rate is None:
+            mc = native._dev32(m3, eng.device)
+        else:
+            fs = self._model_rate("sample_rate=")
+            mc = eng.resample(m3, sample_rate, fs)
+        dry = eng.dereverb(mc, **dopts)
+        keep = inner_kw.get("stems") is not None or inner_kw.get("beamform") is not None
+        est, *others = self.separate(dry if keep else native.downmix(dry), target_dim, **inner_kw, **kwargs)
+        if sample_rate is not None:
+            lead = tuple(est.shape[:-1])
+            est = eng.resample(est.reshape(B, -1, int(est.shape[-1])), fs, sample_rate)[..., :L].reshape(*lead, L)
+        return (est, *others)
+
+    @torch.no_grad()
+    def _dereverb_of_lists(self, clips, rates, dopts, keep, run):
+        """The list entry points with dereverb=: `clips` [C_b, L_b] each (or [L_b], [1, C_b, L_b]) at `rates` (None:
+        the model's rate); every clip is dereverberated whole at the model's rate (one Engine.dereverb call), and
+        run(list) -- of the results' downmixes [1, L'_b], or with `keep` (stems=, beamform=) of their channels
+        [C_b, L'_b] -- gives (the list of outputs at the model's rate, *others).  -> (the outputs at each clip's own
+        rate and sample count, *others)"""
+        eng = self.engine
+        clips = self._as_channel_clips(clips, "dereverb")
+        self._dereverb_refusals(dopts, [(int(c.shape[0]), int(c.shape[-1])) for c in clips], rates)
+        if rates is None:
+            mc = [native._dev32(c, eng.device) for c in clips]
+        else:
+            fs = self._model_rate("sample_rates=")
+            mc = eng.to_model_rate(clips, rates, fs, downmix=False)
+        dry = eng.dereverb(mc, **dopts)
+        out, *others = run(list(dry) if keep else [native.downmix(d[None])[0] for d in dry])
+        if rates is not None:
+            back = eng.stems_from_model_rate if out[0].dim() == 3 else eng.from_model_rate
+            out = back(list(out), rates, fs, [int(c.shape[-1]) for c in clips])
+        return (out, *others)
+
     # ------------------------------------------------------------------ loudness (the `loudness` keyword)
     def _loudness_refusals(self, lopts, channels, latent=False, intermediate=None):
         """What the `loudness` keyword refuses, before any device work"""
@@ -515,7 +580,7 @@ class LatentDiffSep:
 
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
-                 return_info=False, stems=None, loudness=None, limit=None, beamform=None, **kwargs):
+                 return_info=False, stems=None, loudness=None, limit=None, beamform=None, dereverb=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -567,7 +632,19 @@ class LatentDiffSep:
         channels kept, zero-extended or cut to the estimates' length) towards every source with a mask-based MVDR
         beamformer, after combine and refine and before the resampling back, loudness and limit, which see mono
         estimates as they do without the keyword; loudness with link "mixture" measures channel `ref`.  One filter
-        per recording; not a trained step.  Refused together with stems=, with latent=True and with intermediate."""
+        per recording; not a trained step.  Refused together with stems=, with latent=True and with intermediate.
+        dereverb (default None: the call returns the bits it returned before): True or a dict of taps / delay /
+        iterations / n_fft / hop / reg / eps (native.dereverb_options) -- the first waveform step: mix [B, C, L]
+        (C <= 8; mono [B, L] is one channel) goes to the model's rate with its channels kept, Engine.dereverb removes
+        the late reverberation (WPE, one filter per recording), and the call above runs on the result at the model's
+        rate with every other keyword: on native.downmix of the dereverberated channels, or -- with stems= or
+        beamform= -- on the channels themselves; the outputs go back to `sample_rate`.  loudness / limit stay the
+        last step and link "mixture" keeps measuring `mix` as given.  Not a trained step; its effect on separation
+        quality is unmeasured.  Refused with latent=True, with intermediate, with more than 8 channels and with an
+        item shorter than n_fft / 2 + 1 samples at the model's rate."""
+        dopts = native.dereverb_options(dereverb)
+        if dopts is not None and (latent or kwargs.get("intermediate")):
+            self._dereverb_refusals(dopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
         bopts = native.beamform_options(beamform)
         if bopts is not None:
             chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else []
@@ -579,7 +656,8 @@ class LatentDiffSep:
             rate = self._model_rate("loudness=") if sample_rate is None else int(sample_rate)
             inner = bool(return_info) and samples is not None
             est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
-                                         combine=combine, return_info=inner, stems=stems, beamform=beamform, **kwargs)
+                                         combine=combine, return_info=inner, stems=stems, beamform=beamform,
+                                         dereverb=dereverb, **kwargs)
             B = int(est.shape[0])
             m3 = mix[:, None] if mix.dim() == 2 else mix
             if bopts is not None:
@@ -587,6 +665,10 @@ class LatentDiffSep:
             outs, others = self._normalise(lopts, [m3[b] for b in range(B)], [est[b] for b in range(B)], rate, others,
                                            return_info, inner)
             return (torch.stack(outs), *others)
+        if dopts is not None:
+            inner_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info, stems=stems,
+                            beamform=beamform)
+            return self._separate_dereverb(mix, target_dim, sample_rate, dopts, inner_kw, kwargs)
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
@@ -644,7 +726,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
                        combine="mean", return_info=False, stems=None, loudness=None, limit=None, beamform=None,
-                       **sampler_kwargs):
+                       dereverb=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -673,8 +755,14 @@ class LatentDiffSep:
         beamform (default None: off), as in `separate`: the mixtures are array recordings [C_b, L_b] (mixed channel
         counts are fine), the call runs on channel `ref` of each, one Engine.beamform call on the padded batch filters
         every item's own channels at the model's rate, and a list of [n, L_b] comes back, each item with the bits it
-        gets alone."""
+        gets alone.
+        dereverb (default None: off), as in `separate`: the mixtures are [C_b, L_b] (or [L_b]; mixed channel counts
+        are fine), one Engine.dereverb call on the padded batch dereverberates every item at the model's rate, the
+        call above runs on the results there, and the outputs go back to every item's own rate and sample count."""
         eng = self.engine
+        dopts = native.dereverb_options(dereverb)
+        if dopts is not None and sampler_kwargs.get("intermediate"):
+            self._dereverb_refusals(dopts, [], intermediate=sampler_kwargs.get("intermediate"))
         bopts = native.beamform_options(beamform)
         if bopts is not None:
             mixes = self._as_channel_clips(list(mixes), "beamform")
@@ -690,9 +778,17 @@ class LatentDiffSep:
             inner = bool(return_info) and samples is not None
             est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
                                                samples=samples, combine=combine, return_info=inner, stems=stems,
-                                               beamform=beamform, **sampler_kwargs)
+                                               beamform=beamform, dereverb=dereverb, **sampler_kwargs)
             outs, others = self._normalise(lopts, sources, est, rates, others, return_info, inner)
             return (outs, *others)
+        if dopts is not None:
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
+            return self._dereverb_of_lists(list(mixes), rates, dopts, stems is not None or bopts is not None,
+                                           lambda at_fs: self.separate_batch(
+                at_fs, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
+                stems=stems, beamform=beamform, **sampler_kwargs))
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -759,7 +855,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
                       mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
-                      beamform=None, **sampler_kwargs):
+                      beamform=None, dereverb=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -784,8 +880,13 @@ class LatentDiffSep:
         limit (default None: off), as in `separate_batch`: every recording is limited whole.
         beamform (default None: off), as in `separate_batch`, in both modes: the recordings are [C, L_r], the call runs
         on channel `ref` of each, and every recording's channels are beamformed whole (Engine.beamform: one filter per
-        recording) at the model's rate after the stitch and refine: [n, L] or a list of [n, L_r] comes back."""
+        recording) at the model's rate after the stitch and refine: [n, L] or a list of [n, L_r] comes back.
+        dereverb (default None: off), as in `separate_batch`, in both modes: every recording [C, L_r] (or [1, L_r]) is
+        dereverberated whole at the model's rate, before any windowing, and the call above runs on the result."""
         eng = self.engine
+        dopts = native.dereverb_options(dereverb)
+        if dopts is not None and sampler_kwargs.get("intermediate"):
+            self._dereverb_refusals(dopts, [], intermediate=sampler_kwargs.get("intermediate"))
         bopts = native.beamform_options(beamform)
         if bopts is not None:
             bclips = self._as_channel_clips([mixes] if torch.is_tensor(mixes) else list(mixes), "beamform")
@@ -802,10 +903,22 @@ class LatentDiffSep:
             rates = self._model_rate("loudness=") if sample_rates is None else sample_rates
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
                                               return_info=return_info, mode=mode, sample_rates=sample_rates,
-                                              refine=refine, stems=stems, beamform=beamform, **sampler_kwargs)
+                                              refine=refine, stems=stems, beamform=beamform, dereverb=dereverb,
+                                              **sampler_kwargs)
             outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
                                            bool(return_info))
             return (outs[0] if single else outs, *others)
+        if dopts is not None:
+            single = torch.is_tensor(mixes)
+            clips = [mixes] if single else list(mixes)
+            rates = sample_rates
+            if rates is not None:
+                rates = [int(rates)] * len(clips) if isinstance(rates, int) else [int(r) for r in rates]
+            out, *others = self._dereverb_of_lists(clips, rates, dopts, stems is not None or bopts is not None,
+                                                   lambda at_fs: self.separate_long(
+                at_fs, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
+                refine=refine, stems=stems, beamform=beamform, **sampler_kwargs))
+            return (out[0] if single else out, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -889,7 +1002,7 @@ class LatentDiffSep:
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
                        samples=None, combine="mean", stems=None, loudness=None, limit=None, beamform=None,
-                       **sampler_kwargs):
+                       dereverb=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -933,13 +1046,20 @@ class LatentDiffSep:
         rescale (against channel `ref`), the resampling back, loudness (link "mixture" measures channel `ref` of the
         file) and limit as without the keyword.  The outputs stay mono `out_dir/s{i}/{stem}.wav`.  Each dict gains
         "beamform" (the reference channel).  A file with too few channels for `ref`, more than 8, or too short for one
-        reflection is refused before any device work; so is stems= together with it."""
+        reflection is refused before any device work; so is stems= together with it.
+        dereverb (default None: off, the files are the bytes they were), as in `separate`: the files are decoded with
+        their channels kept (up to 8), taken to the model's rate and dereverberated whole (Engine.dereverb, one call
+        per batch of files) before anything else; the separation runs on native.downmix of the result, stems= and
+        beamform= on its channels.  loudness with link "mixture" keeps measuring the file as given.  Each dict gains
+        "dereverb" (the options).  A file with more than 8 channels or too short for one reflection is refused
+        before any device work."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
-                                    loudness=loudness, limit=limit, beamform=beamform, **sampler_kwargs)
+                                    loudness=loudness, limit=limit, beamform=beamform, dereverb=dereverb,
+                                    **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -42,7 +42,7 @@ EXPORTS = [
     "dsn_mask_refine",
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
-    "dsn_beamform",
+    "dsn_beamform", "dsn_dereverb",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
@@ -791,6 +791,83 @@ def check_beamform(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=
     return (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, BEAMFORM_POSTFILTERS[postfilter], budget
 
 
+DEREVERB_MAX_CHANNELS, DEREVERB_MAX_TAPS, DEREVERB_MAX_DELAY, DEREVERB_MAX_UNKNOWNS, DEREVERB_MAX_ITERATIONS = 8, 16, 8, 80, 8
+DEREVERB_DEFAULT_BUDGET = 512 << 20
+# the offline recipe's usual values at 16 kHz; reg and eps are not tuned beyond the sanity runs the README names
+DEREVERB_DEFAULTS = dict(taps=10, delay=3, iterations=3, n_fft=512, hop=128, reg=1e-4, eps=1e-10)
+
+
+def dereverb_options(dereverb) -> Optional[dict]:
+    """The `dereverb` keyword of the separation entry points as Engine.dereverb's keywords: None (off, the default)
+    -> None; True -> DEREVERB_DEFAULTS; a dict of taps / delay / iterations / n_fft / hop / reg / eps -> the defaults
+    with those replaced.  Anything else, False and an unknown key included, is refused by name."""
+    if dereverb is None:
+        return None
+    if dereverb is True:
+        return dict(DEREVERB_DEFAULTS)
+    if isinstance(dereverb, Mapping):
+        extra = sorted(set(dereverb) - set(DEREVERB_DEFAULTS))
+        if extra:
+            raise ValueError(f"dereverb: unknown keys {extra} (a dict of {sorted(DEREVERB_DEFAULTS)})")
+        return dict(DEREVERB_DEFAULTS, **dereverb)
+    raise ValueError(f"dereverb must be None, True or a dict of {sorted(DEREVERB_DEFAULTS)} (got {dereverb!r})")
+
+
+def dereverb_item_bytes(n_fft: int, hop: int, L: int, Cn: int, taps: int) -> int:
+    """The workspace one item of a [B, C, L] batch needs in dsn_dereverb: per bin the filter (C taps x C complex
+    doubles), lambda (Fs doubles), the spectra and the result (C x Fs complex floats each) and a flag, Fs = 1 +
+    ceil(L / hop) frames.  The one formula: the C side computes the same number."""
+    bins, Fs = n_fft // 2 + 1, 1 + (L + hop - 1) // hop
+    return bins * (8 * (2 * Cn * taps * Cn + Fs + 2 * Cn * Fs) + 4)
+
+
+def check_dereverb(mix_shape, lens=None, channels=None, taps=10, delay=3, iterations=3, n_fft=512, hop=128, reg=1e-4,
+                   eps=1e-10, workspace_budget=0) -> tuple:
+    """The refusals of dsn_dereverb (include/ditsep_hip.h), raised by name before the library is touched: mix that is
+    not [B, C, L]; C outside [1, 8]; taps outside [1, 16]; delay outside [1, 8]; C taps > 80; iterations outside
+    [1, 8]; what check_mask_refine refuses (n_fft, hop, eps, an item too short for one reflection); reg not finite or
+    < 0; not one channel count per item, or one outside [1, C]; a negative workspace budget or one smaller than one
+    item.
+    -> ((B, C, L), lens or None, channels or None, taps, delay, iterations, n_fft, hop, reg, eps, workspace_budget)"""
+    mix_shape = tuple(int(v) for v in mix_shape)
+    if len(mix_shape) != 3:
+        raise ValueError(f"dereverb: mix must be [B, C, L] (got {mix_shape})")
+    B, Cn, L = mix_shape
+    if Cn < 1 or Cn > DEREVERB_MAX_CHANNELS:
+        raise ValueError(f"dereverb: C = {Cn} outside [1, {DEREVERB_MAX_CHANNELS}]")
+    for name, v, top in (("taps", taps, DEREVERB_MAX_TAPS), ("delay", delay, DEREVERB_MAX_DELAY),
+                         ("iterations", iterations, DEREVERB_MAX_ITERATIONS)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= top:
+            raise ValueError(f"dereverb: {name} = {v!r} outside [1, {top}]")
+    taps, delay, iterations = int(taps), int(delay), int(iterations)
+    if Cn * taps > DEREVERB_MAX_UNKNOWNS:
+        raise ValueError(f"dereverb: C taps = {Cn} x {taps} = {Cn * taps} unknowns per bin, more than "
+                         f"{DEREVERB_MAX_UNKNOWNS}")
+    try:
+        _, ln, n_fft, hop, _, eps = check_mask_refine((B, L), (B, 1, L), lens, n_fft, hop, 2, eps)
+    except ValueError as e:
+        raise ValueError(str(e).replace("mask_refine:", "dereverb:")) from None
+    reg = float(reg)
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError(f"dereverb: reg = {reg} is not a finite number >= 0")
+    ch = None
+    if channels is not None:
+        ch = [int(v) for v in channels]
+        if len(ch) != B:
+            raise ValueError(f"dereverb: channels must hold one channel count per item (B = {B}), got {len(ch)}")
+        for b, v in enumerate(ch):
+            if v < 1 or v > Cn:
+                raise ValueError(f"dereverb: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    budget = 0 if workspace_budget is None else int(workspace_budget)
+    if budget < 0:
+        raise ValueError(f"dereverb: workspace_budget = {budget} < 0")
+    per_item = dereverb_item_bytes(n_fft, hop, L, Cn, taps)
+    if (budget or DEREVERB_DEFAULT_BUDGET) < per_item:
+        raise ValueError(f"dereverb: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
+                         f"C = {Cn}, taps = {taps}, n_fft = {n_fft}, hop = {hop}, L = {L})")
+    return (B, Cn, L), ln, ch, taps, delay, iterations, n_fft, hop, reg, eps, budget
+
+
 ENSEMBLE_MODES = {"mean": 0, "median": 1, "best": 2, "medoid": 3}                  # DSN_ENSEMBLE_*
 ENSEMBLE_MAX_K, ENSEMBLE_MAX_SRC = 16, 4
 
@@ -1244,6 +1321,8 @@ def load_library() -> C.CDLL:
     lib.dsn_pcm_encode_frames.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
     lib.dsn_beamform.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
                                  C.c_int64, vp, f64p, vp]
+    lib.dsn_dereverb.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, ci, C.c_float, C.c_float, C.c_int64, vp,
+                                 f64p, i32p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
     lib.dsn_mrstft_loss_ragged.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, C.POINTER(DsnMrstftConfig),
                                            C.POINTER(DsnMrstftOut), vp]
@@ -2104,6 +2183,54 @@ class Engine:
             None if w is None else C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_double)), self._stream()),
             "dsn_beamform")
         return (out, {"w": w}) if return_info else out
+
+    # ------------------------------------------------------------------ WPE dereverberation
+    def dereverb(self, mix, lens=None, channels=None, taps=10, delay=3, iterations=3, n_fft=512, hop=128, reg=1e-4,
+                 eps=1e-10, workspace_budget=None, return_info=False):
+        """The channels of a reverberant recording with their late reverberation removed (dsn_dereverb,
+        csrc/dereverb.hip; the definition is in include/ditsep_hip.h and tests/dereverb_restatement.py): mix [B, C, L]
+        (C <= 8) -> [B, C, L].  Weighted prediction error: per bin a filter G over `taps` frames of all channels,
+        `delay` frames back, is estimated in float64 against the time-varying power lambda(t) of the current estimate
+        (R = sum y~ y~^H / lambda, P = sum y~ Y^H / lambda, G = (R + delta I)^-1 P by Cholesky, delta = reg tr(R) /
+        (C taps) + eps) and its prediction subtracted, `iterations` times; C taps <= 80.  Analysis and synthesis are
+        mask_refine's.  lens / channels (one per item): a ragged batch padded to L and C -- nothing past an item's end
+        or in a channel it does not have is read (it may hold NaN), the result is zero there and each item gets the
+        bits it gets alone, under any workspace_budget (bytes, None or 0 = 512 MiB: the items are processed in chunks
+        of native.dereverb_item_bytes each).  A list of [C_b, L_b] is padded once and a list of [C_b, L_b] comes back.
+        return_info=True: (out, {"G": complex128 [B, bins, C taps, C], the last iteration's filter, "fail": int32 [B],
+        the bins that passed through because a pivot failed}) on the host.  Offline, one filter per recording; not a
+        trained step: what it does to separation quality is unmeasured.  Needs no score network and no codec; two
+        calls give identical bits."""
+        kw = dict(taps=taps, delay=delay, iterations=iterations, n_fft=n_fft, hop=hop, reg=reg, eps=eps,
+                  workspace_budget=workspace_budget, return_info=return_info)
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or channels is not None:
+                raise ValueError("dereverb: a list of mixtures goes with no lens or channels")
+            for b, m in enumerate(mix):
+                if m.dim() != 2:
+                    raise ValueError(f"dereverb: item {b} must be [C, L] (got {tuple(m.shape)})")
+            ln, ch = [int(m.shape[-1]) for m in mix], [int(m.shape[0]) for m in mix]
+            mp = torch.zeros((len(mix), max(ch), max(ln)), device=self.device, dtype=torch.float32)
+            for b, m in enumerate(mix):
+                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
+            res = self.dereverb(mp, lens=ln, channels=ch, **kw)
+            out = res[0] if return_info else res
+            outs = [out[b, :ch[b], :ln[b]] for b in range(len(mix))]
+            return (outs, res[1]) if return_info else outs
+        (B, Cn, L), ln, ch, taps, delay, iterations, n_fft, hop, reg, eps, budget = check_dereverb(
+            tuple(mix.shape), lens, channels, taps, delay, iterations, n_fft, hop, reg, eps, workspace_budget)
+        mix = _dev32(mix, self.device)
+        out = torch.empty((B, Cn, L), device=self.device, dtype=torch.float32)
+        G = torch.zeros((B, n_fft // 2 + 1, Cn * taps, Cn), dtype=torch.complex128) if return_info else None
+        fail = torch.zeros((B,), dtype=torch.int32) if return_info else None
+        i32 = C.c_int32 * B
+        self._check(self.lib.dsn_dereverb(
+            self.ctx, _ptr(mix), B, Cn, L, None if ln is None else i32(*ln), None if ch is None else i32(*ch), n_fft,
+            hop, taps, delay, iterations, reg, eps, budget, _ptr(out),
+            None if G is None else C.cast(C.c_void_p(G.data_ptr()), C.POINTER(C.c_double)),
+            None if fail is None else C.cast(C.c_void_p(fail.data_ptr()), C.POINTER(C.c_int32)), self._stream()),
+            "dsn_dereverb")
+        return (out, {"G": G, "fail": fail}) if return_info else out
 
     # ------------------------------------------------------------------ K candidates -> one separation
     def ensemble_combine(self, cands, mix=None, lens=None, mode="mean", return_info=False):

@@ -97,6 +97,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Diagonal loading of the beamformer's solve, relative to the mean interference power")
     p.add_argument("--beamform-post", default="none", choices=["none", "mask"],
                    help="Post-filter of the beamformed spectrum: the speaker's own mask, or none")
+    p.add_argument("--dereverb", action="store_true",
+                   help="Dereverberate every recording first (weighted prediction error on up to 8 channels, kept for "
+                        "the steps that use them; not a trained step; off by default)")
+    p.add_argument("--dereverb-taps", type=int, default=10, help="Frames of the prediction filter")
+    p.add_argument("--dereverb-delay", type=int, default=3, help="Frames between the predicted frame and the filter's first")
+    p.add_argument("--dereverb-iterations", type=int, default=3, help="Re-estimations of the variance and the filter")
+    p.add_argument("--dereverb-nfft", type=int, default=512, help="Window of the dereverberation, samples at the model's rate")
+    p.add_argument("--dereverb-hop", type=int, default=128, help="Hop of the dereverberation (window / 2, / 4 or / 8)")
+    p.add_argument("--dereverb-reg", type=float, default=1e-4,
+                   help="Diagonal loading of the filter's solve, relative to the mean diagonal of the correlation matrix")
     p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                    help="Bring every file's stems to this programme loudness (ITU-R BS.1770 / EBU R 128, measured on "
                         "the device) with one gain, e.g. -23; a gain, not a limiter (off by default)")
@@ -163,6 +173,14 @@ def beamform_of(args):
                 postfilter=None if args.beamform_post == "none" else args.beamform_post)
 
 
+def dereverb_of(args):
+    """The `dereverb` keyword of separate_files from the parsed flags: None unless --dereverb is given."""
+    if not args.dereverb:
+        return None
+    return dict(taps=args.dereverb_taps, delay=args.dereverb_delay, iterations=args.dereverb_iterations,
+                n_fft=args.dereverb_nfft, hop=args.dereverb_hop, reg=args.dereverb_reg)
+
+
 def loudness_of(args):
     """The `loudness` keyword of separate_files from the parsed flags: None unless --loudness is given."""
     if args.loudness is None:
@@ -207,6 +225,7 @@ def main(argv=None) -> int:
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
                                            stems=stems_of(args), beamform=beamform_of(args),
+                                           dereverb=dereverb_of(args),
                                            loudness=loudness_of(args), limit=limit_of(args),
                                            denoise=args.denoise, **kw)
         except ValueError as e:

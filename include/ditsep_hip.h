@@ -667,6 +667,49 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
                  const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
                  int64_t workspace_budget, float* out, double* info_w, void* stream);
 
+/* Weighted prediction error (WPE) dereverberation: the channels of a reverberant recording in, the same channels with
+ * the late reverberation predicted from their own delayed past and subtracted out (Nakatani et al. 2010; Yoshioka &
+ * Nakatani 2012; the offline recipe; csrc/dereverb.hip, restated in float64 in tests/dereverb_restatement.py).  A
+ * definition, not a trained step; nothing calls it unless asked to.  mix and out [B][C][Lmax] fp32 (device), C <= 8,
+ * taps K in [1, 16], delay D in [1, 8], C K <= 80, iterations I in [1, 8].  lens and channels (HOST, [B], or NULL: Lmax
+ * and C for every item): item b has L_b = lens[b] samples and C_b = channels[b] channels; nothing at or past lens[b]
+ * and no channel >= channels[b] is read (they may hold NaN), and out is zero there.  Padding, window, reflection, frame
+ * count F and the spectra Y_c(f,t) are dsn_mask_refine's (above), with the bits they have there, widened to fp64.  Per
+ * item and bin f, all in fp64:
+ *   stacked past  y~(t) in C^(C_b K), entry k C_b + c = Y_c(f, t - D - k), zero where t - D - k < 0
+ *   start         X = Y
+ *   I times       lambda(t) = (1 / C_b) sum_c |X_c(t)|^2 in channel order;  m = max_t lambda(t), taken as an integer
+ *                 maximum on the bits (exact in any order);  lambda(t) <- max(lambda(t), 1e-10 m);  where m == 0 the bin
+ *                 passes through (G = 0).
+ *                 R = sum_t y~ y~^H / lambda(t) (Hermitian, one triangle kept),  P = sum_t y~ Y(t)^H / lambda(t)
+ *                 (C_b K x C_b), both added in increasing t whatever the tiling: y~_i / lambda(t) is formed first (a
+ *                 multiplication with the quotient 1 / lambda(t)), then the product.
+ *                 delta = reg tr(R) / (C_b K) + eps,  A = R + delta I = L L^H by Cholesky,  G = A^-1 P.  A pivot that is
+ *                 not finite and positive sets G = 0 for this and the remaining iterations of that bin; the bin is
+ *                 counted.
+ *                 X_c(t) = Y_c(t) - sum_j conj(G[j][c]) y~_j(t) in index order
+ *   after the last iteration X is rounded once to fp32; synthesis is dsn_mask_refine's: the inverse transform, the
+ *   overlap-add, the envelope division, cropped to L_b.
+ * Consequences.  No floating-point atomics: an item has the same bits alone, at any batch position, under any padding,
+ * from a base pointer of any 4-byte alignment, under any workspace budget and in a second call.  An item with F <= D
+ * has P = 0 exactly, so G = 0 and X = Y: every channel comes back as dsn_mask_refine of that channel with n = 1, bit
+ * for bit; so does a silent item.  Scaling the input by a power of two scales lambda by its square and leaves R, P,
+ * delta and G bit-identical: dereverb(2^k x) = 2^k dereverb(x) to the bit, away from under- and overflow.
+ * The spectra, X, lambda, G and the per-bin flags of a chunk of items live in a workspace the context keeps,
+ * (n_fft / 2 + 1) (8 (2 C^2 K + Fs + 2 C Fs) + 4) bytes per item with Fs = 1 + ceil(Lmax / hop); the batch is processed
+ * in chunks of as many items as fit `workspace_budget` bytes (0: 512 MiB).  info_G (HOST, [B][n_fft / 2 + 1][C K][C]
+ * complex as double pairs, or NULL): the last iteration's filter, row k C_b + c of the item's own system, zero outside
+ * it.  info_fail (HOST, [B] int32, or NULL): the bins of the item that passed through because of a failed pivot.  With
+ * either one the stream is synchronised.  The call uploads lens and channels when given and then synchronises the
+ * stream, so with them it must not be captured into a graph.  Needs no score network and no codec.  Offline: one
+ * filter per recording, no PSD context, no recursive form; its effect on separation quality is unmeasured.
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_mask_refine refuses; C, taps, delay, C taps or
+ * iterations outside the limits above; channels[b] outside [1, C]; reg not finite or < 0; eps not finite or <= 0; a
+ * negative budget or one too small for one item (the message names the bytes needed); out overlapping mix. */
+int dsn_dereverb(dsn_ctx* ctx, const float* mix, int B, int C, int Lmax, const int32_t* lens, const int32_t* channels,
+                 int n_fft, int hop, int taps, int delay, int iterations, float reg, float eps, int64_t workspace_budget,
+                 float* out, double* info_G, int32_t* info_fail, void* stream);
+
 /* Ensemble combine: K candidate separations of the same mixtures (K draws of the diffusion sampler) -> one separation
  * (csrc/ensemble.hip, restated in float64 in tests/ensemble_restatement.py).  A definition, not a trained step; nothing
  * calls it unless asked to.  cands [B][K][n][Lmax], mix [B][Lmax] or NULL, out [B][n][Lmax] fp32 (device),
