@@ -1,8 +1,9 @@
 // Mask-based MVDR beamforming (dsn_beamform; the definition is in include/ditsep_hip.h, restated in float64 in
 // tests/beamform_restatement.py): the masks of the mono estimates give one spatial covariance per source and bin from
 // the mixture's own channels, and a minimum-variance distortionless-response filter (Souden, Benesty, Affes 2010)
-// returns one mono signal per source.  Frames, spectra and masks are formed by the code of maskrefine.hip
-// (maskrefine_dev.h), so they have the bits they have there.  Three launches per chunk of items, then one for the batch:
+// returns one mono signal per source.  Frames, spectra, masks and output samples are formed by the functions of
+// maskrefine_dev.h that maskrefine.hip calls (mr_tables, mr_load, mr_fft, mr_split, mr_masks, mr_merge, mr_add,
+// mr_finish), so they have the bits they have there.  Three launches per chunk of items, then one for the batch:
 //   stats    workgroup (o, b, i) owns the frames [o fpo, (o + 1) fpo) of item b for source i -- every frame has exactly
 //            one owner per source; fpo is a whole number of spans, more than one where the item has more than
 //            BEAMFORM_MAX_OWNERS spans --, transforms the item's C_b channels and n estimates in groups of
@@ -30,9 +31,6 @@ namespace {
 constexpr int BF_MAX_CH = BEAMFORM_MAX_CH;
 constexpr int BF_TRI = BF_MAX_CH * (BF_MAX_CH + 1) / 2;                          // Hermitian entries held in registers
 constexpr int BF_BF = (BF_MAX_CH + MR_MAX_SRC) * (MR_POINTS / 2) / MRT;          // butterflies per thread and stage
-// output samples a workgroup of the apply launch owns, and the frames of one owner's span: maskrefine.hip's spans
-template <int NFFT>
-constexpr int bf_span() { return NFFT >= 2048 ? 4096 : 2048; }
 constexpr int BF_LANES = 8, BF_GROUPS = MRT / BF_LANES;                          // weights launch: lanes per system
 
 __host__ __device__ inline int bf_tri(int C) { return C * (C + 1) / 2; }
@@ -43,40 +41,6 @@ __host__ __device__ inline int bf_idx(int C, int c1, int c2) { return c1 * C - c
 __host__ __device__ inline int bf_owner_frames(int F, int base) {
   const int spans = (F + base - 1) / base;
   return base * ((spans + BEAMFORM_MAX_OWNERS - 1) / BEAMFORM_MAX_OWNERS);
-}
-
-// The load of maskrefine.hip: slot fg of signal s holds frame f0 + fg, even samples in .x and odd in .y, windowed;
-// signals 0 .. nx - 1 are the mixture's channels, then ne estimates.
-template <int H>
-__device__ __forceinline__ void bf_load(float2* buf, const float* win, const float* mixb, const float* estb, int Lmax,
-                                        int L, int Lp, int hop, int nx, int ne, int f0, int f_last, int tid) {
-  constexpr int LOGH = __builtin_ctz(H), G = MR_POINTS / H;
-  for (int e = tid; e < G * H; e += MRT) {
-    const int fg = e >> LOGH, tp = e & (H - 1), f = f0 + fg;
-    const bool valid = f <= f_last;
-    int i0 = f * hop - H + 2 * tp, i1 = i0 + 1;   // (f hop <= Lp: no overflow)
-    i0 = i0 < 0 ? -i0 : i0;
-    i1 = i1 < 0 ? -i1 : i1;
-    i0 = i0 >= Lp ? 2 * (Lp - 1) - i0 : i0;   // Lp > H: one reflection reaches [0, Lp)
-    i1 = i1 >= Lp ? 2 * (Lp - 1) - i1 : i1;
-    const float w0 = win[2 * tp], w1 = win[2 * tp + 1];
-    for (int s = 0; s < nx + ne; ++s) {
-      const float* row = s < nx ? mixb + (long)s * Lmax : estb + (long)(s - nx) * Lmax;
-      const float v0 = valid && i0 < L ? row[i0] : 0.f;
-      const float v1 = valid && i1 < L ? row[i1] : 0.f;
-      buf[(s * G + fg) * H + tp] = make_float2(v0 * w0, v1 * w1);
-    }
-  }
-}
-
-template <int H>
-__device__ __forceinline__ void bf_tables(float2* tw, float* win, int tid) {
-  for (int t = tid; t < H; t += MRT) {
-    double s, c;
-    sincospi((double)t / H, &s, &c);   // exp(-2 pi i t / NFFT)
-    tw[t] = make_float2((float)c, (float)-s);
-  }
-  for (int t = tid; t < 2 * H; t += MRT) win[t] = (float)(0.5 - 0.5 * cospi((double)t / H));   // periodic Hann
 }
 
 // Source `src`, bin j: rows [R0, R1) of M_src X X^H (upper triangle, X_c1 conj X_c2) of the `frames` frames in LDS,
@@ -150,12 +114,12 @@ __global__ __launch_bounds__(MRT) void beamform_stats_kernel(const MaskRefineSha
                                                              const float* __restrict__ est,
                                                              const int* __restrict__ lens, const int* __restrict__ chans,
                                                              double* __restrict__ part) {
-  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = bf_span<NFFT>();
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = mr_span(NFFT);
   extern __shared__ __attribute__((aligned(16))) float2 bf_lds[];
   const int n = q.n, hop = q.hop, tid = threadIdx.x, b = blockIdx.y, src = blockIdx.z;
   const int Cb = chans ? chans[b] : q.C;
-  const int L = lens ? lens[b] : q.Lmax;
-  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const MrItem it = mr_item(lens, b, q.Lmax, hop);
+  const int F = it.F;
   const int fpo = bf_owner_frames(F, SPAN / hop);
   if ((long)blockIdx.x * fpo >= F) return;   // (uniform)
   float2* tw = bf_lds;
@@ -163,7 +127,7 @@ __global__ __launch_bounds__(MRT) void beamform_stats_kernel(const MaskRefineSha
   float* win = reinterpret_cast<float*>(buf + (q.C + n) * MR_POINTS);
   const float* mixb = mix + (long)b * q.C * q.Lmax;
   const float* estb = est + (long)b * n * q.Lmax;
-  bf_tables<H>(tw, win, tid);
+  mr_tables<H>(tw, win, tid);
   const int f_first = blockIdx.x * fpo, f_last = min(F, f_first + fpo) - 1;
   const int T2 = 2 * bf_tri(q.C);
   double* partw = part + (((long)b * gridDim.x + blockIdx.x) * n + src) * T2 * (H + 1);
@@ -173,7 +137,7 @@ __global__ __launch_bounds__(MRT) void beamform_stats_kernel(const MaskRefineSha
 
   for (int f0 = f_first; f0 <= f_last; f0 += G) {
     __syncthreads();   // the tables are in; the previous group's spectra have been read
-    bf_load<H>(buf, win, mixb, estb, q.Lmax, L, Lp, hop, Cb, n, f0, f_last, tid);
+    mr_load<H>(buf, win, mixb, estb, q.Lmax, it, hop, Cb, n, f0, f_last, tid);
     __syncthreads();
     mr_fft<H, false, BF_BF>(buf, tw, (Cb + n) * (MR_POINTS / 2), tid);
     const int frames = min(G, f_last - f0 + 1);
@@ -355,9 +319,9 @@ __global__ __launch_bounds__(MRT) void beamform_apply_kernel(const MaskRefineSha
                                                              const float* __restrict__ est,
                                                              const int* __restrict__ lens, const int* __restrict__ chans,
                                                              const double* __restrict__ w, float* __restrict__ out) {
-  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = bf_span<NFFT>();
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = mr_span(NFFT);
   extern __shared__ __attribute__((aligned(16))) float2 bf_lds[];
-  const int n = q.n, hop = q.hop, r = NFFT / hop, tid = threadIdx.x;
+  const int n = q.n, hop = q.hop, tid = threadIdx.x;
   const int b = blockIdx.y, src = blockIdx.z, s0 = blockIdx.x * SPAN;
   const int Cb = chans ? chans[b] : q.C;
   const int ne = post ? n : 0;
@@ -365,29 +329,25 @@ __global__ __launch_bounds__(MRT) void beamform_apply_kernel(const MaskRefineSha
   float2* buf = tw + H;
   float* win = reinterpret_cast<float*>(buf + (q.C + ne) * MR_POINTS);
   float* ola = win + NFFT;
-  const int L = lens ? lens[b] : q.Lmax;
-  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const MrItem it = mr_item(lens, b, q.Lmax, hop);
   const float* mixb = mix + (long)b * q.C * q.Lmax;
   const float* estb = est + (long)b * n * q.Lmax;
   float* outb = out + ((long)b * n + src) * q.Lmax;
 
-  if (s0 >= L) {   // (uniform) past the item's end
-    for (int v = tid; v < SPAN / 4; v += MRT)
-      if (s0 + 4 * v < q.Lmax) mr_store(q, outb, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
+  if (s0 >= it.L) {   // (uniform) past the item's end
+    mr_zero<H>(outb, 0, 1, s0, q.Lmax, q.vec, tid);
     return;
   }
-  bf_tables<H>(tw, win, tid);
+  mr_tables<H>(tw, win, tid);
   for (int e = tid; e < SPAN; e += MRT) ola[e] = 0.f;
 
-  // sample p is covered by the r frames (p + H) / hop - r + 1 .. (p + H) / hop, where they exist
-  const int pend = min(s0 + SPAN, L);
-  const int f_first = max(0, (s0 + H) / hop - r + 1), f_last = min(F - 1, (pend - 1 + H) / hop);
-  const float inv_n = 1.f / (float)NFFT;   // mr_merge hands back twice the packed transform: 1 / (2 H)
+  const MrFrames fr = mr_frames<H>(it, s0, hop);
+  const int f_first = fr.f_first, f_last = fr.f_last;
   const double* wb = w + 2L * ((long)b * n + src) * (H + 1) * q.C;   // bin j, channel c: wb[2 (j C + c)]
 
   for (int f0 = f_first; f0 <= f_last; f0 += G) {
     __syncthreads();   // the tables are in; the previous group's frames have been added
-    bf_load<H>(buf, win, mixb, estb, q.Lmax, L, Lp, hop, Cb, ne, f0, f_last, tid);
+    mr_load<H>(buf, win, mixb, estb, q.Lmax, it, hop, Cb, ne, f0, f_last, tid);
     __syncthreads();
     mr_fft<H, false, BF_BF>(buf, tw, (Cb + ne) * (MR_POINTS / 2), tid);
     // ---- contract: one thread per (frame, pair of bins k and H - k); channel 0's slot becomes Y, packed again
@@ -429,58 +389,9 @@ __global__ __launch_bounds__(MRT) void beamform_apply_kernel(const MaskRefineSha
     }
     __syncthreads();
     mr_fft<H, true, BF_BF>(buf, tw, MR_POINTS / 2, tid);
-    // ---- add: a thread owns quads of samples for the whole launch, so every sample's sum runs in frame order
-    const int g_last = min(f0 + G - 1, f_last);
-    const float* y = reinterpret_cast<const float*>(buf);
-    for (int v = tid; v < SPAN / 4; v += MRT) {
-      const int p = s0 + 4 * v;
-      if (p >= pend) continue;
-      const int fhi = (p + H) / hop;   // (hop % 4 == 0: the same frames cover the whole quad)
-      const int fa = max(fhi - r + 1, f0), fb = min(fhi, g_last);
-      float4 acc = *reinterpret_cast<float4*>(ola + 4 * v);
-      for (int f = fa; f <= fb; ++f) {
-        const int t = p + H - f * hop;
-        const float4 yv = *reinterpret_cast<const float4*>(y + (f - f0) * NFFT + t);
-        const float4 wv = *reinterpret_cast<const float4*>(win + t);
-        acc.x = acc.x + (yv.x * inv_n) * wv.x;
-        acc.y = acc.y + (yv.y * inv_n) * wv.y;
-        acc.z = acc.z + (yv.z * inv_n) * wv.z;
-        acc.w = acc.w + (yv.w * inv_n) * wv.w;
-      }
-      *reinterpret_cast<float4*>(ola + 4 * v) = acc;
-    }
+    mr_add<H>(ola, buf, win, s0, fr.pend, hop, f0, min(f0 + G - 1, f_last), tid);
   }
-
-  // ---- the envelope of the frames that exist, the division and the store (the quads this thread summed itself)
-  for (int v = tid; v < SPAN / 4; v += MRT) {
-    const int p = s0 + 4 * v;
-    if (p >= q.Lmax) continue;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < pend) {
-      float env[4] = {0.f, 0.f, 0.f, 0.f};
-      const int fhi = (p + H) / hop;
-      const int fa = max(fhi - r + 1, 0), fb = min(fhi, F - 1);
-      for (int f = fa; f <= fb; ++f) {
-        const float4 wv = *reinterpret_cast<const float4*>(win + (p + H - f * hop));
-        env[0] = env[0] + wv.x * wv.x;
-        env[1] = env[1] + wv.y * wv.y;
-        env[2] = env[2] + wv.z * wv.z;
-        env[3] = env[3] + wv.w * wv.w;
-      }
-      const float4 acc = *reinterpret_cast<const float4*>(ola + 4 * v);
-      o.x = acc.x / env[0];
-      o.y = p + 1 < L ? acc.y / env[1] : 0.f;
-      o.z = p + 2 < L ? acc.z / env[2] : 0.f;
-      o.w = p + 3 < L ? acc.w / env[3] : 0.f;
-    }
-    mr_store(q, outb, p, o);
-  }
-}
-
-template <int NFFT>
-size_t bf_lds_bytes(int slots, bool ola) {
-  return sizeof(float2) * ((size_t)NFFT / 2 + (size_t)slots * MR_POINTS) +
-         sizeof(float) * ((size_t)NFFT + (ola ? (size_t)bf_span<NFFT>() : 0));
+  mr_finish<H>(ola, win, outb, 0, 1, it, s0, fr.pend, hop, q.Lmax, q.vec, tid);
 }
 
 struct BfArgs {
@@ -495,12 +406,12 @@ struct BfArgs {
 
 template <int NFFT>
 void bf_run(int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st) {
-  constexpr int SPAN = bf_span<NFFT>();
+  constexpr int SPAN = mr_span(NFFT);
   const int bins = NFFT / 2 + 1, T2 = 2 * bf_tri(q.C), OW = beamform_owners(NFFT, q.hop, q.Lmax);
   if (stage == 0) {
-    dsn_allow_lds<beamform_stats_kernel<NFFT>>((int)bf_lds_bytes<NFFT>(BF_MAX_CH + MR_MAX_SRC, false));
+    dsn_allow_lds<beamform_stats_kernel<NFFT>>((int)mr_lds_bytes(NFFT, BF_MAX_CH + MR_MAX_SRC, 0));
     hipLaunchKernelGGL((beamform_stats_kernel<NFFT>), dim3((unsigned)OW, (unsigned)a.items, (unsigned)q.n), dim3(MRT),
-                       bf_lds_bytes<NFFT>(q.C + q.n, false), st, q, a.mix, a.est, a.lens, a.chans, a.part);
+                       mr_lds_bytes(NFFT, q.C + q.n, 0), st, q, a.mix, a.est, a.lens, a.chans, a.part);
     const long rows = (long)a.items * q.n * T2 * bins;
     hipLaunchKernelGGL(beamform_reduce_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, a.part,
                        a.lens, a.chans, a.items, q.n, q.C, q.Lmax, bins, q.hop, SPAN / q.hop, OW, a.N);
@@ -510,27 +421,20 @@ void bf_run(int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st
     return;
   }
   const int slots = q.C + (a.post ? q.n : 0);
-  dsn_allow_lds<beamform_apply_kernel<NFFT>>((int)bf_lds_bytes<NFFT>(BF_MAX_CH + MR_MAX_SRC, true));
+  dsn_allow_lds<beamform_apply_kernel<NFFT>>((int)mr_lds_bytes(NFFT, BF_MAX_CH + MR_MAX_SRC, 1));
   hipLaunchKernelGGL((beamform_apply_kernel<NFFT>),
                      dim3((unsigned)((q.Lmax + SPAN - 1) / SPAN), (unsigned)a.items, (unsigned)q.n), dim3(MRT),
-                     bf_lds_bytes<NFFT>(slots, true), st, q, a.post, a.mix, a.est, a.lens, a.chans, a.w, a.out);
+                     mr_lds_bytes(NFFT, slots, 1), st, q, a.post, a.mix, a.est, a.lens, a.chans, a.w, a.out);
 }
 
 void bf_dispatch(int nfft, int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st) {
-  switch (nfft) {
-    case 64: bf_run<64>(stage, q, a, st); break;
-    case 128: bf_run<128>(stage, q, a, st); break;
-    case 256: bf_run<256>(stage, q, a, st); break;
-    case 512: bf_run<512>(stage, q, a, st); break;
-    case 1024: bf_run<1024>(stage, q, a, st); break;
-    default: bf_run<2048>(stage, q, a, st); break;
-  }
+  mr_for_nfft(nfft, [&](auto N) { bf_run<decltype(N)::value>(stage, q, a, st); });
 }
 
 }  // namespace
 
 int beamform_owners(int nfft, int hop, int Lmax) {
-  const int F = 1 + (Lmax + hop - 1) / hop, base = (nfft >= 2048 ? bf_span<2048>() : bf_span<64>()) / hop;
+  const int F = 1 + (Lmax + hop - 1) / hop, base = mr_span(nfft) / hop;
   return std::min(BEAMFORM_MAX_OWNERS, (F + base - 1) / base);   // (an item of L <= Lmax samples has no more owners)
 }
 

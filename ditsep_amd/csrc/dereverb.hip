@@ -1,8 +1,9 @@
 // Weighted prediction error dereverberation (dsn_dereverb; the definition is in include/ditsep_hip.h, restated in
 // float64 in tests/dereverb_restatement.py): per frequency bin a multichannel linear prediction filter over the delayed
 // past of all channels is estimated against a time-varying variance and its prediction, the late reverberation, is
-// subtracted (Nakatani et al. 2010; Yoshioka & Nakatani 2012).  Frames and spectra are formed by the code of
-// maskrefine.hip (maskrefine_dev.h), so they have the bits they have there.  Three launches per chunk of items:
+// subtracted (Nakatani et al. 2010; Yoshioka & Nakatani 2012).  Frames, spectra and output samples are formed by the
+// functions of maskrefine_dev.h that maskrefine.hip calls (mr_tables, mr_load, mr_fft, mr_split; mr_merge, mr_add,
+// mr_finish), so they have the bits they have there.  Three launches per chunk of items:
 //   analysis   workgroup (group of 2048 / n_fft frames, item, channel): the frames' transforms, written bin-major into
 //              Y [item][bin][channel][frame], so that one bin's history is C contiguous rows.
 //   solve      workgroup (bin, item), 256 threads, all iterations on-die.  The bin's frames pass twice per iteration in
@@ -25,8 +26,6 @@ namespace {
 
 constexpr int DV_TILE = 64;                      // frames per tile of the solve launch
 constexpr int DV_BF = MR_POINTS / 2 / MRT;       // butterflies per thread and stage: one signal
-template <int NFFT>
-constexpr int dv_span() { return NFFT >= 2048 ? 4096 : 2048; }   // maskrefine.hip's spans
 
 struct DvShape {
   int C, K, D, I, Lmax, hop, Fs, items;
@@ -44,51 +43,26 @@ struct DvWorkspace {
 
 __host__ __device__ inline int dv_tri(int i, int j) { return i * (i + 1) / 2 + j; }   // entry (i, j <= i), row after row
 
-template <int H>
-__device__ __forceinline__ void dv_tables(float2* tw, float* win, int tid) {
-  for (int t = tid; t < H; t += MRT) {
-    double s, c;
-    sincospi((double)t / H, &s, &c);   // exp(-2 pi i t / NFFT)
-    tw[t] = make_float2((float)c, (float)-s);
-  }
-  if (win)
-    for (int t = tid; t < 2 * H; t += MRT) win[t] = (float)(0.5 - 0.5 * cospi((double)t / H));   // periodic Hann
-}
-
 // ---------------------------------------------------------------------------------------------------- analysis
 // grid (ceil(Fs / G), items, C).  Dynamic LDS: float2 tw[H] | float2 buf[G][H] | float win[NFFT]
 template <int NFFT>
 __global__ __launch_bounds__(MRT) void dereverb_analysis_kernel(const DvShape q, const float* __restrict__ mix,
                                                                 const int* __restrict__ lens,
                                                                 const int* __restrict__ chans, float2* __restrict__ Yw) {
-  constexpr int H = NFFT / 2, LOGH = __builtin_ctz(H), G = MR_POINTS / H, NP = H / 2 + 1;
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1;
   extern __shared__ __attribute__((aligned(16))) float2 dv_lds[];
   const int tid = threadIdx.x, b = blockIdx.y, c = blockIdx.z, hop = q.hop;
   const int Cb = chans ? chans[b] : q.C;
-  const int L = lens ? lens[b] : q.Lmax;
-  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const MrItem it = mr_item(lens, b, q.Lmax, hop);
   const int f0 = blockIdx.x * G;
-  if (c >= Cb || f0 >= F) return;   // (uniform)
+  if (c >= Cb || f0 >= it.F) return;   // (uniform)
   float2* tw = dv_lds;
   float2* buf = tw + H;
   float* win = reinterpret_cast<float*>(buf + MR_POINTS);
-  dv_tables<H>(tw, win, tid);
+  mr_tables<H>(tw, win, tid);
   __syncthreads();
-  const int f_last = min(F - 1, f0 + G - 1);
-  const float* row = mix + ((long)b * q.C + c) * q.Lmax;
-  // the load of maskrefine.hip: slot fg holds frame f0 + fg, even samples in .x and odd in .y, windowed
-  for (int e = tid; e < G * H; e += MRT) {
-    const int fg = e >> LOGH, tp = e & (H - 1), f = f0 + fg;
-    const bool valid = f <= f_last;
-    int i0 = f * hop - H + 2 * tp, i1 = i0 + 1;
-    i0 = i0 < 0 ? -i0 : i0;
-    i1 = i1 < 0 ? -i1 : i1;
-    i0 = i0 >= Lp ? 2 * (Lp - 1) - i0 : i0;
-    i1 = i1 >= Lp ? 2 * (Lp - 1) - i1 : i1;
-    const float v0 = valid && i0 < L ? row[i0] : 0.f;
-    const float v1 = valid && i1 < L ? row[i1] : 0.f;
-    buf[fg * H + tp] = make_float2(v0 * win[2 * tp], v1 * win[2 * tp + 1]);
-  }
+  const int f_last = min(it.F - 1, f0 + G - 1);
+  mr_load<H>(buf, win, mix + ((long)b * q.C + c) * q.Lmax, nullptr, q.Lmax, it, hop, 1, 0, f0, f_last, tid);
   __syncthreads();
   mr_fft<H, false, DV_BF>(buf, tw, MR_POINTS / 2, tid);
   const long bin_stride = (long)q.C * q.Fs;
@@ -379,34 +353,30 @@ __global__ __launch_bounds__(MRT) void dereverb_solve_kernel(const DvShape q, co
 // ---------------------------------------------------------------------------------------------------- synthesis
 // grid (ceil(Lmax / SPAN), items, C).  Dynamic LDS: float2 tw[H] | float2 buf[G][H] | float win[NFFT] | float ola[SPAN]
 template <int NFFT>
-__global__ __launch_bounds__(MRT) void dereverb_synthesis_kernel(const DvShape q, const MaskRefineShape ms,
+__global__ __launch_bounds__(MRT) void dereverb_synthesis_kernel(const DvShape q, int vec,
                                                                  const int* __restrict__ lens,
                                                                  const int* __restrict__ chans,
                                                                  const float2* __restrict__ Xw, float* __restrict__ out) {
-  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = dv_span<NFFT>();
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = mr_span(NFFT);
   extern __shared__ __attribute__((aligned(16))) float2 dv_lds[];
-  const int hop = q.hop, r = NFFT / hop, tid = threadIdx.x;
+  const int hop = q.hop, tid = threadIdx.x;
   const int b = blockIdx.y, c = blockIdx.z, s0 = blockIdx.x * SPAN;
   const int Cb = chans ? chans[b] : q.C;
-  const int L = lens ? lens[b] : q.Lmax;
-  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const MrItem it = mr_item(lens, b, q.Lmax, hop);
   float* outb = out + ((long)b * q.C + c) * q.Lmax;
-  if (s0 >= L || c >= Cb) {   // (uniform) past the item's end, or a channel it does not have
-    for (int v = tid; v < SPAN / 4; v += MRT)
-      if (s0 + 4 * v < q.Lmax) mr_store(ms, outb, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
+  if (s0 >= it.L || c >= Cb) {   // (uniform) past the item's end, or a channel it does not have
+    mr_zero<H>(outb, 0, 1, s0, q.Lmax, vec, tid);
     return;
   }
   float2* tw = dv_lds;
   float2* buf = tw + H;
   float* win = reinterpret_cast<float*>(buf + MR_POINTS);
   float* ola = win + NFFT;
-  dv_tables<H>(tw, win, tid);
+  mr_tables<H>(tw, win, tid);
   for (int e = tid; e < SPAN; e += MRT) ola[e] = 0.f;
 
-  // sample p is covered by the r frames (p + H) / hop - r + 1 .. (p + H) / hop, where they exist
-  const int pend = min(s0 + SPAN, L);
-  const int f_first = max(0, (s0 + H) / hop - r + 1), f_last = min(F - 1, (pend - 1 + H) / hop);
-  const float inv_n = 1.f / (float)NFFT;   // mr_merge hands back twice the packed transform: 1 / (2 H)
+  const MrFrames fr = mr_frames<H>(it, s0, hop);
+  const int f_first = fr.f_first, f_last = fr.f_last;
   const long bin_stride = (long)q.C * q.Fs;
   const float2* Xb = Xw + ((long)b * (H + 1) * q.C + c) * q.Fs;
 
@@ -422,59 +392,16 @@ __global__ __launch_bounds__(MRT) void dereverb_synthesis_kernel(const DvShape q
     }
     __syncthreads();
     mr_fft<H, true, DV_BF>(buf, tw, MR_POINTS / 2, tid);
-    // ---- add: a thread owns quads of samples for the whole launch, so every sample's sum runs in frame order
-    const int g_last = min(f0 + G - 1, f_last);
-    const float* y = reinterpret_cast<const float*>(buf);
-    for (int v = tid; v < SPAN / 4; v += MRT) {
-      const int p = s0 + 4 * v;
-      if (p >= pend) continue;
-      const int fhi = (p + H) / hop;   // (hop % 4 == 0: the same frames cover the whole quad)
-      const int fa = max(fhi - r + 1, f0), fb = min(fhi, g_last);
-      float4 acc = *reinterpret_cast<float4*>(ola + 4 * v);
-      for (int f = fa; f <= fb; ++f) {
-        const int t = p + H - f * hop;
-        const float4 yv = *reinterpret_cast<const float4*>(y + (f - f0) * NFFT + t);
-        const float4 wv = *reinterpret_cast<const float4*>(win + t);
-        acc.x = acc.x + (yv.x * inv_n) * wv.x;
-        acc.y = acc.y + (yv.y * inv_n) * wv.y;
-        acc.z = acc.z + (yv.z * inv_n) * wv.z;
-        acc.w = acc.w + (yv.w * inv_n) * wv.w;
-      }
-      *reinterpret_cast<float4*>(ola + 4 * v) = acc;
-    }
+    mr_add<H>(ola, buf, win, s0, fr.pend, hop, f0, min(f0 + G - 1, f_last), tid);
   }
-
-  // ---- the envelope of the frames that exist, the division and the store (the quads this thread summed itself)
-  for (int v = tid; v < SPAN / 4; v += MRT) {
-    const int p = s0 + 4 * v;
-    if (p >= q.Lmax) continue;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < pend) {
-      float env[4] = {0.f, 0.f, 0.f, 0.f};
-      const int fhi = (p + H) / hop;
-      const int fa = max(fhi - r + 1, 0), fb = min(fhi, F - 1);
-      for (int f = fa; f <= fb; ++f) {
-        const float4 wv = *reinterpret_cast<const float4*>(win + (p + H - f * hop));
-        env[0] = env[0] + wv.x * wv.x;
-        env[1] = env[1] + wv.y * wv.y;
-        env[2] = env[2] + wv.z * wv.z;
-        env[3] = env[3] + wv.w * wv.w;
-      }
-      const float4 acc = *reinterpret_cast<const float4*>(ola + 4 * v);
-      o.x = acc.x / env[0];
-      o.y = p + 1 < L ? acc.y / env[1] : 0.f;
-      o.z = p + 2 < L ? acc.z / env[2] : 0.f;
-      o.w = p + 3 < L ? acc.w / env[3] : 0.f;
-    }
-    mr_store(ms, outb, p, o);
-  }
+  mr_finish<H>(ola, win, outb, 0, 1, it, s0, fr.pend, hop, q.Lmax, vec, tid);
 }
 
 template <int NFFT>
 void dv_run(const DvShape& q, const float* mix, const int* lens, const int* chans, const DvWorkspace& ws, float* out,
             hipStream_t st) {
-  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = dv_span<NFFT>();
-  const size_t lds_a = sizeof(float2) * (H + MR_POINTS) + sizeof(float) * NFFT, lds_s = lds_a + sizeof(float) * SPAN;
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = mr_span(NFFT);
+  const size_t lds_a = mr_lds_bytes(NFFT, 1, 0), lds_s = mr_lds_bytes(NFFT, 1, 1);
   hipLaunchKernelGGL((dereverb_analysis_kernel<NFFT>), dim3((unsigned)((q.Fs + G - 1) / G), (unsigned)q.items,
                      (unsigned)q.C), dim3(MRT), lds_a, st, q, mix, lens, chans, ws.Y);
   // the launch asks for what its own C K needs; the limit is set once per device, so it is the largest any call may
@@ -484,9 +411,9 @@ void dv_run(const DvShape& q, const float* mix, const int* lens, const int* chan
                                                                DEREVERB_MAX_DELAY + DEREVERB_MAX_TAPS));
   hipLaunchKernelGGL(dereverb_solve_kernel, dim3((unsigned)(H + 1), (unsigned)q.items), dim3(MRT), lds, st, q, lens,
                      chans, ws);
-  const MaskRefineShape ms{1, q.Lmax, q.hop, 2, 0.f, ((uintptr_t)out & 15) == 0 && q.Lmax % 4 == 0 ? 1 : 0, q.C, 0.f};
+  const int vec = ((uintptr_t)out & 15) == 0 && q.Lmax % 4 == 0 ? 1 : 0;   // mr_store: whole quads at once
   hipLaunchKernelGGL((dereverb_synthesis_kernel<NFFT>), dim3((unsigned)((q.Lmax + SPAN - 1) / SPAN), (unsigned)q.items,
-                     (unsigned)q.C), dim3(MRT), lds_s, st, q, ms, lens, chans, ws.X, out);
+                     (unsigned)q.C), dim3(MRT), lds_s, st, q, vec, lens, chans, ws.X, out);
 }
 
 }  // namespace
@@ -513,12 +440,5 @@ void launch_dereverb(const float* mix, const int* lens, const int* chans, void* 
   ws.Y = reinterpret_cast<float2*>(ws.lam + sys * q.Fs);
   ws.X = ws.Y + sys * C * q.Fs;
   ws.failed = reinterpret_cast<int*>(ws.X + sys * C * q.Fs);
-  switch (nfft) {
-    case 64: dv_run<64>(q, mix, lens, chans, ws, out, st); break;
-    case 128: dv_run<128>(q, mix, lens, chans, ws, out, st); break;
-    case 256: dv_run<256>(q, mix, lens, chans, ws, out, st); break;
-    case 512: dv_run<512>(q, mix, lens, chans, ws, out, st); break;
-    case 1024: dv_run<1024>(q, mix, lens, chans, ws, out, st); break;
-    default: dv_run<2048>(q, mix, lens, chans, ws, out, st); break;
-  }
+  mr_for_nfft(nfft, [&](auto N) { dv_run<decltype(N)::value>(q, mix, lens, chans, ws, out, st); });
 }

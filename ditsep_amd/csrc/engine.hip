@@ -208,7 +208,7 @@ struct dsn_ctx {
     int O = -1, kind = -1;
   } stitch_fade;
   // dsn_resample: the compact polyphase tables per (orig, new), uploaded once (taps [new][stride], stride = the
-  // support made odd; k0 [new]) and kept until the context goes; the item lengths last uploaded ("resample_lens")
+  // support made odd; k0 [new]) and kept until the context goes
   struct ResampleTables {
     ResamplePlan plan;
     float* taps = nullptr;
@@ -216,14 +216,12 @@ struct dsn_ctx {
     int stride = 1, kmin = 0, kspan = 1;
   };
   std::map<std::pair<int, int>, ResampleTables> resample_tables;
-  std::vector<int> resample_lens_host;
-  const int* resample_lens_dev = nullptr;
-  // dsn_mask_refine: the item lengths last uploaded ("refine_lens") and where they went
-  std::vector<int> refine_lens_host;
-  const int* refine_lens_dev = nullptr;
-  // dsn_ensemble_combine: likewise ("ensemble_lens")
-  std::vector<int> ensemble_lens_host;
-  const int* ensemble_lens_dev = nullptr;
+  // the item lengths last uploaded and where they went (upload_lens_cached): dsn_resample's ("resample_lens"),
+  // dsn_mask_refine's ("refine_lens") and dsn_ensemble_combine's ("ensemble_lens")
+  struct CachedLens {
+    std::vector<int> host;
+    const int* dev = nullptr;
+  } resample_lens, refine_lens, ensemble_lens;
 
   // DiT
   float* tf_w = nullptr;
@@ -3074,6 +3072,90 @@ int dsn_resample_length(int fs_in, int fs_out, int L) {
   return (int)resample_length(fs_in / g, fs_out / g, L);
 }
 
+// A host table on the device (workspace buffer `name`).  The stream is drained before the buffer is rewritten (an
+// earlier call may still read it) and after the copy (the host image is the caller's local).
+static const void* upload_table(dsn_ctx* ctx, const char* name, const void* h, size_t bytes, hipStream_t st) {
+  char* d = ctx->wsbuf<char>(name, bytes);
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return d;
+}
+
+// lens [B] (or null) on the device (workspace buffer `name`), drained as upload_table drains; a repeated call with the
+// lengths the buffer already holds uploads nothing and drains nothing.
+static const int* upload_lens_cached(dsn_ctx* ctx, const char* name, dsn_ctx::CachedLens& last, const int32_t* lens,
+                                     int B, hipStream_t st) {
+  if (!lens) return nullptr;
+  std::vector<int> h(lens, lens + B);
+  int* d = ctx->wsbuf<int>(name, B);
+  if (h != last.host || d != last.dev) {
+    HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
+    HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    last.host = h;
+    last.dev = d;
+  }
+  return d;
+}
+
+// ---- what dsn_mask_refine, dsn_stems, dsn_beamform and dsn_dereverb refuse alike, each under the caller's name
+static void check_stft(const char* who, int n_fft, int hop) {
+  if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
+  if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
+    fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
+}
+
+static void check_power(const char* who, int power) {
+  if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
+}
+
+static void check_eps(const char* who, float eps) {
+  if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
+}
+
+static void check_reg(const char* who, float reg) {
+  if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
+}
+
+static void check_lmax(const char* who, int Lmax) {
+  if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
+}
+
+// every item: lens[b] (null: Lmax) long enough for one reflection, channels[b] (null: C) in [1, C], *ref (null: the
+// call has none) one of the item's channels
+static void check_items(const char* who, int B, int Lmax, int n_fft, const int32_t* lens, const int32_t* channels, int C,
+                        const int* ref) {
+  const int need = n_fft / 2 + 1;
+  for (int b = 0; b < B; ++b) {
+    const int len = lens ? lens[b] : Lmax;
+    if (len < need || len > Lmax)
+      fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
+           "reflection must reach the item)", who, b, len, need, Lmax, need);
+    const int cb = channels ? (int)channels[b] : C;
+    if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
+    if (ref && (*ref < 0 || *ref >= cb))
+      fail(DSN_EINVAL, "%s: ref = %d outside [0, %d): item %d has %d channels", who, *ref, cb, b, cb);
+    if (!lens && !channels) break;   // (every item is the first)
+  }
+}
+
+// the items of one chunk under workspace_budget bytes (0: fallback), per_item bytes each; `unit` names what, with C,
+// sizes an item ("n", "taps")
+static int items_per_chunk(const char* who, int64_t workspace_budget, int64_t fallback, size_t per_item, int B, int C,
+                           const char* unit, int units, int n_fft, int hop, int Lmax) {
+  if (workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)workspace_budget);
+  const size_t fit = (size_t)(workspace_budget ? workspace_budget : fallback) / per_item;
+  if (fit < 1)
+    fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at C = %d, %s = %d, "
+         "n_fft = %d, hop = %d, Lmax = %d)", who, (long)workspace_budget, (long)per_item, C, unit, units, n_fft, hop, Lmax);
+  return (int)std::min<size_t>(fit, (size_t)B);
+}
+
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
+
 // The tables of (orig, new) on the device.  Equal rates are the one-tap filter h = 1: a copy that honours lens and
 // downmix.  Refuses a plan that does not fit the kernel's LDS before anything is allocated.
 static const dsn_ctx::ResampleTables& resample_tables(dsn_ctx* ctx, const char* who, int fs_in, int fs_out) {
@@ -3129,19 +3211,7 @@ int dsn_resample(dsn_ctx* ctx, const float* x, int B, int C, int L, const int32_
     if (Lout < need) fail(DSN_EINVAL, "%s: Lout = %d < ceil(new * L / orig) = %ld", who, Lout, need);
     const dsn_ctx::ResampleTables& t = resample_tables(ctx, who, fs_in, fs_out);
     hipStream_t st = (hipStream_t)stream;
-    const int* dlens = nullptr;
-    if (lens) {
-      std::vector<int> h(lens, lens + B);
-      int* d = ctx->wsbuf<int>("resample_lens", B);
-      if (h != ctx->resample_lens_host || d != ctx->resample_lens_dev) {
-        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
-        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        ctx->resample_lens_host = h;
-        ctx->resample_lens_dev = d;
-      }
-      dlens = d;
-    }
+    const int* dlens = upload_lens_cached(ctx, "resample_lens", ctx->resample_lens, lens, B, st);
     const ResamplePlan& p = t.plan;
     ctx->prof_launch("resample", 4.0 * ((double)B * C * L + (double)B * (downmix ? 1 : C) * Lout), st, [&] {
       launch_resample(x, dlens, t.taps, t.k0, out, B, C, L, Lout, p.o, p.n, p.width, p.S, t.stride, t.kmin, t.kspan,
@@ -3159,38 +3229,16 @@ int dsn_mask_refine(dsn_ctx* ctx, const float* mix, const float* est, int B, int
     if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
     if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
     if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
-    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
-    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
-      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
-    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
-    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
-    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
-    const int need = n_fft / 2 + 1;
-    for (int b = 0; b < B; ++b) {
-      const int len = lens ? lens[b] : Lmax;
-      if (len < need || len > Lmax)
-        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
-             "reflection must reach the item)", who, b, len, need, Lmax, need);
-      if (!lens) break;
-    }
-    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    check_stft(who, n_fft, hop);
+    check_power(who, power);
+    check_eps(who, eps);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, nullptr, 1, nullptr);
     const size_t row = sizeof(float) * (size_t)B * Lmax;
-    if ((o0 < m0 + row && m0 < o0 + row * n) || (o0 < e0 + row * n && e0 < o0 + row * n))
+    if (overlaps(out, row * n, mix, row) || overlaps(out, row * n, est, row * n))
       fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
     hipStream_t st = (hipStream_t)stream;
-    const int* dlens = nullptr;
-    if (lens) {
-      std::vector<int> h(lens, lens + B);
-      int* d = ctx->wsbuf<int>("refine_lens", B);
-      if (h != ctx->refine_lens_host || d != ctx->refine_lens_dev) {
-        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
-        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        ctx->refine_lens_host = h;
-        ctx->refine_lens_dev = d;
-      }
-      dlens = d;
-    }
+    const int* dlens = upload_lens_cached(ctx, "refine_lens", ctx->refine_lens, lens, B, st);
     ctx->prof_launch("mask_refine", 4.0 * (double)B * Lmax * (2 * n + 1), st, [&] {
       launch_mask_refine(mix, est, dlens, out, B, n, Lmax, n_fft, hop, power, eps, st);
     });
@@ -3220,19 +3268,7 @@ int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int
     const size_t row = sizeof(float) * (size_t)B * n * Lmax;
     if (o0 < c0 + row * K && c0 < o0 + row) fail(DSN_EINVAL, "%s: out overlaps cands", who);
     hipStream_t st = (hipStream_t)stream;
-    const int* dlens = nullptr;
-    if (lens) {
-      std::vector<int> h(lens, lens + B);
-      int* d = ctx->wsbuf<int>("ensemble_lens", B);
-      if (h != ctx->ensemble_lens_host || d != ctx->ensemble_lens_dev) {
-        HIPCHK(hipStreamSynchronize(st));   // (an earlier call on this stream may still read the buffer)
-        HIPCHK(hipMemcpyAsync(d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        ctx->ensemble_lens_host = h;
-        ctx->ensemble_lens_dev = d;
-      }
-      dlens = d;
-    }
+    const int* dlens = upload_lens_cached(ctx, "ensemble_lens", ctx->ensemble_lens, lens, B, st);
     const long R = (long)K * n + (mix ? 1 : 0), tiles = ensemble_tiles(Lmax);
     int RB, NB, S, SUBQ;
     ensemble_gram_plan((int)R, &RB, &NB, &S, &SUBQ);
@@ -3267,16 +3303,6 @@ int dsn_ensemble_combine(dsn_ctx* ctx, const float* cands, const float* mix, int
 }
 
 // ---- WAV payloads and the output gain (pcm.hip)
-// A host table on the device (workspace buffer `name`).  The stream is drained before the buffer is rewritten (an
-// earlier call may still read it) and after the copy (the host image is the caller's local).
-static const void* upload_table(dsn_ctx* ctx, const char* name, const void* h, size_t bytes, hipStream_t st) {
-  char* d = ctx->wsbuf<char>(name, bytes);
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return d;
-}
-
 int dsn_pcm_decode(dsn_ctx* ctx, const void* bytes, int64_t nbytes, int B, const int64_t* offset, const int32_t* frames,
                    const int32_t* channels, const int32_t* encoding, int downmix, float* out, int Cout, int Lmax,
                    void* stream) {
@@ -3430,25 +3456,14 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
       fail(DSN_EINVAL, "%s: C = %d outside [1, %d] (%s)", who, C, Cmax,
            wiener ? "DSN_STEMS_WIENER solves 1 x 1 and 2 x 2 systems" : "DSN_STEMS_MASK");
     if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
-    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
-    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
-      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
-    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
-    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
-    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
-    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
-    const int need = n_fft / 2 + 1;
-    for (int b = 0; b < B; ++b) {
-      const int len = lens ? lens[b] : Lmax;
-      if (len < need || len > Lmax)
-        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
-             "reflection must reach the item)", who, b, len, need, Lmax, need);
-      if (channels && (channels[b] < 1 || channels[b] > C))
-        fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, (int)channels[b], C);
-    }
-    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    check_stft(who, n_fft, hop);
+    check_power(who, power);
+    check_eps(who, eps);
+    check_reg(who, reg);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, channels, C, nullptr);
     const size_t row = sizeof(float) * (size_t)B * Lmax;
-    if ((o0 < m0 + row * C && m0 < o0 + row * n * C) || (o0 < e0 + row * n && e0 < o0 + row * n * C))
+    if (overlaps(out, row * n * C, mix, row * C) || overlaps(out, row * n * C, est, row * n))
       fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
     hipStream_t st = (hipStream_t)stream;
     const int *dlens = nullptr, *dch = nullptr;
@@ -3491,39 +3506,22 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
     if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
     if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
     if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
-    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
-    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
-      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
-    if (power != 1 && power != 2) fail(DSN_EINVAL, "%s: power = %d is not 1 or 2", who, power);
-    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
-    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
-    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
-    const int need = n_fft / 2 + 1;
-    for (int b = 0; b < B; ++b) {
-      const int len = lens ? lens[b] : Lmax;
-      if (len < need || len > Lmax)
-        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
-             "reflection must reach the item)", who, b, len, need, Lmax, need);
-      const int cb = channels ? (int)channels[b] : C;
-      if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
-      if (ref < 0 || ref >= cb)
-        fail(DSN_EINVAL, "%s: ref = %d outside [0, %d): item %d has %d channels", who, ref, cb, b, cb);
-    }
-    if (workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)workspace_budget);
-    const size_t per_item = sizeof(double) * beamform_item_doubles(n_fft, hop, Lmax, C, n);
-    const size_t fit = (size_t)(workspace_budget ? workspace_budget : BEAMFORM_DEFAULT_BUDGET) / per_item;
-    if (fit < 1)
-      fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at C = %d, n = %d, "
-           "n_fft = %d, hop = %d, Lmax = %d)", who, (long)workspace_budget, (long)per_item, C, n, n_fft, hop, Lmax);
-    const char *m0 = (const char*)mix, *e0 = (const char*)est, *o0 = (const char*)out;
+    check_stft(who, n_fft, hop);
+    check_power(who, power);
+    check_eps(who, eps);
+    check_reg(who, reg);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, channels, C, &ref);
+    const int ipc = items_per_chunk(who, workspace_budget, BEAMFORM_DEFAULT_BUDGET,
+                                    sizeof(double) * beamform_item_doubles(n_fft, hop, Lmax, C, n), B, C, "n", n, n_fft,
+                                    hop, Lmax);
     const size_t row = sizeof(float) * (size_t)B * Lmax;
-    if ((o0 < m0 + row * C && m0 < o0 + row * n) || (o0 < e0 + row * n && e0 < o0 + row * n))
+    if (overlaps(out, row * n, mix, row * C) || overlaps(out, row * n, est, row * n))
       fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
     hipStream_t st = (hipStream_t)stream;
     const int *dlens = nullptr, *dch = nullptr;
     if (lens) dlens = (const int*)upload_table(ctx, "beamform_lens", lens, sizeof(int32_t) * (size_t)B, st);
     if (channels) dch = (const int*)upload_table(ctx, "beamform_channels", channels, sizeof(int32_t) * (size_t)B, st);
-    const int ipc = (int)std::min<size_t>(fit, (size_t)B);
     const size_t bins = (size_t)n_fft / 2 + 1, T2 = (size_t)C * (C + 1), nw = (size_t)B * n * bins * C * 2;
     const size_t npart = (size_t)ipc * beamform_owners(n_fft, hop, Lmax) * n * T2 * bins;
     double* part = ctx->wsbuf<double>("beamform_part", npart + (size_t)ipc * n * T2 * bins);
@@ -3564,37 +3562,22 @@ int dsn_dereverb(dsn_ctx* ctx, const float* mix, int B, int C, int Lmax, const i
            DEREVERB_MAX_UNKNOWNS);
     if (iterations < 1 || iterations > DEREVERB_MAX_ITER)
       fail(DSN_EINVAL, "%s: iterations = %d outside [1, %d]", who, iterations, DEREVERB_MAX_ITER);
-    if (!mask_refine_fft_ok(n_fft)) fail(DSN_EINVAL, "%s: n_fft = %d is not a power of two in [64, 2048]", who, n_fft);
-    if (hop < 1 || n_fft % hop != 0 || (n_fft / hop != 2 && n_fft / hop != 4 && n_fft / hop != 8))
-      fail(DSN_EINVAL, "%s: n_fft / hop = %d / %d is not one of 2, 4, 8", who, n_fft, hop);
-    if (!std::isfinite(reg) || reg < 0.f) fail(DSN_EINVAL, "%s: reg = %g is not a finite number >= 0", who, reg);
-    if (!std::isfinite(eps) || !(eps > 0.f)) fail(DSN_EINVAL, "%s: eps = %g is not a finite positive number", who, eps);
-    if (Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d > 2^30", who, Lmax);
-    const int need = n_fft / 2 + 1;
-    for (int b = 0; b < B; ++b) {
-      const int len = lens ? lens[b] : Lmax;
-      if (len < need || len > Lmax)
-        fail(DSN_EINVAL, "%s: item %d has %d samples, outside [n_fft / 2 + 1 = %d, Lmax = %d] (%d samples needed: one "
-             "reflection must reach the item)", who, b, len, need, Lmax, need);
-      const int cb = channels ? (int)channels[b] : C;
-      if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
-    }
-    if (workspace_budget < 0) fail(DSN_EINVAL, "%s: workspace_budget = %ld < 0", who, (long)workspace_budget);
+    check_stft(who, n_fft, hop);
+    check_reg(who, reg);
+    check_eps(who, eps);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, channels, C, nullptr);
     const size_t per_item = dereverb_item_bytes(n_fft, hop, Lmax, C, taps);
-    const size_t fit = (size_t)(workspace_budget ? workspace_budget : DEREVERB_DEFAULT_BUDGET) / per_item;
-    if (fit < 1)
-      fail(DSN_EINVAL, "%s: workspace_budget = %ld bytes is smaller than one item (%ld bytes at C = %d, taps = %d, "
-           "n_fft = %d, hop = %d, Lmax = %d)", who, (long)workspace_budget, (long)per_item, C, taps, n_fft, hop, Lmax);
-    const char *m0 = (const char*)mix, *o0 = (const char*)out;
+    const int ipc = items_per_chunk(who, workspace_budget, DEREVERB_DEFAULT_BUDGET, per_item, B, C, "taps", taps, n_fft,
+                                    hop, Lmax);
     const size_t all = sizeof(float) * (size_t)B * C * Lmax;
-    if (o0 < m0 + all && m0 < o0 + all)
+    if (overlaps(out, all, mix, all))
       fail(DSN_EINVAL, "%s: out overlaps mix (the analysis of one chunk of items runs after the synthesis of another)",
            who);
     hipStream_t st = (hipStream_t)stream;
     const int *dlens = nullptr, *dch = nullptr;
     if (lens) dlens = (const int*)upload_table(ctx, "dereverb_lens", lens, sizeof(int32_t) * (size_t)B, st);
     if (channels) dch = (const int*)upload_table(ctx, "dereverb_channels", channels, sizeof(int32_t) * (size_t)B, st);
-    const int ipc = (int)std::min<size_t>(fit, (size_t)B);
     const size_t bins = (size_t)n_fft / 2 + 1, gsz = bins * C * taps * C * 2;   // doubles of G per item
     char* ws = ctx->wsbuf<char>("dereverb_ws", per_item * ipc);
     std::vector<int32_t> flags;

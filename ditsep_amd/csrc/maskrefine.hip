@@ -39,23 +39,30 @@
 //   MR_WIENER  as MR_MASK, but all C channels are transformed and, in place of Y = M X, the per-bin solve of the
 //              multichannel Wiener filter runs in fp64 with R read from global memory; only channel ch of the n
 //              outputs is formed, rounded once to fp32, and transformed back.
-// In every mode a frame goes through the same loads, transform and split, so X, S and M have the same bits wherever
-// they are formed.
+// In every mode a frame goes through the same functions of maskrefine_dev.h -- mr_tables, mr_load, mr_fft, mr_split and
+// mr_masks, then mr_merge, mr_add and mr_finish --, which beamform.hip and dereverb.hip call too, so X, S, M and the
+// output samples have the same bits wherever they are formed.
 #include "kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#include "maskrefine_dev.h"   // mr_fft, mr_split, mr_merge, mr_mag, mr_store, mr_masks: shared with beamform.hip
+#include "maskrefine_dev.h"   // the frame pipeline: shared with beamform.hip and dereverb.hip
+
+// tests/test_gpu_mask_refine.py reads the spans from the text of this file, so they are stated here as well.  Every
+// kernel and launch uses maskrefine_dev.h's mr_span(nfft); the assertion keeps this statement equal to it.
+template <int NFFT>
+constexpr int mr_span() { return NFFT >= 2048 ? 4096 : 2048; }
+static_assert(mr_span<64>() == mr_span(64) && mr_span<128>() == mr_span(128) && mr_span<256>() == mr_span(256) &&
+                  mr_span<512>() == mr_span(512) && mr_span<1024>() == mr_span(1024) &&
+                  mr_span<2048>() == mr_span(2048),
+              "the spans stated in maskrefine.hip are not those of maskrefine_dev.h");
 
 constexpr int MR_BF = (MR_MAX_SRC + 1) * (MR_POINTS / 2) / MRT;   // butterflies per thread and stage at n = 4
 constexpr int MR_BF_STEMS = (STEMS_WIENER_MAX_CH + MR_MAX_SRC) * (MR_POINTS / 2) / MRT;   // .. with C = 2 channels
 enum { MR_MASK = 0, MR_STATS = 1, MR_WIENER = 2 };
 constexpr int MR_STAT = 5;   // fp64 sums per (source, bin): N00, N11, Re N01, Im N01, d
-
-template <int NFFT>
-constexpr int mr_span() { return NFFT >= 2048 ? 4096 : 2048; }
 
 // One bin of the multichannel Wiener filter in fp64 (include/ditsep_hip.h, dsn_stems): X [Cb] the mixture's channels,
 // M [n] the masks, R -> R_0 of this bin ([C][C] complex as double pairs, source stride rs doubles); Y [n] = channel
@@ -117,10 +124,10 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
                                                           float* __restrict__ out, const double* __restrict__ Rg,
                                                           double* __restrict__ part) {
   static_assert(NFFT >= 64 && NFFT <= 2 * MR_POINTS && (NFFT & (NFFT - 1)) == 0, "FFT size");
-  constexpr int H = NFFT / 2, LOGH = __builtin_ctz(H), G = MR_POINTS / H, NP = H / 2 + 1, SPAN = mr_span<NFFT>();
+  constexpr int H = NFFT / 2, G = MR_POINTS / H, NP = H / 2 + 1, SPAN = mr_span(NFFT);
   constexpr int BF = MODE == MR_MASK ? MR_BF : MR_BF_STEMS;
   extern __shared__ __attribute__((aligned(16))) float2 mr_lds[];
-  const int n = q.n, hop = q.hop, r = NFFT / hop, tid = threadIdx.x;
+  const int n = q.n, hop = q.hop, tid = threadIdx.x;
   const int b = blockIdx.y, co = blockIdx.z, s0 = blockIdx.x * SPAN;
   const int Cb = chans ? chans[b] : q.C;
   const int nx = MODE == MR_MASK ? 1 : Cb;          // mixture channels in LDS: slots 0 .. nx - 1, then the estimates
@@ -129,58 +136,33 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
   float2* buf = tw + H;
   float* win = reinterpret_cast<float*>(buf + ((MODE == MR_MASK ? 1 : q.C) + n) * MR_POINTS);
   float* ola = win + NFFT;
-  const int L = lens ? lens[b] : q.Lmax;
-  const int Lp = (L + hop - 1) / hop * hop, F = 1 + Lp / hop;
+  const MrItem it = mr_item(lens, b, q.Lmax, hop);
   const float* mixb = mix + ((long)b * q.C + cx) * q.Lmax;
   const float* estb = est + (long)b * n * q.Lmax;
   float* outb = out + ((long)b * n * q.C + co) * q.Lmax;   // source i: + i C Lmax
   const long orow = (long)q.C * q.Lmax;
 
-  if (MODE != MR_STATS && (s0 >= L || co >= Cb)) {   // (uniform) past the item's end, or a channel it does not have
-    for (int i = 0; i < n; ++i)
-      for (int v = tid; v < SPAN / 4; v += MRT)
-        if (s0 + 4 * v < q.Lmax) mr_store(q, outb + i * orow, s0 + 4 * v, make_float4(0.f, 0.f, 0.f, 0.f));
+  if (MODE != MR_STATS && (s0 >= it.L || co >= Cb)) {   // (uniform) past the item's end, or a channel it does not have
+    mr_zero<H>(outb, orow, n, s0, q.Lmax, q.vec, tid);
     return;
   }
   const int fps = SPAN / hop;   // MR_STATS: the frames one workgroup owns
-  if (MODE == MR_STATS && (int)blockIdx.x * fps >= F) return;   // (uniform)
+  if (MODE == MR_STATS && (int)blockIdx.x * fps >= it.F) return;   // (uniform)
 
-  for (int t = tid; t < H; t += MRT) {
-    double s, c;
-    sincospi((double)t / H, &s, &c);   // exp(-2 pi i t / NFFT)
-    tw[t] = make_float2((float)c, (float)-s);
-  }
-  for (int t = tid; t < NFFT; t += MRT) win[t] = (float)(0.5 - 0.5 * cospi((double)t / H));   // periodic Hann
+  mr_tables<H>(tw, win, tid);
   if (MODE != MR_STATS)
     for (int e = tid; e < n * SPAN; e += MRT) ola[e] = 0.f;
 
-  // sample p is covered by the r frames (p + H) / hop - r + 1 .. (p + H) / hop, where they exist
-  const int pend = min(s0 + SPAN, L);
-  const int f_first = MODE == MR_STATS ? (int)blockIdx.x * fps : max(0, (s0 + H) / hop - r + 1);
-  const int f_last = MODE == MR_STATS ? min(F, f_first + fps) - 1 : min(F - 1, (pend - 1 + H) / hop);
-  const float inv_n = 1.f / (float)NFFT;   // mr_merge hands back twice the packed transform: 1 / (2 H)
+  const MrFrames fr = mr_frames<H>(it, s0, hop);
+  const int pend = fr.pend;
+  const int f_first = MODE == MR_STATS ? (int)blockIdx.x * fps : fr.f_first;
+  const int f_last = MODE == MR_STATS ? min(it.F, f_first + fps) - 1 : fr.f_last;
   const long rs = 2L * (H + 1) * q.C * q.C;   // doubles between R_i and R_{i+1} of an item
   double* partw = MODE == MR_STATS ? part + ((long)b * gridDim.x + blockIdx.x) * n * MR_STAT * (H + 1) : nullptr;
 
   for (int f0 = f_first; f0 <= f_last; f0 += G) {
     __syncthreads();   // the tables are in; the previous group's frames have been added
-    // ---- load: slot fg holds frame f0 + fg of every signal, even samples in .x and odd in .y, windowed
-    for (int e = tid; e < G * H; e += MRT) {
-      const int fg = e >> LOGH, tp = e & (H - 1), f = f0 + fg;
-      const bool valid = f <= f_last;
-      int i0 = f * hop - H + 2 * tp, i1 = i0 + 1;   // (f hop <= Lp: no overflow)
-      i0 = i0 < 0 ? -i0 : i0;
-      i1 = i1 < 0 ? -i1 : i1;
-      i0 = i0 >= Lp ? 2 * (Lp - 1) - i0 : i0;   // Lp > H: one reflection reaches [0, Lp)
-      i1 = i1 >= Lp ? 2 * (Lp - 1) - i1 : i1;
-      const float w0 = win[2 * tp], w1 = win[2 * tp + 1];
-      for (int s = 0; s < nx + n; ++s) {
-        const float* row = s < nx ? mixb + (long)s * q.Lmax : estb + (long)(s - nx) * q.Lmax;
-        const float v0 = valid && i0 < L ? row[i0] : 0.f;
-        const float v1 = valid && i1 < L ? row[i1] : 0.f;
-        buf[(s * G + fg) * H + tp] = make_float2(v0 * w0, v1 * w1);
-      }
-    }
+    mr_load<H>(buf, win, mixb, estb, q.Lmax, it, hop, nx, n, f0, f_last, tid);
     __syncthreads();
     mr_fft<H, false, BF>(buf, tw, (nx + n) * (MR_POINTS / 2), tid);
     if (MODE == MR_STATS) {
@@ -268,59 +250,10 @@ __global__ __launch_bounds__(MRT) void mask_refine_kernel(const MaskRefineShape 
     }
     __syncthreads();
     mr_fft<H, true, BF>(buf + nx * MR_POINTS, tw, n * (MR_POINTS / 2), tid);
-    // ---- add: a thread owns quads of samples for the whole launch, so every sample's sum runs in frame order
-    const int g_last = min(f0 + G - 1, f_last);
-    for (int i = 0; i < n; ++i) {
-      const float* y = reinterpret_cast<const float*>(buf + (nx + i) * MR_POINTS);
-      for (int v = tid; v < SPAN / 4; v += MRT) {
-        const int p = s0 + 4 * v;
-        if (p >= pend) continue;
-        const int fhi = (p + H) / hop;   // (hop % 4 == 0: the same frames cover the whole quad)
-        const int fa = max(fhi - r + 1, f0), fb = min(fhi, g_last);
-        float4 acc = *reinterpret_cast<float4*>(ola + i * SPAN + 4 * v);
-        for (int f = fa; f <= fb; ++f) {
-          const int t = p + H - f * hop;
-          const float4 yv = *reinterpret_cast<const float4*>(y + (f - f0) * NFFT + t);
-          const float4 wv = *reinterpret_cast<const float4*>(win + t);
-          acc.x = acc.x + (yv.x * inv_n) * wv.x;
-          acc.y = acc.y + (yv.y * inv_n) * wv.y;
-          acc.z = acc.z + (yv.z * inv_n) * wv.z;
-          acc.w = acc.w + (yv.w * inv_n) * wv.w;
-        }
-        *reinterpret_cast<float4*>(ola + i * SPAN + 4 * v) = acc;
-      }
-    }
+    for (int i = 0; i < n; ++i)
+      mr_add<H>(ola + i * SPAN, buf + (nx + i) * MR_POINTS, win, s0, pend, hop, f0, min(f0 + G - 1, f_last), tid);
   }
-  if (MODE == MR_STATS) return;
-
-  // ---- the envelope of the frames that exist, the division and the store (the quads this thread summed itself)
-  for (int v = tid; v < SPAN / 4; v += MRT) {
-    const int p = s0 + 4 * v;
-    if (p >= q.Lmax) continue;
-    float env[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p < pend) {
-      const int fhi = (p + H) / hop;
-      const int fa = max(fhi - r + 1, 0), fb = min(fhi, F - 1);
-      for (int f = fa; f <= fb; ++f) {
-        const float4 wv = *reinterpret_cast<const float4*>(win + (p + H - f * hop));
-        env[0] = env[0] + wv.x * wv.x;
-        env[1] = env[1] + wv.y * wv.y;
-        env[2] = env[2] + wv.z * wv.z;
-        env[3] = env[3] + wv.w * wv.w;
-      }
-    }
-    for (int i = 0; i < n; ++i) {
-      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p < pend) {
-        const float4 acc = *reinterpret_cast<const float4*>(ola + i * SPAN + 4 * v);
-        o.x = acc.x / env[0];
-        o.y = p + 1 < L ? acc.y / env[1] : 0.f;
-        o.z = p + 2 < L ? acc.z / env[2] : 0.f;
-        o.w = p + 3 < L ? acc.w / env[3] : 0.f;
-      }
-      mr_store(q, outb + i * orow, p, o);
-    }
-  }
+  if (MODE != MR_STATS) mr_finish<H>(ola, win, outb, orow, n, it, s0, pend, hop, q.Lmax, q.vec, tid);
 }
 
 // R [B][n][H + 1][C][C] complex and den [B][n][H + 1] from part [B][spans][n][MR_STAT][H + 1]: one thread per (item,
@@ -354,12 +287,6 @@ __global__ __launch_bounds__(MRT) void stems_reduce_kernel(const double* __restr
   den[e] = d;
 }
 
-template <int NFFT>
-size_t mr_lds_bytes(int nx, int n, bool ola) {
-  return sizeof(float2) * ((size_t)NFFT / 2 + (size_t)(nx + n) * MR_POINTS) +
-         sizeof(float) * ((size_t)NFFT + (ola ? (size_t)n * mr_span<NFFT>() : 0));
-}
-
 struct MrArgs {
   const float *mix, *est;
   const int *lens, *chans;
@@ -371,14 +298,15 @@ struct MrArgs {
 template <int NFFT, int MODE>
 void mr_launch(const MaskRefineShape& q, const MrArgs& a, dim3 grid, hipStream_t st) {
   const int nxmax = MODE == MR_MASK ? 1 : STEMS_WIENER_MAX_CH, nx = MODE == MR_MASK ? 1 : q.C;
-  dsn_allow_lds<mask_refine_kernel<NFFT, MODE>>((int)mr_lds_bytes<NFFT>(nxmax, MR_MAX_SRC, MODE != MR_STATS));
-  hipLaunchKernelGGL((mask_refine_kernel<NFFT, MODE>), grid, dim3(MRT), mr_lds_bytes<NFFT>(nx, q.n, MODE != MR_STATS),
-                     st, q, a.mix, a.est, a.lens, a.chans, a.out, a.R, a.part);
+  const bool ola = MODE != MR_STATS;
+  dsn_allow_lds<mask_refine_kernel<NFFT, MODE>>((int)mr_lds_bytes(NFFT, nxmax + MR_MAX_SRC, ola ? MR_MAX_SRC : 0));
+  hipLaunchKernelGGL((mask_refine_kernel<NFFT, MODE>), grid, dim3(MRT), mr_lds_bytes(NFFT, nx + q.n, ola ? q.n : 0), st,
+                     q, a.mix, a.est, a.lens, a.chans, a.out, a.R, a.part);
 }
 
 template <int NFFT>
 void mr_run(int wiener, const MaskRefineShape& q, const MrArgs& a, hipStream_t st) {
-  constexpr int SPAN = mr_span<NFFT>();
+  constexpr int SPAN = mr_span(NFFT);
   const dim3 grid((unsigned)((q.Lmax + SPAN - 1) / SPAN), (unsigned)a.B, (unsigned)q.C);
   if (!wiener) {
     mr_launch<NFFT, MR_MASK>(q, a, grid, st);
@@ -393,14 +321,7 @@ void mr_run(int wiener, const MaskRefineShape& q, const MrArgs& a, hipStream_t s
 }
 
 void mr_dispatch(int nfft, int wiener, const MaskRefineShape& q, const MrArgs& a, hipStream_t st) {
-  switch (nfft) {
-    case 64: mr_run<64>(wiener, q, a, st); break;
-    case 128: mr_run<128>(wiener, q, a, st); break;
-    case 256: mr_run<256>(wiener, q, a, st); break;
-    case 512: mr_run<512>(wiener, q, a, st); break;
-    case 1024: mr_run<1024>(wiener, q, a, st); break;
-    default: mr_run<2048>(wiener, q, a, st); break;
-  }
+  mr_for_nfft(nfft, [&](auto N) { mr_run<decltype(N)::value>(wiener, q, a, st); });
 }
 
 }  // namespace
@@ -414,7 +335,7 @@ void launch_mask_refine(const float* mix, const float* est, const int* lens, flo
 }
 
 int stems_stat_spans(int nfft, int hop, int Lmax) {
-  const int F = 1 + (Lmax + hop - 1) / hop, fps = (nfft >= 2048 ? mr_span<2048>() : mr_span<64>()) / hop;
+  const int F = 1 + (Lmax + hop - 1) / hop, fps = mr_span(nfft) / hop;
   return (F + fps - 1) / fps;
 }
 

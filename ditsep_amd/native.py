@@ -589,20 +589,95 @@ MASK_REFINE_DEFAULTS = dict(n_fft=512, hop=128, power=2, eps=1e-10)
 MASK_REFINE_MAX_SRC = 4
 
 
+def _options(who, value, defaults, forms, shorthand, validate=None) -> Optional[dict]:
+    """A keyword of the separation entry points (`who`) as its Engine method's keywords: None -> None; a value
+    `shorthand` maps to a dict of replacements, or a dict of `defaults`' keys -> the defaults with those replaced (and
+    `validate`d); anything else is refused by name, `forms` naming what is accepted besides a dict."""
+    if value is None:
+        return None
+    short = shorthand(value)
+    if short is not None:
+        return dict(defaults, **short)
+    if isinstance(value, Mapping):
+        extra = sorted(set(value) - set(defaults))
+        if extra:
+            raise ValueError(f"{who}: unknown keys {extra} (a dict of {sorted(defaults)})")
+        opts = dict(defaults, **value)
+        if validate is not None:
+            validate(opts)
+        return opts
+    raise ValueError(f"{who} must be {forms} or a dict of {sorted(defaults)} (got {value!r})")
+
+
 def refine_options(refine) -> Optional[dict]:
     """The `refine` keyword of the separation entry points as Engine.mask_refine's keywords: None (off, the default)
     -> None; True or "mask" -> MASK_REFINE_DEFAULTS; a dict of n_fft / hop / power / eps -> the defaults with those
     replaced.  Anything else, False included, is refused by name."""
-    if refine is None:
+    return _options("refine", refine, MASK_REFINE_DEFAULTS, "None, True, 'mask'",
+                    lambda v: {} if v is True or v == "mask" else None)
+
+
+def _check_stft(who, B, n, n_fft, hop, power, eps) -> tuple:
+    """B, n and the STFT parameters as dsn_mask_refine takes them -> (n_fft, hop, power, eps)"""
+    if B < 1:
+        raise ValueError(f"{who}: B = {B} < 1")
+    if n < 1 or n > MASK_REFINE_MAX_SRC:
+        raise ValueError(f"{who}: n = {n} outside [1, {MASK_REFINE_MAX_SRC}]")
+    if int(n_fft) != n_fft or int(n_fft) < 64 or int(n_fft) > 2048 or int(n_fft) & (int(n_fft) - 1):
+        raise ValueError(f"{who}: n_fft = {n_fft!r} is not a power of two in [64, 2048]")
+    n_fft = int(n_fft)
+    if int(hop) != hop or int(hop) < 1 or n_fft % int(hop) or n_fft // int(hop) not in (2, 4, 8):
+        raise ValueError(f"{who}: n_fft / hop = {n_fft} / {hop!r} is not one of 2, 4, 8")
+    if power not in (1, 2):
+        raise ValueError(f"{who}: power = {power!r} is not 1 or 2")
+    eps = float(eps)
+    if not math.isfinite(eps) or not eps > 0.0:
+        raise ValueError(f"{who}: eps = {eps} is not a finite positive number")
+    return n_fft, int(hop), int(power), eps
+
+
+def _check_item_lens(who, lens, B, L, n_fft) -> Optional[list]:
+    """One sample count per item, each long enough for one reflection -> lens as a list or None"""
+    need = n_fft // 2 + 1
+    ln = [L] if lens is None else [int(v) for v in lens]
+    if lens is not None and len(ln) != B:
+        raise ValueError(f"lens must hold one sample count per item (B = {B}), got {len(ln)}")
+    for b, v in enumerate(ln):
+        if v < need or v > L:
+            raise ValueError(f"{who}: item {b} has {v} samples, outside [n_fft / 2 + 1 = {need}, L = {L}] "
+                             f"({need} samples needed: one reflection must reach the item)")
+    return None if lens is None else ln
+
+
+def _check_reg(who, reg) -> float:
+    reg = float(reg)
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError(f"{who}: reg = {reg} is not a finite number >= 0")
+    return reg
+
+
+def _check_channels(who, channels, B, Cn) -> Optional[list]:
+    """One channel count in [1, C] per item -> channels as a list or None"""
+    if channels is None:
         return None
-    if refine is True or refine == "mask":
-        return dict(MASK_REFINE_DEFAULTS)
-    if isinstance(refine, Mapping):
-        extra = sorted(set(refine) - set(MASK_REFINE_DEFAULTS))
-        if extra:
-            raise ValueError(f"refine: unknown keys {extra} (a dict of {sorted(MASK_REFINE_DEFAULTS)})")
-        return dict(MASK_REFINE_DEFAULTS, **refine)
-    raise ValueError(f"refine must be None, True, 'mask' or a dict of {sorted(MASK_REFINE_DEFAULTS)} (got {refine!r})")
+    ch = [int(v) for v in channels]
+    if len(ch) != B:
+        raise ValueError(f"{who}: channels must hold one channel count per item (B = {B}), got {len(ch)}")
+    for b, v in enumerate(ch):
+        if v < 1 or v > Cn:
+            raise ValueError(f"{who}: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    return ch
+
+
+def _check_budget(who, workspace_budget, default, per_item, at) -> int:
+    """A workspace budget in bytes (0: `default`) that holds at least one item of `per_item` bytes -> the budget"""
+    budget = int(workspace_budget)
+    if budget < 0:
+        raise ValueError(f"{who}: workspace_budget = {budget} < 0")
+    if (budget or default) < per_item:
+        raise ValueError(f"{who}: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
+                         f"{at})")
+    return budget
 
 
 def check_mask_refine(mix_shape, est_shape, lens=None, n_fft=512, hop=128, power=2, eps=1e-10) -> tuple:
@@ -618,29 +693,8 @@ def check_mask_refine(mix_shape, est_shape, lens=None, n_fft=512, hop=128, power
         raise ValueError(f"mask_refine: mix must be [B, L] or [B, 1, L] and est [B, n, L] of the same B and L (got "
                          f"{mix_shape} and {est_shape})")
     B, n, L = est_shape
-    if B < 1:
-        raise ValueError(f"mask_refine: B = {B} < 1")
-    if n < 1 or n > MASK_REFINE_MAX_SRC:
-        raise ValueError(f"mask_refine: n = {n} outside [1, {MASK_REFINE_MAX_SRC}]")
-    if int(n_fft) != n_fft or int(n_fft) < 64 or int(n_fft) > 2048 or int(n_fft) & (int(n_fft) - 1):
-        raise ValueError(f"mask_refine: n_fft = {n_fft!r} is not a power of two in [64, 2048]")
-    n_fft = int(n_fft)
-    if int(hop) != hop or int(hop) < 1 or n_fft % int(hop) or n_fft // int(hop) not in (2, 4, 8):
-        raise ValueError(f"mask_refine: n_fft / hop = {n_fft} / {hop!r} is not one of 2, 4, 8")
-    if power not in (1, 2):
-        raise ValueError(f"mask_refine: power = {power!r} is not 1 or 2")
-    eps = float(eps)
-    if not math.isfinite(eps) or not eps > 0.0:
-        raise ValueError(f"mask_refine: eps = {eps} is not a finite positive number")
-    need = n_fft // 2 + 1
-    ln = [L] if lens is None else [int(v) for v in lens]
-    if lens is not None and len(ln) != B:
-        raise ValueError(f"lens must hold one sample count per item (B = {B}), got {len(ln)}")
-    for b, v in enumerate(ln):
-        if v < need or v > L:
-            raise ValueError(f"mask_refine: item {b} has {v} samples, outside [n_fft / 2 + 1 = {need}, L = {L}] "
-                             f"({need} samples needed: one reflection must reach the item)")
-    return (B, n, L), (None if lens is None else ln), n_fft, int(hop), int(power), eps
+    n_fft, hop, power, eps = _check_stft("mask_refine", B, n, n_fft, hop, power, eps)
+    return (B, n, L), _check_item_lens("mask_refine", lens, B, L, n_fft), n_fft, hop, power, eps
 
 
 STEMS_MODES = {"mask": 0, "wiener": 1}                                              # DSN_STEMS_*
@@ -648,23 +702,27 @@ STEMS_MAX_CHANNELS = {"mask": 8, "wiener": 2}
 STEMS_DEFAULTS = dict(mode="wiener", n_fft=512, hop=128, power=2, eps=1e-10, reg=1e-3)
 
 
+def _check_stems_mode(mode) -> None:
+    if mode not in STEMS_MODES:
+        raise ValueError(f"stems: mode must be one of {sorted(STEMS_MODES)} (got {mode!r})")
+
+
 def stems_options(stems) -> Optional[dict]:
     """The `stems` keyword of the separation entry points as Engine.stems' keywords: None (off, the default) -> None;
     "mask" or "wiener" -> STEMS_DEFAULTS with that mode; a dict of mode / n_fft / hop / power / eps / reg -> the
     defaults with those replaced.  Anything else, an unknown key or mode included, is refused by name."""
-    if stems is None:
-        return None
-    if isinstance(stems, str) and stems in STEMS_MODES:
-        return dict(STEMS_DEFAULTS, mode=stems)
-    if isinstance(stems, Mapping):
-        extra = sorted(set(stems) - set(STEMS_DEFAULTS))
-        if extra:
-            raise ValueError(f"stems: unknown keys {extra} (a dict of {sorted(STEMS_DEFAULTS)})")
-        opts = dict(STEMS_DEFAULTS, **stems)
-        if opts["mode"] not in STEMS_MODES:
-            raise ValueError(f"stems: mode must be one of {sorted(STEMS_MODES)} (got {opts['mode']!r})")
-        return opts
-    raise ValueError(f"stems must be None, 'mask', 'wiener' or a dict of {sorted(STEMS_DEFAULTS)} (got {stems!r})")
+    return _options("stems", stems, STEMS_DEFAULTS, "None, 'mask', 'wiener'",
+                    lambda v: {"mode": v} if isinstance(v, str) and v in STEMS_MODES else None,
+                    lambda opts: _check_stems_mode(opts["mode"]))
+
+
+def _check_mix_est(who, mix_shape, est_shape) -> tuple:
+    """mix [B, C, L] and est [B, n, L] of the same B and L -> (B, C, n, L)"""
+    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
+    if len(mix_shape) != 3 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != (mix_shape[0], mix_shape[2]):
+        raise ValueError(f"{who}: mix must be [B, C, L] and est [B, n, L] of the same B and L (got {mix_shape} and "
+                         f"{est_shape})")
+    return mix_shape[0], mix_shape[1], est_shape[1], mix_shape[2]
 
 
 def check_stems(mix_shape, est_shape, lens=None, channels=None, mode="wiener", n_fft=512, hop=128, power=2, eps=1e-10,
@@ -674,31 +732,15 @@ def check_stems(mix_shape, est_shape, lens=None, channels=None, mode="wiener", n
     [1, 2] (wiener); what check_mask_refine refuses (n, n_fft, hop, power, eps, an item too short for one reflection);
     reg not finite or < 0; not one channel count per item, or one outside [1, C].
     -> ((B, C, n, L), lens or None, channels or None, the DSN_STEMS_* mode, n_fft, hop, power, eps, reg)"""
-    if mode not in STEMS_MODES:
-        raise ValueError(f"stems: mode must be one of {sorted(STEMS_MODES)} (got {mode!r})")
-    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
-    if len(mix_shape) != 3 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != (mix_shape[0], mix_shape[2]):
-        raise ValueError(f"stems: mix must be [B, C, L] and est [B, n, L] of the same B and L (got {mix_shape} and "
-                         f"{est_shape})")
-    B, Cn, L = mix_shape
+    _check_stems_mode(mode)
+    B, Cn, n, L = _check_mix_est("stems", mix_shape, est_shape)
     if Cn < 1 or Cn > STEMS_MAX_CHANNELS[mode]:
         raise ValueError(f"stems: C = {Cn} outside [1, {STEMS_MAX_CHANNELS[mode]}] for mode {mode!r}"
                          + (" (the Wiener filter solves 1 x 1 and 2 x 2 systems)" if mode == "wiener" else ""))
-    try:
-        (_, n, _), ln, n_fft, hop, power, eps = check_mask_refine((B, L), est_shape, lens, n_fft, hop, power, eps)
-    except ValueError as e:
-        raise ValueError(str(e).replace("mask_refine:", "stems:")) from None
-    reg = float(reg)
-    if not math.isfinite(reg) or reg < 0.0:
-        raise ValueError(f"stems: reg = {reg} is not a finite number >= 0")
-    ch = None
-    if channels is not None:
-        ch = [int(v) for v in channels]
-        if len(ch) != B:
-            raise ValueError(f"stems: channels must hold one channel count per item (B = {B}), got {len(ch)}")
-        for b, v in enumerate(ch):
-            if v < 1 or v > Cn:
-                raise ValueError(f"stems: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    n_fft, hop, power, eps = _check_stft("stems", B, n, n_fft, hop, power, eps)
+    ln = _check_item_lens("stems", lens, B, L, n_fft)
+    reg = _check_reg("stems", reg)
+    ch = _check_channels("stems", channels, B, Cn)
     return (B, Cn, n, L), ln, ch, STEMS_MODES[mode], n_fft, hop, power, eps, reg
 
 
@@ -709,29 +751,28 @@ BEAMFORM_DEFAULTS = dict(ref=0, n_fft=STEMS_DEFAULTS["n_fft"], hop=STEMS_DEFAULT
                          eps=STEMS_DEFAULTS["eps"], reg=STEMS_DEFAULTS["reg"], postfilter=None)
 
 
+def _check_postfilter(postfilter) -> None:
+    if postfilter not in BEAMFORM_POSTFILTERS:
+        raise ValueError(f"beamform: postfilter must be None, 'none' or 'mask' (got {postfilter!r})")
+
+
+def _beamform_shorthand(v) -> Optional[dict]:
+    if v is True:
+        return {}
+    if isinstance(v, int) and not isinstance(v, bool):
+        if v < 0:
+            raise ValueError(f"beamform: the reference channel {v} is negative")
+        return {"ref": int(v)}
+    return None
+
+
 def beamform_options(beamform) -> Optional[dict]:
     """The `beamform` keyword of the separation entry points as Engine.beamform's keywords: None (off, the default)
     -> None; True -> BEAMFORM_DEFAULTS; an int -> the defaults with that reference channel; a dict of ref / n_fft /
     hop / power / eps / reg / postfilter -> the defaults with those replaced.  Anything else, False and an unknown key
     or post-filter included, is refused by name."""
-    if beamform is None:
-        return None
-    if beamform is True:
-        return dict(BEAMFORM_DEFAULTS)
-    if isinstance(beamform, int) and not isinstance(beamform, bool):
-        if beamform < 0:
-            raise ValueError(f"beamform: the reference channel {beamform} is negative")
-        return dict(BEAMFORM_DEFAULTS, ref=int(beamform))
-    if isinstance(beamform, Mapping):
-        extra = sorted(set(beamform) - set(BEAMFORM_DEFAULTS))
-        if extra:
-            raise ValueError(f"beamform: unknown keys {extra} (a dict of {sorted(BEAMFORM_DEFAULTS)})")
-        opts = dict(BEAMFORM_DEFAULTS, **beamform)
-        if opts["postfilter"] not in BEAMFORM_POSTFILTERS:
-            raise ValueError(f"beamform: postfilter must be None, 'none' or 'mask' (got {opts['postfilter']!r})")
-        return opts
-    raise ValueError(f"beamform must be None, True, a reference channel or a dict of {sorted(BEAMFORM_DEFAULTS)} "
-                     f"(got {beamform!r})")
+    return _options("beamform", beamform, BEAMFORM_DEFAULTS, "None, True, a reference channel", _beamform_shorthand,
+                    lambda opts: _check_postfilter(opts["postfilter"]))
 
 
 def beamform_item_bytes(n_fft: int, hop: int, L: int, Cn: int, n: int) -> int:
@@ -751,43 +792,23 @@ def check_beamform(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=
     workspace budget or one smaller than one item.
     -> ((B, C, n, L), lens or None, channels or None, ref, n_fft, hop, power, eps, reg, the DSN_BEAMFORM_POST_* code,
     workspace_budget)"""
-    if postfilter not in BEAMFORM_POSTFILTERS:
-        raise ValueError(f"beamform: postfilter must be None, 'none' or 'mask' (got {postfilter!r})")
-    mix_shape, est_shape = tuple(int(v) for v in mix_shape), tuple(int(v) for v in est_shape)
-    if len(mix_shape) != 3 or len(est_shape) != 3 or (est_shape[0], est_shape[2]) != (mix_shape[0], mix_shape[2]):
-        raise ValueError(f"beamform: mix must be [B, C, L] and est [B, n, L] of the same B and L (got {mix_shape} and "
-                         f"{est_shape})")
-    B, Cn, L = mix_shape
+    _check_postfilter(postfilter)
+    B, Cn, n, L = _check_mix_est("beamform", mix_shape, est_shape)
     if Cn < 1 or Cn > BEAMFORM_MAX_CHANNELS:
         raise ValueError(f"beamform: C = {Cn} outside [1, {BEAMFORM_MAX_CHANNELS}]")
-    try:
-        (_, n, _), ln, n_fft, hop, power, eps = check_mask_refine((B, L), est_shape, lens, n_fft, hop, power, eps)
-    except ValueError as e:
-        raise ValueError(str(e).replace("mask_refine:", "beamform:")) from None
-    reg = float(reg)
-    if not math.isfinite(reg) or reg < 0.0:
-        raise ValueError(f"beamform: reg = {reg} is not a finite number >= 0")
-    ch = None
-    if channels is not None:
-        ch = [int(v) for v in channels]
-        if len(ch) != B:
-            raise ValueError(f"beamform: channels must hold one channel count per item (B = {B}), got {len(ch)}")
-        for b, v in enumerate(ch):
-            if v < 1 or v > Cn:
-                raise ValueError(f"beamform: item {b} has channels = {v}, outside [1, C = {Cn}]")
+    n_fft, hop, power, eps = _check_stft("beamform", B, n, n_fft, hop, power, eps)
+    ln = _check_item_lens("beamform", lens, B, L, n_fft)
+    reg = _check_reg("beamform", reg)
+    ch = _check_channels("beamform", channels, B, Cn)
     if isinstance(ref, bool) or int(ref) != ref:
         raise ValueError(f"beamform: ref = {ref!r} is not a channel index")
     ref = int(ref)
     for b, v in enumerate(ch if ch is not None else [Cn]):
         if ref < 0 or ref >= v:
             raise ValueError(f"beamform: ref = {ref} outside [0, {v}): item {b} has {v} channels")
-    budget = int(workspace_budget)
-    if budget < 0:
-        raise ValueError(f"beamform: workspace_budget = {budget} < 0")
-    per_item = beamform_item_bytes(n_fft, hop, L, Cn, n)
-    if (budget or BEAMFORM_DEFAULT_BUDGET) < per_item:
-        raise ValueError(f"beamform: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
-                         f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L})")
+    budget = _check_budget("beamform", workspace_budget, BEAMFORM_DEFAULT_BUDGET,
+                           beamform_item_bytes(n_fft, hop, L, Cn, n),
+                           f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L}")
     return (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, BEAMFORM_POSTFILTERS[postfilter], budget
 
 
@@ -801,16 +822,7 @@ def dereverb_options(dereverb) -> Optional[dict]:
     """The `dereverb` keyword of the separation entry points as Engine.dereverb's keywords: None (off, the default)
     -> None; True -> DEREVERB_DEFAULTS; a dict of taps / delay / iterations / n_fft / hop / reg / eps -> the defaults
     with those replaced.  Anything else, False and an unknown key included, is refused by name."""
-    if dereverb is None:
-        return None
-    if dereverb is True:
-        return dict(DEREVERB_DEFAULTS)
-    if isinstance(dereverb, Mapping):
-        extra = sorted(set(dereverb) - set(DEREVERB_DEFAULTS))
-        if extra:
-            raise ValueError(f"dereverb: unknown keys {extra} (a dict of {sorted(DEREVERB_DEFAULTS)})")
-        return dict(DEREVERB_DEFAULTS, **dereverb)
-    raise ValueError(f"dereverb must be None, True or a dict of {sorted(DEREVERB_DEFAULTS)} (got {dereverb!r})")
+    return _options("dereverb", dereverb, DEREVERB_DEFAULTS, "None, True", lambda v: {} if v is True else None)
 
 
 def dereverb_item_bytes(n_fft: int, hop: int, L: int, Cn: int, taps: int) -> int:
@@ -843,28 +855,13 @@ def check_dereverb(mix_shape, lens=None, channels=None, taps=10, delay=3, iterat
     if Cn * taps > DEREVERB_MAX_UNKNOWNS:
         raise ValueError(f"dereverb: C taps = {Cn} x {taps} = {Cn * taps} unknowns per bin, more than "
                          f"{DEREVERB_MAX_UNKNOWNS}")
-    try:
-        _, ln, n_fft, hop, _, eps = check_mask_refine((B, L), (B, 1, L), lens, n_fft, hop, 2, eps)
-    except ValueError as e:
-        raise ValueError(str(e).replace("mask_refine:", "dereverb:")) from None
-    reg = float(reg)
-    if not math.isfinite(reg) or reg < 0.0:
-        raise ValueError(f"dereverb: reg = {reg} is not a finite number >= 0")
-    ch = None
-    if channels is not None:
-        ch = [int(v) for v in channels]
-        if len(ch) != B:
-            raise ValueError(f"dereverb: channels must hold one channel count per item (B = {B}), got {len(ch)}")
-        for b, v in enumerate(ch):
-            if v < 1 or v > Cn:
-                raise ValueError(f"dereverb: item {b} has channels = {v}, outside [1, C = {Cn}]")
-    budget = 0 if workspace_budget is None else int(workspace_budget)
-    if budget < 0:
-        raise ValueError(f"dereverb: workspace_budget = {budget} < 0")
-    per_item = dereverb_item_bytes(n_fft, hop, L, Cn, taps)
-    if (budget or DEREVERB_DEFAULT_BUDGET) < per_item:
-        raise ValueError(f"dereverb: workspace_budget = {budget} bytes is smaller than one item ({per_item} bytes at "
-                         f"C = {Cn}, taps = {taps}, n_fft = {n_fft}, hop = {hop}, L = {L})")
+    n_fft, hop, _, eps = _check_stft("dereverb", B, 1, n_fft, hop, 2, eps)
+    ln = _check_item_lens("dereverb", lens, B, L, n_fft)
+    reg = _check_reg("dereverb", reg)
+    ch = _check_channels("dereverb", channels, B, Cn)
+    budget = _check_budget("dereverb", 0 if workspace_budget is None else workspace_budget, DEREVERB_DEFAULT_BUDGET,
+                           dereverb_item_bytes(n_fft, hop, L, Cn, taps),
+                           f"C = {Cn}, taps = {taps}, n_fft = {n_fft}, hop = {hop}, L = {L}")
     return (B, Cn, L), ln, ch, taps, delay, iterations, n_fft, hop, reg, eps, budget
 
 
@@ -1342,6 +1339,16 @@ def load_library() -> C.CDLL:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _host(t: Optional[torch.Tensor], ctype=C.c_double):
+    """A host tensor the library writes, as a pointer to its elements"""
+    return None if t is None else C.cast(C.c_void_p(t.data_ptr()), C.POINTER(ctype))
+
+
+def _i32(v: Optional[list]):
+    """One int32 per item, or None"""
+    return None if v is None else (C.c_int32 * len(v))(*v)
 
 
 def mrstft_unsupported(*, window="hann_window", w_phs=0.0, scale=None, scale_invariance=False, decay=1.0, **other):
@@ -2043,6 +2050,30 @@ class Engine:
         out = out.reshape((Lout,) if nd == 1 else (Co, Lout) if nd == 2 else (B, Co, Lout))
         return out if ln is None else (out, [resample_length(fs_in, fs_out, v) for v in ln])
 
+    def _pad_items(self, mix, est=None):
+        """The list form of mask_refine, stems, beamform and dereverb as one padded batch: mix a list of [C_b, L_b],
+        est a list of as many [n, L_b] or None -> (mix [B, C, L], est [B, n, L] or None, lens, channels, cut), zero
+        past an item's end and in the channels it does not have.  cut(res, ch_dim=None): the call's result (out, or
+        (out, info)) with out as a list of the items' own samples and, ch_dim being the axis of an item's out that
+        holds its channels, own channels."""
+        ln, ch = [int(m.shape[-1]) for m in mix], [int(m.shape[0]) for m in mix]
+        mp = torch.zeros((len(mix), max(ch), max(ln)), device=self.device, dtype=torch.float32)
+        ep = None if est is None else torch.zeros((len(mix), int(est[0].shape[0]), max(ln)), device=self.device,
+                                                  dtype=torch.float32)
+        for b, m in enumerate(mix):
+            mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
+            if est is not None:
+                ep[b, :, :ln[b]] = _dev32(est[b], self.device)
+
+        def cut(res, ch_dim=None):
+            out, info = res if isinstance(res, tuple) else (res, None)
+            outs = [out[b, ..., :ln[b]] for b in range(len(mix))]
+            if ch_dim is not None:
+                outs = [o.narrow(ch_dim, 0, ch[b]) for b, o in enumerate(outs)]
+            return outs if info is None else (outs, info)
+
+        return mp, ep, ln, ch, cut
+
     # ------------------------------------------------------------------ mixture-consistent masks
     def mask_refine(self, mix, est, lens=None, n_fft=512, hop=128, power=2, eps=1e-10):
         """Mixture-consistent STFT masks on the device (dsn_mask_refine, csrc/maskrefine.hip; the definition is in
@@ -2062,21 +2093,14 @@ class Engine:
                 if e.dim() != 2 or m.numel() != ln[b] or m.dim() not in (1, 2):
                     raise ValueError(f"mask_refine: item {b} must be mix [1, L] and est [n, L] (got {tuple(m.shape)} "
                                      f"and {tuple(e.shape)})")
-            Lmax = max(ln)
-            mp = torch.zeros((len(mix), Lmax), device=self.device, dtype=torch.float32)
-            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
-            for b, (m, e) in enumerate(zip(mix, est)):
-                mp[b, :ln[b]] = _dev32(m, self.device).reshape(-1)
-                ep[b, :, :ln[b]] = _dev32(e, self.device)
-            out = self.mask_refine(mp, ep, lens=ln, n_fft=n_fft, hop=hop, power=power, eps=eps)
-            return [out[b, :, :ln[b]] for b in range(len(mix))]
+            mp, ep, ln, _, cut = self._pad_items([m.reshape(1, -1) for m in mix], est)
+            return cut(self.mask_refine(mp, ep, lens=ln, n_fft=n_fft, hop=hop, power=power, eps=eps))
         (B, n, L), ln, n_fft, hop, power, eps = check_mask_refine(tuple(mix.shape), tuple(est.shape), lens, n_fft, hop,
                                                                   power, eps)
         mix = _dev32(mix, self.device).reshape(B, L)
         est = _dev32(est, self.device)
         out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
-        self._check(self.lib.dsn_mask_refine(self.ctx, _ptr(mix), _ptr(est), B, n, L,
-                                             None if ln is None else (C.c_int32 * B)(*ln), n_fft, hop, power, eps,
+        self._check(self.lib.dsn_mask_refine(self.ctx, _ptr(mix), _ptr(est), B, n, L, _i32(ln), n_fft, hop, power, eps,
                                              _ptr(out), self._stream()), "dsn_mask_refine")
         return out
 
@@ -2105,18 +2129,9 @@ class Engine:
                 if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
                     raise ValueError(f"stems: item {b} must be mix [C, L] and est [n, L] (got {tuple(m.shape)} and "
                                      f"{tuple(e.shape)})")
-            ch = [int(m.shape[0]) for m in mix]
-            Lmax = max(ln)
-            mp = torch.zeros((len(mix), max(ch), Lmax), device=self.device, dtype=torch.float32)
-            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
-            for b, (m, e) in enumerate(zip(mix, est)):
-                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
-                ep[b, :, :ln[b]] = _dev32(e, self.device)
-            res = self.stems(mp, ep, lens=ln, channels=ch, mode=mode, n_fft=n_fft, hop=hop, power=power, eps=eps,
-                             reg=reg, return_info=return_info)
-            out = res[0] if return_info else res
-            outs = [out[b, :, :ch[b], :ln[b]] for b in range(len(mix))]
-            return (outs, res[1]) if return_info else outs
+            mp, ep, ln, ch, cut = self._pad_items(mix, est)
+            return cut(self.stems(mp, ep, lens=ln, channels=ch, mode=mode, n_fft=n_fft, hop=hop, power=power, eps=eps,
+                                  reg=reg, return_info=return_info), ch_dim=1)
         (B, Cn, n, L), ln, ch, code, n_fft, hop, power, eps, reg = check_stems(
             tuple(mix.shape), tuple(est.shape), lens, channels, mode, n_fft, hop, power, eps, reg)
         mix, est = _dev32(mix, self.device), _dev32(est, self.device)
@@ -2124,11 +2139,8 @@ class Engine:
         bins = n_fft // 2 + 1
         R = torch.zeros((B, n, bins, Cn, Cn), dtype=torch.complex128) if return_info else None
         den = torch.zeros((B, n, bins), dtype=torch.float64) if return_info else None
-        host = lambda t: None if t is None else C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double))
-        i32 = C.c_int32 * B
-        self._check(self.lib.dsn_stems(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, None if ln is None else i32(*ln),
-                                       None if ch is None else i32(*ch), code, n_fft, hop, power, eps, reg, _ptr(out),
-                                       host(R), host(den), self._stream()), "dsn_stems")
+        self._check(self.lib.dsn_stems(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), code, n_fft, hop,
+                                       power, eps, reg, _ptr(out), _host(R), _host(den), self._stream()), "dsn_stems")
         return (out, {"R": R, "den": den}) if return_info else out
 
     # ------------------------------------------------------------------ mask-based MVDR beamforming
@@ -2157,31 +2169,19 @@ class Engine:
                 if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
                     raise ValueError(f"beamform: item {b} must be mix [C, L] and est [n, L] (got {tuple(m.shape)} and "
                                      f"{tuple(e.shape)})")
-            ch = [int(m.shape[0]) for m in mix]
-            Lmax = max(ln)
-            mp = torch.zeros((len(mix), max(ch), Lmax), device=self.device, dtype=torch.float32)
-            ep = torch.zeros((len(mix), int(est[0].shape[0]), Lmax), device=self.device, dtype=torch.float32)
-            for b, (m, e) in enumerate(zip(mix, est)):
-                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
-                ep[b, :, :ln[b]] = _dev32(e, self.device)
-            res = self.beamform(mp, ep, lens=ln, channels=ch, ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps,
-                                reg=reg, postfilter=postfilter, workspace_budget=workspace_budget,
-                                return_info=return_info)
-            out = res[0] if return_info else res
-            outs = [out[b, :, :ln[b]] for b in range(len(mix))]
-            return (outs, res[1]) if return_info else outs
+            mp, ep, ln, ch, cut = self._pad_items(mix, est)
+            return cut(self.beamform(mp, ep, lens=ln, channels=ch, ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps,
+                                     reg=reg, postfilter=postfilter, workspace_budget=workspace_budget,
+                                     return_info=return_info))
         (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, post, budget = check_beamform(
             tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg, postfilter,
             workspace_budget)
         mix, est = _dev32(mix, self.device), _dev32(est, self.device)
         out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
         w = torch.zeros((B, n, n_fft // 2 + 1, Cn), dtype=torch.complex128) if return_info else None
-        i32 = C.c_int32 * B
-        self._check(self.lib.dsn_beamform(
-            self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, None if ln is None else i32(*ln),
-            None if ch is None else i32(*ch), ref, n_fft, hop, power, eps, reg, post, budget, _ptr(out),
-            None if w is None else C.cast(C.c_void_p(w.data_ptr()), C.POINTER(C.c_double)), self._stream()),
-            "dsn_beamform")
+        self._check(self.lib.dsn_beamform(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref, n_fft, hop,
+                                          power, eps, reg, post, budget, _ptr(out), _host(w), self._stream()),
+                    "dsn_beamform")
         return (out, {"w": w}) if return_info else out
 
     # ------------------------------------------------------------------ WPE dereverberation
@@ -2209,27 +2209,17 @@ class Engine:
             for b, m in enumerate(mix):
                 if m.dim() != 2:
                     raise ValueError(f"dereverb: item {b} must be [C, L] (got {tuple(m.shape)})")
-            ln, ch = [int(m.shape[-1]) for m in mix], [int(m.shape[0]) for m in mix]
-            mp = torch.zeros((len(mix), max(ch), max(ln)), device=self.device, dtype=torch.float32)
-            for b, m in enumerate(mix):
-                mp[b, :ch[b], :ln[b]] = _dev32(m, self.device)
-            res = self.dereverb(mp, lens=ln, channels=ch, **kw)
-            out = res[0] if return_info else res
-            outs = [out[b, :ch[b], :ln[b]] for b in range(len(mix))]
-            return (outs, res[1]) if return_info else outs
+            mp, _, ln, ch, cut = self._pad_items(mix)
+            return cut(self.dereverb(mp, lens=ln, channels=ch, **kw), ch_dim=0)
         (B, Cn, L), ln, ch, taps, delay, iterations, n_fft, hop, reg, eps, budget = check_dereverb(
             tuple(mix.shape), lens, channels, taps, delay, iterations, n_fft, hop, reg, eps, workspace_budget)
         mix = _dev32(mix, self.device)
         out = torch.empty((B, Cn, L), device=self.device, dtype=torch.float32)
         G = torch.zeros((B, n_fft // 2 + 1, Cn * taps, Cn), dtype=torch.complex128) if return_info else None
         fail = torch.zeros((B,), dtype=torch.int32) if return_info else None
-        i32 = C.c_int32 * B
-        self._check(self.lib.dsn_dereverb(
-            self.ctx, _ptr(mix), B, Cn, L, None if ln is None else i32(*ln), None if ch is None else i32(*ch), n_fft,
-            hop, taps, delay, iterations, reg, eps, budget, _ptr(out),
-            None if G is None else C.cast(C.c_void_p(G.data_ptr()), C.POINTER(C.c_double)),
-            None if fail is None else C.cast(C.c_void_p(fail.data_ptr()), C.POINTER(C.c_int32)), self._stream()),
-            "dsn_dereverb")
+        self._check(self.lib.dsn_dereverb(self.ctx, _ptr(mix), B, Cn, L, _i32(ln), _i32(ch), n_fft, hop, taps, delay,
+                                          iterations, reg, eps, budget, _ptr(out), _host(G), _host(fail, C.c_int32),
+                                          self._stream()), "dsn_dereverb")
         return (out, {"G": G, "fail": fail}) if return_info else out
 
     # ------------------------------------------------------------------ K candidates -> one separation

@@ -113,8 +113,10 @@ def test_every_kind_on_an_array(eng, kind):
 def test_one_channel_is_mask_refine(eng):
     """C = 1: w = Z / Z = 1.0, so every source is mask_refine with n = 1 (the mixture's own transform handed back), and
     with the mask post-filter mask_refine itself"""
+    every = tuple((n_fft, n_fft // r, 2 * span_of(n_fft) + 37)   # every size, over two span boundaries, L % 4 != 0
+                  for n_fft, r in ((64, 2), (128, 4), (256, 8), (512, 2), (1024, 4), (2048, 8)))
     for n_fft, hop, L in ((512, 128, 2 * span_of(512) + 301), (64, 8, 33), (2048, 1024, 3 * span_of(2048) + 17),
-                          (256, 64, native.BEAMFORM_MAX_OWNERS * span_of(256) + 77)):
+                          (256, 64, native.BEAMFORM_MAX_OWNERS * span_of(256) + 77)) + every:
         for n, power in ((1, 2), (2, 1), (3, 2), (4, 2)):
             mix, est = br.make_case(n_fft + L + n, "generic", n, 1, L)
             m, e = torch.from_numpy(mix)[None].to(eng.device), torch.from_numpy(est)[None].to(eng.device)

@@ -93,7 +93,8 @@ def test_against_the_restatement(eng, name):
 def test_short_and_silent_items_are_the_round_trip(eng):
     """F <= D: P = 0, G = 0, X = Y; so is a silent item.  Every channel is mask_refine of that channel with n = 1"""
     g = torch.Generator().manual_seed(5)
-    for n_fft, hop, D, L, C in ((512, 128, 8, 700, 3), (2048, 1024, 4, 2500, 2), (64, 32, 3, 33, 8)):
+    for n_fft, hop, D, L, C in ((512, 128, 8, 700, 3), (2048, 1024, 4, 2500, 2), (64, 32, 3, 33, 8),
+                                (128, 64, 8, 401, 2), (256, 128, 8, 799, 2), (1024, 512, 8, 3001, 2)):
         F = 1 + (L + hop - 1) // hop
         assert F <= D
         x = (0.3 * torch.randn((1, C, L), generator=g)).to(eng.device)

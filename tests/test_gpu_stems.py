@@ -51,22 +51,25 @@ def lengths_of(n_fft, hop):
 
 
 # ------------------------------------------------------------------ 1. mask mode
-@pytest.mark.parametrize("n_fft", [64, 512, 2048])
+@pytest.mark.parametrize("n_fft", [64, 128, 256, 512, 1024, 2048])
 def test_mask_mode_is_mask_refine_per_channel(eng, n_fft):
-    q = 0
+    cases = []
     for r in (2, 4, 8):
+        for L in lengths_of(n_fft, n_fft // r):
+            q = len(cases)
+            cases.append((r, L, (1, 2, 3, 8)[q % 4], 1 + (q // 2) % 4, 1 + q % 2))
+    # every size at one of the ratios: two channels and two sources over two span boundaries, L % 4 != 0
+    cases.append(({64: 2, 128: 4, 256: 8, 512: 2, 1024: 4, 2048: 8}[n_fft], 2 * span_of(n_fft) + 37, 2, 2, 2))
+    for r, L, C, n, power in cases:
         hop = n_fft // r
-        for L in lengths_of(n_fft, hop):
-            C, n, power = (1, 2, 3, 8)[q % 4], 1 + (q // 2) % 4, 1 + q % 2
-            q += 1
-            mix, est = sr.make_case(n_fft + 13 * r + L, "generic", n, C, L)
-            m = off_alignment(torch.from_numpy(mix)[None], eng.device)
-            e = off_alignment(torch.from_numpy(est)[None], eng.device)
-            out = eng.stems(m, e, mode="mask", n_fft=n_fft, hop=hop, power=power)
-            assert tuple(out.shape) == (1, n, C, L) and float(out.abs().max()) > 0
-            for c in range(C):
-                want = eng.mask_refine(m[:, c].contiguous(), e, n_fft=n_fft, hop=hop, power=power)
-                assert torch.equal(out[:, :, c].view(torch.int32), want.view(torch.int32)), (n_fft, hop, L, C, n, c)
+        mix, est = sr.make_case(n_fft + 13 * r + L, "generic", n, C, L)
+        m = off_alignment(torch.from_numpy(mix)[None], eng.device)
+        e = off_alignment(torch.from_numpy(est)[None], eng.device)
+        out = eng.stems(m, e, mode="mask", n_fft=n_fft, hop=hop, power=power)
+        assert tuple(out.shape) == (1, n, C, L) and float(out.abs().max()) > 0
+        for c in range(C):
+            want = eng.mask_refine(m[:, c].contiguous(), e, n_fft=n_fft, hop=hop, power=power)
+            assert torch.equal(out[:, :, c].view(torch.int32), want.view(torch.int32)), (n_fft, hop, L, C, n, c)
 
 
 # ------------------------------------------------------------------ 2. wiener mode against the restatement
