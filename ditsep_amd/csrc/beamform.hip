@@ -15,7 +15,9 @@
 //   weights  eight lanes per (item, source, bin): every lane forms A = Q_i + lambda I and its Cholesky factor itself
 //            (channels the item does not have are an identity block, which leaves the other entries' arithmetic as it
 //            is) and solves column `lane` of Z = A^-1 N_i; the diagonal of Z goes through LDS, tau is added in channel
-//            order by the lane of the reference channel, which writes w = Z[:, ref] / tau.
+//            order by the lane of the reference channel, which writes w = Z[:, ref] / tau.  The launch also runs alone
+//            on given statistics of `classes` >= n classes (launch_beamform_solve; spatial.hip's noise class): all
+//            classes enter Q_i, the first n get a filter.
 //   apply    workgroup (span, item, source), the mask kernel's layout: transforms the C_b channels (and the n
 //            estimates only where the post-filter needs the masks), contracts the channels with w in fp64 in channel
 //            order, rounds once, writes Y_i over channel 0's slot, inverse-transforms that slot and overlap-adds.
@@ -186,12 +188,13 @@ __global__ __launch_bounds__(MRT) void beamform_reduce_kernel(const double* __re
   N[e] = s;
 }
 
-// N [items][n][2 tri(C)][bins] -> w [items][n][bins][C] complex doubles.  Thread (g, lane) of a workgroup: system
-// blockIdx.x BF_GROUPS + g = (item, source, bin), right-hand side `lane`.
+// N [items][classes][2 tri(C)][bins] -> w [items][n][bins][C] complex doubles: the first n of the classes >= n get a
+// filter, all of them enter the interference.  Thread (g, lane) of a workgroup: system blockIdx.x BF_GROUPS + g =
+// (item, source, bin), right-hand side `lane`.
 __global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __restrict__ N,
                                                                const int* __restrict__ chans, int ref, int items,
-                                                               int n, int C, int bins, double reg, double eps,
-                                                               double* __restrict__ w) {
+                                                               int n, int classes, int C, int bins, double reg,
+                                                               double eps, double* __restrict__ w) {
   __shared__ double zd[BF_GROUPS][BF_LANES];
   const int lane = threadIdx.x % BF_LANES, g = threadIdx.x / BF_LANES;
   const long sys = (long)blockIdx.x * BF_GROUPS + g, total = (long)items * n * bins;
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __r
   const int j = (int)(e % bins), i = (int)(e / bins % n), b = (int)(e / bins / n);
   const int Cb = chans ? chans[b] : C;
   const int T2 = 2 * bf_tri(C);
-  const double* Nb = N + (long)b * n * T2 * bins + j;   // entry u of source s: Nb[(s T2 + u) bins]
+  const double* Nb = N + (long)b * classes * T2 * bins + j;   // entry u of class s: Nb[(s T2 + u) bins]
 
   // A = Q_i + lambda I: the lower triangle, row after row; a[r (r + 1) / 2 + c] = A[r][c] = conj(Q[c][r]), c <= r
   double ar[BF_TRI], ai[BF_TRI];
@@ -212,7 +215,7 @@ __global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __r
       ar[p] = ai[p] = 0.0;
       if (r < Cb) {
         const long at = 2L * bf_idx(C, c, r) * bins;
-        for (int s = 0; s < n; ++s)
+        for (int s = 0; s < classes; ++s)
           if (s != i) {
             ar[p] += Nb[(long)s * T2 * bins + at];
             ai[p] -= Nb[(long)s * T2 * bins + at + bins];
@@ -415,9 +418,7 @@ void bf_run(int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st
     const long rows = (long)a.items * q.n * T2 * bins;
     hipLaunchKernelGGL(beamform_reduce_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, a.part,
                        a.lens, a.chans, a.items, q.n, q.C, q.Lmax, bins, q.hop, SPAN / q.hop, OW, a.N);
-    const long systems = (long)a.items * q.n * bins;
-    hipLaunchKernelGGL(beamform_weights_kernel, dim3((unsigned)((systems + BF_GROUPS - 1) / BF_GROUPS)), dim3(MRT), 0,
-                       st, a.N, a.chans, a.ref, a.items, q.n, q.C, bins, a.reg, a.eps, a.w);
+    launch_beamform_solve(a.N, a.chans, a.ref, a.w, a.items, q.C, q.n, q.n, NFFT, a.reg, a.eps, st);
     return;
   }
   const int slots = q.C + (a.post ? q.n : 0);
@@ -440,6 +441,13 @@ int beamform_owners(int nfft, int hop, int Lmax) {
 
 size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n) {
   return ((size_t)beamform_owners(nfft, hop, Lmax) + 1) * n * 2 * bf_tri(C) * ((size_t)nfft / 2 + 1);
+}
+
+void launch_beamform_solve(const double* N, const int* chans, int ref, double* w, int items, int C, int n, int classes,
+                           int nfft, double reg, double eps, hipStream_t st) {
+  const long systems = (long)items * n * (nfft / 2 + 1);
+  hipLaunchKernelGGL(beamform_weights_kernel, dim3((unsigned)((systems + BF_GROUPS - 1) / BF_GROUPS)), dim3(MRT), 0, st,
+                     N, chans, ref, items, n, classes, C, nfft / 2 + 1, reg, eps, w);
 }
 
 void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,

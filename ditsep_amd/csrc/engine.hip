@@ -3544,6 +3544,79 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
   });
 }
 
+// ---- beamforming on spatially refined masks (spatial.hip, beamform.hip; include/ditsep_hip.h states the definition)
+int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                         const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                         float reg, int iterations, float noise, float floor, float mask_reg, float mask_eps,
+                         int64_t workspace_budget, float* out, double* info_w, double* info_gamma, int32_t* info_fail,
+                         void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_beamform_spatial";
+    if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (iterations < 0 || iterations > SPATIAL_MAX_ITER)
+      fail(DSN_EINVAL, "%s: iterations = %d outside [0, %d]", who, iterations, SPATIAL_MAX_ITER);
+    if (!(noise >= 0.f && noise <= 0.9f)) fail(DSN_EINVAL, "%s: noise = %g outside [0, 0.9]", who, noise);
+    if (!(floor >= 0.f && floor <= 1.f)) fail(DSN_EINVAL, "%s: floor = %g outside [0, 1]", who, floor);
+    check_stft(who, n_fft, hop);
+    check_power(who, power);
+    check_eps(who, eps);
+    check_reg(who, reg);
+    if (!std::isfinite(mask_reg) || mask_reg < 0.f)
+      fail(DSN_EINVAL, "%s: mask_reg = %g is not a finite number >= 0", who, mask_reg);
+    if (!std::isfinite(mask_eps) || !(mask_eps > 0.f))
+      fail(DSN_EINVAL, "%s: mask_eps = %g is not a finite positive number", who, mask_eps);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, channels, C, &ref);
+    const size_t per_item = spatial_item_bytes(n_fft, hop, Lmax, C, n);
+    const int ipc = items_per_chunk(who, workspace_budget, SPATIAL_DEFAULT_BUDGET, per_item, B, C, "n", n, n_fft, hop,
+                                    Lmax);
+    const size_t row = sizeof(float) * (size_t)B * Lmax;
+    if (overlaps(out, row * n, mix, row * C) || overlaps(out, row * n, est, row * n))
+      fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int *dlens = nullptr, *dch = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "spatial_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    if (channels) dch = (const int*)upload_table(ctx, "spatial_channels", channels, sizeof(int32_t) * (size_t)B, st);
+    const int K = noise > 0.f ? n + 1 : n;
+    const size_t bins = (size_t)n_fft / 2 + 1, Fs = (size_t)spatial_frames(hop, Lmax);
+    const size_t nw = (size_t)B * n * bins * C * 2, ng = (size_t)K * bins * Fs;   // (gamma: per item)
+    char* ws = ctx->wsbuf<char>("spatial_ws", per_item * ipc);
+    double* w = ctx->wsbuf<double>("spatial_w", nw);
+    double* gamma = info_gamma ? ctx->wsbuf<double>("spatial_gamma", ng * ipc) : nullptr;
+    for (int b0 = 0; b0 < B; b0 += ipc) {   // the chunk's workspace is reused from chunk to chunk on the one stream
+      const int items = std::min(ipc, B - b0);
+      ctx->prof_launch("beamform_spatial", 4.0 * (double)items * Lmax * (C + n), st, [&] {
+        launch_spatial_statistics(mix + (size_t)b0 * C * Lmax, est + (size_t)b0 * n * Lmax,
+                                  dlens ? dlens + b0 : nullptr, dch ? dch + b0 : nullptr, ws, gamma, items, C, n, K,
+                                  Lmax, n_fft, hop, power, eps, iterations, (double)noise, (double)floor,
+                                  (double)mask_reg, (double)mask_eps, st);
+        launch_beamform_solve((const double*)ws, dch ? dch + b0 : nullptr, ref, w + (size_t)b0 * n * bins * C * 2, items,
+                              C, n, K, n_fft, (double)reg, (double)eps, st);
+      });
+      HIPCHK(hipGetLastError());
+      if (info_gamma)
+        HIPCHK(hipMemcpyAsync(info_gamma + (size_t)b0 * ng, gamma, sizeof(double) * ng * items, hipMemcpyDeviceToHost,
+                              st));
+      if (info_fail) {   // (failed is the last array of the workspace)
+        const char* failed = ws + (size_t)items * (per_item - 4 * bins);
+        HIPCHK(hipMemcpyAsync(info_fail + (size_t)b0 * bins, failed, sizeof(int32_t) * items * bins,
+                              hipMemcpyDeviceToHost, st));
+      }
+      if (info_gamma || info_fail) HIPCHK(hipStreamSynchronize(st));
+    }
+    ctx->prof_launch("beamform_spatial", 4.0 * (double)B * Lmax * (C + 2.0 * n), st, [&] {
+      launch_beamform_apply(mix, est, dlens, dch, w, out, B, C, n, Lmax, n_fft, hop, power, eps, 0, st);
+    });
+    HIPCHK(hipGetLastError());
+    if (!info_w) return;
+    HIPCHK(hipMemcpyAsync(info_w, w, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  });
+}
+
 // ---- WPE dereverberation (dereverb.hip; include/ditsep_hip.h states the definition)
 int dsn_dereverb(dsn_ctx* ctx, const float* mix, int B, int C, int Lmax, const int32_t* lens, const int32_t* channels,
                  int n_fft, int hop, int taps, int delay, int iterations, float reg, float eps, int64_t workspace_budget,

@@ -475,9 +475,30 @@ size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n);   // pa
 void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,
                              double* part, double* N, double* w, int items, int C, int n, int Lmax, int nfft, int hop,
                              int power, float eps, float reg, hipStream_t s);
+// the weights launch alone, on given statistics N [items][classes][C (C + 1)][bins]: the first n <= classes of the
+// classes get a filter, all of them enter the interference (dsn_beamform: classes = n)
+void launch_beamform_solve(const double* N, const int* chans, int ref, double* w, int items, int C, int n, int classes,
+                           int nfft, double reg, double eps, hipStream_t s);
 void launch_beamform_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
                            float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
                            int post, hipStream_t s);
+
+// ---- spatial mask refinement for the beamformer (spatial.hip) --------------------------------------------------------
+// mix [items][C][Lmax], est [items][n][Lmax] fp32, lens / chans [items] (device) or null.  Two launches: the transforms
+// of the channels and the estimates, spectra and fp32 masks bin-major into the workspace, and one workgroup per
+// (bin, item) that runs all iterations of the guided cACGMM in fp64 on-die and writes the statistics of its `classes`
+// (n, or n + 1 with the noise class) in the layout launch_beamform_solve reads.  `workspace` holds spatial_item_bytes
+// per item: N [n + 1][C (C + 1)][bins] doubles | X [bins][C][Fs] complex floats | M [bins][n][Fs] floats | failed [bins]
+// int32, each array for all items in turn (N with `classes` per item); Fs = spatial_frames, bins = nfft / 2 + 1.
+// gamma [items][classes][bins][Fs] doubles (device) or null.
+#define SPATIAL_MAX_ITER 16
+#define SPATIAL_DEFAULT_BUDGET (512L << 20)
+int spatial_frames(int hop, int Lmax);
+size_t spatial_item_bytes(int nfft, int hop, int Lmax, int C, int n);
+void launch_spatial_statistics(const float* mix, const float* est, const int* lens, const int* chans, void* workspace,
+                               double* gamma, int items, int C, int n, int classes, int Lmax, int nfft, int hop,
+                               int power, float eps, int iterations, double noise, double floor, double mask_reg,
+                               double mask_eps, hipStream_t s);
 
 // ---- weighted prediction error dereverberation (dereverb.hip) ------------------------------------------------------
 // mix / out [items][C][Lmax] fp32, lens / chans [items] (device) or null.  Three launches: the frames' transforms

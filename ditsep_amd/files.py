@@ -90,7 +90,8 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, loudness=None, limit=None, beamform=None, dereverb=None, **sampler_kwargs) -> list:
+                   stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None,
+                   **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -105,6 +106,12 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
                          "mixture")
     beam = native.beamform_options(beamform)
+    spat = native.spatial_options(spatial)
+    if spat is not None:
+        if stems is not None:
+            raise ValueError("spatial= does not go with stems=: it refines the masks of the beamformer, which stems= "
+                             "does not run")
+        native.spatial_beamform_keywords(beam, spat)
     if beam is not None and stems is not None:
         raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, stems= "
                          "the mixture's channels")
@@ -227,7 +234,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         if stems is not None:
             return finish_stems(idx, clips, est, label, channels_fs)
         if beam is not None:
-            est = eng.beamform([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est), **beam)
+            est = model._beamform_step([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est),
+                                       beam, spat)
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)
@@ -253,6 +261,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 rec["alpha"] = [float(a) for a in alpha[j]]
             if beam is not None:
                 rec["beamform"] = beam["ref"]
+            if spat is not None:
+                rec["spatial"] = dict(spat)
             if dere is not None:
                 rec["dereverb"] = dict(dere)
             records[i] = dict(rec, **levels[j])

@@ -42,7 +42,7 @@ EXPORTS = [
     "dsn_mask_refine",
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
-    "dsn_beamform", "dsn_dereverb",
+    "dsn_beamform", "dsn_beamform_spatial", "dsn_dereverb",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
@@ -783,6 +783,17 @@ def beamform_item_bytes(n_fft: int, hop: int, L: int, Cn: int, n: int) -> int:
     return 8 * (owners + 1) * n * Cn * (Cn + 1) * (n_fft // 2 + 1)
 
 
+def _check_ref(who, ref, ch, Cn) -> int:
+    """A reference channel every item has (ch: the items' channel counts, or None: Cn each) -> ref as an int"""
+    if isinstance(ref, bool) or int(ref) != ref:
+        raise ValueError(f"{who}: ref = {ref!r} is not a channel index")
+    ref = int(ref)
+    for b, v in enumerate(ch if ch is not None else [Cn]):
+        if ref < 0 or ref >= v:
+            raise ValueError(f"{who}: ref = {ref} outside [0, {v}): item {b} has {v} channels")
+    return ref
+
+
 def check_beamform(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
                    reg=1e-3, postfilter=None, workspace_budget=0) -> tuple:
     """The refusals of dsn_beamform (include/ditsep_hip.h), raised by name before the library is touched: mix that is
@@ -800,16 +811,84 @@ def check_beamform(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=
     ln = _check_item_lens("beamform", lens, B, L, n_fft)
     reg = _check_reg("beamform", reg)
     ch = _check_channels("beamform", channels, B, Cn)
-    if isinstance(ref, bool) or int(ref) != ref:
-        raise ValueError(f"beamform: ref = {ref!r} is not a channel index")
-    ref = int(ref)
-    for b, v in enumerate(ch if ch is not None else [Cn]):
-        if ref < 0 or ref >= v:
-            raise ValueError(f"beamform: ref = {ref} outside [0, {v}): item {b} has {v} channels")
+    ref = _check_ref("beamform", ref, ch, Cn)
     budget = _check_budget("beamform", workspace_budget, BEAMFORM_DEFAULT_BUDGET,
                            beamform_item_bytes(n_fft, hop, L, Cn, n),
                            f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L}")
     return (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, BEAMFORM_POSTFILTERS[postfilter], budget
+
+
+SPATIAL_MAX_ITERATIONS, SPATIAL_MAX_NOISE, SPATIAL_DEFAULT_BUDGET = 16, 0.9, 512 << 20
+# one pass, a tenth of the prior mass for the noise class and a tenth spread over the sources; reg and eps load the
+# classes' covariances.  These are not tuned.
+SPATIAL_DEFAULTS = dict(iterations=1, noise=0.1, floor=0.1, reg=1e-3, eps=1e-10)
+
+
+def spatial_options(spatial) -> Optional[dict]:
+    """The `spatial` keyword of the separation entry points as the mask-refinement keywords of Engine.beamform_spatial
+    (reg and eps are its mask_reg and mask_eps): None (off, the default) -> None; True -> SPATIAL_DEFAULTS; a dict of
+    iterations / noise / floor / reg / eps -> the defaults with those replaced.  Anything else, False and an unknown key
+    included, is refused by name."""
+    return _options("spatial", spatial, SPATIAL_DEFAULTS, "None, True", lambda v: {} if v is True else None)
+
+
+def spatial_beamform_keywords(beam: dict, spatial: Optional[dict]) -> dict:
+    """The keywords of the beamforming step of the separation entry points: `beam` (beamform_options) for
+    Engine.beamform, or, with `spatial` (spatial_options), those of Engine.beamform_spatial.  spatial= without
+    beamform= and spatial= with the mask post-filter are refused by name."""
+    if spatial is None:
+        return dict(beam)
+    if beam is None:
+        raise ValueError("spatial= refines the masks of the beamformer: it needs beamform=")
+    if BEAMFORM_POSTFILTERS[beam["postfilter"]]:
+        raise ValueError("spatial= does not go with postfilter='mask': the post-filter would apply the estimates' masks, "
+                         "not the refined ones (there is no gamma post-filter)")
+    kw = {k: v for k, v in beam.items() if k != "postfilter"}
+    return dict(kw, iterations=spatial["iterations"], noise=spatial["noise"], floor=spatial["floor"],
+                mask_reg=spatial["reg"], mask_eps=spatial["eps"])
+
+
+def spatial_item_bytes(n_fft: int, hop: int, L: int, Cn: int, n: int) -> int:
+    """The workspace one item of a [B, C, L] batch needs in dsn_beamform_spatial: per bin the statistics of n + 1
+    classes (C (C + 1) doubles each), the spectra (C x Fs complex floats), the masks (n x Fs floats) and a flag, Fs =
+    1 + ceil(L / hop) frames.  The one formula: the C side computes the same number."""
+    bins, Fs = n_fft // 2 + 1, 1 + (L + hop - 1) // hop
+    return bins * (8 * (n + 1) * Cn * (Cn + 1) + Fs * (8 * Cn + 4 * n) + 4)
+
+
+def check_spatial(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
+                  reg=1e-3, iterations=1, noise=0.1, floor=0.1, mask_reg=1e-3, mask_eps=1e-10,
+                  workspace_budget=0) -> tuple:
+    """The refusals of dsn_beamform_spatial (include/ditsep_hip.h), raised by name before the library is touched: what
+    check_beamform refuses (there is no post-filter); iterations outside [0, 16]; noise outside [0, 0.9]; floor outside
+    [0, 1]; mask_reg not finite or < 0; mask_eps not finite or <= 0; a workspace budget smaller than one item.
+    -> ((B, C, n, L), lens or None, channels or None, ref, n_fft, hop, power, eps, reg, iterations, noise, floor,
+    mask_reg, mask_eps, workspace_budget)"""
+    who = "beamform_spatial"
+    B, Cn, n, L = _check_mix_est(who, mix_shape, est_shape)
+    if Cn < 1 or Cn > BEAMFORM_MAX_CHANNELS:
+        raise ValueError(f"{who}: C = {Cn} outside [1, {BEAMFORM_MAX_CHANNELS}]")
+    n_fft, hop, power, eps = _check_stft(who, B, n, n_fft, hop, power, eps)
+    ln = _check_item_lens(who, lens, B, L, n_fft)
+    reg = _check_reg(who, reg)
+    ch = _check_channels(who, channels, B, Cn)
+    ref = _check_ref(who, ref, ch, Cn)
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 0 <= int(iterations) <= SPATIAL_MAX_ITERATIONS:
+        raise ValueError(f"{who}: iterations = {iterations!r} outside [0, {SPATIAL_MAX_ITERATIONS}]")
+    noise, floor = float(noise), float(floor)
+    if not 0.0 <= noise <= SPATIAL_MAX_NOISE:
+        raise ValueError(f"{who}: noise = {noise} outside [0, {SPATIAL_MAX_NOISE}]")
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError(f"{who}: floor = {floor} outside [0, 1]")
+    mask_reg, mask_eps = float(mask_reg), float(mask_eps)
+    if not math.isfinite(mask_reg) or mask_reg < 0.0:
+        raise ValueError(f"{who}: mask_reg = {mask_reg} is not a finite number >= 0")
+    if not math.isfinite(mask_eps) or not mask_eps > 0.0:
+        raise ValueError(f"{who}: mask_eps = {mask_eps} is not a finite positive number")
+    budget = _check_budget(who, workspace_budget, SPATIAL_DEFAULT_BUDGET, spatial_item_bytes(n_fft, hop, L, Cn, n),
+                           f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L}")
+    return ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, int(iterations), noise, floor, mask_reg, mask_eps,
+            budget)
 
 
 DEREVERB_MAX_CHANNELS, DEREVERB_MAX_TAPS, DEREVERB_MAX_DELAY, DEREVERB_MAX_UNKNOWNS, DEREVERB_MAX_ITERATIONS = 8, 16, 8, 80, 8
@@ -1318,6 +1397,8 @@ def load_library() -> C.CDLL:
     lib.dsn_pcm_encode_frames.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, vp, C.c_int64, i64p, i64p, vp]
     lib.dsn_beamform.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
                                  C.c_int64, vp, f64p, vp]
+    lib.dsn_beamform_spatial.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
+                                         C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp, f64p, f64p, i32p, vp]
     lib.dsn_dereverb.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, ci, C.c_float, C.c_float, C.c_int64, vp,
                                  f64p, i32p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
@@ -2183,6 +2264,54 @@ class Engine:
                                           power, eps, reg, post, budget, _ptr(out), _host(w), self._stream()),
                     "dsn_beamform")
         return (out, {"w": w}) if return_info else out
+
+    # ------------------------------------------------------------------ beamforming on spatially refined masks
+    def beamform_spatial(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
+                         reg=1e-3, iterations=1, noise=0.1, floor=0.1, mask_reg=1e-3, mask_eps=1e-10, workspace_budget=0,
+                         return_info=False):
+        """`beamform` with the masks refined by where the sources sit (dsn_beamform_spatial, csrc/spatial.hip; the
+        definition is in include/ditsep_hip.h and tests/spatial_restatement.py): mix [B, C, L] (C <= 8), est
+        [B, n, L] -> [B, n, L].  Per bin a complex angular central Gaussian mixture model (Ito et al. 2016) is fitted
+        to the normalised channel vectors z = X / |X| in float64, one class per source and, with noise > 0, one for
+        the noise, with the estimates' masks as time-frequency priors a_k = (1 - noise) ((1 - floor) M_k + floor / n)
+        (guided source separation: Nakatani et al. 2017, Drude & Haeb-Umbach 2017): `iterations` times the posteriors
+        gamma from the classes' covariances B_k (by Cholesky) and the covariances from the posteriors, loaded with
+        mask_reg tr(B_k) / C + mask_eps.  The posteriors replace the masks in the beamformer's statistics, the noise
+        class enters every source's interference, and the weights and the filter are `beamform`'s (no post-filter).
+        lens / channels / workspace_budget / lists as in `beamform` (items of native.spatial_item_bytes each); each
+        item gets the bits it gets alone; an item with one channel skips the model.  return_info=True: (out, {"w":
+        complex128 [B, n, bins, C], "gamma": float64 [B, K, bins, F] (K = n + 1 with noise > 0; zero in frames an item
+        does not have), "fail": int32 [B, bins], 1 where a pivot failed and the bin fell back to its priors}) on the
+        host.  Not trained and not tuned: what it does to separation quality is unmeasured.  Needs no score network
+        and no codec; two calls give identical bits."""
+        kw = dict(ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps, reg=reg, iterations=iterations, noise=noise,
+                  floor=floor, mask_reg=mask_reg, mask_eps=mask_eps, workspace_budget=workspace_budget,
+                  return_info=return_info)
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
+                raise ValueError("beamform_spatial: a list of mixtures goes with a list of as many estimates and no lens "
+                                 "or channels")
+            ln = [int(e.shape[-1]) for e in est]
+            for b, (m, e) in enumerate(zip(mix, est)):
+                if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
+                    raise ValueError(f"beamform_spatial: item {b} must be mix [C, L] and est [n, L] (got "
+                                     f"{tuple(m.shape)} and {tuple(e.shape)})")
+            mp, ep, ln, ch, cut = self._pad_items(mix, est)
+            return cut(self.beamform_spatial(mp, ep, lens=ln, channels=ch, **kw))
+        ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, iterations, noise, floor, mask_reg, mask_eps,
+         budget) = check_spatial(tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg,
+                                 iterations, noise, floor, mask_reg, mask_eps, workspace_budget)
+        mix, est = _dev32(mix, self.device), _dev32(est, self.device)
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        bins, K, Fs = n_fft // 2 + 1, n + (C.c_float(noise).value > 0), 1 + (L + hop - 1) // hop
+        w = torch.zeros((B, n, bins, Cn), dtype=torch.complex128) if return_info else None
+        gamma = torch.zeros((B, K, bins, Fs), dtype=torch.float64) if return_info else None
+        bad = torch.zeros((B, bins), dtype=torch.int32) if return_info else None
+        self._check(self.lib.dsn_beamform_spatial(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref,
+                                                  n_fft, hop, power, eps, reg, iterations, noise, floor, mask_reg,
+                                                  mask_eps, budget, _ptr(out), _host(w), _host(gamma),
+                                                  _host(bad, C.c_int32), self._stream()), "dsn_beamform_spatial")
+        return (out, {"w": w, "gamma": gamma, "fail": bad}) if return_info else out
 
     # ------------------------------------------------------------------ WPE dereverberation
     def dereverb(self, mix, lens=None, channels=None, taps=10, delay=3, iterations=3, n_fft=512, hop=128, reg=1e-4,

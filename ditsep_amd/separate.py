@@ -97,6 +97,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Diagonal loading of the beamformer's solve, relative to the mean interference power")
     p.add_argument("--beamform-post", default="none", choices=["none", "mask"],
                    help="Post-filter of the beamformed spectrum: the speaker's own mask, or none")
+    p.add_argument("--spatial", action="store_true",
+                   help="With --beamform: refine the masks that steer the beamformer with a spatial mixture model "
+                        "(guided cACGMM) fitted to the recording's own channels (not a trained step; not tuned; off by "
+                        "default)")
+    p.add_argument("--spatial-iterations", type=int, default=1, help="Expectation-maximisation passes of the model")
+    p.add_argument("--spatial-noise", type=float, default=0.1, help="Prior mass of the noise class (0: no noise class)")
+    p.add_argument("--spatial-floor", type=float, default=0.1,
+                   help="Share of the prior spread equally over the speakers, whatever the estimates say")
+    p.add_argument("--spatial-reg", type=float, default=1e-3,
+                   help="Diagonal loading of the classes' covariances, relative to their mean diagonal")
     p.add_argument("--dereverb", action="store_true",
                    help="Dereverberate every recording first (weighted prediction error on up to 8 channels, kept for "
                         "the steps that use them; not a trained step; off by default)")
@@ -173,6 +183,14 @@ def beamform_of(args):
                 postfilter=None if args.beamform_post == "none" else args.beamform_post)
 
 
+def spatial_of(args):
+    """The `spatial` keyword of separate_files from the parsed flags: None unless --spatial is given."""
+    if not args.spatial:
+        return None
+    return dict(iterations=args.spatial_iterations, noise=args.spatial_noise, floor=args.spatial_floor,
+                reg=args.spatial_reg)
+
+
 def dereverb_of(args):
     """The `dereverb` keyword of separate_files from the parsed flags: None unless --dereverb is given."""
     if not args.dereverb:
@@ -225,7 +243,7 @@ def main(argv=None) -> int:
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
                                            stems=stems_of(args), beamform=beamform_of(args),
-                                           dereverb=dereverb_of(args),
+                                           dereverb=dereverb_of(args), spatial=spatial_of(args),
                                            loudness=loudness_of(args), limit=limit_of(args),
                                            denoise=args.denoise, **kw)
         except ValueError as e:

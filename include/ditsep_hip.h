@@ -667,6 +667,56 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
                  const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
                  int64_t workspace_budget, float* out, double* info_w, void* stream);
 
+/* dsn_beamform on spatially refined masks: between the estimates' masks and the MVDR filter a complex angular central
+ * Gaussian mixture model (cACGMM; Ito, Araki, Nakatani 2016) learns where every source sits, with the estimates' masks
+ * as time-frequency priors (Nakatani et al. 2017; Drude & Haeb-Umbach 2017: "guided source separation"), and its
+ * posteriors gamma replace the masks in the statistics (csrc/spatial.hip, restated in float64 in
+ * tests/spatial_restatement.py).  A definition, not a trained step; nothing calls it unless asked to.  mix, est, out,
+ * lens, channels, ref, n_fft, hop, power, eps and reg are dsn_beamform's; the spectra X_c(f,t) and the fp32 masks M_k
+ * are dsn_mask_refine's, with the bits they have there, widened to fp64.  Per item (C_b channels) and bin f, in fp64:
+ *   setup       p(t) = sum_c |X_c|^2 in channel order; a frame is live where p > 0 (false for NaN);
+ *               z(t) = X(t) / sqrt(p(t)).  Classes: K = n + 1 if noise > 0, otherwise n.  Priors
+ *               a_k = (1 - noise) ((1 - floor) M_k + floor / n) for k < n, a_n = noise.  B_k = I.
+ *   `iterations` times
+ *     E-step    B_k = L L^H by Cholesky, q_k(t) = z^H B_k^-1 z = sum_c |y_c|^2 with L y = z, l_k = 2 sum_c log L_cc,
+ *               log gamma_k(t) = log a_k - l_k - C_b log q_k, normalised over the classes in class order with the
+ *               maximum subtracted
+ *     M-step    over the live frames in increasing t whatever the tiling:
+ *               B_k = C_b sum_t (gamma_k / q_k) z z^H / sum_t gamma_k, the identity where sum_t gamma_k is zero (a
+ *               class whose prior is zero everywhere); then B_k += (mask_reg tr(B_k) / C_b + mask_eps) I.
+ *               A Cholesky pivot of any B_k that is not finite and positive makes every B_k of that bin the identity
+ *               from then on (gamma is then the normalised prior); the bin is flagged in info_fail.
+ *   after the last M-step one more E-step gives gamma; dead frames take gamma = a.  gamma stays fp64 and is never
+ *   rounded before use.  An item with one channel skips the model and takes gamma = a, and so does every item with
+ *   iterations = 0: nothing has been learned, every class has B_k = I, and the posterior is the prior.
+ *   statistics  N_k(f) = sum_t gamma_k X X^H for all K classes in increasing t, the upper triangle, on the
+ *               unnormalised spectra as in dsn_beamform
+ *   then dsn_beamform's interference, loading, solve and weights with Q_i = sum_{j != i, j < K} N_j -- the noise class
+ *   enters every Q_i and gets no filter --, its apply without post-filter and its synthesis.
+ * With iterations = 0, noise = 0, floor = 0, gamma is M and the call is dsn_beamform up to the order of its sums (the
+ * fp32 masks of a frame sum to 1 only up to fp32 rounding, which a normalisation would move into the weights).  A NaN in an estimate makes the priors of the frames it touches NaN, every bin
+ * fails its first pivot, N is NaN and w = e_ref: the reference channel is handed back.  A NaN in the mixture makes the
+ * frames it touches dead; N is NaN as well and w = e_ref, with no bin flagged.  No floating-point atomics: an item has
+ * the same bits alone, at any batch position, under any padding, from a base pointer of any 4-byte alignment, under
+ * any workspace budget and in a second call.  The statistics, spectra, masks and flags of a chunk of items live in a
+ * workspace the context keeps, (n_fft / 2 + 1) (8 (n + 1) C (C + 1) + Fs (8 C + 4 n) + 4) bytes per item with
+ * Fs = 1 + ceil(Lmax / hop); the batch is processed in chunks of as many items as fit `workspace_budget` bytes
+ * (0: 512 MiB); the weights are kept for the whole batch outside that budget.  info_w (HOST, as dsn_beamform's),
+ * info_gamma (HOST, [B][K][n_fft / 2 + 1][Fs] doubles: gamma as the statistics used it, zero in frames an item does
+ * not have) and info_fail (HOST, [B][n_fft / 2 + 1] int32: 1 where the bin failed a pivot) or NULL; with any of them the
+ * stream is synchronised.  The call uploads lens and channels when given and then synchronises the stream, so with
+ * them it must not be captured into a graph.  Needs no score network and no codec.  Not trained and not tuned; its
+ * effect on separation quality is unmeasured; time-frequency priors only (no activity-only guidance); no gamma
+ * post-filter.
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_beamform refuses (it has no post-filter);
+ * iterations outside [0, 16]; noise outside [0, 0.9]; floor outside [0, 1]; mask_reg not finite or < 0; mask_eps not
+ * finite or <= 0. */
+int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                         const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                         float reg, int iterations, float noise, float floor, float mask_reg, float mask_eps,
+                         int64_t workspace_budget, float* out, double* info_w, double* info_gamma, int32_t* info_fail,
+                         void* stream);
+
 /* Weighted prediction error (WPE) dereverberation: the channels of a reverberant recording in, the same channels with
  * the late reverberation predicted from their own delayed past and subtracted out (Nakatani et al. 2010; Yoshioka &
  * Nakatani 2012; the offline recipe; csrc/dereverb.hip, restated in float64 in tests/dereverb_restatement.py).  A
