@@ -3,7 +3,9 @@
 // the mixture's own channels, and a minimum-variance distortionless-response filter (Souden, Benesty, Affes 2010)
 // returns one mono signal per source.  Frames, spectra, masks and output samples are formed by the functions of
 // maskrefine_dev.h that maskrefine.hip calls (mr_tables, mr_load, mr_fft, mr_split, mr_masks, mr_merge, mr_add,
-// mr_finish), so they have the bits they have there.  Three launches per chunk of items, then one for the batch:
+// mr_finish), so they have the bits they have there; the statistics of a range of frames and the channel contraction are
+// beamform_dev.h's (bf_stats_frames, bf_contract), which beamform_track.hip calls as well.  Three launches per chunk of
+// items, then one for the batch:
 //   stats    workgroup (o, b, i) owns the frames [o fpo, (o + 1) fpo) of item b for source i -- every frame has exactly
 //            one owner per source; fpo is a whole number of spans, more than one where the item has more than
 //            BEAMFORM_MAX_OWNERS spans --, transforms the item's C_b channels and n estimates in groups of
@@ -30,14 +32,9 @@ namespace {
 
 #include "maskrefine_dev.h"
 
-constexpr int BF_MAX_CH = BEAMFORM_MAX_CH;
-constexpr int BF_TRI = BF_MAX_CH * (BF_MAX_CH + 1) / 2;                          // Hermitian entries held in registers
-constexpr int BF_BF = (BF_MAX_CH + MR_MAX_SRC) * (MR_POINTS / 2) / MRT;          // butterflies per thread and stage
-constexpr int BF_LANES = 8, BF_GROUPS = MRT / BF_LANES;                          // weights launch: lanes per system
+#include "beamform_dev.h"
 
-__host__ __device__ inline int bf_tri(int C) { return C * (C + 1) / 2; }
-// entry (c1 <= c2) of the upper triangle of a C x C matrix, row after row
-__host__ __device__ inline int bf_idx(int C, int c1, int c2) { return c1 * C - c1 * (c1 - 1) / 2 + (c2 - c1); }
+constexpr int BF_LANES = 8, BF_GROUPS = MRT / BF_LANES;                          // weights launch: lanes per system
 
 // frames one owner takes of an item of F frames: whole spans of `base` frames, as few as keep the owners within the cap
 __host__ __device__ inline int bf_owner_frames(int F, int base) {
@@ -45,123 +42,23 @@ __host__ __device__ inline int bf_owner_frames(int F, int base) {
   return base * ((spans + BEAMFORM_MAX_OWNERS - 1) / BEAMFORM_MAX_OWNERS);
 }
 
-// Source `src`, bin j: rows [R0, R1) of M_src X X^H (upper triangle, X_c1 conj X_c2) of the `frames` frames in LDS,
-// added to acc in frame order.  Products and sums in fp64 on the widened fp32 spectra and masks.
-template <int H, int R0, int R1>
-__device__ __forceinline__ void bf_accumulate(const MaskRefineShape& q, const float2* buf, const float2* tw, int Cb,
-                                              int src, int j, int frames, double (&acc)[BF_TRI][2]) {
-  const bool lower = 2 * j <= H;
-  const int k = lower ? j : H - j, km = (H - k) & (H - 1);
-  const float2 t = tw[k];
-  for (int fg = 0; fg < frames; ++fg) {
-    double xr[BF_MAX_CH], xi[BF_MAX_CH];
-#pragma unroll
-    for (int c = 0; c < BF_MAX_CH; ++c) {
-      xr[c] = xi[c] = 0.0;
-      if (c < Cb) {
-        const float2* a = buf + c * MR_POINTS + fg * H;
-        float2 xk, xm;
-        mr_split(a[k], a[km], t, xk, xm);
-        xr[c] = lower ? xk.x : xm.x;
-        xi[c] = lower ? xk.y : xm.y;
-      }
-    }
-    float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
-    mr_masks(q, buf + Cb * MR_POINTS + fg * H, k, km, t, mk, mm);
-    float mi = 0.f;
-#pragma unroll
-    for (int s = 0; s < MR_MAX_SRC; ++s)
-      if (s == src) mi = lower ? mk[s] : mm[s];
-    const double m = mi;
-#pragma unroll
-    for (int c1 = R0; c1 < R1; ++c1)
-#pragma unroll
-      for (int c2 = c1; c2 < BF_MAX_CH; ++c2)
-        if (c2 < Cb) {
-          const int u = c1 * BF_MAX_CH - c1 * (c1 - 1) / 2 + (c2 - c1);
-          acc[u][0] += m * (xr[c1] * xr[c2] + xi[c1] * xi[c2]);
-          acc[u][1] += m * (xi[c1] * xr[c2] - xr[c1] * xi[c2]);
-        }
-  }
-}
-
-// Bin j >= 256 of one frame group: rows [R0, R1) summed over the group in registers, then added to the owner's partial.
-template <int H, int R0, int R1>
-__device__ __forceinline__ void bf_high_bin(const MaskRefineShape& q, const float2* buf, const float2* tw, int Cb,
-                                            int src, int j, int frames, bool first, double* __restrict__ partw) {
-  double acc[BF_TRI][2];
-#pragma unroll
-  for (int u = 0; u < BF_TRI; ++u) acc[u][0] = acc[u][1] = 0.0;
-  bf_accumulate<H, R0, R1>(q, buf, tw, Cb, src, j, frames, acc);
-#pragma unroll
-  for (int c1 = R0; c1 < R1; ++c1)
-#pragma unroll
-    for (int c2 = c1; c2 < BF_MAX_CH; ++c2)
-      if (c2 < Cb) {
-        const int u = c1 * BF_MAX_CH - c1 * (c1 - 1) / 2 + (c2 - c1);
-        double* d = partw + 2L * bf_idx(q.C, c1, c2) * (H + 1) + j;
-        d[0] = first ? acc[u][0] : d[0] + acc[u][0];
-        d[H + 1] = first ? acc[u][1] : d[H + 1] + acc[u][1];
-      }
-}
-
-// grid (owners, items, n).  part [items][gridDim.x][n][2 tri(C)][H + 1].
-// Dynamic LDS: float2 tw[H] | float2 buf[C + n][G][H] | float win[NFFT]
-// A thread owns bin `tid` for the whole launch and keeps that bin's sums of its one source in registers over all the
-// owner's frames (36 complex doubles at C = 8: one source is what the registers hold, so the source is in the grid and
-// the transforms are formed once per source); they are stored once at the end.  Bins 256 and up (n_fft >= 512) are
-// added a frame group at a time into the partial in global memory, by the same thread every group.
+// grid (owners, items, n).  part [items][gridDim.x][n][2 tri(C)][H + 1]; the owner's frames go through bf_stats_frames.
 template <int NFFT>
 __global__ __launch_bounds__(MRT) void beamform_stats_kernel(const MaskRefineShape q, const float* __restrict__ mix,
                                                              const float* __restrict__ est,
                                                              const int* __restrict__ lens, const int* __restrict__ chans,
                                                              double* __restrict__ part) {
-  constexpr int H = NFFT / 2, G = MR_POINTS / H, SPAN = mr_span(NFFT);
-  extern __shared__ __attribute__((aligned(16))) float2 bf_lds[];
-  const int n = q.n, hop = q.hop, tid = threadIdx.x, b = blockIdx.y, src = blockIdx.z;
+  constexpr int H = NFFT / 2, SPAN = mr_span(NFFT);
+  const int n = q.n, hop = q.hop, b = blockIdx.y, src = blockIdx.z;
   const int Cb = chans ? chans[b] : q.C;
   const MrItem it = mr_item(lens, b, q.Lmax, hop);
   const int F = it.F;
   const int fpo = bf_owner_frames(F, SPAN / hop);
   if ((long)blockIdx.x * fpo >= F) return;   // (uniform)
-  float2* tw = bf_lds;
-  float2* buf = tw + H;
-  float* win = reinterpret_cast<float*>(buf + (q.C + n) * MR_POINTS);
-  const float* mixb = mix + (long)b * q.C * q.Lmax;
-  const float* estb = est + (long)b * n * q.Lmax;
-  mr_tables<H>(tw, win, tid);
   const int f_first = blockIdx.x * fpo, f_last = min(F, f_first + fpo) - 1;
   const int T2 = 2 * bf_tri(q.C);
-  double* partw = part + (((long)b * gridDim.x + blockIdx.x) * n + src) * T2 * (H + 1);
-  double own[BF_TRI][2];
-#pragma unroll
-  for (int u = 0; u < BF_TRI; ++u) own[u][0] = own[u][1] = 0.0;
-
-  for (int f0 = f_first; f0 <= f_last; f0 += G) {
-    __syncthreads();   // the tables are in; the previous group's spectra have been read
-    mr_load<H>(buf, win, mixb, estb, q.Lmax, it, hop, Cb, n, f0, f_last, tid);
-    __syncthreads();
-    mr_fft<H, false, BF_BF>(buf, tw, (Cb + n) * (MR_POINTS / 2), tid);
-    const int frames = min(G, f_last - f0 + 1);
-    if (tid <= H) bf_accumulate<H, 0, BF_MAX_CH>(q, buf, tw, Cb, src, tid, frames, own);
-    if (H + 1 > MRT)
-      for (int j = tid + MRT; j <= H; j += MRT) {   // (in two halves of the triangle: `own` stays in registers)
-        bf_high_bin<H, 0, 3>(q, buf, tw, Cb, src, j, frames, f0 == f_first, partw);
-        bf_high_bin<H, 3, BF_MAX_CH>(q, buf, tw, Cb, src, j, frames, f0 == f_first, partw);
-      }
-  }
-  if (tid <= H) {
-    int u = 0;
-#pragma unroll
-    for (int c1 = 0; c1 < BF_MAX_CH; ++c1)
-#pragma unroll
-      for (int c2 = c1; c2 < BF_MAX_CH; ++c2, ++u)
-        if (c2 < Cb) {
-          double* d = partw + 2L * bf_idx(q.C, c1, c2) * (H + 1) + tid;
-          d[0] = own[u][0];
-          d[H + 1] = own[u][1];
-        }
-  }
+  bf_stats_frames<NFFT>(q, mix + (long)b * q.C * q.Lmax, est + (long)b * n * q.Lmax, it, Cb, src, f_first, f_last,
+                        part + (((long)b * gridDim.x + blockIdx.x) * n + src) * T2 * (H + 1));
 }
 
 // N [items][n][2 tri(C)][bins] from part [items][OW][n][2 tri(C)][bins]: the item's own owners, in owner order.  Entries
@@ -355,40 +252,13 @@ __global__ __launch_bounds__(MRT) void beamform_apply_kernel(const MaskRefineSha
     mr_fft<H, false, BF_BF>(buf, tw, (Cb + ne) * (MR_POINTS / 2), tid);
     // ---- contract: one thread per (frame, pair of bins k and H - k); channel 0's slot becomes Y, packed again
     for (int e = tid; e < G * NP; e += MRT) {
-      const int fg = e / NP, k = e - fg * NP, km = (H - k) & (H - 1);
+      const int fg = e / NP, k = e - fg * NP;
       if (f0 + fg > f_last) continue;
-      const float2 t = tw[k];
-      const double* wk = wb + 2L * k * q.C;
-      const double* wm = wb + 2L * (H - k) * q.C;
-      double ykr = 0.0, yki = 0.0, ymr = 0.0, ymi = 0.0;
-      for (int c = 0; c < Cb; ++c) {   // conj(w_c) X_c
-        const float2* a = buf + c * MR_POINTS + fg * H;
-        float2 xk, xm;
-        mr_split(a[k], a[km], t, xk, xm);
-        const double kr = wk[2 * c], ki = wk[2 * c + 1], mr = wm[2 * c], mi = wm[2 * c + 1];
-        const double pkr = kr * (double)xk.x + ki * (double)xk.y, pki = kr * (double)xk.y - ki * (double)xk.x;
-        const double pmr = mr * (double)xm.x + mi * (double)xm.y, pmi = mr * (double)xm.y - mi * (double)xm.x;
-        ykr = c == 0 ? pkr : ykr + pkr;
-        yki = c == 0 ? pki : yki + pki;
-        ymr = c == 0 ? pmr : ymr + pmr;
-        ymi = c == 0 ? pmi : ymi + pmi;
-      }
-      float2 yk = make_float2((float)ykr, (float)yki), ym = make_float2((float)ymr, (float)ymi);
-      if (post) {
-        float mk[MR_MAX_SRC], mm[MR_MAX_SRC];
-        mr_masks(q, buf + Cb * MR_POINTS + fg * H, k, km, t, mk, mm);
-        float sk = 0.f, sm = 0.f;
-#pragma unroll
-        for (int s = 0; s < MR_MAX_SRC; ++s)
-          if (s == src) sk = mk[s], sm = mm[s];
-        yk = make_float2(sk * yk.x, sk * yk.y);
-        ym = make_float2(sm * ym.x, sm * ym.y);
-      }
-      float2 zk, zm;
-      mr_merge(yk, ym, t, zk, zm);
-      float2* o = buf + fg * H;
-      o[k] = zk;
-      if (km != k) o[km] = zm;
+      bf_contract<H>(q, post, buf, tw, Cb, src, fg, k, [&](int j, int c, double& re, double& im) {
+        const double* wj = wb + 2L * j * q.C;
+        re = wj[2 * c];
+        im = wj[2 * c + 1];
+      });
     }
     __syncthreads();
     mr_fft<H, true, BF_BF>(buf, tw, MR_POINTS / 2, tid);

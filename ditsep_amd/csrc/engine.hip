@@ -3544,6 +3544,71 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
   });
 }
 
+// ---- block-adaptive MVDR weights (beamform_track.hip, beamform.hip; include/ditsep_hip.h states the definition)
+int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                       const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                       float reg, int postfilter, int block_frames, int context, int interpolate,
+                       int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_beamform_track";
+    if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
+    if (postfilter != DSN_BEAMFORM_POST_NONE && postfilter != DSN_BEAMFORM_POST_MASK)
+      fail(DSN_EINVAL, "%s: postfilter = %d is not one of 0 (DSN_BEAMFORM_POST_NONE), 1 (DSN_BEAMFORM_POST_MASK)", who,
+           postfilter);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (block_frames < TRACK_MIN_BLOCK || block_frames > TRACK_MAX_BLOCK)
+      fail(DSN_EINVAL, "%s: block_frames = %d outside [%d, 2^20]", who, block_frames, TRACK_MIN_BLOCK);
+    if (context < 0 || context > TRACK_MAX_CONTEXT)
+      fail(DSN_EINVAL, "%s: context = %d outside [0, %d]", who, context, TRACK_MAX_CONTEXT);
+    if (interpolate != 0 && interpolate != 1) fail(DSN_EINVAL, "%s: interpolate = %d is not 0 or 1", who, interpolate);
+    check_stft(who, n_fft, hop);
+    check_power(who, power);
+    check_eps(who, eps);
+    check_reg(who, reg);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, channels, C, &ref);
+    const int Kmax = track_blocks(hop, Lmax, block_frames);
+    if (Kmax > TRACK_MAX_BLOCKS)
+      fail(DSN_EINVAL, "%s: %d blocks of block_frames = %d frames at Lmax = %d, hop = %d: more than %d", who, Kmax,
+           block_frames, Lmax, hop, TRACK_MAX_BLOCKS);
+    const size_t per_item = track_item_bytes(n_fft, hop, Lmax, C, n, block_frames);
+    const int ipc = items_per_chunk(who, workspace_budget, TRACK_DEFAULT_BUDGET, per_item, B, C, "n", n, n_fft, hop, Lmax);
+    const size_t row = sizeof(float) * (size_t)B * Lmax;
+    if (overlaps(out, row * n, mix, row * C) || overlaps(out, row * n, est, row * n))
+      fail(DSN_EINVAL, "%s: out overlaps mix or est (neighbouring workgroups read the samples around a span)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int *dlens = nullptr, *dch = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "track_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    if (channels) dch = (const int*)upload_table(ctx, "track_channels", channels, sizeof(int32_t) * (size_t)B, st);
+    const size_t bins = (size_t)n_fft / 2 + 1, T2 = (size_t)C * (C + 1);
+    const size_t npart = (size_t)ipc * Kmax * n * T2 * bins, nw = (size_t)Kmax * n * bins * C * 2;   // (nw: per item)
+    char* ws = ctx->wsbuf<char>("track_ws", per_item * ipc);   // part | N | w | the blocks' channel counts
+    double* part = (double*)ws;
+    double* N = part + npart;
+    double* w = N + npart;
+    int* blockch = (int*)(w + nw * ipc);
+    for (int b0 = 0; b0 < B; b0 += ipc) {   // the chunk's workspace is reused from chunk to chunk on the one stream
+      const int items = std::min(ipc, B - b0);
+      const float *mixc = mix + (size_t)b0 * C * Lmax, *estc = est + (size_t)b0 * n * Lmax;
+      const int *lensc = dlens ? dlens + b0 : nullptr, *chc = dch ? dch + b0 : nullptr;
+      ctx->prof_launch("beamform_track",
+                       4.0 * (double)items * Lmax * ((double)C * (n + 1) + (postfilter ? 2.0 : 1.0) * n + n), st, [&] {
+        launch_track_weights(mixc, estc, lensc, chc, ref, part, N, w, blockch, items, C, n, Lmax, n_fft, hop, power, eps,
+                             reg, block_frames, context, st);
+        launch_track_apply(mixc, estc, lensc, chc, w, out + (size_t)b0 * n * Lmax, items, C, n, Lmax, n_fft, hop, power,
+                           eps, postfilter == DSN_BEAMFORM_POST_MASK, block_frames, interpolate, st);
+      });
+      HIPCHK(hipGetLastError());
+      if (info_w) {
+        HIPCHK(hipMemcpyAsync(info_w + (size_t)b0 * nw, w, sizeof(double) * nw * items, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+      }
+    }
+  });
+}
+
 // ---- beamforming on spatially refined masks (spatial.hip, beamform.hip; include/ditsep_hip.h states the definition)
 int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
                          const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,

@@ -483,6 +483,28 @@ void launch_beamform_apply(const float* mix, const float* est, const int* lens, 
                            float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
                            int post, hipStream_t s);
 
+// ---- block-adaptive MVDR weights (beamform_track.hip) ---------------------------------------------------------------
+// dsn_beamform_track: blocks of Tb frames, Kmax = track_blocks(hop, Lmax, Tb) per item.  launch_track_weights, three
+// launches: fp64 partials part [items][Kmax][n][C (C + 1)][bins] (grid (block, item, source): a block has one owner per
+// source), their sums over the blocks within `context` of each block N [items][Kmax][n][C (C + 1)][bins] together with
+// blockch [items][Kmax], the item's channel count for the blocks it has and 0 for the others (the solve then writes
+// zero weights there), and launch_beamform_solve with (item, block) as its item: w [items][Kmax][n][bins][C] complex
+// doubles.  launch_track_apply: launch_beamform_apply's layout with the weights of frame t interpolated between the
+// blocks k0 and k0 + 1 (track_frame_weight).  track_item_bytes: part, N, w and blockch of one item.
+#define TRACK_MIN_BLOCK 4
+#define TRACK_MAX_BLOCK (1 << 20)
+#define TRACK_MAX_CONTEXT 64
+#define TRACK_MAX_BLOCKS 4096
+#define TRACK_DEFAULT_BUDGET (512L << 20)
+int track_blocks(int hop, int Lmax, int Tb);
+size_t track_item_bytes(int nfft, int hop, int Lmax, int C, int n, int Tb);
+void launch_track_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref, double* part,
+                          double* N, double* w, int* blockch, int items, int C, int n, int Lmax, int nfft, int hop,
+                          int power, float eps, float reg, int Tb, int context, hipStream_t s);
+void launch_track_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
+                        float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps, int post,
+                        int Tb, int interpolate, hipStream_t s);
+
 // ---- spatial mask refinement for the beamformer (spatial.hip) --------------------------------------------------------
 // mix [items][C][Lmax], est [items][n][Lmax] fp32, lens / chans [items] (device) or null.  Two launches: the transforms
 // of the channels and the estimates, spectra and fp32 masks bin-major into the workspace, and one workgroup per

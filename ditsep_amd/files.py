@@ -90,7 +90,7 @@ def _padded(rows, device):
 
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
-                   stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None,
+                   stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None, track=None,
                    **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
@@ -112,6 +112,12 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             raise ValueError("spatial= does not go with stems=: it refines the masks of the beamformer, which stems= "
                              "does not run")
         native.spatial_beamform_keywords(beam, spat)
+    trk = native.track_options(track)
+    if trk is not None:
+        if stems is not None:
+            raise ValueError("track= does not go with stems=: it adapts the weights of the beamformer, which stems= "
+                             "does not run")
+        native.track_beamform_keywords(beam, trk, fs, spat)
     if beam is not None and stems is not None:
         raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, stems= "
                          "the mixture's channels")
@@ -235,7 +241,7 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             return finish_stems(idx, clips, est, label, channels_fs)
         if beam is not None:
             est = model._beamform_step([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est),
-                                       beam, spat)
+                                       beam, spat, trk)
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)
@@ -263,6 +269,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 rec["beamform"] = beam["ref"]
             if spat is not None:
                 rec["spatial"] = dict(spat)
+            if trk is not None:
+                rec["track"] = dict(trk)
             if dere is not None:
                 rec["dereverb"] = dict(dere)
             records[i] = dict(rec, **levels[j])

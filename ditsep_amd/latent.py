@@ -440,8 +440,24 @@ class LatentDiffSep:
             raise ValueError("spatial= does not go with intermediate: the per-step states are not filtered")
         return native.spatial_beamform_keywords(bopts, spopts)
 
-    def _beamform_step(self, mix, est, bopts, spopts):
-        """The beamforming step of the entry points: Engine.beamform, or with spatial= Engine.beamform_spatial"""
+    @staticmethod
+    def _track_refusals(tropts, bopts, spopts, stems=None, latent=False, intermediate=None):
+        """What the `track` keyword refuses, before any device work"""
+        if stems is not None:
+            raise ValueError("track= does not go with stems=: it adapts the weights of the beamformer, which stems= "
+                             "does not run")
+        if latent:
+            raise ValueError("track= adapts the filter of waveforms: with latent=True there is no mixture to filter")
+        if intermediate:
+            raise ValueError("track= does not go with intermediate: the per-step states are not filtered")
+        native.track_beamform_keywords(bopts, tropts, None, spopts)
+
+    def _beamform_step(self, mix, est, bopts, spopts, tropts=None):
+        """The beamforming step of the entry points: Engine.beamform, with spatial= Engine.beamform_spatial, with track=
+        Engine.beamform_track on blocks of tropts["block"] seconds at the model's rate"""
+        if tropts is not None:
+            return self.engine.beamform_track(mix, est, **native.track_beamform_keywords(
+                bopts, tropts, self._model_rate("track="), spopts))
         if spopts is None:
             return self.engine.beamform(mix, est, **bopts)
         return self.engine.beamform_spatial(mix, est, **native.spatial_beamform_keywords(bopts, spopts))
@@ -452,7 +468,7 @@ class LatentDiffSep:
         return [c[ref:ref + 1].contiguous() for c in clips]
 
     @torch.no_grad()
-    def _separate_beamform(self, mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts=None):
+    def _separate_beamform(self, mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts=None, tropts=None):
         """`separate` with beamform=: mix [B, C, L] -> the mono call on channel `ref`, Engine.beamform against all
         channels at the model's rate (zero-extended or cut to the estimates' length), back to `sample_rate`"""
         eng = self.engine
@@ -460,6 +476,8 @@ class LatentDiffSep:
             raise ValueError(f"beamform= takes mix [B, C, L] (got {tuple(getattr(mix, 'shape', ()))})")
         B, Cn, L = (int(v) for v in mix.shape)
         self._beamform_refusals(bopts, [Cn], intermediate=kwargs.get("intermediate"))
+        if tropts is not None:
+            self._model_rate("track=")
         if sample_rate is None:
             mc = native._dev32(mix, eng.device)
         else:
@@ -467,7 +485,7 @@ class LatentDiffSep:
             mc = eng.resample(mix, sample_rate, fs)
         one = mc[:, bopts["ref"]:bopts["ref"] + 1].contiguous()
         est, *others = self.separate(one, target_dim, **mono_kw, **kwargs)
-        out = self._beamform_step(self._fit(mc, int(est.shape[-1])), est, bopts, spopts)
+        out = self._beamform_step(self._fit(mc, int(est.shape[-1])), est, bopts, spopts, tropts)
         if sample_rate is not None:
             out = eng.resample(out, fs, sample_rate)[..., :L]
         return (out, *others)
@@ -481,20 +499,23 @@ class LatentDiffSep:
         return clips
 
     @torch.no_grad()
-    def _beamform_of_lists(self, clips, rates, bopts, run, spopts=None):
+    def _beamform_of_lists(self, clips, rates, bopts, run, spopts=None, tropts=None):
         """The list entry points with beamform=: `clips` [C_b, L_b] each (or [L_b], [1, C_b, L_b]) at `rates` (None:
         the model's rate); run(list of [1, L'_b], channel `ref` of each) -> (list of [n, Le_b] estimates at the model's
         rate, *others).  -> (list of [n, L_b] at each clip's own rate, *others)"""
         eng = self.engine
         clips = self._as_channel_clips(clips, "beamform")
         self._beamform_refusals(bopts, [int(c.shape[0]) for c in clips])
+        if tropts is not None:
+            self._model_rate("track=")
         if rates is None:
             mc = [native._dev32(c, eng.device) for c in clips]
         else:
             fs = self._model_rate("sample_rates=")
             mc = eng.to_model_rate(clips, rates, fs, downmix=False)
         est, *others = run(self._reference_channel(mc, bopts["ref"]))
-        out = self._beamform_step([self._fit(m, int(e.shape[-1])) for m, e in zip(mc, est)], list(est), bopts, spopts)
+        out = self._beamform_step([self._fit(m, int(e.shape[-1])) for m, e in zip(mc, est)], list(est), bopts, spopts,
+                                  tropts)
         if rates is not None:
             out = eng.from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
@@ -599,7 +620,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
                  return_info=False, stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None,
-                 **kwargs):
+                 track=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -665,13 +686,25 @@ class LatentDiffSep:
         floor / reg / eps (native.spatial_options) -- only together with beamform=: the beamforming step is then
         Engine.beamform_spatial, whose guided cACGMM refines the masks that weight the beamformer's statistics, in the
         same place and on the same inputs.  Not trained and not tuned.  Refused without beamform=, with its
-        postfilter "mask", with stems=, with latent=True and with intermediate."""
+        postfilter "mask", with stems=, with latent=True and with intermediate.
+        track (default None: the call returns the bits it returned before): True, a block length in seconds or a dict
+        of block / context / interpolate (native.track_options; 0.8 s, 1, True -- not tuned) -- only together with
+        beamform=: the beamforming step is then Engine.beamform_track, in the same place and on the same inputs: one
+        MVDR filter per block of max(4, round(block fs / hop)) frames at the model's rate, solved on the blocks within
+        `context` of it and interpolated between the blocks' centres, so the filter follows a speaker who moves.
+        Blocks of fixed length; not a trained step.  Refused without beamform=, with spatial= (the cACGMM sums its
+        statistics inside its solve workgroup; cutting those per block is a separate piece of work), with stems=, with
+        latent=True and with intermediate."""
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and (latent or kwargs.get("intermediate")):
             self._dereverb_refusals(dopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
+        tropts = native.track_options(track)
+        if tropts is not None:
+            self._track_refusals(tropts, bopts, spopts, stems=stems, latent=latent,
+                                 intermediate=kwargs.get("intermediate"))
         if bopts is not None:
             chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else []
             self._beamform_refusals(bopts, chans, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
@@ -683,7 +716,7 @@ class LatentDiffSep:
             inner = bool(return_info) and samples is not None
             est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
                                          combine=combine, return_info=inner, stems=stems, beamform=beamform,
-                                         dereverb=dereverb, spatial=spatial, **kwargs)
+                                         dereverb=dereverb, spatial=spatial, track=track, **kwargs)
             B = int(est.shape[0])
             m3 = mix[:, None] if mix.dim() == 2 else mix
             if bopts is not None:
@@ -693,7 +726,7 @@ class LatentDiffSep:
             return (torch.stack(outs), *others)
         if dopts is not None:
             inner_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info, stems=stems,
-                            beamform=beamform, spatial=spatial)
+                            beamform=beamform, spatial=spatial, track=track)
             return self._separate_dereverb(mix, target_dim, sample_rate, dopts, inner_kw, kwargs)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -702,7 +735,7 @@ class LatentDiffSep:
             return self._separate_stems(mix, target_dim, sample_rate, sopts, mono_kw, kwargs)
         if bopts is not None:
             mono_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info)
-            return self._separate_beamform(mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts)
+            return self._separate_beamform(mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts, tropts)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -752,7 +785,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
                        combine="mean", return_info=False, stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -786,7 +819,9 @@ class LatentDiffSep:
         are fine), one Engine.dereverb call on the padded batch dereverberates every item at the model's rate, the
         call above runs on the results there, and the outputs go back to every item's own rate and sample count.
         spatial (default None: off), as in `separate`: with beamform=, one Engine.beamform_spatial call on the padded
-        batch in place of Engine.beamform."""
+        batch in place of Engine.beamform.
+        track (default None: off), as in `separate`: with beamform=, one Engine.beamform_track call on the padded batch
+        in place of Engine.beamform; every item has its own number of blocks."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
@@ -794,6 +829,9 @@ class LatentDiffSep:
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
+        tropts = native.track_options(track)
+        if tropts is not None:
+            self._track_refusals(tropts, bopts, spopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         if bopts is not None:
             mixes = self._as_channel_clips(list(mixes), "beamform")
             self._beamform_refusals(bopts, [int(m.shape[0]) for m in mixes], stems=stems,
@@ -808,7 +846,7 @@ class LatentDiffSep:
             inner = bool(return_info) and samples is not None
             est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
                                                samples=samples, combine=combine, return_info=inner, stems=stems,
-                                               beamform=beamform, dereverb=dereverb, spatial=spatial,
+                                               beamform=beamform, dereverb=dereverb, spatial=spatial, track=track,
                                                **sampler_kwargs)
             outs, others = self._normalise(lopts, sources, est, rates, others, return_info, inner)
             return (outs, *others)
@@ -819,7 +857,7 @@ class LatentDiffSep:
             return self._dereverb_of_lists(list(mixes), rates, dopts, stems is not None or bopts is not None,
                                            lambda at_fs: self.separate_batch(
                 at_fs, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
-                stems=stems, beamform=beamform, spatial=spatial, **sampler_kwargs))
+                stems=stems, beamform=beamform, spatial=spatial, track=track, **sampler_kwargs))
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -835,7 +873,7 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
             return self._beamform_of_lists(mixes, rates, bopts, lambda one: self.separate_batch(
                 one, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
-                **sampler_kwargs), spopts)
+                **sampler_kwargs), spopts, tropts)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -886,7 +924,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
                       mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
-                      beamform=None, dereverb=None, spatial=None, **sampler_kwargs):
+                      beamform=None, dereverb=None, spatial=None, track=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -915,7 +953,9 @@ class LatentDiffSep:
         dereverb (default None: off), as in `separate_batch`, in both modes: every recording [C, L_r] (or [1, L_r]) is
         dereverberated whole at the model's rate, before any windowing, and the call above runs on the result.
         spatial (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's channels
-        are beamformed whole by Engine.beamform_spatial."""
+        are beamformed whole by Engine.beamform_spatial.
+        track (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's channels are
+        beamformed whole by Engine.beamform_track -- a filter per block of the recording, not one for all of it."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
@@ -923,6 +963,9 @@ class LatentDiffSep:
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
+        tropts = native.track_options(track)
+        if tropts is not None:
+            self._track_refusals(tropts, bopts, spopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         if bopts is not None:
             bclips = self._as_channel_clips([mixes] if torch.is_tensor(mixes) else list(mixes), "beamform")
             self._beamform_refusals(bopts, [int(m.shape[0]) for m in bclips], stems=stems,
@@ -939,7 +982,7 @@ class LatentDiffSep:
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
                                               return_info=return_info, mode=mode, sample_rates=sample_rates,
                                               refine=refine, stems=stems, beamform=beamform, dereverb=dereverb,
-                                              spatial=spatial, **sampler_kwargs)
+                                              spatial=spatial, track=track, **sampler_kwargs)
             outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
                                            bool(return_info))
             return (outs[0] if single else outs, *others)
@@ -952,7 +995,7 @@ class LatentDiffSep:
             out, *others = self._dereverb_of_lists(clips, rates, dopts, stems is not None or bopts is not None,
                                                    lambda at_fs: self.separate_long(
                 at_fs, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
-                refine=refine, stems=stems, beamform=beamform, spatial=spatial, **sampler_kwargs))
+                refine=refine, stems=stems, beamform=beamform, spatial=spatial, track=track, **sampler_kwargs))
             return (out[0] if single else out, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -973,7 +1016,7 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(bclips) if isinstance(rates, int) else [int(r) for r in rates]
             out, *others = self._beamform_of_lists(bclips, rates, bopts, lambda one: self.separate_long(
                 one, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
-                refine=refine, **sampler_kwargs), spopts)
+                refine=refine, **sampler_kwargs), spopts, tropts)
             return (out[0] if single else out, *others)
         opts = native.refine_options(refine)
         if sample_rates is not None:
@@ -1037,7 +1080,7 @@ class LatentDiffSep:
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
                        samples=None, combine="mean", stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -1090,14 +1133,17 @@ class LatentDiffSep:
         before any device work.
         spatial (default None: off, the files are the bytes they were), as in `separate`: with beamform=, every file's
         channels are beamformed by Engine.beamform_spatial.  Each dict gains "spatial" (the options).  Refused before
-        any device work without beamform=, with its postfilter "mask" and with stems=."""
+        any device work without beamform=, with its postfilter "mask" and with stems=.
+        track (default None: off, the files are the bytes they were), as in `separate`: with beamform=, every file's
+        channels are beamformed by Engine.beamform_track.  Each dict gains "track" (the options).  Refused before any
+        device work without beamform=, with spatial= and with stems=."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
                                     loudness=loudness, limit=limit, beamform=beamform, dereverb=dereverb,
-                                    spatial=spatial, **sampler_kwargs)
+                                    spatial=spatial, track=track, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -42,7 +42,7 @@ EXPORTS = [
     "dsn_mask_refine",
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
-    "dsn_beamform", "dsn_beamform_spatial", "dsn_dereverb",
+    "dsn_beamform", "dsn_beamform_spatial", "dsn_beamform_track", "dsn_dereverb",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
@@ -891,6 +891,119 @@ def check_spatial(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=5
             budget)
 
 
+TRACK_MIN_BLOCK, TRACK_MAX_BLOCK, TRACK_MAX_CONTEXT, TRACK_MAX_BLOCKS, TRACK_DEFAULT_BUDGET = 4, 1 << 20, 64, 4096, 512 << 20
+# blocks of 0.8 s (100 frames at 16 kHz and hop 128) with one block of context each side, interpolated.  These are not
+# tuned.
+TRACK_DEFAULTS = dict(block=0.8, context=1, interpolate=True)
+
+
+def _track_shorthand(v) -> Optional[dict]:
+    if v is True:
+        return {}
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return {"block": float(v)}
+    return None
+
+
+def _check_track_options(opts) -> None:
+    block, context, interp = opts["block"], opts["context"], opts["interpolate"]
+    if isinstance(block, bool) or not isinstance(block, (int, float)) or not math.isfinite(block) or not block > 0:
+        raise ValueError(f"track: block = {block!r} is not a positive number of seconds")
+    if isinstance(context, bool) or not isinstance(context, int) or not 0 <= context <= TRACK_MAX_CONTEXT:
+        raise ValueError(f"track: context = {context!r} outside [0, {TRACK_MAX_CONTEXT}]")
+    if not isinstance(interp, bool):
+        raise ValueError(f"track: interpolate = {interp!r} is not True or False")
+
+
+def track_options(track) -> Optional[dict]:
+    """The `track` keyword of the separation entry points: None (off, the default) -> None; True -> TRACK_DEFAULTS; a
+    number -> the defaults with that block length in seconds; a dict of block / context / interpolate -> the defaults
+    with those replaced.  Anything else, False, an unknown key, a block that is not a positive number, a context
+    outside [0, 64] and an interpolate that is not a bool included, is refused by name."""
+    return _options("track", track, TRACK_DEFAULTS, "None, True, a block length in seconds", _track_shorthand,
+                    _check_track_options)
+
+
+def track_block_frames(block: float, fs: int, hop: int) -> int:
+    """A block of `block` seconds in frames of `hop` samples at `fs`: max(4, block fs / hop rounded to nearest, halves
+    up)"""
+    return max(TRACK_MIN_BLOCK, int(math.floor(float(block) * int(fs) / int(hop) + 0.5)))
+
+
+def track_beamform_keywords(beam: Optional[dict], track: Optional[dict], fs: Optional[int], spatial=None) -> dict:
+    """The keywords of Engine.beamform_track for the beamforming step of the separation entry points: `beam`
+    (beamform_options) and `track` (track_options) at the model's rate fs (None: only the refusals are made).  track=
+    without beamform= and track= together with spatial= are refused by name."""
+    if beam is None:
+        raise ValueError("track= adapts the weights of the beamformer block by block: it needs beamform=")
+    if spatial is not None:
+        raise ValueError("track= does not go with spatial=: the cACGMM sums its statistics inside its solve workgroup, "
+                         "and cutting those per block is a separate piece of work (not implemented)")
+    frames = None if fs is None else track_block_frames(track["block"], fs, beam["hop"])
+    return dict(beam, block_frames=frames, context=track["context"], interpolate=track["interpolate"])
+
+
+def track_item_bytes(n_fft: int, hop: int, L: int, Cn: int, n: int, block_frames: int) -> int:
+    """The workspace one item of a [B, C, L] batch needs in dsn_beamform_track: per block (Kmax = ceil(F / block_frames),
+    F = 1 + ceil(L / hop)) the float64 partials and their context sums (n C (C + 1) bins doubles each), the weights
+    (n bins C complex doubles) and one int32.  The one formula: the C side computes the same number."""
+    F = 1 + (L + hop - 1) // hop
+    kmax = (F + block_frames - 1) // block_frames
+    return kmax * (8 * n * (n_fft // 2 + 1) * (2 * Cn * (Cn + 1) + 2 * Cn) + 4)
+
+
+def track_plan(F: int, block_frames: int, interpolate=True) -> tuple:
+    """Frame t = 0 .. F - 1 of an item of F frames -> (k0 [F] int64, alpha [F] float64) on the host: the frame is
+    filtered with w^(k0) + alpha (w^(k0+1) - w^(k0)).  The integer arithmetic of the kernel (include/ditsep_hip.h):
+    centre to centre between neighbouring blocks, the first and the last half block hold, alpha in [0, 1)."""
+    F, Tb = int(F), int(block_frames)
+    K = (F + Tb - 1) // Tb
+    t = torch.arange(F, dtype=torch.int64)
+    zero = torch.zeros(F, dtype=torch.float64)
+    if not interpolate:
+        return t // Tb, zero
+    num = 2 * t + 1 - Tb
+    k0 = torch.where(num <= 0, 0, num // (2 * Tb))
+    alpha = torch.where(num <= 0, zero, (num % (2 * Tb)).to(torch.float64) / float(2 * Tb))
+    last = k0 >= K - 1
+    return torch.where(last, K - 1, k0), torch.where(last, zero, alpha)
+
+
+def check_track(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
+                reg=1e-3, postfilter=None, block_frames=100, context=1, interpolate=True, workspace_budget=0) -> tuple:
+    """The refusals of dsn_beamform_track (include/ditsep_hip.h), raised by name before the library is touched: what
+    check_beamform refuses; block_frames outside [4, 2^20]; context outside [0, 64]; interpolate not a bool (or 0 / 1);
+    more than 4096 blocks; a workspace budget smaller than one item.
+    -> ((B, C, n, L), lens or None, channels or None, ref, n_fft, hop, power, eps, reg, the DSN_BEAMFORM_POST_* code,
+    block_frames, context, interpolate as 0 / 1, the blocks Kmax, workspace_budget)"""
+    who = "beamform_track"
+    _check_postfilter(postfilter)
+    B, Cn, n, L = _check_mix_est(who, mix_shape, est_shape)
+    if Cn < 1 or Cn > BEAMFORM_MAX_CHANNELS:
+        raise ValueError(f"{who}: C = {Cn} outside [1, {BEAMFORM_MAX_CHANNELS}]")
+    n_fft, hop, power, eps = _check_stft(who, B, n, n_fft, hop, power, eps)
+    ln = _check_item_lens(who, lens, B, L, n_fft)
+    reg = _check_reg(who, reg)
+    ch = _check_channels(who, channels, B, Cn)
+    ref = _check_ref(who, ref, ch, Cn)
+    if (isinstance(block_frames, bool) or int(block_frames) != block_frames
+            or not TRACK_MIN_BLOCK <= int(block_frames) <= TRACK_MAX_BLOCK):
+        raise ValueError(f"{who}: block_frames = {block_frames!r} outside [{TRACK_MIN_BLOCK}, 2^20]")
+    if isinstance(context, bool) or int(context) != context or not 0 <= int(context) <= TRACK_MAX_CONTEXT:
+        raise ValueError(f"{who}: context = {context!r} outside [0, {TRACK_MAX_CONTEXT}]")
+    if interpolate not in (False, True):
+        raise ValueError(f"{who}: interpolate = {interpolate!r} is not 0 or 1")
+    Tb = int(block_frames)
+    kmax = (1 + (L + hop - 1) // hop + Tb - 1) // Tb
+    if kmax > TRACK_MAX_BLOCKS:
+        raise ValueError(f"{who}: {kmax} blocks of block_frames = {Tb} frames at L = {L}, hop = {hop}: more than "
+                         f"{TRACK_MAX_BLOCKS}")
+    budget = _check_budget(who, workspace_budget, TRACK_DEFAULT_BUDGET, track_item_bytes(n_fft, hop, L, Cn, n, Tb),
+                           f"C = {Cn}, n = {n}, n_fft = {n_fft}, hop = {hop}, L = {L}, block_frames = {Tb}")
+    return ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, BEAMFORM_POSTFILTERS[postfilter], Tb, int(context),
+            int(bool(interpolate)), kmax, budget)
+
+
 DEREVERB_MAX_CHANNELS, DEREVERB_MAX_TAPS, DEREVERB_MAX_DELAY, DEREVERB_MAX_UNKNOWNS, DEREVERB_MAX_ITERATIONS = 8, 16, 8, 80, 8
 DEREVERB_DEFAULT_BUDGET = 512 << 20
 # the offline recipe's usual values at 16 kHz; reg and eps are not tuned beyond the sanity runs the README names
@@ -1399,6 +1512,8 @@ def load_library() -> C.CDLL:
                                  C.c_int64, vp, f64p, vp]
     lib.dsn_beamform_spatial.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp, f64p, f64p, i32p, vp]
+    lib.dsn_beamform_track.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci, ci,
+                                       ci, ci, C.c_int64, vp, f64p, vp]
     lib.dsn_dereverb.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, ci, C.c_float, C.c_float, C.c_int64, vp,
                                  f64p, i32p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
@@ -2238,8 +2353,8 @@ class Engine:
         end or in a channel it does not have is read (it may hold NaN), the result is zero past the end and each item
         gets the bits it gets alone, under any workspace_budget (bytes, 0 = 512 MiB: the items are processed in
         chunks).  Lists (mix: [C_b, L_b] each, est: [n, L_b] each) are padded once and a list of [n, L_b] comes back.
-        return_info=True: (out, {"w": complex128 [B, n, bins, C]}) on the host.  One filter per recording (no tracking
-        of moving sources); not a trained step: what it does to separation quality is unmeasured.  Needs no score
+        return_info=True: (out, {"w": complex128 [B, n, bins, C]}) on the host.  One filter per recording
+        (`beamform_track` follows moving sources); not a trained step: what it does to separation quality is unmeasured.  Needs no score
         network and no codec; two calls give identical bits."""
         if isinstance(mix, (list, tuple)):
             if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
@@ -2312,6 +2427,46 @@ class Engine:
                                                   mask_eps, budget, _ptr(out), _host(w), _host(gamma),
                                                   _host(bad, C.c_int32), self._stream()), "dsn_beamform_spatial")
         return (out, {"w": w, "gamma": gamma, "fail": bad}) if return_info else out
+
+    # ------------------------------------------------------------------ block-adaptive MVDR weights
+    def beamform_track(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
+                       reg=1e-3, postfilter=None, block_frames=100, context=1, interpolate=True, workspace_budget=0,
+                       return_info=False):
+        """`beamform` with weights that follow a moving source (dsn_beamform_track, csrc/beamform_track.hip; the
+        definition is in include/ditsep_hip.h and tests/beamform_track_restatement.py): mix [B, C, L] (C <= 8), est
+        [B, n, L] -> [B, n, L].  The frames are cut into blocks of `block_frames`; block k gets the MVDR filter of
+        `beamform` solved on the statistics of the blocks k - context .. k + context, and frame t is filtered with the
+        weights interpolated between the centres of its two nearest blocks (interpolate=False: with its own block's).
+        One block is `beamform` up to the order of its sums.  lens / channels / postfilter / workspace_budget / lists as
+        in `beamform` (items of native.track_item_bytes each: the weights live in the workspace too); each item gets
+        the bits it gets alone.  return_info=True: (out, {"w": complex128 [B, Kmax, n, bins, C]}) on the host, zero in
+        blocks and channels an item does not have.  Blocks of fixed length, not speaker-activity segments; no
+        recursive or online form; not trained and not tuned: what it does to separation quality on real recordings
+        is unmeasured.  Needs no score network and no codec; two calls give identical bits."""
+        kw = dict(ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps, reg=reg, postfilter=postfilter,
+                  block_frames=block_frames, context=context, interpolate=interpolate, workspace_budget=workspace_budget,
+                  return_info=return_info)
+        if isinstance(mix, (list, tuple)):
+            if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
+                raise ValueError("beamform_track: a list of mixtures goes with a list of as many estimates and no lens "
+                                 "or channels")
+            ln = [int(e.shape[-1]) for e in est]
+            for b, (m, e) in enumerate(zip(mix, est)):
+                if e.dim() != 2 or m.dim() != 2 or int(m.shape[-1]) != ln[b]:
+                    raise ValueError(f"beamform_track: item {b} must be mix [C, L] and est [n, L] (got "
+                                     f"{tuple(m.shape)} and {tuple(e.shape)})")
+            mp, ep, ln, ch, cut = self._pad_items(mix, est)
+            return cut(self.beamform_track(mp, ep, lens=ln, channels=ch, **kw))
+        ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, post, Tb, context, interp, kmax,
+         budget) = check_track(tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg,
+                               postfilter, block_frames, context, interpolate, workspace_budget)
+        mix, est = _dev32(mix, self.device), _dev32(est, self.device)
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        w = torch.zeros((B, kmax, n, n_fft // 2 + 1, Cn), dtype=torch.complex128) if return_info else None
+        self._check(self.lib.dsn_beamform_track(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref,
+                                                n_fft, hop, power, eps, reg, post, Tb, context, interp, budget,
+                                                _ptr(out), _host(w), self._stream()), "dsn_beamform_track")
+        return (out, {"w": w}) if return_info else out
 
     # ------------------------------------------------------------------ WPE dereverberation
     def dereverb(self, mix, lens=None, channels=None, taps=10, delay=3, iterations=3, n_fft=512, hop=128, reg=1e-4,

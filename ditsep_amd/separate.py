@@ -107,6 +107,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Share of the prior spread equally over the speakers, whatever the estimates say")
     p.add_argument("--spatial-reg", type=float, default=1e-3,
                    help="Diagonal loading of the classes' covariances, relative to their mean diagonal")
+    p.add_argument("--track", action="store_true",
+                   help="With --beamform: follow moving speakers -- one MVDR filter per block of the recording, solved on "
+                        "the blocks around it and interpolated from frame to frame (not a trained step; not tuned; off "
+                        "by default)")
+    p.add_argument("--track-block", type=float, default=0.8, metavar="SECONDS", help="Length of a block")
+    p.add_argument("--track-context", type=int, default=1, metavar="N",
+                   help="Blocks each side of a block whose statistics enter its filter")
+    p.add_argument("--track-hold", action="store_true",
+                   help="Hold a block's filter over the whole block (no interpolation between the blocks' centres)")
     p.add_argument("--dereverb", action="store_true",
                    help="Dereverberate every recording first (weighted prediction error on up to 8 channels, kept for "
                         "the steps that use them; not a trained step; off by default)")
@@ -191,6 +200,13 @@ def spatial_of(args):
                 reg=args.spatial_reg)
 
 
+def track_of(args):
+    """The `track` keyword of separate_files from the parsed flags: None unless --track is given."""
+    if not args.track:
+        return None
+    return dict(block=args.track_block, context=args.track_context, interpolate=not args.track_hold)
+
+
 def dereverb_of(args):
     """The `dereverb` keyword of separate_files from the parsed flags: None unless --dereverb is given."""
     if not args.dereverb:
@@ -243,7 +259,7 @@ def main(argv=None) -> int:
                                            overlap=args.overlap, long_mode=args.long_mode, seed=args.seed,
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
                                            stems=stems_of(args), beamform=beamform_of(args),
-                                           dereverb=dereverb_of(args), spatial=spatial_of(args),
+                                           dereverb=dereverb_of(args), spatial=spatial_of(args), track=track_of(args),
                                            loudness=loudness_of(args), limit=limit_of(args),
                                            denoise=args.denoise, **kw)
         except ValueError as e:

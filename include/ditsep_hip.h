@@ -656,8 +656,9 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
  * batch outside that budget.  info_w (HOST, [B][n][n_fft / 2 + 1][C] complex as double pairs, or NULL): the weights,
  * zero in channels an item does not have; with it the stream is synchronised.  The call uploads lens and channels
  * when given and then synchronises the stream, so with them it must not be captured into a graph.  Needs no score
- * network and no codec.  It computes one filter per recording (no tracking of moving sources); dual-mono input has no
- * spatial information and gives the channel average; its effect on separation quality is unmeasured.
+ * network and no codec.  It computes one filter per recording (dsn_beamform_track, below, follows moving sources);
+ * dual-mono input has no spatial information and gives the channel average; its effect on separation quality is
+ * unmeasured.
  * DSN_EINVAL by name, before anything is allocated or launched: what dsn_mask_refine refuses; C outside [1, 8];
  * channels[b] outside [1, C]; ref outside [0, channels[b]) for any item (the message names the item); reg not finite or
  * < 0; an unknown post-filter; a negative budget or one too small for one item (the message names the bytes needed);
@@ -716,6 +717,49 @@ int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B
                          float reg, int iterations, float noise, float floor, float mask_reg, float mask_eps,
                          int64_t workspace_budget, float* out, double* info_w, double* info_gamma, int32_t* info_fail,
                          void* stream);
+
+/* dsn_beamform with block-adaptive weights: the recording is cut into blocks of `block_frames` frames, every block gets
+ * the MVDR filter of the statistics of a context window of blocks around it, and every frame is filtered with the
+ * weights interpolated between the centres of the two nearest blocks, so the filter follows a source that moves
+ * (the per-segment beamformer of the guided-source-separation recipes since CHiME-5; csrc/beamform_track.hip, restated in
+ * float64 in tests/beamform_track_restatement.py).  A definition, not a trained step; nothing calls it unless asked to.
+ * mix, est, out, lens, channels, ref, n_fft, hop, power, eps, reg and postfilter are dsn_beamform's, and so is
+ * everything up to the statistics: the frames, the spectra X_c(f,t), the fp32 masks M_i, F = 1 + ceil(L_b / hop), the
+ * widening to fp64.  With Tb = block_frames, per item, source i and bin f:
+ *   blocks         block k holds the frames [k Tb, min(F, (k + 1) Tb)); K = ceil(F / Tb) from the item's own length; the
+ *                  last block is as short as it falls
+ *   partials       P_i^(k) = sum_{t in block k} M_i X X^H in increasing t whatever the tiling, the upper triangle,
+ *                  products in fp64; every block has exactly one owning workgroup per source (bins below 256 over all
+ *                  the block's frames in registers; bins 256 and up a group of 2048 / n_fft frames in registers, then
+ *                  into the partial)
+ *   context        N_i^(k) = sum_{j = max(0, k - context)}^{min(K - 1, k + context)} P_i^(j), added in increasing j
+ *   weights        w_i^(k)(f): dsn_beamform's interference, loading, Cholesky solve, tau and e_ref fallback on N^(k)
+ *   frame weights  in integers: num = 2 t + 1 - Tb; num <= 0: k0 = 0, alpha = 0; otherwise k0 = num div 2 Tb and
+ *                  alpha = (double)(num mod 2 Tb) / (double)(2 Tb); k0 >= K - 1: k0 = K - 1, alpha = 0 (the first and the
+ *                  last half block hold their block's weights).  With interpolate = 0: k0 = t div Tb, alpha = 0.
+ *                  w(t) = w^(k0) + alpha (w^(k0+1) - w^(k0)) per real and imaginary part in fp64, not contracted; where
+ *                  alpha = 0, w(t) = w^(k0) and block k0 + 1 is not read.  Equal neighbours give exactly that weight.
+ *   apply          Y_i(f,t) = sum_c conj(w_i,c(t)) X_c in fp64 and in channel order, rounded once to fp32; post-filter and
+ *                  synthesis are dsn_beamform's
+ * One block (Tb >= F) is dsn_beamform up to the order of its sums.  With C_b = 1 every w is 1.0 exactly and the output
+ * is dsn_mask_refine's as in dsn_beamform; silent estimates give n equal outputs; context >= K - 1 gives every block
+ * the same weights and interpolate = 1 the bits of interpolate = 0.  No floating-point atomics: an item has the same
+ * bits alone, at any batch position, under any padding, from a base pointer of any 4-byte alignment, under any
+ * workspace budget and in a second call.  With Kmax = ceil((1 + ceil(Lmax / hop)) / Tb), the partials, their context
+ * sums, the weights (they scale with Kmax) and the blocks' channel counts live in a workspace the context keeps,
+ * Kmax (8 n (n_fft / 2 + 1) (2 C (C + 1) + 2 C) + 4) bytes per item; the batch is processed in chunks of as many items
+ * as fit `workspace_budget` bytes (0: 512 MiB); an item that does not fit is refused, not split.  info_w (HOST,
+ * [B][Kmax][n][n_fft / 2 + 1][C] complex as double pairs, or NULL): the blocks' weights, zero in blocks and channels an
+ * item does not have; with it the stream is synchronised.  The call uploads lens and channels when given and then
+ * synchronises the stream, so with them it must not be captured into a graph.  Needs no score network and no codec.
+ * Blocks of fixed length, not speaker-activity segments; no recursive or online form; no combination with
+ * dsn_beamform_spatial; its effect on separation quality is unmeasured.
+ * DSN_EINVAL by name, before anything is allocated or launched: what dsn_beamform refuses; block_frames outside
+ * [4, 2^20]; context outside [0, 64]; interpolate not 0 or 1; Kmax above 4096. */
+int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                       const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                       float reg, int postfilter, int block_frames, int context, int interpolate,
+                       int64_t workspace_budget, float* out, double* info_w, void* stream);
 
 /* Weighted prediction error (WPE) dereverberation: the channels of a reverberant recording in, the same channels with
  * the late reverberation predicted from their own delayed past and subtracted out (Nakatani et al. 2010; Yoshioka &
