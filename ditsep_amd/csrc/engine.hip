@@ -3958,6 +3958,84 @@ int dsn_apply_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const 
   });
 }
 
+// ---- speaker activity of separated stems (activity.hip; include/ditsep_hip.h states the definition)
+int dsn_activity(dsn_ctx* ctx, const float* est, int B, int n, int Lmax, const int32_t* lens, int n_fft, int hop, int j_lo,
+                 int j_hi, int half_width, double c_r, double c_d, double c_r_stay, double c_d_stay, int min_on,
+                 int min_off, int pad, uint8_t* act, int32_t* frames_on, double* energy, double* level, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_activity";
+    if (!est || !act || !frames_on || !energy || !level)
+      fail(DSN_EINVAL, "%s: est, act, frames_on, energy or level is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    check_stft(who, n_fft, hop);
+    check_lmax(who, Lmax);
+    check_items(who, B, Lmax, n_fft, lens, nullptr, 1, nullptr);
+    if (j_lo < 0 || j_hi > n_fft / 2 || j_lo > j_hi)
+      fail(DSN_EINVAL, "%s: the band of bins [%d, %d] is empty or outside [0, n_fft / 2 = %d]", who, j_lo, j_hi, n_fft / 2);
+    if (half_width < 0 || half_width > ACTIVITY_MAX_HALF_WIDTH)
+      fail(DSN_EINVAL, "%s: half_width = %d outside [0, %d]", who, half_width, ACTIVITY_MAX_HALF_WIDTH);
+    const double c[4] = {c_r, c_d, c_r_stay, c_d_stay};
+    const char* cn[4] = {"c_r", "c_d", "c_r_stay", "c_d_stay"};
+    for (int k = 0; k < 4; ++k)
+      if (!(c[k] >= 0.0 && c[k] <= 1.0)) fail(DSN_EINVAL, "%s: %s = %g outside [0, 1]", who, cn[k], c[k]);
+    if (c_r_stay > c_r || c_d_stay > c_d)
+      fail(DSN_EINVAL, "%s: a stay threshold above its on threshold (c_r %g -> %g, c_d %g -> %g): the hysteresis is "
+           "negative", who, c_r, c_r_stay, c_d, c_d_stay);
+    if (min_on < 1 || min_off < 1) fail(DSN_EINVAL, "%s: min_on = %d or min_off = %d < 1 frame", who, min_on, min_off);
+    if (pad < 0) fail(DSN_EINVAL, "%s: pad = %d < 0", who, pad);
+    const int Fmax = activity_frames(hop, Lmax);
+    if (Fmax > ACTIVITY_MAX_FRAMES)
+      fail(DSN_EINVAL, "%s: %d frames (Lmax = %d, hop = %d) > 2^22 per item", who, Fmax, Lmax, hop);
+    hipStream_t st = (hipStream_t)stream;
+    const int* dlens = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "activity_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    ctx->prof_launch("activity", (double)B * n * (4.0 * Lmax + 42.0 * Fmax), st, [&] {
+      launch_activity(est, dlens, B, n, Lmax, n_fft, hop, j_lo, j_hi, half_width, c_r, c_d, c_r_stay, c_d_stay, min_on,
+                      min_off, pad, energy, level, act, frames_on, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dsn_activity_gate(dsn_ctx* ctx, const float* x, const uint8_t* act, int B, int n, int Lmax, int Fa,
+                      const int32_t* lens, int hop, int fade, const float* ramp, float* out, void* stream) {
+  return guarded(ctx, [&] {
+    const char* who = "dsn_activity_gate";
+    if (!x || !act || !out) fail(DSN_EINVAL, "%s: x, act or out is null", who);
+    if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (Lmax < 1 || Lmax > (1 << 30)) fail(DSN_EINVAL, "%s: Lmax = %d outside [1, 2^30]", who, Lmax);
+    if (hop < ACTIVITY_MIN_HOP || hop > ACTIVITY_MAX_HOP)
+      fail(DSN_EINVAL, "%s: hop = %d outside [%d, %d]", who, hop, ACTIVITY_MIN_HOP, ACTIVITY_MAX_HOP);
+    if (fade < 0 || fade > ACTIVITY_MAX_FADE) fail(DSN_EINVAL, "%s: fade = %d outside [0, %d]", who, fade, ACTIVITY_MAX_FADE);
+    if (fade > 0 && !ramp) fail(DSN_EINVAL, "%s: fade = %d needs the ramp table: ramp is null", who, fade);
+    for (int b = 0; lens && b < B; ++b)
+      if (lens[b] < 1 || lens[b] > Lmax)
+        fail(DSN_EINVAL, "%s: sample count lens[%d] = %d outside [1, Lmax = %d]", who, b, (int)lens[b], Lmax);
+    const int need = (Lmax - 1 + hop / 2) / hop + 1;
+    if (Fa < need)
+      fail(DSN_EINVAL, "%s: act holds %d frames per row, %d needed for Lmax = %d at hop = %d", who, Fa, need, Lmax, hop);
+    const char *x0 = (const char*)x, *o0 = (const char*)out;
+    const size_t bytes = sizeof(float) * (size_t)B * n * Lmax;
+    if (o0 != x0 && o0 < x0 + bytes && x0 < o0 + bytes)
+      fail(DSN_EINVAL, "%s: out overlaps x without being x (in place is fine, a shifted copy is not)", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int* dlens = nullptr;
+    if (lens) dlens = (const int*)upload_table(ctx, "gate_lens", lens, sizeof(int32_t) * (size_t)B, st);
+    const float* dramp = nullptr;
+    if (fade > 0) {
+      for (int d = 0; d < fade; ++d)
+        if (!(ramp[d] >= 0.f && ramp[d] <= 1.f)) fail(DSN_EINVAL, "%s: ramp[%d] = %g outside [0, 1]", who, d, (double)ramp[d]);
+      dramp = (const float*)upload_table(ctx, "gate_ramp", ramp, sizeof(float) * (size_t)fade, st);
+    }
+    ctx->prof_launch("activity_gate", (double)B * n * (8.0 * Lmax + Fa), st, [&] {
+      launch_activity_gate(x, act, dlens, dramp, out, B, n, Lmax, Fa, hop, fade, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
 // Modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2 (numpy.kaiser's window function)
 static double bessel_i0(double x) {
   double s = 1.0, t = 1.0;

@@ -617,3 +617,23 @@ void launch_limiter_curve(const float* x, const LimRow* rows, const LimGroup* gr
 // out = (pregain[group] x) curve[group][t] over a row's own samples and channels, zero elsewhere; out may be x
 void launch_apply_curve(const float* x, const LimRow* rows, const float* pregain, const float* curve, float* out, int R,
                         int C, int Lmax, hipStream_t s);
+
+// ---- speaker activity of separated stems (activity.hip) ----------------------------------------------------------
+// est [B][n][Lmax] fp32, lens [B] (device) or null; energy, level [B][n][Fmax] fp64, act [B][n][Fmax] bytes, frames_on
+// [B][n], Fmax = activity_frames(hop, Lmax).  Two launches: the band energies (workgroup per frame group and item), then
+// level, thresholds, hysteresis and run rules (workgroup per item, chunked scans).  The band [j_lo, j_hi] and the four
+// threshold factors come from the host.
+#define ACTIVITY_MAX_FRAMES (1 << 22)
+#define ACTIVITY_MAX_HALF_WIDTH 1024
+#define ACTIVITY_MAX_FADE 4096
+#define ACTIVITY_MIN_HOP 8   // the smallest hop of the STFT; bounds the frames a gate span stages
+#define ACTIVITY_MAX_HOP 65536
+int activity_frames(int hop, int Lmax);
+void launch_activity(const float* est, const int* lens, int B, int n, int Lmax, int nfft, int hop, int j_lo, int j_hi,
+                     int half_width, double c_r, double c_d, double c_rs, double c_ds, int min_on, int min_off, int pad,
+                     double* energy, double* level, uint8_t* act, int* frames_on, hipStream_t s);
+// out = x inside the segments act marks (frame (m + hop / 2) / hop owns sample m), ramp[d - 1] x at distance d <= fade
+// from the nearest segment sample, +0 further away and past the item's end.  act [B][n][Fa] bytes, ramp [fade]; out may
+// be x.
+void launch_activity_gate(const float* x, const uint8_t* act, const int* lens, const float* ramp, float* out, int B, int n,
+                          int Lmax, int Fa, int hop, int fade, hipStream_t s);

@@ -91,7 +91,7 @@ def _padded(rows, device):
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
                    stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None, track=None,
-                   **sampler_kwargs) -> list:
+                   activity=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -122,6 +122,10 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         raise ValueError("beamform= does not go with stems=: the beamformer returns one mono signal per source, stems= "
                          "the mixture's channels")
     dere = native.dereverb_options(dereverb)
+    act = native.activity_options(activity)
+    if act is not None and stems is not None:
+        raise ValueError("activity= does not go with stems=: it decides on mono estimates, stems= returns the mixture's "
+                         "channels (no gate for stems)")
     loud = native.level_options(loudness, limit)
     linked = loud is not None and loud["link"] == "mixture" and loud["target"] is not None   # the file is the source
     if long_mode not in native.LONG_MODES:
@@ -185,6 +189,13 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
             native.check_dereverb((1, h.channels, 2049), None, None, **dere)
             if v < need:
                 raise ValueError(f"{p}: {v} samples at the model's rate; dereverb= needs at least n_fft / 2 + 1 = {need}")
+    if act is not None:
+        # .. and those of the activity decision: the parameters on a stand-in item, every file's length
+        need = native.check_activity((1, n, 2049), None, **native.activity_keywords(act, fs))[2] // 2 + 1
+        native.activity_ramp(native.activity_frames(act, fs)["fade"])
+        for p, v in zip(paths, plan["lengths"]):
+            if v < need:
+                raise ValueError(f"{p}: {v} samples at the model's rate; activity= needs at least n_fft / 2 + 1 = {need}")
     records = [None] * len(paths)
 
     def reference(clips):
@@ -242,6 +253,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
         if beam is not None:
             est = model._beamform_step([model._fit(m, int(e.shape[-1])) for m, e in zip(channels_fs, est)], list(est),
                                        beam, spat, trk)
+        decided = None
+        if act is not None:
+            # on the final mono estimates at the model's rate, before rescale, the resampling back and loudness
+            est = model._activity_step(list(est), act)
+            decided = model.last_activity
         if rescale:
             sep, lens = _padded(est, eng.device)
             mix, _ = _padded(at_fs, eng.device)
@@ -273,6 +289,11 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 rec["track"] = dict(trk)
             if dere is not None:
                 rec["dereverb"] = dict(dere)
+            if decided is not None:
+                rec["activity"] = dict(segments=decided[j]["seconds"], active=decided[j]["active"])
+                os.makedirs(out_dir, exist_ok=True)
+                with open(os.path.join(out_dir, stem + ".rttm"), "w") as f:
+                    f.write("".join(line + "\n" for line in native.activity_rttm(stem, decided[j]["segments"], fs)))
             records[i] = dict(rec, **levels[j])
 
     def mono_at_model_rate(idx, clips):

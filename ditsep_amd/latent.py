@@ -92,6 +92,8 @@ class LatentDiffSep:
       * `...LatentScoreModelNCSNpp`                      the NCSN++ latent U-Net the reference wires in
     """
 
+    last_activity = None   # what the last call with activity= decided: one dict per item (Engine.activity_of)
+
     def __init__(self, config, device: int = 0, precision: str = "fp16"):
         self.config = config
         self.device_index = device
@@ -338,7 +340,7 @@ class LatentDiffSep:
         return out
 
     @torch.no_grad()
-    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs, refine=None, **ens):
+    def _separate_at_rate(self, mix, sample_rate, target_dim, kwargs, refine=None, activity=None, **ens):
         """`separate` of mix [B, C, L] (or [B, L]) at `sample_rate`: to the model's rate (mixed down), the existing
         call (with `refine` and the `samples` keywords `ens`, there), every estimate back to `sample_rate` and cropped
         to L."""
@@ -346,7 +348,7 @@ class LatentDiffSep:
         mix = mix[:, None] if mix.dim() == 2 else mix
         L = int(mix.shape[-1])
         m = eng.resample(mix, sample_rate, fs, downmix=True)
-        est, *others = self.separate(m, target_dim, refine=refine, **ens, **kwargs)
+        est, *others = self.separate(m, target_dim, refine=refine, activity=activity, **ens, **kwargs)
         return (eng.resample(est, fs, sample_rate)[..., :L], *others)
 
     # ------------------------------------------------------------------ multichannel stems (the `stems` keyword)
@@ -468,7 +470,8 @@ class LatentDiffSep:
         return [c[ref:ref + 1].contiguous() for c in clips]
 
     @torch.no_grad()
-    def _separate_beamform(self, mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts=None, tropts=None):
+    def _separate_beamform(self, mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts=None, tropts=None,
+                           aopts=None):
         """`separate` with beamform=: mix [B, C, L] -> the mono call on channel `ref`, Engine.beamform against all
         channels at the model's rate (zero-extended or cut to the estimates' length), back to `sample_rate`"""
         eng = self.engine
@@ -486,6 +489,8 @@ class LatentDiffSep:
         one = mc[:, bopts["ref"]:bopts["ref"] + 1].contiguous()
         est, *others = self.separate(one, target_dim, **mono_kw, **kwargs)
         out = self._beamform_step(self._fit(mc, int(est.shape[-1])), est, bopts, spopts, tropts)
+        if aopts is not None:
+            out = self._activity_step(out, aopts)
         if sample_rate is not None:
             out = eng.resample(out, fs, sample_rate)[..., :L]
         return (out, *others)
@@ -499,7 +504,7 @@ class LatentDiffSep:
         return clips
 
     @torch.no_grad()
-    def _beamform_of_lists(self, clips, rates, bopts, run, spopts=None, tropts=None):
+    def _beamform_of_lists(self, clips, rates, bopts, run, spopts=None, tropts=None, aopts=None):
         """The list entry points with beamform=: `clips` [C_b, L_b] each (or [L_b], [1, C_b, L_b]) at `rates` (None:
         the model's rate); run(list of [1, L'_b], channel `ref` of each) -> (list of [n, Le_b] estimates at the model's
         rate, *others).  -> (list of [n, L_b] at each clip's own rate, *others)"""
@@ -516,6 +521,8 @@ class LatentDiffSep:
         est, *others = run(self._reference_channel(mc, bopts["ref"]))
         out = self._beamform_step([self._fit(m, int(e.shape[-1])) for m, e in zip(mc, est)], list(est), bopts, spopts,
                                   tropts)
+        if aopts is not None:
+            out = self._activity_step(out, aopts)
         if rates is not None:
             out = eng.from_model_rate(out, rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
@@ -585,6 +592,33 @@ class LatentDiffSep:
             out = back(list(out), rates, fs, [int(c.shape[-1]) for c in clips])
         return (out, *others)
 
+    # ------------------------------------------------------------------ speaker activity (the `activity` keyword)
+    @staticmethod
+    def _activity_refusals(aopts, stems=None, latent=False, intermediate=None):
+        """What the `activity` keyword refuses, before any device work"""
+        if stems is not None:
+            raise ValueError("activity= does not go with stems=: it decides on mono estimates, stems= returns the "
+                             "mixture's channels (no gate for stems)")
+        if latent:
+            raise ValueError("activity= decides on waveforms: with latent=True there is nothing to frame")
+        if intermediate:
+            raise ValueError("activity= does not go with intermediate: the per-step states are not decided on")
+
+    def _activity_step(self, est, aopts):
+        """The activity step of the entry points, on the final mono estimates at the model's rate: est [B, n, L] or a
+        list of [n, L_b] (one padded Engine.activity call with the items' lengths) -> the same, gated when the options
+        say so; leaves self.last_activity, one dict per item (Engine.activity_of)"""
+        eng, fs = self.engine, self._model_rate("activity=")
+        if torch.is_tensor(est):
+            out, self.last_activity = eng.activity_of(est, aopts, fs)
+            return out
+        ln = [int(e.shape[-1]) for e in est]
+        ep = torch.zeros((len(est), int(est[0].shape[0]), max(ln)), device=eng.device, dtype=torch.float32)
+        for b, e in enumerate(est):
+            ep[b, :, :ln[b]] = e
+        out, self.last_activity = eng.activity_of(ep, aopts, fs, lens=ln)
+        return list(est) if out is ep else [out[b, :, :ln[b]] for b in range(len(est))]
+
     # ------------------------------------------------------------------ loudness (the `loudness` keyword)
     def _loudness_refusals(self, lopts, channels, latent=False, intermediate=None):
         """What the `loudness` keyword refuses, before any device work"""
@@ -620,7 +654,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
                  return_info=False, stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None,
-                 track=None, **kwargs):
+                 track=None, activity=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -694,7 +728,15 @@ class LatentDiffSep:
         `context` of it and interpolated between the blocks' centres, so the filter follows a speaker who moves.
         Blocks of fixed length; not a trained step.  Refused without beamform=, with spatial= (the cACGMM sums its
         statistics inside its solve workgroup; cutting those per block is a separate piece of work), with stems=, with
-        latent=True and with intermediate."""
+        latent=True and with intermediate.
+        activity (default None: the call is what it was): None, True (segments only), "gate" or a dict of
+        native.ACTIVITY_DEFAULTS' keys (native.activity_options; seconds, Hz and dB, not tuned) -- Engine.activity decides
+        per source and STFT frame where a stem carries its speaker, on the final mono estimates at the model's rate:
+        after samples / combine, refine and beamform (with or without spatial / track) and before the resampling back,
+        loudness and limit.  What is returned is what was returned, with gate=True after Engine.activity_gate (the
+        stretches outside a stem's segments become digital silence); self.last_activity holds per item the segments
+        per source in samples at the model's rate and in seconds, the active seconds, frames_on and the options.  A
+        decision rule, not a trained detector.  Refused with stems=, latent=True and with intermediate."""
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and (latent or kwargs.get("intermediate")):
             self._dereverb_refusals(dopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
@@ -708,6 +750,9 @@ class LatentDiffSep:
         if bopts is not None:
             chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 else []
             self._beamform_refusals(bopts, chans, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
+        aopts = native.activity_options(activity)
+        if aopts is not None:
+            self._activity_refusals(aopts, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
             chans = [int(mix.shape[1])] if torch.is_tensor(mix) and mix.dim() == 3 and bopts is None else [1]
@@ -716,7 +761,7 @@ class LatentDiffSep:
             inner = bool(return_info) and samples is not None
             est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
                                          combine=combine, return_info=inner, stems=stems, beamform=beamform,
-                                         dereverb=dereverb, spatial=spatial, track=track, **kwargs)
+                                         dereverb=dereverb, spatial=spatial, track=track, activity=activity, **kwargs)
             B = int(est.shape[0])
             m3 = mix[:, None] if mix.dim() == 2 else mix
             if bopts is not None:
@@ -726,7 +771,7 @@ class LatentDiffSep:
             return (torch.stack(outs), *others)
         if dopts is not None:
             inner_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info, stems=stems,
-                            beamform=beamform, spatial=spatial, track=track)
+                            beamform=beamform, spatial=spatial, track=track, activity=activity)
             return self._separate_dereverb(mix, target_dim, sample_rate, dopts, inner_kw, kwargs)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -735,7 +780,7 @@ class LatentDiffSep:
             return self._separate_stems(mix, target_dim, sample_rate, sopts, mono_kw, kwargs)
         if bopts is not None:
             mono_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info)
-            return self._separate_beamform(mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts, tropts)
+            return self._separate_beamform(mix, target_dim, sample_rate, bopts, mono_kw, kwargs, spopts, tropts, aopts)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -753,7 +798,10 @@ class LatentDiffSep:
         if sample_rate is not None:
             if latent:
                 raise ValueError("sample_rate= applies to waveforms: a latent has no sample rate to convert")
-            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs, refine=refine, **ens)
+            return self._separate_at_rate(mix, sample_rate, target_dim, kwargs, refine=refine, activity=activity, **ens)
+        if aopts is not None:
+            est, *others = self.separate(mix, target_dim, refine=refine, **ens, **kwargs)
+            return (self._activity_step(est, aopts), *others)
         if opts is not None:
             est, *others = self.separate(mix, target_dim, **ens, **kwargs)
             short = int(est.shape[-1]) - int(mix.shape[-1])
@@ -785,7 +833,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
                        combine="mean", return_info=False, stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, track=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -821,7 +869,10 @@ class LatentDiffSep:
         spatial (default None: off), as in `separate`: with beamform=, one Engine.beamform_spatial call on the padded
         batch in place of Engine.beamform.
         track (default None: off), as in `separate`: with beamform=, one Engine.beamform_track call on the padded batch
-        in place of Engine.beamform; every item has its own number of blocks."""
+        in place of Engine.beamform; every item has its own number of blocks.
+        activity (default None: off), as in `separate`: one Engine.activity call (and with gate=True one
+        Engine.activity_gate call) on the padded batch with the items' lengths at the model's rate; each item gets the
+        bits it gets alone, and last_activity holds one entry per item."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
@@ -836,6 +887,9 @@ class LatentDiffSep:
             mixes = self._as_channel_clips(list(mixes), "beamform")
             self._beamform_refusals(bopts, [int(m.shape[0]) for m in mixes], stems=stems,
                                     intermediate=sampler_kwargs.get("intermediate"))
+        aopts = native.activity_options(activity)
+        if aopts is not None:
+            self._activity_refusals(aopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
             mixes = list(mixes)
@@ -847,7 +901,7 @@ class LatentDiffSep:
             est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
                                                samples=samples, combine=combine, return_info=inner, stems=stems,
                                                beamform=beamform, dereverb=dereverb, spatial=spatial, track=track,
-                                               **sampler_kwargs)
+                                               activity=activity, **sampler_kwargs)
             outs, others = self._normalise(lopts, sources, est, rates, others, return_info, inner)
             return (outs, *others)
         if dopts is not None:
@@ -857,7 +911,7 @@ class LatentDiffSep:
             return self._dereverb_of_lists(list(mixes), rates, dopts, stems is not None or bopts is not None,
                                            lambda at_fs: self.separate_batch(
                 at_fs, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
-                stems=stems, beamform=beamform, spatial=spatial, track=track, **sampler_kwargs))
+                stems=stems, beamform=beamform, spatial=spatial, track=track, activity=activity, **sampler_kwargs))
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -873,7 +927,7 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(mixes) if isinstance(rates, int) else [int(r) for r in rates]
             return self._beamform_of_lists(mixes, rates, bopts, lambda one: self.separate_batch(
                 one, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
-                **sampler_kwargs), spopts, tropts)
+                **sampler_kwargs), spopts, tropts, aopts)
         ens = {}
         if samples is not None:
             ens = dict(samples=native.check_samples(samples, combine), combine=combine, return_info=return_info)
@@ -886,8 +940,12 @@ class LatentDiffSep:
             fs = self._model_rate("sample_rates=")
             rates = [int(sample_rates)] * len(mixes) if isinstance(sample_rates, int) else [int(r) for r in sample_rates]
             at_fs = eng.to_model_rate(list(mixes), rates, fs)
-            est, *others = self.separate_batch(at_fs, target_dims, codec, refine=refine, **ens, **sampler_kwargs)
+            est, *others = self.separate_batch(at_fs, target_dims, codec, refine=refine, activity=activity, **ens,
+                                               **sampler_kwargs)
             return (eng.from_model_rate(est, rates, fs, [int(m.shape[-1]) for m in mixes]), *others)
+        if aopts is not None:
+            est, *others = self.separate_batch(mixes, target_dims, codec, refine=refine, **ens, **sampler_kwargs)
+            return (self._activity_step(est, aopts), *others)
         if opts is not None:
             est, *others = self.separate_batch(mixes, target_dims, codec, **ens, **sampler_kwargs)
             return (eng.mask_refine(list(mixes), est, **opts), *others)
@@ -924,7 +982,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
                       mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
-                      beamform=None, dereverb=None, spatial=None, track=None, **sampler_kwargs):
+                      beamform=None, dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -955,7 +1013,9 @@ class LatentDiffSep:
         spatial (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's channels
         are beamformed whole by Engine.beamform_spatial.
         track (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's channels are
-        beamformed whole by Engine.beamform_track -- a filter per block of the recording, not one for all of it."""
+        beamformed whole by Engine.beamform_track -- a filter per block of the recording, not one for all of it.
+        activity (default None: off), as in `separate`: decided over every whole recording after the stitch, refine and
+        the beamforming step, at the model's rate."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
@@ -970,6 +1030,9 @@ class LatentDiffSep:
             bclips = self._as_channel_clips([mixes] if torch.is_tensor(mixes) else list(mixes), "beamform")
             self._beamform_refusals(bopts, [int(m.shape[0]) for m in bclips], stems=stems,
                                     intermediate=sampler_kwargs.get("intermediate"))
+        aopts = native.activity_options(activity)
+        if aopts is not None:
+            self._activity_refusals(aopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         lopts = native.level_options(loudness, limit)
         if lopts is not None:
             single = torch.is_tensor(mixes)
@@ -982,7 +1045,7 @@ class LatentDiffSep:
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
                                               return_info=return_info, mode=mode, sample_rates=sample_rates,
                                               refine=refine, stems=stems, beamform=beamform, dereverb=dereverb,
-                                              spatial=spatial, track=track, **sampler_kwargs)
+                                              spatial=spatial, track=track, activity=activity, **sampler_kwargs)
             outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
                                            bool(return_info))
             return (outs[0] if single else outs, *others)
@@ -995,7 +1058,8 @@ class LatentDiffSep:
             out, *others = self._dereverb_of_lists(clips, rates, dopts, stems is not None or bopts is not None,
                                                    lambda at_fs: self.separate_long(
                 at_fs, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
-                refine=refine, stems=stems, beamform=beamform, spatial=spatial, track=track, **sampler_kwargs))
+                refine=refine, stems=stems, beamform=beamform, spatial=spatial, track=track, activity=activity,
+                **sampler_kwargs))
             return (out[0] if single else out, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -1016,7 +1080,7 @@ class LatentDiffSep:
                 rates = [int(rates)] * len(bclips) if isinstance(rates, int) else [int(r) for r in rates]
             out, *others = self._beamform_of_lists(bclips, rates, bopts, lambda one: self.separate_long(
                 one, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
-                refine=refine, **sampler_kwargs), spopts, tropts)
+                refine=refine, **sampler_kwargs), spopts, tropts, aopts)
             return (out[0] if single else out, *others)
         opts = native.refine_options(refine)
         if sample_rates is not None:
@@ -1027,9 +1091,15 @@ class LatentDiffSep:
             at_fs = eng.to_model_rate(clips, rates, fs)
             est, *others = self.separate_long(at_fs[0] if single else at_fs, window, overlap=overlap, fade=fade,
                                               align=align, batch=batch, return_info=return_info, mode=mode,
-                                              refine=refine, **sampler_kwargs)
+                                              refine=refine, activity=activity, **sampler_kwargs)
             back = eng.from_model_rate([est] if single else est, rates, fs, [int(m.shape[-1]) for m in clips])
             return (back[0] if single else back, *others)
+        if aopts is not None:
+            single = torch.is_tensor(mixes)
+            est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
+                                              return_info=return_info, mode=mode, refine=refine, **sampler_kwargs)
+            out = self._activity_step([est] if single else list(est), aopts)
+            return (out[0] if single else out, *others)
         if opts is not None:
             single = torch.is_tensor(mixes)
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
@@ -1080,7 +1150,7 @@ class LatentDiffSep:
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
                        samples=None, combine="mean", stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, track=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -1136,14 +1206,20 @@ class LatentDiffSep:
         any device work without beamform=, with its postfilter "mask" and with stems=.
         track (default None: off, the files are the bytes they were), as in `separate`: with beamform=, every file's
         channels are beamformed by Engine.beamform_track.  Each dict gains "track" (the options).  Refused before any
-        device work without beamform=, with spatial= and with stems=."""
+        device work without beamform=, with spatial= and with stems=.
+        activity (default None: off), as in `separate`: per batch Engine.activity on the final mono estimates at the
+        model's rate (after refine and the beamforming step, before rescale, the resampling back and loudness), with
+        gate=True Engine.activity_gate; every record gains "activity" (segments in seconds and active seconds per
+        source) and every input an `out_dir/{stem}.rttm`, one "SPEAKER {stem} 1 {onset:.3f} {duration:.3f} <NA> <NA>
+        s{i} <NA> <NA>" line per segment sorted by onset, then source (empty when nobody is active).  Refused with
+        stems=."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
                                     loudness=loudness, limit=limit, beamform=beamform, dereverb=dereverb,
-                                    spatial=spatial, track=track, **sampler_kwargs)
+                                    spatial=spatial, track=track, activity=activity, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

@@ -46,6 +46,7 @@ EXPORTS = [
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
+    "dsn_activity", "dsn_activity_gate",
 ]
 
 
@@ -1415,6 +1416,195 @@ def limiter_best(history, target) -> int:
 _lib = None
 
 
+# seconds, Hz and dB at this layer; NOT tuned (sanity figures on synthetic bursts only, README "Speaker activity")
+ACTIVITY_DEFAULTS = dict(gate=False, n_fft=512, hop=128, band=(100.0, 4000.0), smooth=0.04, range_db=40.0,
+                         dominance_db=6.0, hysteresis_db=3.0, min_on=0.1, min_off=0.1, pad=0.0, fade_ms=5.0)
+ACTIVITY_MAX_FRAMES = 1 << 22                                                      # ACTIVITY_MAX_FRAMES
+ACTIVITY_MAX_HALF_WIDTH = 1024                                                     # ACTIVITY_MAX_HALF_WIDTH
+ACTIVITY_MAX_FADE = 4096                                                           # ACTIVITY_MAX_FADE
+ACTIVITY_MIN_HOP, ACTIVITY_MAX_HOP = 8, 65536                                       # ACTIVITY_MIN_HOP, ACTIVITY_MAX_HOP
+
+
+def _number(who, key, v, lo=None) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+        raise ValueError(f"{who}: {key} = {v!r} is not a finite number")
+    if lo is not None and v < lo:
+        raise ValueError(f"{who}: {key} = {v!r} < {lo}")
+    return float(v)
+
+
+def _check_activity_options(opts) -> None:
+    if not isinstance(opts["gate"], bool):
+        raise ValueError(f"activity: gate = {opts['gate']!r} is not True or False")
+    for key in ("n_fft", "hop"):
+        if isinstance(opts[key], bool) or not isinstance(opts[key], int):
+            raise ValueError(f"activity: {key} = {opts[key]!r} is not an integer")
+    band = opts["band"]
+    if isinstance(band, (str, bytes)) or not hasattr(band, "__len__") or len(band) != 2:
+        raise ValueError(f"activity: band = {band!r} is not a pair (low, high) in Hz")
+    lo, hi = _number("activity", "band[0]", band[0], 0.0), _number("activity", "band[1]", band[1], 0.0)
+    if hi < lo:
+        raise ValueError(f"activity: band = ({lo}, {hi}) Hz: the high edge is below the low edge")
+    opts["band"] = (lo, hi)
+    for key in ("smooth", "range_db", "dominance_db", "hysteresis_db", "pad", "fade_ms"):
+        opts[key] = _number("activity", key, opts[key], 0.0)
+    for key in ("min_on", "min_off"):
+        opts[key] = _number("activity", key, opts[key], 0.0)
+        if opts[key] <= 0.0:
+            raise ValueError(f"activity: {key} = {opts[key]!r} s is not positive")
+
+
+def activity_options(spec) -> Optional[dict]:
+    """The `activity` keyword of the separation entry points: None (off, the default) -> None; True ->
+    ACTIVITY_DEFAULTS (segments only); "gate" -> the defaults with gate=True (the inactive stretches of every stem
+    become digital silence); a dict of ACTIVITY_DEFAULTS' keys -> the defaults with those replaced: band a pair of
+    Hz, smooth / min_on / min_off / pad seconds, range_db / dominance_db / hysteresis_db dB >= 0, fade_ms
+    milliseconds.  Anything else, False included, is refused by name."""
+    opts = _options("activity", spec, ACTIVITY_DEFAULTS, "None, True, 'gate'",
+                    lambda v: {} if v is True else dict(gate=True) if isinstance(v, str) and v == "gate" else None,
+                    _check_activity_options)
+    if opts is not None and "band" in opts:
+        opts["band"] = tuple(opts["band"])
+    return opts
+
+
+def activity_frames(opts, fs: int) -> dict:
+    """The seconds of activity_options at rate fs and the options' hop as Engine.activity's frame counts and
+    Engine.activity_gate's fade: a duration is max(1, int(sec fs / hop + 0.5)) frames (pad may be 0), half_width =
+    int(smooth fs / hop + 0.5) // 2, fade = int(fade_ms fs / 1000 + 0.5) samples."""
+    fs, hop = int(fs), int(opts["hop"])
+
+    def frames(sec, least=1):
+        return max(least, int(float(sec) * fs / hop + 0.5))
+
+    return dict(min_on=frames(opts["min_on"]), min_off=frames(opts["min_off"]), pad=frames(opts["pad"], 0),
+                half_width=int(float(opts["smooth"]) * fs / hop + 0.5) // 2,
+                fade=int(float(opts["fade_ms"]) * fs / 1000.0 + 0.5))
+
+
+def activity_keywords(opts, fs: int) -> dict:
+    """activity_options at rate fs -> the keywords of Engine.activity (the gate's hop and fade are
+    activity_frames')"""
+    fr = activity_frames(opts, fs)
+    return dict(fs=int(fs), n_fft=opts["n_fft"], hop=opts["hop"], band=opts["band"], half_width=fr["half_width"],
+                range_db=opts["range_db"], dominance_db=opts["dominance_db"], hysteresis_db=opts["hysteresis_db"],
+                min_on=fr["min_on"], min_off=fr["min_off"], pad=fr["pad"])
+
+
+def activity_band(band, fs, n_fft: int) -> tuple:
+    """A band in Hz as bins of an n_fft-point STFT at rate fs: j_lo = ceil(f_lo n_fft / fs), j_hi = min(n_fft / 2,
+    floor(f_hi n_fft / fs)); an empty band is refused by name."""
+    lo, hi = float(band[0]), float(band[1])
+    j_lo, j_hi = int(math.ceil(lo * n_fft / fs)), min(n_fft // 2, int(math.floor(hi * n_fft / fs)))
+    if j_lo > j_hi:
+        raise ValueError(f"activity: the band ({lo}, {hi}) Hz holds no bin of an n_fft = {n_fft} transform at {fs} Hz "
+                         f"(bins {j_lo} .. {j_hi})")
+    return j_lo, j_hi
+
+
+def activity_constants(range_db, dominance_db, hysteresis_db) -> tuple:
+    """(c_r, c_d, c_r', c_d'): 10^(-dB / 10) of the range, the dominance and each with the hysteresis added, as the
+    doubles the device multiplies with"""
+    r, d, h = float(range_db), float(dominance_db), float(hysteresis_db)
+    return 10.0 ** (-r / 10.0), 10.0 ** (-d / 10.0), 10.0 ** (-(r + h) / 10.0), 10.0 ** (-(d + h) / 10.0)
+
+
+def activity_ramp(fade: int):
+    """The gate's fade: ramp[d - 1] = float32(0.5 + 0.5 cos(pi d / (fade + 1))), d = 1 .. fade, formed in float64 and
+    rounded once -> float32 [fade] (empty for the hard gate)."""
+    import numpy as np
+
+    fade = int(fade)
+    if not 0 <= fade <= ACTIVITY_MAX_FADE:
+        raise ValueError(f"activity_gate: fade = {fade} samples outside [0, {ACTIVITY_MAX_FADE}]")
+    d = np.arange(1, fade + 1, dtype=np.float64)
+    return (0.5 + 0.5 * np.cos(np.pi * d / (fade + 1))).astype(np.float32)
+
+
+def activity_segments(act_row, F: int, hop: int, L: int) -> list:
+    """The runs of set frames among act_row[:F] as sample segments [(start, end), ..]: frame t owns the samples
+    [t hop - hop / 2, (t + 1) hop - hop / 2) of [0, L), so a run [s, e) is [max(0, s hop - hop / 2), min(L, e hop -
+    hop / 2)); runs that own no sample of the item are dropped."""
+    import numpy as np
+
+    a = np.asarray(act_row).reshape(-1)[:int(F)] != 0
+    edges = np.flatnonzero(np.diff(np.concatenate([[False], a, [False]]).astype(np.int8)))
+    h2 = int(hop) // 2
+    segs = []
+    for s, e in zip(edges[0::2].tolist(), edges[1::2].tolist()):
+        lo, hi = max(0, s * hop - h2), min(int(L), e * hop - h2)
+        if hi > lo:
+            segs.append((lo, hi))
+    return segs
+
+
+def activity_rttm(stem: str, segments, fs: int) -> list:
+    """The RTTM lines of one recording: segments[i] = [(start, end), ..] in samples at rate fs of source i -> one
+    "SPEAKER {stem} 1 {onset:.3f} {duration:.3f} <NA> <NA> s{i} <NA> <NA>" per segment, sorted by onset, then source"""
+    rows = sorted((s, i, e) for i, row in enumerate(segments) for s, e in row)
+    return [f"SPEAKER {stem} 1 {s / fs:.3f} {(e - s) / fs:.3f} <NA> <NA> s{i} <NA> <NA>" for s, i, e in rows]
+
+
+def check_activity(est_shape, lens=None, fs=16000, n_fft=512, hop=128, band=(100.0, 4000.0), half_width=2,
+                   range_db=40.0, dominance_db=6.0, hysteresis_db=3.0, min_on=13, min_off=13, pad=0) -> tuple:
+    """The refusals of dsn_activity (include/ditsep_hip.h), raised by name before the library is touched: est that is
+    not [B, n, L]; n outside [1, 4]; what check_mask_refine refuses of n_fft, hop and lens; fs that is not a positive
+    integer; a band that holds no bin; half_width outside [0, 1024]; range_db, dominance_db or hysteresis_db that is
+    not a finite number >= 0; min_on or min_off < 1 frame; pad < 0; more than 2^22 frames per item.
+    -> ((B, n, L), lens as a list or None, n_fft, hop, (j_lo, j_hi), the four factors, Fmax)"""
+    who = "activity"
+    est_shape = tuple(int(v) for v in est_shape)
+    if len(est_shape) != 3:
+        raise ValueError(f"{who}: est must be [B, n, L] (got {est_shape})")
+    B, n, L = est_shape
+    n_fft, hop, _, _ = _check_stft(who, B, n, n_fft, hop, 2, 1.0)
+    ln = _check_item_lens(who, lens, B, L, n_fft)
+    if isinstance(fs, bool) or int(fs) != fs or int(fs) < 1:
+        raise ValueError(f"{who}: fs = {fs!r} is not a positive integer")
+    if isinstance(band, (str, bytes)) or not hasattr(band, "__len__") or len(band) != 2:
+        raise ValueError(f"{who}: band = {band!r} is not a pair (low, high) in Hz")
+    bins = activity_band((_number(who, "band[0]", band[0], 0.0), _number(who, "band[1]", band[1], 0.0)), int(fs), n_fft)
+    for key, v in (("half_width", half_width), ("min_on", min_on), ("min_off", min_off), ("pad", pad)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{who}: {key} = {v!r} is not an integer number of frames")
+    if not 0 <= int(half_width) <= ACTIVITY_MAX_HALF_WIDTH:
+        raise ValueError(f"{who}: half_width = {half_width} outside [0, {ACTIVITY_MAX_HALF_WIDTH}]")
+    for key, v in (("range_db", range_db), ("dominance_db", dominance_db), ("hysteresis_db", hysteresis_db)):
+        _number(who, key, v, 0.0)
+    if int(min_on) < 1 or int(min_off) < 1:
+        raise ValueError(f"{who}: min_on = {min_on} or min_off = {min_off} < 1 frame")
+    if int(pad) < 0:
+        raise ValueError(f"{who}: pad = {pad} < 0")
+    Fmax = 1 + -(-L // hop)
+    if Fmax > ACTIVITY_MAX_FRAMES:
+        raise ValueError(f"{who}: {Fmax} frames (L = {L}, hop = {hop}) > 2^22 per item")
+    return (B, n, L), ln, n_fft, hop, bins, activity_constants(range_db, dominance_db, hysteresis_db), Fmax
+
+
+def check_activity_gate(x_shape, act_shape, lens=None, hop=128, fade=80) -> tuple:
+    """The refusals of dsn_activity_gate, raised by name before the library is touched: x that is not [B, n, L] with n
+    in [1, 4]; act that is not [B, n, Fa] with Fa >= the frames L needs; hop outside [8, 65536]; fade outside
+    [0, 4096]; lens that is not one sample count in [1, L] per item.  -> ((B, n, L), Fa, lens as a list or None)"""
+    who = "activity_gate"
+    x_shape, act_shape = tuple(int(v) for v in x_shape), tuple(int(v) for v in act_shape)
+    if len(x_shape) != 3 or x_shape[2] < 1:
+        raise ValueError(f"{who}: x must be [B, n, L] (got {x_shape})")
+    B, n, L = x_shape
+    if B < 1:
+        raise ValueError(f"{who}: B = {B} < 1")
+    if n < 1 or n > MASK_REFINE_MAX_SRC:
+        raise ValueError(f"{who}: n = {n} outside [1, {MASK_REFINE_MAX_SRC}]")
+    if isinstance(hop, bool) or int(hop) != hop or not ACTIVITY_MIN_HOP <= int(hop) <= ACTIVITY_MAX_HOP:
+        raise ValueError(f"{who}: hop = {hop!r} outside [{ACTIVITY_MIN_HOP}, {ACTIVITY_MAX_HOP}]")
+    if isinstance(fade, bool) or int(fade) != fade or not 0 <= int(fade) <= ACTIVITY_MAX_FADE:
+        raise ValueError(f"{who}: fade = {fade!r} samples outside [0, {ACTIVITY_MAX_FADE}]")
+    need = (L - 1 + int(hop) // 2) // int(hop) + 1
+    if len(act_shape) != 3 or act_shape[:2] != (B, n) or act_shape[2] < need:
+        raise ValueError(f"{who}: act must be [B, n, F] with x's B and n and F >= {need} frames (L = {L}, hop = {hop}; "
+                         f"got {act_shape})")
+    return (B, n, L), act_shape[2], check_lens(lens, B, L) if lens is not None else None
+
+
 def load_library() -> C.CDLL:
     """dlopen the in-tree HIP library; loud failure when it has not been built."""
     global _lib
@@ -1525,6 +1715,10 @@ def load_library() -> C.CDLL:
     lib.dsn_limiter_curve.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, i32p, ci, fp, cf, C.c_double, vp, vp, f64p,
                                       vp]
     lib.dsn_apply_curve.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, i32p, ci, fp, vp, vp, vp]
+    cd = C.c_double
+    lib.dsn_activity.argtypes = [vp, vp, ci, ci, ci, i32p, ci, ci, ci, ci, ci, cd, cd, cd, cd, ci, ci, ci, vp, vp, vp, vp,
+                                 vp]
+    lib.dsn_activity_gate.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, ci, ci, fp, vp, vp]
     lib.dsn_debug_read.argtypes = [vp, C.c_char_p, vp, C.c_int64]
     lib.dsn_bench_igemm.argtypes = [vp] + [ci] * 10 + [C.POINTER(C.c_double)]
     for name in EXPORTS:
@@ -2840,6 +3034,72 @@ class Engine:
                                              None if ch is None else i32(*ch), i32(*grp), G, (C.c_float * G)(*pg),
                                              _ptr(curve), _ptr(out), self._stream()), "dsn_apply_curve")
         return out
+
+    # ------------------------------------------------------------------ speaker activity of separated stems
+    def activity(self, est, lens=None, fs=16000, n_fft=512, hop=128, band=(100.0, 4000.0), half_width=2, range_db=40.0,
+                 dominance_db=6.0, hysteresis_db=3.0, min_on=13, min_off=13, pad=0) -> dict:
+        """Where every stem carries its speaker (dsn_activity, csrc/activity.hip; the definition is in
+        include/ditsep_hip.h and tests/activity_restatement.py): est [B, n <= 4, L] separated estimates -> per item,
+        source and STFT frame (mask_refine's frames, F = 1 + ceil(L / hop)) a decision from the band energy
+        (`band` in Hz at rate fs) smoothed over 2 half_width + 1 frames: on where the level is within range_db of the
+        item's peak and within dominance_db of the loudest stem of the frame, kept while it stays within
+        hysteresis_db more of both; then gaps shorter than min_off frames between two runs are filled, runs shorter
+        than min_on frames cleared and every run padded by `pad` frames.  Durations are in frames here
+        (activity_frames converts seconds).  lens: a ragged batch padded to L, nothing past lens[b] is read.
+        -> dict(act [B, n, Fmax] uint8, frames_on [B, n] int32, energy and level [B, n, Fmax] float64 -- on the
+        device --, frames [B] the items' frame counts).  A decision rule, not a trained detector; the defaults are not
+        tuned.  native.activity_segments turns a row of act into sample segments.  Two calls give identical bits."""
+        (B, n, L), ln, n_fft, hop, (j_lo, j_hi), cs, Fmax = check_activity(
+            tuple(est.shape), lens, fs, n_fft, hop, band, half_width, range_db, dominance_db, hysteresis_db, min_on,
+            min_off, pad)
+        est = _dev32(est, self.device)
+        act = torch.empty((B, n, Fmax), device=self.device, dtype=torch.uint8)
+        frames_on = torch.empty((B, n), device=self.device, dtype=torch.int32)
+        energy = torch.empty((B, n, Fmax), device=self.device, dtype=torch.float64)
+        level = torch.empty((B, n, Fmax), device=self.device, dtype=torch.float64)
+        self._check(self.lib.dsn_activity(self.ctx, _ptr(est), B, n, L, _i32(ln), n_fft, hop, j_lo, j_hi, int(half_width),
+                                          cs[0], cs[1], cs[2], cs[3], int(min_on), int(min_off), int(pad), _ptr(act),
+                                          _ptr(frames_on), _ptr(energy), _ptr(level), self._stream()), "dsn_activity")
+        return dict(act=act, frames_on=frames_on, energy=energy, level=level,
+                    frames=[1 + -(-v // hop) for v in (ln if ln is not None else [L] * B)])
+
+    def activity_gate(self, x, act, lens=None, hop=128, fade=80):
+        """The stems with their inactive stretches made digital silence (dsn_activity_gate): x [B, n, L], act
+        [B, n, F] (Engine.activity's) -> [B, n, L].  Sample m lies in a segment iff act[(m + hop / 2) // hop] is set:
+        there the output is x bit for bit; at distance d <= fade samples from the nearest segment sample of its row it
+        is activity_ramp(fade)[d - 1] x (a raised-cosine fade, one float32 product), further away +0 whatever x holds,
+        and +0 at or past lens[b], where nothing is read.  fade = 0 is a hard gate."""
+        (B, n, L), Fa, ln = check_activity_gate(tuple(x.shape), tuple(act.shape), lens, hop, fade)
+        x = _dev32(x, self.device)
+        if not torch.is_tensor(act) or act.dtype != torch.uint8:
+            raise ValueError("activity_gate: act must be a uint8 tensor [B, n, F] (Engine.activity's act)")
+        act = act.to(self.device).contiguous()
+        ramp = activity_ramp(int(fade))
+        out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
+        table = (C.c_float * max(1, len(ramp)))(*ramp.tolist())
+        self._check(self.lib.dsn_activity_gate(self.ctx, _ptr(x), _ptr(act), B, n, L, Fa, _i32(ln), int(hop), int(fade),
+                                               table if len(ramp) else None, _ptr(out), self._stream()),
+                    "dsn_activity_gate")
+        return out
+
+    def activity_of(self, est, opts, fs: int, lens=None) -> tuple:
+        """The `activity` keyword on final mono estimates at rate fs: est [B, n, L] (lens: the items' own lengths),
+        opts native.activity_options' dict -> (est, gated when opts["gate"] is set; per item a dict of "segments" (per
+        source [(start, end), ..] in samples at fs), "seconds" (the same in seconds), "active" (seconds per source),
+        "frames_on" and "options")."""
+        kw, fr = activity_keywords(opts, fs), activity_frames(opts, fs)
+        res = self.activity(est, lens=lens, **kw)
+        out = self.activity_gate(est, res["act"], lens=lens, hop=kw["hop"], fade=fr["fade"]) if opts["gate"] else est
+        act, on = res["act"].cpu().numpy(), res["frames_on"].cpu().tolist()
+        B, n, L = (int(v) for v in est.shape)
+        items = []
+        for b in range(B):
+            Lb = L if lens is None else int(lens[b])
+            segs = [activity_segments(act[b, i], res["frames"][b], kw["hop"], Lb) for i in range(n)]
+            items.append(dict(segments=segs, seconds=[[(s / fs, e / fs) for s, e in row] for row in segs],
+                              active=[sum(e - s for s, e in row) / fs for row in segs], frames_on=on[b],
+                              options=dict(opts)))
+        return out, items
 
     def _limit_groups(self, xs, rt, ln, ch, grp, prog, g_lo, i_src, target, ceiling, lim):
         """The `limit` keyword's loop for the groups the ceiling held back: xs [R, C, L] the rows before any gain, grp

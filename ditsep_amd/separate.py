@@ -116,6 +116,27 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Blocks each side of a block whose statistics enter its filter")
     p.add_argument("--track-hold", action="store_true",
                    help="Hold a block's filter over the whole block (no interpolation between the blocks' centres)")
+    p.add_argument("--activity", action="store_true",
+                   help="Decide where every stem carries its speaker (a level floor and a dominance test between the "
+                        "stems, with hysteresis and minimum durations) and write the segments to OUT/{name}.rttm (a "
+                        "decision rule, not a trained detector; not tuned; off by default)")
+    p.add_argument("--activity-gate", action="store_true",
+                   help="--activity, and the stretches of a stem outside its segments become digital silence")
+    p.add_argument("--activity-range", type=float, default=40.0, metavar="DB",
+                   help="A frame is active within this many dB of the recording's loudest frame")
+    p.add_argument("--activity-dominance", type=float, default=6.0, metavar="DB",
+                   help=".. and within this many dB of the loudest stem of the same frame")
+    p.add_argument("--activity-hysteresis", type=float, default=3.0, metavar="DB",
+                   help="An active stem stays active this many dB below both thresholds")
+    p.add_argument("--activity-min-on", type=float, default=0.1, metavar="SECONDS", help="Shorter segments are dropped")
+    p.add_argument("--activity-min-off", type=float, default=0.1, metavar="SECONDS",
+                   help="Shorter gaps between two segments are closed")
+    p.add_argument("--activity-pad", type=float, default=0.0, metavar="SECONDS", help="Every segment grows by this at both ends")
+    p.add_argument("--activity-smooth", type=float, default=0.04, metavar="SECONDS", help="Length of the level's box window")
+    p.add_argument("--activity-band", type=float, nargs=2, default=(100.0, 4000.0), metavar=("LO", "HI"),
+                   help="The band of the level in Hz")
+    p.add_argument("--activity-fade", type=float, default=5.0, metavar="MS",
+                   help="With --activity-gate: raised-cosine fade at the segments' edges in milliseconds (0: hard gate)")
     p.add_argument("--dereverb", action="store_true",
                    help="Dereverberate every recording first (weighted prediction error on up to 8 channels, kept for "
                         "the steps that use them; not a trained step; off by default)")
@@ -207,6 +228,17 @@ def track_of(args):
     return dict(block=args.track_block, context=args.track_context, interpolate=not args.track_hold)
 
 
+def activity_of(args):
+    """The `activity` keyword of separate_files from the parsed flags: None unless --activity or --activity-gate is
+    given."""
+    if not (args.activity or args.activity_gate):
+        return None
+    return dict(gate=bool(args.activity_gate), band=tuple(args.activity_band), smooth=args.activity_smooth,
+                range_db=args.activity_range, dominance_db=args.activity_dominance,
+                hysteresis_db=args.activity_hysteresis, min_on=args.activity_min_on, min_off=args.activity_min_off,
+                pad=args.activity_pad, fade_ms=args.activity_fade)
+
+
 def dereverb_of(args):
     """The `dereverb` keyword of separate_files from the parsed flags: None unless --dereverb is given."""
     if not args.dereverb:
@@ -260,7 +292,7 @@ def main(argv=None) -> int:
                                            refine=refine_of(args), samples=args.samples, combine=args.combine,
                                            stems=stems_of(args), beamform=beamform_of(args),
                                            dereverb=dereverb_of(args), spatial=spatial_of(args), track=track_of(args),
-                                           loudness=loudness_of(args), limit=limit_of(args),
+                                           loudness=loudness_of(args), limit=limit_of(args), activity=activity_of(args),
                                            denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)

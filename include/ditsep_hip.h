@@ -1012,6 +1012,57 @@ int dsn_limiter_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, cons
 int dsn_apply_curve(dsn_ctx* ctx, const float* x, int R, int C, int Lmax, const int32_t* lens, const int32_t* channels,
                     const int32_t* group, int G, const float* pregain, const float* curve, float* out, void* stream);
 
+/* Speaker activity of separated stems: per item, source and STFT frame the decision "this stem carries its speaker
+ * here", and a gate that makes the other stretches digital silence (csrc/activity.hip, restated in float64 in
+ * tests/activity_restatement.py).  A decision rule on separated estimates -- a level floor relative to the recording
+ * plus a dominance test between the stems, with hysteresis and minimum durations --, not a trained voice-activity
+ * detector, and nothing calls it unless asked to.  Per item, with L = lens[b] and estimates s_i [L] (i < n):
+ *   frames     dsn_mask_refine's (above): periodic Hann, centred, reflected at the item's own end, F = 1 + ceil(L / hop)
+ *              frames, fp32 spectra S_i(j, t) with the bits they have there
+ *   energy     E_i(t) = sum_{j = j_lo .. j_hi} (re^2 + im^2), every term and the sum in fp64 from the fp32 spectrum, in
+ *              increasing j.  The caller turns a band in Hz into bins: j_lo = ceil(f_lo n_fft / fs), j_hi =
+ *              min(n_fft / 2, floor(f_hi n_fft / fs)).
+ *   level      lev_i(t) = (sum_{u = max(0, t - h)}^{min(F - 1, t + h)} E_i(u)) / count, in increasing u, one division
+ *              (h = half_width)
+ *   peak, top  P = max_{i,t} lev_i(t), top(t) = max_i lev_i(t).  A NaN compares false everywhere: its frame is inactive
+ *              and P and top pass it over.  P = 0 makes the item inactive throughout.
+ *   on, stay   on_i(t) = lev >= P c_r and lev >= top(t) c_d; stay_i(t) the same with c_r_stay, c_d_stay.  The caller
+ *              passes the four factors as doubles (c_r = 10^(-range_db / 10), c_d = 10^(-dominance_db / 10), the stay
+ *              factors with hysteresis_db added to both); the device multiplies and compares, contraction off.
+ *   hysteresis a_i(t) = on_i(t) or (a_i(t - 1) and stay_i(t)), a_i(-1) = 0
+ *   run rules  in this order: an off-run between two on-runs that is shorter than min_off frames becomes on (the
+ *              stretches before the first and after the last on-run never do); an on-run shorter than min_on frames is
+ *              cleared; every remaining run [s, e) becomes [max(0, s - pad), min(F, e + pad)) and runs that touch merge.
+ * act [B][n][Fmax] bytes (device, Fmax = 1 + ceil(Lmax / hop)) is the result, 0 for the frames an item does not have;
+ * frames_on [B][n] int32 (device) its sum per row; energy and level [B][n][Fmax] fp64 (device) are E and lev, 0 for the
+ * frames an item does not have.  Frame t owns the samples [t hop - hop / 2, (t + 1) hop - hop / 2) of [0, L): a run
+ * [s, e) is the sample segment [max(0, s hop - hop / 2), min(L, e hop - hop / 2)).  The device writes no segment table.
+ * Two launches: the band energies (workgroup per group of frames and item), then everything else with one workgroup
+ * per item: hysteresis and the run rules are chunked scans over the workgroup, so no thread walks more than
+ * ceil(F / 256) frames.  No floating-point atomics: an item has the same bits alone, at any batch position, under any
+ * padding (nothing at or past lens[b] is read; it may hold NaN), from a base pointer of any 4-byte alignment and in a
+ * second call.  Uploads lens and synchronises the stream when lens is given: not for capture.
+ * DSN_EINVAL by name, before anything is allocated or launched: a null pointer; B outside [1, 65535]; n outside [1, 4];
+ * what dsn_mask_refine refuses of n_fft, hop, Lmax and lens; a band that is empty or outside [0, n_fft / 2]; half_width
+ * outside [0, 1024]; a factor outside [0, 1] or a stay factor above its on factor; min_on or min_off < 1; pad < 0; more
+ * than 2^22 frames per item.
+ *
+ * dsn_activity_gate: x [B][n][Lmax] -> out [B][n][Lmax] with act [B][n][Fa] bytes.  Sample m < L of a row lies in a
+ * segment iff act[(m + hop / 2) / hop] is set; there out = x bit for bit (NaN and -0 included).  Elsewhere d >= 1 is the
+ * distance in samples to the nearest sample inside a segment of the same row: out = +0 for d > fade whatever x holds,
+ * else ramp[d - 1] x, one fp32 multiply.  ramp [fade] (HOST) is float(0.5 + 0.5 cos(pi d / (fade + 1))), d = 1 .. fade,
+ * formed by the caller in fp64 and rounded once: the device evaluates no cosine.  Where two ramps overlap the nearer
+ * segment rules; fade = 0 is a hard gate.  Samples at or past lens[b] are written +0 and nothing there is read.  out may
+ * be x itself.  Uploads its tables and synchronises the stream: not for capture.
+ * DSN_EINVAL by name: a null pointer; B, n as above; Lmax outside [1, 2^30]; hop outside [8, 65536]; fade outside
+ * [0, 4096]; a ramp value outside [0, 1]; lens[b] outside [1, Lmax]; Fa smaller than the frames Lmax needs; out
+ * overlapping x without being x. */
+int dsn_activity(dsn_ctx* ctx, const float* est, int B, int n, int Lmax, const int32_t* lens, int n_fft, int hop, int j_lo,
+                 int j_hi, int half_width, double c_r, double c_d, double c_r_stay, double c_d_stay, int min_on,
+                 int min_off, int pad, uint8_t* act, int32_t* frames_on, double* energy, double* level, void* stream);
+int dsn_activity_gate(dsn_ctx* ctx, const float* x, const uint8_t* act, int B, int n, int Lmax, int Fa,
+                      const int32_t* lens, int hop, int fade, const float* ramp, float* out, void* stream);
+
 /* The pair tables behind the generator objective of the reference's src/ldm.py (LDM.losses_gen, forward value only):
  * the multi-resolution STFT loss of stable_audio_tools/training/losses/auraloss.py (MultiResolutionSTFTLoss, optionally
  * A-weighted) and the L1 / MSE waveform losses of training/losses/losses.py, each wrapped in PITLoss there (restated in
