@@ -19,11 +19,13 @@
 //            is) and solves column `lane` of Z = A^-1 N_i; the diagonal of Z goes through LDS, tau is added in channel
 //            order by the lane of the reference channel, which writes w = Z[:, ref] / tau.  The launch also runs alone
 //            on given statistics of `classes` >= n classes (launch_beamform_solve; spatial.hip's noise class): all
-//            classes enter Q_i, the first n get a filter.
+//            classes enter Q_i, the first n get a filter.  This is Souden's filter, DSN_BEAMFORM_DESIGN_SOUDEN; for the
+//            other designs launch_beamform_solve launches beamform_design.hip's kernel in its place.
 //   apply    workgroup (span, item, source), the mask kernel's layout: transforms the C_b channels (and the n
 //            estimates only where the post-filter needs the masks), contracts the channels with w in fp64 in channel
 //            order, rounds once, writes Y_i over channel 0's slot, inverse-transforms that slot and overlap-adds.
 // No atomics; nothing depends on the batch position, the padding or the chunking, so an item has the same bits alone.
+#include "../../include/ditsep_hip.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -102,56 +104,9 @@ __global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __r
   const int T2 = 2 * bf_tri(C);
   const double* Nb = N + (long)b * classes * T2 * bins + j;   // entry u of class s: Nb[(s T2 + u) bins]
 
-  // A = Q_i + lambda I: the lower triangle, row after row; a[r (r + 1) / 2 + c] = A[r][c] = conj(Q[c][r]), c <= r
+  // A = Q_i + lambda I and its Cholesky factor (bf_factor, beamform_dev.h): a[r (r + 1) / 2 + c] = L[r][c], c <= r
   double ar[BF_TRI], ai[BF_TRI];
-#pragma unroll
-  for (int r = 0; r < BF_MAX_CH; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) {
-      const int p = r * (r + 1) / 2 + c;
-      ar[p] = ai[p] = 0.0;
-      if (r < Cb) {
-        const long at = 2L * bf_idx(C, c, r) * bins;
-        for (int s = 0; s < classes; ++s)
-          if (s != i) {
-            ar[p] += Nb[(long)s * T2 * bins + at];
-            ai[p] -= Nb[(long)s * T2 * bins + at + bins];
-          }
-      }
-    }
-  double tr = 0.0;
-#pragma unroll
-  for (int c = 0; c < BF_MAX_CH; ++c)
-    if (c < Cb) tr += ar[c * (c + 1) / 2 + c];
-  const double lam = reg * (tr / (double)Cb) + eps;
-#pragma unroll
-  for (int c = 0; c < BF_MAX_CH; ++c) {
-    const int p = c * (c + 1) / 2 + c;
-    ar[p] = c < Cb ? ar[p] + lam : 1.0;
-    ai[p] = 0.0;
-  }
-  // Cholesky A = L L^H in place, column after column; the diagonal holds L[c][c], real
-#pragma unroll
-  for (int c = 0; c < BF_MAX_CH; ++c) {
-    const int pc = c * (c + 1) / 2;
-    double d = ar[pc + c];
-#pragma unroll
-    for (int k = 0; k < c; ++k) d -= ar[pc + k] * ar[pc + k] + ai[pc + k] * ai[pc + k];
-    const double l = sqrt(d);
-    ar[pc + c] = l;
-#pragma unroll
-    for (int r = c + 1; r < BF_MAX_CH; ++r) {
-      const int pr = r * (r + 1) / 2;
-      double sr = ar[pr + c], si = ai[pr + c];
-#pragma unroll
-      for (int k = 0; k < c; ++k) {   // L[r][k] conj L[c][k]
-        sr -= ar[pr + k] * ar[pc + k] + ai[pr + k] * ai[pc + k];
-        si -= ai[pr + k] * ar[pc + k] - ar[pr + k] * ai[pc + k];
-      }
-      ar[pr + c] = sr / l;
-      ai[pr + c] = si / l;
-    }
-  }
+  bf_factor(Nb, i, classes, C, Cb, bins, reg, eps, ar, ai);
   // column `lane` of N_i: N[r][lane] = upper(r, lane) for r <= lane, conj upper(lane, r) below
   double zr[BF_MAX_CH], zi[BF_MAX_CH];
 #pragma unroll
@@ -165,28 +120,8 @@ __global__ __launch_bounds__(MRT) void beamform_weights_kernel(const double* __r
     }
   }
   // L y = b, then L^H z = y
-#pragma unroll
-  for (int r = 0; r < BF_MAX_CH; ++r) {
-    const int pr = r * (r + 1) / 2;
-#pragma unroll
-    for (int k = 0; k < r; ++k) {
-      zr[r] -= ar[pr + k] * zr[k] - ai[pr + k] * zi[k];
-      zi[r] -= ar[pr + k] * zi[k] + ai[pr + k] * zr[k];
-    }
-    zr[r] = zr[r] / ar[pr + r];
-    zi[r] = zi[r] / ar[pr + r];
-  }
-#pragma unroll
-  for (int r = BF_MAX_CH - 1; r >= 0; --r) {
-#pragma unroll
-    for (int k = r + 1; k < BF_MAX_CH; ++k) {   // conj(L[k][r]) z[k]
-      const int pk = k * (k + 1) / 2;
-      zr[r] -= ar[pk + r] * zr[k] + ai[pk + r] * zi[k];
-      zi[r] -= ar[pk + r] * zi[k] - ai[pk + r] * zr[k];
-    }
-    zr[r] = zr[r] / ar[r * (r + 1) / 2 + r];
-    zi[r] = zi[r] / ar[r * (r + 1) / 2 + r];
-  }
+  bf_forward(ar, ai, zr, zi);
+  bf_backward(ar, ai, zr, zi);
   double own = 0.0;
 #pragma unroll
   for (int r = 0; r < BF_MAX_CH; ++r)
@@ -275,6 +210,7 @@ struct BfArgs {
   float* out;
   int items, post;
   double reg, eps;
+  int design, sweeps;
 };
 
 template <int NFFT>
@@ -288,7 +224,7 @@ void bf_run(int stage, const MaskRefineShape& q, const BfArgs& a, hipStream_t st
     const long rows = (long)a.items * q.n * T2 * bins;
     hipLaunchKernelGGL(beamform_reduce_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, a.part,
                        a.lens, a.chans, a.items, q.n, q.C, q.Lmax, bins, q.hop, SPAN / q.hop, OW, a.N);
-    launch_beamform_solve(a.N, a.chans, a.ref, a.w, a.items, q.C, q.n, q.n, NFFT, a.reg, a.eps, st);
+    launch_beamform_solve(a.N, a.chans, a.ref, a.w, a.items, q.C, q.n, q.n, bins, a.reg, a.eps, a.design, a.sweeps, st);
     return;
   }
   const int slots = q.C + (a.post ? q.n : 0);
@@ -314,18 +250,22 @@ size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n) {
 }
 
 void launch_beamform_solve(const double* N, const int* chans, int ref, double* w, int items, int C, int n, int classes,
-                           int nfft, double reg, double eps, hipStream_t st) {
-  const long systems = (long)items * n * (nfft / 2 + 1);
+                           int bins, double reg, double eps, int design, int sweeps, hipStream_t st) {
+  if (design != DSN_BEAMFORM_DESIGN_SOUDEN) {
+    launch_beamform_design(N, chans, ref, w, items, C, n, classes, bins, reg, eps, design, sweeps, st);
+    return;
+  }
+  const long systems = (long)items * n * bins;
   hipLaunchKernelGGL(beamform_weights_kernel, dim3((unsigned)((systems + BF_GROUPS - 1) / BF_GROUPS)), dim3(MRT), 0, st,
-                     N, chans, ref, items, n, classes, C, nfft / 2 + 1, reg, eps, w);
+                     N, chans, ref, items, n, classes, C, bins, reg, eps, w);
 }
 
 void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,
                              double* part, double* N, double* w, int items, int C, int n, int Lmax, int nfft, int hop,
-                             int power, float eps, float reg, hipStream_t st) {
+                             int power, float eps, float reg, int design, int sweeps, hipStream_t st) {
   const MaskRefineShape q{n, Lmax, hop, power, eps, 0, C, reg};
-  bf_dispatch(nfft, 0, q, BfArgs{mix, est, lens, chans, ref, part, N, w, nullptr, items, 0, (double)reg, (double)eps},
-              st);
+  bf_dispatch(nfft, 0, q, BfArgs{mix, est, lens, chans, ref, part, N, w, nullptr, items, 0, (double)reg, (double)eps,
+                                 design, sweeps}, st);
 }
 
 void launch_beamform_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
@@ -333,5 +273,5 @@ void launch_beamform_apply(const float* mix, const float* est, const int* lens, 
                            int post, hipStream_t st) {
   const MaskRefineShape q{n, Lmax, hop, power, eps, ((uintptr_t)out & 15) == 0 && Lmax % 4 == 0 ? 1 : 0, C, 0.f};
   bf_dispatch(nfft, 1, q, BfArgs{mix, est, lens, chans, 0, nullptr, nullptr, const_cast<double*>(w), out, items,
-                                 post, 0.0, (double)eps}, st);
+                                 post, 0.0, (double)eps, 0, 0}, st);
 }

@@ -1,7 +1,9 @@
-// The statistics and the channel contraction of the MVDR beamformers, dsn_beamform (beamform.hip) and dsn_beamform_track
-// (beamform_track.hip): M_src X X^H summed in frame order over a range of frames by one workgroup (bf_stats_frames) and
-// Y = sum_c conj(w_c) X_c of one frame and pair of bins (bf_contract).  Both files call exactly these functions, floating
-// point contraction off, so a range of frames and a weight have the same bits in either.
+// The statistics, the loaded factorisation and the channel contraction of the MVDR beamformers, dsn_beamform
+// (beamform.hip, beamform_design.hip) and dsn_beamform_track (beamform_track.hip): M_src X X^H summed in frame order over
+// a range of frames by one workgroup (bf_stats_frames), A = Q_i + lambda I = L L^H with its two triangular solves
+// (bf_factor, bf_forward, bf_backward) and Y = sum_c conj(w_c) X_c of one frame and pair of bins (bf_contract).  The
+// files call exactly these functions, floating point contraction off, so a range of frames, a factor and a weight have
+// the same bits in each.
 // Include it inside the file's own unnamed namespace, after maskrefine_dev.h.
 #pragma once
 
@@ -119,6 +121,95 @@ __device__ __forceinline__ void bf_stats_frames(const MaskRefineShape& q, const 
           d[0] = own[u][0];
           d[H + 1] = own[u][1];
         }
+  }
+}
+
+// Source i, one bin (Nb: entry u of class s at Nb[(s T2 + u) bins]): A = Q_i + lambda I with Q_i the sum of the other
+// classes, lambda = reg tr(Q_i) / Cb + eps and an identity block for the channels >= Cb, then its Cholesky factor in
+// place.  Both weights kernels (beamform.hip, beamform_design.hip) call this, so L has the same bits in either.
+__device__ __forceinline__ void bf_factor(const double* __restrict__ Nb, int i, int classes, int C, int Cb, int bins,
+                                          double reg, double eps, double (&ar)[BF_TRI], double (&ai)[BF_TRI]) {
+  const int T2 = 2 * bf_tri(C);
+  // A: the lower triangle, row after row; a[r (r + 1) / 2 + c] = A[r][c] = conj(Q[c][r]), c <= r
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r)
+#pragma unroll
+    for (int c = 0; c <= r; ++c) {
+      const int p = r * (r + 1) / 2 + c;
+      ar[p] = ai[p] = 0.0;
+      if (r < Cb) {
+        const long at = 2L * bf_idx(C, c, r) * bins;
+        for (int s = 0; s < classes; ++s)
+          if (s != i) {
+            ar[p] += Nb[(long)s * T2 * bins + at];
+            ai[p] -= Nb[(long)s * T2 * bins + at + bins];
+          }
+      }
+    }
+  double tr = 0.0;
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c)
+    if (c < Cb) tr += ar[c * (c + 1) / 2 + c];
+  const double lam = reg * (tr / (double)Cb) + eps;
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c) {
+    const int p = c * (c + 1) / 2 + c;
+    ar[p] = c < Cb ? ar[p] + lam : 1.0;
+    ai[p] = 0.0;
+  }
+  // Cholesky A = L L^H in place, column after column; the diagonal holds L[c][c], real
+#pragma unroll
+  for (int c = 0; c < BF_MAX_CH; ++c) {
+    const int pc = c * (c + 1) / 2;
+    double d = ar[pc + c];
+#pragma unroll
+    for (int k = 0; k < c; ++k) d -= ar[pc + k] * ar[pc + k] + ai[pc + k] * ai[pc + k];
+    const double l = sqrt(d);
+    ar[pc + c] = l;
+#pragma unroll
+    for (int r = c + 1; r < BF_MAX_CH; ++r) {
+      const int pr = r * (r + 1) / 2;
+      double sr = ar[pr + c], si = ai[pr + c];
+#pragma unroll
+      for (int k = 0; k < c; ++k) {   // L[r][k] conj L[c][k]
+        sr -= ar[pr + k] * ar[pc + k] + ai[pr + k] * ai[pc + k];
+        si -= ai[pr + k] * ar[pc + k] - ar[pr + k] * ai[pc + k];
+      }
+      ar[pr + c] = sr / l;
+      ai[pr + c] = si / l;
+    }
+  }
+}
+
+// L y = z in place, z one right-hand side in registers
+__device__ __forceinline__ void bf_forward(const double (&ar)[BF_TRI], const double (&ai)[BF_TRI],
+                                           double (&zr)[BF_MAX_CH], double (&zi)[BF_MAX_CH]) {
+#pragma unroll
+  for (int r = 0; r < BF_MAX_CH; ++r) {
+    const int pr = r * (r + 1) / 2;
+#pragma unroll
+    for (int k = 0; k < r; ++k) {
+      zr[r] -= ar[pr + k] * zr[k] - ai[pr + k] * zi[k];
+      zi[r] -= ar[pr + k] * zi[k] + ai[pr + k] * zr[k];
+    }
+    zr[r] = zr[r] / ar[pr + r];
+    zi[r] = zi[r] / ar[pr + r];
+  }
+}
+
+// L^H z = y in place
+__device__ __forceinline__ void bf_backward(const double (&ar)[BF_TRI], const double (&ai)[BF_TRI],
+                                            double (&zr)[BF_MAX_CH], double (&zi)[BF_MAX_CH]) {
+#pragma unroll
+  for (int r = BF_MAX_CH - 1; r >= 0; --r) {
+#pragma unroll
+    for (int k = r + 1; k < BF_MAX_CH; ++k) {   // conj(L[k][r]) z[k]
+      const int pk = k * (k + 1) / 2;
+      zr[r] -= ar[pk + r] * zr[k] + ai[pk + r] * zi[k];
+      zi[r] -= ar[pk + r] * zi[k] - ai[pk + r] * zr[k];
+    }
+    zr[r] = zr[r] / ar[r * (r + 1) / 2 + r];
+    zi[r] = zi[r] / ar[r * (r + 1) / 2 + r];
   }
 }
 

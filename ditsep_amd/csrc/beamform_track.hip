@@ -170,7 +170,8 @@ size_t track_item_bytes(int nfft, int hop, int Lmax, int C, int n, int Tb) {
 
 void launch_track_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref, double* part,
                           double* N, double* w, int* blockch, int items, int C, int n, int Lmax, int nfft, int hop,
-                          int power, float eps, float reg, int Tb, int context, hipStream_t st) {
+                          int power, float eps, float reg, int Tb, int context, int design, int sweeps,
+                          hipStream_t st) {
   const MaskRefineShape q{n, Lmax, hop, power, eps, 0, C, reg};
   const int Kmax = track_blocks(hop, Lmax, Tb), bins = nfft / 2 + 1;
   mr_for_nfft(nfft, [&](auto NF) {
@@ -182,7 +183,7 @@ void launch_track_weights(const float* mix, const float* est, const int* lens, c
   const long rows = (long)items * Kmax * n * 2 * bf_tri(C) * bins;
   hipLaunchKernelGGL(track_context_kernel, dim3((unsigned)((rows + MRT - 1) / MRT)), dim3(MRT), 0, st, part, lens, chans,
                      items, Kmax, n, C, Lmax, bins, hop, Tb, context, N, blockch);
-  launch_beamform_solve(N, blockch, ref, w, items * Kmax, C, n, n, nfft, (double)reg, (double)eps, st);
+  launch_beamform_solve(N, blockch, ref, w, items * Kmax, C, n, n, bins, (double)reg, (double)eps, design, sweeps, st);
 }
 
 void launch_track_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,

@@ -3493,12 +3493,22 @@ int dsn_stems(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, in
   });
 }
 
+// ---- the design of the beamforming weights (beamform_design.hip): what the three _design calls and dsn_beamform_solve
+// refuse alike
+static void check_design(const char* who, int design, int sweeps) {
+  if (design != DSN_BEAMFORM_DESIGN_SOUDEN && design != DSN_BEAMFORM_DESIGN_RANK1 && design != DSN_BEAMFORM_DESIGN_GEV)
+    fail(DSN_EINVAL, "%s: design = %d is not one of 0 (DSN_BEAMFORM_DESIGN_SOUDEN), 1 (DSN_BEAMFORM_DESIGN_RANK1), 2 "
+         "(DSN_BEAMFORM_DESIGN_GEV)", who, design);
+  if (sweeps < 1 || sweeps > BEAMFORM_MAX_SWEEPS)
+    fail(DSN_EINVAL, "%s: sweeps = %d outside [1, %d]", who, sweeps, BEAMFORM_MAX_SWEEPS);
+}
+
 // ---- mask-based MVDR beamforming (beamform.hip; include/ditsep_hip.h states the definition)
-int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
-                 const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
-                 int64_t workspace_budget, float* out, double* info_w, void* stream) {
+static int beamform_call(dsn_ctx* ctx, const char* who, const float* mix, const float* est, int B, int C, int n,
+                         int Lmax, const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                         float eps, float reg, int design, int sweeps, int postfilter, int64_t workspace_budget,
+                         float* out, double* info_w, void* stream) {
   return guarded(ctx, [&] {
-    const char* who = "dsn_beamform";
     if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
     if (postfilter != DSN_BEAMFORM_POST_NONE && postfilter != DSN_BEAMFORM_POST_MASK)
       fail(DSN_EINVAL, "%s: postfilter = %d is not one of 0 (DSN_BEAMFORM_POST_NONE), 1 (DSN_BEAMFORM_POST_MASK)", who,
@@ -3510,6 +3520,7 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
     check_power(who, power);
     check_eps(who, eps);
     check_reg(who, reg);
+    check_design(who, design, sweeps);
     check_lmax(who, Lmax);
     check_items(who, B, Lmax, n_fft, lens, channels, C, &ref);
     const int ipc = items_per_chunk(who, workspace_budget, BEAMFORM_DEFAULT_BUDGET,
@@ -3532,7 +3543,7 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
         const int items = std::min(ipc, B - b0);
         launch_beamform_weights(mix + (size_t)b0 * C * Lmax, est + (size_t)b0 * n * Lmax, dlens ? dlens + b0 : nullptr,
                                 dch ? dch + b0 : nullptr, ref, part, N, w + (size_t)b0 * n * bins * C * 2, items, C, n,
-                                Lmax, n_fft, hop, power, eps, reg, st);
+                                Lmax, n_fft, hop, power, eps, reg, design, sweeps, st);
       }
       launch_beamform_apply(mix, est, dlens, dch, w, out, B, C, n, Lmax, n_fft, hop, power, eps,
                             postfilter == DSN_BEAMFORM_POST_MASK, st);
@@ -3544,13 +3555,62 @@ int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C,
   });
 }
 
-// ---- block-adaptive MVDR weights (beamform_track.hip, beamform.hip; include/ditsep_hip.h states the definition)
-int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
-                       const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
-                       float reg, int postfilter, int block_frames, int context, int interpolate,
-                       int64_t workspace_budget, float* out, double* info_w, void* stream) {
+int dsn_beamform(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax, const int32_t* lens,
+                 const int32_t* channels, int ref, int n_fft, int hop, int power, float eps, float reg, int postfilter,
+                 int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return beamform_call(ctx, "dsn_beamform", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop, power, eps, reg,
+                       DSN_BEAMFORM_DESIGN_SOUDEN, BEAMFORM_DEFAULT_SWEEPS, postfilter, workspace_budget, out, info_w,
+                       stream);
+}
+
+int dsn_beamform_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                        const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                        float reg, int design, int sweeps, int postfilter, int64_t workspace_budget, float* out,
+                        double* info_w, void* stream) {
+  return beamform_call(ctx, "dsn_beamform_design", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop, power, eps,
+                       reg, design, sweeps, postfilter, workspace_budget, out, info_w, stream);
+}
+
+// the weights launch alone on the caller's statistics (device), one chunk
+int dsn_beamform_solve(dsn_ctx* ctx, const double* N, const int32_t* channels, int ref, int items, int C, int n,
+                       int classes, int bins, float reg, float eps, int design, int sweeps, double* w, void* stream) {
   return guarded(ctx, [&] {
-    const char* who = "dsn_beamform_track";
+    const char* who = "dsn_beamform_solve";
+    if (!N || !w) fail(DSN_EINVAL, "%s: N or w is null", who);
+    if (items < 1 || items > (1 << 24)) fail(DSN_EINVAL, "%s: items = %d outside [1, 2^24]", who, items);
+    if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
+    if (n < 1 || n > MASK_REFINE_MAX_SRC) fail(DSN_EINVAL, "%s: n = %d outside [1, %d]", who, n, MASK_REFINE_MAX_SRC);
+    if (classes < n || classes > n + 1) fail(DSN_EINVAL, "%s: classes = %d is not n = %d or n + 1", who, classes, n);
+    if (bins < 1 || bins > 1025) fail(DSN_EINVAL, "%s: bins = %d outside [1, 1025]", who, bins);
+    if ((long)items * n * bins > (1L << 31))
+      fail(DSN_EINVAL, "%s: items n bins = %d x %d x %d = %ld systems, more than the 2^31 one launch takes", who, items, n,
+           bins, (long)items * n * bins);
+    check_eps(who, eps);
+    check_reg(who, reg);
+    check_design(who, design, sweeps);
+    for (int b = 0; b < items; ++b) {
+      const int cb = channels ? (int)channels[b] : C;
+      if (cb < 1 || cb > C) fail(DSN_EINVAL, "%s: channels[%d] = %d outside [1, C = %d]", who, b, cb, C);
+      if (ref < 0 || ref >= cb)
+        fail(DSN_EINVAL, "%s: ref = %d outside [0, %d): item %d has %d channels", who, ref, cb, b, cb);
+      if (!channels) break;   // (every item is the first)
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int* dch = nullptr;
+    if (channels) dch = (const int*)upload_table(ctx, "beamform_channels", channels, sizeof(int32_t) * (size_t)items, st);
+    ctx->prof_launch("beamform_solve", 8.0 * (double)items * bins * C * ((double)classes * (C + 1) + 2.0 * n), st, [&] {
+      launch_beamform_solve(N, dch, ref, w, items, C, n, classes, bins, (double)reg, (double)eps, design, sweeps, st);
+    });
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// ---- block-adaptive MVDR weights (beamform_track.hip, beamform.hip; include/ditsep_hip.h states the definition)
+static int track_call(dsn_ctx* ctx, const char* who, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                      const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                      float reg, int design, int sweeps, int postfilter, int block_frames, int context, int interpolate,
+                      int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return guarded(ctx, [&] {
     if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
     if (postfilter != DSN_BEAMFORM_POST_NONE && postfilter != DSN_BEAMFORM_POST_MASK)
       fail(DSN_EINVAL, "%s: postfilter = %d is not one of 0 (DSN_BEAMFORM_POST_NONE), 1 (DSN_BEAMFORM_POST_MASK)", who,
@@ -3567,6 +3627,7 @@ int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, 
     check_power(who, power);
     check_eps(who, eps);
     check_reg(who, reg);
+    check_design(who, design, sweeps);
     check_lmax(who, Lmax);
     check_items(who, B, Lmax, n_fft, lens, channels, C, &ref);
     const int Kmax = track_blocks(hop, Lmax, block_frames);
@@ -3596,7 +3657,7 @@ int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, 
       ctx->prof_launch("beamform_track",
                        4.0 * (double)items * Lmax * ((double)C * (n + 1) + (postfilter ? 2.0 : 1.0) * n + n), st, [&] {
         launch_track_weights(mixc, estc, lensc, chc, ref, part, N, w, blockch, items, C, n, Lmax, n_fft, hop, power, eps,
-                             reg, block_frames, context, st);
+                             reg, block_frames, context, design, sweeps, st);
         launch_track_apply(mixc, estc, lensc, chc, w, out + (size_t)b0 * n * Lmax, items, C, n, Lmax, n_fft, hop, power,
                            eps, postfilter == DSN_BEAMFORM_POST_MASK, block_frames, interpolate, st);
       });
@@ -3609,14 +3670,31 @@ int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, 
   });
 }
 
+int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                       const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                       float reg, int postfilter, int block_frames, int context, int interpolate,
+                       int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return track_call(ctx, "dsn_beamform_track", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop, power, eps,
+                    reg, DSN_BEAMFORM_DESIGN_SOUDEN, BEAMFORM_DEFAULT_SWEEPS, postfilter, block_frames, context,
+                    interpolate, workspace_budget, out, info_w, stream);
+}
+
+int dsn_beamform_track_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                              const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                              float eps, float reg, int design, int sweeps, int postfilter, int block_frames, int context,
+                              int interpolate, int64_t workspace_budget, float* out, double* info_w, void* stream) {
+  return track_call(ctx, "dsn_beamform_track_design", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop, power,
+                    eps, reg, design, sweeps, postfilter, block_frames, context, interpolate, workspace_budget, out,
+                    info_w, stream);
+}
+
 // ---- beamforming on spatially refined masks (spatial.hip, beamform.hip; include/ditsep_hip.h states the definition)
-int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
-                         const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
-                         float reg, int iterations, float noise, float floor, float mask_reg, float mask_eps,
-                         int64_t workspace_budget, float* out, double* info_w, double* info_gamma, int32_t* info_fail,
-                         void* stream) {
+static int spatial_call(dsn_ctx* ctx, const char* who, const float* mix, const float* est, int B, int C, int n,
+                        int Lmax, const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                        float eps, float reg, int design, int sweeps, int iterations, float noise, float floor,
+                        float mask_reg, float mask_eps, int64_t workspace_budget, float* out, double* info_w,
+                        double* info_gamma, int32_t* info_fail, void* stream) {
   return guarded(ctx, [&] {
-    const char* who = "dsn_beamform_spatial";
     if (!mix || !est || !out) fail(DSN_EINVAL, "%s: mix, est or out is null", who);
     if (B < 1 || B > 65535) fail(DSN_EINVAL, "%s: B = %d outside [1, 65535]", who, B);
     if (C < 1 || C > BEAMFORM_MAX_CH) fail(DSN_EINVAL, "%s: C = %d outside [1, %d]", who, C, BEAMFORM_MAX_CH);
@@ -3629,6 +3707,7 @@ int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B
     check_power(who, power);
     check_eps(who, eps);
     check_reg(who, reg);
+    check_design(who, design, sweeps);
     if (!std::isfinite(mask_reg) || mask_reg < 0.f)
       fail(DSN_EINVAL, "%s: mask_reg = %g is not a finite number >= 0", who, mask_reg);
     if (!std::isfinite(mask_eps) || !(mask_eps > 0.f))
@@ -3659,7 +3738,7 @@ int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B
                                   Lmax, n_fft, hop, power, eps, iterations, (double)noise, (double)floor,
                                   (double)mask_reg, (double)mask_eps, st);
         launch_beamform_solve((const double*)ws, dch ? dch + b0 : nullptr, ref, w + (size_t)b0 * n * bins * C * 2, items,
-                              C, n, K, n_fft, (double)reg, (double)eps, st);
+                              C, n, K, (int)bins, (double)reg, (double)eps, design, sweeps, st);
       });
       HIPCHK(hipGetLastError());
       if (info_gamma)
@@ -3680,6 +3759,26 @@ int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B
     HIPCHK(hipMemcpyAsync(info_w, w, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   });
+}
+
+int dsn_beamform_spatial(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                         const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                         float reg, int iterations, float noise, float floor, float mask_reg, float mask_eps,
+                         int64_t workspace_budget, float* out, double* info_w, double* info_gamma, int32_t* info_fail,
+                         void* stream) {
+  return spatial_call(ctx, "dsn_beamform_spatial", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop, power, eps,
+                      reg, DSN_BEAMFORM_DESIGN_SOUDEN, BEAMFORM_DEFAULT_SWEEPS, iterations, noise, floor, mask_reg,
+                      mask_eps, workspace_budget, out, info_w, info_gamma, info_fail, stream);
+}
+
+int dsn_beamform_spatial_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                                const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                                float eps, float reg, int design, int sweeps, int iterations, float noise, float floor,
+                                float mask_reg, float mask_eps, int64_t workspace_budget, float* out, double* info_w,
+                                double* info_gamma, int32_t* info_fail, void* stream) {
+  return spatial_call(ctx, "dsn_beamform_spatial_design", mix, est, B, C, n, Lmax, lens, channels, ref, n_fft, hop,
+                      power, eps, reg, design, sweeps, iterations, noise, floor, mask_reg, mask_eps, workspace_budget,
+                      out, info_w, info_gamma, info_fail, stream);
 }
 
 // ---- WPE dereverberation (dereverb.hip; include/ditsep_hip.h states the definition)

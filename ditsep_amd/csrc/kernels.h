@@ -470,15 +470,21 @@ void launch_stems(const float* mix, const float* est, const int* lens, const int
 #define BEAMFORM_MAX_CH 8
 #define BEAMFORM_MAX_OWNERS 16
 #define BEAMFORM_DEFAULT_BUDGET (512L << 20)
+#define BEAMFORM_MAX_SWEEPS 30
+#define BEAMFORM_DEFAULT_SWEEPS 10
 int beamform_owners(int nfft, int hop, int Lmax);
 size_t beamform_item_doubles(int nfft, int hop, int Lmax, int C, int n);   // part and N of one item
 void launch_beamform_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref,
                              double* part, double* N, double* w, int items, int C, int n, int Lmax, int nfft, int hop,
-                             int power, float eps, float reg, hipStream_t s);
+                             int power, float eps, float reg, int design, int sweeps, hipStream_t s);
 // the weights launch alone, on given statistics N [items][classes][C (C + 1)][bins]: the first n <= classes of the
-// classes get a filter, all of them enter the interference (dsn_beamform: classes = n)
+// classes get a filter, all of them enter the interference (dsn_beamform: classes = n).  `design`
+// (DSN_BEAMFORM_DESIGN_*) picks the launch: Souden's filter is beamform.hip's kernel, the rank-one MVDR and the GEV
+// filter are launch_beamform_design (beamform_design.hip: `sweeps` Jacobi sweeps on the whitened N_i).
 void launch_beamform_solve(const double* N, const int* chans, int ref, double* w, int items, int C, int n, int classes,
-                           int nfft, double reg, double eps, hipStream_t s);
+                           int bins, double reg, double eps, int design, int sweeps, hipStream_t s);
+void launch_beamform_design(const double* N, const int* chans, int ref, double* w, int items, int C, int n, int classes,
+                            int bins, double reg, double eps, int design, int sweeps, hipStream_t s);
 void launch_beamform_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
                            float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps,
                            int post, hipStream_t s);
@@ -500,7 +506,7 @@ int track_blocks(int hop, int Lmax, int Tb);
 size_t track_item_bytes(int nfft, int hop, int Lmax, int C, int n, int Tb);
 void launch_track_weights(const float* mix, const float* est, const int* lens, const int* chans, int ref, double* part,
                           double* N, double* w, int* blockch, int items, int C, int n, int Lmax, int nfft, int hop,
-                          int power, float eps, float reg, int Tb, int context, hipStream_t s);
+                          int power, float eps, float reg, int Tb, int context, int design, int sweeps, hipStream_t s);
 void launch_track_apply(const float* mix, const float* est, const int* lens, const int* chans, const double* w,
                         float* out, int items, int C, int n, int Lmax, int nfft, int hop, int power, float eps, int post,
                         int Tb, int interpolate, hipStream_t s);

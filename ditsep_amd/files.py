@@ -91,7 +91,7 @@ def _padded(rows, device):
 def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False, long_after=None,
                    window=None, overlap=None, long_mode="stitch", seed=None, refine=None, samples=None, combine="mean",
                    stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None, track=None,
-                   activity=None, **sampler_kwargs) -> list:
+                   activity=None, design=None, **sampler_kwargs) -> list:
     """LatentDiffSep.separate_files (see there)."""
     import torch
 
@@ -105,7 +105,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
     if stems is not None and rescale:
         raise ValueError("stems= does not go with rescale: the stems of a channel already sum to that channel of the "
                          "mixture")
-    beam = native.beamform_options(beamform)
+    des = native.design_options(design)
+    beam = native.design_beamform_keywords(native.beamform_options(beamform), des)
     spat = native.spatial_options(spatial)
     if spat is not None:
         if stems is not None:
@@ -171,7 +172,9 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 raise ValueError(f"{p}: {v} samples at the model's rate; stems= needs at least n_fft / 2 + 1 = {need}")
     if beam is not None:
         # .. and those of the beamformer: the parameters on a stand-in item, every file's channel count and length
-        need = native.check_beamform((1, 8, 2049), (1, n, 2049), None, None, **dict(beam, ref=0))[4] // 2 + 1
+        # (design= was checked by design_options and is no argument of check_beamform)
+        plain = {k: v for k, v in beam.items() if k != "design"}
+        need = native.check_beamform((1, 8, 2049), (1, n, 2049), None, None, **dict(plain, ref=0))[4] // 2 + 1
         ref = beam["ref"]
         for p, h, v in zip(paths, headers, plan["lengths"]):
             if h.channels > native.BEAMFORM_MAX_CHANNELS:
@@ -287,6 +290,8 @@ def separate_files(model, paths, out_dir, *, batch=64, codec="padded", encoding=
                 rec["spatial"] = dict(spat)
             if trk is not None:
                 rec["track"] = dict(trk)
+            if des is not None:
+                rec["design"] = dict(des)
             if dere is not None:
                 rec["dereverb"] = dict(dere)
             if decided is not None:

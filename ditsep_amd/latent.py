@@ -654,7 +654,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate(self, mix, target_dim=None, latent=False, sample_rate=None, refine=None, samples=None, combine="mean",
                  return_info=False, stems=None, loudness=None, limit=None, beamform=None, dereverb=None, spatial=None,
-                 track=None, activity=None, **kwargs):
+                 track=None, activity=None, design=None, **kwargs):
         """reference src/diffsep_latent.py:471-487.  sample_rate (default None: mix is mono at the model's rate, the
         call is what it was): the rate of `mix` [B, C, L] -- it is resampled to config.model.fs on the device and mixed
         down, separated (target_dim keeps its meaning at the model's rate), and the estimates come back at
@@ -736,11 +736,19 @@ class LatentDiffSep:
         loudness and limit.  What is returned is what was returned, with gate=True after Engine.activity_gate (the
         stretches outside a stem's segments become digital silence); self.last_activity holds per item the segments
         per source in samples at the model's rate and in seconds, the active seconds, frames_on and the options.  A
-        decision rule, not a trained detector.  Refused with stems=, latent=True and with intermediate."""
+        decision rule, not a trained detector.  Refused with stems=, latent=True and with intermediate.
+        design (default None: the call returns the bits it returned before): "rank1", "gev", "souden" or a dict of
+        kind / sweeps (native.design_options; "rank1", 10 -- not tuned) -- only together with beamform=: whichever of
+        Engine.beamform, beamform_spatial and beamform_track runs the beamforming step gets design=, in the same place
+        and on the same inputs: the rank-one MVDR filter from the principal generalised eigenvector of (N_i, Q_i +
+        lambda I), or the GEV (max-SNR) filter with blind analytic normalisation, which is not distortionless.
+        Combines with spatial=, track=, dereverb=, activity=, loudness= and limit= as beamform= does.  Refused without
+        beamform= and wherever beamform= is (stems=, latent=True, intermediate)."""
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and (latent or kwargs.get("intermediate")):
             self._dereverb_refusals(dopts, [], latent=latent, intermediate=kwargs.get("intermediate"))
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
+        bopts = native.design_beamform_keywords(bopts, native.design_options(design))
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, latent=latent, intermediate=kwargs.get("intermediate"))
         tropts = native.track_options(track)
@@ -761,7 +769,8 @@ class LatentDiffSep:
             inner = bool(return_info) and samples is not None
             est, *others = self.separate(mix, target_dim, sample_rate=sample_rate, refine=refine, samples=samples,
                                          combine=combine, return_info=inner, stems=stems, beamform=beamform,
-                                         dereverb=dereverb, spatial=spatial, track=track, activity=activity, **kwargs)
+                                         dereverb=dereverb, spatial=spatial, track=track, activity=activity,
+                                         design=design, **kwargs)
             B = int(est.shape[0])
             m3 = mix[:, None] if mix.dim() == 2 else mix
             if bopts is not None:
@@ -771,7 +780,7 @@ class LatentDiffSep:
             return (torch.stack(outs), *others)
         if dopts is not None:
             inner_kw = dict(refine=refine, samples=samples, combine=combine, return_info=return_info, stems=stems,
-                            beamform=beamform, spatial=spatial, track=track, activity=activity)
+                            beamform=beamform, spatial=spatial, track=track, activity=activity, design=design)
             return self._separate_dereverb(mix, target_dim, sample_rate, dopts, inner_kw, kwargs)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -833,7 +842,7 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_batch(self, mixes, target_dims=None, codec="grouped", sample_rates=None, refine=None, samples=None,
                        combine="mean", return_info=False, stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, activity=None, design=None, **sampler_kwargs):
         """Mixtures of different lengths in one batch (DiT score network): `mixes` is a list of [1, L_b] tensors ->
         (list of [n, target_dims[b] or L_b] estimates, *what the sampler returns besides).  Every item gets what
         `separate` gives it alone: the codec runs per group of equal latent frame count, the sampler once on the
@@ -872,12 +881,15 @@ class LatentDiffSep:
         in place of Engine.beamform; every item has its own number of blocks.
         activity (default None: off), as in `separate`: one Engine.activity call (and with gate=True one
         Engine.activity_gate call) on the padded batch with the items' lengths at the model's rate; each item gets the
-        bits it gets alone, and last_activity holds one entry per item."""
+        bits it gets alone, and last_activity holds one entry per item.
+        design (default None: off), as in `separate`: with beamform=, the one beamforming call on the padded batch gets
+        design=."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
             self._dereverb_refusals(dopts, [], intermediate=sampler_kwargs.get("intermediate"))
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
+        bopts = native.design_beamform_keywords(bopts, native.design_options(design))
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         tropts = native.track_options(track)
@@ -901,7 +913,7 @@ class LatentDiffSep:
             est, *others = self.separate_batch(mixes, target_dims, codec, sample_rates=sample_rates, refine=refine,
                                                samples=samples, combine=combine, return_info=inner, stems=stems,
                                                beamform=beamform, dereverb=dereverb, spatial=spatial, track=track,
-                                               activity=activity, **sampler_kwargs)
+                                               activity=activity, design=design, **sampler_kwargs)
             outs, others = self._normalise(lopts, sources, est, rates, others, return_info, inner)
             return (outs, *others)
         if dopts is not None:
@@ -911,7 +923,8 @@ class LatentDiffSep:
             return self._dereverb_of_lists(list(mixes), rates, dopts, stems is not None or bopts is not None,
                                            lambda at_fs: self.separate_batch(
                 at_fs, target_dims, codec, refine=refine, samples=samples, combine=combine, return_info=return_info,
-                stems=stems, beamform=beamform, spatial=spatial, track=track, activity=activity, **sampler_kwargs))
+                stems=stems, beamform=beamform, spatial=spatial, track=track, activity=activity, design=design,
+                **sampler_kwargs))
         sopts = native.stems_options(stems)
         if sopts is not None:
             self._stems_refusals(sopts, [], intermediate=sampler_kwargs.get("intermediate"))
@@ -982,7 +995,8 @@ class LatentDiffSep:
     @torch.no_grad()
     def separate_long(self, mixes, window, overlap=None, fade="hann", align=True, batch=64, return_info=False,
                       mode="stitch", sample_rates=None, refine=None, stems=None, loudness=None, limit=None,
-                      beamform=None, dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
+                      beamform=None, dereverb=None, spatial=None, track=None, activity=None, design=None,
+                      **sampler_kwargs):
         """Long recordings as batched windows (Engine.separate_long's plan and stitch): `mixes` is one [1, L] tensor
         or a list of [1, L_r] tensors -> (estimates [n, L] or a list of [n, L_r], the summed nfe).  The windows of all
         recordings are pooled and go `batch` at a time through encode -> get_pc_sampler with the configured sampler
@@ -1015,12 +1029,15 @@ class LatentDiffSep:
         track (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's channels are
         beamformed whole by Engine.beamform_track -- a filter per block of the recording, not one for all of it.
         activity (default None: off), as in `separate`: decided over every whole recording after the stitch, refine and
-        the beamforming step, at the model's rate."""
+        the beamforming step, at the model's rate.
+        design (default None: off), as in `separate_batch`, in both modes: with beamform=, every recording's beamforming
+        call gets design=."""
         eng = self.engine
         dopts = native.dereverb_options(dereverb)
         if dopts is not None and sampler_kwargs.get("intermediate"):
             self._dereverb_refusals(dopts, [], intermediate=sampler_kwargs.get("intermediate"))
         bopts, spopts = native.beamform_options(beamform), native.spatial_options(spatial)
+        bopts = native.design_beamform_keywords(bopts, native.design_options(design))
         if spopts is not None:
             self._spatial_refusals(spopts, bopts, stems=stems, intermediate=sampler_kwargs.get("intermediate"))
         tropts = native.track_options(track)
@@ -1045,7 +1062,8 @@ class LatentDiffSep:
             est, *others = self.separate_long(mixes, window, overlap=overlap, fade=fade, align=align, batch=batch,
                                               return_info=return_info, mode=mode, sample_rates=sample_rates,
                                               refine=refine, stems=stems, beamform=beamform, dereverb=dereverb,
-                                              spatial=spatial, track=track, activity=activity, **sampler_kwargs)
+                                              spatial=spatial, track=track, activity=activity, design=design,
+                                              **sampler_kwargs)
             outs, others = self._normalise(lopts, clips, [est] if single else est, rates, others, return_info,
                                            bool(return_info))
             return (outs[0] if single else outs, *others)
@@ -1059,7 +1077,7 @@ class LatentDiffSep:
                                                    lambda at_fs: self.separate_long(
                 at_fs, window, overlap=overlap, fade=fade, align=align, batch=batch, return_info=return_info, mode=mode,
                 refine=refine, stems=stems, beamform=beamform, spatial=spatial, track=track, activity=activity,
-                **sampler_kwargs))
+                design=design, **sampler_kwargs))
             return (out[0] if single else out, *others)
         sopts = native.stems_options(stems)
         if sopts is not None:
@@ -1150,7 +1168,7 @@ class LatentDiffSep:
     def separate_files(self, paths, out_dir, *, batch=64, codec="padded", encoding="s16", rescale=False,
                        long_after=None, window=None, overlap=None, long_mode="stitch", seed=None, refine=None,
                        samples=None, combine="mean", stems=None, loudness=None, limit=None, beamform=None,
-                       dereverb=None, spatial=None, track=None, activity=None, **sampler_kwargs):
+                       dereverb=None, spatial=None, track=None, activity=None, design=None, **sampler_kwargs):
         """WAV files in, one mono WAV per speaker out: `out_dir/s{i}/{stem}.wav` at each input's own rate and frame
         count (what the reference's src/inference/separate.py does one file per call; a file at another rate is
         resampled, not "skipped").  All headers are parsed first (wavio.read_header): a file that is refused, or two
@@ -1212,14 +1230,17 @@ class LatentDiffSep:
         gate=True Engine.activity_gate; every record gains "activity" (segments in seconds and active seconds per
         source) and every input an `out_dir/{stem}.rttm`, one "SPEAKER {stem} 1 {onset:.3f} {duration:.3f} <NA> <NA>
         s{i} <NA> <NA>" line per segment sorted by onset, then source (empty when nobody is active).  Refused with
-        stems=."""
+        stems=.
+        design (default None: off, the files are the bytes they were), as in `separate`: with beamform=, every file's
+        beamforming call gets design=.  Each dict gains "design" (the options).  Refused before any device work
+        without beamform=."""
         from . import files
 
         return files.separate_files(self, paths, out_dir, batch=batch, codec=codec, encoding=encoding, rescale=rescale,
                                     long_after=long_after, window=window, overlap=overlap, long_mode=long_mode,
                                     seed=seed, refine=refine, samples=samples, combine=combine, stems=stems,
                                     loudness=loudness, limit=limit, beamform=beamform, dereverb=dereverb,
-                                    spatial=spatial, track=track, activity=activity, **sampler_kwargs)
+                                    spatial=spatial, track=track, activity=activity, design=design, **sampler_kwargs)
 
     # ------------------------------------------------------------------ score-matching loss (forward only)
     @staticmethod

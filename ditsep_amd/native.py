@@ -43,6 +43,7 @@ EXPORTS = [
     "dsn_ensemble_combine",
     "dsn_stems", "dsn_pcm_encode_frames",
     "dsn_beamform", "dsn_beamform_spatial", "dsn_beamform_track", "dsn_dereverb",
+    "dsn_beamform_design", "dsn_beamform_spatial_design", "dsn_beamform_track_design", "dsn_beamform_solve",
     "dsn_score_loss_ragged", "dsn_mrstft_loss_ragged",
     "dsn_kweight_coeffs", "dsn_loudness", "dsn_apply_gain",
     "dsn_limiter_curve", "dsn_apply_curve",
@@ -1005,6 +1006,49 @@ def check_track(mix_shape, est_shape, lens=None, channels=None, ref=0, n_fft=512
             int(bool(interpolate)), kmax, budget)
 
 
+BEAMFORM_DESIGNS = {"souden": 0, "rank1": 1, "gev": 2}                               # DSN_BEAMFORM_DESIGN_*
+BEAMFORM_MAX_SWEEPS = 30
+# the rank-one MVDR filter with ten Jacobi sweeps (five reach 1e-15 of the matrix where the eigenvalues are 1e-2 apart).
+# These are not tuned.
+DESIGN_DEFAULTS = dict(kind="rank1", sweeps=10)
+
+
+def _check_design_options(opts) -> None:
+    kind, sweeps = opts["kind"], opts["sweeps"]
+    if not isinstance(kind, str) or kind not in BEAMFORM_DESIGNS:
+        raise ValueError(f"design: kind must be one of {sorted(BEAMFORM_DESIGNS)} (got {kind!r})")
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int) or not 1 <= sweeps <= BEAMFORM_MAX_SWEEPS:
+        raise ValueError(f"design: sweeps = {sweeps!r} outside [1, {BEAMFORM_MAX_SWEEPS}]")
+
+
+def design_options(design) -> Optional[dict]:
+    """The `design` keyword of the separation entry points and of Engine.beamform / beamform_spatial / beamform_track:
+    None (the default: Souden's MVDR filter through today's call) -> None; "rank1", "gev" or "souden" ->
+    DESIGN_DEFAULTS with that kind; a dict of kind / sweeps -> the defaults with those replaced.  Anything else, True,
+    False, an unknown kind or key and sweeps outside [1, 30] included, is refused by name."""
+    return _options("design", design, DESIGN_DEFAULTS, "None, 'rank1', 'gev', 'souden'",
+                    lambda v: {"kind": v} if isinstance(v, str) and v in BEAMFORM_DESIGNS else None,
+                    _check_design_options)
+
+
+def check_design(design) -> Optional[tuple]:
+    """`design` in any form design_options takes -> None (today's call) or (the DSN_BEAMFORM_DESIGN_* code, sweeps)"""
+    opts = design_options(design)
+    return None if opts is None else (BEAMFORM_DESIGNS[opts["kind"]], int(opts["sweeps"]))
+
+
+def design_beamform_keywords(beam: Optional[dict], design: Optional[dict]) -> Optional[dict]:
+    """`beam` (beamform_options) with `design` (design_options) added for whichever of Engine.beamform,
+    beamform_spatial and beamform_track runs the beamforming step -- spatial_beamform_keywords and
+    track_beamform_keywords hand the key on.  design= without beamform= is refused by name; without design= `beam`
+    comes back as it is."""
+    if design is None:
+        return beam
+    if beam is None:
+        raise ValueError("design= picks the filter of the beamformer: it needs beamform=")
+    return dict(beam, design=dict(design))
+
+
 DEREVERB_MAX_CHANNELS, DEREVERB_MAX_TAPS, DEREVERB_MAX_DELAY, DEREVERB_MAX_UNKNOWNS, DEREVERB_MAX_ITERATIONS = 8, 16, 8, 80, 8
 DEREVERB_DEFAULT_BUDGET = 512 << 20
 # the offline recipe's usual values at 16 kHz; reg and eps are not tuned beyond the sanity runs the README names
@@ -1704,6 +1748,14 @@ def load_library() -> C.CDLL:
                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, vp, f64p, f64p, i32p, vp]
     lib.dsn_beamform_track.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci, ci,
                                        ci, ci, C.c_int64, vp, f64p, vp]
+    lib.dsn_beamform_design.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float, C.c_float, ci,
+                                        ci, ci, C.c_int64, vp, f64p, vp]
+    lib.dsn_beamform_spatial_design.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float,
+                                                C.c_float, ci, ci, ci, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                C.c_int64, vp, f64p, f64p, i32p, vp]
+    lib.dsn_beamform_track_design.argtypes = [vp, vp, vp, ci, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, C.c_float,
+                                              C.c_float, ci, ci, ci, ci, ci, ci, C.c_int64, vp, f64p, vp]
+    lib.dsn_beamform_solve.argtypes = [vp, vp, i32p, ci, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, ci, vp, vp]
     lib.dsn_dereverb.argtypes = [vp, vp, ci, ci, ci, i32p, i32p, ci, ci, ci, ci, ci, C.c_float, C.c_float, C.c_int64, vp,
                                  f64p, i32p, vp]
     lib.dsn_mrstft_loss.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(DsnMrstftConfig), C.POINTER(DsnMrstftOut), vp]
@@ -2535,7 +2587,7 @@ class Engine:
 
     # ------------------------------------------------------------------ mask-based MVDR beamforming
     def beamform(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10, reg=1e-3,
-                 postfilter=None, workspace_budget=0, return_info=False):
+                 postfilter=None, workspace_budget=0, return_info=False, design=None):
         """A microphone-array recording beamformed towards every source the mono estimates describe (dsn_beamform,
         csrc/beamform.hip; the definition is in include/ditsep_hip.h and tests/beamform_restatement.py): mix
         [B, C, L] (C <= 8), est [B, n, L] -> [B, n, L], every source a linear time-invariant filter of the channels.
@@ -2549,7 +2601,14 @@ class Engine:
         chunks).  Lists (mix: [C_b, L_b] each, est: [n, L_b] each) are padded once and a list of [n, L_b] comes back.
         return_info=True: (out, {"w": complex128 [B, n, bins, C]}) on the host.  One filter per recording
         (`beamform_track` follows moving sources); not a trained step: what it does to separation quality is unmeasured.  Needs no score
-        network and no codec; two calls give identical bits."""
+        network and no codec; two calls give identical bits.
+        design (default None: the call above, to the bit): "rank1", "gev", "souden" or a dict of kind / sweeps
+        (native.design_options) -- the weights of dsn_beamform_design (csrc/beamform_design.hip;
+        tests/beamform_design_restatement.py): with A = Q + lambda I = L L^H the principal eigenpair of
+        L^-1 N_i L^-H by `sweeps` Jacobi sweeps in float64 gives the steering estimate h = L u and v = L^-H u;
+        "rank1" is the MVDR filter of the rank-one model, w = v conj(h_ref); "gev" the max-SNR filter with blind
+        analytic normalisation, w = v (conj(h_ref) / |h_ref|) |h| / sqrt(C), which is not distortionless.  Not
+        tuned; what either does to real recordings is unmeasured."""
         if isinstance(mix, (list, tuple)):
             if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
                 raise ValueError("beamform: a list of mixtures goes with a list of as many estimates and no lens or "
@@ -2562,22 +2621,59 @@ class Engine:
             mp, ep, ln, ch, cut = self._pad_items(mix, est)
             return cut(self.beamform(mp, ep, lens=ln, channels=ch, ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps,
                                      reg=reg, postfilter=postfilter, workspace_budget=workspace_budget,
-                                     return_info=return_info))
+                                     return_info=return_info, design=design))
         (B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, post, budget = check_beamform(
             tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg, postfilter,
             workspace_budget)
+        des = check_design(design)
         mix, est = _dev32(mix, self.device), _dev32(est, self.device)
         out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
         w = torch.zeros((B, n, n_fft // 2 + 1, Cn), dtype=torch.complex128) if return_info else None
-        self._check(self.lib.dsn_beamform(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref, n_fft, hop,
-                                          power, eps, reg, post, budget, _ptr(out), _host(w), self._stream()),
-                    "dsn_beamform")
+        head = (self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref, n_fft, hop, power, eps, reg)
+        tail = (post, budget, _ptr(out), _host(w), self._stream())
+        if des is None:
+            self._check(self.lib.dsn_beamform(*head, *tail), "dsn_beamform")
+        else:
+            self._check(self.lib.dsn_beamform_design(*head, *des, *tail), "dsn_beamform_design")
         return (out, {"w": w}) if return_info else out
+
+    def beamform_solve(self, N, n=None, channels=None, ref=0, reg=1e-3, eps=1e-10, design="rank1"):
+        """The weights launch of the beamformers alone, on the caller's own covariances (dsn_beamform_solve): N
+        [items, classes, C (C + 1), bins] float64 -- per class the upper triangle of a Hermitian C x C matrix row after
+        row, per entry a plane of real parts, then one of imaginary parts -- -> w [items, n, bins, C] complex128 on
+        the device.  n (default: classes) sources get a filter; with classes = n + 1 the last class is noise that only
+        enters the interference.  channels (one per item): entries of channels an item does not have are not read
+        and their weights are zero.  design as in `beamform` (None and "souden": Souden's filter)."""
+        if not torch.is_tensor(N) or N.dim() != 4 or N.dtype != torch.float64:
+            raise ValueError("beamform_solve: N must be a float64 tensor [items, classes, C (C + 1), bins]")
+        items, classes, T2, bins = (int(v) for v in N.shape)
+        Cn = int((math.isqrt(4 * T2 + 1) - 1) // 2)
+        if Cn * (Cn + 1) != T2 or Cn < 1 or Cn > BEAMFORM_MAX_CHANNELS:
+            raise ValueError(f"beamform_solve: N has {T2} planes per class, not C (C + 1) for a C in [1, "
+                             f"{BEAMFORM_MAX_CHANNELS}]")
+        n = classes if n is None else int(n)
+        if n < 1 or n > MASK_REFINE_MAX_SRC or classes not in (n, n + 1):
+            raise ValueError(f"beamform_solve: n = {n} outside [1, {MASK_REFINE_MAX_SRC}] or classes = {classes} is not "
+                             "n or n + 1")
+        if items < 1 or bins < 1 or bins > 1025:
+            raise ValueError(f"beamform_solve: items = {items} < 1 or bins = {bins} outside [1, 1025]")
+        ch = _check_channels("beamform_solve", channels, items, Cn)
+        ref = _check_ref("beamform_solve", ref, ch, Cn)
+        reg = _check_reg("beamform_solve", reg)
+        eps = float(eps)
+        if not math.isfinite(eps) or not eps > 0.0:
+            raise ValueError(f"beamform_solve: eps = {eps} is not a finite positive number")
+        des = check_design(design) or (BEAMFORM_DESIGNS["souden"], DESIGN_DEFAULTS["sweeps"])
+        N = N.to(self.device).contiguous()
+        w = torch.empty((items, n, bins, Cn), device=self.device, dtype=torch.complex128)
+        self._check(self.lib.dsn_beamform_solve(self.ctx, _ptr(N), _i32(ch), ref, items, Cn, n, classes, bins, reg, eps,
+                                                *des, _ptr(w), self._stream()), "dsn_beamform_solve")
+        return w
 
     # ------------------------------------------------------------------ beamforming on spatially refined masks
     def beamform_spatial(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
                          reg=1e-3, iterations=1, noise=0.1, floor=0.1, mask_reg=1e-3, mask_eps=1e-10, workspace_budget=0,
-                         return_info=False):
+                         return_info=False, design=None):
         """`beamform` with the masks refined by where the sources sit (dsn_beamform_spatial, csrc/spatial.hip; the
         definition is in include/ditsep_hip.h and tests/spatial_restatement.py): mix [B, C, L] (C <= 8), est
         [B, n, L] -> [B, n, L].  Per bin a complex angular central Gaussian mixture model (Ito et al. 2016) is fitted
@@ -2592,10 +2688,11 @@ class Engine:
         complex128 [B, n, bins, C], "gamma": float64 [B, K, bins, F] (K = n + 1 with noise > 0; zero in frames an item
         does not have), "fail": int32 [B, bins], 1 where a pivot failed and the bin fell back to its priors}) on the
         host.  Not trained and not tuned: what it does to separation quality is unmeasured.  Needs no score network
-        and no codec; two calls give identical bits."""
+        and no codec; two calls give identical bits.  design (default None: the call above, to the bit) as in
+        `beamform`: the weights of that design on the refined statistics (dsn_beamform_spatial_design)."""
         kw = dict(ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps, reg=reg, iterations=iterations, noise=noise,
                   floor=floor, mask_reg=mask_reg, mask_eps=mask_eps, workspace_budget=workspace_budget,
-                  return_info=return_info)
+                  return_info=return_info, design=design)
         if isinstance(mix, (list, tuple)):
             if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
                 raise ValueError("beamform_spatial: a list of mixtures goes with a list of as many estimates and no lens "
@@ -2610,22 +2707,26 @@ class Engine:
         ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, iterations, noise, floor, mask_reg, mask_eps,
          budget) = check_spatial(tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg,
                                  iterations, noise, floor, mask_reg, mask_eps, workspace_budget)
+        des = check_design(design)
         mix, est = _dev32(mix, self.device), _dev32(est, self.device)
         out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
         bins, K, Fs = n_fft // 2 + 1, n + (C.c_float(noise).value > 0), 1 + (L + hop - 1) // hop
         w = torch.zeros((B, n, bins, Cn), dtype=torch.complex128) if return_info else None
         gamma = torch.zeros((B, K, bins, Fs), dtype=torch.float64) if return_info else None
         bad = torch.zeros((B, bins), dtype=torch.int32) if return_info else None
-        self._check(self.lib.dsn_beamform_spatial(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref,
-                                                  n_fft, hop, power, eps, reg, iterations, noise, floor, mask_reg,
-                                                  mask_eps, budget, _ptr(out), _host(w), _host(gamma),
-                                                  _host(bad, C.c_int32), self._stream()), "dsn_beamform_spatial")
+        head = (self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref, n_fft, hop, power, eps, reg)
+        tail = (iterations, noise, floor, mask_reg, mask_eps, budget, _ptr(out), _host(w), _host(gamma),
+                _host(bad, C.c_int32), self._stream())
+        if des is None:
+            self._check(self.lib.dsn_beamform_spatial(*head, *tail), "dsn_beamform_spatial")
+        else:
+            self._check(self.lib.dsn_beamform_spatial_design(*head, *des, *tail), "dsn_beamform_spatial_design")
         return (out, {"w": w, "gamma": gamma, "fail": bad}) if return_info else out
 
     # ------------------------------------------------------------------ block-adaptive MVDR weights
     def beamform_track(self, mix, est, lens=None, channels=None, ref=0, n_fft=512, hop=128, power=2, eps=1e-10,
                        reg=1e-3, postfilter=None, block_frames=100, context=1, interpolate=True, workspace_budget=0,
-                       return_info=False):
+                       return_info=False, design=None):
         """`beamform` with weights that follow a moving source (dsn_beamform_track, csrc/beamform_track.hip; the
         definition is in include/ditsep_hip.h and tests/beamform_track_restatement.py): mix [B, C, L] (C <= 8), est
         [B, n, L] -> [B, n, L].  The frames are cut into blocks of `block_frames`; block k gets the MVDR filter of
@@ -2636,10 +2737,12 @@ class Engine:
         the bits it gets alone.  return_info=True: (out, {"w": complex128 [B, Kmax, n, bins, C]}) on the host, zero in
         blocks and channels an item does not have.  Blocks of fixed length, not speaker-activity segments; no
         recursive or online form; not trained and not tuned: what it does to separation quality on real recordings
-        is unmeasured.  Needs no score network and no codec; two calls give identical bits."""
+        is unmeasured.  Needs no score network and no codec; two calls give identical bits.  design (default None: the
+        call above, to the bit) as in `beamform`: every block's weights are that design's
+        (dsn_beamform_track_design)."""
         kw = dict(ref=ref, n_fft=n_fft, hop=hop, power=power, eps=eps, reg=reg, postfilter=postfilter,
                   block_frames=block_frames, context=context, interpolate=interpolate, workspace_budget=workspace_budget,
-                  return_info=return_info)
+                  return_info=return_info, design=design)
         if isinstance(mix, (list, tuple)):
             if lens is not None or channels is not None or not isinstance(est, (list, tuple)) or len(est) != len(mix):
                 raise ValueError("beamform_track: a list of mixtures goes with a list of as many estimates and no lens "
@@ -2654,12 +2757,16 @@ class Engine:
         ((B, Cn, n, L), ln, ch, ref, n_fft, hop, power, eps, reg, post, Tb, context, interp, kmax,
          budget) = check_track(tuple(mix.shape), tuple(est.shape), lens, channels, ref, n_fft, hop, power, eps, reg,
                                postfilter, block_frames, context, interpolate, workspace_budget)
+        des = check_design(design)
         mix, est = _dev32(mix, self.device), _dev32(est, self.device)
         out = torch.empty((B, n, L), device=self.device, dtype=torch.float32)
         w = torch.zeros((B, kmax, n, n_fft // 2 + 1, Cn), dtype=torch.complex128) if return_info else None
-        self._check(self.lib.dsn_beamform_track(self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref,
-                                                n_fft, hop, power, eps, reg, post, Tb, context, interp, budget,
-                                                _ptr(out), _host(w), self._stream()), "dsn_beamform_track")
+        head = (self.ctx, _ptr(mix), _ptr(est), B, Cn, n, L, _i32(ln), _i32(ch), ref, n_fft, hop, power, eps, reg)
+        tail = (post, Tb, context, interp, budget, _ptr(out), _host(w), self._stream())
+        if des is None:
+            self._check(self.lib.dsn_beamform_track(*head, *tail), "dsn_beamform_track")
+        else:
+            self._check(self.lib.dsn_beamform_track_design(*head, *des, *tail), "dsn_beamform_track_design")
         return (out, {"w": w}) if return_info else out
 
     # ------------------------------------------------------------------ WPE dereverberation

@@ -97,6 +97,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Diagonal loading of the beamformer's solve, relative to the mean interference power")
     p.add_argument("--beamform-post", default="none", choices=["none", "mask"],
                    help="Post-filter of the beamformed spectrum: the speaker's own mask, or none")
+    p.add_argument("--beamform-design", default=None, choices=["rank1", "gev"],
+                   help="With --beamform: the filter -- rank1, the MVDR filter of a rank-one steering estimate (the "
+                        "principal generalised eigenvector), or gev, the max-SNR filter with blind analytic "
+                        "normalisation, which is not distortionless (not tuned; without the flag the filter is Souden's "
+                        "MVDR, which is why 'souden' is no choice here)")
+    p.add_argument("--beamform-sweeps", type=int, default=10, metavar="N",
+                   help="Jacobi sweeps of the eigen-solver behind --beamform-design (1 .. 30); without "
+                        "--beamform-design there is no eigen-solver and the value is not used")
     p.add_argument("--spatial", action="store_true",
                    help="With --beamform: refine the masks that steer the beamformer with a spatial mixture model "
                         "(guided cACGMM) fitted to the recording's own channels (not a trained step; not tuned; off by "
@@ -213,6 +221,13 @@ def beamform_of(args):
                 postfilter=None if args.beamform_post == "none" else args.beamform_post)
 
 
+def design_of(args):
+    """The `design` keyword of separate_files from the parsed flags: None unless --beamform-design is given."""
+    if args.beamform_design is None:
+        return None
+    return dict(kind=args.beamform_design, sweeps=args.beamform_sweeps)
+
+
 def spatial_of(args):
     """The `spatial` keyword of separate_files from the parsed flags: None unless --spatial is given."""
     if not args.spatial:
@@ -293,7 +308,7 @@ def main(argv=None) -> int:
                                            stems=stems_of(args), beamform=beamform_of(args),
                                            dereverb=dereverb_of(args), spatial=spatial_of(args), track=track_of(args),
                                            loudness=loudness_of(args), limit=limit_of(args), activity=activity_of(args),
-                                           denoise=args.denoise, **kw)
+                                           design=design_of(args), denoise=args.denoise, **kw)
         except ValueError as e:
             print(f"error: {e}", file=sys.stderr)
             return 2

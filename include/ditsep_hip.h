@@ -761,6 +761,64 @@ int dsn_beamform_track(dsn_ctx* ctx, const float* mix, const float* est, int B, 
                        float reg, int postfilter, int block_frames, int context, int interpolate,
                        int64_t workspace_budget, float* out, double* info_w, void* stream);
 
+/* The design of the beamforming weights: what dsn_beamform, dsn_beamform_spatial and dsn_beamform_track do with the
+ * statistics of a bin once A is factored (csrc/beamform_design.hip, restated in float64 in
+ * tests/beamform_design_restatement.py).  Everything up to and including A = Q_i + lambda I = L L^H is dsn_beamform's: the
+ * statistics N_k, the interference Q_i over all classes j != i, the loading lambda = reg tr(Q_i) / C_b + eps, the identity
+ * block for the channels an item does not have.  Then, per (item, source, bin), in fp64:
+ *   whitening   G = L^-1 N_i L^-H by two forward solves per column (Y = L^-1 N_i, then G = L^-1 Y^H); Hermitian and
+ *               positive semidefinite; the diagonal is taken as real
+ *   eigenpair   (mu, u), the principal eigenpair of G, by a cyclic-by-row two-sided complex Jacobi iteration: `sweeps`
+ *               sweeps (1 .. 30) over the pairs (p, q), p < q, row by row.  A pair with G_pq = 0 exactly is skipped.
+ *               Otherwise theta = (G_qq - G_pp) / (2 |G_pq|), t = sign(theta) / (|theta| + sqrt(1 + theta^2)) (sign(0) = 1;
+ *               t = 1 / (2 theta) where |theta| > 1e150), c = 1 / sqrt(1 + t^2), s = t c, e = G_pq / |G_pq|,
+ *               J = [[c, s e], [-s conj(e), c]] on (p, q); G <- G J, V <- V J, then G <- J^H G (V starts as I; nothing
+ *               is set to zero by hand).  After the last sweep mu is the largest diagonal entry of G (ties: the lowest
+ *               index m) and u = V[:, m], a unit vector.
+ *   steering    v = L^-H u and h = L u = A v, the steering estimate; v^H A v = 1
+ *   weights     DSN_BEAMFORM_DESIGN_SOUDEN: dsn_beamform's solve and weights, none of the above.
+ *               DSN_BEAMFORM_DESIGN_RANK1:  w = v conj(h_ref), the MVDR filter A^-1 h / (h^H A^-1 h) conj(h_ref) of the
+ *               rank-one model N_i ~ h h^H; it does not depend on the phase of u.
+ *               DSN_BEAMFORM_DESIGN_GEV:    w = (v p) |h| / sqrt(C_b) with p = conj(h_ref) / |h_ref| (1 where |h_ref| = 0)
+ *               and |h|^2 summed over the item's channels in channel order: the max-SNR filter (Warsitz & Haeb-Umbach
+ *               2007; Heymann et al. 2016) with blind analytic normalisation on the loaded A, its phase fixed at the
+ *               reference microphone.  Not distortionless.
+ *   fallbacks   w = e_ref where a Cholesky pivot or mu is not finite and positive (silent estimates: mu = 0; a NaN
+ *               estimate); an item with C_b = 1 takes w = 1.0 exactly for every design; channels an item does not have
+ *               get zero weight.
+ * The apply step, the post-filter, dsn_beamform_track's blocks and interpolation and dsn_beamform_spatial's noise class
+ * (it enters Q_i; the first n classes get a filter) are untouched, and so are the invariants: no floating-point atomics,
+ * an item has the same bits alone, at any batch position, under any padding, under any workspace budget and in a second
+ * call.  The three _design calls take the arguments of their namesakes with `design, sweeps` after `reg`; with
+ * DSN_BEAMFORM_DESIGN_SOUDEN they are their namesakes to the bit (sweeps is still checked).  Not trained, not tuned;
+ * no eigenvalue-based rank selection, no MPDR, no LCMV; the effect on real recordings is unmeasured.
+ * DSN_EINVAL by name: what the namesake refuses; an unknown design; sweeps outside [1, 30].
+ *
+ * dsn_beamform_solve is the weights launch alone, for callers with their own covariances: N (DEVICE,
+ * [items][classes][C (C + 1)][bins] doubles: per class the upper triangle of a Hermitian C x C matrix row after row,
+ * every entry a plane of real parts followed by a plane of imaginary parts, [bins] each), classes = n or n + 1 (all
+ * classes enter Q_i, the first n get a filter), channels (HOST, [items], or NULL: C each), ref, bins in [1, 1025], reg
+ * and eps as above -> w (DEVICE, [items][n][bins][C] complex as double pairs, info_w's layout).  Entries of channels an
+ * item does not have are not read.  One launch on `stream`, nothing is synchronised unless channels is given (it is
+ * uploaded, as above).  DSN_EINVAL by name: N or w null; items outside [1, 2^24]; items n bins above 2^31; C, n,
+ * classes, bins, reg, eps, channels[b], ref, design or sweeps out of range. */
+enum { DSN_BEAMFORM_DESIGN_SOUDEN = 0, DSN_BEAMFORM_DESIGN_RANK1 = 1, DSN_BEAMFORM_DESIGN_GEV = 2 };
+int dsn_beamform_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                        const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power, float eps,
+                        float reg, int design, int sweeps, int postfilter, int64_t workspace_budget, float* out,
+                        double* info_w, void* stream);
+int dsn_beamform_spatial_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                                const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                                float eps, float reg, int design, int sweeps, int iterations, float noise, float floor,
+                                float mask_reg, float mask_eps, int64_t workspace_budget, float* out, double* info_w,
+                                double* info_gamma, int32_t* info_fail, void* stream);
+int dsn_beamform_track_design(dsn_ctx* ctx, const float* mix, const float* est, int B, int C, int n, int Lmax,
+                              const int32_t* lens, const int32_t* channels, int ref, int n_fft, int hop, int power,
+                              float eps, float reg, int design, int sweeps, int postfilter, int block_frames, int context,
+                              int interpolate, int64_t workspace_budget, float* out, double* info_w, void* stream);
+int dsn_beamform_solve(dsn_ctx* ctx, const double* N, const int32_t* channels, int ref, int items, int C, int n,
+                       int classes, int bins, float reg, float eps, int design, int sweeps, double* w, void* stream);
+
 /* Weighted prediction error (WPE) dereverberation: the channels of a reverberant recording in, the same channels with
  * the late reverberation predicted from their own delayed past and subtracted out (Nakatani et al. 2010; Yoshioka &
  * Nakatani 2012; the offline recipe; csrc/dereverb.hip, restated in float64 in tests/dereverb_restatement.py).  A
